@@ -10,7 +10,14 @@ parameters that are already resident in HBM.  The path shards by mesh with no da
 (SURVEY.md §8(e)): every rank processes its own B meshes ("weak" scaling), the timed region is
 bracketed by barrier + synchronize and the MAX over ranks is taken.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run does only what the headline needs: set up, warm up, time EXACTLY --steps steps, print the line
+(`value`, `ms_per_step` = the timed window / --steps).  `--dump-outputs DIR` then also writes what the last timed step
+returned to its caller (verts, proj, mask, seg, joints, x_grad) as DIR/<name>.npy in float32, rank 0's, at most 64 MB
+(a fixed seeded sample of the meshes when the batch is larger); the inputs are seeded, so two builds compare array by array.
+Everything else - nine more windows of --steps, the one-step-per-graph figure, the train legs, the stage breakdown,
+roofline, strict-fp32 step, aux legs, CPU baseline and parity sample - runs only with `--full`.
+
+Extra objects in the --full line:
   roofline      - the dominant kernel (raster_fwd_kernel alone, smplr_seg_raster), timed live with HIP events on
                   the launch stream; achieved = FLOPs of the pairs it evaluates (counted on the device) / mean launch
                   time, frac = achieved / fp32 vector peak (< 1); the brute-force count of SURVEY 8(d) is carried as
@@ -476,6 +483,27 @@ def parity_sample(model, consts, pt, W, dev, Bp=2):
             "seg_bar": "|d| <= 1e-3 |ref| + 1e-6", "oracle": "oracle/np_oracle.py (float64)"}
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6 - 64 * 1024      # --dump-outputs: 64 MB in all, less room for the .npy headers
+
+
+def dump_outputs(path, outs, seed=0):
+    """Write the arrays of `outs` (name -> tensor with the mesh batch as its leading axis; None / empty ones skipped) as
+    path/<name>.npy in float32.  Over DUMP_MAX_BYTES, the same fixed seeded sample of meshes is kept in every array."""
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in outs.items() if v is not None and v.numel() > 0}
+    total = sum(a.nbytes for a in arrs.values())
+    B = next(iter(arrs.values())).shape[0]
+    sample = None
+    if total > DUMP_MAX_BYTES:
+        keep = max(1, B * DUMP_MAX_BYTES // total)
+        sample = np.sort(np.random.default_rng(seed).choice(B, keep, replace=False))
+        arrs = {k: a[sample] for k, a in arrs.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return {"dir": path, "arrays": {k: list(a.shape) for k, a in arrs.items()},
+            "meshes": B if sample is None else int(len(sample)), "mesh_sample_seed": None if sample is None else seed}
+
+
 def _free_port():
     import socket
     sk = socket.socket()
@@ -699,9 +727,9 @@ def dry_run(args, rank, world):
         dist.all_gather(rows, torch.tensor([seed, mine, sums[0], work], dtype=torch.float64))
         seeds, times, sums, works = ([float(r[i]) for r in rows] for i in range(4))
     # the train leg's protocol on CPU: a stand-in regressor (the real one's IEF head on random features) under
-    # DistributedDataParallel over gloo - ddp step, no_sync step, all-reduce volume - same keys as the GPU leg
+    # DistributedDataParallel over gloo - ddp step, no_sync step, all-reduce volume - same keys as the GPU leg (--full only)
     tleg = None
-    if not args.no_train_leg:
+    if args.full and not args.no_train_leg:
         import contextlib
         from torch import nn
         torch.manual_seed(7)
@@ -767,6 +795,11 @@ def main():
                     help="graph mode: whole steps captured per graph launch (cut to a divisor of --steps)")
     ap.add_argument("--streams", type=int, default=1,
                     help="concurrent mesh chunks per step (HIP streams / parallel graph branches)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the spread windows, one-step graph, train legs, stage breakdown, roofline, "
+                         "aux legs, CPU baseline and parity sample (each --no-* below still drops its part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-breakdown", action="store_true")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
@@ -777,7 +810,7 @@ def main():
     ap.add_argument("--train-steps", type=int, default=10)
     ap.add_argument("--train-global-batch", type=int, default=1024,
                     help="train leg, world > 1: the fixed global batch of its strong-scaling point (configs[4]: 1024)")
-    ap.add_argument("--windows", type=int, default=10, help="timed windows of --steps for the min/median/max spread")
+    ap.add_argument("--windows", type=int, default=10, help="--full: timed windows of --steps for the min/median/max spread")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: run the N-rank launch / timing protocol over gloo with a CPU stand-in step")
     args = ap.parse_args()
@@ -825,12 +858,21 @@ def main():
     x = torch.tensor(make_x(B, W, 1000 + rank), device=dev)      # resident in HBM before timing
     gen = torch.Generator(device="cpu").manual_seed(rank)
     dseg = torch.randn(B, W, W, 32, generator=gen).to(dev)
+    # --dump-outputs: what the step hands its caller, kept from the step that ran last (in graph mode the last captured
+    # step's tensors, which every replay rewrites)
+    last = {}
+
+    def keep(outs, xg):
+        if args.dump_outputs:
+            last.clear()
+            last.update(zip(("verts", "proj", "mask", "seg", "silhouette", "joints", "loss"), (t.detach() for t in outs)))
+            last["x_grad"] = xg.grad
 
     def step():
         xg = x.detach().requires_grad_(True)
-        verts, proj, mask, seg, silh, jt, _ls = ops.DecoderFn.apply(xg, consts, 4, W, vs_main, pt, 64, True, False,
-                                                               args.streams)
-        seg.backward(dseg)
+        outs = ops.DecoderFn.apply(xg, consts, 4, W, vs_main, pt, 64, True, False, args.streams)
+        outs[3].backward(dseg)
+        keep(outs, xg)
         return xg.grad
 
     # `--step` other than "default" times a VARIANT of the decoder step instead (for the profile passes, which trace
@@ -866,6 +908,7 @@ def main():
                 o_[4].backward(dsl_v)
             else:
                 o_[3].backward(dseg)
+            keep(o_, xg)
             return xg.grad
 
     mode = args.mode
@@ -923,14 +966,17 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     seen = _ranks_seen(dist, rank, world, dev, backend, own_ms)
-    # the spread: further windows of the same K steps, same bracketing (the first window above is `value`)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, last)
+    # --full: the spread: further windows of the same K steps, same bracketing (the first window above is `value`)
     windows = [elapsed / args.steps * 1e3]
-    for _ in range(max(0, args.windows - 1)):
+    for _ in range(max(0, args.windows - 1) if args.full else 0):
         windows.append(_timed_steps(run, 0, nrun, dist, dev, backend, torch.cuda.synchronize) / args.steps * 1e3)
     # the same K steps with ONE step per graph launch: what a caller gets who replays the decoder's graph once per
     # training step, between two encoder steps (the headline replays `gsteps` decoder steps per launch)
     ms_graph1 = None
-    if mode == "graph" and gsteps > 1:
+    if args.full and mode == "graph" and gsteps > 1:
         try:
             g1 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g1):
@@ -942,11 +988,11 @@ def main():
             del g1
         except Exception as e:
             sys.stderr.write("bench: one-step graph failed (%s)\n" % e)
-    elif mode == "graph":
+    elif args.full and mode == "graph":
         ms_graph1 = windows[0]
     # the design's one collective: the data-parallel train step (every rank takes part)
     tleg = None
-    if not args.no_train_leg:
+    if args.full and not args.no_train_leg:
         try:
             tleg = train_leg(args, rank, world, dev, dist, backend, model, W)
         except Exception as e:              # the decoder line must still come out: the leg's failure is reported in it
@@ -955,7 +1001,7 @@ def main():
 
     # BASELINE configs[3] as written: the same train step at B = 256 on one GPU (VERDICT r04 missing #4)
     tleg256 = None
-    if not args.no_train_leg and world == 1 and int(args.train_batch) != 256:
+    if args.full and not args.no_train_leg and world == 1 and int(args.train_batch) != 256:
         try:
             tleg256 = train_leg(args, rank, world, dev, dist, backend, model, W, per=256)
         except Exception as e:
@@ -969,15 +1015,10 @@ def main():
             "metric": "meshes/sec fwd+bwd (SMPL->48x48 31-part seg)",
             "value": round(value, 1), "unit": "meshes/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "ms_per_step_windows": {"n": len(windows), "steps_each": args.steps, "min": round(min(windows), 4),
-                                    "median": round(float(np.median(windows)), 4), "max": round(max(windows), 4),
-                                    "note": "the first window is `ms_per_step` / `value`; boxes differ by +-4 %"},
+            "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
             "build_id": _lib.build_id(),
             "warmup_actual": nwarm * gsteps,
-            "ms_per_step_graph1": None if ms_graph1 is None else round(ms_graph1, 4),
             "rccl_ranks_seen": seen, "rank_ms_per_step": [d["ms_per_step"] for d in seen],
-            "train_step": tleg, "train_step_B256": tleg256,
             "config": {"workload": ("full decoder fwd+bwd (batch_smpl + projection + compute_mask + "
                                     "projects_to_seg), BASELINE configs[2]" if variant_note is None
                                     else "VARIANT --step %s (not the headline): %s" % (args.step, variant_note)),
@@ -989,7 +1030,16 @@ def main():
                                       else "fp32 MFMA"),
                        "sharding": "by mesh, no collective"},
         }
-        if not args.no_breakdown:
+        if dumped is not None:
+            line["dump_outputs"] = dumped
+        if args.full:
+            line.update({
+                "ms_per_step_windows": {"n": len(windows), "steps_each": args.steps, "min": round(min(windows), 4),
+                                        "median": round(float(np.median(windows)), 4), "max": round(max(windows), 4),
+                                        "note": "the first window is `ms_per_step` / `value`; boxes differ by +-4 %"},
+                "ms_per_step_graph1": None if ms_graph1 is None else round(ms_graph1, 4),
+                "train_step": tleg, "train_step_B256": tleg256})
+        if args.full and not args.no_breakdown:
             stages = stage_breakdown(x, consts, pt, W)
             line["stages_us"] = stages
             line["stage_rooflines"] = stage_rooflines(stages, B, W, consts.V, ops.blend_gemm_mode())
@@ -1027,7 +1077,7 @@ def main():
                                                        "uses bf16x3 (3 x 8 = 24 significant bits per operand)"}
             except Exception as e:
                 line["step_blend_gemm_f32"] = {"error": str(e)}
-        if not args.no_breakdown:
+        if args.full and not args.no_breakdown:
             # BASELINE configs[1]: batch_smpl fwd+bwd only, B=256, eager, HIP events
             x2 = torch.tensor(make_x(256, W, 7), device=dev)
             gv = torch.randn(256, consts.V, 3, device=dev)
@@ -1273,7 +1323,7 @@ def main():
                 "fwd_GBps": round(npx * 136 / (tf_ms * 1e-3) / 1e9, 1),
                 "bwd_GBps": round(npx * 264 / (tb_ms * 1e-3) / 1e9, 1), "hbm_peak_GBps": 8000,
                 "note": "latency-bound at B=128 (37.7 MB tensor); bytes = algorithmic, per SURVEY 8(f) next-2"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(model, W)
             except Exception as e:

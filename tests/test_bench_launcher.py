@@ -21,7 +21,7 @@ def _run(args, env=None, timeout=240):
 
 
 def test_gpus_2_launches_two_ranks_itself():
-    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--batch", "6", "--dry-run"])
+    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--batch", "6", "--dry-run", "--full"])
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1, lines                       # ONE line on stdout, rank 0's
@@ -51,7 +51,7 @@ def test_gpus_8_dry_run_is_the_eight_rank_protocol():
     eight ranks started by bench.py itself, per-rank seeds, MAX reduction, the strong split 1024 -> 128, every rank
     listed in `rccl_ranks_seen` with its own time, and the train leg's keys (train.py:196,205-210: 4 x num_gpus split)."""
     r = _run(["--gpus", "8", "--steps", "3", "--warmup", "1", "--scaling", "strong", "--global-batch", "1024", "--dry-run",
-              "--train-batch", "8", "--train-steps", "2"], timeout=600)
+              "--train-batch", "8", "--train-steps", "2", "--full"], timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -118,7 +118,7 @@ def test_gpus_2_on_a_one_gpu_box():
     """The real N = 2 path on hardware: `bench.py --gpus 2` starts two ranks itself, both on cuda:0 (local rank modulo
     the device count), process group over gloo (RCCL needs a device per rank): HIP graph capture, barrier-bracketed
     timing, MAX over ranks, one line with n_gpus = 2 and the whole-job rate."""
-    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-breakdown", "--train-batch", "16",
+    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-breakdown", "--train-batch", "16",
               "--train-steps", "3", "--train-global-batch", "64"],
              env={"BENCH_DIST_BACKEND": "gloo", "HSA_ENABLE_IPC_MODE_LEGACY": "0"}, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]

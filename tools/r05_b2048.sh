@@ -4,7 +4,7 @@
 #   graph-replayed step time at --batch BATCH (default 2048), all in ONE lease
 TAG=${1:-r05_b2048}; B=${2:-2048}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R; export TMPDIR=/tmp
-ARGS="--batch $B --no-cpu-baseline --no-breakdown --no-train-leg"
+ARGS="--batch $B --full --no-cpu-baseline --no-breakdown --no-train-leg"
 for i in 1 2; do timeout -k 10 200 python bench.py $ARGS --steps 30 --warmup 5 2>/dev/null | python -c "import sys,json; l=json.loads(sys.stdin.read().strip().splitlines()[-1]); w=l['ms_per_step_windows']; print('B=$B', l['value'], l['ms_per_step'], w['min'], w['median'], w['max'], l['build_id'][:12])"; done > $O/step.txt; cat $O/step.txt
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_eager -- python3 $R/bench.py $ARGS --steps 20 --warmup 5 --min-warmup 20 --mode eager > $O/rocprof_eager.log 2>&1; echo "rocprof(eager) rc=$?")
 cp $(ls $O/prof_eager/*/*_kernel_stats.csv | head -1) $O/eager_kernel_stats.csv 2>/dev/null

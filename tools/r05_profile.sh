@@ -10,17 +10,17 @@ TAG=${1:-r05}; MODE=${2:-main}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R; export TMPDIR=/tmp
 EAGER="--steps 20 --warmup 5 --mode eager --no-cpu-baseline --no-breakdown --no-train-leg"
 if [ "$MODE" = main ]; then
-  timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-200 $O/bench.json
+  timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-200 $O/bench.json
   (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_eager -- python3 $R/bench.py $EAGER > $O/rocprof_eager.log 2>&1; echo "rocprof(eager) rc=$?")
   cp $(ls $O/prof_eager/*/*_kernel_stats.csv | head -1) $O/eager_kernel_stats.csv 2>/dev/null
   # the same box's headline right after the trace: three short runs of the graph-replayed step
-  for i in 1 2 3; do timeout -k 10 200 python bench.py --steps 50 --no-cpu-baseline --no-breakdown --no-train-leg 2>/dev/null | python -c "import sys,json; l=json.loads(sys.stdin.read().strip().splitlines()[-1]); w=l['ms_per_step_windows']; print(l['ms_per_step'], w['min'], w['median'], w['max'], l['ms_per_step_graph1'], l['build_id'][:12])"; done > $O/headline_runs.txt
+  for i in 1 2 3; do timeout -k 10 200 python bench.py --steps 50 --full --no-cpu-baseline --no-breakdown --no-train-leg 2>/dev/null | python -c "import sys,json; l=json.loads(sys.stdin.read().strip().splitlines()[-1]); w=l['ms_per_step_windows']; print(l['ms_per_step'], w['min'], w['median'], w['max'], l['ms_per_step_graph1'], l['build_id'][:12])"; done > $O/headline_runs.txt
   python tools/same_box.py $O/eager_kernel_stats.csv $O/headline_runs.txt $O/bench.json > $O/same_box.txt
   # ... and the same kernels INSIDE the replayed graph (durations and the gap to the next dispatch), same box
-  (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/prof_graph -- python3 $R/bench.py --steps 50 --no-cpu-baseline --no-breakdown --no-train-leg > $O/rocprof_graph.log 2>&1; echo "rocprof(graph) rc=$?")
+  (cd "$TMPDIR" && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/prof_graph -- python3 $R/bench.py --steps 50 --full --no-cpu-baseline --no-breakdown --no-train-leg > $O/rocprof_graph.log 2>&1; echo "rocprof(graph) rc=$?")
   { echo "# the step's kernels inside the replayed HIP graph (last 2000 dispatches of a rocprofv3 --kernel-trace of the headline command, tools/graph_gaps.py):"; python tools/graph_gaps.py $O/prof_graph 2000; } >> $O/same_box.txt
   cat $O/same_box.txt
-  (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 $R/bench.py --no-cpu-baseline > $O/rocprof_default.log 2>&1; echo "rocprof(default) rc=$?")
+  (cd "$TMPDIR" && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 $R/bench.py --full --no-cpu-baseline > $O/rocprof_default.log 2>&1; echo "rocprof(default) rc=$?")
   cp $(ls $O/prof_default/*/*_kernel_stats.csv | head -1) $O/default_kernel_stats.csv 2>/dev/null
   i=0
   for SET in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU" \
@@ -31,7 +31,7 @@ if [ "$MODE" = main ]; then
   done
   python tools/pmc_summary.py $O/pmc_step_1 $O/pmc_step_2 > $O/pmc_step_sq.txt
   for b in 32 128 512 2048; do timeout -k 10 200 python bench.py --batch $b --steps 30 --warmup 5 --no-cpu-baseline --no-breakdown --no-train-leg 2>/dev/null | python -c "import sys,json; l=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('B=%d' % $b, l['value'], l['ms_per_step'])"; done > $O/batch_sweep.txt; cat $O/batch_sweep.txt
-  for V in default seg_only fused_loss unfused_loss both_heads silhouette_only; do timeout -k 10 200 python bench.py --step $V --steps 50 --no-cpu-baseline --no-breakdown --no-train-leg 2>/dev/null | python -c "import sys,json; l=json.loads(sys.stdin.read().strip().splitlines()[-1]); w=l['ms_per_step_windows']; print('$V', l['value'], l['ms_per_step'], w['min'], w['median'], w['max'])"; done > $O/step_variants.txt; cat $O/step_variants.txt
+  for V in default seg_only fused_loss unfused_loss both_heads silhouette_only; do timeout -k 10 200 python bench.py --step $V --steps 50 --full --no-cpu-baseline --no-breakdown --no-train-leg 2>/dev/null | python -c "import sys,json; l=json.loads(sys.stdin.read().strip().splitlines()[-1]); w=l['ms_per_step_windows']; print('$V', l['value'], l['ms_per_step'], w['min'], w['median'], w['max'])"; done > $O/step_variants.txt; cat $O/step_variants.txt
 fi
 if [ "$MODE" = variants ]; then
   for V in seg_only fused_loss unfused_loss both_heads silhouette_only; do
