@@ -320,6 +320,33 @@ int smplr_skin_vis_seg_fwd_ex(const float *v_posed, const float *lbs_top4, const
 int smplr_seg_loss_bwd(const float *dloss, const float *stats, const int16_t *arg, const float *rec, int B, int VP,
                        int W, int P, int K, float *dproj, void *workspace, int deterministic, void *stream);
 
+/* ---- segmentation metrics: evaluate.py:22-127, evaluate_autoencoder.py:23-117 (per-class intersection / union and
+ * correct pixels of the arg-max map) and Keras' metrics=['accuracy'] (train.py:207-215) -------------------------------
+ * All counts go into ONE confusion matrix conf (C + 1, C) uint64, ADDED to (the caller zeroes it): row = ground-truth
+ * label (row C: a label outside [0, C)), column = predicted class.  Then I_k = conf[k][k], U_k = rowsum_k + colsum_k -
+ * conf[k][k], correct = trace, total = sum (every pixel, invalid labels included).  Integer counts: the result does not
+ * depend on launch order, streams or chunking.
+ *   smplr_seg_confusion            scores (npix, C) fp32, 2 <= C <= 32, arg-max per pixel in torch.argmax's order (NaN
+ *                                  above every number, ties to the lower channel) - OR pred (npix) int32, an existing
+ *                                  prediction map (a prediction outside [0, C) is not counted); exactly one of the two.
+ *                                  labels (npix) int32 laid out as the scores (seg's rows flipped).  pred_out (npix) uint8
+ *                                  or NULL receives the arg-max.
+ *   smplr_seg_raster_ex_conf       smplr_seg_raster_ex + conf (33, 32): the loss epilogue also counts each pixel's
+ *   smplr_skin_vis_seg_fwd_ex_conf (label, arg-max of the 32 scores seg receives) - the scores still need not be written.
+ *                                  conf != NULL needs the loss epilogue (loss, labels, stats) and the default
+ *                                  rasteriser (refused under SMPLR_RASTER=1); conf = NULL is the _ex entry point. */
+int smplr_seg_confusion(const float *scores, const int32_t *pred, const int32_t *labels, long long npix, int C,
+                        uint64_t *conf, uint8_t *pred_out, void *stream);
+int smplr_seg_raster_ex_conf(int B, int W, int P, int K, const void *workspace, const float *rec,
+                             const int32_t *labels, const float *class_w, float gamma, float *seg, int16_t *arg,
+                             float *loss, float *stats, float *vmax, uint64_t *conf, void *stream);
+int smplr_skin_vis_seg_fwd_ex_conf(const float *v_posed, const float *lbs_top4, const float *A, const float *cam,
+                                   int x_stride, int B, int V, int W, int grid_wh, int ref_compat,
+                                   const int32_t *part_pos, const int32_t *part_off, int P, int K, void *workspace,
+                                   const int32_t *labels, const float *class_w, float gamma, float *verts, float *proj,
+                                   float *mask, float *seg, int16_t *arg, float *rec, int16_t *vslot, float *loss,
+                                   float *stats, float *vmax, uint64_t *conf, void *stream);
+
 /* ---- projects_to_silhouette: keras_smpl/projects_to_silhouette.py:14-44 ----------------- */
 /* silh (B,W,W,2) = [1-s, s], s = max_v exp(-|proj_v-(c,r)|/1.2) over ALL VP vertices, rows
  * flipped; arg (B,W,W) int32 = maximising vertex.  workspace: smplr_silh_workspace(B,VP,W) B.  */

@@ -73,6 +73,10 @@ SIGNATURES = {
     "smplr_skin_vis_seg_fwd_ex": (c_int, [P, P, P, P, I, I, I, I, I, I, P, P, I, I, P, P, P, c_float, P, P, P, P, P, P,
                                           P, P, P, P, P]),
     "smplr_seg_loss_bwd": (c_int, [P, P, P, P, I, I, I, I, I, P, P, I, P]),
+    "smplr_seg_confusion": (c_int, [P, P, P, c_longlong, I, P, P, P]),
+    "smplr_seg_raster_ex_conf": (c_int, [I, I, I, I, P, P, P, P, c_float, P, P, P, P, P, P, P]),
+    "smplr_skin_vis_seg_fwd_ex_conf": (c_int, [P, P, P, P, I, I, I, I, I, I, P, P, I, I, P, P, P, c_float, P, P, P, P, P,
+                                               P, P, P, P, P, P, P]),
     "smplr_silh_workspace": (c_size_t, [I, I, I]),
     "smplr_silh_fwd": (c_int, [P, I, I, I, P, P, P, P]),
     "smplr_silh_fwd_hint": (c_int, [P, P, I, I, I, P, P, P, P]),

@@ -241,4 +241,12 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// The order of torch.argmax / np.argmax on (score, channel): NaN above every number (the first NaN wins), equal scores
+// (+0 and -0 included) go to the lower channel.  A strict total order on pairs with distinct channels, so a reduction
+// over it gives the same winner in any grouping (metrics.hip, raster2_fwd_kernel's metrics epilogue).
+__device__ __forceinline__ bool argmax_beats(float v, int i, float bv, int bi) {
+  const bool n = v != v, bn = bv != bv;
+  return (n || bn) ? (n && (!bn || i < bi)) : (v > bv || (v == bv && i < bi));
+}
+
 }  // namespace smplr

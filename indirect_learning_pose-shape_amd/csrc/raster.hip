@@ -1244,11 +1244,15 @@ __device__ __forceinline__ int scan2_parts_chunk(const char *tb, int offv, int o
   return done - 1;
 }
 
-template <bool LOSS, int NG2, int PL>
+// MET (with LOSS): the metrics epilogue - each pixel's arg-max over the 32 scores seg would receive, counted by (label,
+// prediction) into conf (33, 32) uint64, the confusion matrix of metrics.hip.  The instantiations without it compile to
+// the code they had before the parameter existed (conf is never read there).
+template <bool LOSS, int NG2, int PL, bool MET = false>
 __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SGPRS void raster2_fwd_kernel(
     const float4 *__restrict__ G, const int *__restrict__ goff, const int *__restrict__ lstart,
     const uint2 *__restrict__ lrec, int P, int K, int S, int W, int B, int ntiles, float *__restrict__ seg,
-    short *__restrict__ arg, unsigned wmagic, LossOut lo) {
+    short *__restrict__ arg, unsigned wmagic, LossOut lo, unsigned long long *__restrict__ conf) {
+  static_assert(LOSS || !MET, "the metrics epilogue rides on the loss epilogue's labels");
   constexpr int NT = PL * NG2;           // threads
   constexpr int TS = 2 * PL;             // pixels of the block's tile
   constexpr int PW = PL / 64;            // waves per part range (64 pair-lanes each)
@@ -1436,6 +1440,14 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
   SMPLR_TL_STAMP(4);
   __syncthreads();
   SMPLR_TL_STAMP(5);
+  // MET: the block's (33 x 32) confusion counts live in the table's arena, which no wave reads after the barrier above
+  // (there is no room for an array of their own beside the tile: two blocks per CU)
+  constexpr int NCONF = 33 * 32;
+  static_assert(AR >= NCONF, "the confusion counts fit the arena");
+  unsigned *hist = reinterpret_cast<unsigned *>(sTab);
+  if (MET) {
+    for (int i = tid; i < NCONF; i += NT) hist[i] = 0u;
+  }
   // Merge of the local records and write-out.  raster_fwd_kernel's scheme (LDS atomic max on the score bits, ties keep
   // the earlier winner, global before local) with FOUR lanes per pixel: a lane takes every 4th record of the pixel's list,
   // then the channel chunks sub and sub + 4.  The background's sum keeps raster_fwd_kernel's tree bit for bit: chunk sums
@@ -1454,6 +1466,7 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
   };
   float den_[NIT], st_[NIT], eg_[NIT];
   unsigned po_[NIT];
+  int pred_[NIT];                                          // MET: the pixel's arg-max channel, in all 4 of its lanes
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int e = it * NT + tid;
@@ -1509,6 +1522,25 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
       aa[0] = (sum >= 0.0f && sum <= 1.0f) ? 1 : 0;        // clip pass-through gate
     }
     const int qq = qqa[it];
+    if (MET) {
+      // over exactly the values seg receives (channel 0 = the background): the lane's 8 channels in ascending order,
+      // then (value, channel) across the pixel's 4 lanes by two quad exchanges (all lanes take part)
+      float bv = va[0];
+      int bi = cA;
+#pragma unroll
+      for (int t = 1; t < 4; ++t)
+        if (argmax_beats(va[t], cA + t, bv, bi)) { bv = va[t]; bi = cA + t; }
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        if (argmax_beats(vb[t], cB + t, bv, bi)) { bv = vb[t]; bi = cB + t; }
+      const float ov1 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(bv), 0xB1, 0xF, 0xF, false));
+      const int oi1 = __builtin_amdgcn_update_dpp(0, bi, 0xB1, 0xF, 0xF, false);       // quad_perm 1,0,3,2
+      if (argmax_beats(ov1, oi1, bv, bi)) { bv = ov1; bi = oi1; }
+      const float ov2 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(bv), 0x4E, 0xF, 0xF, false));
+      const int oi2 = __builtin_amdgcn_update_dpp(0, bi, 0x4E, 0xF, 0xF, false);       // quad_perm 2,3,0,1
+      if (argmax_beats(ov2, oi2, bv, bi)) bi = oi2;
+      pred_[it] = bi;
+    }
     if (LOSS) {                                            // (C == 32: checked by the launcher; all lanes take part)
       den_[it] = quad_sum((__expf(va[0]) + __expf(va[1])) + (__expf(va[2]) + __expf(va[3]))) +
                  quad_sum((__expf(vb[0]) + __expf(vb[1])) + (__expf(vb[2]) + __expf(vb[3])));
@@ -1578,6 +1610,25 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
     if (sub < NIT && po != ~0u) {
       lo.loss[(size_t)n * npix + po] = ls;
       lo.stats[(size_t)n * npix + po] = make_float4(k1 * inv, k1 * gbu, k1, __int_as_float(t));
+    }
+  }
+  if (MET) {
+    // (label, prediction) of every pixel of the tile into the block's counts (row 32: a label outside [0, 32)), then
+    // one 64-bit atomic add per non-zero count into conf
+    __syncthreads();                                       // the counts are zeroed
+    if (sub == 0) {
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        if (qqa[it] >= 0) {
+          const int t = lab[it];
+          atomicAdd(&hist[((unsigned)t < 32u ? t : 32) * 32 + pred_[it]], 1u);
+        }
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < NCONF; i += NT) {
+      const unsigned v = hist[i];
+      if (v) atomicAdd(conf + i, (unsigned long long)v);
     }
   }
   SMPLR_TL_STAMP(6);
@@ -2982,7 +3033,8 @@ static int seg_bin_impl(const char *fn, const float *proj, float *mask, bool fus
 // returns its own duration - begin to end on the device, what rocprofv3's kernel trace reports, without the dispatch
 // gap an event pair around a launch includes.  A measurement aid for bench.py's roofline only.
 static int seg_raster_impl(const char *fn, int B, int W, int P, int K, const void *workspace, const float *rec,
-                           float *seg, int16_t *arg, void *stream, LossOut lo = LossOut{}, float *kernel_ms = nullptr) {
+                           float *seg, int16_t *arg, void *stream, LossOut lo = LossOut{}, float *kernel_ms = nullptr,
+                           uint64_t *conf = nullptr) {
   SMPLR_REQUIRE(B >= 0 && W > 0 && W <= 160 && P >= 1 && P <= 31 && K > 0 && K <= BIN_T * IPT_MAX,
                 "%s: bad sizes B=%d W=%d (max 160) P=%d (max 31) K=%d", fn, B, W, P, K);
   const bool with_loss = lo.loss != nullptr;
@@ -2991,6 +3043,7 @@ static int seg_raster_impl(const char *fn, int B, int W, int P, int K, const voi
   if (B == 0) return 0;
   SMPLR_REQUIRE(workspace && rec && (seg || with_loss) && arg, "%s: null pointer (seg may be NULL only with a loss)", fn);
   SMPLR_REQUIRE(!with_loss || (lo.labels && lo.stats), "%s: the loss epilogue needs labels and stats", fn);
+  SMPLR_REQUIRE(!conf || with_loss, "%s: the metrics epilogue (conf) needs the loss epilogue (loss, labels, stats)", fn);
   const SegWs ws = seg_ws_layout(B, W, P, K);
   const int S = seg_slots(P, K);
   const char *base = reinterpret_cast<const char *>(workspace);
@@ -2998,6 +3051,9 @@ static int seg_raster_impl(const char *fn, int B, int W, int P, int K, const voi
   // kernel's block, 0 = by batch (below), 1 = 128 pair-lanes x 8 part ranges, 2 = 64 x 10, 3 = 128 x 4
   static const int version = getenv("SMPLR_RASTER") ? atoi(getenv("SMPLR_RASTER")) : 2;
   static const int shape_env = getenv("SMPLR_RASTER_SHAPE") ? atoi(getenv("SMPLR_RASTER_SHAPE")) : 0;
+  SMPLR_REQUIRE(!conf || version != 1, "%s: the metrics epilogue (conf) exists in the default rasteriser only, not with "
+                "SMPLR_RASTER=1", fn);
+  unsigned long long *confp = reinterpret_cast<unsigned long long *>(conf);
   if (version != 1) {
     const int shape = shape_env ? shape_env : raster2_shape(B, W, K);
     const int pl = shape == 2 ? 64 : PLN;
@@ -3014,22 +3070,24 @@ static int seg_raster_impl(const char *fn, int B, int W, int P, int K, const voi
       SMPLR_HIP(hipEventCreate(&e0));
       SMPLR_HIP(hipEventCreate(&e1));
     }
-#define SMPLR_RASTER2_LAUNCH(LOSS_, NG_, PL_)                                                                       \
+#define SMPLR_RASTER2_LAUNCH(LOSS_, MET_, NG_, PL_)                                                                 \
   {                                                                                                                 \
     if (kernel_ms)                                                                                                  \
-      hipExtLaunchKernelGGL((raster2_fwd_kernel<LOSS_, NG_, PL_>), dim3(grid2), dim3(PL_ * NG_), 0, as_stream(stream), \
-                            e0, e1, 0, Gp, goffp, lsp, lrp, P, K, S, W, B, nt2, seg, argp, wm, lo);                 \
+      hipExtLaunchKernelGGL((raster2_fwd_kernel<LOSS_, NG_, PL_, MET_>), dim3(grid2), dim3(PL_ * NG_), 0,            \
+                            as_stream(stream), e0, e1, 0, Gp, goffp, lsp, lrp, P, K, S, W, B, nt2, seg, argp, wm, lo, \
+                            confp);                                                                                 \
     else                                                                                                            \
-      hipLaunchKernelGGL((raster2_fwd_kernel<LOSS_, NG_, PL_>), dim3(grid2), dim3(PL_ * NG_), 0, as_stream(stream), \
-                         Gp, goffp, lsp, lrp, P, K, S, W, B, nt2, seg, argp, wm, lo);                               \
+      hipLaunchKernelGGL((raster2_fwd_kernel<LOSS_, NG_, PL_, MET_>), dim3(grid2), dim3(PL_ * NG_), 0,               \
+                         as_stream(stream), Gp, goffp, lsp, lrp, P, K, S, W, B, nt2, seg, argp, wm, lo, confp);     \
   }
-#define SMPLR_RASTER2_SHAPES(LOSS_)                                                                                 \
+#define SMPLR_RASTER2_SHAPES(LOSS_, MET_)                                                                           \
   {                                                                                                                 \
-    if (shape == 2) SMPLR_RASTER2_LAUNCH(LOSS_, 10, 64)                                                             \
-    else if (shape == 3) SMPLR_RASTER2_LAUNCH(LOSS_, 4, 128)                                                        \
-    else SMPLR_RASTER2_LAUNCH(LOSS_, 8, 128)                                                                        \
+    if (shape == 2) SMPLR_RASTER2_LAUNCH(LOSS_, MET_, 10, 64)                                                       \
+    else if (shape == 3) SMPLR_RASTER2_LAUNCH(LOSS_, MET_, 4, 128)                                                  \
+    else SMPLR_RASTER2_LAUNCH(LOSS_, MET_, 8, 128)                                                                  \
   }
-    if (with_loss) SMPLR_RASTER2_SHAPES(true) else SMPLR_RASTER2_SHAPES(false)
+    if (conf) SMPLR_RASTER2_SHAPES(true, true) else if (with_loss) SMPLR_RASTER2_SHAPES(true, false)
+    else SMPLR_RASTER2_SHAPES(false, false)
 #undef SMPLR_RASTER2_SHAPES
 #undef SMPLR_RASTER2_LAUNCH
     SMPLR_LAUNCH_CHECK(fn);
@@ -3162,8 +3220,16 @@ int smplr_seg_raster_plan(int B, int W, int P, int K, int32_t *info, int32_t *ti
 int smplr_seg_raster_ex(int B, int W, int P, int K, const void *workspace, const float *rec, const int32_t *labels,
                         const float *class_w, float gamma, float *seg, int16_t *arg, float *loss, float *stats,
                         float *vmax, void *stream) {
+  return smplr_seg_raster_ex_conf(B, W, P, K, workspace, rec, labels, class_w, gamma, seg, arg, loss, stats, vmax,
+                                  nullptr, stream);
+}
+
+int smplr_seg_raster_ex_conf(int B, int W, int P, int K, const void *workspace, const float *rec, const int32_t *labels,
+                             const float *class_w, float gamma, float *seg, int16_t *arg, float *loss, float *stats,
+                             float *vmax, uint64_t *conf, void *stream) {
   return smplr::seg_raster_impl("smplr_seg_raster_ex", B, W, P, K, workspace, rec, seg, arg, stream,
-                                smplr::LossOut{labels, class_w, gamma, loss, reinterpret_cast<float4 *>(stats), vmax});
+                                smplr::LossOut{labels, class_w, gamma, loss, reinterpret_cast<float4 *>(stats), vmax},
+                                nullptr, conf);
 }
 
 int smplr_skin_vis_seg_fwd_ex(const float *v_posed, const float *lbs_top4, const float *A, const float *cam,
@@ -3172,14 +3238,30 @@ int smplr_skin_vis_seg_fwd_ex(const float *v_posed, const float *lbs_top4, const
                               const float *class_w, float gamma, float *verts, float *proj, float *mask, float *seg,
                               int16_t *arg, float *rec, int16_t *vslot, float *loss, float *stats, float *vmax,
                               void *stream) {
+  return smplr_skin_vis_seg_fwd_ex_conf(v_posed, lbs_top4, A, cam, x_stride, B, V, W, grid_wh, ref_compat, part_pos,
+                                        part_off, P, K, workspace, labels, class_w, gamma, verts, proj, mask, seg, arg,
+                                        rec, vslot, loss, stats, vmax, nullptr, stream);
+}
+
+int smplr_skin_vis_seg_fwd_ex_conf(const float *v_posed, const float *lbs_top4, const float *A, const float *cam,
+                                   int x_stride, int B, int V, int W, int grid_wh, int ref_compat,
+                                   const int32_t *part_pos, const int32_t *part_off, int P, int K, void *workspace,
+                                   const int32_t *labels, const float *class_w, float gamma, float *verts, float *proj,
+                                   float *mask, float *seg, int16_t *arg, float *rec, int16_t *vslot, float *loss,
+                                   float *stats, float *vmax, uint64_t *conf, void *stream) {
   using namespace smplr;
   SMPLR_REQUIRE(B <= 0 || (v_posed && lbs_top4 && A && cam), "smplr_skin_vis_seg_fwd_ex: null pointer");
+  // (before the binning launch: a refused conf must not leave half a pass behind)
+  SMPLR_REQUIRE(!conf || loss, "smplr_skin_vis_seg_fwd_ex: the metrics epilogue (conf) needs the loss epilogue");
+  SMPLR_REQUIRE(!conf || !(getenv("SMPLR_RASTER") && atoi(getenv("SMPLR_RASTER")) == 1),
+                "smplr_skin_vis_seg_fwd_ex: the metrics epilogue (conf) exists in the default rasteriser only, not with "
+                "SMPLR_RASTER=1");
   const SkinIn sk{v_posed, lbs_top4, A, cam, x_stride, verts, proj};
   int rc = seg_bin_impl("smplr_skin_vis_seg_fwd_ex", proj, mask, true, grid_wh, ref_compat, B, V, W, part_pos, part_off,
                         P, K, workspace, rec, vslot, stream, sk);
   if (rc) return rc;
   return seg_raster_impl("smplr_skin_vis_seg_fwd_ex", B, W, P, K, workspace, rec, seg, arg, stream,
-                         LossOut{labels, class_w, gamma, loss, reinterpret_cast<float4 *>(stats), vmax});
+                         LossOut{labels, class_w, gamma, loss, reinterpret_cast<float4 *>(stats), vmax}, nullptr, conf);
 }
 
 int smplr_seg_bwd_nsplit(int B, int W) {

@@ -354,6 +354,41 @@ std::vector<Tensor> decoder_fwd_meta(const Tensor &x, const std::vector<Tensor> 
           at::empty({B, 24, 3}, o)};
 }
 
+// ---- segmentation metrics (evaluate.py:22-127): conf (C + 1, C) int64 += the (label, arg-max) counts ----------------
+// scores: fp32 (..., C) raw scores, or an integer prediction map (npix entries, C = conf.size(1)); labels: int32, one per
+// pixel (as the scores lie); conf is added to, in place.
+void seg_confusion(const Tensor &scores, const Tensor &labels, Tensor &conf) {
+  dev_typed(conf, at::kLong, "conf");
+  TORCH_CHECK(conf.dim() == 2 && conf.size(1) >= 2 && conf.size(1) <= 32 && conf.size(0) == conf.size(1) + 1,
+              "conf must be (C + 1, C) int64 with 2 <= C <= 32");
+  const int64_t C = conf.size(1);
+  const bool is_scores = scores.is_floating_point();
+  if (is_scores) {
+    dev_f32(scores, "scores");
+    TORCH_CHECK(scores.dim() >= 1 && scores.size(-1) == C, "scores must be (..., C) with C = conf.size(1) = ", C);
+  } else {
+    dev_typed(scores, at::kInt, "pred");
+  }
+  const int64_t npix = is_scores ? scores.numel() / C : scores.numel();
+  dev_typed(labels, at::kInt, "labels");
+  TORCH_CHECK(labels.numel() == npix, "labels hold ", labels.numel(), " entries for ", npix, " pixels");
+  same_device(conf, {{"scores", &scores}, {"labels", &labels}});
+  DeviceGuard g(conf.device());
+  ok(smplr_seg_confusion(is_scores ? scores.data_ptr<float>() : nullptr, is_scores ? nullptr : scores.data_ptr<int32_t>(),
+                         labels.data_ptr<int32_t>(), (long long)npix, (int)C,
+                         reinterpret_cast<uint64_t *>(conf.data_ptr<int64_t>()), nullptr, cur_stream()),
+     "smplr_seg_confusion");
+}
+void seg_confusion_meta(const Tensor &scores, const Tensor &labels, Tensor &conf) {
+  TORCH_CHECK(conf.dim() == 2 && conf.size(1) >= 2 && conf.size(1) <= 32 && conf.size(0) == conf.size(1) + 1,
+              "conf must be (C + 1, C) int64 with 2 <= C <= 32");
+  TORCH_CHECK(conf.scalar_type() == at::kLong, "conf must be int64");
+  const int64_t C = conf.size(1);
+  const int64_t npix = scores.is_floating_point() ? scores.numel() / C : scores.numel();
+  TORCH_CHECK(!scores.is_floating_point() || (scores.dim() >= 1 && scores.size(-1) == C), "scores must be (..., C)");
+  TORCH_CHECK(labels.numel() == npix, "labels hold ", labels.numel(), " entries for ", npix, " pixels");
+}
+
 int64_t abi_version() { return smplr_abi_version(); }
 #ifndef SMPLR_TORCH_OPS_ID
 #define SMPLR_TORCH_OPS_ID "unknown"
@@ -379,6 +414,7 @@ TORCH_LIBRARY(smplraster, m) {
         "Tensor A, Tensor v_posed, int num_cam=4, int vertex_sampling=1) -> Tensor");
   m.def("decoder_fwd(Tensor x, Tensor[] consts, Tensor part_pos, Tensor part_off, int W, int grid_wh=64, "
         "bool ref_compat=True, int num_cam=4) -> Tensor[]");
+  m.def("seg_confusion(Tensor scores, Tensor labels, Tensor(a!) conf) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch key is named CUDA in torch)
@@ -392,6 +428,7 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("smpl_fwd", &smpl_fwd);
   m.impl("smpl_bwd", &smpl_bwd);
   m.impl("decoder_fwd", &decoder_fwd);
+  m.impl("seg_confusion", &seg_confusion);
 }
 
 TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
@@ -405,4 +442,5 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("smpl_fwd", &smpl_fwd_meta);
   m.impl("smpl_bwd", &smpl_bwd_meta);
   m.impl("decoder_fwd", &decoder_fwd_meta);
+  m.impl("seg_confusion", &seg_confusion_meta);
 }

@@ -84,8 +84,11 @@ class SMPLDecoder(nn.Module):
         self._consts = None
         return self
 
-    def forward(self, x, labels=None):
-        """Returns dict(J_transformed [, verts, projects, mask] [, seg | seg_loss] [, silhouette])."""
+    def forward(self, x, labels=None, confusion=None):
+        """Returns dict(J_transformed [, verts, projects, mask] [, seg | seg_loss] [, silhouette]).
+        confusion: a `metrics.SegConfusion(32, device)` (or its (33, 32) int64 `counts`) that each pixel's (label,
+        arg-max of the 32 scores) is added to - by the rasteriser's loss epilogue when the loss is fused (no scores
+        written), else by the confusion kernel on `seg`.  Needs `labels`; the returned dict is unchanged."""
         if x.dim() != 2 or x.shape[1] != self.num_cam + 82:
             raise RuntimeError("SMPLDecoder expects x of shape (B, %d)" % (self.num_cam + 82))
         c = self.constants(x.device)
@@ -108,8 +111,14 @@ class SMPLDecoder(nn.Module):
                     if k in self.outputs:
                         out[k] = t
                 return out
+        conf = getattr(confusion, "counts", confusion)
+        if conf is not None:
+            if labels is None or "seg" not in self.heads:
+                raise RuntimeError("confusion counts the seg head's arg-max against labels: needs labels and the seg head")
+            if conf.dtype != torch.int64 or tuple(conf.shape) != (33, 32):
+                raise RuntimeError("confusion must count the 32 classes: SegConfusion(32, device) / a (33, 32) int64 tensor")
         fused = self.loss is not None and labels is not None
-        if labels is not None and self.loss is None:
+        if labels is not None and self.loss is None and conf is None:
             raise RuntimeError("labels were given but the decoder was built without loss=softmax_focal_loss(...)")
         spec = None
         if fused:
@@ -118,7 +127,7 @@ class SMPLDecoder(nn.Module):
             spec = (labels, w, float(self.loss.gamma))
         opts = ops.DecoderOpts(want_verts="verts" in self.outputs, want_proj="projects" in self.outputs,
                                want_mask="mask" in self.outputs, seg="seg" in self.heads,
-                               want_seg=(not fused) or self.keep_seg, loss=spec)
+                               want_seg=(not fused) or self.keep_seg, loss=spec, confusion=conf if fused else None)
         verts, proj, mask, seg, silh, jt, loss = ops.DecoderFn.apply(
             x, c, self.num_cam, self.img_wh, self.vs, pt, self.grid_wh, self.ref_compat,
             (True if self.silh_wh == self.img_wh else self.silh_wh) if self.with_silhouette else False, self.streams,
@@ -137,6 +146,9 @@ class SMPLDecoder(nn.Module):
                     out["seg"] = seg
             else:
                 out["seg"] = seg
+                if conf is not None:
+                    from .metrics import seg_confusion
+                    seg_confusion(seg.detach(), labels, conf)
         if self.with_silhouette:
             out["silhouette"] = silh
         return out

@@ -365,11 +365,12 @@ def _skin_vis_seg_fwd(v_posed, A, c: SMPLConstants, cam, W, pt: PartTable, grid_
 @on_device
 def _skin_vis_seg_fwd_ex(v_posed, A, c: SMPLConstants, cam, W, pt: PartTable, labels=None, class_w=None, gamma=0.0,
                          grid_wh=64, ref_compat=True, verts=None, proj=None, mask=None, seg=None, arg=None, rec=None,
-                         vslot=None, loss=None, stats=None, vmax=None):
+                         vslot=None, loss=None, stats=None, vmax=None, conf=None):
     """_skin_vis_seg_fwd with optional extras (smplr_skin_vis_seg_fwd_ex): with `labels` (B,W,W) int32 the loss head
     runs as the rasteriser's epilogue -> loss (B, W*W), stats (B, W*W, 4); `vmax` (B,W,W) receives each pixel's largest
     part score (the silhouette rasteriser's hint); verts / proj / mask / seg are written only where a tensor is given
-    (seg may be omitted only with labels)."""
+    (seg may be omitted only with labels); `conf` (33, 32) int64 (with labels) += the (label, arg-max) counts
+    (smplr_skin_vis_seg_fwd_ex_conf)."""
     lib = _lib.load()
     B, V = v_posed.shape[0], c.V
     if c.lbs_top4 is None or pt.VP != V or not lib.smplr_skin_vis_seg_fits(V, int(W), int(grid_wh)):
@@ -385,6 +386,14 @@ def _skin_vis_seg_fwd_ex(v_posed, A, c: SMPLConstants, cam, W, pt: PartTable, la
         stats = _empty((B, W * W, 4), v_posed) if stats is None else stats
     else:
         loss = stats = None
+    if conf is not None:
+        check(lib.smplr_skin_vis_seg_fwd_ex_conf(ptr(v_posed), ptr(c.lbs_top4), ptr(A), ptr(cam), cam.shape[1], B, V, W,
+                                                 int(grid_wh), 1 if ref_compat else 0, ptr(pt.part_pos),
+                                                 ptr(pt.part_off), pt.P, pt.K, ptr(ws), ptr(labels), ptr(class_w),
+                                                 float(gamma), ptr(verts), ptr(proj), ptr(mask), ptr(seg), ptr(arg),
+                                                 ptr(rec), ptr(vslot), ptr(loss), ptr(stats), ptr(vmax), ptr(conf),
+                                                 stream()), "smplr_skin_vis_seg_fwd_ex_conf")
+        return loss, stats, arg, rec
     check(lib.smplr_skin_vis_seg_fwd_ex(ptr(v_posed), ptr(c.lbs_top4), ptr(A), ptr(cam), cam.shape[1], B, V, W,
                                         int(grid_wh), 1 if ref_compat else 0, ptr(pt.part_pos), ptr(pt.part_off),
                                         pt.P, pt.K, ptr(ws), ptr(labels), ptr(class_w), float(gamma), ptr(verts),
@@ -395,9 +404,10 @@ def _skin_vis_seg_fwd_ex(v_posed, A, c: SMPLConstants, cam, W, pt: PartTable, la
 
 @on_device
 def _seg_raster_ex(ws, rec, B, W, pt: PartTable, labels=None, class_w=None, gamma=0.0, seg=None, arg=None, loss=None,
-                   stats=None, vmax=None):
+                   stats=None, vmax=None, conf=None):
     """Stage 2 with optional extras (smplr_seg_raster_ex) over a binned workspace -> loss, stats, arg (loss epilogue with
-    `labels`; `vmax`: per-pixel largest part score)."""
+    `labels`; `vmax`: per-pixel largest part score; `conf` (33, 32) int64, with labels: += the (label, arg-max) counts,
+    smplr_seg_raster_ex_conf)."""
     lib = _lib.load()
     if arg is None:
         arg = _empty((B, W, W, 32), rec, torch.int16)
@@ -406,6 +416,11 @@ def _seg_raster_ex(ws, rec, B, W, pt: PartTable, labels=None, class_w=None, gamm
         stats = _empty((B, W * W, 4), rec) if stats is None else stats
     else:
         loss = stats = None
+    if conf is not None:
+        check(lib.smplr_seg_raster_ex_conf(B, W, pt.P, pt.K, ptr(ws), ptr(rec), ptr(labels), ptr(class_w), float(gamma),
+                                           ptr(seg), ptr(arg), ptr(loss), ptr(stats), ptr(vmax), ptr(conf), stream()),
+              "smplr_seg_raster_ex_conf")
+        return loss, stats, arg
     check(lib.smplr_seg_raster_ex(B, W, pt.P, pt.K, ptr(ws), ptr(rec), ptr(labels), ptr(class_w), float(gamma),
                                   ptr(seg), ptr(arg), ptr(loss), ptr(stats), ptr(vmax), stream()), "smplr_seg_raster_ex")
     return loss, stats, arg
@@ -915,6 +930,9 @@ class DecoderOpts:
     # the loss head fused into the rasteriser (model.py:119-120 + focal_loss.py:10-46 at an integer class map):
     # (labels (B,W,W) integer, class_w (32,) or None, gamma) -> the pass returns the per-pixel loss (B, W*W)
     loss: Optional[tuple] = None
+    # with `loss`: a (33, 32) int64 device tensor the loss epilogue adds each pixel's (label, arg-max of the 32 scores)
+    # count to (metrics.SegConfusion.counts; every chunk adds into the same tensor)
+    confusion: Optional[torch.Tensor] = None
 
 
 # Batch from which the decoder's forward runs the pose kernel and the blend GEMM as two launches instead of one: the
@@ -998,6 +1016,13 @@ class DecoderFn(torch.autograd.Function):
                 class_w = require_cuda(class_w, "class_w")
                 if class_w.numel() != 32:
                     raise RuntimeError("class_w needs 32 entries")
+        conf = opts.confusion if opts.seg else None
+        if conf is not None:
+            if loss_spec is None:
+                raise RuntimeError("DecoderOpts.confusion rides on the fused loss: it needs DecoderOpts.loss")
+            if (not conf.is_cuda or conf.device != x.device or conf.dtype != torch.int64
+                    or tuple(conf.shape) != (33, 32) or not conf.is_contiguous()):
+                raise RuntimeError("DecoderOpts.confusion must be a contiguous (33, 32) int64 tensor on %s" % x.device)
         want_seg = opts.seg and (opts.want_seg or loss_spec is None)
         seg = _empty((B, W, W, pt.P + 1), x) if want_seg else None
         if opts.seg:
@@ -1040,7 +1065,7 @@ class DecoderFn(torch.autograd.Function):
                     v_posed[lo:hi], A[lo:hi], consts, xs, W, pt, sl(labels, lo, hi), class_w, gamma, grid_wh, ref_compat,
                     verts=sl(verts, lo, hi), proj=sl(proj, lo, hi), mask=sl(mask, lo, hi), seg=sl(seg, lo, hi),
                     arg=arg[lo:hi], rec=rec[lo:hi], vslot=vslot[lo:hi], loss=sl(loss, lo, hi), stats=sl(stats, lo, hi),
-                    vmax=sl(vmax, lo, hi))
+                    vmax=sl(vmax, lo, hi), conf=conf)
             elif fuse_skin:
                 _skin_vis_seg_opt(v_posed[lo:hi], A[lo:hi], consts, xs, W, pt, grid_wh, ref_compat,
                                   sl(verts, lo, hi), sl(proj, lo, hi), sl(mask, lo, hi), seg[lo:hi], arg[lo:hi],
@@ -1055,7 +1080,8 @@ class DecoderFn(torch.autograd.Function):
                     if loss_spec is not None or vmax is not None:
                         ws_, _ = _seg_bin(pj, mk, W, pt, grid_wh, ref_compat, rec=rec[lo:hi], vslot=vslot[lo:hi])
                         _seg_raster_ex(ws_, rec[lo:hi], n, W, pt, sl(labels, lo, hi), class_w, gamma, seg=sl(seg, lo, hi),
-                                       arg=arg[lo:hi], loss=sl(loss, lo, hi), stats=sl(stats, lo, hi), vmax=sl(vmax, lo, hi))
+                                       arg=arg[lo:hi], loss=sl(loss, lo, hi), stats=sl(stats, lo, hi), vmax=sl(vmax, lo, hi),
+                                       conf=conf)
                     else:
                         _vis_seg_fwd(pj, W, pt, grid_wh, ref_compat,
                                      out=(mk, seg[lo:hi], arg[lo:hi], rec[lo:hi]), vslot=vslot[lo:hi])

@@ -38,6 +38,7 @@ SCHEMAS = {
                  "Tensor Rs, Tensor J, Tensor A, Tensor v_posed, int num_cam=4, int vertex_sampling=1) -> Tensor"),
     "decoder_fwd": ("smplraster::decoder_fwd(Tensor x, Tensor[] consts, Tensor part_pos, Tensor part_off, int W, "
                     "int grid_wh=64, bool ref_compat=True, int num_cam=4) -> Tensor[]"),
+    "seg_confusion": "smplraster::seg_confusion(Tensor scores, Tensor labels, Tensor(a!) conf) -> ()",
 }
 
 _ns = None

@@ -77,10 +77,16 @@ class SegTrainer:
                 bucket_cap_mb=bucket_mb, gradient_as_bucket_view=True, broadcast_buffers=False)
         self.opt = torch.optim.Adam(self.smpl_model.parameters(), lr=lr)       # train.py:179
 
-    def step(self, images, labels, silh_labels=None, _marks=None):
+    def step(self, images, labels, silh_labels=None, metrics=None, _marks=None):
         """images (N,3,H,W) or (N,H,W,3); labels (N,W,W) integer class map or (N,W*W,32) one-hot, or None for the
         silhouette-only step of the alternating schedule (then silh_labels is required).
+        metrics: Keras' metrics=['accuracy'] (train.py:207-215, train_stage2_silhouette.py:228-234) - a
+        `metrics.SegConfusion(32, device)` for the seg head, or a pair (seg, silhouette) of which either may be None,
+        the silhouette one a SegConfusion(2, device); each pixel's (label, arg-max) is added to it (for the seg head
+        inside the rasteriser's loss epilogue when the loss is fused), no host sync.
         Returns the mean loss (a 0-d tensor; no host sync).  (`_marks`: see `step_timed`.)"""
+        seg_m, silh_m = metrics if isinstance(metrics, (tuple, list)) else (metrics, None)
+        as_map = lambda t: t if t.dtype in (torch.int64, torch.int32, torch.int16, torch.uint8) else t.argmax(dim=-1)
         mark = (lambda k: None) if _marks is None else _marks
         mark("start")
         self.opt.zero_grad(set_to_none=True)
@@ -97,16 +103,22 @@ class SegTrainer:
                 raise RuntimeError("a step without labels is the silhouette-only step: needs with_silhouette and silh_labels")
             out = self.silh_decoder(param)
             loss = self.silh_loss_fn(silh_labels, out["silhouette"]).mean()
+            if silh_m is not None:
+                silh_m.update(out["silhouette"], as_map(silh_labels))
         else:
             is_map = labels.dtype in (torch.int64, torch.int32, torch.int16, torch.uint8)
             if self.decoder.loss is not None and is_map:           # model.py:119-120 + focal_loss.py, in the rasteriser
-                loss = self.decoder(param, labels)
+                loss = self.decoder(param, labels, confusion=seg_m)
                 out, loss = loss, loss["seg_loss"].mean()
             else:
                 out = self.decoder(param)
                 loss = self.loss_fn(labels, out["seg"]).mean()
+                if seg_m is not None:
+                    seg_m.update(out["seg"], as_map(labels))
             if self.with_silhouette and silh_labels is not None:  # train_stage2_silhouette.py:85-86,226-229
                 loss = loss + self.silh_loss_fn(silh_labels, out["silhouette"]).mean()
+                if silh_m is not None:
+                    silh_m.update(out["silhouette"], as_map(silh_labels))
         mark("decoder_fwd")
         loss.backward()
         mark("backward")
@@ -187,21 +199,26 @@ def save_name(dataset, output_wh, use_IEF=True, scaledown=0.005, vertex_sampling
 
 
 def fit(trainer, batches, trials, steps_per_trial, save_dir=None, save_every=10, name_fn=None, start_trial=0,
-        on_trial_end=None):
+        on_trial_end=None, metrics=None):
     """The loop of train.py:221-315: `trials` rounds of `steps_per_trial` optimiser steps (`fit_generator(...,
     steps_per_epoch, nb_epoch=1)`) over `batches` - an iterator of (images, labels[, silhouette labels]) already
     on the device, the data generators being the caller's - and every `save_every` trials (on rank 0) the monitor
     hook `on_trial_end(trial, trainer)` (use `trainer.monitor(images)` for verts / projects / seg: the train decoder
     `trainer.decoder` writes losses only) and a checkpoint named like the reference's.  -> list of per-trial mean losses (python floats; the one
-    host sync per trial)."""
+    host sync per trial).  metrics: what `step` takes (a SegConfusion, or a (seg, silhouette) pair), handed to every
+    step and reset at the start of every trial - `on_trial_end` reads the trial's accuracy from it (Keras'
+    metrics=['accuracy'])."""
     it = iter(batches)
     rank0 = (not dist.is_initialized()) or dist.get_rank() == 0
     history = []
+    mlist = [m for m in (metrics if isinstance(metrics, (tuple, list)) else (metrics,)) if m is not None]
     for trial in range(start_trial, trials):
         total = None
+        for m in mlist:
+            m.reset()
         for _ in range(steps_per_trial):
             batch = next(it)
-            loss = trainer.step(*batch)
+            loss = trainer.step(*batch, metrics=metrics) if metrics is not None else trainer.step(*batch)
             total = loss if total is None else total + loss
         history.append(float(total) / max(1, steps_per_trial))
         if trial % save_every == 0:
