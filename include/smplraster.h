@@ -359,6 +359,11 @@ int smplr_silh_fwd(const float *proj, int B, int VP, int W, float *silh, int32_t
  * for that pixel; hint = NULL is smplr_silh_fwd.                                                                 */
 int smplr_silh_fwd_hint(const float *proj, const float *hint, int B, int VP, int W, float *silh, int32_t *arg,
                         void *workspace, void *stream);
+/* Which kernel smplr_silh_fwd / _hint run for meshes of VP vertices at W (host arithmetic only; they choose through
+ * this function): 0 the pixel-per-lane kernel (W <= 48 while its LDS layout holds the mesh), 1 the fused kernel with
+ * one row-mask word (W <= 48, larger meshes up to 8 192 vertices), 2 the fused kernel with two (48 < W <= 96,
+ * VP <= 8 192), 3 brute force over every vertex (W > 96 or VP > 8 192); -1 for sizes smplr_silh_fwd refuses.     */
+int smplr_silh_fwd_form(int VP, int W);
 int smplr_silh_bwd(const float *dsilh, const float *silh, const int32_t *arg,
                    const float *proj, int B, int VP, int W, float *dproj, int deterministic, void *stream);
 

@@ -80,6 +80,7 @@ SIGNATURES = {
     "smplr_silh_workspace": (c_size_t, [I, I, I]),
     "smplr_silh_fwd": (c_int, [P, I, I, I, P, P, P, P]),
     "smplr_silh_fwd_hint": (c_int, [P, P, I, I, I, P, P, P, P]),
+    "smplr_silh_fwd_form": (c_int, [I, I]),
     "smplr_silh_bwd": (c_int, [P, P, P, P, I, I, I, P, I, P]),
     "smplr_focal_fwd": (c_int, [P, P, P, P, c_float, c_longlong, I, P, P, P]),
     "smplr_focal_bwd": (c_int, [P, P, P, P, c_float, P, c_longlong, I, P, P]),

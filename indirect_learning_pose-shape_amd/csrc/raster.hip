@@ -2238,23 +2238,26 @@ __global__ __launch_bounds__(RT) void silh_fwd_kernel(const float4 *__restrict__
   const int r = qc / W, c = qc - r * W;
   const float fc = (float)c, fr = (float)r;
   const float4 *S = sorted + (size_t)n * KP;
-  float best = INFINITY;
-  int bestk = 0;
+  // keys (d^2 bits, vertex index) compared as 64-bit integers, as in the pruned kernels below: the same d^2 expression,
+  // ties to the lowest index, and a NaN position (its d^2 bits lie above +inf's) wins only a pixel that has no other
+  // vertex - an all-NaN mesh gets the NaN silhouette the pruned kernels give it.  Padding records (index -1) never win.
+  unsigned long long best = ~0ull;
   for (int k = 0; k < KP; k += CH) {
-    float cm = pair_key(S[k], fc, fr);
 #pragma unroll
-    for (int j = 1; j < CH; ++j) cm = fminf(cm, pair_key(S[k + j], fc, fr));
-    if (cm < best) { best = cm; bestk = k; }
+    for (int j = 0; j < CH; ++j) {
+      const float4 a = S[k + j];
+      const int v = __float_as_int(a.w);
+      const float du = a.x - fc, dv = a.y - fr;
+      const unsigned long long key =
+          v < 0 ? ~0ull : ((unsigned long long)__float_as_uint(fmaf(du, du, dv * dv)) << 32) | (unsigned int)v;
+      best = key < best ? key : best;
+    }
   }
   int pos = -1;
   float score = 0.0f;
-  if (best < INFINITY) {
-#pragma unroll
-    for (int j = CH - 1; j >= 0; --j) {
-      const float4 a = S[bestk + j];
-      if (pair_key(a, fc, fr) == best) pos = __float_as_int(a.w);
-    }
-    score = expf(-sqrtf(best) / 1.2f);
+  if (best != ~0ull) {
+    score = expf(-sqrtf(__uint_as_float((unsigned int)(best >> 32))) / 1.2f);
+    pos = (int)(best & 0xffffffffull);
   }
   if (live) {
     const size_t o = ((size_t)n * W + (W - 1 - r)) * W + c;   // rows flipped (:42)
@@ -3341,6 +3344,14 @@ int smplr_silh_fwd(const float *proj, int B, int VP, int W, float *silh, int32_t
   return smplr_silh_fwd_hint(proj, nullptr, B, VP, W, silh, arg, workspace, stream);
 }
 
+int smplr_silh_fwd_form(int VP, int W) {
+  using namespace smplr;
+  if (VP <= 0 || W <= 0 || W > 1024) return -1;
+  if (W + 2 * SM <= 64 && VP <= SF_T * IPT_MAX && silh_px_layout(VP, W).total <= 159 * 1024) return 0;
+  if (W <= SILH_WMAX && VP <= SF_T * IPT_MAX && silh_fused_lds(VP, W) <= 150 * 1024) return W + 2 * SM <= 64 ? 1 : 2;
+  return 3;
+}
+
 int smplr_silh_fwd_hint(const float *proj, const float *hint, int B, int VP, int W, float *silh, int32_t *arg,
                         void *workspace, void *stream) {
   using namespace smplr;
@@ -3348,7 +3359,8 @@ int smplr_silh_fwd_hint(const float *proj, const float *hint, int B, int VP, int
   if (B == 0) return 0;
   SMPLR_REQUIRE(proj && silh && arg && workspace, "smplr_silh_fwd: null pointer");
   hipStream_t st = as_stream(stream);
-  if (W + 2 * SM <= 64 && VP <= SF_T * IPT_MAX && silh_px_layout(VP, W).total <= 159 * 1024) {
+  const int form = smplr_silh_fwd_form(VP, W);
+  if (form == 0) {
     const SpxLds L = silh_px_layout(VP, W);
     const int nsplit = B >= 256 ? 1 : (B >= 128 ? 2 : 4);      // one workgroup per CU (256 CUs)
     int rc = lds_attr<&silh_px_kernel>(L.total);
@@ -3357,10 +3369,10 @@ int smplr_silh_fwd_hint(const float *proj, const float *hint, int B, int VP, int
     SMPLR_LAUNCH_CHECK("smplr_silh_fwd");
     return 0;
   }
-  if (W <= SILH_WMAX && VP <= SF_T * IPT_MAX && silh_fused_lds(VP, W) <= 150 * 1024) {
+  if (form == 1 || form == 2) {
     const size_t lds = silh_fused_lds(VP, W);
     const int nsplit = B >= 256 ? 1 : (B >= 128 ? 2 : 4);      // one workgroup per CU (256 CUs)
-    if (W + 2 * SM <= 64) {
+    if (form == 1) {
       int rc = lds_attr<&silh_fused_kernel<true>>(lds);
       if (rc) return rc;
       hipLaunchKernelGGL(silh_fused_kernel<true>, dim3(B, nsplit), dim3(SF_T), lds, st, proj, VP, W, silh, arg);

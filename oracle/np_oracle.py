@@ -251,19 +251,68 @@ def projects_to_seg(projects_with_depth, mask_vals, img_wh, part_ids, part_off,
     return out
 
 
-def projects_to_silhouette(projects_with_depth, img_wh):
-    """`keras_smpl/projects_to_silhouette.py:14-44`: all vertices, no mask, exp(-d/1.2)."""
+def projects_to_silhouette(projects_with_depth, img_wh, return_argmin=False, chunk=None):
+    """`keras_smpl/projects_to_silhouette.py:14-44`: all vertices, no mask, exp(-d/1.2).
+
+    Evaluated `chunk` pixels at a time (default: about 4 M vertex-pixel pairs) instead of the reference's whole
+    (W2, V, 2) difference tensor (:35; 1.8 GB per mesh at W = 128), with the same elementwise operations: the values
+    are the dense formula's bit for bit (a sum over a length-2 axis is the one addition written out here).
+    return_argmin: also (N, W, W) int64, rows flipped like the output: the vertex nearest each pixel, the lowest index
+    on an exact tie in distance (the HIP kernels' rule, DESIGN.md's deviations)."""
     proj = np.asarray(projects_with_depth, F)[:, :, :2]                  # :20
-    N = proj.shape[0]
+    N, V = proj.shape[0], proj.shape[1]
     grid = _grid(img_wh)
-    out = np.empty((N, img_wh * img_wh), F)
-    for n in range(N):                                                   # batch loop: memory only
-        diff = proj[n][None, :, :] - grid[:, None, :]                    # (W2,V,2) :35
-        norm = np.sqrt(np.sum(diff * diff, axis=2))                      # :36
-        out[n] = np.exp(-norm / 1.2).max(axis=1)                         # :37-38
+    npix = img_wh * img_wh
+    step = int(chunk) if chunk else max(1, (1 << 22) // max(V, 1))
+    out = np.empty((N, npix), F)
+    arg = np.empty((N, npix), np.int64) if return_argmin else None
+    for n in range(N):                                                   # batch and pixel loops: memory only
+        pu, pv = proj[n, :, 0][None, :], proj[n, :, 1][None, :]
+        for p0 in range(0, npix, step):
+            g = grid[p0:p0 + step]
+            du, dv = pu - g[:, 0:1], pv - g[:, 1:2]                      # (chunk,V) of the (W2,V,2) diff, :35
+            norm = np.sqrt(du * du + dv * dv)                            # :36
+            out[n, p0:p0 + step] = np.exp(-norm / 1.2).max(axis=1)       # :37-38
+            if return_argmin:
+                arg[n, p0:p0 + step] = np.argmin(norm, axis=1)
     sil = out.reshape(N, img_wh, img_wh)                                 # :39
-    res = np.stack([1.0 - sil, sil], axis=3)                             # :40-41
-    return res[:, ::-1]                                                  # :42
+    res = np.stack([1.0 - sil, sil], axis=3)[:, ::-1]                    # :40-42
+    if return_argmin:
+        return res, arg.reshape(N, img_wh, img_wh)[:, ::-1]
+    return res
+
+
+def silhouette_vjp(projects_with_depth, dsilh, img_wh, arg):
+    """The backward of `projects_to_silhouette` w.r.t. the projected vertices, in closed form, given the vertex that
+    wins each pixel: arg (N, W, W) as the output lies (rows flipped), -1 = none.  Pixel p = (c, r) won by vertex v adds
+    (dsilh[p,1] - dsilh[p,0]) * (-s_p / 1.2) * (proj_v - p) / d_p to row v, d_p = |proj_v - p|, s_p = exp(-d_p / 1.2):
+    the derivative of exp(-norm / 1.2) (:36-41) through the maximum (:37-38), which routes it to the winner.  The z
+    column is 0 (:20 drops it); the term is 0 where d = 0 (TF: NaN - the HIP kernels' rule, DESIGN.md's deviations)
+    and where d is NaN.
+    Returns dproj (N, V, 3) and abs_sum (N, V, 2): per vertex and component the sum of |term|, the size against which
+    the rounding of any order of summation is measured."""
+    proj = np.asarray(projects_with_depth, F)
+    g = np.asarray(dsilh, F)
+    arg = np.asarray(arg, np.int64)
+    N, V, W = proj.shape[0], proj.shape[1], img_wh
+    dproj = np.zeros((N, V, 3), F)
+    abs_sum = np.zeros((N, V, 2), F)
+    ro, c = np.divmod(np.arange(W * W), W)
+    pix = np.stack([c, W - 1 - ro], axis=1).astype(F)                   # (x=c, y=r) of output position (ro, c)
+    for n in range(N):
+        a = arg[n].reshape(-1)
+        ok = a >= 0
+        v = a[ok]
+        diff = proj[n, v, :2] - pix[ok]
+        d = np.sqrt(diff[:, 0] * diff[:, 0] + diff[:, 1] * diff[:, 1])
+        gg = (g[n, ..., 1] - g[n, ..., 0]).reshape(-1)[ok]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            k = np.where(d > 0, gg * (-np.exp(-d / 1.2) / 1.2) / d, 0.0)
+            term = np.where((d > 0)[:, None], k[:, None] * diff, 0.0)
+        for comp in range(2):
+            dproj[n, :, comp] = np.bincount(v, weights=term[:, comp], minlength=V)
+            abs_sum[n, :, comp] = np.bincount(v, weights=np.abs(term[:, comp]), minlength=V)
+    return dproj, abs_sum
 
 
 # --------------------------------------------------------------------------- conditioning

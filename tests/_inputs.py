@@ -38,6 +38,28 @@ def argmin_disagreements(a, warg, want, proj, mask, W, rtol=1e-5):
     return len(idx), bad
 
 
+def silh_argmin_disagreements(a, warg, proj, W, rtol=1e-6):
+    """The silhouette's arg-min check with a cause: a / warg (B, W, W) the vertex nearest each pixel from the HIP path
+    and from the float64 oracle (np_oracle.projects_to_silhouette(return_argmin=True)); proj (B, V', >= 2) what both
+    were given.  They may differ only on a near-tie proven in float64: the HIP's vertex within `rtol` (relative, in
+    d^2) of the oracle's.  Returns (number of disagreements, number of unexplained ones)."""
+    a, warg = np.asarray(a, np.int64), np.asarray(warg, np.int64)
+    proj = np.asarray(proj, np.float64)
+    idx = np.argwhere(a != warg)
+    bad = 0
+    for n, ro, c in idx:
+        va, vw = a[n, ro, c], warg[n, ro, c]
+        if not (0 <= va < proj.shape[1] and 0 <= vw < proj.shape[1]):
+            bad += 1
+            continue
+        r = W - 1 - ro                                            # rows are flipped on output
+        da = (proj[n, va, 0] - c) ** 2 + (proj[n, va, 1] - r) ** 2
+        dw = (proj[n, vw, 0] - c) ** 2 + (proj[n, vw, 1] - r) ** 2
+        if not da <= dw * (1.0 + rtol):
+            bad += 1
+    return len(idx), bad
+
+
 def unstable_cells(proj, grid_wh=64, eps=1e-4, zeps=1e-5):
     """Cells of the visibility grid whose winner may differ between fp32 and float64 vertices, by cause: a vertex
     within `eps` px of a cell border (it may round into either cell - both are marked), or the two largest depths

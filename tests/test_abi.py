@@ -83,6 +83,25 @@ def test_seg_bwd_row_blocks_by_batch():
         assert lib.smplr_seg_bwd_workspace(B, W) == B * lib.smplr_seg_bwd_nsplit(B, W) * 5 * 4096 * 2 * 4
 
 
+def test_silh_fwd_form_boundaries():
+    """smplr_silh_fwd_form(VP, W) (host arithmetic only): the silhouette forward smplr_silh_fwd runs - 0 the
+    pixel-per-lane kernel, 1 / 2 the fused kernel with one / two row-mask words, 3 brute force.  The width edges at the
+    reference's 6 890 vertices, and at W = 48 the VP edges where the function puts them (the px kernel's LDS layout,
+    then 8 192 = 8 vertices per thread of the fused kernels): one run of each form, in that order."""
+    from ilps_amd import _lib
+    f = _lib.load().smplr_silh_fwd_form
+    assert [f(6890, W) for W in (1, 47, 48, 49, 64, 96, 97, 128, 1024)] == [0, 0, 0, 2, 2, 2, 3, 3, 3]
+    vps = range(1, 8300)
+    forms = [f(vp, 48) for vp in vps]
+    px_last = max(vp for vp, fm in zip(vps, forms) if fm == 0)
+    fused_last = max(vp for vp, fm in zip(vps, forms) if fm == 1)
+    assert forms == [0] * px_last + [1] * (fused_last - px_last) + [3] * (len(vps) - fused_last)
+    assert 6890 < px_last < 8192 and fused_last == 8192
+    assert f(px_last + 1, 48) == 1 and f(8193, 48) == 3
+    assert f(8192, 96) == 2 and f(8193, 96) == 3 and f(8192, 1) == 0 and f(8193, 1) == 3
+    assert f(0, 48) == -1 and f(6890, 0) == -1 and f(6890, 1025) == -1
+
+
 def test_library_is_built_from_the_sources_beside_it(monkeypatch):
     """smplr_build_id() = sha256 over csrc/*.hip, csrc/*.h and the header as csrc/Makefile took it; `_lib.load()`
     recomputes it from the files and refuses a library built from anything else."""

@@ -79,6 +79,43 @@ def test_bad_rows_do_not_reach_their_neighbours(smpl_model, part_tables):
     assert torch.isnan(dx[3, 4:]).all()
 
 
+def test_bad_rows_with_the_silhouette_at_its_own_resolution(smpl_model):
+    """The same batch through SMPLDecoder(img_wh=48, silh_wh=112): the silhouette runs the brute-force kernel there
+    (smplr_silh_fwd_form = 3).  The good rows bit-equal to the rows run alone, rows 5-7 the oracle's silhouette at 112,
+    the NaN row a NaN silhouette as at 48."""
+    from ilps_amd import _lib
+    from ilps_amd.decoder import SMPLDecoder
+    from oracle import np_oracle as o
+    dev = torch.device("cuda", 0)
+    W, WS, B = 48, 112, 8
+    assert _lib.load().smplr_silh_fwd_form(6890, WS) == 3
+    xn = make_x(B, W, 4242)
+    xn[3, 10] = np.nan
+    xn[5, 0] = 1e30
+    xn[6, 0:4] = [0.0, 0.0, 24.0, 24.0]
+    xn[7, 2:4] = [1e4, -1e4]
+    x = torch.tensor(xn, device=dev)
+    g = torch.Generator(device="cpu").manual_seed(1)
+    dseg = torch.randn(B, W, W, 32, generator=g).to(dev)
+    dsilh = torch.randn(B, WS, WS, 2, generator=g).to(dev)
+    dec = SMPLDecoder(smpl_model, img_wh=W, silh_wh=WS, with_silhouette=True, deterministic=True)
+    out, dx = _run(dec, x, dseg, dsilh)
+    assert out["silhouette"].shape == (B, WS, WS, 2)
+    good = [0, 1, 2, 4]
+    out_g, dx_g = _run(dec, x[good].contiguous(), dseg[good].contiguous(), dsilh[good].contiguous())
+    for k in ("projects", "seg", "silhouette"):
+        assert torch.equal(out[k][good], out_g[k]), "%s of the good rows changed beside bad rows" % k
+    assert torch.equal(dx[good], dx_g), "dx of the good rows changed beside bad rows"
+    proj = out["projects"].cpu().numpy().astype(np.float64)
+    for r in (5, 6, 7):
+        wsil = o.projects_to_silhouette(proj[r:r + 1], WS)
+        gsil = out["silhouette"][r:r + 1].cpu().numpy()
+        assert np.all(np.abs(gsil - wsil) <= SEG_RTOL * np.abs(wsil) + SEG_ATOL), "row %d: silhouette at %d" % (r, WS)
+        assert torch.isfinite(dx[r]).all(), "row %d: gradient" % r
+    assert torch.isnan(out["silhouette"][3]).all(), "the NaN row's silhouette at %d is not NaN" % WS
+    assert torch.isnan(dx[3, 4:]).all()
+
+
 def test_bad_rows_through_the_fused_loss(smpl_model):
     """The same batch through the training path's decoder (loss head inside the rasteriser, no outputs written):
     finite loss and gradient for the good rows, equal to the rows run alone."""

@@ -186,6 +186,61 @@ def test_silhouette_kats():
     assert np.allclose(t, s, atol=1e-14)
 
 
+def test_silhouette_chunked_equals_dense_formula():
+    """The pixel-chunked forward = the dense (W2, V, 2) formula of projects_to_silhouette.py:35-42 bit for bit, for any
+    chunk; return_argmin gives the nearest vertex, the lowest index on an exact tie."""
+    rng = np.random.default_rng(22)
+    W = 9
+    p = rng.uniform(-4.0, W + 4.0, (2, 50, 3))
+    p[0, 7, :2] = [3.0, 4.0]                                  # on a pixel centre: d = 0
+    grid = o._grid(W)
+    dense = np.empty((2, W * W))
+    for n in range(2):
+        diff = p[n, :, :2][None, :, :] - grid[:, None, :]
+        dense[n] = np.exp(-np.sqrt(np.sum(diff * diff, axis=2)) / 1.2).max(axis=1)
+    sil = dense.reshape(2, W, W)
+    want = np.stack([1.0 - sil, sil], axis=3)[:, ::-1]
+    for chunk in (1, 7, 81, None):
+        assert np.array_equal(o.projects_to_silhouette(p, W, chunk=chunk), want)
+    s, arg = o.projects_to_silhouette(p, W, return_argmin=True, chunk=10)
+    assert np.array_equal(s, want) and arg.shape == (2, W, W) and arg[0, W - 1 - 4, 3] == 7
+    d2 = ((p[:, None, :, :2] - grid[None, :, None, :]) ** 2).sum(-1)
+    assert np.array_equal(arg, d2.argmin(axis=2).reshape(2, W, W)[:, ::-1])
+    q = np.array([[[1.5, 1.0, 0.0], [0.5, 1.0, 0.0], [0.5, 1.0, 0.0]]])   # exact ties at pixels (1, 1) and (0, 1)
+    _, qa = o.projects_to_silhouette(q, 3, return_argmin=True)
+    assert qa[0, 3 - 1 - 1, 1] == 0 and qa[0, 3 - 1 - 1, 0] == 1
+
+
+def test_silhouette_vjp_equals_autograd():
+    """np_oracle.silhouette_vjp (closed form at the winning vertex) = autograd of torch_oracle.projects_to_silhouette,
+    float64, on random cases without ties; the z column and the vertices that win no pixel are 0; d = 0 gives no term."""
+    rng = np.random.default_rng(23)
+    B, V, W = 2, 40, 12
+    p = rng.uniform(-3.0, W + 3.0, (B, V, 3))
+    p[:, -3:, :2] = 100.0                                     # win no pixel
+    g = rng.normal(0.0, 1.0, (B, W, W, 2))
+    _, arg = o.projects_to_silhouette(p, W, return_argmin=True)
+    pt = torch.tensor(p, requires_grad=True)
+    (to.projects_to_silhouette(pt, W) * torch.tensor(g)).sum().backward()
+    dproj, abs_sum = o.silhouette_vjp(p, g, W, arg)
+    want = pt.grad.numpy()
+    assert np.abs(dproj - want).max() <= 1e-12 * max(1.0, np.abs(want).max())
+    assert np.all(dproj[..., 2] == 0) and np.all(abs_sum >= np.abs(dproj[..., :2]))
+    won = np.zeros((B, V), bool)
+    for n in range(B):
+        won[n, np.unique(arg[n])] = True
+    assert not won[:, -3:].any() and np.all(dproj[~won] == 0) and np.all(abs_sum[~won] == 0)
+    one = np.array([[[5.0, 6.0, 0.0]]])
+    zero = np.zeros((1, W, W), np.int64)
+    gg = np.zeros((1, W, W, 2))
+    gg[0, W - 1 - 6, 5] = [0.3, -1.1]                         # the pixel under the vertex: d = 0, no term
+    d, a = o.silhouette_vjp(one, gg, W, zero)
+    assert np.all(d == 0) and np.all(a == 0)
+    gg[0, W - 1 - 6, 7] = [0.0, 1.0]                          # pixel (7, 6): proj - pixel = (-2, 0)
+    d, _ = o.silhouette_vjp(one, gg, W, zero)
+    assert np.isclose(d[0, 0, 0], np.exp(-2.0 / 1.2) / 1.2, rtol=1e-14, atol=0) and d[0, 0, 1] == 0
+
+
 def test_conditioning():
     from ilps_amd.smpl_model import load_mean_params
     pose, shape = load_mean_params()
