@@ -347,6 +347,44 @@ int smplr_skin_vis_seg_fwd_ex_conf(const float *v_posed, const float *lbs_top4, 
                                    float *mask, float *seg, int16_t *arg, float *rec, int16_t *vslot, float *loss,
                                    float *stats, float *vmax, uint64_t *conf, void *stream);
 
+/* ---- triangle renderer: renderer.py:33-115 (SMPLRenderer), 146-237 (Lambertian point lights / part colours) --------
+ * B meshes (B, V, 3) fp32 sharing one faces (F, 3) int32 -> per-pixel face id, depth, part, coverage and colour.  Not
+ * differentiable, no anti-aliasing, no near-plane clipping.  Pixel [i, j] samples (x, y) = (j, i) of sample space.
+ *   SMPLR_MESH_ORTHO        cam (B, 4) = smpl[:, :4] (k_u, k_v, u0, v0): x = s (u0 + k_u X), y = H - 1 - s (v0 + k_v Y)
+ *                           (projection.py:54-81, rows flipped as projects_to_seg.py:68); nearer = LARGER z.
+ *   SMPLR_MESH_PERSPECTIVE  cam (B, 3) = (f, px, py): x = s (f X / Z + px), y = s (f Y / Z + py) (renderer.py:55-69,
+ *                           OpenCV rows); nearer = smaller z; a face with a vertex Z outside (max(znear, 0), zfar] is
+ *                           dropped.  X, Y, Z = verts + trans (trans (B, 3) or NULL).
+ * Coverage is exact (8 sub-pixel bits, int64 edge functions, both windings, a top-left rule); the nearest face wins,
+ * equal depths go to the lower face id.  A face covers nothing if it has zero area, an index outside [0, V), or a vertex
+ * that is not finite or lies outside the +-2^15 px guard band.  Depth (ortho z, perspective z) and colour are
+ * interpolated from the exact barycentrics, perspective-correct in perspective mode.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= H, W <= 4096; 1 <= V <= 2^24; 0 <= F <= 2^24; mode ortho or
+ * perspective; B = 0 is a no-op.
+ *   smplr_mesh_vbuf_bytes  the per-vertex buffer vbuf the two stages share: B V 32 bytes.
+ *   smplr_mesh_vertex      vertex stage.  shading SMPLR_MESH_LAMBERT: colour = albedo * sum_k c_k max(0, n . l_k), n the
+ *                          normalised sum of (v1 - v0) x (v2 - v0) over the vertex's incident faces in the order of the
+ *                          CSR vf_off (V + 1) / vf_face (nnz) (0 if the sum is zero), l_k the unit vector to light k;
+ *                          light = HOST floats: albedo[3], then nlights x (position[3], colour[3]), nlights <= 8.
+ *                          SMPLR_MESH_VERTEX_COLOR: vcol (V, 3) fp32 with a batch stride of vcol_bstride floats (0: one
+ *                          table for every mesh).  Colours are clipped to [0, 1].
+ *   smplr_mesh_raster      raster + resolve.  face_part (F) uint8 or NULL (part 0); bg (B, H, W, 3) fp32 or NULL (white).
+ *                          Outputs, each optional (NULL: not written): face (B, H, W) int32, -1 = background; depth
+ *                          (B, H, W) fp32, 0 on background; part (B, H, W) uint8; alpha (B, H, W) uint8 0 / 1; rgb
+ *                          (B, H, W, 3) fp32 composited over bg.  vbuf, B, V, H, W and mode as given to the vertex stage. */
+#define SMPLR_MESH_ORTHO 0
+#define SMPLR_MESH_PERSPECTIVE 1
+#define SMPLR_MESH_LAMBERT 0
+#define SMPLR_MESH_VERTEX_COLOR 1
+size_t smplr_mesh_vbuf_bytes(int B, int V);
+int smplr_mesh_vertex(const float *verts, const float *cam, const float *trans, int B, int V, int mode, float scale,
+                      int H, int W, float znear, float zfar, int shading, const int32_t *faces, int F,
+                      const int32_t *vf_off, const int32_t *vf_face, int nnz, const float *light, int nlights,
+                      const float *vcol, long long vcol_bstride, void *vbuf, void *stream);
+int smplr_mesh_raster(const void *vbuf, const int32_t *faces, const uint8_t *face_part, int B, int V, int F, int H,
+                      int W, int mode, const float *bg, int32_t *face, float *depth, uint8_t *part, uint8_t *alpha,
+                      float *rgb, void *stream);
+
 /* ---- projects_to_silhouette: keras_smpl/projects_to_silhouette.py:14-44 ----------------- */
 /* silh (B,W,W,2) = [1-s, s], s = max_v exp(-|proj_v-(c,r)|/1.2) over ALL VP vertices, rows
  * flipped; arg (B,W,W) int32 = maximising vertex.  workspace: smplr_silh_workspace(B,VP,W) B.  */

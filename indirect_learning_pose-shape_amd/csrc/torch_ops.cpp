@@ -389,6 +389,99 @@ void seg_confusion_meta(const Tensor &scores, const Tensor &labels, Tensor &conf
   TORCH_CHECK(labels.numel() == npix, "labels hold ", labels.numel(), " entries for ", npix, " pixels");
 }
 
+// ---- triangle renderer (renderer.py:33-115): verts (B, V, 3) + faces (F, 3) -> [face, depth, part, alpha, rgb] -------
+// cam (B, 4) ortho (mode 0) or (B, 3) perspective (mode 1); shading from the optionals: vcol (V, 3) or (B, V, 3) ->
+// per-vertex colours, else Lambert with the vertex->face CSR vf_off (V + 1) / vf_face and light = albedo (3) then
+// (position, colour) per light.  face_part (F) uint8, background (B, H, W, 3) fp32 in [0, 1] (None: white).
+void mesh_render_check(const Tensor &verts, const Tensor &cam, const c10::optional<Tensor> &trans, const Tensor &faces,
+                       const c10::optional<Tensor> &face_part, const c10::optional<Tensor> &vcol,
+                       const c10::optional<Tensor> &background, at::ArrayRef<double> light, int64_t H, int64_t W,
+                       int64_t mode, bool lambert) {
+  TORCH_CHECK(verts.dim() == 3 && verts.size(2) == 3, "verts must be (B, V, 3)");
+  TORCH_CHECK(mode == 0 || mode == 1, "mode must be 0 (ortho) or 1 (perspective)");
+  const int64_t B = verts.size(0), V = verts.size(1);
+  TORCH_CHECK(V >= 1 && V <= (1 << 24), "V must be in 1..2^24");
+  TORCH_CHECK(H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "H and W must be in 1..4096");
+  TORCH_CHECK(cam.dim() == 2 && cam.size(0) == B && cam.size(1) == (mode == 0 ? 4 : 3),
+              "cam must be (B, 4) in ortho mode and (B, 3) in perspective mode");
+  TORCH_CHECK(!trans || (trans->dim() == 2 && trans->size(0) == B && trans->size(1) == 3), "trans must be (B, 3)");
+  TORCH_CHECK(faces.dim() == 2 && faces.size(1) == 3 && faces.size(0) <= (1 << 24), "faces must be (F, 3), F <= 2^24");
+  TORCH_CHECK(faces.scalar_type() == at::kInt, "faces must be int32");
+  TORCH_CHECK(!face_part || (face_part->dim() == 1 && face_part->size(0) == faces.size(0) &&
+                             face_part->scalar_type() == at::kByte), "face_part must be (F,) uint8");
+  TORCH_CHECK(!vcol || (vcol->dim() == 2 && vcol->size(0) == V && vcol->size(1) == 3) ||
+                  (vcol->dim() == 3 && vcol->size(0) == B && vcol->size(1) == V && vcol->size(2) == 3),
+              "vcol must be (V, 3) or (B, V, 3)");
+  TORCH_CHECK(!background || (background->dim() == 4 && background->size(0) == B && background->size(1) == H &&
+                              background->size(2) == W && background->size(3) == 3), "background must be (B, H, W, 3)");
+  TORCH_CHECK(!lambert || (light.size() >= 3 && (light.size() - 3) % 6 == 0 && (light.size() - 3) / 6 <= 8),
+              "light must be albedo (3) followed by up to 8 (position (3), colour (3)) lights");
+}
+std::vector<Tensor> mesh_render_outputs(const Tensor &verts, int64_t H, int64_t W) {
+  const int64_t B = verts.size(0);
+  auto o = verts.options();
+  return {at::empty({B, H, W}, o.dtype(at::kInt)), at::empty({B, H, W}, o.dtype(at::kFloat)),
+          at::empty({B, H, W}, o.dtype(at::kByte)), at::empty({B, H, W}, o.dtype(at::kBool)),
+          at::empty({B, H, W, 3}, o.dtype(at::kFloat))};
+}
+std::vector<Tensor> mesh_render(const Tensor &verts, const Tensor &cam, const c10::optional<Tensor> &trans,
+                                const Tensor &faces, const c10::optional<Tensor> &face_part,
+                                const c10::optional<Tensor> &vf_off, const c10::optional<Tensor> &vf_face,
+                                const c10::optional<Tensor> &vcol, const c10::optional<Tensor> &background,
+                                at::ArrayRef<double> light, int64_t H, int64_t W, int64_t mode, double scale,
+                                double znear, double zfar) {
+  const bool lambert = !vcol.has_value();
+  mesh_render_check(verts, cam, trans, faces, face_part, vcol, background, light, H, W, mode, lambert);
+  dev_f32(verts, "verts");
+  dev_f32(cam, "cam");
+  if (trans) dev_f32(*trans, "trans");
+  dev_typed(faces, at::kInt, "faces");
+  if (face_part) dev_typed(*face_part, at::kByte, "face_part");
+  if (vcol) dev_f32(*vcol, "vcol");
+  if (background) dev_f32(*background, "background");
+  if (lambert) {
+    TORCH_CHECK(vf_off && vf_face, "lambert shading needs the vertex->face CSR (vf_off, vf_face)");
+    dev_typed(*vf_off, at::kInt, "vf_off");
+    dev_typed(*vf_face, at::kInt, "vf_face");
+    TORCH_CHECK(vf_off->dim() == 1 && vf_off->size(0) == verts.size(1) + 1, "vf_off must be (V + 1,)");
+  }
+  const Tensor none;
+  same_device(verts, {{"cam", &cam}, {"trans", trans ? &*trans : &none}, {"faces", &faces},
+                      {"face_part", face_part ? &*face_part : &none}, {"vf_off", vf_off ? &*vf_off : &none},
+                      {"vf_face", vf_face ? &*vf_face : &none}, {"vcol", vcol ? &*vcol : &none},
+                      {"background", background ? &*background : &none}});
+  DeviceGuard g(verts.device());
+  const int B = (int)verts.size(0), V = (int)verts.size(1), F = (int)faces.size(0);
+  auto out = mesh_render_outputs(verts, H, W);
+  if (B == 0) return out;
+  Tensor vbuf = at::empty({(int64_t)smplr_mesh_vbuf_bytes(B, V)}, verts.options().dtype(at::kByte));
+  std::vector<float> lt(light.begin(), light.end());
+  const int nl = lambert ? (int)(lt.size() - 3) / 6 : 0;
+  ok(smplr_mesh_vertex(verts.data_ptr<float>(), cam.data_ptr<float>(), trans ? fp(*trans) : nullptr, B, V, (int)mode,
+                       (float)scale, (int)H, (int)W, (float)znear, (float)zfar,
+                       lambert ? SMPLR_MESH_LAMBERT : SMPLR_MESH_VERTEX_COLOR, faces.data_ptr<int32_t>(), F,
+                       lambert ? vf_off->data_ptr<int32_t>() : nullptr, lambert ? vf_face->data_ptr<int32_t>() : nullptr,
+                       lambert ? (int)vf_face->numel() : 0, lambert ? lt.data() : nullptr, nl,
+                       vcol ? fp(*vcol) : nullptr, vcol && vcol->dim() == 3 ? (long long)V * 3 : 0, vbuf.data_ptr(),
+                       cur_stream()),
+     "smplr_mesh_vertex");
+  ok(smplr_mesh_raster(vbuf.data_ptr(), faces.data_ptr<int32_t>(), face_part ? face_part->data_ptr<uint8_t>() : nullptr,
+                       B, V, F, (int)H, (int)W, (int)mode, background ? fp(*background) : nullptr,
+                       out[0].data_ptr<int32_t>(), out[1].data_ptr<float>(), out[2].data_ptr<uint8_t>(),
+                       reinterpret_cast<uint8_t *>(out[3].data_ptr<bool>()), out[4].data_ptr<float>(), cur_stream()),
+     "smplr_mesh_raster");
+  return out;
+}
+std::vector<Tensor> mesh_render_meta(const Tensor &verts, const Tensor &cam, const c10::optional<Tensor> &trans,
+                                     const Tensor &faces, const c10::optional<Tensor> &face_part,
+                                     const c10::optional<Tensor> &vf_off, const c10::optional<Tensor> &vf_face,
+                                     const c10::optional<Tensor> &vcol, const c10::optional<Tensor> &background,
+                                     at::ArrayRef<double> light, int64_t H, int64_t W, int64_t mode, double scale,
+                                     double znear, double zfar) {
+  mesh_render_check(verts, cam, trans, faces, face_part, vcol, background, light, H, W, mode, !vcol.has_value());
+  return mesh_render_outputs(verts, H, W);
+}
+
 int64_t abi_version() { return smplr_abi_version(); }
 #ifndef SMPLR_TORCH_OPS_ID
 #define SMPLR_TORCH_OPS_ID "unknown"
@@ -415,6 +508,9 @@ TORCH_LIBRARY(smplraster, m) {
   m.def("decoder_fwd(Tensor x, Tensor[] consts, Tensor part_pos, Tensor part_off, int W, int grid_wh=64, "
         "bool ref_compat=True, int num_cam=4) -> Tensor[]");
   m.def("seg_confusion(Tensor scores, Tensor labels, Tensor(a!) conf) -> ()");
+  m.def("mesh_render(Tensor verts, Tensor cam, Tensor? trans, Tensor faces, Tensor? face_part, Tensor? vf_off, "
+        "Tensor? vf_face, Tensor? vcol, Tensor? background, float[] light, int H, int W, int mode=0, float scale=1.0, "
+        "float near=0.0, float far=1e30) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch key is named CUDA in torch)
@@ -429,6 +525,7 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("smpl_bwd", &smpl_bwd);
   m.impl("decoder_fwd", &decoder_fwd);
   m.impl("seg_confusion", &seg_confusion);
+  m.impl("mesh_render", &mesh_render);
 }
 
 TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
@@ -443,4 +540,5 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("smpl_bwd", &smpl_bwd_meta);
   m.impl("decoder_fwd", &decoder_fwd_meta);
   m.impl("seg_confusion", &seg_confusion_meta);
+  m.impl("mesh_render", &mesh_render_meta);
 }

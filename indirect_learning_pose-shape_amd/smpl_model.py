@@ -44,6 +44,7 @@ class SMPLModelData:
     weights: np.ndarray             # (V,24)
     parents: np.ndarray = field(default_factory=lambda: SMPL_PARENTS.copy())
     cocoplus_regressor: Optional[np.ndarray] = None   # (19,V), unused by the hot path
+    faces: Optional[np.ndarray] = None                # (F,3) int32, the pkl's `f` (render.py); None: no topology
 
     @property
     def num_verts(self) -> int:
@@ -66,6 +67,12 @@ class SMPLModelData:
         for i in range(1, NUM_JOINTS):
             if not (0 <= int(self.parents[i]) < i):
                 raise ValueError("parents must be topologically ordered (parent[i] < i)")
+        if self.faces is not None:
+            f = np.asarray(self.faces)
+            if f.ndim != 2 or f.shape[1] != 3 or not np.issubdtype(f.dtype, np.integer):
+                raise ValueError("faces must be (F,3) integers")
+            if f.size and (int(f.min()) < 0 or int(f.max()) >= V):
+                raise ValueError("faces must index vertices in [0, V)")
 
 
 # Rest-pose joint centres of a 1.7 m body, y up, origin near the chest (metres).

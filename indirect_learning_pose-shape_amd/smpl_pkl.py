@@ -74,12 +74,21 @@ def _arr(v):
 
 
 def load_smpl_pkl(path: str) -> SMPLModelData:
-    """Fields used by `SMPLLayer.build` (`batch_smpl.py:38-87`)."""
+    """Fields used by `SMPLLayer.build` (`batch_smpl.py:38-87`), and the faces `f` (F, 3) for render.py when present."""
     with open(path, "rb") as f:
         dd = _Restricted(f, encoding="latin1").load()
     parents = np.asarray(dd["kintree_table"])[0].astype(np.int64)
     parents = np.where(parents > 1000, -1, parents).astype(np.int32)    # root: uint32 max (:71)
     coco = dd.get("cocoplus_regressor")
+    f = dd.get("f")
+    if f is not None:
+        f = np.asarray(f)
+        if not np.issubdtype(f.dtype, np.integer) and not (f.size and np.array_equal(f, np.round(f))):
+            raise ValueError("SMPL pkl: 'f' must hold integer vertex indices")
+        f = f.astype(np.int64)
+        if f.size and (f.min() < 0 or f.max() > np.iinfo(np.int32).max):
+            raise ValueError("SMPL pkl: 'f' holds vertex indices outside int32")
+        f = f.astype(np.int32)
     m = SMPLModelData(
         v_template=_arr(dd["v_template"]).astype(np.float64),
         shapedirs=_arr(dd["shapedirs"]).astype(np.float64)[..., :10],
@@ -87,6 +96,7 @@ def load_smpl_pkl(path: str) -> SMPLModelData:
         J_regressor=_arr(dd["J_regressor"]).astype(np.float64),
         weights=_arr(dd["weights"]).astype(np.float64),
         parents=parents,
-        cocoplus_regressor=_arr(coco).astype(np.float64) if coco is not None else None)
+        cocoplus_regressor=_arr(coco).astype(np.float64) if coco is not None else None,
+        faces=f)
     m.validate()
     return m

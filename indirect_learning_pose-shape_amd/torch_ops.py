@@ -39,6 +39,9 @@ SCHEMAS = {
     "decoder_fwd": ("smplraster::decoder_fwd(Tensor x, Tensor[] consts, Tensor part_pos, Tensor part_off, int W, "
                     "int grid_wh=64, bool ref_compat=True, int num_cam=4) -> Tensor[]"),
     "seg_confusion": "smplraster::seg_confusion(Tensor scores, Tensor labels, Tensor(a!) conf) -> ()",
+    "mesh_render": ("smplraster::mesh_render(Tensor verts, Tensor cam, Tensor? trans, Tensor faces, Tensor? face_part, "
+                    "Tensor? vf_off, Tensor? vf_face, Tensor? vcol, Tensor? background, float[] light, int H, int W, "
+                    "int mode=0, float scale=1., float near=0., float far=1e+30) -> Tensor[]"),
 }
 
 _ns = None
