@@ -385,6 +385,32 @@ int smplr_mesh_raster(const void *vbuf, const int32_t *faces, const uint8_t *fac
                       int W, int mode, const float *bg, int32_t *face, float *depth, uint8_t *part, uint8_t *alpha,
                       float *rgb, void *stream);
 
+/* ---- data generator: train.py:96-143 (Keras ImageDataGenerator + flow_from_directory), INTEGRATION.md 4d -----------
+ * One affine warp per sample out of a resident uint8 pool, written in the forms the train step consumes.
+ *   pool   (N, Hs, Ws, C) uint8, NHWC; C = 3 or 1 for images, 1 for label maps.
+ *   mat    (B, 2, 3) fp32, output -> input in (row, column) index space: output pixel (r, c) of the H x W output reads
+ *          sr = (m00 r + m01 c) + m02, sc = (m10 r + m11 c) + m12, fp32 in that order, no FMA contraction.
+ *   index  (B) int32 (index_i64 = 0) or int64 (index_i64 != 0) rows of the pool, or NULL for 0..B-1 (B > N then
+ *          repeats row N - 1); a value outside [0, N) is clamped inside the kernel.
+ *   mode   SMPLR_WARP_IMAGE_NEAREST   out (B, C, H, W) fp32 = float(texel) * rescale, texel (ir, ic) =
+ *                                     clamp(floor(s + 0.5), 0, size - 1) per axis (fill_mode='nearest', order 0)
+ *          SMPLR_WARP_IMAGE_BILINEAR  the same output from the four neighbours of (clamp(sr, 0, H - 1),
+ *                                     clamp(sc, 0, W - 1)); needs Hs = H and Ws = W
+ *          SMPLR_WARP_LABEL           out (B, H, W) int32 = the nearest texel, unchanged (rescale unused)
+ *          SMPLR_WARP_LABEL_BINARY    out (B, H, W) int32 = texel > 0
+ *   A NaN coordinate counts as 0 and infinities clamp, in floating point, before any integer is formed: no matrix makes
+ *   the kernel read outside its plane.  A pool stored at another size than the output is read through PIL's NEAREST
+ *   resize: grid index i of n -> stored index ((2 i + 1) S) / (2 n).
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= H, W <= 4096; 1 <= Hs, Ws <= 8192; N >= 1; B >= 0 (B = 0 is
+ * a no-op); C as above; the launch has B * ceil(H * W / 1024) workgroups (/ 256 when W % 4 != 0 or out is not 16-byte
+ * aligned), fewer than 2^31. */
+#define SMPLR_WARP_IMAGE_NEAREST 0
+#define SMPLR_WARP_IMAGE_BILINEAR 1
+#define SMPLR_WARP_LABEL 2
+#define SMPLR_WARP_LABEL_BINARY 3
+int smplr_affine_warp(const uint8_t *pool, int N, int Hs, int Ws, int C, const float *mat, const void *index,
+                      int index_i64, int B, int H, int W, int mode, float rescale, void *out, void *stream);
+
 /* ---- projects_to_silhouette: keras_smpl/projects_to_silhouette.py:14-44 ----------------- */
 /* silh (B,W,W,2) = [1-s, s], s = max_v exp(-|proj_v-(c,r)|/1.2) over ALL VP vertices, rows
  * flipped; arg (B,W,W) int32 = maximising vertex.  workspace: smplr_silh_workspace(B,VP,W) B.  */

@@ -20,4 +20,8 @@ def __getattr__(name):
         mod = {"orthographic_project": "projection", "set_cam_params": "set_cam_params",
                "load_mean_set_cam_params": "set_cam_params"}.get(name, name)
         return getattr(importlib.import_module(__name__ + ".keras_smpl." + mod), name)
+    if name in ("ImageDataGenerator", "DeviceBatches", "BatchIndexer", "affine_matrices", "random_draws", "warp_images",
+                "warp_labels"):
+        from . import augment
+        return getattr(augment, name)
     raise AttributeError(name)

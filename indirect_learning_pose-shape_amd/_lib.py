@@ -81,6 +81,7 @@ SIGNATURES = {
     "smplr_mesh_vertex": (c_int, [P, P, P, I, I, I, c_float, I, I, c_float, c_float, I, P, I, P, P, I, P, I, P, c_longlong,
                                   P, P]),
     "smplr_mesh_raster": (c_int, [P, P, P, I, I, I, I, I, I, P, P, P, P, P, P, P]),
+    "smplr_affine_warp": (c_int, [P, I, I, I, I, P, P, I, I, I, I, I, c_float, P, P]),
     "smplr_silh_workspace": (c_size_t, [I, I, I]),
     "smplr_silh_fwd": (c_int, [P, I, I, I, P, P, P, P]),
     "smplr_silh_fwd_hint": (c_int, [P, P, I, I, I, P, P, P, P]),

@@ -482,6 +482,58 @@ std::vector<Tensor> mesh_render_meta(const Tensor &verts, const Tensor &cam, con
   return mesh_render_outputs(verts, H, W);
 }
 
+// ---- data generator (train.py:96-143): pool (N, Hs, Ws[, C]) uint8 + matrices (B, 2, 3) -> out, in place ---------------
+// mode 0 / 1: images, nearest / bilinear, out (B, C, H, W) fp32 = texel * rescale; mode 2 / 3: labels / labels > 0, out
+// (B, H, W) int32.  index (B,) int32 / int64 rows of the pool (None: 0..B-1); its VALUES are clamped by the kernel, not
+// read here (that would be a host synchronisation).
+void affine_warp_check(const Tensor &pool, const Tensor &matrices, const c10::optional<Tensor> &index, const Tensor &out,
+                       int64_t mode) {
+  TORCH_CHECK(mode >= 0 && mode <= 3, "mode must be 0 (image nearest), 1 (image bilinear), 2 (label) or 3 (binary label)");
+  TORCH_CHECK(pool.scalar_type() == at::kByte, "pool must be uint8");
+  TORCH_CHECK(pool.dim() == 3 || pool.dim() == 4, "pool must be (N, Hs, Ws) or (N, Hs, Ws, C)");
+  const int64_t C = pool.dim() == 4 ? pool.size(3) : 1;
+  const bool label = mode >= 2;
+  TORCH_CHECK(label ? C == 1 : (C == 1 || C == 3), "pool has ", C, " channels (images 1 or 3, labels 1)");
+  TORCH_CHECK(pool.size(0) >= 1 && pool.size(0) <= INT32_MAX, "pool must hold 1..2^31-1 samples");
+  TORCH_CHECK(pool.size(1) >= 1 && pool.size(1) <= 8192 && pool.size(2) >= 1 && pool.size(2) <= 8192,
+              "pool planes must be 1..8192 on a side");
+  TORCH_CHECK(out.dim() == (label ? 3 : 4), "out must be ", label ? "(B, H, W)" : "(B, C, H, W)");
+  TORCH_CHECK(out.scalar_type() == (label ? at::kInt : at::kFloat), "out must be ", label ? "int32" : "float32");
+  TORCH_CHECK(label || out.size(1) == C, "out has ", out.size(1), " channels, the pool ", C);
+  const int64_t B = out.size(0), H = out.size(-2), W = out.size(-1);
+  TORCH_CHECK(H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "H and W of out must be in 1..4096");
+  TORCH_CHECK(B <= INT32_MAX, "out holds too many samples");
+  TORCH_CHECK(matrices.dim() == 3 && matrices.size(0) == B && matrices.size(1) == 2 && matrices.size(2) == 3,
+              "matrices must be (B, 2, 3) with B = out.size(0) = ", B);
+  TORCH_CHECK(matrices.scalar_type() == at::kFloat, "matrices must be float32");
+  TORCH_CHECK(!index || (index->dim() == 1 && index->size(0) == B &&
+                         (index->scalar_type() == at::kInt || index->scalar_type() == at::kLong)),
+              "index must be (B,) int32 or int64");
+  TORCH_CHECK(mode != 1 || (pool.size(1) == H && pool.size(2) == W), "bilinear needs pool size = output size");
+}
+void affine_warp(const Tensor &pool, const Tensor &matrices, const c10::optional<Tensor> &index, Tensor &out, int64_t mode,
+                 double rescale) {
+  affine_warp_check(pool, matrices, index, out, mode);
+  dev_typed(out, mode >= 2 ? at::kInt : at::kFloat, "out");
+  dev_typed(pool, at::kByte, "pool");
+  dev_f32(matrices, "matrices");
+  if (index) dev_typed(*index, index->scalar_type(), "index");
+  const Tensor none;
+  same_device(out, {{"pool", &pool}, {"matrices", &matrices}, {"index", index ? &*index : &none}});
+  DeviceGuard g(out.device());
+  if (out.size(0) == 0) return;
+  ok(smplr_affine_warp(pool.data_ptr<uint8_t>(), (int)pool.size(0), (int)pool.size(1), (int)pool.size(2),
+                       pool.dim() == 4 ? (int)pool.size(3) : 1, matrices.data_ptr<float>(),
+                       index ? index->data_ptr() : nullptr, index && index->scalar_type() == at::kLong ? 1 : 0,
+                       (int)out.size(0), (int)out.size(-2), (int)out.size(-1), (int)mode, (float)rescale, out.data_ptr(),
+                       cur_stream()),
+     "smplr_affine_warp");
+}
+void affine_warp_meta(const Tensor &pool, const Tensor &matrices, const c10::optional<Tensor> &index, Tensor &out,
+                      int64_t mode, double rescale) {
+  affine_warp_check(pool, matrices, index, out, mode);
+}
+
 int64_t abi_version() { return smplr_abi_version(); }
 #ifndef SMPLR_TORCH_OPS_ID
 #define SMPLR_TORCH_OPS_ID "unknown"
@@ -511,6 +563,7 @@ TORCH_LIBRARY(smplraster, m) {
   m.def("mesh_render(Tensor verts, Tensor cam, Tensor? trans, Tensor faces, Tensor? face_part, Tensor? vf_off, "
         "Tensor? vf_face, Tensor? vcol, Tensor? background, float[] light, int H, int W, int mode=0, float scale=1.0, "
         "float near=0.0, float far=1e30) -> Tensor[]");
+  m.def("affine_warp(Tensor pool, Tensor matrices, Tensor? index, Tensor(a!) out, int mode=0, float rescale=1.0) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch key is named CUDA in torch)
@@ -526,6 +579,7 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("decoder_fwd", &decoder_fwd);
   m.impl("seg_confusion", &seg_confusion);
   m.impl("mesh_render", &mesh_render);
+  m.impl("affine_warp", &affine_warp);
 }
 
 TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
@@ -541,4 +595,5 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("decoder_fwd", &decoder_fwd_meta);
   m.impl("seg_confusion", &seg_confusion_meta);
   m.impl("mesh_render", &mesh_render_meta);
+  m.impl("affine_warp", &affine_warp_meta);
 }

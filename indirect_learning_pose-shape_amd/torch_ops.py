@@ -42,6 +42,8 @@ SCHEMAS = {
     "mesh_render": ("smplraster::mesh_render(Tensor verts, Tensor cam, Tensor? trans, Tensor faces, Tensor? face_part, "
                     "Tensor? vf_off, Tensor? vf_face, Tensor? vcol, Tensor? background, float[] light, int H, int W, "
                     "int mode=0, float scale=1., float near=0., float far=1e+30) -> Tensor[]"),
+    "affine_warp": ("smplraster::affine_warp(Tensor pool, Tensor matrices, Tensor? index, Tensor(a!) out, int mode=0, "
+                    "float rescale=1.) -> ()"),
 }
 
 _ns = None

@@ -202,7 +202,8 @@ def fit(trainer, batches, trials, steps_per_trial, save_dir=None, save_every=10,
         on_trial_end=None, metrics=None):
     """The loop of train.py:221-315: `trials` rounds of `steps_per_trial` optimiser steps (`fit_generator(...,
     steps_per_epoch, nb_epoch=1)`) over `batches` - an iterator of (images, labels[, silhouette labels]) already
-    on the device, the data generators being the caller's - and every `save_every` trials (on rank 0) the monitor
+    on the device, the data generators being the caller's (`augment.DeviceBatches` is the reference's
+    `ImageDataGenerator` pair over a uint8 pool on the device and plugs in here unchanged) - and every `save_every` trials (on rank 0) the monitor
     hook `on_trial_end(trial, trainer)` (use `trainer.monitor(images)` for verts / projects / seg: the train decoder
     `trainer.decoder` writes losses only) and a checkpoint named like the reference's.  -> list of per-trial mean losses (python floats; the one
     host sync per trial).  metrics: what `step` takes (a SegConfusion, or a (seg, silhouette) pair), handed to every
