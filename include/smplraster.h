@@ -411,6 +411,47 @@ int smplr_mesh_raster(const void *vbuf, const int32_t *faces, const uint8_t *fac
 int smplr_affine_warp(const uint8_t *pool, int N, int Hs, int Ws, int C, const float *mat, const void *index,
                       int index_i64, int B, int H, int W, int mode, float rescale, void *out, void *stream);
 
+/* ---- input preprocessing: load_input_img / load_input_seg (predict.py:17-25, evaluate.py:13-19,96-100,
+ * predict_autoencoder.py:17-24), preprocessing.pad_image, predict_realtime.py:52-58; INTEGRATION.md 4e ----------------
+ * Ragged uint8 images or masks -> zero padding (pad_image) -> resize, written in the forms the network and the metrics
+ * consume.  One launch; never allocates or synchronises.
+ *   data   one flat uint8 device buffer of data_bytes bytes (1..2^48) that holds every image, pixels HWC with C
+ *          channels (3 or 1 for images, 1 for label maps).
+ *   desc   (N, 4) int64 on the device, per image: byte offset of the view's first pixel, row pitch in bytes, height h,
+ *          width w (1..8192).  A crop is another row: larger offset, smaller w, same pitch.
+ *   index  (B) int32 (index_i64 = 0) or int64 rows of desc, or NULL for 0..B-1 (B > N then repeats row N - 1); a value
+ *          outside [0, N) is clamped inside the kernel.
+ *   mode   SMPLR_RESIZE_IMAGE_BILINEAR  out (B, C, H, W) fp32.  Output column i of W over a padded width S reads the
+ *                                       padded columns s, min(s + 1, S - 1) with weights (d - r) / d, r / d, where
+ *                                       n = (2 i + 1) S - W, d = 2 W, s = floor(n / d), r = n - s d (n < 0: s = r = 0;
+ *                                       s >= S - 1: s = S - 1, r = 0); rows alike.  num / D is the exact bilinear
+ *                                       sum over D = 2 W * 2 H.  With SMPLR_RESIZE_QUANTIZE the value is
+ *                                       float(floor((2 num + D) / (2 D))) * rescale, the quotient exact (what resizing a
+ *                                       uint8 image gives: round half up); without it (float(num) / float(D)) * rescale.
+ *          SMPLR_RESIZE_IMAGE_NEAREST   out (B, C, H, W) fp32 = float(texel) * rescale, texel at padded index
+ *                                       min((i S) / W, S - 1) per axis, or ((2 i + 1) S) / (2 W) with SMPLR_RESIZE_PIL
+ *          SMPLR_RESIZE_LABEL           out (B, H, W) int32 = that texel, unchanged (rescale unused)
+ *          SMPLR_RESIZE_LABEL_BINARY    out (B, H, W) int32 = texel > 0
+ *   flags  SMPLR_RESIZE_PAD: the padded plane is pad_image's - w < h: b = (h - w) / 2 zero columns on either side, else
+ *          b = (w - h) / 2 zero rows above and below (an odd difference leaves the plane one short of square); without
+ *          it the padded plane is the image.  Padding texels are 0 and take part in the interpolation.
+ *          SMPLR_RESIZE_SWAP_RB: output channel c reads source channel 2 - c (C = 3).
+ *   A row of desc is checked inside the kernel before anything is read through it: offset >= 0, sides 1..8192,
+ *   pitch >= w C, offset + (h - 1) pitch + w C <= data_bytes.  A sample whose row fails is written as zeros.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= H, W <= 4096; N >= 1; B >= 0 (B = 0 is a no-op); C, mode and
+ * flags as above; the launch has B * ceil(H * W / 1024) workgroups (/ 256 when W % 4 != 0 or out is not 16-byte
+ * aligned), fewer than 2^31. */
+#define SMPLR_RESIZE_IMAGE_BILINEAR 0
+#define SMPLR_RESIZE_IMAGE_NEAREST 1
+#define SMPLR_RESIZE_LABEL 2
+#define SMPLR_RESIZE_LABEL_BINARY 3
+#define SMPLR_RESIZE_PAD 1
+#define SMPLR_RESIZE_SWAP_RB 2
+#define SMPLR_RESIZE_QUANTIZE 4
+#define SMPLR_RESIZE_PIL 8
+int smplr_resize_pad(const uint8_t *data, long long data_bytes, const long long *desc, int N, int C, const void *index,
+                     int index_i64, int B, int H, int W, int mode, int flags, float rescale, void *out, void *stream);
+
 /* ---- projects_to_silhouette: keras_smpl/projects_to_silhouette.py:14-44 ----------------- */
 /* silh (B,W,W,2) = [1-s, s], s = max_v exp(-|proj_v-(c,r)|/1.2) over ALL VP vertices, rows
  * flipped; arg (B,W,W) int32 = maximising vertex.  workspace: smplr_silh_workspace(B,VP,W) B.  */

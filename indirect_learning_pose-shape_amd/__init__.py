@@ -24,4 +24,7 @@ def __getattr__(name):
                 "warp_labels"):
         from . import augment
         return getattr(augment, name)
+    if name in ("RaggedImages", "EvalBatches", "load_images", "load_labels", "pad_geometry"):
+        from . import preprocess
+        return getattr(preprocess, name)
     raise AttributeError(name)

@@ -534,6 +534,53 @@ void affine_warp_meta(const Tensor &pool, const Tensor &matrices, const c10::opt
   affine_warp_check(pool, matrices, index, out, mode);
 }
 
+// ---- input preprocessing (predict.py:17-25, evaluate.py:13-19,96-100): data (bytes) uint8 + desc (N, 4) int64 -> out, in place --
+// mode 0 / 1: images, bilinear / nearest, out (B, C, H, W) fp32; mode 2 / 3: labels / labels > 0, out (B, H, W) int32.
+// flags: 1 pad, 2 swap_rb, 4 quantize, 8 pil rule.  desc rows (byte offset, pitch, h, w) and the VALUES of index are
+// checked / clamped by the kernel, not read here (that would be a host synchronisation).
+void resize_pad_check(const Tensor &data, const Tensor &desc, const c10::optional<Tensor> &index, const Tensor &out,
+                      int64_t channels, int64_t mode, int64_t flags) {
+  TORCH_CHECK(mode >= 0 && mode <= 3, "mode must be 0 (image bilinear), 1 (image nearest), 2 (label) or 3 (binary label)");
+  TORCH_CHECK(flags >= 0 && flags <= 15, "flags must be a sum of 1 (pad), 2 (swap_rb), 4 (quantize), 8 (pil rule)");
+  TORCH_CHECK(data.scalar_type() == at::kByte, "data must be uint8");
+  TORCH_CHECK(data.numel() >= 1, "data must hold at least one byte");
+  const bool label = mode >= 2;
+  TORCH_CHECK(label ? channels == 1 : (channels == 1 || channels == 3), "channels = ", channels, " (images 1 or 3, labels 1)");
+  TORCH_CHECK(desc.scalar_type() == at::kLong, "desc must be int64");
+  TORCH_CHECK(desc.dim() == 2 && desc.size(1) == 4 && desc.size(0) >= 1 && desc.size(0) <= INT32_MAX,
+              "desc must be (N, 4) with N >= 1: byte offset, pitch, height, width per image");
+  TORCH_CHECK(out.dim() == (label ? 3 : 4), "out must be ", label ? "(B, H, W)" : "(B, C, H, W)");
+  TORCH_CHECK(out.scalar_type() == (label ? at::kInt : at::kFloat), "out must be ", label ? "int32" : "float32");
+  TORCH_CHECK(label || out.size(1) == channels, "out has ", out.size(1), " channels, the call names ", channels);
+  const int64_t B = out.size(0), H = out.size(-2), W = out.size(-1);
+  TORCH_CHECK(H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "H and W of out must be in 1..4096");
+  TORCH_CHECK(B <= INT32_MAX, "out holds too many samples");
+  TORCH_CHECK(!index || (index->dim() == 1 && index->size(0) == B &&
+                         (index->scalar_type() == at::kInt || index->scalar_type() == at::kLong)),
+              "index must be (B,) int32 or int64 with B = out.size(0) = ", B);
+}
+void resize_pad(const Tensor &data, const Tensor &desc, const c10::optional<Tensor> &index, Tensor &out, int64_t channels,
+                int64_t mode, int64_t flags, double rescale) {
+  resize_pad_check(data, desc, index, out, channels, mode, flags);
+  dev_typed(out, mode >= 2 ? at::kInt : at::kFloat, "out");
+  dev_typed(data, at::kByte, "data");
+  dev_typed(desc, at::kLong, "desc");
+  if (index) dev_typed(*index, index->scalar_type(), "index");
+  const Tensor none;
+  same_device(out, {{"data", &data}, {"desc", &desc}, {"index", index ? &*index : &none}});
+  DeviceGuard g(out.device());
+  if (out.size(0) == 0) return;
+  ok(smplr_resize_pad(data.data_ptr<uint8_t>(), (long long)data.numel(), reinterpret_cast<const long long *>(desc.data_ptr<int64_t>()),
+                      (int)desc.size(0), (int)channels, index ? index->data_ptr() : nullptr,
+                      index && index->scalar_type() == at::kLong ? 1 : 0, (int)out.size(0), (int)out.size(-2),
+                      (int)out.size(-1), (int)mode, (int)flags, (float)rescale, out.data_ptr(), cur_stream()),
+     "smplr_resize_pad");
+}
+void resize_pad_meta(const Tensor &data, const Tensor &desc, const c10::optional<Tensor> &index, Tensor &out, int64_t channels,
+                     int64_t mode, int64_t flags, double rescale) {
+  resize_pad_check(data, desc, index, out, channels, mode, flags);
+}
+
 int64_t abi_version() { return smplr_abi_version(); }
 #ifndef SMPLR_TORCH_OPS_ID
 #define SMPLR_TORCH_OPS_ID "unknown"
@@ -564,6 +611,8 @@ TORCH_LIBRARY(smplraster, m) {
         "Tensor? vf_face, Tensor? vcol, Tensor? background, float[] light, int H, int W, int mode=0, float scale=1.0, "
         "float near=0.0, float far=1e30) -> Tensor[]");
   m.def("affine_warp(Tensor pool, Tensor matrices, Tensor? index, Tensor(a!) out, int mode=0, float rescale=1.0) -> ()");
+  m.def("resize_pad(Tensor data, Tensor desc, Tensor? index, Tensor(a!) out, int channels, int mode=0, int flags=4, "
+        "float rescale=1.0) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch key is named CUDA in torch)
@@ -580,6 +629,7 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("seg_confusion", &seg_confusion);
   m.impl("mesh_render", &mesh_render);
   m.impl("affine_warp", &affine_warp);
+  m.impl("resize_pad", &resize_pad);
 }
 
 TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
@@ -596,4 +646,5 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("seg_confusion", &seg_confusion_meta);
   m.impl("mesh_render", &mesh_render_meta);
   m.impl("affine_warp", &affine_warp_meta);
+  m.impl("resize_pad", &resize_pad_meta);
 }

@@ -1,4 +1,4 @@
-"""Evaluation of the reference (`evaluate.py:59-127`, `evaluate_autoencoder.py:23-117`) without its file, `cv2` and
+"""Evaluation of the reference (`evaluate.py:59-127`, `evaluate_autoencoder.py:23-117`, `evaluate3d.py:32-65`) without its file, `cv2` and
 printing I/O: per-part IoU over classes 1..31 and pixel accuracy of the arg-max part map against ground-truth maps, in the
 style of `inference.predict_batch`.  With a decoder built with a fused loss (`SMPLDecoder(..., loss=softmax_focal_loss(..))`)
 the counting runs inside the rasteriser's loss epilogue and the (N, W, W, 32) scores are never written; a decoder without
@@ -31,3 +31,27 @@ def evaluate_iou_and_acc(smpl_model, decoder, batches, num_classes=32):
         raise ValueError("evaluate_iou_and_acc: no batches")
     return {"ious": m.iou(), "mean_iou": m.mean_iou(), "accuracy": m.pixel_accuracy(), "counts": m.counts,
             "intersections": m.intersections(), "unions": m.unions(), "correct": m.correct(), "total": m.total()}
+
+
+@torch.no_grad()
+def evaluate_pose_param_mse(smpl_model, batches):
+    """`evaluate3d.py:32-65`: batches: an iterable of (images, gt_pose (N, 72) axis-angle pose parameters) on the model's
+    device.  -> the mean of (gt_pose[:, 3:] - smpl[:, 7:76])^2 over all samples and the 69 parameters without the global
+    rotation, as a float (accumulated in float64)."""
+    total, count = None, 0
+    was_training = smpl_model.training
+    smpl_model.eval()
+    try:
+        for images, gt_pose in batches:
+            smpl = smpl_model(images)
+            gt = torch.as_tensor(gt_pose, device=smpl.device)
+            if gt.dim() != 2 or gt.shape[1] != 72 or gt.shape[0] != smpl.shape[0]:
+                raise ValueError("gt_pose must be (N, 72) with N = the batch's images")
+            err = (gt[:, 3:].to(torch.float64) - smpl[:, 7:76].to(torch.float64)).square().sum()
+            total = err if total is None else total + err
+            count += int(smpl.shape[0]) * 69
+    finally:
+        smpl_model.train(was_training)
+    if total is None:
+        raise ValueError("evaluate_pose_param_mse: no batches")
+    return float(total) / count

@@ -26,7 +26,9 @@ class GraphedPredictor:
     """`predict_batch` for a fixed image shape replayed from ONE captured HIP graph: at batch 1 the eager forward
     is bound by ~500 host-side kernel launches (6.7 ms per image), the graph by the kernels themselves.
     `predictor(images)` copies the images into the static input and returns views of the static outputs
-    (valid until the next call)."""
+    (valid until the next call).  `predictor.input` is that static input: whatever writes into it in place
+    (`preprocess.load_images(frame, 256, ..., out=predictor.input)`) followed by `predictor.replay()` is the per-frame
+    path of predict_realtime.py:52-64 without the copy."""
 
     def __init__(self, smpl_model, decoder, example_images, warmup=3):
         self.smpl_model, self.decoder = smpl_model, decoder
@@ -46,6 +48,16 @@ class GraphedPredictor:
                 self._out = predict_batch(smpl_model, decoder, self._in)
         finally:
             smpl_model.train(was_training)
+
+    @property
+    def input(self):
+        """The captured graph's static input tensor, shaped as the example images."""
+        return self._in
+
+    def replay(self):
+        """Replay the graph on what `input` holds now -> the static outputs (valid until the next replay)."""
+        self._graph.replay()
+        return self._out
 
     def __call__(self, images):
         if images.shape != self._in.shape:

@@ -44,6 +44,8 @@ SCHEMAS = {
                     "int mode=0, float scale=1., float near=0., float far=1e+30) -> Tensor[]"),
     "affine_warp": ("smplraster::affine_warp(Tensor pool, Tensor matrices, Tensor? index, Tensor(a!) out, int mode=0, "
                     "float rescale=1.) -> ()"),
+    "resize_pad": ("smplraster::resize_pad(Tensor data, Tensor desc, Tensor? index, Tensor(a!) out, int channels, "
+                   "int mode=0, int flags=4, float rescale=1.) -> ()"),
 }
 
 _ns = None
