@@ -452,6 +452,39 @@ int smplr_affine_warp(const uint8_t *pool, int N, int Hs, int Ws, int C, const f
 int smplr_resize_pad(const uint8_t *data, long long data_bytes, const long long *desc, int N, int C, const void *index,
                      int index_i64, int B, int H, int W, int mode, int flags, float rescale, void *out, void *stream);
 
+/* ---- 3D evaluation: per-vertex error, MPJPE, scale-corrected and Procrustes-aligned error (the figures evaluate3d.py:32-65
+ * stops short of: it reports a mean squared error over 69 pose parameters); INTEGRATION.md 4f -------------------------
+ * pred, gt (B, N, 3) fp32, contiguous: two point sets per mesh (vertices, or joints), in metres.  One launch computes each
+ * mesh's per-point Euclidean errors |a(p_i) - g_i| under four alignments a of pred to gt, and their means over the N points:
+ *   mode 0 none         a(p) = p
+ *   mode 1 translation  both sets minus their centroids - or, with root >= 0, minus their own point `root` (root-relative)
+ *   mode 2 scale        centroids removed, then a(pc) = s pc with s = sum pc.gc / sum |pc|^2
+ *   mode 3 similarity   a(p) = s R p + t, the least-squares similarity: M = sum gc pc^T = U S V^T, d = det(U) det(V),
+ *                       R = U diag(1, 1, d) V^T (always a rotation), s = (S1 + S2 + d S3) / sum |pc|^2, t = mean(g) - s R mean(p)
+ *   mean_err  (B, 4) fp32, required: the four means.
+ *   transform (B, 13) fp32 or NULL: s, R row-major (9), t (3) of mode 3.
+ *   per_point (B, N) fp32 or NULL: the per-point errors of mode pp_mode (0..3).
+ *   status    (B) int32 or NULL: SMPLR_PE_DEGENERATE - sum |pc|^2 == 0 or N == 1: modes 2 and 3 fell back to translation
+ *             (s = 1, R = I); SMPLR_PE_NONFINITE - a NaN or Inf in the mesh, or an error beyond fp32: the mesh's means (and
+ *             per-point errors, transform) are NaN; SMPLR_PE_RANK_DEFICIENT - collinear or coincident points
+ *             (S2 <= 1e-5 S1: a second direction within the rounding of fp32 coordinates up to 10 m out): R is a rotation
+ *             and the error minimal, but R is one of many.  Other meshes of the batch are not affected.
+ * Moments are centred and summed in fp64 in a fixed order, without atomics: a mesh's outputs are the same bits in every run
+ * and for every batch it is part of.  Coordinates are meant to stay within ~10 m of the origin (fp32 inputs: beyond that
+ * the inputs themselves lose the 1e-4 m the project holds vertices to).  No workspace, no allocation, no synchronisation.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): N >= 1, B >= 0 (B = 0 is a no-op), B * N <= 2^31 / 3, root in
+ * [-1, N) (-1: the centroid), pp_mode in 0..3, pred / gt / mean_err not NULL.  N <= 64 runs a wave per mesh (four meshes per
+ * workgroup), larger N a workgroup per mesh; up to 7 168 points the sets stay in registers between the passes. */
+#define SMPLR_PE_NONE 0
+#define SMPLR_PE_TRANSLATION 1
+#define SMPLR_PE_SCALE 2
+#define SMPLR_PE_SIMILARITY 3
+#define SMPLR_PE_DEGENERATE 1
+#define SMPLR_PE_NONFINITE 2
+#define SMPLR_PE_RANK_DEFICIENT 4
+int smplr_point_errors(const float *pred, const float *gt, int B, int N, int root, int pp_mode, float *mean_err,
+                       float *transform, float *per_point, int32_t *status, void *stream);
+
 /* ---- projects_to_silhouette: keras_smpl/projects_to_silhouette.py:14-44 ----------------- */
 /* silh (B,W,W,2) = [1-s, s], s = max_v exp(-|proj_v-(c,r)|/1.2) over ALL VP vertices, rows
  * flipped; arg (B,W,W) int32 = maximising vertex.  workspace: smplr_silh_workspace(B,VP,W) B.  */

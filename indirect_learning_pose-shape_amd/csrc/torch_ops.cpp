@@ -581,6 +581,45 @@ void resize_pad_meta(const Tensor &data, const Tensor &desc, const c10::optional
   resize_pad_check(data, desc, index, out, channels, mode, flags);
 }
 
+// ---- 3D evaluation (the figures evaluate3d.py:32-65 stops short of): pred, gt (B, N, 3) -> [mean_err (B, 4), status (B) int32,
+// per_point (B, N) or (0), transform (B, 13) or (0)] --------------------------------------------------------------------
+// Modes 0 none, 1 translation (centroid, or the point `root` of each set when root >= 0), 2 scale, 3 similarity (Procrustes).
+// per_point_mode -1: no per-point errors; transform: s, R row-major, t of mode 3.
+void point_errors_check(const Tensor &pred, const Tensor &gt, int64_t root, int64_t pp_mode) {
+  TORCH_CHECK(pred.dim() == 3 && pred.size(2) == 3, "pred must be (B, N, 3)");
+  TORCH_CHECK(gt.dim() == 3 && gt.sizes() == pred.sizes(), "gt must have pred's shape (B, N, 3)");
+  TORCH_CHECK(pred.scalar_type() == at::kFloat && gt.scalar_type() == at::kFloat, "pred and gt must be float32");
+  const int64_t B = pred.size(0), N = pred.size(1);
+  TORCH_CHECK(N >= 1, "point sets must hold at least one point");
+  TORCH_CHECK(B * N <= (int64_t(1) << 31) / 3, "B * N = ", B * N, " points exceed 2^31 / 3");
+  TORCH_CHECK(root >= -1 && root < N, "root = ", root, " outside [0, ", N, ") (-1: the centroid)");
+  TORCH_CHECK(pp_mode >= -1 && pp_mode <= 3, "per_point_mode must be -1 (none) or 0..3");
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> point_errors(const Tensor &pred, const Tensor &gt, int64_t root, int64_t pp_mode,
+                                                        bool transform) {
+  point_errors_check(pred, gt, root, pp_mode);
+  dev_f32(pred, "pred");
+  dev_f32(gt, "gt");
+  same_device(pred, {{"gt", &gt}});
+  DeviceGuard g(pred.device());
+  const int64_t B = pred.size(0), N = pred.size(1);
+  Tensor mean = f32({B, 4}, pred), status = at::empty({B}, pred.options().dtype(at::kInt));
+  Tensor pp = f32({pp_mode >= 0 ? B : 0, pp_mode >= 0 ? N : 0}, pred), tr = f32({transform ? B : 0, transform ? 13 : 0}, pred);
+  if (B == 0) return {mean, status, pp, tr};
+  ok(smplr_point_errors(pred.data_ptr<float>(), gt.data_ptr<float>(), (int)B, (int)N, (int)root, pp_mode >= 0 ? (int)pp_mode : 0,
+                        mean.data_ptr<float>(), fpm(tr), fpm(pp), status.data_ptr<int32_t>(), cur_stream()),
+     "smplr_point_errors");
+  return {mean, status, pp, tr};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> point_errors_meta(const Tensor &pred, const Tensor &gt, int64_t root, int64_t pp_mode,
+                                                             bool transform) {
+  point_errors_check(pred, gt, root, pp_mode);
+  const int64_t B = pred.size(0), N = pred.size(1);
+  return {at::empty({B, 4}, pred.options()), at::empty({B}, pred.options().dtype(at::kInt)),
+          at::empty({pp_mode >= 0 ? B : 0, pp_mode >= 0 ? N : 0}, pred.options()),
+          at::empty({transform ? B : 0, transform ? 13 : 0}, pred.options())};
+}
+
 int64_t abi_version() { return smplr_abi_version(); }
 #ifndef SMPLR_TORCH_OPS_ID
 #define SMPLR_TORCH_OPS_ID "unknown"
@@ -613,6 +652,8 @@ TORCH_LIBRARY(smplraster, m) {
   m.def("affine_warp(Tensor pool, Tensor matrices, Tensor? index, Tensor(a!) out, int mode=0, float rescale=1.0) -> ()");
   m.def("resize_pad(Tensor data, Tensor desc, Tensor? index, Tensor(a!) out, int channels, int mode=0, int flags=4, "
         "float rescale=1.0) -> ()");
+  m.def("point_errors(Tensor pred, Tensor gt, int root=-1, int per_point_mode=-1, bool transform=False) -> "
+        "(Tensor, Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch key is named CUDA in torch)
@@ -630,6 +671,7 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("mesh_render", &mesh_render);
   m.impl("affine_warp", &affine_warp);
   m.impl("resize_pad", &resize_pad);
+  m.impl("point_errors", &point_errors);
 }
 
 TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
@@ -647,4 +689,5 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("mesh_render", &mesh_render_meta);
   m.impl("affine_warp", &affine_warp_meta);
   m.impl("resize_pad", &resize_pad_meta);
+  m.impl("point_errors", &point_errors_meta);
 }

@@ -2,11 +2,14 @@
 printing I/O: per-part IoU over classes 1..31 and pixel accuracy of the arg-max part map against ground-truth maps, in the
 style of `inference.predict_batch`.  With a decoder built with a fused loss (`SMPLDecoder(..., loss=softmax_focal_loss(..))`)
 the counting runs inside the rasteriser's loss epilogue and the (N, W, W, 32) scores are never written; a decoder without
-one writes them and the confusion kernel counts them."""
+one writes them and the confusion kernel counts them.  `evaluate_3d` adds what `evaluate3d.py` leaves out: the distance between the
+predicted and the ground-truth surface and joints in metres, raw and after translation, scale and Procrustes alignment
+(eval3d.py, csrc/eval3d.hip), and the pose-parameter MSE in the same pass."""
 from __future__ import annotations
 
 import torch
 
+from .eval3d import Eval3D
 from .metrics import SegConfusion
 
 
@@ -55,3 +58,59 @@ def evaluate_pose_param_mse(smpl_model, batches):
     if total is None:
         raise ValueError("evaluate_pose_param_mse: no batches")
     return float(total) / count
+
+
+@torch.no_grad()
+def evaluate_3d(smpl_model, smpl_layer, batches, root_joint=None):
+    """The loop of `evaluate3d.py:32-65` with 3D errors in metres.  batches: an iterable of (images, gt) on the model's
+    device, gt either (gt_pose (N, 72), gt_shape (N, 10)) - decoded by the same `smpl_layer` as the prediction - or
+    ground-truth vertices (N, V, 3).  The predicted vertices are smpl_layer(smpl) with pose = smpl[:, 4:76] and shape =
+    smpl[:, 76:86] (the layout `evaluate_pose_param_mse` assumes).
+    -> dict(pve, pve_t, pve_sc, pve_pa: mean per-vertex error as given / centroids removed / + least-squares scale /
+    Procrustes-aligned; with a joint regressor in the SMPL model also mpjpe, mpjpe_root (relative to joint `root_joint`,
+    the joints' centroid when None) and mpjpe_pa over `smpl_layer.joints`; count = meshes counted, nonfinite = meshes left
+    out because they held a NaN or Inf; pose_mse = `evaluate_pose_param_mse`'s number when gt carries the pose, else None)."""
+    ev_v = ev_j = None
+    mse_sum, mse_n = None, 0
+    was_training = smpl_model.training
+    smpl_model.eval()
+    try:
+        for images, gt in batches:
+            smpl = smpl_model(images)
+            dev = smpl.device
+            if ev_v is None:
+                ev_v = Eval3D(dev)
+                has_j = smpl_layer.constants(dev).joint_regressor is not None
+                ev_j = Eval3D(dev) if has_j else None
+            pred_v = smpl_layer(smpl.float())
+            if isinstance(gt, (tuple, list)):
+                gt_pose, gt_shape = (torch.as_tensor(t, device=dev) for t in gt)
+                if gt_pose.dim() != 2 or gt_pose.shape[1] != 72 or gt_pose.shape[0] != smpl.shape[0]:
+                    raise ValueError("gt_pose must be (N, 72) with N = the batch's images")
+                if gt_shape.shape != (smpl.shape[0], 10):
+                    raise ValueError("gt_shape must be (N, 10) with N = the batch's images")
+                x = torch.cat([smpl[:, :smpl_layer.num_cam].float(), gt_pose.float(), gt_shape.float()], 1)
+                gt_v = smpl_layer(x)
+                err = (gt_pose[:, 3:].to(torch.float64) - smpl[:, 7:76].to(torch.float64)).square().sum()
+                mse_sum = err if mse_sum is None else mse_sum + err
+                mse_n += int(smpl.shape[0]) * 69
+            else:
+                gt_v = torch.as_tensor(gt, device=dev).float()
+                if gt_v.shape != pred_v.shape:
+                    raise ValueError("ground-truth vertices must be %s, got %s" % (tuple(pred_v.shape), tuple(gt_v.shape)))
+            ev_v.update(pred_v, gt_v)
+            if ev_j is not None:
+                pj, gj = smpl_layer.joints(pred_v).contiguous(), smpl_layer.joints(gt_v).contiguous()
+                ev_j.update(pj, gj, root=root_joint)          # (the root only changes the translation mode)
+    finally:
+        smpl_model.train(was_training)
+    if ev_v is None:
+        raise ValueError("evaluate_3d: no batches")
+    v = ev_v.result()
+    out = {"pve": v["none"], "pve_t": v["translation"], "pve_sc": v["scale"], "pve_pa": v["similarity"],
+           "count": v["count"], "nonfinite": v["nonfinite"],
+           "pose_mse": float(mse_sum) / mse_n if mse_n else None}
+    if ev_j is not None:
+        j = ev_j.result()
+        out.update(mpjpe=j["none"], mpjpe_root=j["translation"], mpjpe_pa=j["similarity"], joint_count=j["count"])
+    return out

@@ -46,6 +46,8 @@ SCHEMAS = {
                     "float rescale=1.) -> ()"),
     "resize_pad": ("smplraster::resize_pad(Tensor data, Tensor desc, Tensor? index, Tensor(a!) out, int channels, "
                    "int mode=0, int flags=4, float rescale=1.) -> ()"),
+    "point_errors": ("smplraster::point_errors(Tensor pred, Tensor gt, int root=-1, int per_point_mode=-1, "
+                     "bool transform=False) -> (Tensor, Tensor, Tensor, Tensor)"),
 }
 
 _ns = None
