@@ -107,7 +107,7 @@ Blend3BwdGeom blend3_bwd_geom(int B, int N3);
 int launch_blend3_bwd_partials(const float *dv_posed, const void *pk_bwd, int B, int N3, float *part,
                                hipStream_t st);
 int skin_bwd_nblk(int V);
-// The segmentation backward's per-row-block slot sums (raster.hip), which the skinning backward can gather
+// The segmentation backward's per-row-block slot sums (seg_bwd.hip), which the skinning backward can gather
 // by vertex instead of reading a merged dproj: part (B, nsplit, SB_NWIN, SB_SLOTS, 2), vslot (B, VP) = the
 // record slot of each vertex (-1: none), nsplit = ceil(W / seg_bwd_rows(B, W)).
 constexpr int SB_SLOTS = 4096;   // 32 KB of LDS accumulators per window
@@ -141,7 +141,7 @@ int launch_skin_bwd_partials(const float *dverts, const float *dproj, SegGrad sg
 
 // Linear-blend skinning of one vertex from its <= 4 (weight, joint) pairs against the mesh's 24 x 12 joint matrix in
 // LDS (sAj: 72 float4), then the orthographic projection.  One definition for the two kernels that must
-// agree bit for bit: skin_fwd_kernel (skin.hip) and the binning kernel that skins its own vertices (raster.hip).
+// agree bit for bit: skin_fwd_kernel (skin.hip) and the binning kernel that skins its own vertices (seg_bin.hip).
 __device__ __forceinline__ void skin_T_sparse(const float4 *sAj, const float4 ww, const float4 jj, float T[12]) {
   const float w[4] = {ww.x, ww.y, ww.z, ww.w};
   const int jx[4] = {(int)jj.x, (int)jj.y, (int)jj.z, (int)jj.w};
@@ -149,13 +149,7 @@ __device__ __forceinline__ void skin_T_sparse(const float4 *sAj, const float4 ww
   for (int e = 0; e < 12; ++e) T[e] = 0.0f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-#if defined(SMPLR_KO_SKIN_NOLDS)      // knock-outs (tools/build_variant.sh; wrong results on purpose): no LDS read at all ...
-    const float4 r0 = make_float4(jj.x, jj.y, jj.z, jj.w), r1 = make_float4(jj.y, jj.x, jj.w, jj.z), r2 = make_float4(jj.w, jj.z, jj.y, jj.x);
-#elif defined(SMPLR_KO_SKIN_JOINT0)   // ... / every lane reads joint k's rows (pure broadcast: no bank conflict)
-    const float4 r0 = sAj[k * 3], r1 = sAj[k * 3 + 1], r2 = sAj[k * 3 + 2];
-#else
     const float4 r0 = sAj[jx[k] * 3], r1 = sAj[jx[k] * 3 + 1], r2 = sAj[jx[k] * 3 + 2];
-#endif
     const float wj = w[k];
     T[0] = fmaf(wj, r0.x, T[0]); T[1] = fmaf(wj, r0.y, T[1]); T[2] = fmaf(wj, r0.z, T[2]); T[3] = fmaf(wj, r0.w, T[3]);
     T[4] = fmaf(wj, r1.x, T[4]); T[5] = fmaf(wj, r1.y, T[5]); T[6] = fmaf(wj, r1.z, T[6]); T[7] = fmaf(wj, r1.w, T[7]);
@@ -219,7 +213,7 @@ __device__ __forceinline__ Frag3 split8(const float x[8]) {
   return f;
 }
 
-// ---- focal loss pieces shared by the loss head (loss.hip) and the rasteriser's loss epilogue (raster.hip) ----
+// ---- focal loss pieces shared by the loss head (loss.hip) and the rasterisers' loss epilogue (raster.hip, raster1.hip) ----
 constexpr float K_EPS = 1e-7f;   // keras.backend.epsilon()  (focal_loss.py:17)
 __device__ __forceinline__ float pow_gamma(float x, float gamma) {
   // (1-p)^gamma; the reference's only values are 2 (focal) and, for cross-entropy, 0

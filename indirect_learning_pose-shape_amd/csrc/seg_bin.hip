@@ -1,0 +1,469 @@
+// Segmentation forward, stage 1: seg_bin_kernel, one workgroup per mesh (optionally with compute_mask's z-buffer fused in
+// front, the mesh's vertices staged in LDS, or skinned and projected by the workgroup itself): splits the part-major
+// vertex list by reach.
+//      In fp32 exp(-x) == 0 for x >= 104, so a vertex with mask m only matters within
+//      104/m pixels.  m > 208 ("local": the invisible vertices, m = 500) reaches at most its
+//      nearest pixel centre -> one (pixel, part, x, vertex) record, counting-sorted by pixel.
+//      m <= 208 ("global": the visible vertices, m = 1) are compacted part-major, in table
+//      order, each part padded to a multiple of 4 with +inf sentinels, as (u, v, m^2, vertex).
+//      This drops the pair count from 2304 x 6879 to 2304 x (#visible ~ 570) per mesh without
+//      changing a single fp32 result.
+// The rasteriser (raster.hip) and the backward (seg_bwd.hip) read what it leaves; the layout is in raster_common.h.
+#include "raster_common.h"
+
+namespace smplr {
+constexpr int BIN_Q0 = 3;            // seg_bin_kernel<.., SKIN>: vertices per thread whose operands are requested before the first barrier
+constexpr float X_ZERO = 104.0f;     // expf(-x) rounds to 0 in fp32 for x >= 104
+constexpr float M_LOCAL = 208.0f;    // m > 208 => 104/m < 0.5 px: only the nearest pixel centre
+#ifdef SMPLR_TL
+constexpr int TL_BIN_WG = 128;
+__device__ unsigned g_tl_bin[TL_BIN_WG * (BIN_T / 64) * 32];
+#endif
+
+struct Slot {
+  int cls;      // 0 skip, 1 global, 2 local
+  int pos, pix;
+  float u, v, m, x;
+};
+
+__device__ __forceinline__ Slot classify(float u, float v, float m, int pos, int W) {
+  Slot s;
+  s.pos = pos;
+  s.u = u;
+  s.v = v;
+  s.m = m;
+  s.cls = 1;
+  s.pix = 0;
+  s.x = 0.f;
+  if (s.m > M_LOCAL) {
+    s.cls = 0;
+    const float c = rintf(s.u), r = rintf(s.v);
+    if (c >= 0.0f && c <= (float)(W - 1) && r >= 0.0f && r <= (float)(W - 1)) {
+      const float du = s.u - c, dv = s.v - r;
+      // v_sqrt_f32 (1 ulp), as the pair loop and the backward compute it; the IEEE sequence was a fifth of this
+      // kernel's per-slot instructions
+      s.x = __builtin_amdgcn_sqrtf(fmaf(du, du, dv * dv) * (s.m * s.m));
+      if (s.x < X_ZERO) {
+        s.cls = 2;
+        s.pix = (int)r * W + (int)c;
+      }
+    }
+  }
+  return s;
+}
+
+// rec[n] (S = Kpad + K slots of (u, v, m^2, vertex)): [0, goff[P]) the global list, part-major,
+// padded per part; [goff[P], goff[P] + L) the local records in pixel order.  Saved for backward.
+// scratch per mesh: goff[P+1] | lstart[npix+1] | lrec[K] uint2 (x bits, part)
+// VIS = true fuses compute_mask (visibility.hip's kernel, same arithmetic) in front: the z-buffer
+// over the vgrid x vgrid grid and the per-vertex flags live in LDS after the pixel counters, the
+// mask is written out (it is an output of the decoder) and classification reads the flags.
+// STAGE = true keeps every vertex' (u, v) in LDS as well (2 VP floats): the workgroup then makes
+// ONE round trip to global memory - its vertices (coalesced) and its part-table slots, requested
+// together at the top - and the per-slot gathers of classification become LDS reads.
+// SKIN = true (with VIS and STAGE): the workgroup skins and projects its mesh's vertices itself (skin_fwd_kernel's
+// arithmetic, common.h) from v_posed, the sparse weights and the joint matrices, writes verts and proj out and goes on
+// with the values in registers: the skinning launch, its ramp and the re-read of proj go away.
+template <bool VIS, bool STAGE, bool SKIN>
+__global__ __launch_bounds__(BIN_T) void seg_bin_kernel(const float *__restrict__ proj,
+                                                        float *__restrict__ mask,
+                                                        const int *__restrict__ part_pos,
+                                                        const int *__restrict__ part_off, int P, int K,
+                                                        int VP, int W, int S, float4 *__restrict__ G,
+                                                        int *__restrict__ goff, int *__restrict__ lstart,
+                                                        uint2 *__restrict__ lrec, int vgrid, int ref_compat,
+                                                        short *__restrict__ vslot, SkinIn sk) {
+  // (16-B aligned: the 64-bit z-buffer keys behind the counters need 8, whatever the static LDS in front)
+  extern __shared__ __attribute__((aligned(16))) int s_cnt[];   // npix | VIS: z-buffer keys, visible flags | STAGE: u[VP], v[VP]
+  __shared__ int s_poff[33], s_gstart[33], s_gpad[33], s_wave[BIN_T / 64], s_gb[BIN_T];
+  __shared__ int s_any_empty, s_nonunit;
+  __shared__ float4 sAj[SKIN ? 72 : 1];
+  static_assert(!SKIN || (VIS && STAGE), "the skinning form is built for the decoder's path only");
+  const int n = blockIdx.x, tid = threadIdx.x;
+  SMPLR_TL_WAVE(g_tl_bin, BIN_T / 64, n, TL_BIN_WG)
+  const int npix = W * W;
+  const float *pj = proj + (size_t)n * VP * 3;
+  float *mk = mask + (size_t)n * VP;
+  const int cells = VIS ? vgrid * vgrid : 0, words = VIS ? (VP + 31) / 32 : 0;
+  unsigned long long *zbuf = reinterpret_cast<unsigned long long *>(s_cnt + ((npix + 1) & ~1));
+  unsigned int *vis = reinterpret_cast<unsigned int *>(zbuf + cells);
+  float *sU = reinterpret_cast<float *>(vis + words), *sV = sU + VP;
+  // vertex -> record slot (for the backward's gather by vertex).  Round 4: written straight to global memory - -1
+  // everywhere up front (coalesced, under the first requests), a record's slot by the placement (a 2-B store per
+  // record, nothing waits for it; the barriers in between order the two stores to one address) - instead of a map
+  // staged in 13.8 KB of LDS and copied out behind one more barrier: 2.8 k of the kernel's 48 k clocks.
+  short *vsl = vslot ? vslot + (size_t)n * VP : nullptr;
+
+  // ---- every global operand of the block, requested up front
+  const int ipt = (K + BIN_T - 1) / BIN_T;      // <= IPT_MAX (checked by the launcher)
+  const int k0 = tid * ipt, k1 = min(K, k0 + ipt);
+  int pos[IPT_MAX];
+  if (!SKIN) {                                  // (the skinning form asks after its vertices are done: registers)
+#pragma unroll
+    for (int j = 0; j < IPT_MAX; ++j) pos[j] = (j < ipt) ? part_pos[min(k0 + j, K - 1)] : 0;
+  }
+  constexpr int VPT = SKIN ? 7 : 8;             // vertices per thread and trip: 8192 per trip (skinning: 7168, one trip)
+  float vu[VPT], vv[VPT], vz[VPT];
+  float4 tw[SKIN ? VPT : 1], tj[SKIN ? VPT : 1], aj = {0.f, 0.f, 0.f, 0.f};
+  float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f;
+  if (SKIN) {                                   // (VP <= 7 BIN_T: one trip, checked by the launcher)
+    aj = reinterpret_cast<const float4 *>(sk.A + (size_t)n * 288)[tid < 72 ? tid : 71];
+    const float *c = sk.cam + (size_t)n * sk.x_stride;
+    c0 = c[0]; c1 = c[1]; c2 = c[2]; c3 = c[3];
+    const float *vp = sk.v_posed + (size_t)n * VP * 3;
+    // (the first BIN_Q0 vertices' operands here, the rest behind the barrier: the CU's address unit takes 7.5 k clocks
+    // for all 35 requests of every thread, and the skinning that follows is bound by LDS reads - the later vertices'
+    // requests are worked off under the first ones' skinning instead of in front of the barrier)
+#pragma unroll
+    for (int q = 0; q < BIN_Q0; ++q) {
+      const int v = min(tid + q * BIN_T, VP - 1);
+      const float4 *tp = reinterpret_cast<const float4 *>(sk.top4 + (size_t)v * 8);
+      tw[q] = tp[0];
+      tj[q] = tp[1];
+      vu[q] = vp[v * 3 + 0];                    // the posed vertex for now
+      vv[q] = vp[v * 3 + 1];
+      vz[q] = vp[v * 3 + 2];
+    }
+  } else if (VIS || STAGE) {
+#pragma unroll
+    for (int q = 0; q < VPT; ++q) {
+      const int v = min(tid + q * BIN_T, VP - 1);
+      vu[q] = pj[v * 3 + 0];
+      vv[q] = pj[v * 3 + 1];
+      vz[q] = VIS ? pj[v * 3 + 2] : 0.0f;
+    }
+  }
+  if (tid <= P) s_poff[tid] = part_off[tid];
+  if (tid == 0) { s_nonunit = 0; s_any_empty = 0; }
+  for (int i = tid; i < npix; i += BIN_T) s_cnt[i] = 0;
+  if (vslot && !SKIN)                                         // block-uniform
+    for (int i = tid; i < VP; i += BIN_T) vsl[i] = -1;
+  if (VIS) {
+    for (int i = tid; i < cells; i += BIN_T) zbuf[i] = 0ull;
+    for (int i = tid; i < words; i += BIN_T) vis[i] = 0u;
+  }
+  if (SKIN && tid < 72) sAj[tid] = aj;
+  SMPLR_TL_STAMP(1);
+  __syncthreads();
+  SMPLR_TL_STAMP(2);
+  if (SKIN) {
+    const float *vp = sk.v_posed + (size_t)n * VP * 3;
+#pragma unroll
+    for (int q = BIN_Q0; q < VPT; ++q) {
+      const int v = min(tid + q * BIN_T, VP - 1);
+      const float4 *tp = reinterpret_cast<const float4 *>(sk.top4 + (size_t)v * 8);
+      tw[q] = tp[0];
+      tj[q] = tp[1];
+      vu[q] = vp[v * 3 + 0];
+      vv[q] = vp[v * 3 + 1];
+      vz[q] = vp[v * 3 + 2];
+    }
+    if (vslot)                                                // block-uniform
+      for (int i = tid; i < VP; i += BIN_T) vsl[i] = -1;
+    __builtin_amdgcn_sched_barrier(0);
+    float *vo = sk.verts + (size_t)n * VP * 3, *po = sk.proj + (size_t)n * VP * 3;
+#pragma unroll
+    for (int q = 0; q < VPT; ++q) {
+      const int v = tid + q * BIN_T;
+      float T[12], X, Y, Z;
+      skin_T_sparse(sAj, tw[q], tj[q], T);
+      skin_apply(T, vu[q], vv[q], vz[q], X, Y, Z);
+      vu[q] = project_u(X, c0, c2);
+      vv[q] = project_u(Y, c1, c3);
+      vz[q] = Z;
+      if (v < VP) {                                // (either output may be NULL: block-uniform)
+        if (sk.verts) { SMPLR_OUT_STORE(&vo[v * 3 + 0], X); SMPLR_OUT_STORE(&vo[v * 3 + 1], Y); SMPLR_OUT_STORE(&vo[v * 3 + 2], Z); }
+        if (sk.proj) { SMPLR_OUT_STORE(&po[v * 3 + 0], vu[q]); SMPLR_OUT_STORE(&po[v * 3 + 1], vv[q]); SMPLR_OUT_STORE(&po[v * 3 + 2], Z); }
+      }
+      __builtin_amdgcn_sched_barrier(0);          // one vertex at a time: seven T matrices at once do not fit the registers
+    }
+#pragma unroll
+    for (int j = 0; j < IPT_MAX; ++j) pos[j] = (j < ipt) ? part_pos[min(k0 + j, K - 1)] : 0;
+  }
+  if (VIS || STAGE) {
+    const float fG = (float)vgrid;
+    for (int base = 0; base < VP; base += VPT * BIN_T) {
+      if (base > 0) {                           // VP > 8192: further trips (block-uniform)
+#pragma unroll
+        for (int q = 0; q < VPT; ++q) {
+          const int v = min(base + tid + q * BIN_T, VP - 1);
+          vu[q] = pj[v * 3 + 0];
+          vv[q] = pj[v * 3 + 1];
+          vz[q] = VIS ? pj[v * 3 + 2] : 0.0f;
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < VPT; ++q) {
+        const int v = base + tid + q * BIN_T;
+        if (v < VP) {
+          if (STAGE) { sU[v] = vu[q]; sV[v] = vv[q]; }
+          if (VIS) {
+            const float pu = rintf(vu[q]);      // round half to even, like tf.round (compute_mask.py:22)
+            const float pv = rintf(vv[q]);
+            if (pu >= 0.0f && pu < fG && pv >= 0.0f && pv < fG) {
+              const int cell = (int)pv * vgrid + (int)pu;
+              const unsigned long long key = ((unsigned long long)orderable(vz[q]) << 32) |
+                                             (unsigned long long)(0xFFFFFFFFu - (unsigned)v);
+              atomicMax(&zbuf[cell], key);
+            }
+          }
+        }
+      }
+    }
+    SMPLR_TL_STAMP(3);
+    __syncthreads();
+    SMPLR_TL_STAMP(4);
+  }
+  bool vertex1 = false;                          // an empty cell makes vertex 1 visible (compute_mask.py:99)
+  if (VIS) {
+    int empty = 0;
+    for (int i = tid; i < cells; i += BIN_T) {
+      const unsigned long long key = zbuf[i];
+      if (key == 0ull) {
+        empty = 1;
+      } else {
+        const unsigned int v = 0xFFFFFFFFu - (unsigned int)(key & 0xFFFFFFFFull);
+        atomicOr(&vis[v >> 5], 1u << (v & 31));
+      }
+    }
+    if (empty) s_any_empty = 1;   // benign same-value race
+    SMPLR_TL_STAMP(5);
+    __syncthreads();
+    SMPLR_TL_STAMP(6);
+    vertex1 = s_any_empty && ref_compat && VP > 1;
+    if (mask)                                      // (NULL with SKIN when the caller does not want it: block-uniform)
+      for (int v = tid; v < VP; v += BIN_T)
+        SMPLR_OUT_STORE(&mk[v], (((vis[v >> 5] >> (v & 31)) & 1u) || (vertex1 && v == 1)) ? 1.0f : 500.0f);
+  }
+  SMPLR_TL_STAMP(7);
+  float4 *Gn = G + (size_t)n * S;
+  int *goffn = goff + (size_t)n * goff_stride(P);
+  int *lstartn = lstart + (size_t)n * (npix + 1);
+  uint2 *lrecn = lrec + (size_t)n * K;
+
+  // pass 1: classify each of this thread's slots ONCE (results stay in registers for the later
+  // passes), count
+  Slot sl[IPT_MAX];
+  int gcnt = 0;
+  unsigned gbits = 0;                            // bit j: this thread's slot j is a global record
+#pragma unroll
+  for (int j = 0; j < IPT_MAX; ++j) {
+    const int k = k0 + j;
+    sl[j].cls = 0;
+    if (j < ipt && k < k1) {
+      const int ps = pos[j];
+      const float m = VIS ? ((((vis[ps >> 5] >> (ps & 31)) & 1u) || (vertex1 && ps == 1)) ? 1.0f : 500.0f) : mk[ps];
+      const float u = STAGE ? sU[ps] : pj[ps * 3], v = STAGE ? sV[ps] : pj[ps * 3 + 1];
+      sl[j] = classify(u, v, m, ps, W);
+    }
+    if (sl[j].cls == 1) {
+      ++gcnt;
+      gbits |= 1u << j;
+      if (sl[j].m != 1.0f) s_nonunit = 1;     // benign same-value race; read after the scans' barriers
+    } else if (sl[j].cls == 2) {
+      atomicAdd(&s_cnt[sl[j].pix], 1);
+    }
+  }
+  // the part of this thread's first slot (largest p with poff[p] <= k0), for the placement
+  int p0 = 0;
+  if (k0 < k1) {
+    int lo = 0, hi = P;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (s_poff[mid] <= k0) lo = mid; else hi = mid;
+    }
+    p0 = lo;
+  }
+  SMPLR_TL_STAMP(8);
+  __syncthreads();                               // pixel counters complete
+  SMPLR_TL_STAMP(9);
+  // ONE block scan for both prefixes: global records per thread (low half) and local records per thread's
+  // pixel range (high half); K <= 8192 keeps either total below 2^16
+  const int ept = (npix + BIN_T - 1) / BIN_T;
+  const int e0 = tid * ept, e1 = min(npix, e0 + ept);
+  int loc = 0;
+  for (int e = e0; e < e1; ++e) loc += s_cnt[e];
+  int tot2;
+  const int base2 = block_excl_scan(gcnt | (loc << 16), s_wave, &tot2);
+  const int gbase = base2 & 0xffff, gtotal = tot2 & 0xffff, ltotal = tot2 >> 16;
+  SMPLR_TL_STAMP(10);
+  s_gb[tid] = gbase | (int)(gbits << 16);
+  {
+    int run = base2 >> 16;                       // counting sort offsets over pixels
+    for (int e = e0; e < e1; ++e) {
+      const int c = s_cnt[e];
+      s_cnt[e] = run;            // becomes the placement cursor
+      lstartn[e] = run;
+      run += c;
+    }
+    if (tid == 0) lstartn[npix] = ltotal;
+  }
+  SMPLR_TL_STAMP(11);
+  __syncthreads();
+  SMPLR_TL_STAMP(12);
+  if (tid < 128) {
+    // global prefix at each part's first slot: the owning thread's base + its global flags below that slot
+    // (empty parts share a slot; parts that start at K take the total); then the padded part offsets (P <= 31)
+    const int l = tid & 63;
+    int gs = gtotal;
+    const int kk = s_poff[l <= P ? l : P];
+    if (l < P && kk < K) {
+      const int t = kk / ipt, j = kk - t * ipt;
+      const int w = s_gb[t];
+      gs = (w & 0xffff) + __popc(((unsigned)w >> 16) & ((1u << j) - 1u));
+    }
+    const int gnext = __shfl_down(gs, 1, 64);
+    const int cnt = (l < P) ? (gnext - gs + GP - 1) / GP * GP : 0;
+    if (tid < 64) {
+      int inc = cnt;
+#pragma unroll
+      for (int o = 1; o < 32; o <<= 1) {
+        const int t = __shfl_up(inc, o, 64);
+        if (tid >= o) inc += t;
+      }
+      if (tid <= P) {
+        s_gstart[tid] = gs;
+        s_gpad[tid] = inc - cnt;               // tid == P: cnt = 0, inc = total
+        goffn[tid] = inc - cnt;
+      }
+    } else {
+      // the block's second wave, beside the prefix: the parts in order of record count (largest first, ties by part
+      // number) for the rasteriser, whose waves take them from this list as they become free (raster2_fwd_kernel)
+      const int key = l < P ? ((cnt << 5) | (31 - l)) : -1;                    // distinct keys; cnt < 2^16
+      int rank = 0;
+#pragma unroll
+      for (int q = 0; q < 31; ++q) rank += (__builtin_amdgcn_readlane(key, q) > key) ? 1 : 0;
+      if (l < P) goffn[P + 2 + rank] = l;
+    }
+  }
+  SMPLR_TL_STAMP(13);
+  __syncthreads();
+  SMPLR_TL_STAMP(14);
+  // pass 3: placement
+  {
+    int p = p0;
+    int run = gbase;
+#pragma unroll
+    for (int j = 0; j < IPT_MAX; ++j) {
+      const int k = k0 + j;
+      if (!(j < ipt && k < k1)) continue;
+      while (k >= s_poff[p + 1]) ++p;
+      const Slot s = sl[j];
+      if (s.cls == 1) {
+        const int slot = s_gpad[p] + (run - s_gstart[p]);
+        Gn[slot] = make_float4(s.u, s.v, s.m * s.m, __int_as_float(s.pos));
+        if (vslot) vsl[s.pos] = (short)slot;
+        ++run;
+      } else if (s.cls == 2) {
+        const int dst = atomicAdd(&s_cnt[s.pix], 1);
+        lrecn[dst] = make_uint2(__float_as_uint(s.x), (unsigned)p);
+        Gn[s_gpad[P] + dst] = make_float4(s.u, s.v, s.m * s.m, __int_as_float(s.pos));
+        if (vslot) vsl[s.pos] = (short)(s_gpad[P] + dst);
+      }
+    }
+  }
+  SMPLR_TL_STAMP(15);
+  // header: used slots | 1 if some far-reaching record has a weight other than 1 (else the pair loop skips m^2) | length
+  // of the far-reaching list, padded per part (what the rasteriser's table has to hold: smplr_seg_raster_plan)
+  if (tid == 0) goffn[P + 1] = s_nonunit;
+  if (tid == 0)
+    Gn[S - 1] = make_float4(__int_as_float(s_gpad[P] + lstartn[npix]), __int_as_float(s_nonunit), __int_as_float(s_gpad[P]),
+                            __int_as_float(-1));
+  // sentinels in the padding
+  if (tid < P) {
+    const int cnt = s_gstart[tid + 1] - s_gstart[tid];
+    for (int i = s_gpad[tid] + cnt; i < s_gpad[tid + 1]; ++i)
+      Gn[i] = make_float4(INFINITY, INFINITY, 1.0f, __int_as_float(-1));
+  }
+  SMPLR_TL_STAMP(16);
+  SMPLR_TL_STAMP(17);
+  SMPLR_TL_STAMP(18);
+}
+
+// LDS of the binning workgroup: pixel counters [+ z-buffer keys and visible flags with the fused mask] = base,
+// and - when it still fits - every vertex' (u, v) (stage).
+struct BinLds { size_t base, total; bool stage; };
+static BinLds bin_lds(int VP, int W, int grid_wh /* 0: mask not fused */) {
+  BinLds b;
+  b.base = (size_t)((W * W + 1) & ~1) * sizeof(int);
+  if (grid_wh > 0) b.base += (size_t)grid_wh * grid_wh * 8 + (size_t)((VP + 31) / 32) * 4;
+  b.stage = b.base + (size_t)VP * 8 <= 150 * 1024;
+  b.total = b.base + (b.stage ? (size_t)VP * 8 : 0);
+  return b;
+}
+
+// stage 1: binning (optionally with compute_mask fused in front) -> rec, workspace (part offsets, pixel lists), vslot
+int seg_bin_impl(const char *fn, const float *proj, float *mask, bool fuse_vis, int grid_wh, int ref_compat, int B, int VP,
+                 int W, const int32_t *part_pos, const int32_t *part_off, int P, int K, void *workspace, float *rec,
+                 int16_t *vslot, void *stream, SkinIn sk) {
+  SMPLR_REQUIRE(B >= 0 && VP > 0 && VP <= 32767 && W > 0 && W <= 160 && P >= 1 && P <= 31 && K > 0 && K <= BIN_T * IPT_MAX,
+                "%s: bad sizes B=%d VP=%d W=%d (max 160) P=%d (max 31) K=%d", fn, B, VP, W, P, K);
+  SMPLR_REQUIRE(!fuse_vis || (grid_wh > 0 && grid_wh <= 128), "%s: bad grid_wh=%d (max 128)", fn, grid_wh);
+  if (B == 0) return 0;
+  const bool skin = sk.v_posed != nullptr;
+  // (the skinning form reads v_posed, not proj, and keeps the mask in LDS: there proj, verts and mask are optional outputs)
+  SMPLR_REQUIRE((skin || (proj && mask)) && part_pos && part_off && workspace && rec, "%s: null pointer", fn);
+  SMPLR_REQUIRE(!skin || (sk.top4 && sk.A && sk.cam && sk.x_stride >= 4 && sk.proj == proj && fuse_vis &&
+                          VP <= 7 * BIN_T),
+                "%s: the skinning form needs the sparse weights, A, camera rows, the fused mask and V <= %d",
+                fn, 7 * BIN_T);
+  hipStream_t st = as_stream(stream);
+  const SegWs ws = seg_ws_layout(B, W, P, K);
+  const int S = seg_slots(P, K);
+  char *base = reinterpret_cast<char *>(workspace);
+  float4 *G = reinterpret_cast<float4 *>(rec);
+  int *goff = reinterpret_cast<int *>(base + ws.goff_off);
+  int *lstart = reinterpret_cast<int *>(base + ws.lstart_off);
+  uint2 *lrec = reinterpret_cast<uint2 *>(base + ws.lrec_off);
+  // LDS: pixel counters | fused mask: z-buffer keys + visible flags | staged (u, v) of every vertex
+  const BinLds bl = bin_lds(VP, W, fuse_vis ? grid_wh : 0);
+  SMPLR_REQUIRE(bl.base <= 150 * 1024, "%s: pixel counters + grid + flags need %zu B of LDS (max 153600)", fn, bl.base);
+  const bool stage = bl.stage;
+  const size_t lds = bl.total;
+#define SMPLR_BIN_LAUNCH(VIS_, STAGE_, SKIN_)                                                                 \
+  {                                                                                                           \
+    int rc = lds_attr<&seg_bin_kernel<VIS_, STAGE_, SKIN_>>(lds);          \
+    if (rc) return rc;                                                                                        \
+    hipLaunchKernelGGL((seg_bin_kernel<VIS_, STAGE_, SKIN_>), dim3(B), dim3(BIN_T), lds, st, proj, mask,      \
+                       part_pos, part_off, P, K, VP, W, S, G, goff, lstart, lrec, fuse_vis ? grid_wh : 1,     \
+                       ref_compat, reinterpret_cast<short *>(vslot), sk);                                     \
+  }
+  SMPLR_REQUIRE(!skin || stage, "%s: the skinning form needs the staged (u, v) to fit LDS", fn);
+  if (skin) SMPLR_BIN_LAUNCH(true, true, true)
+  else if (fuse_vis && stage) SMPLR_BIN_LAUNCH(true, true, false)
+  else if (fuse_vis) SMPLR_BIN_LAUNCH(true, false, false)
+  else if (stage) SMPLR_BIN_LAUNCH(false, true, false)
+  else SMPLR_BIN_LAUNCH(false, false, false)
+#undef SMPLR_BIN_LAUNCH
+  SMPLR_LAUNCH_CHECK(fn);
+  return 0;
+}
+}  // namespace smplr
+
+extern "C" {
+
+int smplr_seg_slots(int P, int K) { return (P > 0 && K > 0) ? smplr::seg_slots(P, K) : 0; }
+
+size_t smplr_seg_workspace(int B, int VP, int W, int P, int K) {
+  if (B <= 0 || VP <= 0 || W <= 0 || P <= 0 || K <= 0) return 0;
+  return smplr::seg_ws_layout(B, W, P, K).total;
+}
+
+int smplr_seg_bin(const float *proj, float *mask, int B, int VP, int W, int grid_wh, int ref_compat,
+                  const int32_t *part_pos, const int32_t *part_off, int P, int K, void *workspace, float *rec,
+                  int16_t *vslot, void *stream) {
+  return smplr::seg_bin_impl("smplr_seg_bin", proj, mask, grid_wh > 0, grid_wh, ref_compat, B, VP, W, part_pos,
+                             part_off, P, K, workspace, rec, vslot, stream);
+}
+
+int smplr_skin_vis_seg_fits(int V, int W, int grid_wh) {
+  if (V <= 0 || V > 7 * smplr::BIN_T || W <= 0 || W > 160 || grid_wh <= 0 || grid_wh > 128) return 0;
+  const smplr::BinLds b = smplr::bin_lds(V, W, grid_wh);
+  return (b.base <= 150 * 1024 && b.stage) ? 1 : 0;
+}
+
+}  // extern "C"
+
+#ifdef SMPLR_TL
+SMPLR_TL_EXPORT(bin, smplr::g_tl_bin, smplr::TL_BIN_WG * (smplr::BIN_T / 64) * 32)
+#endif

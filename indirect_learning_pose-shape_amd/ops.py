@@ -954,7 +954,7 @@ FUSE_SKIN_BELOW_B = int(os.environ.get("SMPLR_FUSE_SKIN_BELOW_B", "448"))
 FUSE_SKIN_FROM_B = int(os.environ.get("SMPLR_FUSE_SKIN_FROM_B", "768"))
 
 
-SILH_HINT_MAX_W = 48     # smplr_silh_fwd_hint uses the hint in silh_px_kernel only (W <= 48, raster.hip)
+SILH_HINT_MAX_W = 48     # smplr_silh_fwd_hint uses the hint in silh_px_kernel only (W <= 48, silh.hip)
 
 
 class DecoderFn(torch.autograd.Function):
