@@ -505,6 +505,31 @@ int smplr_silh_fwd_form(int VP, int W);
 int smplr_silh_bwd(const float *dsilh, const float *silh, const int32_t *arg,
                    const float *proj, int B, int VP, int W, float *dproj, int deterministic, void *stream);
 
+/* ---- silhouette loss head: train_stage2_silhouette.py:82-86,226-234 (softmax over the two silhouette channels +
+ *      categorical cross-entropy / focal loss at an integer label map + the accuracy metric's counts) ------------- */
+/* Per pixel, s = silh[..., 1] and z0 = silh[..., 0] as the forward stored them, t = labels (B, W, W) int32:
+ *   p = softmax(z0, s),  loss = w_t (1 - p_t)^gamma (-log p_t)   (smplr_focal_fwd's expression at C = 2, without its clip,
+ *   which cannot bind: p lies in [0.2689, 0.7311] for s in [0, 1]),  k = d loss / d s = +-2 q p0 p1 (+: t = 1),
+ *   q = w_t (gamma (1 - p_t)^(gamma - 1) log p_t - (1 - p_t)^gamma / p_t).
+ * class_w (2,) or NULL (ones); gamma = 0 without weights is Keras' categorical_crossentropy.  A label outside {0, 1}
+ * gives loss = k = 0; a NaN score under a label in {0, 1} gives NaN loss and k.  loss, k: (B, W * W).
+ * conf (3, 2) int64 or NULL: += the (label, s > z0) counts, row 2 = labels outside {0, 1} - what smplr_seg_confusion
+ * counts on the written silhouette (channel 0 on a tie); at most six atomics per workgroup.                          */
+int smplr_silh_loss_fwd(const float *silh, const int32_t *labels, const float *class_w, float gamma, int B, int W,
+                        float *loss, float *k, int64_t *conf, void *stream);
+/* smplr_silh_fwd_hint (hint may be NULL) + smplr_silh_loss_fwd: silh and arg are those of smplr_silh_fwd, loss / k /
+ * conf those of smplr_silh_loss_fwd on that silh, bit for bit.  Form 0 of smplr_silh_fwd_form runs the loss head as the
+ * rasteriser's epilogue (one launch) or behind it (two), the other forms always behind it; the environment variable
+ * SMPLR_SILH_LOSS_EPILOGUE=1 / 0 picks for form 0 (A/B runs); default: behind it, until the epilogue is measured faster. */
+int smplr_silh_fwd_loss(const float *proj, const float *hint, const int32_t *labels, const float *class_w, float gamma,
+                        int B, int VP, int W, float *silh, int32_t *arg, float *loss, float *k, int64_t *conf,
+                        void *workspace, void *stream);
+/* smplr_silh_bwd with g = dloss * k (one fp32 multiply per pixel) in place of dsilh[..., 1] - dsilh[..., 0]: the
+ * gradient of the silhouette never exists.  dloss, k: (B, W * W); deterministic as smplr_silh_bwd (the scale from
+ * the mesh's max |dloss * k|): the bits smplr_silh_bwd gives for dsilh = (0, dloss * k).                             */
+int smplr_silh_loss_bwd(const float *dloss, const float *k, const float *silh, const int32_t *arg, const float *proj,
+                        int B, int VP, int W, float *dproj, int deterministic, void *stream);
+
 /* ---- loss head: model.py:119-120 + focal_loss.py:10-46 ----------- */
 /* Reshape(W*W, C) + softmax + categorical_focal_loss fused: logits (npix, C) are the raw
  * rasteriser scores (seg: C = 32, silhouette: C = 2), loss (npix) is the per-pixel value the Keras

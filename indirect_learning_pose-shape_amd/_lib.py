@@ -89,6 +89,9 @@ SIGNATURES = {
     "smplr_silh_fwd_hint": (c_int, [P, P, I, I, I, P, P, P, P]),
     "smplr_silh_fwd_form": (c_int, [I, I]),
     "smplr_silh_bwd": (c_int, [P, P, P, P, I, I, I, P, I, P]),
+    "smplr_silh_loss_fwd": (c_int, [P, P, P, c_float, I, I, P, P, P, P]),
+    "smplr_silh_fwd_loss": (c_int, [P, P, P, P, c_float, I, I, I, P, P, P, P, P, P, P]),
+    "smplr_silh_loss_bwd": (c_int, [P, P, P, P, P, I, I, I, P, I, P]),
     "smplr_focal_fwd": (c_int, [P, P, P, P, c_float, c_longlong, I, P, P, P]),
     "smplr_focal_bwd": (c_int, [P, P, P, P, c_float, P, c_longlong, I, P, P]),
     "smplr_prelu_fwd": (c_int, [P, P, c_longlong, I, I, P, P]),

@@ -213,16 +213,17 @@ __device__ __forceinline__ Frag3 split8(const float x[8]) {
   return f;
 }
 
-// ---- focal loss pieces shared by the loss head (loss.hip) and the rasterisers' loss epilogue (raster.hip, raster1.hip) ----
+// ---- focal loss pieces shared by the loss head (loss.hip), the rasterisers' loss epilogue (raster.hip, raster1.hip) and the
+// silhouette loss head (silh_loss_device.h: host and device) ----
 constexpr float K_EPS = 1e-7f;   // keras.backend.epsilon()  (focal_loss.py:17)
-__device__ __forceinline__ float pow_gamma(float x, float gamma) {
+__host__ __device__ __forceinline__ float pow_gamma(float x, float gamma) {
   // (1-p)^gamma; the reference's only values are 2 (focal) and, for cross-entropy, 0
   if (gamma == 2.0f) return x * x;
   if (gamma == 0.0f) return 1.0f;
   if (gamma == 1.0f) return x;
   return powf(x, gamma);
 }
-__device__ __forceinline__ float dpow_gamma(float x, float gamma) {   // d/dx x^gamma
+__host__ __device__ __forceinline__ float dpow_gamma(float x, float gamma) {   // d/dx x^gamma
   if (gamma == 2.0f) return 2.0f * x;
   if (gamma == 0.0f) return 0.0f;
   if (gamma == 1.0f) return 1.0f;

@@ -1,8 +1,11 @@
 // Silhouette rasteriser, forward and backward.  The forward has four forms, picked by smplr_silh_fwd_form() from the image
 // and mesh size: silh_px_kernel (one lane per pixel, W <= 48), silh_fused_kernel<ONEWORD> (four lanes per pixel, W <= 96)
 // and the brute force silh_prep_kernel + silh_fwd_kernel; all give the same bits.  silh_bwd_kernel is the backward.
+// smplr_silh_fwd_loss adds the silhouette loss head (silh_loss_device.h): silh_px_kernel<true>'s epilogue, or
+// silh_loss.hip's stand-alone kernel behind any form.
 // Reference: keras_smpl/projects_to_silhouette.py:20-42.
 #include "raster_common.h"
+#include "silh_loss_device.h"
 
 namespace smplr {
 constexpr int CH = SMPLR_CHUNK;      // 8: silhouette list padding
@@ -338,6 +341,11 @@ __global__ __launch_bounds__(SF_T) void silh_fused_kernel(const float *__restric
 // Keys are (d^2 bits, vertex index) compared as 64-bit integers, exactly as in silh_fused_kernel: the same d^2
 // expression, ties to the lowest vertex index - the two kernels give bit-identical outputs.
 constexpr int SPX_TILE = 8;      // 8 x 8 pixels per wave
+#ifndef SMPLR_SILH_LOSS_EPILOGUE_DEFAULT
+// form 0 of smplr_silh_fwd_loss: false = silh_loss_fwd_kernel behind the forward, true = the loss head inside silh_px_kernel.
+// The epilogue becomes the default only once it is measured ahead of the stand-alone kernel beyond the spread.
+#define SMPLR_SILH_LOSS_EPILOGUE_DEFAULT false
+#endif
 constexpr int SPX_EMPTY = 127;   // offset-table entry of an empty row
 
 // LDS (bytes): cell starts | offset table | row words | own-cell keys | per-wave candidate maps | records.
@@ -365,12 +373,22 @@ static SpxLds silh_px_layout(int VP, int W) {
 // A pixel whose own cell is empty then takes -log(hint) as its search radius instead of walking the rows for the
 // nearest occupied cell (step (2): a third of this kernel's time); the candidates of step (3) are a superset of
 // those the nearest vertex' cell belongs to either way, so the result is the same bit for bit.
+// LOSS: the silhouette loss head as the epilogue (silh_loss_device.h): a live lane holds its pixel's final score at the
+// store, so it also writes the pixel's loss and k = dL/ds and, with io.conf, the wave counts its (label, prediction)
+// cells by ballot - six wave-uniform counters over the wave's tiles, added to 24 B of LDS at the end and from there with
+// at most six global atomics per workgroup.  Without LOSS none of it is compiled: the same bits as before.
+template <bool LOSS>
 __global__ __launch_bounds__(SF_T) void silh_px_kernel(const float *__restrict__ proj, int VP, int W, SpxLds L,
                                                        float *__restrict__ out, int *__restrict__ arg_out,
-                                                       const float *__restrict__ hint) {
+                                                       const float *__restrict__ hint, SilhLossIO io) {
   extern __shared__ __attribute__((aligned(16))) int s_cnt[];
   __shared__ int s_next_tile;
   if (threadIdx.x == 0) s_next_tile = 0;             // (ordered by the binning's barriers)
+  __shared__ unsigned s_conf[LOSS ? 6 : 1];
+  if (LOSS && threadIdx.x < 6) s_conf[threadIdx.x] = 0u;
+  unsigned ccnt[6] = {0u, 0u, 0u, 0u, 0u, 0u};      // (LOSS) wave-uniform counts of the confusion cells
+  float lw0 = 1.0f, lw1 = 1.0f;
+  if (LOSS && io.class_w) { lw0 = io.class_w[0]; lw1 = io.class_w[1]; }
   __shared__ int s_wave[SF_T / 64];
   __shared__ int s_nout;
   const int n = blockIdx.x, tid = threadIdx.x;
@@ -514,6 +532,8 @@ __global__ __launch_bounds__(SF_T) void silh_px_kernel(const float *__restrict__
     float lim = -1.0f;                                      // squared search radius (< 0: nothing to search)
     float hs = 0.0f;                                        // the hint's score for this pixel (0: none)
     if (hint) hs = hint[((size_t)n * W + (W - 1 - r)) * W + c];
+    int lab = 0;
+    if (LOSS) lab = io.labels[((size_t)n * W + (W - 1 - r)) * W + c];   // (clamped lanes: a border pixel's, unused)
     if (best != ~0ull) {
       // (1) own cell occupied: other cells matter only if the nearest own vertex is farther than half a cell
       const float d2 = __uint_as_float((unsigned int)(best >> 32));
@@ -626,6 +646,7 @@ __global__ __launch_bounds__(SF_T) void silh_px_kernel(const float *__restrict__
       }
     }
     if (nout > 0) SMPLR_SPX_RANGE(tot_v, tot_v + nout)       // outliers: always
+    float score_l = 0.0f;                                   // (LOSS) the live lane's score, for the counts below
     if (live) {
       float score = 0.0f;
       int pos = -1;
@@ -633,9 +654,20 @@ __global__ __launch_bounds__(SF_T) void silh_px_kernel(const float *__restrict__
         score = expf(-sqrtf(__uint_as_float((unsigned int)(best >> 32))) / 1.2f);
         pos = (int)(best & 0xffffffffull);
       }
+      score_l = score;
       const size_t o = ((size_t)n * W + (W - 1 - r)) * W + c;   // rows flipped (:42)
       *reinterpret_cast<float2 *>(out + o * 2) = make_float2(1.0f - score, score);
       arg_out[o] = pos;
+      if (LOSS) {
+        const SilhLossPx lp = silh_loss_px(1.0f - score, score, lab, lw0, lw1, io.gamma);
+        io.loss[o] = lp.loss;
+        io.k[o] = lp.k;
+      }
+    }
+    if (LOSS && io.conf) {                                  // (dead lanes of a partial tile: cell -1, never counted)
+      const int cell = live ? silh_conf_cell(lab, silh_pred(1.0f - score_l, score_l)) : -1;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) ccnt[i] += (unsigned)__popcll(__ballot(cell == i));
     }
 #ifdef SMPLR_TL
     tl_a += tl_t1 - tl_t0; tl_b += tl_t2 - tl_t1; tl_c += (unsigned)clock64() - tl_t2;
@@ -645,6 +677,15 @@ __global__ __launch_bounds__(SF_T) void silh_px_kernel(const float *__restrict__
     }
     ++tl_k;
 #endif
+  }
+  if (LOSS && io.conf) {
+    if (lane == 0) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+        if (ccnt[i]) atomicAdd(&s_conf[i], ccnt[i]);
+    }
+    __syncthreads();
+    if (tid < 6 && s_conf[tid]) atomicAdd(io.conf + tid, (unsigned long long)s_conf[tid]);
   }
   SMPLR_TL_STAMP(5);
 #ifdef SMPLR_TL
@@ -749,20 +790,24 @@ int smplr_silh_fwd_form(int VP, int W) {
   return 3;
 }
 
-int smplr_silh_fwd_hint(const float *proj, const float *hint, int B, int VP, int W, float *silh, int32_t *arg,
-                        void *workspace, void *stream) {
+// the silhouette forward in whichever form fits; io (form 0 only): the loss head as silh_px_kernel's epilogue
+static int silh_fwd_launch(const float *proj, const float *hint, int B, int VP, int W, float *silh, int32_t *arg,
+                           void *workspace, hipStream_t st, const smplr::SilhLossIO *io) {
   using namespace smplr;
-  SMPLR_REQUIRE(B >= 0 && VP > 0 && W > 0 && W <= 1024, "smplr_silh_fwd: bad sizes B=%d VP=%d W=%d", B, VP, W);
-  if (B == 0) return 0;
-  SMPLR_REQUIRE(proj && silh && arg && workspace, "smplr_silh_fwd: null pointer");
-  hipStream_t st = as_stream(stream);
   const int form = smplr_silh_fwd_form(VP, W);
   if (form == 0) {
     const SpxLds L = silh_px_layout(VP, W);
     const int nsplit = B >= 256 ? 1 : (B >= 128 ? 2 : 4);      // one workgroup per CU (256 CUs)
-    int rc = lds_attr<&silh_px_kernel>(L.total);
-    if (rc) return rc;
-    hipLaunchKernelGGL(silh_px_kernel, dim3(B, nsplit), dim3(SF_T), L.total, st, proj, VP, W, L, silh, arg, hint);
+    if (io) {
+      int rc = lds_attr<&silh_px_kernel<true>>(L.total);
+      if (rc) return rc;
+      hipLaunchKernelGGL(silh_px_kernel<true>, dim3(B, nsplit), dim3(SF_T), L.total, st, proj, VP, W, L, silh, arg, hint, *io);
+    } else {
+      int rc = lds_attr<&silh_px_kernel<false>>(L.total);
+      if (rc) return rc;
+      hipLaunchKernelGGL(silh_px_kernel<false>, dim3(B, nsplit), dim3(SF_T), L.total, st, proj, VP, W, L, silh, arg, hint,
+                         SilhLossIO{});
+    }
     SMPLR_LAUNCH_CHECK("smplr_silh_fwd");
     return 0;
   }
@@ -788,6 +833,41 @@ int smplr_silh_fwd_hint(const float *proj, const float *hint, int B, int VP, int
   hipLaunchKernelGGL(silh_fwd_kernel, dim3((W * W + RT - 1) / RT, B), dim3(RT), 0, st,
                      reinterpret_cast<const float4 *>(workspace), KP, W, silh, arg);
   SMPLR_LAUNCH_CHECK("smplr_silh_fwd");
+  return 0;
+}
+
+int smplr_silh_fwd_hint(const float *proj, const float *hint, int B, int VP, int W, float *silh, int32_t *arg,
+                        void *workspace, void *stream) {
+  using namespace smplr;
+  SMPLR_REQUIRE(B >= 0 && VP > 0 && W > 0 && W <= 1024, "smplr_silh_fwd: bad sizes B=%d VP=%d W=%d", B, VP, W);
+  if (B == 0) return 0;
+  SMPLR_REQUIRE(proj && silh && arg && workspace, "smplr_silh_fwd: null pointer");
+  return silh_fwd_launch(proj, hint, B, VP, W, silh, arg, workspace, as_stream(stream), nullptr);
+}
+
+// Whether form 0 runs the loss head inside silh_px_kernel (one launch) or as silh_loss_fwd_kernel behind it (two):
+// SMPLR_SILH_LOSS_EPILOGUE=1 / 0, read at every call (an A/B run and the tests switch it inside one process; a getenv
+// is nothing beside a launch); the same bits either way (DESIGN 12 holds the measurement that sets the default).
+static bool silh_loss_epilogue() {
+  const char *e = getenv("SMPLR_SILH_LOSS_EPILOGUE");
+  return e ? atoi(e) != 0 : SMPLR_SILH_LOSS_EPILOGUE_DEFAULT;
+}
+
+int smplr_silh_fwd_loss(const float *proj, const float *hint, const int32_t *labels, const float *class_w, float gamma,
+                        int B, int VP, int W, float *silh, int32_t *arg, float *loss, float *k, int64_t *conf,
+                        void *workspace, void *stream) {
+  using namespace smplr;
+  SMPLR_REQUIRE(B >= 0 && VP > 0 && W > 0 && W <= 1024, "smplr_silh_fwd_loss: bad sizes B=%d VP=%d W=%d", B, VP, W);
+  SMPLR_REQUIRE(gamma >= 0.0f, "smplr_silh_fwd_loss: gamma=%g must be >= 0", (double)gamma);
+  if (B == 0) return 0;
+  SMPLR_REQUIRE(proj && labels && silh && arg && loss && k && workspace, "smplr_silh_fwd_loss: null pointer");
+  hipStream_t st = as_stream(stream);
+  const SilhLossIO io{labels, class_w, gamma, loss, k, reinterpret_cast<unsigned long long *>(conf)};
+  if (smplr_silh_fwd_form(VP, W) == 0 && silh_loss_epilogue())
+    return silh_fwd_launch(proj, hint, B, VP, W, silh, arg, workspace, st, &io);
+  if (int rc = silh_fwd_launch(proj, hint, B, VP, W, silh, arg, workspace, st, nullptr)) return rc;
+  launch_silh_loss_fwd(silh, io, (long long)B * W * W, st);
+  SMPLR_LAUNCH_CHECK("smplr_silh_fwd_loss");
   return 0;
 }
 

@@ -1,6 +1,6 @@
 // TORCH_LIBRARY(smplraster, ...): the at::Tensor layer SURVEY.md section 8(b) specifies on top of the extern "C"
 // launchers of libsmplraster_hip.so ("C-ABI / extension layer beneath": smpl_fwd / smpl_bwd, project_fwd / bwd,
-// visibility, seg_fwd / seg_bwd, silh_fwd / bwd - all contiguous fp32 / int tensors on one HIP device, launched on
+// visibility, seg_fwd / seg_bwd, silh_fwd / bwd (and the silhouette loss head around them) - all contiguous fp32 / int tensors on one HIP device, launched on
 // at::hip::getCurrentHIPStream()).  One host call per op instead of a dozen ctypes marshalling steps: outputs and
 // workspaces are allocated here (at::empty on the caching allocator - no hipMalloc, so the ops stay HIP-graph
 // capturable like the launchers), arguments are TORCH_CHECKed, launcher errors become c10::Error with
@@ -205,6 +205,105 @@ Tensor silh_bwd(const Tensor &dsilh, const Tensor &silh, const Tensor &sarg, con
   return dproj;
 }
 Tensor silh_bwd_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &proj, bool) { return at::empty_like(proj); }
+
+// ---- silhouette loss head (train_stage2_silhouette.py:82-86,226-234; csrc/silh_loss.hip) --------------------------------
+// labels (B,W,W) int32, class_w (2,) or None, conf (3,2) int64 or None (added to, in place) -> loss, k (B, W*W)
+struct SilhLossArgs { const int32_t *labels; const float *class_w; int64_t *conf; };
+SilhLossArgs silh_loss_check(const Tensor &ref, int64_t B, int64_t W, const Tensor &labels, const c10::optional<Tensor> &class_w,
+                             double gamma, const c10::optional<Tensor> &conf) {
+  dev_typed(labels, at::kInt, "labels");
+  TORCH_CHECK(labels.dim() == 3 && labels.size(0) == B && labels.size(1) == W && labels.size(2) == W,
+              "labels must be (B,W,W) int32 as the silhouette lies");
+  TORCH_CHECK(gamma >= 0.0, "gamma must be >= 0");
+  SilhLossArgs a{labels.data_ptr<int32_t>(), nullptr, nullptr};
+  if (class_w) {
+    dev_f32(*class_w, "class_w");
+    TORCH_CHECK(class_w->numel() == 2, "class_w needs 2 entries");
+    a.class_w = class_w->data_ptr<float>();
+  }
+  if (conf) {
+    dev_typed(*conf, at::kLong, "conf");
+    TORCH_CHECK(conf->dim() == 2 && conf->size(0) == 3 && conf->size(1) == 2, "conf must be (3, 2) int64");
+    a.conf = conf->data_ptr<int64_t>();
+  }
+  same_device(ref, {{"labels", &labels}});
+  if (class_w) same_device(ref, {{"class_w", &*class_w}});
+  if (conf) same_device(ref, {{"conf", &*conf}});
+  return a;
+}
+std::tuple<Tensor, Tensor> silh_loss_fwd(const Tensor &silh, const Tensor &labels, const c10::optional<Tensor> &class_w,
+                                         double gamma, const c10::optional<Tensor> &conf) {
+  dev_f32(silh, "silh");
+  TORCH_CHECK(silh.dim() == 4 && silh.size(1) == silh.size(2) && silh.size(3) == 2, "silh must be (B,W,W,2)");
+  const int64_t B = silh.size(0), W = silh.size(1);
+  TORCH_CHECK(W > 0, "silh_loss_fwd: W > 0");
+  const SilhLossArgs a = silh_loss_check(silh, B, W, labels, class_w, gamma, conf);
+  DeviceGuard g(silh.device());
+  Tensor loss = f32({B, W * W}, silh), k = f32({B, W * W}, silh);
+  ok(smplr_silh_loss_fwd(fp(silh), a.labels, a.class_w, (float)gamma, (int)B, (int)W, fpm(loss), fpm(k), a.conf, cur_stream()),
+     "smplr_silh_loss_fwd");
+  return {loss, k};
+}
+std::tuple<Tensor, Tensor> silh_loss_fwd_meta(const Tensor &silh, const Tensor &, const c10::optional<Tensor> &, double,
+                                              const c10::optional<Tensor> &) {
+  const int64_t B = silh.size(0), W = silh.size(1);
+  return {at::empty({B, W * W}, silh.options()), at::empty({B, W * W}, silh.options())};
+}
+// -> silh (B,W,W,2), arg (B,W,W) int32, loss, k (B, W*W); hint (B,W,W) or None as smplr_silh_fwd_hint takes it
+std::tuple<Tensor, Tensor, Tensor, Tensor> silh_fwd_loss(const Tensor &proj, const c10::optional<Tensor> &hint, const Tensor &labels,
+                                                         const c10::optional<Tensor> &class_w, double gamma, int64_t W,
+                                                         const c10::optional<Tensor> &conf) {
+  dev_f32(proj, "proj");
+  TORCH_CHECK(proj.dim() == 3 && proj.size(2) == 3, "proj must be (B, VP, 3)");
+  TORCH_CHECK(W > 0, "silh_fwd_loss: W > 0");
+  const int64_t B = proj.size(0), VP = proj.size(1);
+  const SilhLossArgs a = silh_loss_check(proj, B, W, labels, class_w, gamma, conf);
+  if (hint) {
+    dev_f32(*hint, "hint");
+    TORCH_CHECK(hint->dim() == 3 && hint->size(0) == B && hint->size(1) == W && hint->size(2) == W, "hint must be (B,W,W)");
+    same_device(proj, {{"hint", &*hint}});
+  }
+  DeviceGuard g(proj.device());
+  Tensor silh = f32({B, W, W, 2}, proj), sarg = at::empty({B, W, W}, proj.options().dtype(at::kInt));
+  Tensor loss = f32({B, W * W}, proj), k = f32({B, W * W}, proj);
+  Tensor ws = bytes(smplr_silh_workspace((int)B, (int)VP, (int)W), proj);
+  ok(smplr_silh_fwd_loss(fp(proj), hint ? fp(*hint) : nullptr, a.labels, a.class_w, (float)gamma, (int)B, (int)VP, (int)W,
+                         fpm(silh), sarg.data_ptr<int32_t>(), fpm(loss), fpm(k), a.conf, ws.data_ptr(), cur_stream()),
+     "smplr_silh_fwd_loss");
+  return {silh, sarg, loss, k};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> silh_fwd_loss_meta(const Tensor &proj, const c10::optional<Tensor> &, const Tensor &,
+                                                              const c10::optional<Tensor> &, double, int64_t W,
+                                                              const c10::optional<Tensor> &) {
+  const int64_t B = proj.size(0);
+  return {at::empty({B, W, W, 2}, proj.options()), at::empty({B, W, W}, proj.options().dtype(at::kInt)),
+          at::empty({B, W * W}, proj.options()), at::empty({B, W * W}, proj.options())};
+}
+Tensor silh_loss_bwd(const Tensor &dloss, const Tensor &k, const Tensor &silh, const Tensor &sarg, const Tensor &proj,
+                     bool deterministic) {
+  dev_f32(dloss, "dloss");
+  dev_f32(k, "k");
+  dev_f32(silh, "silh");
+  dev_typed(sarg, at::kInt, "arg");
+  dev_f32(proj, "proj");
+  TORCH_CHECK(proj.dim() == 3 && proj.size(2) == 3, "proj must be (B, VP, 3)");
+  TORCH_CHECK(silh.dim() == 4 && silh.size(0) == proj.size(0) && silh.size(1) == silh.size(2) && silh.size(3) == 2,
+              "silh must be (B,W,W,2) as silh_fwd_loss returned it");
+  const int64_t B = proj.size(0), VP = proj.size(1), W = silh.size(1);
+  TORCH_CHECK(dloss.dim() == 2 && dloss.size(0) == B && dloss.size(1) == W * W, "dloss must be (B, W*W)");
+  TORCH_CHECK(k.sizes() == dloss.sizes(), "k must have dloss' shape");
+  TORCH_CHECK(sarg.dim() == 3 && sarg.size(0) == B && sarg.size(1) == W && sarg.size(2) == W,
+              "arg must be (B,W,W) int32 as silh_fwd_loss returned it");
+  same_device(proj, {{"dloss", &dloss}, {"k", &k}, {"silh", &silh}, {"arg", &sarg}});
+  DeviceGuard g(proj.device());
+  Tensor dproj = f32({B, VP, 3}, proj);
+  ok(smplr_silh_loss_bwd(fp(dloss), fp(k), fp(silh), sarg.data_ptr<int32_t>(), fp(proj), (int)B, (int)VP, (int)W, fpm(dproj),
+                         deterministic ? 1 : 0, cur_stream()), "smplr_silh_loss_bwd");
+  return dproj;
+}
+Tensor silh_loss_bwd_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &proj, bool) {
+  return at::empty_like(proj);
+}
 
 // ---- SMPLLayer.call ---------------------------------------------------------------------------------------
 // consts (the device constants of SMPLLayer.build, ops.SMPLConstants.as_list()):
@@ -640,6 +739,10 @@ TORCH_LIBRARY(smplraster, m) {
   m.def("seg_bwd(Tensor dseg, Tensor arg, Tensor rec, int VP, int P, int K, bool deterministic=False) -> Tensor");
   m.def("silh_fwd(Tensor proj, int W) -> (Tensor, Tensor)");
   m.def("silh_bwd(Tensor dsilh, Tensor silh, Tensor arg, Tensor proj, bool deterministic=False) -> Tensor");
+  m.def("silh_loss_fwd(Tensor silh, Tensor labels, Tensor? class_w, float gamma, Tensor(a!)? conf) -> (Tensor, Tensor)");
+  m.def("silh_fwd_loss(Tensor proj, Tensor? hint, Tensor labels, Tensor? class_w, float gamma, int W, Tensor(a!)? conf) -> "
+        "(Tensor, Tensor, Tensor, Tensor)");
+  m.def("silh_loss_bwd(Tensor dloss, Tensor k, Tensor silh, Tensor arg, Tensor proj, bool deterministic=False) -> Tensor");
   m.def("smpl_fwd(Tensor x, Tensor[] consts, int num_cam=4) -> Tensor[]");
   m.def("smpl_bwd(Tensor? dverts, Tensor? dproj, Tensor? dJ_transformed, Tensor x, Tensor[] consts, Tensor Rs, Tensor J, "
         "Tensor A, Tensor v_posed, int num_cam=4, int vertex_sampling=1) -> Tensor");
@@ -664,6 +767,9 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("seg_bwd", &seg_bwd);
   m.impl("silh_fwd", &silh_fwd);
   m.impl("silh_bwd", &silh_bwd);
+  m.impl("silh_loss_fwd", &silh_loss_fwd);
+  m.impl("silh_fwd_loss", &silh_fwd_loss);
+  m.impl("silh_loss_bwd", &silh_loss_bwd);
   m.impl("smpl_fwd", &smpl_fwd);
   m.impl("smpl_bwd", &smpl_bwd);
   m.impl("decoder_fwd", &decoder_fwd);
@@ -682,6 +788,9 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("seg_bwd", &seg_bwd_meta);
   m.impl("silh_fwd", &silh_fwd_meta);
   m.impl("silh_bwd", &silh_bwd_meta);
+  m.impl("silh_loss_fwd", &silh_loss_fwd_meta);
+  m.impl("silh_fwd_loss", &silh_fwd_loss_meta);
+  m.impl("silh_loss_bwd", &silh_loss_bwd_meta);
   m.impl("smpl_fwd", &smpl_fwd_meta);
   m.impl("smpl_bwd", &smpl_bwd_meta);
   m.impl("decoder_fwd", &decoder_fwd_meta);

@@ -27,11 +27,16 @@ class SMPLDecoder(nn.Module):
     loss: a `focal_loss.softmax_focal_loss(...)` - the loss head (model.py:119-120 + focal_loss.py:10-46) then runs
     inside the rasteriser: `forward(x, labels)` with an integer class map (B, W, W) returns `seg_loss` (B, W*W), the
     per-pixel loss, and the (B, W, W, 32) scores and their gradient never exist in memory (`seg` is returned only
-    with keep_seg=True, detached)."""
+    with keep_seg=True, detached).
+    silh_loss: a `focal_loss.softmax_focal_loss(...)` for the silhouette head (gamma = 0 without weights is the
+    reference's categorical cross-entropy, train_stage2_silhouette.py:85-86,226-229): `forward(x, silh_labels=...)` with
+    an integer map (B, silh_wh, silh_wh) returns `silh_loss` (B, silh_wh**2) computed around the silhouette rasteriser
+    (softmax, loss, gradient and accuracy counts fused; no (B, Ws, Ws, 2) gradient in memory); `silhouette` is still
+    returned, detached."""
 
     def __init__(self, smpl_path=None, img_wh=48, vertex_sampling=None, num_cam=4, grid_wh=64,
                  ref_compat=True, with_silhouette=False, streams=1, silh_wh=None, deterministic=False,
-                 heads=None, outputs=("verts", "projects", "mask"), loss=None, keep_seg=False):
+                 heads=None, outputs=("verts", "projects", "mask"), loss=None, keep_seg=False, silh_loss=None):
         super().__init__()
         self._model = _resolve_model(smpl_path)
         self.img_wh = int(img_wh)
@@ -67,6 +72,12 @@ class SMPLDecoder(nn.Module):
             if not hasattr(loss, "gamma") or not hasattr(loss, "weight_classes"):
                 raise ValueError("loss must come from focal_loss.softmax_focal_loss(gamma, weight_classes)")
         self.loss = loss
+        if silh_loss is not None:
+            if "silhouette" not in heads:
+                raise ValueError("a fused silhouette loss needs the 'silhouette' head")
+            if not hasattr(silh_loss, "gamma") or not hasattr(silh_loss, "weight_classes"):
+                raise ValueError("silh_loss must come from focal_loss.softmax_focal_loss(gamma, weight_classes)")
+        self.silh_loss = silh_loss
         self.keep_seg = bool(keep_seg)
         self._consts = None
         self._dev = None
@@ -84,8 +95,11 @@ class SMPLDecoder(nn.Module):
         self._consts = None
         return self
 
-    def forward(self, x, labels=None, confusion=None):
-        """Returns dict(J_transformed [, verts, projects, mask] [, seg | seg_loss] [, silhouette]).
+    def forward(self, x, labels=None, confusion=None, silh_labels=None, silh_confusion=None):
+        """Returns dict(J_transformed [, verts, projects, mask] [, seg | seg_loss] [, silhouette [, silh_loss]]).
+        silh_labels (B, silh_wh, silh_wh) integer, with `silh_loss=`: adds `silh_loss` (B, silh_wh**2); a label outside
+        {0, 1} contributes 0.  silh_confusion: a `metrics.SegConfusion(2, device)` (or its (3, 2) int64 `counts`) that
+        the loss head adds each pixel's (label, s > 1 - s) count to.
         confusion: a `metrics.SegConfusion(32, device)` (or its (33, 32) int64 `counts`) that each pixel's (label,
         arg-max of the 32 scores) is added to - by the rasteriser's loss epilogue when the loss is fused (no scores
         written), else by the confusion kernel on `seg`.  Needs `labels`; the returned dict is unchanged."""
@@ -96,7 +110,7 @@ class SMPLDecoder(nn.Module):
         # gradient-free forward of the plain decoder (predict.py:99-118): ONE host call into the at::Tensor layer
         # (torch.ops.smplraster.decoder_fwd, csrc/torch_ops.cpp) instead of the autograd node's ctypes calls - the same
         # two launches, outputs bit for bit; at batch 1 the eager forward is host-bound and this is what it costs
-        if (labels is None and self.heads == ("seg",) and self.vs == 1 and self.streams == 1 and c.blend3_fwd is not None
+        if (labels is None and silh_labels is None and self.heads == ("seg",) and self.vs == 1 and self.streams == 1 and c.blend3_fwd is not None
                 and not (torch.is_grad_enabled() and x.requires_grad) and x.is_cuda and x.dtype == torch.float32
                 and x.shape[0] < ops.POSE_BLEND_SPLIT_B
                 # (the one-call op always skins inside the binning launch: an A/B run that switches that off must get
@@ -120,6 +134,20 @@ class SMPLDecoder(nn.Module):
         fused = self.loss is not None and labels is not None
         if labels is not None and self.loss is None and conf is None:
             raise RuntimeError("labels were given but the decoder was built without loss=softmax_focal_loss(...)")
+        sconf = getattr(silh_confusion, "counts", silh_confusion)
+        if silh_labels is not None and self.silh_loss is None:
+            raise RuntimeError("silh_labels were given but the decoder was built without silh_loss=softmax_focal_loss(...)")
+        if sconf is not None and silh_labels is None:
+            raise RuntimeError("silh_confusion is counted by the fused silhouette loss: needs silh_labels")
+        sspec = None
+        if silh_labels is not None:
+            from .focal_loss import class_weights
+            Ws = self.silh_wh
+            if (silh_labels.numel() != x.shape[0] * Ws * Ws
+                    or silh_labels.dtype not in (torch.int64, torch.int32, torch.int16, torch.uint8)):
+                raise RuntimeError("silh_labels must be an integer map of %d x %d x %d entries" % (x.shape[0], Ws, Ws))
+            sw = class_weights(x.device)[:2].contiguous() if self.silh_loss.weight_classes else None
+            sspec = (silh_labels.to(torch.int32).reshape(x.shape[0], Ws, Ws), sw, float(self.silh_loss.gamma))
         spec = None
         if fused:
             from .focal_loss import class_weights
@@ -127,11 +155,13 @@ class SMPLDecoder(nn.Module):
             spec = (labels, w, float(self.loss.gamma))
         opts = ops.DecoderOpts(want_verts="verts" in self.outputs, want_proj="projects" in self.outputs,
                                want_mask="mask" in self.outputs, seg="seg" in self.heads,
-                               want_seg=(not fused) or self.keep_seg, loss=spec, confusion=conf if fused else None)
-        verts, proj, mask, seg, silh, jt, loss = ops.DecoderFn.apply(
+                               want_seg=(not fused) or self.keep_seg, loss=spec, confusion=conf if fused else None,
+                               silh_loss=sspec, silh_confusion=sconf)
+        res = ops.DecoderFn.apply(
             x, c, self.num_cam, self.img_wh, self.vs, pt, self.grid_wh, self.ref_compat,
             (True if self.silh_wh == self.img_wh else self.silh_wh) if self.with_silhouette else False, self.streams,
             self.deterministic, opts)
+        verts, proj, mask, seg, silh, jt, loss = res[:7]
         out = dict(J_transformed=jt)
         if "verts" in self.outputs:
             out["verts"] = verts
@@ -151,4 +181,6 @@ class SMPLDecoder(nn.Module):
                     seg_confusion(seg.detach(), labels, conf)
         if self.with_silhouette:
             out["silhouette"] = silh
+            if sspec is not None:
+                out["silh_loss"] = res[7]
         return out

@@ -548,6 +548,67 @@ def _silh_bwd(dsilh, silh, arg, proj, W, deterministic=False):
     return dproj
 
 
+def _silh_loss_args(labels, class_w, conf, B, W, like):
+    if labels.dtype != torch.int32 or tuple(labels.shape) != (B, W, W):
+        raise RuntimeError("silhouette labels must be (%d, %d, %d) int32, got %s %s"
+                           % (B, W, W, tuple(labels.shape), labels.dtype))
+    labels = require_cuda(labels, "silhouette labels", torch.int32)
+    if class_w is not None:
+        class_w = require_cuda(class_w, "class_w")
+        if class_w.numel() != 2:
+            raise RuntimeError("the silhouette loss takes 2 class weights, got %d" % class_w.numel())
+    if conf is not None and (not conf.is_cuda or conf.dtype != torch.int64 or tuple(conf.shape) != (3, 2)
+                             or not conf.is_contiguous()):
+        raise RuntimeError("the silhouette confusion must be a contiguous (3, 2) int64 device tensor (SegConfusion(2).counts)")
+    for name, t in (("labels", labels), ("class_w", class_w), ("confusion", conf)):
+        if t is not None and t.device != like.device:
+            raise RuntimeError("silhouette %s lives on %s, the silhouette on %s" % (name, t.device, like.device))
+    return labels, class_w
+
+
+@on_device
+def _silh_loss_fwd(silh, labels, class_w=None, gamma=0.0, conf=None, out=None):
+    """The silhouette loss head over a written silhouette (smplr_silh_loss_fwd): silh (B,W,W,2), labels (B,W,W) int32,
+    class_w (2,) or None -> loss, k = d loss / d s (B, W*W); conf (3, 2) int64: += the (label, s > 1 - s) counts."""
+    lib = _lib.load()
+    silh = require_cuda(silh, "silh")
+    B, W = silh.shape[0], silh.shape[1]
+    labels, class_w = _silh_loss_args(labels, class_w, conf, B, W, silh)
+    loss, k = out if out is not None else (_empty((B, W * W), silh), _empty((B, W * W), silh))
+    check(lib.smplr_silh_loss_fwd(ptr(silh), ptr(labels), ptr(class_w), float(gamma), B, W, ptr(loss), ptr(k), ptr(conf),
+                                  stream()), "smplr_silh_loss_fwd")
+    return loss, k
+
+
+@on_device
+def _silh_fwd_loss(proj, W, labels, class_w=None, gamma=0.0, conf=None, out=None, hint=None):
+    """_silh_fwd + _silh_loss_fwd as one call (smplr_silh_fwd_loss: the loss head as the pixel-per-lane kernel's epilogue
+    where that kernel runs, else behind the forward) -> silh, arg, loss, k; the same bits as the two calls."""
+    lib = _lib.load()
+    B, VP = proj.shape[0], proj.shape[1]
+    labels, class_w = _silh_loss_args(labels, class_w, conf, B, W, proj)
+    if out is not None:
+        silh, arg, loss, k = out
+    else:
+        silh, arg = _empty((B, W, W, 2), proj), _empty((B, W, W), proj, torch.int32)
+        loss, k = _empty((B, W * W), proj), _empty((B, W * W), proj)
+    ws = _workspace(lib.smplr_silh_workspace(B, VP, W), proj)
+    check(lib.smplr_silh_fwd_loss(ptr(proj), ptr(hint), ptr(labels), ptr(class_w), float(gamma), B, VP, W, ptr(silh),
+                                  ptr(arg), ptr(loss), ptr(k), ptr(conf), ptr(ws), stream()), "smplr_silh_fwd_loss")
+    return silh, arg, loss, k
+
+
+@on_device
+def _silh_loss_bwd(dloss, k, silh, arg, proj, W, deterministic=False):
+    """_silh_bwd fed g = dloss * k (B, W*W each) instead of dsilh (smplr_silh_loss_bwd)."""
+    lib = _lib.load()
+    B, VP = proj.shape[0], proj.shape[1]
+    dproj = _empty((B, VP, 3), proj)
+    check(lib.smplr_silh_loss_bwd(ptr(dloss), ptr(k), ptr(silh), ptr(arg), ptr(proj), B, VP, W, ptr(dproj),
+                                  1 if deterministic else 0, stream()), "smplr_silh_loss_bwd")
+    return dproj
+
+
 # --------------------------------------------------------------------------- autograd nodes
 class BatchSMPLFn(torch.autograd.Function):
     """x (B, num_cam+82) -> verts (B,V,3), J_transformed (B,24,3)."""
@@ -933,6 +994,12 @@ class DecoderOpts:
     # with `loss`: a (33, 32) int64 device tensor the loss epilogue adds each pixel's (label, arg-max of the 32 scores)
     # count to (metrics.SegConfusion.counts; every chunk adds into the same tensor)
     confusion: Optional[torch.Tensor] = None
+    # the silhouette loss head fused around the silhouette rasteriser (train_stage2_silhouette.py:82-86,226-234):
+    # (labels (B,Ws,Ws) int32, class_w (2,) or None, gamma) -> the pass returns an EIGHTH output, the per-pixel silhouette
+    # loss (B, Ws*Ws), and the silhouette itself is a by-product (not differentiable)
+    silh_loss: Optional[tuple] = None
+    # with `silh_loss`: a (3, 2) int64 device tensor += each pixel's (label, s > 1 - s) count (SegConfusion(2).counts)
+    silh_confusion: Optional[torch.Tensor] = None
 
 
 # Batch from which the decoder's forward runs the pose kernel and the blend GEMM as two launches instead of one: the
@@ -961,7 +1028,8 @@ class DecoderFn(torch.autograd.Function):
     """The model.py:108-118 chain as ONE autograd node.
 
     x (B, 86) -> verts (B,V,3), proj (B,V',3), mask (B,V'), seg (B,W,W,32), silh (B,W,W,2), J_transformed, loss (B,W*W)
-    (outputs that were not asked for - DecoderOpts - come back as empty tensors).
+    (outputs that were not asked for - DecoderOpts - come back as empty tensors) and, only with `opts.silh_loss`, an eighth:
+    silh_loss (B,Ws*Ws), whose cotangent drives smplr_silh_loss_bwd (no (B,Ws,Ws,2) gradient in memory).
     The projection is the skinning kernel's epilogue, the mask is computed in between, and the
     backward fuses d(seg)/d(silh)/d(verts)/d(proj) into one skinning-backward launch.  With `opts.loss` the loss
     head runs as the rasteriser's epilogue and its backward inside the rasteriser's backward: the (B,W,W,32) scores
@@ -1037,6 +1105,17 @@ class DecoderFn(torch.autograd.Function):
             silh, sarg = _empty((B, Ws, Ws, 2), x), _empty((B, Ws, Ws), x, torch.int32)
         else:
             silh = sarg = None
+        sl_spec = opts.silh_loss
+        sl_labels = sl_w = sloss = sk = None
+        sl_gamma, sconf = 0.0, opts.silh_confusion
+        if sl_spec is not None:
+            if not with_silh:
+                raise RuntimeError("DecoderOpts.silh_loss needs the silhouette head")
+            sl_labels, sl_w, sl_gamma = sl_spec
+            sl_labels, sl_w = _silh_loss_args(sl_labels, sl_w, sconf, B, Ws, x)
+            sloss, sk = _empty((B, Ws * Ws), x), _empty((B, Ws * Ws), x)
+        elif sconf is not None:
+            raise RuntimeError("DecoderOpts.silh_confusion rides on the fused silhouette loss: it needs DecoderOpts.silh_loss")
         # both heads at one resolution: the part rasteriser hands the silhouette rasteriser each pixel's largest part
         # score - an upper bound of the distance to the nearest vertex that spares it its own search for one
         # (only where the silhouette rasteriser reads it: its pixel-per-lane kernel, W <= SILH_HINT_MAX_W - beyond that
@@ -1085,7 +1164,10 @@ class DecoderFn(torch.autograd.Function):
                     else:
                         _vis_seg_fwd(pj, W, pt, grid_wh, ref_compat,
                                      out=(mk, seg[lo:hi], arg[lo:hi], rec[lo:hi]), vslot=vslot[lo:hi])
-            if with_silh:
+            if with_silh and sl_spec is not None:
+                _silh_fwd_loss(proj[lo:hi], Ws, sl_labels[lo:hi], sl_w, sl_gamma, sconf,
+                               out=(silh[lo:hi], sarg[lo:hi], sloss[lo:hi], sk[lo:hi]), hint=sl(vmax, lo, hi))
+            elif with_silh:
                 _silh_fwd(proj[lo:hi], Ws, out=(silh[lo:hi], sarg[lo:hi]), hint=sl(vmax, lo, hi))
 
         bounds = _chunk_bounds(B, nchunk)
@@ -1095,25 +1177,32 @@ class DecoderFn(torch.autograd.Function):
         ctx.Ws, ctx.VP = Ws, VP
         ctx.det = bool(deterministic)
         ctx.bounds = bounds
-        ctx.has_seg, ctx.has_loss = bool(opts.seg), loss_spec is not None
+        ctx.has_seg, ctx.has_loss, ctx.has_silh_loss = bool(opts.seg), loss_spec is not None, sl_spec is not None
         E = none
         saved = [x, Rs, J, A, v_posed, proj if with_silh else E(), arg if opts.seg else E(), rec if opts.seg else E(),
                  silh if with_silh else E(), sarg if with_silh else E(), vslot if opts.seg else E(),
                  stats if loss_spec is not None else E()]
+        if sl_spec is not None:
+            saved.append(sk)
         ctx.save_for_backward(*saved)
         outs = [t if t is not None else E() for t in (verts, proj, mask, seg, silh, Jt, loss)]
         ctx.mark_non_differentiable(outs[2])
         if loss_spec is not None:
             ctx.mark_non_differentiable(outs[3])         # with a fused loss the scores are a by-product, not a path
+        if sl_spec is not None:
+            ctx.mark_non_differentiable(outs[4])         # likewise the silhouette (the monitor pass and the backward read it)
+            outs.append(sloss)                           # the eighth output exists only with a fused silhouette loss
         return tuple(outs)
 
     @staticmethod
     @on_device
-    def backward(ctx, dverts, dproj_in, _dmask, dseg, dsilh, dJt, dloss):
-        x, Rs, J, A, v_posed, proj, arg, rec, silh, sarg, vslot, stats = ctx.saved_tensors
+    def backward(ctx, dverts, dproj_in, _dmask, dseg, dsilh, dJt, dloss, dsloss=None):
+        x, Rs, J, A, v_posed, proj, arg, rec, silh, sarg, vslot, stats = ctx.saved_tensors[:12]
+        sk = ctx.saved_tensors[12] if ctx.has_silh_loss else None
         dseg = require_cuda(dseg, "dseg") if (dseg is not None and ctx.has_seg and not ctx.has_loss) else None
         dloss = require_cuda(dloss, "dloss") if (dloss is not None and ctx.has_loss) else None
-        dsilh = require_cuda(dsilh, "dsilh") if (ctx.with_silh and dsilh is not None) else None
+        dsilh = require_cuda(dsilh, "dsilh") if (ctx.with_silh and dsilh is not None and not ctx.has_silh_loss) else None
+        dsloss = require_cuda(dsloss, "dsilh_loss") if (dsloss is not None and ctx.has_silh_loss) else None
         dproj_in = require_cuda(dproj_in, "dproj") if dproj_in is not None else None
         dverts = require_cuda(dverts, "dverts") if dverts is not None else None
         dJt = require_cuda(dJt, "dJ_transformed") if dJt is not None else None
@@ -1134,6 +1223,8 @@ class DecoderFn(torch.autograd.Function):
             if dsilh is not None:
                 d2 = _silh_bwd(dsilh[lo:hi], silh[lo:hi], sarg[lo:hi], proj[lo:hi], ctx.Ws, ctx.det)
                 dproj = d2 if dproj is None else dproj + d2
+            elif dsloss is not None:
+                dproj = _silh_loss_bwd(dsloss[lo:hi], sk[lo:hi], silh[lo:hi], sarg[lo:hi], proj[lo:hi], ctx.Ws, ctx.det)
             if dproj_in is not None:
                 dproj = dproj_in[lo:hi] if dproj is None else dproj + dproj_in[lo:hi]
             dv = dverts[lo:hi] if dverts is not None else None

@@ -33,6 +33,12 @@ SCHEMAS = {
     "seg_bwd": "smplraster::seg_bwd(Tensor dseg, Tensor arg, Tensor rec, int VP, int P, int K, bool deterministic=False) -> Tensor",
     "silh_fwd": "smplraster::silh_fwd(Tensor proj, int W) -> (Tensor, Tensor)",
     "silh_bwd": "smplraster::silh_bwd(Tensor dsilh, Tensor silh, Tensor arg, Tensor proj, bool deterministic=False) -> Tensor",
+    "silh_loss_fwd": ("smplraster::silh_loss_fwd(Tensor silh, Tensor labels, Tensor? class_w, float gamma, Tensor(a!)? conf) -> "
+                      "(Tensor, Tensor)"),
+    "silh_fwd_loss": ("smplraster::silh_fwd_loss(Tensor proj, Tensor? hint, Tensor labels, Tensor? class_w, float gamma, int W, "
+                      "Tensor(a!)? conf) -> (Tensor, Tensor, Tensor, Tensor)"),
+    "silh_loss_bwd": ("smplraster::silh_loss_bwd(Tensor dloss, Tensor k, Tensor silh, Tensor arg, Tensor proj, "
+                      "bool deterministic=False) -> Tensor"),
     "smpl_fwd": "smplraster::smpl_fwd(Tensor x, Tensor[] consts, int num_cam=4) -> Tensor[]",
     "smpl_bwd": ("smplraster::smpl_bwd(Tensor? dverts, Tensor? dproj, Tensor? dJ_transformed, Tensor x, Tensor[] consts, "
                  "Tensor Rs, Tensor J, Tensor A, Tensor v_posed, int num_cam=4, int vertex_sampling=1) -> Tensor"),

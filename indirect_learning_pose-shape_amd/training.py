@@ -39,7 +39,9 @@ class SegTrainer:
 
     def __init__(self, smpl_path=None, input_wh=256, output_wh=48, encoder_architecture="enet", use_IEF=True,
                  weight_classes=True, gamma=2.0, lr=1e-4, device=None, ddp=False, bucket_mb=25,
-                 with_silhouette=False, silh_wh=None, fused_loss=True):
+                 with_silhouette=False, silh_wh=None, fused_loss=True, fused_silh_loss=False):
+        if fused_silh_loss and not with_silhouette:
+            raise ValueError("fused_silh_loss needs with_silhouette=True")
         self.device = (torch.device(device) if device is not None
                        else torch.device("cuda", torch.cuda.current_device()))
         if self.device.type == "cuda" and os.environ.get("SMPLR_CONV_BACKEND", "default") == "find":
@@ -58,8 +60,12 @@ class SegTrainer:
         self.silh_loss_fn = softmax_focal_loss(0.0, False)            # softmax + categorical CE
         # the train pass consumes losses only: verts / projects / mask are not written out, and with an integer class
         # map the segmentation loss runs inside the rasteriser (no (B,W,W,32) score or gradient tensor in memory)
+        # fused_silh_loss (opt-in): the silhouette cross-entropy, its gradient and the accuracy counts run around the
+        # silhouette rasteriser too (SMPLDecoder(silh_loss=...)), in the joint step and in the silhouette-only step
+        self.fused_silh_loss = bool(fused_silh_loss)
+        silh_head = self.silh_loss_fn if fused_silh_loss else None
         self.decoder = SMPLDecoder(smpl_path, img_wh=output_wh, with_silhouette=with_silhouette, silh_wh=silh_wh,
-                                   outputs=(), loss=self.loss_fn if fused_loss else None)
+                                   outputs=(), loss=self.loss_fn if fused_loss else None, silh_loss=silh_head)
         self.with_silhouette = with_silhouette
         # what the reference's monitor step reads every 10 trials (train.py:245-300: `verts_model` / `projects_model` /
         # `segs_model` predictions of the monitor images): verts, projects, mask and the raw scores - the train
@@ -68,7 +74,8 @@ class SegTrainer:
         self.monitor_decoder = SMPLDecoder(smpl_path, img_wh=output_wh, with_silhouette=with_silhouette,
                                            silh_wh=silh_wh).share_constants(self.decoder)
         # the silhouette-only pass of the reference's alternating schedule (train_stage2_silhouette.py:262-270)
-        self.silh_decoder = (SMPLDecoder(smpl_path, img_wh=output_wh, heads=("silhouette",), silh_wh=silh_wh, outputs=())
+        self.silh_decoder = (SMPLDecoder(smpl_path, img_wh=output_wh, heads=("silhouette",), silh_wh=silh_wh, outputs=(),
+                                         silh_loss=silh_head)
                              .share_constants(self.decoder)) if with_silhouette else None
         self.net = self.smpl_model
         if ddp:
@@ -101,21 +108,28 @@ class SegTrainer:
             # the silhouette head alone - no mask, no binning, no 31-part rasteriser
             if self.silh_decoder is None or silh_labels is None:
                 raise RuntimeError("a step without labels is the silhouette-only step: needs with_silhouette and silh_labels")
-            out = self.silh_decoder(param)
-            loss = self.silh_loss_fn(silh_labels, out["silhouette"]).mean()
-            if silh_m is not None:
-                silh_m.update(out["silhouette"], as_map(silh_labels))
+            if self.fused_silh_loss:
+                loss = self.silh_decoder(param, silh_labels=as_map(silh_labels), silh_confusion=silh_m)["silh_loss"].mean()
+            else:
+                out = self.silh_decoder(param)
+                loss = self.silh_loss_fn(silh_labels, out["silhouette"]).mean()
+                if silh_m is not None:
+                    silh_m.update(out["silhouette"], as_map(silh_labels))
         else:
             is_map = labels.dtype in (torch.int64, torch.int32, torch.int16, torch.uint8)
+            fused_silh = self.fused_silh_loss and silh_labels is not None
+            skw = dict(silh_labels=as_map(silh_labels), silh_confusion=silh_m) if fused_silh else {}
             if self.decoder.loss is not None and is_map:           # model.py:119-120 + focal_loss.py, in the rasteriser
-                loss = self.decoder(param, labels, confusion=seg_m)
+                loss = self.decoder(param, labels, confusion=seg_m, **skw)
                 out, loss = loss, loss["seg_loss"].mean()
             else:
-                out = self.decoder(param)
+                out = self.decoder(param, **skw)
                 loss = self.loss_fn(labels, out["seg"]).mean()
                 if seg_m is not None:
                     seg_m.update(out["seg"], as_map(labels))
-            if self.with_silhouette and silh_labels is not None:  # train_stage2_silhouette.py:85-86,226-229
+            if fused_silh:
+                loss = loss + out["silh_loss"].mean()
+            elif self.with_silhouette and silh_labels is not None:  # train_stage2_silhouette.py:85-86,226-229
                 loss = loss + self.silh_loss_fn(silh_labels, out["silhouette"]).mean()
                 if silh_m is not None:
                     silh_m.update(out["silhouette"], as_map(silh_labels))
