@@ -5,14 +5,23 @@
 // channels only: on ENet's 16-channel 128x128 and 64x64 maps (B = 256: 268 / 67 MB per tensor) it moves
 // 0.5-0.75 TB/s and is a third of the reference train step on this GPU (27.5 of 75 ms, plus 4.8 ms of
 // PReLU).  Here every pass is cut into (image, channel, 4096-element chunk) workgroups like act.hip:
-//   forward : stats (sum x, sum x^2 per chunk) -> finalize (per channel, fixed order, in double; running
-//             statistics updated as torch.nn.BatchNorm2d does) -> apply y = (x - mean) rstd gamma + beta,
+//   forward : stats (sum (x - K), sum (x - K)^2 per chunk, K = the channel's first element of image 0) ->
+//             finalize (per channel, fixed order, in double: mean = K + S / M, var = Q / M - (S / M)^2; running
+//             statistics updated as torch.nn.BatchNorm2d does) -> apply y = (x - mean) (rstd gamma) + beta,
 //             z = y > 0 ? y : a y;
 //   backward: with x_hat and y recomputed from x (nothing but mean / rstd is saved),
 //             dy = dz (y > 0 ? 1 : a);  partial sums of dy, dy x_hat, dz y [y <= 0] -> finalize ->
 //             dx = gamma rstd (dy - mean(dy) - x_hat mean(dy x_hat)).
 // NCHW, fp32, HBM-bound: forward 3 passes over the tensor, backward 5 (the unfused pair: 5 and 8).
 // Every reduction has a fixed order (no atomics): results are run-to-run identical.
+// The sums are taken about the pivot K because E[x^2] - mean^2 on fp32 chunk sums loses mean^2 / var of its digits,
+// and a channel whose offset is large against its spread is ordinary after a biased convolution.  About K the loss is
+// (K - mean)^2 / var instead.  K is ONE sample of the channel (x[0, c, 0]): for planes without heavy tails it lies a few
+// standard deviations from the mean and nothing that matters cancels; where that element is an outlier (a sparse plane
+// whose first element is one of its rare spikes: (K - mean)^2 / var ~ 1 / share of spikes) the sums lose that many digits,
+// as E[x^2] - mean^2 does for a channel with mean^2 / var of that size.  The same holds for the apply: y is formed from
+// x - mean, never from a shift mean * rstd * gamma rounded to fp32, and forward and backward share bn_y() so that
+// they agree on the PReLU branch of every element.
 #include "common.h"
 
 namespace smplr {
@@ -35,25 +44,32 @@ __device__ __forceinline__ void block_store3(float s0, float s1, float s2, float
   }
 }
 
-// part[(plane * chunks + chunk) * 2 + {0, 1}] = sum x, sum x^2 of the chunk
-__global__ __launch_bounds__(BN_T) void bn_stats_kernel(const float *__restrict__ x, int HW, int chunks,
+// the normalised, scaled and shifted value of one element: THE expression of the forward and of the backward's
+// sign test (sc = rstd * gamma)
+__device__ __forceinline__ float bn_y(float xv, float mu, float sc, float b) { return fmaf(xv - mu, sc, b); }
+
+// part[(plane * chunks + chunk) * 2 + {0, 1}] = sum (x - K), sum (x - K)^2 of the chunk, K = x[0, c, 0]: the pivot
+// of channel c, which every workgroup of the channel (and the finalize) reads from the same place
+__global__ __launch_bounds__(BN_T) void bn_stats_kernel(const float *__restrict__ x, int C, int HW, int chunks,
                                                         float *__restrict__ part) {
   __shared__ float red[12];
   const long long plane = blockIdx.x / chunks;
   const int chunk = blockIdx.x - (int)(plane * chunks);
+  const float K = x[(size_t)(plane % C) * HW];
   const size_t base = (size_t)plane * HW;
   const int e0 = chunk * BN_CHUNK, e1 = min(HW, e0 + BN_CHUNK);
   float s = 0.f, q = 0.f;
   if (((HW | e0) & 3) == 0) {
     const float4 *xv = reinterpret_cast<const float4 *>(x + base);
     for (int i = e0 / 4 + threadIdx.x; i < e1 / 4; i += BN_T) {
-      const float4 v = xv[i];
+      float4 v = xv[i];
+      v.x -= K; v.y -= K; v.z -= K; v.w -= K;
       s += (v.x + v.y) + (v.z + v.w);
       q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
     }
   } else {
     for (int i = e0 + threadIdx.x; i < e1; i += BN_T) {
-      const float v = x[base + i];
+      const float v = x[base + i] - K;
       s += v;
       q += v * v;
     }
@@ -62,7 +78,8 @@ __global__ __launch_bounds__(BN_T) void bn_stats_kernel(const float *__restrict_
 }
 
 // per channel: the chunk sums of all images in index order (thread-strided, then a fixed tree), in double
-__global__ __launch_bounds__(BN_T) void bn_finalize_kernel(const float *__restrict__ part, long long N, int C,
+__global__ __launch_bounds__(BN_T) void bn_finalize_kernel(const float *__restrict__ x, int HW,
+                                                           const float *__restrict__ part, long long N, int C,
                                                            int chunks, long long M, float eps, float momentum,
                                                            float *__restrict__ mean, float *__restrict__ rstd,
                                                            float *__restrict__ run_mean,
@@ -88,8 +105,9 @@ __global__ __launch_bounds__(BN_T) void bn_finalize_kernel(const float *__restri
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    const double m = rs[0] / (double)M;
-    double var = rq[0] / (double)M - m * m;             // biased (population) variance normalises
+    const double d = rs[0] / (double)M;                 // mean - K: small against the spread unless K is an outlier
+    const double m = (double)x[(size_t)c * HW] + d;
+    double var = rq[0] / (double)M - d * d;             // biased (population) variance normalises
     if (var < 0.0) var = 0.0;
     mean[c] = (float)m;
     rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
@@ -111,7 +129,7 @@ __global__ __launch_bounds__(BN_T) void bn_apply_kernel(const float *__restrict_
   const long long plane = blockIdx.x / chunks;
   const int chunk = blockIdx.x - (int)(plane * chunks);
   const int c = (int)(plane % C);
-  const float sc = rstd[c] * gamma[c], sh = beta[c] - mean[c] * sc;   // y = x sc + sh
+  const float mu = mean[c], sc = rstd[c] * gamma[c], b = beta[c];    // y = (x - mu) sc + b
   const float a = PRELU ? slope[c] : 1.0f;
   const size_t base = (size_t)plane * HW;
   const int e0 = chunk * BN_CHUNK, e1 = min(HW, e0 + BN_CHUNK);
@@ -121,7 +139,7 @@ __global__ __launch_bounds__(BN_T) void bn_apply_kernel(const float *__restrict_
     for (int i = e0 / 4 + threadIdx.x; i < e1 / 4; i += BN_T) {
       const float4 v = xv[i];
       float4 y;
-      y.x = fmaf(v.x, sc, sh); y.y = fmaf(v.y, sc, sh); y.z = fmaf(v.z, sc, sh); y.w = fmaf(v.w, sc, sh);
+      y.x = bn_y(v.x, mu, sc, b); y.y = bn_y(v.y, mu, sc, b); y.z = bn_y(v.z, mu, sc, b); y.w = bn_y(v.w, mu, sc, b);
       if (PRELU) {
         y.x = y.x > 0.f ? y.x : a * y.x; y.y = y.y > 0.f ? y.y : a * y.y;
         y.z = y.z > 0.f ? y.z : a * y.z; y.w = y.w > 0.f ? y.w : a * y.w;
@@ -130,7 +148,7 @@ __global__ __launch_bounds__(BN_T) void bn_apply_kernel(const float *__restrict_
     }
   } else {
     for (int i = e0 + threadIdx.x; i < e1; i += BN_T) {
-      float y = fmaf(x[base + i], sc, sh);
+      float y = bn_y(x[base + i], mu, sc, b);
       if (PRELU) y = y > 0.f ? y : a * y;
       z[base + i] = y;
     }
@@ -143,8 +161,7 @@ __device__ __forceinline__ void bn_elem(float xv, float dz, float mu, float rs, 
                                         float &dy, float &da) {
   xh = (xv - mu) * rs;
   if (PRELU) {
-    const float sc = rs * g;
-    const float y = fmaf(xv, sc, b - mu * sc);       // exactly the forward's y (same sign test)
+    const float y = bn_y(xv, mu, rs * g, b);         // exactly the forward's y (same sign test)
     dy = y > 0.f ? dz : a * dz;
     da = y > 0.f ? 0.f : dz * y;
   } else {
@@ -279,13 +296,13 @@ __global__ __launch_bounds__(BN_T) void bn_res_apply_kernel(const float *__restr
   const int chunk = blockIdx.x - (int)(plane * chunks);
   const int c = (int)(plane % C);
   const float ps = scale ? scale[plane] : 1.0f;
-  const float sc = rstd[c] * gamma[c], sh = beta[c] - mean[c] * sc;   // y = x sc + sh
+  const float mu = mean[c], sc = rstd[c] * gamma[c], b = beta[c];    // y = (x - mu) sc + b
   const float a = slope[c];
   const size_t base = (size_t)plane * HW;
   const int e0 = chunk * BN_CHUNK, e1 = min(HW, e0 + BN_CHUNK);
 #define SMPLR_RES(XV, OV, OUT)                                \
   {                                                           \
-    const float pre_ = fmaf(ps, fmaf(XV, sc, sh), OV);        \
+    const float pre_ = fmaf(ps, bn_y(XV, mu, sc, b), OV);     \
     OUT = pre_ > 0.f ? pre_ : a * pre_;                       \
   }
   if (((HW | e0) & 3) == 0) {
@@ -307,8 +324,7 @@ __global__ __launch_bounds__(BN_T) void bn_res_apply_kernel(const float *__restr
 __device__ __forceinline__ void bn_res_elem(float xv, float ov, float dout, float mu, float rs, float g, float b, float ps,
                                             float a, float &xh, float &dpre, float &da) {
   xh = (xv - mu) * rs;
-  const float sc = rs * g;
-  const float pre = fmaf(ps, fmaf(xv, sc, b - mu * sc), ov);   // exactly the forward's value (same sign test)
+  const float pre = fmaf(ps, bn_y(xv, mu, rs * g, b), ov);     // exactly the forward's value (same sign test)
   dpre = pre > 0.f ? dout : a * dout;
   da = pre > 0.f ? 0.f : dout * pre;
 }
@@ -421,9 +437,10 @@ int smplr_bn_fwd(const float *x, const float *gamma, const float *beta, const fl
   const unsigned grid = (unsigned)(N * C * chunks);
   float *part = reinterpret_cast<float *>(workspace);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(bn_stats_kernel, dim3(grid), dim3(BN_T), 0, st, x, HW, chunks, part);
+  hipLaunchKernelGGL(bn_stats_kernel, dim3(grid), dim3(BN_T), 0, st, x, C, HW, chunks, part);
   SMPLR_LAUNCH_CHECK("smplr_bn_fwd(stats)");
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(BN_T), 0, st, part, N, C, chunks, N * (long long)HW, eps, momentum,
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(BN_T), 0, st, x, HW, part, N, C, chunks, N * (long long)HW, eps,
+                     momentum,
                      save_mean, save_rstd, running_mean, running_var);
   SMPLR_LAUNCH_CHECK("smplr_bn_fwd(finalize)");
   if (slope)
@@ -489,9 +506,10 @@ int smplr_bn_res_fwd(const float *x, const float *gamma, const float *beta, cons
   const unsigned grid = (unsigned)(N * C * chunks);
   float *part = reinterpret_cast<float *>(workspace);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(bn_stats_kernel, dim3(grid), dim3(BN_T), 0, st, x, HW, chunks, part);
+  hipLaunchKernelGGL(bn_stats_kernel, dim3(grid), dim3(BN_T), 0, st, x, C, HW, chunks, part);
   SMPLR_LAUNCH_CHECK("smplr_bn_res_fwd(stats)");
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(BN_T), 0, st, part, N, C, chunks, N * (long long)HW, eps, momentum,
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(BN_T), 0, st, x, HW, part, N, C, chunks, N * (long long)HW, eps,
+                     momentum,
                      save_mean, save_rstd, running_mean, running_var);
   SMPLR_LAUNCH_CHECK("smplr_bn_res_fwd(finalize)");
   hipLaunchKernelGGL(bn_res_apply_kernel, dim3(grid), dim3(BN_T), 0, st, x, gamma, beta, plane_scale, other, slope,
