@@ -485,6 +485,40 @@ int smplr_resize_pad(const uint8_t *data, long long data_bytes, const long long 
 int smplr_point_errors(const float *pred, const float *gt, int B, int N, int root, int pp_mode, float *mean_err,
                        float *transform, float *per_point, int32_t *status, void *stream);
 
+/* ---- prediction figures: predict.py:28-77 (_seg.png, _projects.png, _verts_overlay.png), train.py:283-290,
+ * train_stage2_silhouette.py:318-329, predict_realtime.py:75-96; INTEGRATION.md 4h -------------------------------------
+ * One launch each on the caller's stream; no workspace, no allocation, no synchronisation, no global atomics.  Colours
+ * given as an int are r | g << 8 | b << 16; pictures are (B, H, W, 3) uint8, contiguous.
+ *
+ * The class map as a colour picture: EITHER scores (B, h, w, C) fp32, 2 <= C <= 32, whose arg-max is taken under the order
+ * of the seg confusion kernel (NaN above every number, the first NaN wins, ties to the lower channel), OR labels
+ * (B, h, w) int32; the other is NULL.  rgb[b, i, j] = lut[label[b, (i h) / H, (j w) / W]] (nearest sampling in exact
+ * integers, a score is read once per source pixel), lut (K, 3) uint8; a label outside [0, K) gets bad_colour.
+ * background (B, H, W, 3) uint8 or NULL: where label != 0, (alpha_q colour + (256 - alpha_q) background + 128) >> 8 per
+ * channel; where label == 0 the background pixel.  alpha_q in [0, 256] (ignored without a background).
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= h, w, H, W <= 4096; C as above; 1 <= K <= 2^24; B >= 0 (B = 0
+ * is a no-op); B * h workgroups, fewer than 2^31. */
+int smplr_seg_colour(const float *scores, const int32_t *labels, int B, int h, int w, int C, const uint8_t *lut, int K,
+                     int bad_colour, const uint8_t *background, int alpha_q, int H, int W, uint8_t *rgb, void *stream);
+/* Projected vertices as discs: proj (B, V, 3) fp32 (u, v, z) as the projection gives them; vertex k of mesh b is drawn
+ * unless keep (B, V) uint8 (or NULL) holds 0 for it, u or v is not finite, or - in depth order - z is not finite.  Centre
+ * cx = rint(scale u), cy = H - 1 - rint(scale v): one fp32 multiply, clamped to +-2^20, rounded half to even; rows flipped
+ * as the seg head's and the renderer's ortho mode.  Pixel [i, j] is covered iff (j - cx)^2 + (i - cy)^2 <= radius^2.
+ * A covered pixel goes to the highest vertex index (order SMPLR_SCATTER_INDEX: the painter's order of matplotlib's scatter)
+ * or to the largest z, ties to the lower index (SMPLR_SCATTER_DEPTH; -0 and +0 tie): the maximum of one 64-bit key, so the
+ * maps do not depend on scheduling or on the rest of the batch.
+ *   vertex (B, H, W) int32 or NULL: the winner, -1 where none.
+ *   rgb    (B, H, W, 3) uint8 or NULL: colours[winner] (colours (V, 3) uint8, shared by the batch) or `colour` when colours
+ *          is NULL; elsewhere (alpha_q image + (256 - alpha_q) canvas + 128) >> 8 with image (B, H, W, 3) uint8 upright,
+ *          or the canvas colour when image is NULL.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= V <= 2^24; 1 <= H, W <= 4096; 0 <= radius <= 16; order 0 or 1;
+ * alpha_q in [0, 256]; scale finite; B >= 0 (B = 0 is a no-op); B * ceil(H / 64) * ceil(W / 64) workgroups, fewer than 2^31. */
+#define SMPLR_SCATTER_INDEX 0
+#define SMPLR_SCATTER_DEPTH 1
+int smplr_scatter_points(const float *proj, const uint8_t *keep, const uint8_t *colours, int colour, const uint8_t *image,
+                         int alpha_q, int canvas, int B, int V, float scale, int radius, int order, int H, int W,
+                         int32_t *vertex, uint8_t *rgb, void *stream);
+
 /* ---- projects_to_silhouette: keras_smpl/projects_to_silhouette.py:14-44 ----------------- */
 /* silh (B,W,W,2) = [1-s, s], s = max_v exp(-|proj_v-(c,r)|/1.2) over ALL VP vertices, rows
  * flipped; arg (B,W,W) int32 = maximising vertex.  workspace: smplr_silh_workspace(B,VP,W) B.  */

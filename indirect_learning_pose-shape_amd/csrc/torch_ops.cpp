@@ -719,6 +719,108 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> point_errors_meta(const Tensor &pred,
           at::empty({transform ? B : 0, transform ? 13 : 0}, pred.options())};
 }
 
+// ---- prediction figures (predict.py:28-77, predict_realtime.py:75-96): uint8 pictures (B, H, W, 3) ---------------------------
+// seg_colour: input (B, h, w, C) fp32 scores or (B, h, w) int32 classes, lut (K, 3) uint8, background (B, H, W, 3) uint8 or
+// None -> rgb.  scatter_points: proj (B, V, 3) fp32, keep (B, V) uint8, colours (V, 3) uint8, image (B, H, W, 3) uint8 ->
+// (rgb, vertex (B, H, W) int32, or (0) without return_vertex).  Colours as ints are r | g << 8 | b << 16.
+bool seg_colour_check(const Tensor &input, const Tensor &lut, const c10::optional<Tensor> &background, int64_t H, int64_t W,
+                      int64_t alpha_q, int64_t bad_colour) {
+  const bool is_scores = input.scalar_type() == at::kFloat;
+  TORCH_CHECK(is_scores || input.scalar_type() == at::kInt, "input must be float32 scores (B, h, w, C) or an int32 class map (B, h, w)");
+  TORCH_CHECK(input.dim() == (is_scores ? 4 : 3), "input must be ", is_scores ? "(B, h, w, C) scores" : "a (B, h, w) class map");
+  TORCH_CHECK(!is_scores || (input.size(3) >= 2 && input.size(3) <= 32), "scores have ", is_scores ? input.size(3) : 0,
+              " channels (2..32)");
+  TORCH_CHECK(input.size(1) >= 1 && input.size(1) <= 4096 && input.size(2) >= 1 && input.size(2) <= 4096,
+              "the source map must be 1..4096 on a side");
+  TORCH_CHECK(H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "H and W must be in 1..4096");
+  TORCH_CHECK(input.size(0) * input.size(1) < (int64_t(1) << 31), "too many images");
+  TORCH_CHECK(lut.scalar_type() == at::kByte && lut.dim() == 2 && lut.size(1) == 3 && lut.size(0) >= 1 && lut.size(0) <= (1 << 24),
+              "lut must be (K, 3) uint8 with 1 <= K <= 2^24");
+  TORCH_CHECK(alpha_q >= 0 && alpha_q <= 256, "alpha_q must be in [0, 256]");
+  TORCH_CHECK(bad_colour >= 0 && bad_colour <= 0xffffff, "bad_colour must be r | g << 8 | b << 16");
+  TORCH_CHECK(!background || (background->scalar_type() == at::kByte && background->dim() == 4 &&
+                              background->size(0) == input.size(0) && background->size(1) == H && background->size(2) == W &&
+                              background->size(3) == 3),
+              "background must be (B, H, W, 3) uint8");
+  return is_scores;
+}
+Tensor seg_colour(const Tensor &input, const Tensor &lut, const c10::optional<Tensor> &background, int64_t H, int64_t W,
+                  int64_t alpha_q, int64_t bad_colour) {
+  const bool is_scores = seg_colour_check(input, lut, background, H, W, alpha_q, bad_colour);
+  dev_typed(input, is_scores ? at::kFloat : at::kInt, "input");
+  dev_typed(lut, at::kByte, "lut");
+  if (background) dev_typed(*background, at::kByte, "background");
+  const Tensor none;
+  same_device(input, {{"lut", &lut}, {"background", background ? &*background : &none}});
+  DeviceGuard g(input.device());
+  const int64_t B = input.size(0);
+  Tensor rgb = at::empty({B, H, W, 3}, input.options().dtype(at::kByte));
+  if (B == 0) return rgb;
+  ok(smplr_seg_colour(is_scores ? input.data_ptr<float>() : nullptr, is_scores ? nullptr : input.data_ptr<int32_t>(), (int)B,
+                      (int)input.size(1), (int)input.size(2), is_scores ? (int)input.size(3) : 0, lut.data_ptr<uint8_t>(),
+                      (int)lut.size(0), (int)bad_colour, background ? background->data_ptr<uint8_t>() : nullptr, (int)alpha_q,
+                      (int)H, (int)W, rgb.data_ptr<uint8_t>(), cur_stream()),
+     "smplr_seg_colour");
+  return rgb;
+}
+Tensor seg_colour_meta(const Tensor &input, const Tensor &lut, const c10::optional<Tensor> &background, int64_t H, int64_t W,
+                       int64_t alpha_q, int64_t bad_colour) {
+  seg_colour_check(input, lut, background, H, W, alpha_q, bad_colour);
+  return at::empty({input.size(0), H, W, 3}, input.options().dtype(at::kByte));
+}
+
+void scatter_points_check(const Tensor &proj, const c10::optional<Tensor> &keep, const c10::optional<Tensor> &colours,
+                          const c10::optional<Tensor> &image, int64_t H, int64_t W, int64_t radius, int64_t order,
+                          int64_t colour, int64_t alpha_q, int64_t canvas) {
+  TORCH_CHECK(proj.scalar_type() == at::kFloat && proj.dim() == 3 && proj.size(2) == 3, "proj must be (B, V, 3) float32");
+  const int64_t B = proj.size(0), V = proj.size(1);
+  TORCH_CHECK(V >= 1 && V <= (1 << 24), "proj holds ", V, " vertices (1..2^24)");
+  TORCH_CHECK(H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "H and W must be in 1..4096");
+  TORCH_CHECK(radius >= 0 && radius <= 16, "radius must be in 0..16");
+  TORCH_CHECK(order == 0 || order == 1, "order must be 0 (index) or 1 (depth)");
+  TORCH_CHECK(alpha_q >= 0 && alpha_q <= 256, "alpha_q must be in [0, 256]");
+  TORCH_CHECK(colour >= 0 && colour <= 0xffffff && canvas >= 0 && canvas <= 0xffffff, "colour and canvas must be r | g << 8 | b << 16");
+  TORCH_CHECK(B * ((H + 63) / 64) * ((W + 63) / 64) < (int64_t(1) << 31), "too many meshes");
+  TORCH_CHECK(!keep || (keep->scalar_type() == at::kByte && keep->dim() == 2 && keep->size(0) == B && keep->size(1) == V),
+              "keep must be (B, V) uint8");
+  TORCH_CHECK(!colours || (colours->scalar_type() == at::kByte && colours->dim() == 2 && colours->size(0) == V && colours->size(1) == 3),
+              "colours must be (V, 3) uint8 with V = ", V);
+  TORCH_CHECK(!image || (image->scalar_type() == at::kByte && image->dim() == 4 && image->size(0) == B && image->size(1) == H &&
+                         image->size(2) == W && image->size(3) == 3),
+              "image must be (B, H, W, 3) uint8");
+}
+std::tuple<Tensor, Tensor> scatter_points(const Tensor &proj, const c10::optional<Tensor> &keep, const c10::optional<Tensor> &colours,
+                                          const c10::optional<Tensor> &image, int64_t H, int64_t W, double scale, int64_t radius,
+                                          int64_t order, int64_t colour, int64_t alpha_q, int64_t canvas, bool return_vertex) {
+  scatter_points_check(proj, keep, colours, image, H, W, radius, order, colour, alpha_q, canvas);
+  dev_f32(proj, "proj");
+  if (keep) dev_typed(*keep, at::kByte, "keep");
+  if (colours) dev_typed(*colours, at::kByte, "colours");
+  if (image) dev_typed(*image, at::kByte, "image");
+  const Tensor none;
+  same_device(proj, {{"keep", keep ? &*keep : &none}, {"colours", colours ? &*colours : &none}, {"image", image ? &*image : &none}});
+  DeviceGuard g(proj.device());
+  const int64_t B = proj.size(0);
+  Tensor rgb = at::empty({B, H, W, 3}, proj.options().dtype(at::kByte));
+  Tensor vertex = at::empty({return_vertex ? B : 0, return_vertex ? H : 0, return_vertex ? W : 0}, proj.options().dtype(at::kInt));
+  if (B == 0) return {rgb, vertex};
+  ok(smplr_scatter_points(proj.data_ptr<float>(), keep ? keep->data_ptr<uint8_t>() : nullptr,
+                          colours ? colours->data_ptr<uint8_t>() : nullptr, (int)colour, image ? image->data_ptr<uint8_t>() : nullptr,
+                          (int)alpha_q, (int)canvas, (int)B, (int)proj.size(1), (float)scale, (int)radius, (int)order, (int)H, (int)W,
+                          return_vertex ? vertex.data_ptr<int32_t>() : nullptr, rgb.data_ptr<uint8_t>(), cur_stream()),
+     "smplr_scatter_points");
+  return {rgb, vertex};
+}
+std::tuple<Tensor, Tensor> scatter_points_meta(const Tensor &proj, const c10::optional<Tensor> &keep,
+                                               const c10::optional<Tensor> &colours, const c10::optional<Tensor> &image, int64_t H,
+                                               int64_t W, double scale, int64_t radius, int64_t order, int64_t colour,
+                                               int64_t alpha_q, int64_t canvas, bool return_vertex) {
+  scatter_points_check(proj, keep, colours, image, H, W, radius, order, colour, alpha_q, canvas);
+  const int64_t B = proj.size(0);
+  return {at::empty({B, H, W, 3}, proj.options().dtype(at::kByte)),
+          at::empty({return_vertex ? B : 0, return_vertex ? H : 0, return_vertex ? W : 0}, proj.options().dtype(at::kInt))};
+}
+
 int64_t abi_version() { return smplr_abi_version(); }
 #ifndef SMPLR_TORCH_OPS_ID
 #define SMPLR_TORCH_OPS_ID "unknown"
@@ -757,6 +859,9 @@ TORCH_LIBRARY(smplraster, m) {
         "float rescale=1.0) -> ()");
   m.def("point_errors(Tensor pred, Tensor gt, int root=-1, int per_point_mode=-1, bool transform=False) -> "
         "(Tensor, Tensor, Tensor, Tensor)");
+  m.def("seg_colour(Tensor input, Tensor lut, Tensor? background, int H, int W, int alpha_q=256, int bad_colour=0) -> Tensor");
+  m.def("scatter_points(Tensor proj, Tensor? keep, Tensor? colours, Tensor? image, int H, int W, float scale, int radius=0, "
+        "int order=0, int colour=11826975, int alpha_q=230, int canvas=16777215, bool return_vertex=True) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch key is named CUDA in torch)
@@ -778,6 +883,8 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("affine_warp", &affine_warp);
   m.impl("resize_pad", &resize_pad);
   m.impl("point_errors", &point_errors);
+  m.impl("seg_colour", &seg_colour);
+  m.impl("scatter_points", &scatter_points);
 }
 
 TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
@@ -799,4 +906,6 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("affine_warp", &affine_warp_meta);
   m.impl("resize_pad", &resize_pad_meta);
   m.impl("point_errors", &point_errors_meta);
+  m.impl("seg_colour", &seg_colour_meta);
+  m.impl("scatter_points", &scatter_points_meta);
 }

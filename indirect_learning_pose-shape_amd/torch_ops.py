@@ -54,6 +54,11 @@ SCHEMAS = {
                    "int mode=0, int flags=4, float rescale=1.) -> ()"),
     "point_errors": ("smplraster::point_errors(Tensor pred, Tensor gt, int root=-1, int per_point_mode=-1, "
                      "bool transform=False) -> (Tensor, Tensor, Tensor, Tensor)"),
+    "seg_colour": ("smplraster::seg_colour(Tensor input, Tensor lut, Tensor? background, int H, int W, int alpha_q=256, "
+                   "int bad_colour=0) -> Tensor"),
+    "scatter_points": ("smplraster::scatter_points(Tensor proj, Tensor? keep, Tensor? colours, Tensor? image, int H, int W, "
+                       "float scale, int radius=0, int order=0, int colour=11826975, int alpha_q=230, int canvas=16777215, "
+                       "bool return_vertex=True) -> (Tensor, Tensor)"),
 }
 
 _ns = None
