@@ -519,6 +519,32 @@ int smplr_scatter_points(const float *proj, const uint8_t *keep, const uint8_t *
                          int alpha_q, int canvas, int B, int V, float scale, int radius, int order, int H, int W,
                          int32_t *vertex, uint8_t *rgb, void *stream);
 
+/* ---- fitting parameters to label maps: decoder_loss_debugging.py:103-125 (1601 Adam steps on a table of 86-vectors);
+ *      INTEGRATION.md 4i -------------------------------------------------------------------------------------------------
+ * Everything one iteration does after the decoder's backward, per row b of x (B, P), P = num_cam + 82 <= 256, in ONE launch
+ * of B workgroups; no workspace, no allocation, no synchronisation, no atomics.  All state is device memory (in/out):
+ *   x, m, v, best_x (B, P) fp32; t, calls, stall, bad, best_step (B) int32; active (B) uint8; best_loss (B) fp32.
+ * Inputs: g (B, P) = d(sum_b L_b)/dx; loss (B, N) the per-pixel seg loss; silh_loss (B, Ns) or NULL, weighted by
+ * silh_weight; col_scale (P) per-column learning-rate multiplier (0 freezes a column); history (H, B) or NULL (out).
+ *   1. L = mean(loss[b, :]) (+ silh_weight mean(silh_loss[b, :])): fp32 per-thread strided sums combined by a fixed tree.
+ *   2. history[calls[b], b] = L while calls[b] < H; calls[b] += 1.
+ *   3. L or any g[b, :] not finite: bad[b] += 1, nothing else of the row changes.
+ *   4. else if active[b]: L < best_loss[b] (strict) -> best_loss[b] = L, best_x[b, :] = x[b, :] (before this call's
+ *      update), best_step[b] = t[b], stall[b] = 0; otherwise stall[b] += 1; patience > 0 and stall[b] >= patience ->
+ *      active[b] = 0 and no update.
+ *   5. still active: t += 1, g^ = gscale g, m = beta1 m + (1 - beta1) g^, v = beta2 v + (1 - beta2) g^ g^ and
+ *      SMPLR_FIT_KERAS: x -= lr col_scale[j] sqrt(1 - beta2^t) / (1 - beta1^t) m / (sqrt(v) + eps)   (Keras 2 Adam)
+ *      SMPLR_FIT_TORCH: x -= lr col_scale[j] / (1 - beta1^t) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)  (torch.optim.Adam)
+ *      with the bias corrections in fp64.  x[b, j] keeps its bits where col_scale[j] = 0 or the new m is 0.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= P <= 256; N >= 1; Ns >= 1 with silh_loss; mode 0 or 1; H >= 0;
+ * patience >= 0; beta1, beta2 in [0, 1); eps >= 0; lr, gscale, silh_weight finite; B >= 0 (B = 0 is a no-op).             */
+#define SMPLR_FIT_KERAS 0
+#define SMPLR_FIT_TORCH 1
+int smplr_fit_step(float *x, const float *g, float *m, float *v, int32_t *t, int32_t *calls, int32_t *stall, int32_t *bad,
+                   int32_t *best_step, uint8_t *active, float *best_loss, float *best_x, const float *loss, int N,
+                   const float *silh_loss, int Ns, float silh_weight, const float *col_scale, float *history, int H, int B,
+                   int P, float lr, float beta1, float beta2, float eps, float gscale, int mode, int patience, void *stream);
+
 /* ---- projects_to_silhouette: keras_smpl/projects_to_silhouette.py:14-44 ----------------- */
 /* silh (B,W,W,2) = [1-s, s], s = max_v exp(-|proj_v-(c,r)|/1.2) over ALL VP vertices, rows
  * flipped; arg (B,W,W) int32 = maximising vertex.  workspace: smplr_silh_workspace(B,VP,W) B.  */

@@ -1,0 +1,151 @@
+// Fitting SMPL parameters to label maps: everything one iteration does after the decoder's backward, in one launch.
+//
+// Reference: decoder_loss_debugging.py:103-125 - a table of 86-vectors optimised by Keras' Adam (`optimizer="adam"`, :117)
+// through decoder + focal loss.  Here the table is x (B, P) and every row is its own problem: its own step count, its own
+// best iterate, its own stop.  All state lives in device memory, so a captured graph replays an iteration unchanged.
+//
+//  fit_step_kernel   one workgroup of 256 threads per row b.
+//                    1. L = mean(loss[b, :]) (+ silh_weight mean(silh_loss[b, :])): thread i adds loss[b, i], loss[b, i + 256],
+//                       ... serially in fp32; the 256 partial sums are combined in fp64 by the xor butterfly of a wave and
+//                       then wave 0 + 1 + 2 + 3 through LDS - a fixed tree, no atomics: the same bits on every launch and
+//                       for any batch around the row.  One rounding to fp32 at the end.
+//                    2. history[calls[b], b] = L while calls[b] < H; calls[b] += 1.
+//                    3. L or any g[b, :] not finite: bad[b] += 1 and nothing else of the row changes.
+//                    4. else, an active row: L < best_loss[b] (strict) -> best_loss, best_x (the iterate that produced L),
+//                       best_step = t[b], stall = 0; otherwise stall += 1, and with patience > 0 and stall >= patience the
+//                       row goes inactive without an update.
+//                    5. a row still active: t += 1, g^ = gscale g, m = b1 m + (1 - b1) g^, v = b2 v + (1 - b2) g^ g^, and
+//                         keras: x -= [lr sqrt(1 - b2^t) / (1 - b1^t)] col_scale[j] . m / (sqrt(v) + eps)
+//                         torch: x -= [lr / (1 - b1^t)] col_scale[j] . m / (sqrt(v) / [sqrt(1 - b2^t)] + eps)
+//                       with the bracketed factors computed per row in fp64 (1 - 0.999^t in fp32 is off by 6e-5 at t = 1) and
+//                       rounded to fp32 once.  x[b, j] is not stored to where col_scale[j] = 0 or the new m is 0.
+// Thread j owns column j (P <= 256).  Every thread reads the row's scalars before the one barrier that also carries the
+// "any g not finite" vote, takes the same decisions from them, and thread 0 alone writes them back after it.
+// FMA contraction is off for the file and the two fused operations are spelled out, so that the rounding count behind the
+// test's bars (tests/test_gpu_fitting.py) is the one written here: m 3 roundings, v 4, the step at most 13.
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace smplr {
+
+constexpr int FT_T = 256;      // threads per workgroup = the widest row
+constexpr int FT_NW = FT_T / WAVE;
+
+__device__ __forceinline__ bool ft_finite(float x) { return x - x == 0.f; }
+
+__device__ __forceinline__ double ft_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ float ft_strided_sum(const float *__restrict__ p, int n) {
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += FT_T) s += p[i];
+  return s;
+}
+
+__global__ __launch_bounds__(FT_T) void fit_step_kernel(
+    float *__restrict__ x, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+    int *__restrict__ t, int *__restrict__ calls, int *__restrict__ stall, int *__restrict__ bad,
+    int *__restrict__ best_step, unsigned char *__restrict__ active, float *__restrict__ best_loss,
+    float *__restrict__ best_x, const float *__restrict__ loss, int N, const float *__restrict__ silh_loss, int Ns,
+    float silh_weight, const float *__restrict__ col_scale, float *__restrict__ history, int H, int B, int P, float lr,
+    float beta1, float beta2, float eps, float gscale, int mode, int patience) {
+  __shared__ double swave[2][FT_NW];
+  const int b = blockIdx.x, j = threadIdx.x;
+  const int lane = j & (WAVE - 1), wave = j / WAVE;
+  const long long row = (long long)b * P;
+
+  // the row's scalars, read by every thread before anything of the row is written
+  const int t0 = t[b], stall0 = stall[b], calls0 = calls[b];
+  const bool active0 = active[b] != 0;
+  const float best0 = best_loss[b];
+
+  // 1. the row's loss
+  const double ws = ft_wave_sum((double)ft_strided_sum(loss + (long long)b * N, N));
+  const double wq = silh_loss ? ft_wave_sum((double)ft_strided_sum(silh_loss + (long long)b * Ns, Ns)) : 0.0;
+  if (lane == 0) {
+    swave[0][wave] = ws;
+    swave[1][wave] = wq;
+  }
+  const bool col = j < P;
+  const float gj = col ? g[row + j] : 0.f;
+  const int g_bad = __syncthreads_or(!ft_finite(gj));                     // (the barrier that publishes swave)
+  double Ld = ((swave[0][0] + swave[0][1]) + (swave[0][2] + swave[0][3])) / (double)N;
+  if (silh_loss) Ld += (double)silh_weight * (((swave[1][0] + swave[1][1]) + (swave[1][2] + swave[1][3])) / (double)Ns);
+  const float L = (float)Ld;
+
+  // 2. the trace
+  if (j == 0) {
+    if (history && (unsigned)calls0 < (unsigned)H) history[(long long)calls0 * B + b] = L;
+    calls[b] = calls0 + 1;
+  }
+  // 3. a bad call
+  if (g_bad || !ft_finite(L)) {
+    if (j == 0) bad[b] += 1;
+    return;
+  }
+  if (!active0) return;
+  // 4. the best iterate, the stop
+  const bool better = L < best0;
+  const int stall1 = better ? 0 : stall0 + 1;
+  const bool go = !(patience > 0 && stall1 >= patience);
+  if (j == 0) {
+    if (better) {
+      best_loss[b] = L;
+      best_step[b] = t0;
+    }
+    stall[b] = stall1;
+    if (!go) active[b] = 0;
+  }
+  const float xj = col ? x[row + j] : 0.f;
+  if (better && col) best_x[row + j] = xj;
+  if (!go) return;
+  // 5. the update
+  const int t1 = t0 + 1;
+  if (j == 0) t[b] = t1;
+  const double c1 = 1.0 - pow((double)beta1, (double)t1), c2 = 1.0 - pow((double)beta2, (double)t1);
+  const float step = mode == 0 ? (float)((double)lr * sqrt(c2) / c1) : (float)((double)lr / c1);
+  const float rc2 = (float)sqrt(c2);
+  if (!col) return;
+  const float gh = gscale * gj;
+  const float m1 = fmaf(beta1, m[row + j], (1.0f - beta1) * gh);
+  const float v1 = fmaf((1.0f - beta2) * gh, gh, beta2 * v[row + j]);
+  m[row + j] = m1;
+  v[row + j] = v1;
+  const float cs = col_scale[j];
+  if (cs == 0.f || m1 == 0.f) return;
+  const float sv = __fsqrt_rn(v1);
+  const float den = (mode == 0 ? sv : __fdiv_rn(sv, rc2)) + eps;
+  x[row + j] = xj - (step * cs) * __fdiv_rn(m1, den);
+}
+
+}  // namespace smplr
+
+int smplr_fit_step(float *x, const float *g, float *m, float *v, int32_t *t, int32_t *calls, int32_t *stall, int32_t *bad,
+                   int32_t *best_step, uint8_t *active, float *best_loss, float *best_x, const float *loss, int N,
+                   const float *silh_loss, int Ns, float silh_weight, const float *col_scale, float *history, int H, int B,
+                   int P, float lr, float beta1, float beta2, float eps, float gscale, int mode, int patience, void *stream) {
+  using namespace smplr;
+  SMPLR_REQUIRE(B >= 0, "smplr_fit_step: negative batch B=%d", B);
+  SMPLR_REQUIRE(P >= 1 && P <= FT_T, "smplr_fit_step: P=%d columns (1..%d)", P, FT_T);
+  SMPLR_REQUIRE(N >= 1, "smplr_fit_step: N=%d loss values per row (N >= 1)", N);
+  SMPLR_REQUIRE(!silh_loss || Ns >= 1, "smplr_fit_step: Ns=%d silhouette loss values per row (Ns >= 1)", Ns);
+  SMPLR_REQUIRE(mode == SMPLR_FIT_KERAS || mode == SMPLR_FIT_TORCH, "smplr_fit_step: mode %d is neither keras (0) nor torch (1)",
+                mode);
+  SMPLR_REQUIRE(H >= 0 && patience >= 0, "smplr_fit_step: negative history length H=%d or patience %d", H, patience);
+  SMPLR_REQUIRE(!history || (long long)H * B < (1ll << 40), "smplr_fit_step: history of %d x %d entries", H, B);
+  SMPLR_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "smplr_fit_step: beta1, beta2 must lie in [0, 1)");
+  SMPLR_REQUIRE(eps >= 0.f && lr - lr == 0.f && gscale - gscale == 0.f && silh_weight - silh_weight == 0.f,
+                "smplr_fit_step: eps must be >= 0 and lr, gscale, silh_weight finite");
+  if (B == 0) return 0;
+  SMPLR_REQUIRE(x && g && m && v && t && calls && stall && bad && best_step && active && best_loss && best_x && loss && col_scale,
+                "smplr_fit_step: null pointer (only silh_loss and history may be NULL)");
+  hipLaunchKernelGGL(fit_step_kernel, dim3((unsigned)B), dim3(FT_T), 0, as_stream(stream), x, g, m, v, t, calls, stall, bad,
+                     best_step, active, best_loss, best_x, loss, N, silh_loss, Ns, silh_weight, col_scale, history,
+                     history ? H : 0, B, P, lr, beta1, beta2, eps, gscale, mode, patience);
+  SMPLR_LAUNCH_CHECK("smplr_fit_step");
+  return 0;
+}

@@ -821,6 +821,69 @@ std::tuple<Tensor, Tensor> scatter_points_meta(const Tensor &proj, const c10::op
           at::empty({return_vertex ? B : 0, return_vertex ? H : 0, return_vertex ? W : 0}, proj.options().dtype(at::kInt))};
 }
 
+// ---- fitting parameters to label maps (decoder_loss_debugging.py:103-125; csrc/fit.hip): one launch per iteration ------
+// state, all changed in place: x, m, v, best_x (B, P) fp32; t, calls, stall, bad, best_step (B) int32; active (B) uint8;
+// best_loss (B) fp32.  g (B, P); loss (B, N); silh_loss (B, Ns) or None; col_scale (P); history (H, B) or None.
+void fit_step_check(const Tensor &x, const Tensor &g, const Tensor &m, const Tensor &v, const Tensor &t, const Tensor &calls,
+                    const Tensor &stall, const Tensor &bad, const Tensor &best_step, const Tensor &active,
+                    const Tensor &best_loss, const Tensor &best_x, const Tensor &loss, const c10::optional<Tensor> &silh_loss,
+                    const Tensor &col_scale, const c10::optional<Tensor> &history, int64_t mode, int64_t patience) {
+  TORCH_CHECK(x.dim() == 2 && x.size(1) >= 1 && x.size(1) <= 256 && x.scalar_type() == at::kFloat, "x must be (B, P) float32, 1 <= P <= 256");
+  const int64_t B = x.size(0), P = x.size(1);
+  for (const auto &nt : {std::make_pair("g", &g), std::make_pair("m", &m), std::make_pair("v", &v), std::make_pair("best_x", &best_x)})
+    TORCH_CHECK(nt.second->sizes() == x.sizes() && nt.second->scalar_type() == at::kFloat, nt.first, " must be (B, P) float32 as x");
+  for (const auto &nt : {std::make_pair("t", &t), std::make_pair("calls", &calls), std::make_pair("stall", &stall),
+                         std::make_pair("bad", &bad), std::make_pair("best_step", &best_step)})
+    TORCH_CHECK(nt.second->dim() == 1 && nt.second->size(0) == B && nt.second->scalar_type() == at::kInt, nt.first, " must be (B,) int32");
+  TORCH_CHECK(active.dim() == 1 && active.size(0) == B && active.scalar_type() == at::kByte, "active must be (B,) uint8");
+  TORCH_CHECK(best_loss.dim() == 1 && best_loss.size(0) == B && best_loss.scalar_type() == at::kFloat, "best_loss must be (B,) float32");
+  TORCH_CHECK(loss.dim() == 2 && loss.size(0) == B && loss.size(1) >= 1 && loss.size(1) <= INT32_MAX && loss.scalar_type() == at::kFloat,
+              "loss must be (B, N) float32, N >= 1");
+  TORCH_CHECK(!silh_loss || (silh_loss->dim() == 2 && silh_loss->size(0) == B && silh_loss->size(1) >= 1 &&
+                             silh_loss->size(1) <= INT32_MAX && silh_loss->scalar_type() == at::kFloat),
+              "silh_loss must be (B, Ns) float32, Ns >= 1");
+  TORCH_CHECK(col_scale.dim() == 1 && col_scale.size(0) == P && col_scale.scalar_type() == at::kFloat, "col_scale must be (P,) float32");
+  TORCH_CHECK(!history || (history->dim() == 2 && history->size(1) == B && history->size(0) <= INT32_MAX &&
+                           history->scalar_type() == at::kFloat), "history must be (H, B) float32");
+  TORCH_CHECK(mode == 0 || mode == 1, "mode must be 0 (keras) or 1 (torch)");
+  TORCH_CHECK(patience >= 0 && patience <= INT32_MAX && B <= INT32_MAX, "patience must be >= 0");
+}
+void fit_step(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
+              Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
+              const c10::optional<Tensor> &silh_loss, const Tensor &col_scale, c10::optional<Tensor> history, double lr,
+              double beta1, double beta2, double eps, double gscale, double silh_weight, int64_t mode, int64_t patience) {
+  fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
+                 patience);
+  dev_f32(x, "x"); dev_f32(g, "g"); dev_f32(m, "m"); dev_f32(v, "v"); dev_f32(best_x, "best_x"); dev_f32(best_loss, "best_loss");
+  dev_f32(loss, "loss"); dev_f32(col_scale, "col_scale");
+  dev_typed(t, at::kInt, "t"); dev_typed(calls, at::kInt, "calls"); dev_typed(stall, at::kInt, "stall");
+  dev_typed(bad, at::kInt, "bad"); dev_typed(best_step, at::kInt, "best_step"); dev_typed(active, at::kByte, "active");
+  if (silh_loss) dev_f32(*silh_loss, "silh_loss");
+  if (history) dev_f32(*history, "history");
+  const Tensor none;
+  same_device(x, {{"g", &g}, {"m", &m}, {"v", &v}, {"t", &t}, {"calls", &calls}, {"stall", &stall}, {"bad", &bad},
+                  {"best_step", &best_step}, {"active", &active}, {"best_loss", &best_loss}, {"best_x", &best_x}, {"loss", &loss},
+                  {"silh_loss", silh_loss ? &*silh_loss : &none}, {"col_scale", &col_scale}, {"history", history ? &*history : &none}});
+  DeviceGuard guard(x.device());
+  if (x.size(0) == 0) return;
+  const bool hist = history && history->numel() > 0;
+  ok(smplr_fit_step(x.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), t.data_ptr<int32_t>(),
+                    calls.data_ptr<int32_t>(), stall.data_ptr<int32_t>(), bad.data_ptr<int32_t>(), best_step.data_ptr<int32_t>(),
+                    active.data_ptr<uint8_t>(), best_loss.data_ptr<float>(), best_x.data_ptr<float>(), loss.data_ptr<float>(),
+                    (int)loss.size(1), silh_loss ? silh_loss->data_ptr<float>() : nullptr, silh_loss ? (int)silh_loss->size(1) : 0,
+                    (float)silh_weight, col_scale.data_ptr<float>(), hist ? history->data_ptr<float>() : nullptr,
+                    hist ? (int)history->size(0) : 0, (int)x.size(0), (int)x.size(1), (float)lr, (float)beta1, (float)beta2, (float)eps,
+                    (float)gscale, (int)mode, (int)patience, cur_stream()),
+     "smplr_fit_step");
+}
+void fit_step_meta(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
+                   Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
+                   const c10::optional<Tensor> &silh_loss, const Tensor &col_scale, c10::optional<Tensor> history, double, double,
+                   double, double, double, double, int64_t mode, int64_t patience) {
+  fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
+                 patience);
+}
+
 int64_t abi_version() { return smplr_abi_version(); }
 #ifndef SMPLR_TORCH_OPS_ID
 #define SMPLR_TORCH_OPS_ID "unknown"
@@ -862,6 +925,10 @@ TORCH_LIBRARY(smplraster, m) {
   m.def("seg_colour(Tensor input, Tensor lut, Tensor? background, int H, int W, int alpha_q=256, int bad_colour=0) -> Tensor");
   m.def("scatter_points(Tensor proj, Tensor? keep, Tensor? colours, Tensor? image, int H, int W, float scale, int radius=0, "
         "int order=0, int colour=11826975, int alpha_q=230, int canvas=16777215, bool return_vertex=True) -> (Tensor, Tensor)");
+  m.def("fit_step(Tensor(a!) x, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor(d!) t, Tensor(e!) calls, Tensor(f!) stall, "
+        "Tensor(g!) bad, Tensor(h!) best_step, Tensor(i!) active, Tensor(j!) best_loss, Tensor(k!) best_x, Tensor loss, "
+        "Tensor? silh_loss, Tensor col_scale, Tensor(l!)? history, float lr=0.001, float beta1=0.9, float beta2=0.999, "
+        "float eps=1e-07, float gscale=1.0, float silh_weight=1.0, int mode=0, int patience=0) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch key is named CUDA in torch)
@@ -885,6 +952,7 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("point_errors", &point_errors);
   m.impl("seg_colour", &seg_colour);
   m.impl("scatter_points", &scatter_points);
+  m.impl("fit_step", &fit_step);
 }
 
 TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
@@ -908,4 +976,5 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("point_errors", &point_errors_meta);
   m.impl("seg_colour", &seg_colour_meta);
   m.impl("scatter_points", &scatter_points_meta);
+  m.impl("fit_step", &fit_step_meta);
 }

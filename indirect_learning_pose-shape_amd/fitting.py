@@ -1,0 +1,352 @@
+"""Fitting SMPL parameters to label maps: per-sample Adam on the 86-vectors through the decoder and its fused loss.
+
+The reference's `decoder_loss_debugging.py:103-125` (`train()`: a table of learnable 86-vectors, 1601 Adam steps through
+decoder + focal loss) as a call, and the same loop as test-time refinement of an encoder's prediction:
+
+    fitter = ParamFitter(smpl_path, img_wh=48)
+    result = fitter.fit(labels)                                 # from the mean body; labels (B, 48, 48) integer part maps
+    result = fitter.fit(labels, init=prediction, stages=[(30, column_scale(cam=20., pose=0., shape=0.)),
+                                                         (200, column_scale(cam=0., shape=0.))])
+    result.x, result.loss, result.step                          # best iterate per row, its loss, the step it was reached
+
+One iteration is the decoder's forward (the loss head inside the rasteriser), its backward, and ONE more launch
+(csrc/fit.hip, smplr_fit_step) that does everything else per row of x (B, P): the row's loss, the loss trace, the check
+for non-finite values, the best iterate, the stop, and the Adam update.  No torch reduction, no optimiser object and no
+host synchronisation in the loop; the state is device memory, so G iterations replay from one captured graph.
+
+Semantics of one call for row b (the definition; tests/_fitting_oracle.py restates it in NumPy float64):
+  1. L = mean(loss[b, :]) (+ silh_weight mean(silh_loss[b, :])).  Thread i of `THREADS` adds its strided share serially in
+     fp32; a fixed tree combines the partial sums: the same bits on every launch and in any batch.
+  2. history[calls[b], b] = L while calls[b] < H; calls[b] += 1.
+  3. L or any g[b, :] not finite: bad[b] += 1, and nothing else of the row changes in this call.
+  4. Else, a row with active[b]: L < best_loss[b] (strict) -> best_loss[b] = L, best_x[b, :] = x[b, :] (the iterate that
+     produced L, before this call's update), best_step[b] = t[b], stall[b] = 0; otherwise stall[b] += 1.  With
+     patience > 0 and stall[b] >= patience: active[b] = 0 and no update.
+  5. A row still active: t += 1; g^ = grad_scale g; m = b1 m + (1 - b1) g^; v = b2 v + (1 - b2) g^ g^ (all P columns), and
+       "keras": x -= lr col_scale[j] sqrt(1 - b2^t) / (1 - b1^t) m / (sqrt(v) + eps)     (Keras 2 `Adam`, eps = 1e-7)
+       "torch": x -= lr col_scale[j] / (1 - b1^t) m / (sqrt(v) / sqrt(1 - b2^t) + eps)   (`torch.optim.Adam`)
+     with both bias corrections in fp64.  x[b, j] keeps its bits where col_scale[j] = 0 or the new m is 0 (so: frozen
+     columns, inactive and bad rows, and entries with g = m = v = 0).
+Stages change col_scale only: step counts, moments and the best iterate run on across them.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, fields
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, ptr, stream
+
+THREADS = 256                  # threads of a row's workgroup (csrc/fit.hip FT_T) = the widest row
+MODES = ("keras", "torch")
+KERAS_EPS = 1e-7               # keras.backend.epsilon(): Adam(epsilon=None) of Keras 2
+
+
+@dataclass
+class FitState:
+    """The per-row state smplr_fit_step reads and writes: x, m, v, best_x (B, P) fp32; t (updates done), calls, stall
+    (calls since the best), bad (calls with a non-finite loss or gradient), best_step (B) int32; active (B) uint8;
+    best_loss (B) fp32."""
+    x: torch.Tensor
+    m: torch.Tensor
+    v: torch.Tensor
+    best_x: torch.Tensor
+    t: torch.Tensor
+    calls: torch.Tensor
+    stall: torch.Tensor
+    bad: torch.Tensor
+    best_step: torch.Tensor
+    active: torch.Tensor
+    best_loss: torch.Tensor
+
+    @classmethod
+    def new(cls, x0):
+        """x0 (B, P) -> a fresh state around a float32 copy of it: m = v = 0, t = calls = stall = bad = best_step = 0,
+        active = 1, best_loss = +inf, best_x = x0."""
+        if not isinstance(x0, torch.Tensor):
+            x0 = torch.as_tensor(np.asarray(x0))
+        if x0.dim() != 2 or not 1 <= x0.shape[1] <= THREADS:
+            raise ValueError("x0 must be (B, P) with 1 <= P <= %d, got %s" % (THREADS, tuple(x0.shape)))
+        x = x0.detach().to(torch.float32).clone().contiguous()
+        B = x.shape[0]
+        zi = lambda: torch.zeros(B, dtype=torch.int32, device=x.device)
+        return cls(x=x, m=torch.zeros_like(x), v=torch.zeros_like(x), best_x=x.clone(), t=zi(), calls=zi(), stall=zi(),
+                   bad=zi(), best_step=zi(), active=torch.ones(B, dtype=torch.uint8, device=x.device),
+                   best_loss=torch.full((B,), float("inf"), dtype=torch.float32, device=x.device))
+
+    def clone(self):
+        return FitState(**{f.name: getattr(self, f.name).clone() for f in fields(self)})
+
+
+def column_scale(cam=1.0, pose=1.0, shape=1.0, num_cam=4):
+    """(P,) float32 per-column learning-rate multipliers for x = [cam (num_cam) | pose (72) | shape (10)]: camera columns are
+    in pixels, pose in radians, shape in standard deviations.  0 freezes a block."""
+    num_cam = int(num_cam)
+    if num_cam < 0 or num_cam + 82 > THREADS:
+        raise ValueError("num_cam must lie in 0..%d, got %r" % (THREADS - 82, num_cam))
+    s = torch.empty(num_cam + 82, dtype=torch.float32)
+    s[:num_cam], s[num_cam:num_cam + 72], s[num_cam + 72:] = float(cam), float(pose), float(shape)
+    if not bool(torch.isfinite(s).all()) or bool((s < 0).any()):
+        raise ValueError("column scales must be finite and >= 0, got cam=%r pose=%r shape=%r" % (cam, pose, shape))
+    return s
+
+
+def check_stages(stages, P, steps=None):
+    """A stage list [(steps, column_scale), ...] -> [(int steps, (P,) float32 CPU tensor), ...]; None -> one stage of
+    `steps` with every column at 1."""
+    if stages is None:
+        if steps is None:
+            raise ValueError("either steps or stages is needed")
+        stages = [(steps, torch.ones(P))]
+    out = []
+    for i, st in enumerate(stages):
+        if not isinstance(st, (tuple, list)) or len(st) != 2:
+            raise ValueError("stage %d must be (steps, column_scale), got %r" % (i, st))
+        n, cs = int(st[0]), torch.as_tensor(st[1], dtype=torch.float32).detach().cpu().contiguous()
+        if n < 0:
+            raise ValueError("stage %d has %d steps" % (i, n))
+        if tuple(cs.shape) != (P,):
+            raise ValueError("stage %d: column_scale must be (%d,), got %s" % (i, P, tuple(cs.shape)))
+        if not bool(torch.isfinite(cs).all()) or bool((cs < 0).any()):
+            raise ValueError("stage %d: column scales must be finite and >= 0" % i)
+        out.append((n, cs))
+    return out
+
+
+@_lib.on_device
+def fit_step(state, grad, loss, silh_loss=None, silh_weight=1.0, col_scale=None, history=None, lr=1e-3, beta1=0.9,
+             beta2=0.999, eps=KERAS_EPS, grad_scale=1.0, mode="keras", patience=0):
+    """One smplr_fit_step launch on `state` (in place; see the module's semantics).  grad (B, P): the gradient of
+    sum_b L_b; loss (B, N) and silh_loss (B, Ns): per-pixel losses as `SMPLDecoder(loss=...)` returns them; col_scale (P,)
+    (None: ones); history (H, B) or None.  HIP tensors only."""
+    if mode not in MODES:
+        raise ValueError("mode %r is none of %s" % (mode, MODES))
+    rc = _lib.require_cuda
+    if not state.x.is_contiguous():
+        raise RuntimeError("x must be contiguous (it is updated in place)")
+    x = rc(state.x, "x")
+    B, P = int(x.shape[0]), int(x.shape[1])
+    same = {"grad": grad, "m": state.m, "v": state.v, "best_x": state.best_x}
+    ints = {"t": state.t, "calls": state.calls, "stall": state.stall, "bad": state.bad, "best_step": state.best_step}
+    for name, a in same.items():
+        if tuple(a.shape) != (B, P) or not a.is_contiguous():
+            raise RuntimeError("%s must be a contiguous (%d, %d) tensor, got %s" % (name, B, P, tuple(a.shape)))
+        rc(a, name)
+    for name, a in ints.items():
+        if tuple(a.shape) != (B,):
+            raise RuntimeError("%s must be (%d,), got %s" % (name, B, tuple(a.shape)))
+        rc(a, name, torch.int32)
+    if tuple(state.active.shape) != (B,) or tuple(state.best_loss.shape) != (B,):
+        raise RuntimeError("active and best_loss must be (%d,)" % B)
+    rc(state.active, "active", torch.uint8)
+    rc(state.best_loss, "best_loss")
+    if loss.dim() != 2 or loss.shape[0] != B or loss.shape[1] < 1 or not loss.is_contiguous():
+        raise RuntimeError("loss must be a contiguous (%d, N) tensor, got %s" % (B, tuple(loss.shape)))
+    rc(loss, "loss")
+    Ns = 0
+    if silh_loss is not None:
+        if silh_loss.dim() != 2 or silh_loss.shape[0] != B or silh_loss.shape[1] < 1 or not silh_loss.is_contiguous():
+            raise RuntimeError("silh_loss must be a contiguous (%d, Ns) tensor, got %s" % (B, tuple(silh_loss.shape)))
+        rc(silh_loss, "silh_loss")
+        Ns = int(silh_loss.shape[1])
+    if col_scale is None:
+        col_scale = torch.ones(P, dtype=torch.float32, device=x.device)
+    if tuple(col_scale.shape) != (P,) or not col_scale.is_contiguous():
+        raise RuntimeError("col_scale must be a contiguous (%d,) tensor, got %s" % (P, tuple(col_scale.shape)))
+    rc(col_scale, "col_scale")
+    H = 0
+    if history is not None:
+        if history.dim() != 2 or history.shape[1] != B or not history.is_contiguous():
+            raise RuntimeError("history must be a contiguous (H, %d) tensor, got %s" % (B, tuple(history.shape)))
+        rc(history, "history")
+        H = int(history.shape[0])
+    for name, a in list(same.items()) + list(ints.items()) + [("active", state.active), ("best_loss", state.best_loss),
+                                                               ("loss", loss), ("silh_loss", silh_loss),
+                                                               ("col_scale", col_scale), ("history", history)]:
+        if a is not None and a.device != x.device:
+            raise RuntimeError("%s lives on %s, x on %s" % (name, a.device, x.device))
+    check(_lib.load().smplr_fit_step(ptr(x), ptr(grad), ptr(state.m), ptr(state.v), ptr(state.t), ptr(state.calls),
+                                     ptr(state.stall), ptr(state.bad), ptr(state.best_step), ptr(state.active),
+                                     ptr(state.best_loss), ptr(state.best_x), ptr(loss), int(loss.shape[1]), ptr(silh_loss), Ns,
+                                     float(silh_weight), ptr(col_scale), ptr(history) if H else None, H, B, P, float(lr),
+                                     float(beta1), float(beta2), float(eps), float(grad_scale), MODES.index(mode),
+                                     int(patience), stream()), "smplr_fit_step")
+    return state
+
+
+@dataclass
+class FitResult:
+    """x (B, P): the best iterate of each row; loss (B,): its loss; step (B,) int32: the update count it was reached at;
+    final_x (B, P): where the row stood at the end; nonfinite (B,) int32: calls that met a non-finite loss or gradient (and
+    changed nothing); active (B,) bool: rows the patience rule had not stopped; history (steps run, B) fp32 loss trace or
+    None; steps: iterations run (fewer than asked for when `check_every` found every row stopped); state: the whole
+    `FitState` the loop ended with (moments and counters included)."""
+    x: torch.Tensor
+    loss: torch.Tensor
+    step: torch.Tensor
+    final_x: torch.Tensor
+    nonfinite: torch.Tensor
+    active: torch.Tensor
+    history: Optional[torch.Tensor]
+    steps: int
+    state: Optional[FitState] = None
+
+
+class ParamFitter:
+    """Owns an `SMPLDecoder(outputs=(), loss=softmax_focal_loss(gamma, weight_classes)[, silh_loss=...])` and fits its
+    input to label maps.  The defaults are those of decoder_loss_debugging.py:117-118: focal loss with gamma = 5, no class
+    weights; `fit`'s are Keras' Adam (lr 1e-3, eps 1e-7)."""
+
+    def __init__(self, smpl_path=None, img_wh=48, gamma=5.0, weight_classes=False, with_silhouette=False, silh_wh=None,
+                 silh_weight=1.0, vertex_sampling=None, deterministic=False):
+        from .decoder import SMPLDecoder
+        from .focal_loss import softmax_focal_loss
+        self.img_wh = int(img_wh)
+        self.with_silhouette = bool(with_silhouette)
+        self.silh_weight = float(silh_weight)
+        # (streams=1: one chain of launches, so a captured graph has no parallel branches)
+        self.decoder = SMPLDecoder(smpl_path, img_wh=self.img_wh, vertex_sampling=vertex_sampling,
+                                   with_silhouette=self.with_silhouette, silh_wh=silh_wh, streams=1,
+                                   deterministic=deterministic, outputs=(), loss=softmax_focal_loss(gamma, weight_classes),
+                                   silh_loss=softmax_focal_loss(0.0, False) if self.with_silhouette else None)
+        self.num_cam = self.decoder.num_cam
+        self.P = self.num_cam + 82
+        self.silh_wh = self.decoder.silh_wh
+
+    # ---- inputs -------------------------------------------------------------------------------------------------------
+    def initial(self, B, init=None, generator=None, device=None):
+        """(B, P) float32 start: None = `smpl_model.mean86(img_wh)` per row; "reference" = that plus Keras' Embedding
+        initialiser uniform(-0.05, 0.05) drawn from `generator` (decoder_loss_debugging.py:75-77); a (B, P) tensor as it is
+        (an encoder's prediction)."""
+        from .smpl_model import mean86
+        if isinstance(init, torch.Tensor):
+            if tuple(init.shape) != (B, self.P):
+                raise ValueError("init must be (%d, %d), got %s" % (B, self.P, tuple(init.shape)))
+            x0 = init.detach().to(torch.float32)
+            return x0.to(device) if device is not None else x0
+        if self.num_cam != 4:
+            raise ValueError("the mean parameters have 4 camera columns")
+        mean = torch.as_tensor(mean86(self.img_wh), dtype=torch.float32).repeat(B, 1)
+        if init is None:
+            x0 = mean
+        elif init == "reference":
+            x0 = mean + (torch.rand(B, self.P, generator=generator) * 0.1 - 0.05)
+        else:
+            raise ValueError("init must be None, 'reference' or a (B, %d) tensor, got %r" % (self.P, init))
+        return x0.to(device) if device is not None else x0
+
+    def _labels(self, labels, B, W, name):
+        if not isinstance(labels, torch.Tensor) or labels.is_floating_point() or labels.numel() != B * W * W:
+            raise ValueError("%s must be an integer map of %d x %d x %d entries" % (name, B, W, W))
+        return _lib.require_cuda(labels.to(torch.int32).reshape(B, W, W), name, torch.int32)
+
+    # ---- one iteration ------------------------------------------------------------------------------------------------
+    def losses(self, x, labels, silh_labels=None):
+        """Per-row loss (B,) fp32 of parameters x (B, P) against the labels: one gradient-free decoder forward reduced by
+        the kernel of the loop (a call with a zero gradient on a scratch state), so the bits are those `fit` would record
+        for x in its history."""
+        B = int(x.shape[0])
+        labels = self._labels(labels, B, self.img_wh, "labels")
+        if (silh_labels is not None) != self.with_silhouette:
+            raise ValueError("silh_labels go with ParamFitter(with_silhouette=True), and only with it")
+        if silh_labels is not None:
+            silh_labels = self._labels(silh_labels, B, self.silh_wh, "silh_labels")
+        x = _lib.require_cuda(x.detach(), "x")
+        with torch.no_grad(), torch.cuda.device(x.device):
+            out = self.decoder(x, labels, silh_labels=silh_labels)
+            hist = torch.empty((1, B), dtype=torch.float32, device=x.device)
+            fit_step(FitState.new(x), torch.zeros_like(x), out["seg_loss"],
+                     out["silh_loss"] if silh_labels is not None else None, self.silh_weight, None, hist)
+        return hist[0]
+
+    def _iteration(self, state, labels, silh_labels, gout, sgout, cs, hist, kw):
+        x = state.x.detach().requires_grad_(True)                 # (shares x's memory: the kernel updates it in place)
+        out = self.decoder(x, labels, silh_labels=silh_labels)
+        seg_loss = out["seg_loss"]
+        if silh_labels is None:
+            (g,) = torch.autograd.grad([seg_loss], [x], grad_outputs=[gout])
+            sl = None
+        else:
+            sl = out["silh_loss"]
+            (g,) = torch.autograd.grad([seg_loss, sl], [x], grad_outputs=[gout, sgout])
+            sl = sl.detach()
+        fit_step(state, g.contiguous(), seg_loss.detach(), sl, self.silh_weight, cs, hist, **kw)
+
+    # ---- the loop -----------------------------------------------------------------------------------------------------
+    def fit(self, labels, init=None, steps=1601, lr=1e-3, mode="keras", stages=None, silh_labels=None, patience=0,
+            grad_scale=1.0, graph=False, check_every=0, history=False, beta1=0.9, beta2=0.999, eps=KERAS_EPS,
+            graph_steps=4, generator=None):
+        """labels (B, W, W) integer part maps on the HIP device -> FitResult.
+
+        steps: iterations (decoder_loss_debugging.py:123 runs 1601), or stages = [(steps, column_scale), ...] run one after
+        the other; silh_labels (B, Ws, Ws) with `with_silhouette=True`; patience: a row stops after that many calls in a row
+        without a new best (0: never); grad_scale = 1 / B reproduces Keras' batch-mean loss (decoder_loss_debugging.py:125,
+        batch_size = num_indices); graph=True replays `graph_steps` iterations per launch of one captured HIP graph;
+        check_every = k > 0 reads `active.any()` every k iterations (the loop's only host synchronisation) and stops when
+        no row is active; history=True records every call's loss per row."""
+        if mode not in MODES:
+            raise ValueError("mode %r is none of %s" % (mode, MODES))
+        if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
+            raise ValueError("labels must be a (B, W, W) integer tensor")
+        B, W = int(labels.shape[0]), self.img_wh
+        labels = self._labels(labels, B, W, "labels")
+        dev = labels.device
+        if (silh_labels is not None) != self.with_silhouette:
+            raise ValueError("silh_labels go with ParamFitter(with_silhouette=True), and only with it")
+        if silh_labels is not None:
+            silh_labels = self._labels(silh_labels, B, self.silh_wh, "silh_labels")
+        stage_list = check_stages(stages, self.P, steps)
+        total = sum(n for n, _ in stage_list)
+        G = max(1, int(graph_steps))
+        check_every = int(check_every)
+        with torch.cuda.device(dev):
+            state = FitState.new(self.initial(B, init, generator, dev))
+            hist = torch.full((total, B), float("nan"), dtype=torch.float32, device=dev) if history and total else None
+            N, Ns = W * W, self.silh_wh * self.silh_wh
+            gout = torch.full((B, N), 1.0 / N, dtype=torch.float32, device=dev)
+            sgout = torch.full((B, Ns), self.silh_weight / Ns, dtype=torch.float32, device=dev) if self.with_silhouette else None
+            cs = torch.ones(self.P, dtype=torch.float32, device=dev)
+            scales = [c.to(dev) for _, c in stage_list]
+            kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
+                      mode=mode, patience=int(patience))
+            one = lambda st, h: self._iteration(st, labels, silh_labels, gout, sgout, cs, h, kw)
+            replay = None
+            if graph and B > 0 and any(n >= G for n, _ in stage_list):
+                # warm-up on a side stream and on a scratch state, then G iterations of the real state in one graph
+                scratch = state.clone()
+                side = torch.cuda.Stream(device=dev)
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    for _ in range(3):
+                        one(scratch, None)
+                torch.cuda.current_stream().wait_stream(side)
+                torch.cuda.synchronize()
+                g_ = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g_):
+                    for _ in range(G):
+                        one(state, hist)
+                replay = g_.replay
+            done, stopped = 0, False
+            for (n, _), sc in zip(stage_list, scales):
+                cs.copy_(sc)
+                left = n
+                while left > 0 and not stopped:
+                    if replay is not None and left >= G:
+                        replay()
+                        k = G
+                    else:
+                        one(state, hist)
+                        k = 1
+                    left -= k
+                    if check_every > 0 and B > 0 and (done + k) // check_every > done // check_every:
+                        stopped = not bool(state.active.any())
+                    done += k
+                if stopped:
+                    break
+            torch.cuda.synchronize()
+        return FitResult(x=state.best_x, loss=state.best_loss, step=state.best_step, final_x=state.x, nonfinite=state.bad,
+                         active=state.active.bool(), history=hist[:done] if hist is not None else None, steps=done,
+                         state=state)

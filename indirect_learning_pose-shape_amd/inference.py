@@ -22,6 +22,23 @@ def predict_batch(smpl_model, decoder, images):
             "seg_maps": out["seg"].argmax(dim=-1)}
 
 
+def refine_predictions(smpl_model, fitter, images, labels, **fit_kw):
+    """The encoder's prediction refined against label maps (ground truth or another network's segmentation): one
+    forward of `smpl_model` on images, then `fitter.fit(labels, init=prediction, **fit_kw)` (`fitting.ParamFitter`).
+    -> dict(smpl (N, 86): the network's parameters, refined (N, 86): the best iterate of each row, loss (N,): its loss,
+    result: the whole `fitting.FitResult`).  The best iterate includes step 0, so `refined` is never worse than `smpl`
+    under the fitter's loss."""
+    was_training = smpl_model.training
+    smpl_model.eval()
+    try:
+        with torch.no_grad():
+            pred = smpl_model(images)
+    finally:
+        smpl_model.train(was_training)
+    result = fitter.fit(labels, init=pred, **fit_kw)
+    return {"smpl": pred, "refined": result.x, "loss": result.loss, "result": result}
+
+
 class GraphedPredictor:
     """`predict_batch` for a fixed image shape replayed from ONE captured HIP graph: at batch 1 the eager forward
     is bound by ~500 host-side kernel launches (6.7 ms per image), the graph by the kernels themselves.

@@ -262,6 +262,37 @@ def build_debug_model(batch_size, smpl_path, output_img_wh, num_classes, vertex_
             FullModel(smpl_model, decoder, "projects"))
 
 
+def fit_debug_model(labels, smpl_path=None, output_img_wh=48, num_classes=32, vertex_sampling=None, indices=None,
+                    steps=1601, generator=None, smpl_model=None, **fit_kw):
+    """`train()` of decoder_loss_debugging.py:103-125 as a call: the rows `indices` (default: all of them, as the
+    reference's `train_indices = np.arange(num_indices)`) of an embedding table are fitted to `labels` (num_indices, W, W)
+    integer part maps by `steps` Adam updates through decoder + focal loss (gamma = 5, Keras' Adam, the batch-mean loss of
+    `fit(batch_size=num_indices)`), on `fitting.ParamFitter`.  smpl_model: an `EmbeddedSMPLParams` whose table rows start
+    the fit and receive the result (default: a fresh one, Keras' uniform(-0.05, 0.05) initialiser drawn from `generator`).
+    Returns (smpl_model, result): the table holds the fitted rows - `smpl_model(indices)` is `result.x` - and `result`
+    is the `fitting.FitResult`.  `build_debug_model`'s handles are not needed for it."""
+    from .fitting import ParamFitter
+    if num_classes != 32:
+        raise ValueError("the decoder produces 32 classes (31 parts + background)")
+    n = int(labels.shape[0])
+    idx = torch.arange(n) if indices is None else torch.as_tensor(indices).reshape(-1).long().cpu()
+    if idx.numel() != n:
+        raise ValueError("%d indices for %d label maps" % (idx.numel(), n))
+    if smpl_model is None:
+        smpl_model = EmbeddedSMPLParams(output_img_wh, num_embeddings=max(25, int(idx.max()) + 1 if n else 25))
+        with torch.no_grad():
+            smpl_model.table.weight.copy_(torch.rand(smpl_model.table.weight.shape, generator=generator) * 0.1 - 0.05)
+    fitter = ParamFitter(smpl_path, img_wh=output_img_wh, gamma=5.0, vertex_sampling=vertex_sampling)
+    with torch.no_grad():
+        init = smpl_model(idx.to(smpl_model.table.weight.device))
+    fit_kw.setdefault("grad_scale", 1.0 / max(n, 1))
+    result = fitter.fit(labels, init=init.to(labels.device), steps=steps, **fit_kw)
+    with torch.no_grad():
+        mean = load_mean_set_cam_params(torch.zeros(1, 86, device=result.x.device), output_img_wh)
+        smpl_model.table.weight[idx.to(smpl_model.table.weight.device)] = (result.x - mean).to(smpl_model.table.weight.device)
+    return smpl_model, result
+
+
 def build_full_model_from_saved_model_stage2(smpl_model, segs_output_wh, silhs_output_wh, smpl_path, batch_size,
                                              num_classes_segs=32, num_classes_silhs=2):
     """`build_full_model_from_saved_model` of train_stage2_silhouette.py:72-104: around a saved encoder, the part

@@ -59,6 +59,11 @@ SCHEMAS = {
     "scatter_points": ("smplraster::scatter_points(Tensor proj, Tensor? keep, Tensor? colours, Tensor? image, int H, int W, "
                        "float scale, int radius=0, int order=0, int colour=11826975, int alpha_q=230, int canvas=16777215, "
                        "bool return_vertex=True) -> (Tensor, Tensor)"),
+    "fit_step": ("smplraster::fit_step(Tensor(a!) x, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor(d!) t, Tensor(e!) calls, "
+                 "Tensor(f!) stall, Tensor(g!) bad, Tensor(h!) best_step, Tensor(i!) active, Tensor(j!) best_loss, "
+                 "Tensor(k!) best_x, Tensor loss, Tensor? silh_loss, Tensor col_scale, Tensor(l!)? history, float lr=0.001, "
+                 "float beta1=0.90000000000000002, float beta2=0.999, float eps=9.9999999999999995e-08, float gscale=1., "
+                 "float silh_weight=1., int mode=0, int patience=0) -> ()"),
 }
 
 _ns = None

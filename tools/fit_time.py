@@ -1,0 +1,141 @@
+"""Iterations per second of fitting SMPL parameters to label maps, three loops at the same commit, one GPU:
+    python tools/fit_time.py [--batch 128] [--iters 1600] [--rounds 3] [--launches]
+At B = 128, W = 48 (the reference's decoder_loss_debugging.py runs the loop at W = 48), targets = the arg-max part maps
+of seeded parameters, start = those parameters with pose noise and a camera shift:
+    stock     the loop a user of the decoder writes with stock torch: the same `SMPLDecoder(loss=...)`, `seg_loss.mean(1)`,
+              `torch.optim.Adam([x])`, best-iterate tracking with torch.where (`stock_fit` below)
+    fitter    `fitting.ParamFitter.fit`, eager: decoder forward + backward + ONE smplr_fit_step launch per iteration
+    graph     `ParamFitter.fit(graph=True, graph_steps=G)`: G iterations per replay of one captured HIP graph
+Each figure is a host clock around a whole `fit` / `stock_fit` call of --iters iterations that ends in a device
+synchronise (set-up, warm-up and graph capture of that call included: they are part of what a user waits for), taken
+after one untimed call per loop; the loops alternate --rounds times, every round is printed, the median is reported.
+--launches counts the device kernels per iteration of each loop with torch.profiler in a short run of its own (tracing
+slows the host: no timing is taken from it)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import ilps_amd  # noqa: E402,F401
+
+
+def stock_fit(decoder, labels, x0, steps, lr=1e-3, eps=1e-8, history=False):
+    """The stock loop: torch.optim.Adam on x (B, 86) against the decoder's per-pixel loss, with the best iterate per row.
+    -> (best_x, best_loss, final_x, history (steps, B) or None)."""
+    x = x0.detach().clone().requires_grad_(True)
+    opt = torch.optim.Adam([x], lr=lr, eps=eps)
+    B = x.shape[0]
+    best_loss = torch.full((B,), float("inf"), device=x.device)
+    best_x = x.detach().clone()
+    hist = torch.empty((steps, B), device=x.device) if history else None
+    for k in range(steps):
+        opt.zero_grad(set_to_none=True)
+        L = decoder(x, labels)["seg_loss"].mean(1)
+        L.sum().backward()
+        with torch.no_grad():
+            Ld = L.detach()
+            if hist is not None:
+                hist[k] = Ld
+            better = Ld < best_loss
+            best_loss = torch.where(better, Ld, best_loss)
+            best_x = torch.where(better[:, None], x.detach(), best_x)
+        opt.step()
+    torch.cuda.synchronize()
+    return best_x, best_loss, x.detach(), hist
+
+
+def problem(fitter, B, W, seed=0, pose_sigma=0.05, cam_shift=1.5):
+    """Seeded targets and a perturbed start: labels (B, W, W) int32 = arg-max of the decoder's scores at x*, x0 = x* with
+    N(0, pose_sigma) on the pose columns and cam_shift pixels on the camera translation."""
+    from _inputs import make_x
+    from ilps_amd.decoder import SMPLDecoder
+    dev = torch.device("cuda:0")
+    xs = torch.from_numpy(make_x(B, W, seed=seed)).to(dev)
+    plain = SMPLDecoder(fitter.decoder._model, img_wh=W, outputs=()).share_constants(fitter.decoder)
+    with torch.no_grad():
+        labels = plain(xs)["seg"].argmax(-1).to(torch.int32)
+    rng = np.random.default_rng(seed + 1)
+    d = np.zeros((B, 86), np.float32)
+    d[:, 2:4] = cam_shift * rng.choice([-1.0, 1.0], (B, 2))
+    d[:, 4:76] = rng.normal(0.0, pose_sigma, (B, 72))
+    return labels, xs + torch.from_numpy(d).to(dev), xs
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def kernels_per_iteration(fn, iters):
+    """Device kernels per iteration of fn(n): traced runs of n = iters, 2 iters and 3 iters; the slope between the first and
+    the last (set-up launches cancel), with the raw counts beside it so that a trace that lost records shows."""
+    from torch.profiler import ProfilerActivity, profile
+
+    def count(n):
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn(n)
+            torch.cuda.synchronize()
+        return sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "memcpy" not in e.name.lower()
+                   and "memset" not in e.name.lower())
+    counts = [count(k * iters) for k in (1, 2, 3)]
+    return {"per_iteration": round((counts[2] - counts[0]) / (2.0 * iters), 2), "iterations": [iters, 2 * iters, 3 * iters],
+            "kernels": counts}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=128)
+    ap.add_argument("--wh", type=int, default=48)
+    ap.add_argument("--iters", type=int, default=1600)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--graph-steps", type=int, default=10)
+    ap.add_argument("--launches", action="store_true")
+    a = ap.parse_args()
+    from ilps_amd import _lib
+    from ilps_amd.fitting import ParamFitter
+    B, W, G = a.batch, a.wh, a.graph_steps
+    fitter = ParamFitter(None, img_wh=W)
+    labels, x0, _ = problem(fitter, B, W)
+    loops = {"stock": lambda n: stock_fit(fitter.decoder, labels, x0, n),
+             "fitter": lambda n: fitter.fit(labels, init=x0, steps=n),
+             "graph": lambda n: fitter.fit(labels, init=x0, steps=n, graph=True, graph_steps=G)}
+    res = {"build_id": _lib.build_id()[:16], "B": B, "W": W, "iters": a.iters, "graph_steps": G}
+    if a.launches:
+        for fn in loops.values():
+            fn(2 * G)                                               # untimed and untraced: code objects loaded
+        res["kernels"] = {k: kernels_per_iteration(fn, 4 * G) for k, fn in loops.items()}
+        print(json.dumps(res))
+        return
+    n = a.iters - a.iters % G
+    for fn in loops.values():
+        fn(n)                                                   # untimed: code objects, allocator pools
+    us = {k: [] for k in loops}
+    for _ in range(a.rounds):
+        for k, fn in loops.items():
+            us[k].append(wall(lambda: fn(n)) * 1e6 / n)
+    res["us_per_iteration_rounds"] = {k: [round(v, 1) for v in vs] for k, vs in us.items()}
+    res["us_per_iteration"] = {k: round(statistics.median(vs), 1) for k, vs in us.items()}
+    res["iterations_per_s"] = {k: round(1e6 / statistics.median(vs)) for k, vs in us.items()}
+    # the three loops on the same problem: mean best loss against the start's (not the same optimiser: stock is torch's Adam)
+    s = stock_fit(fitter.decoder, labels, x0, n)
+    f = fitter.fit(labels, init=x0, steps=n)
+    res["mean_loss"] = {"start": round(float(fitter.losses(x0, labels).mean()), 6), "stock": round(float(s[1].mean()), 6),
+                        "fitter": round(float(f.loss.mean()), 6)}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
