@@ -7,70 +7,33 @@
 // slope gradient in registers: a workgroup owns one (image, channel) plane chunk, reduces its
 // sum and stores ONE partial; a second kernel adds the partials of a channel in a fixed order.
 // NCHW, fp32.  HBM-bound: forward 8 B/element, backward 12 B/element.
-#include "common.h"
+#include "plane_walk.h"
 
 namespace smplr {
 
-constexpr int PR_T = 256;
-constexpr int PR_CHUNK = 4096;       // elements of a plane per workgroup (16 per thread)
-
-__global__ __launch_bounds__(PR_T) void prelu_fwd_kernel(const float *__restrict__ x, const float *__restrict__ w,
+__global__ __launch_bounds__(PW_T) void prelu_fwd_kernel(const float *__restrict__ x, const float *__restrict__ w,
                                                          int C, int HW, int chunks, float *__restrict__ y) {
-  const long long plane = blockIdx.x / chunks;
-  const int chunk = blockIdx.x - (int)(plane * chunks);
-  const float a = w[plane % C];
-  const size_t base = (size_t)plane * HW;
-  const int e0 = chunk * PR_CHUNK, e1 = min(HW, e0 + PR_CHUNK);
-  if (((HW | e0) & 3) == 0) {                         // plane rows are 16-B aligned: float4 path
-    const float4 *xv = reinterpret_cast<const float4 *>(x + base);
-    float4 *yv = reinterpret_cast<float4 *>(y + base);
-    for (int i = e0 / 4 + threadIdx.x; i < e1 / 4; i += PR_T) {
-      float4 v = xv[i];
-      v.x = v.x > 0.f ? v.x : a * v.x; v.y = v.y > 0.f ? v.y : a * v.y;
-      v.z = v.z > 0.f ? v.z : a * v.z; v.w = v.w > 0.f ? v.w : a * v.w;
-      yv[i] = v;
-    }
-  } else {
-    for (int i = e0 + threadIdx.x; i < e1; i += PR_T) {
-      const float v = x[base + i];
-      y[base + i] = v > 0.f ? v : a * v;
-    }
-  }
+  const PlaneChunk pc = plane_chunk(C, HW, chunks);
+  const float a = w[pc.c];
+  const float *in[1] = {x};
+  float *out[1] = {y};
+  plane_walk<1, 1>(pc, HW, in, out, [&](const float *v, float *o) { o[0] = v[0] > 0.f ? v[0] : a * v[0]; });
 }
 
-__global__ __launch_bounds__(PR_T) void prelu_bwd_kernel(const float *__restrict__ x, const float *__restrict__ w,
+__global__ __launch_bounds__(PW_T) void prelu_bwd_kernel(const float *__restrict__ x, const float *__restrict__ w,
                                                          const float *__restrict__ gy, int C, int HW, int chunks,
                                                          float *__restrict__ gx, float *__restrict__ part) {
-  __shared__ float red[PR_T / 64];
-  const long long plane = blockIdx.x / chunks;
-  const int chunk = blockIdx.x - (int)(plane * chunks);
-  const float a = w[plane % C];
-  const size_t base = (size_t)plane * HW;
-  const int e0 = chunk * PR_CHUNK, e1 = min(HW, e0 + PR_CHUNK);
+  __shared__ float red[12];
+  const PlaneChunk pc = plane_chunk(C, HW, chunks);
+  const float a = w[pc.c];
+  const float *in[2] = {x, gy};
+  float *out[1] = {gx};
   float s = 0.f;
-  if (((HW | e0) & 3) == 0) {
-    const float4 *xv = reinterpret_cast<const float4 *>(x + base), *gv = reinterpret_cast<const float4 *>(gy + base);
-    float4 *ov = reinterpret_cast<float4 *>(gx + base);
-    for (int i = e0 / 4 + threadIdx.x; i < e1 / 4; i += PR_T) {
-      const float4 v = xv[i], g = gv[i];
-      float4 o;
-      o.x = v.x > 0.f ? g.x : a * g.x; s += v.x > 0.f ? 0.f : g.x * v.x;
-      o.y = v.y > 0.f ? g.y : a * g.y; s += v.y > 0.f ? 0.f : g.y * v.y;
-      o.z = v.z > 0.f ? g.z : a * g.z; s += v.z > 0.f ? 0.f : g.z * v.z;
-      o.w = v.w > 0.f ? g.w : a * g.w; s += v.w > 0.f ? 0.f : g.w * v.w;
-      ov[i] = o;
-    }
-  } else {
-    for (int i = e0 + threadIdx.x; i < e1; i += PR_T) {
-      const float v = x[base + i], g = gy[base + i];
-      gx[base + i] = v > 0.f ? g : a * g;
-      s += v > 0.f ? 0.f : g * v;
-    }
-  }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  plane_walk<2, 1>(pc, HW, in, out, [&](const float *v, float *o) {
+    o[0] = v[0] > 0.f ? v[1] : a * v[1];
+    s += v[0] > 0.f ? 0.f : v[1] * v[0];
+  });
+  block_store3(s, 0.f, 0.f, red, part + blockIdx.x, 1);
 }
 
 // gw[c] = sum over images n and chunks of part[(n*C + c)*chunks + chunk], in index order
@@ -87,18 +50,16 @@ __global__ __launch_bounds__(64) void prelu_bwd_reduce_kernel(const float *__res
   if (lane == 0) gw[c] = s;
 }
 
-static int prelu_chunks(int HW) { return (HW + PR_CHUNK - 1) / PR_CHUNK; }
-
 }  // namespace smplr
 
 extern "C" int smplr_prelu_fwd(const float *x, const float *w, long long N, int C, int HW, float *y, void *stream) {
   using namespace smplr;
-  SMPLR_REQUIRE(N >= 0 && C > 0 && HW > 0 && N * C * (long long)prelu_chunks(HW) < (1ll << 31),
+  SMPLR_REQUIRE(plane_sizes_ok(N, C, HW),
                 "smplr_prelu_fwd: bad sizes N=%lld C=%d HW=%d", N, C, HW);
   if (N == 0) return 0;
   SMPLR_REQUIRE(x && w && y, "smplr_prelu_fwd: null pointer");
-  const int chunks = prelu_chunks(HW);
-  hipLaunchKernelGGL(prelu_fwd_kernel, dim3((unsigned)(N * C * chunks)), dim3(PR_T), 0, as_stream(stream), x, w, C, HW,
+  const int chunks = plane_chunks(HW);
+  hipLaunchKernelGGL(prelu_fwd_kernel, dim3((unsigned)(N * C * chunks)), dim3(PW_T), 0, as_stream(stream), x, w, C, HW,
                      chunks, y);
   SMPLR_LAUNCH_CHECK("smplr_prelu_fwd");
   return 0;
@@ -106,13 +67,13 @@ extern "C" int smplr_prelu_fwd(const float *x, const float *w, long long N, int 
 
 extern "C" size_t smplr_prelu_bwd_workspace(long long N, int C, int HW) {
   if (N <= 0 || C <= 0 || HW <= 0) return 0;
-  return (size_t)N * C * smplr::prelu_chunks(HW) * sizeof(float);
+  return (size_t)N * C * smplr::plane_chunks(HW) * sizeof(float);
 }
 
 extern "C" int smplr_prelu_bwd(const float *x, const float *w, const float *gy, long long N, int C, int HW, float *gx,
                                float *gw, void *workspace, void *stream) {
   using namespace smplr;
-  SMPLR_REQUIRE(N >= 0 && C > 0 && HW > 0 && N * C * (long long)prelu_chunks(HW) < (1ll << 31),
+  SMPLR_REQUIRE(plane_sizes_ok(N, C, HW),
                 "smplr_prelu_bwd: bad sizes N=%lld C=%d HW=%d", N, C, HW);
   SMPLR_REQUIRE(gw != nullptr, "smplr_prelu_bwd: null gw");
   if (N == 0) {
@@ -120,9 +81,9 @@ extern "C" int smplr_prelu_bwd(const float *x, const float *w, const float *gy, 
     return 0;
   }
   SMPLR_REQUIRE(x && w && gy && gx && workspace, "smplr_prelu_bwd: null pointer");
-  const int chunks = prelu_chunks(HW);
+  const int chunks = plane_chunks(HW);
   float *part = reinterpret_cast<float *>(workspace);
-  hipLaunchKernelGGL(prelu_bwd_kernel, dim3((unsigned)(N * C * chunks)), dim3(PR_T), 0, as_stream(stream), x, w, gy, C,
+  hipLaunchKernelGGL(prelu_bwd_kernel, dim3((unsigned)(N * C * chunks)), dim3(PW_T), 0, as_stream(stream), x, w, gy, C,
                      HW, chunks, gx, part);
   SMPLR_LAUNCH_CHECK("smplr_prelu_bwd");
   hipLaunchKernelGGL(prelu_bwd_reduce_kernel, dim3(C), dim3(64), 0, as_stream(stream), part, N, C, chunks, gw);

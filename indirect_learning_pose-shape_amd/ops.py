@@ -928,10 +928,7 @@ def batch_norm_act(x, bn, act=None):
     """`act(bn(x))` for a torch.nn.BatchNorm2d and an optional per-channel nn.PReLU.  Training mode on a HIP
     device with planes of >= 256 elements runs the fused HIP kernels; everything else (eval mode, CPU, tiny
     planes, other dtypes) takes the stock modules.  Parameters, buffers and state dict are the modules' own."""
-    fused = (bn.training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and bn.affine and x.is_contiguous()
-             and bn.track_running_stats and bn.momentum is not None and x.shape[2] * x.shape[3] >= 256
-             and (act is None or act.weight.numel() == x.shape[1]) and x.shape[0] > 0)
-    if not fused:
+    if not (_bn_fusable(x, bn) and (act is None or act.weight.numel() == x.shape[1])):
         y = bn(x)
         return act(y) if act is not None else y
     if bn.num_batches_tracked is not None:
