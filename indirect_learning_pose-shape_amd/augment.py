@@ -18,20 +18,13 @@ import math
 
 import torch
 
-from . import _lib
+from . import _gather, _lib
+from ._gather import MAX_OUT, _hw, _out_hw
 from ._lib import check, ptr, stream
 
 IMAGE_NEAREST, IMAGE_BILINEAR, LABEL, LABEL_BINARY = 0, 1, 2, 3      # SMPLR_WARP_* of include/smplraster.h
-MAX_OUT, MAX_POOL = 4096, 8192
+MAX_POOL = 8192
 DRAW_KEYS = ("theta", "tx", "ty", "shear", "zx", "zy", "flip")
-
-
-def _hw(size):
-    if isinstance(size, (tuple, list)):
-        if len(size) != 2:
-            raise ValueError("a size is H or (H, W)")
-        return int(size[0]), int(size[1])
-    return int(size), int(size)
 
 
 def _zoom_bounds(zoom_range):
@@ -115,21 +108,9 @@ def _warp(pool, matrices, index, out, shape, dtype, mode, rescale):
     if matrices.device != dev:
         raise RuntimeError("matrices live on %s, the pool on %s" % (matrices.device, dev))
     if index is not None:
-        if not isinstance(index, torch.Tensor) or index.dtype not in (torch.int32, torch.int64):
-            raise TypeError("index must be an int32 or int64 tensor")
-        index = _lib.require_cuda(index, "index", index.dtype)
-        if tuple(index.shape) != (B,):
-            raise ValueError("index must be (B,) = (%d,)" % B)
-        if index.device != dev:
-            raise RuntimeError("index lives on %s, the pool on %s" % (index.device, dev))
+        index = _gather._index(index, B, dev, "the pool")
     shape = (B,) + shape
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device=dev)
-    else:
-        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != dev:
-            raise RuntimeError("out must live on the pool's device")
-        if out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
-            raise ValueError("out must be a contiguous %s tensor of shape %s" % (dtype, shape))
+    out = _gather._out(out, shape, dtype, dev, "the pool's")
     if B == 0:
         return out
     C = int(pool.shape[3]) if pool.dim() == 4 else 1
@@ -138,13 +119,6 @@ def _warp(pool, matrices, index, out, shape, dtype, mode, rescale):
                                         B, shape[-2], shape[-1], mode, float(rescale), ptr(out), stream()),
           "smplr_affine_warp")
     return out
-
-
-def _out_hw(out_hw):
-    H, W = _hw(out_hw)
-    if not (1 <= H <= MAX_OUT and 1 <= W <= MAX_OUT):
-        raise ValueError("out_hw must be 1..%d on a side" % MAX_OUT)
-    return H, W
 
 
 def warp_images(pool, matrices, out_hw, index=None, rescale=1 / 255., interpolation="nearest", out=None):

@@ -5,10 +5,9 @@
 // ImageDataGenerator.random_transform + apply_transform, fill_mode='nearest', flow_from_directory's NEAREST resize to
 // target_size), restated in INTEGRATION.md section 4d, which is the definition.
 //
-// One launch per call.  A workgroup stays inside one sample, so the sample's pool row and its 2 x 3 matrix are
-// wave-uniform (scalar loads); a thread owns VEC consecutive columns of one output row and stores VEC * 4 B per
-// plane, consecutive lanes on consecutive columns.  The uint8 gather is local: neighbouring lanes read neighbouring
-// texels.  No LDS, no atomics, no scratch; every output element is a function of its own sample alone.
+// One launch per call, laid out as sample_gather.h says: the sample's pool row and its 2 x 3 matrix are wave-uniform
+// (scalar loads).  The uint8 gather is local: neighbouring lanes read neighbouring texels.  No LDS, no atomics, no
+// scratch; every output element is a function of its own sample alone.
 //
 // The source coordinate of output pixel (r, c) is
 //     sr = (m00 * r + m01 * c) + m02        sc = (m10 * r + m11 * c) + m12
@@ -18,10 +17,9 @@
 #include "common.h"
 
 #pragma clang fp contract(off)
+#include "sample_gather.h"
 
 namespace smplr {
-
-constexpr int AW_T = 256;   // threads per workgroup
 
 // x clamped to [0, hi]; NaN -> 0, +-inf -> the ends
 __device__ __forceinline__ float aw_clamp(float x, float hi) {
@@ -33,21 +31,14 @@ __device__ __forceinline__ int aw_src(int i, int n, int S) { return (n == S) ? i
 
 // KIND 0: image, nearest; 1: image, bilinear (pool size == output size); 2: label map (C = 1, int32 out)
 template <int C, int KIND, int VEC>
-__global__ __launch_bounds__(AW_T, 8) void affine_warp_kernel(const unsigned char *__restrict__ pool, int N, int Hs, int Ws,
+__global__ __launch_bounds__(SG_T, 8) void affine_warp_kernel(const unsigned char *__restrict__ pool, int N, int Hs, int Ws,
                                                            const float *__restrict__ mat,
                                                            const void *__restrict__ index, int index_i64, int H, int W,
                                                            int blocks_per_sample, float rescale, int binarize,
                                                            void *__restrict__ out) {
-  const int b = blockIdx.x / blocks_per_sample;                       // wave-uniform
-  const int gpr = W / VEC;                                            // thread groups per output row
-  const int g = (blockIdx.x - b * blocks_per_sample) * AW_T + threadIdx.x;
-  if (g >= H * gpr) return;
-  const int r = g / gpr, c0 = (g - r * gpr) * VEC;
-
-  long long n = b;
-  if (index) n = index_i64 ? ((const long long *)index)[b] : (long long)((const int *)index)[b];
-  n = n < 0 ? 0 : (n > (long long)N - 1 ? (long long)N - 1 : n);      // an index outside the pool is clamped
-  const unsigned char *src = pool + (size_t)n * Hs * Ws * C;
+  int b, r, c0;
+  if (!gather_pos<VEC>(H, W, blocks_per_sample, b, r, c0)) return;
+  const unsigned char *src = pool + (size_t)gather_row(index, index_i64, b, N) * Hs * Ws * C;
   const float *m = mat + (size_t)b * 6;
   const float m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5];
   const float hmax = (float)(H - 1), wmax = (float)(W - 1);
@@ -81,56 +72,7 @@ __global__ __launch_bounds__(AW_T, 8) void affine_warp_kernel(const unsigned cha
     }
   }
 
-  const size_t plane = (size_t)H * W;
-  const size_t o = (size_t)r * W + c0;
-  if (KIND == 2) {
-    int *dst = (int *)out + (size_t)b * plane + o;
-    int q[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      const int lab = (int)v[0][k];
-      q[k] = binarize ? (lab > 0 ? 1 : 0) : lab;
-    }
-    if (VEC == 4) {
-      *reinterpret_cast<int4 *>(dst) = make_int4(q[0], q[1], q[2], q[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) dst[k] = q[k];
-    }
-  } else {
-#pragma unroll
-    for (int ch = 0; ch < C; ++ch) {
-      float *dst = (float *)out + ((size_t)b * C + ch) * plane + o;
-      float q[VEC];
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) q[k] = (KIND == 1) ? v[ch][k] : v[ch][k] * rescale;
-      if (VEC == 4) {
-        *reinterpret_cast<float4 *>(dst) = make_float4(q[0], q[1], q[2], q[3]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) dst[k] = q[k];
-      }
-    }
-  }
-}
-
-template <int C, int KIND>
-static int launch_affine_warp(const uint8_t *pool, int N, int Hs, int Ws, const float *mat, const void *index,
-                              int index_i64, int B, int H, int W, float rescale, int binarize, void *out, hipStream_t st) {
-  // 16 B per plane and thread where the rows allow it (every row start is then 16-B aligned as well)
-  const bool vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0);
-  const long long groups = (long long)H * (W / (vec4 ? 4 : 1));
-  const long long bps = (groups + AW_T - 1) / AW_T;
-  SMPLR_REQUIRE(bps * B < (1ll << 31), "smplr_affine_warp: %d samples x %lld workgroups exceed the grid", B, bps);
-  const dim3 grid((unsigned)(bps * B)), block(AW_T);
-  if (vec4)
-    hipLaunchKernelGGL((affine_warp_kernel<C, KIND, 4>), grid, block, 0, st, pool, N, Hs, Ws, mat, index, index_i64, H, W,
-                       (int)bps, rescale, binarize, out);
-  else
-    hipLaunchKernelGGL((affine_warp_kernel<C, KIND, 1>), grid, block, 0, st, pool, N, Hs, Ws, mat, index, index_i64, H, W,
-                       (int)bps, rescale, binarize, out);
-  SMPLR_LAUNCH_CHECK("smplr_affine_warp");
-  return 0;
+  gather_store<C, VEC, KIND == 2, KIND == 0>(v, b, r, c0, H, W, rescale, binarize, out);   // (bilinear has rescaled)
 }
 
 }  // namespace smplr
@@ -138,26 +80,17 @@ static int launch_affine_warp(const uint8_t *pool, int N, int Hs, int Ws, const 
 int smplr_affine_warp(const uint8_t *pool, int N, int Hs, int Ws, int C, const float *mat, const void *index,
                       int index_i64, int B, int H, int W, int mode, float rescale, void *out, void *stream) {
   using namespace smplr;
-  SMPLR_REQUIRE(mode >= SMPLR_WARP_IMAGE_NEAREST && mode <= SMPLR_WARP_LABEL_BINARY,
-                "smplr_affine_warp: mode %d is none of image nearest (0), image bilinear (1), label (2), binary label (3)",
-                mode);
-  SMPLR_REQUIRE(B >= 0 && N >= 1, "smplr_affine_warp: bad sizes B=%d N=%d (B >= 0, N >= 1)", B, N);
-  SMPLR_REQUIRE(H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "smplr_affine_warp: output %d x %d outside 1..4096", H, W);
+  if (const int e = gather_check("smplr_affine_warp", "image nearest (0), image bilinear (1)", mode, C, B, N, H, W)) return e;
   SMPLR_REQUIRE(Hs >= 1 && Hs <= 8192 && Ws >= 1 && Ws <= 8192, "smplr_affine_warp: pool planes %d x %d outside 1..8192",
                 Hs, Ws);
-  const bool label = mode >= SMPLR_WARP_LABEL;
-  SMPLR_REQUIRE(label ? C == 1 : (C == 1 || C == 3), "smplr_affine_warp: C=%d channels (images 1 or 3, labels 1)", C);
   SMPLR_REQUIRE(mode != SMPLR_WARP_IMAGE_BILINEAR || (Hs == H && Ws == W),
                 "smplr_affine_warp: bilinear needs pool size = output size (pool %d x %d, output %d x %d)", Hs, Ws, H, W);
   if (B == 0) return 0;
   SMPLR_REQUIRE(pool && mat && out, "smplr_affine_warp: null pointer (pool, mat, out)");
-  hipStream_t st = as_stream(stream);
-  const int i64 = index_i64 ? 1 : 0;
-  if (label)
-    return launch_affine_warp<1, 2>(pool, N, Hs, Ws, mat, index, i64, B, H, W, 1.f, mode == SMPLR_WARP_LABEL_BINARY, out, st);
-  if (mode == SMPLR_WARP_IMAGE_NEAREST)
-    return C == 3 ? launch_affine_warp<3, 0>(pool, N, Hs, Ws, mat, index, i64, B, H, W, rescale, 0, out, st)
-                  : launch_affine_warp<1, 0>(pool, N, Hs, Ws, mat, index, i64, B, H, W, rescale, 0, out, st);
-  return C == 3 ? launch_affine_warp<3, 1>(pool, N, Hs, Ws, mat, index, i64, B, H, W, rescale, 0, out, st)
-                : launch_affine_warp<1, 1>(pool, N, Hs, Ws, mat, index, i64, B, H, W, rescale, 0, out, st);
+  const int i64 = index_i64 ? 1 : 0, binarize = mode == SMPLR_WARP_LABEL_BINARY;
+  if (mode >= SMPLR_WARP_LABEL) rescale = 1.f;
+  return gather_dispatch("smplr_affine_warp", mode, C, B, H, W, out, [&](auto c, auto kind, auto vec, dim3 grid, int bps) {
+    hipLaunchKernelGGL((affine_warp_kernel<decltype(c)::value, decltype(kind)::value, decltype(vec)::value>), grid,
+                       dim3(SG_T), 0, as_stream(stream), pool, N, Hs, Ws, mat, index, i64, H, W, bps, rescale, binarize, out);
+  });
 }

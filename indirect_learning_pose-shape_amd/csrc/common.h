@@ -235,6 +235,14 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// neither NaN nor an infinity
+__device__ __forceinline__ bool finitef(float x) { return x - x == 0.f; }
 
 // The order of torch.argmax / np.argmax on (score, channel): NaN above every number (the first NaN wins), equal scores
 // (+0 and -0 included) go to the lower channel.  A strict total order on pairs with distinct channels, so a reduction

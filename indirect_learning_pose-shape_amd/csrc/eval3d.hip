@@ -31,12 +31,6 @@ constexpr int PE_WAVE_T = 256;   // the wave-per-mesh form: four meshes per work
 // orders below any second direction that means something (a 1 m set whose thickness is 1 cm has S2 / S1 of 1e-2).
 constexpr double PE_RANK_TOL = 1e-5;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 struct V3d { double x, y, z; };
 __device__ __forceinline__ double dot3(const V3d &a, const V3d &b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 __device__ __forceinline__ V3d cross3(const V3d &a, const V3d &b) {

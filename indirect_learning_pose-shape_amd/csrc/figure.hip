@@ -11,7 +11,7 @@
 //                         written, pixel [i, j] from source column (j w) / W: nearest sampling in exact integers.
 //                         With a background, class 0 lets it through and every other class is blended over it,
 //                         (alpha_q colour + (256 - alpha_q) background + 128) >> 8.
-//  scatter_points_kernel  one workgroup per (mesh, 64 x 64 tile), the shape of render.hip's mesh_raster_kernel.  Phase 1:
+//  scatter_points_kernel  one workgroup per (mesh, 64 x 64 tile) on key_tile.h, as render.hip's mesh_raster_kernel.  Phase 1:
 //                         thread t takes the vertices = t (mod 256), rounds the centre (cx, cy) = (rint(s u),
 //                         H - 1 - rint(s v)), rejects the disc by its bounding box against the tile and atomicMax-es a
 //                         64-bit key into the 64 x 64 LDS buffer (32 KB, ds_max_u64) at every covered sample,
@@ -26,23 +26,17 @@
 #include "common.h"
 
 #pragma clang fp contract(off)
+#include "key_tile.h"
 
 namespace smplr {
 
 constexpr int FG_T = 256;          // threads per workgroup, both kernels
-constexpr int FG_TILE = 64;        // scatter tile side: 64 x 64 uint64 keys = 32 KB of LDS
 constexpr int FG_MAX_R = 16;       // largest disc radius
 constexpr int FG_MAX_SIDE = 4096;  // largest source / output side
 constexpr float FG_CLAMP = 1048576.f;   // |s u| is clamped to 2^20 before the conversion: cx +- r cannot overflow
 
-__device__ __forceinline__ bool fg_finite(float x) { return x - x == 0.f; }
 __device__ __forceinline__ unsigned fg_blend(unsigned a, unsigned fg, unsigned bg) {
   return (a * fg + (256u - a) * bg + 128u) >> 8;
-}
-// float -> uint32 with the order of the floats (the caller passes z + 0: -0 and +0 tie)
-__device__ __forceinline__ unsigned fg_ordered_bits(float x) {
-  const unsigned u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
 // colours travel as r | g << 8 | b << 16; bit 24 of an LDS entry of seg_colour_kernel: the class is not 0
@@ -119,36 +113,33 @@ __global__ __launch_bounds__(FG_T) void scatter_points_kernel(const float *__res
                                                               unsigned canvas, int V, float scale, int radius, int order,
                                                               int H, int W, int tiles_x, int ntiles,
                                                               int *__restrict__ vertex, unsigned char *__restrict__ rgb) {
-  __shared__ unsigned long long zb[FG_TILE * FG_TILE];
-  const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
-  const int tx0 = (tile % tiles_x) * FG_TILE, ty0 = (tile / tiles_x) * FG_TILE;
-  const int tx1 = min(tx0 + FG_TILE, W) - 1, ty1 = min(ty0 + FG_TILE, H) - 1;
-  for (int i = threadIdx.x; i < FG_TILE * FG_TILE; i += FG_T) zb[i] = 0ull;
-  __syncthreads();
-  const float *pb = proj + (long long)b * V * 3;
-  const unsigned char *kb = keep ? keep + (long long)b * V : nullptr;
+  __shared__ unsigned long long zb[KT_TILE * KT_TILE];
+  const KeyTile t = key_tile(tiles_x, ntiles, H, W);
+  key_tile_fill<FG_T>(zb, 0ull);
+  const float *pb = proj + (long long)t.b * V * 3;
+  const unsigned char *kb = keep ? keep + (long long)t.b * V : nullptr;
   const int r2 = radius * radius;
 
   for (int v = threadIdx.x; v < V; v += FG_T) {
     if (kb && kb[v] == 0) continue;
     const float pu = pb[3 * v], pv = pb[3 * v + 1];
-    if (!(fg_finite(pu) && fg_finite(pv))) continue;
+    if (!(finitef(pu) && finitef(pv))) continue;
     unsigned long long key;
     if (order == 0) {
       key = (unsigned long long)(unsigned)v + 1ull;
     } else {
       const float z = pb[3 * v + 2];
-      if (!fg_finite(z)) continue;
-      key = ((unsigned long long)fg_ordered_bits(z + 0.0f) << 32) | (unsigned long long)(0xffffffffu - (unsigned)v);
+      if (!finitef(z)) continue;
+      key = ((unsigned long long)ordered_bits(z + 0.0f) << 32) | (unsigned long long)(0xffffffffu - (unsigned)v);
     }
     const float su = fminf(fmaxf(scale * pu, -FG_CLAMP), FG_CLAMP), sv = fminf(fmaxf(scale * pv, -FG_CLAMP), FG_CLAMP);
     const int cx = (int)rintf(su), cy = (H - 1) - (int)rintf(sv);
-    const int j0 = max(cx - radius, tx0), j1 = min(cx + radius, tx1);
-    const int r0 = max(cy - radius, ty0), r1 = min(cy + radius, ty1);
+    const int j0 = max(cx - radius, t.tx0), j1 = min(cx + radius, t.tx1);
+    const int r0 = max(cy - radius, t.ty0), r1 = min(cy + radius, t.ty1);
     if (j0 > j1 || r0 > r1) continue;
     for (int r = r0; r <= r1; ++r) {
       const int dy = r - cy, rem = r2 - dy * dy;
-      unsigned long long *row = zb + (r - ty0) * FG_TILE - tx0;            // row[j], tx0 <= j <= tx1: inside the tile
+      unsigned long long *row = key_tile_row(zb, t, r);
       for (int j = j0; j <= j1; ++j) {
         const int dx = j - cx;
         if (dx * dx <= rem) atomicMax(row + j, key);
@@ -158,18 +149,14 @@ __global__ __launch_bounds__(FG_T) void scatter_points_kernel(const float *__res
   __syncthreads();
 
   const unsigned cr = canvas & 255u, cg = (canvas >> 8) & 255u, cb = (canvas >> 16) & 255u;
-  for (int k = threadIdx.x; k < FG_TILE * FG_TILE; k += FG_T) {
-    const int r = ty0 + k / FG_TILE, j = tx0 + k % FG_TILE;
-    if (r > ty1 || j > tx1) continue;
-    const long long o = ((long long)b * H + r) * W + j;
-    const unsigned long long key = zb[k];
+  key_tile_visit<FG_T>(zb, t, H, W, [&](int, int, long long o, unsigned long long key) {
     int v = -1;
     if (key != 0ull) {
       v = order == 0 ? (int)(unsigned)(key - 1ull) : (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
       if ((unsigned)v >= (unsigned)V) v = -1;                              // (cannot happen: the keys are built from v < V)
     }
     if (vertex) vertex[o] = v;
-    if (!rgb) continue;
+    if (!rgb) return;
     unsigned cr_ = cr, cg_ = cg, cb_ = cb;
     if (v >= 0) {
       if (colours) {
@@ -191,7 +178,7 @@ __global__ __launch_bounds__(FG_T) void scatter_points_kernel(const float *__res
     q[0] = (unsigned char)cr_;
     q[1] = (unsigned char)cg_;
     q[2] = (unsigned char)cb_;
-  }
+  });
 }
 
 }  // namespace smplr
@@ -226,8 +213,8 @@ int smplr_scatter_points(const float *proj, const uint8_t *keep, const uint8_t *
                          int32_t *vertex, uint8_t *rgb, void *stream) {
   using namespace smplr;
   SMPLR_REQUIRE(B >= 0 && V >= 1 && V <= (1 << 24), "smplr_scatter_points: bad sizes B=%d V=%d (B >= 0, 1 <= V <= 2^24)", B, V);
-  SMPLR_REQUIRE(H >= 1 && H <= FG_MAX_SIDE && W >= 1 && W <= FG_MAX_SIDE, "smplr_scatter_points: image %d x %d outside 1..4096",
-                H, W);
+  int tx, ntiles;
+  if (const int e = key_tile_grid("smplr_scatter_points", B, H, W, &tx, &ntiles)) return e;
   SMPLR_REQUIRE(radius >= 0 && radius <= FG_MAX_R, "smplr_scatter_points: radius %d outside 0..%d", radius, FG_MAX_R);
   SMPLR_REQUIRE(order == SMPLR_SCATTER_INDEX || order == SMPLR_SCATTER_DEPTH,
                 "smplr_scatter_points: order %d is neither index (0) nor depth (1)", order);
@@ -235,13 +222,11 @@ int smplr_scatter_points(const float *proj, const uint8_t *keep, const uint8_t *
   SMPLR_REQUIRE(alpha_q >= 0 && alpha_q <= 256, "smplr_scatter_points: alpha_q %d outside [0, 256]", alpha_q);
   SMPLR_REQUIRE(colour >= 0 && colour <= 0xffffff && canvas >= 0 && canvas <= 0xffffff,
                 "smplr_scatter_points: colour %d / canvas %d is not r | g << 8 | b << 16", colour, canvas);
-  const int tx = (W + FG_TILE - 1) / FG_TILE, ty = (H + FG_TILE - 1) / FG_TILE;
-  SMPLR_REQUIRE((long long)B * tx * ty < (1ll << 31), "smplr_scatter_points: %d meshes x %d tiles exceed the grid", B, tx * ty);
   if (B == 0) return 0;
   SMPLR_REQUIRE(proj, "smplr_scatter_points: null pointer (proj)");
   if (!vertex && !rgb) return 0;
-  hipLaunchKernelGGL(scatter_points_kernel, dim3((unsigned)(B * tx * ty)), dim3(FG_T), 0, as_stream(stream), proj, keep, colours,
-                     (unsigned)colour, image, (unsigned)alpha_q, (unsigned)canvas, V, scale, radius, order, H, W, tx, tx * ty,
+  hipLaunchKernelGGL(scatter_points_kernel, dim3((unsigned)(B * ntiles)), dim3(FG_T), 0, as_stream(stream), proj, keep, colours,
+                     (unsigned)colour, image, (unsigned)alpha_q, (unsigned)canvas, V, scale, radius, order, H, W, tx, ntiles,
                      vertex, rgb);
   SMPLR_LAUNCH_CHECK("smplr_scatter_points");
   return 0;

@@ -32,14 +32,6 @@ namespace smplr {
 constexpr int FT_T = 256;      // threads per workgroup = the widest row
 constexpr int FT_NW = FT_T / WAVE;
 
-__device__ __forceinline__ bool ft_finite(float x) { return x - x == 0.f; }
-
-__device__ __forceinline__ double ft_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ __forceinline__ float ft_strided_sum(const float *__restrict__ p, int n) {
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += FT_T) s += p[i];
@@ -64,15 +56,15 @@ __global__ __launch_bounds__(FT_T) void fit_step_kernel(
   const float best0 = best_loss[b];
 
   // 1. the row's loss
-  const double ws = ft_wave_sum((double)ft_strided_sum(loss + (long long)b * N, N));
-  const double wq = silh_loss ? ft_wave_sum((double)ft_strided_sum(silh_loss + (long long)b * Ns, Ns)) : 0.0;
+  const double ws = wave_sum_f64((double)ft_strided_sum(loss + (long long)b * N, N));
+  const double wq = silh_loss ? wave_sum_f64((double)ft_strided_sum(silh_loss + (long long)b * Ns, Ns)) : 0.0;
   if (lane == 0) {
     swave[0][wave] = ws;
     swave[1][wave] = wq;
   }
   const bool col = j < P;
   const float gj = col ? g[row + j] : 0.f;
-  const int g_bad = __syncthreads_or(!ft_finite(gj));                     // (the barrier that publishes swave)
+  const int g_bad = __syncthreads_or(!finitef(gj));                       // (the barrier that publishes swave)
   double Ld = ((swave[0][0] + swave[0][1]) + (swave[0][2] + swave[0][3])) / (double)N;
   if (silh_loss) Ld += (double)silh_weight * (((swave[1][0] + swave[1][1]) + (swave[1][2] + swave[1][3])) / (double)Ns);
   const float L = (float)Ld;
@@ -83,7 +75,7 @@ __global__ __launch_bounds__(FT_T) void fit_step_kernel(
     calls[b] = calls0 + 1;
   }
   // 3. a bad call
-  if (g_bad || !ft_finite(L)) {
+  if (g_bad || !finitef(L)) {
     if (j == 0) bad[b] += 1;
     return;
   }

@@ -6,10 +6,9 @@
 // ground-truth resize (evaluate.py:96-100) and the webcam crop (predict_realtime.py:52-58), restated in INTEGRATION.md
 // section 4e, which is the definition; tests/_preprocess_oracle.py is its NumPy form.
 //
-// One launch per call.  A workgroup stays inside one sample, so the sample's descriptor row (byte offset, pitch, h, w)
-// is wave-uniform; a thread owns VEC consecutive columns of one output row and stores VEC * 4 B per plane, consecutive
-// lanes on consecutive columns.  The uint8 gather is local: neighbouring lanes read neighbouring texels of at most two
-// source rows.  No LDS, no atomics, no scratch; every output element is a function of its own sample alone.
+// One launch per call, laid out as sample_gather.h says: the sample's descriptor row (byte offset, pitch, h, w) is
+// wave-uniform.  The uint8 gather is local: neighbouring lanes read neighbouring texels of at most two source rows.
+// No LDS, no atomics, no scratch; every output element is a function of its own sample alone.
 //
 // Everything up to the last step is integer arithmetic: the bilinear sample is the exact rational num / D with
 // D = 2W * 2H <= 2^26 and num < 2^34 (two 32 x 32 -> 64-bit multiply-adds).  The quantised form
@@ -20,10 +19,9 @@
 #include "common.h"
 
 #pragma clang fp contract(off)
+#include "sample_gather.h"
 
 namespace smplr {
-
-constexpr int RP_T = 256;   // threads per workgroup
 
 struct RpAxis { int s0, s1; unsigned r; };   // the two source indices on the padded axis and the weight numerator of s1
 
@@ -47,21 +45,14 @@ __device__ __forceinline__ int rp_nearest(int i, int n, int S, int pil) {
 
 // KIND 0: image, bilinear; 1: image, nearest; 2: label map (C = 1, int32 out)
 template <int C, int KIND, int VEC>
-__global__ __launch_bounds__(RP_T, 8) void resize_pad_kernel(const unsigned char *__restrict__ data, long long data_bytes,
+__global__ __launch_bounds__(SG_T, 8) void resize_pad_kernel(const unsigned char *__restrict__ data, long long data_bytes,
                                                           const long long *__restrict__ desc, int N,
                                                           const void *__restrict__ index, int index_i64, int H, int W,
                                                           int blocks_per_sample, int flags, float rescale, int binarize,
                                                           void *__restrict__ out) {
-  const int b = blockIdx.x / blocks_per_sample;                       // wave-uniform
-  const int gpr = W / VEC;                                            // thread groups per output row
-  const int g = (blockIdx.x - b * blocks_per_sample) * RP_T + threadIdx.x;
-  if (g >= H * gpr) return;
-  const int r = g / gpr, c0 = (g - r * gpr) * VEC;
-
-  long long n = b;
-  if (index) n = index_i64 ? ((const long long *)index)[b] : (long long)((const int *)index)[b];
-  n = n < 0 ? 0 : (n > (long long)N - 1 ? (long long)N - 1 : n);      // an index outside the table is clamped
-  const long long *d = desc + n * 4;
+  int b, r, c0;
+  if (!gather_pos<VEC>(H, W, blocks_per_sample, b, r, c0)) return;
+  const long long *d = desc + gather_row(index, index_i64, b, N) * 4;
   const long long off = d[0], pitch = d[1], hl = d[2], wl = d[3];
   // nothing is read through a row that does not lie inside data (the host bounds data_bytes by 2^48, so with
   // pitch <= data_bytes the product below cannot overflow)
@@ -142,57 +133,7 @@ __global__ __launch_bounds__(RP_T, 8) void resize_pad_kernel(const unsigned char
     }
   }
 
-  const size_t plane = (size_t)H * W;
-  const size_t o = (size_t)r * W + c0;
-  if (KIND == 2) {
-    int *dst = (int *)out + (size_t)b * plane + o;
-    int q[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      const int lab = (int)v[0][k];
-      q[k] = binarize ? (lab > 0 ? 1 : 0) : lab;
-    }
-    if (VEC == 4) {
-      *reinterpret_cast<int4 *>(dst) = make_int4(q[0], q[1], q[2], q[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) dst[k] = q[k];
-    }
-  } else {
-#pragma unroll
-    for (int ch = 0; ch < C; ++ch) {
-      float *dst = (float *)out + ((size_t)b * C + ch) * plane + o;
-      float q[VEC];
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) q[k] = (KIND == 0) ? v[ch][k] : v[ch][k] * rescale;
-      if (VEC == 4) {
-        *reinterpret_cast<float4 *>(dst) = make_float4(q[0], q[1], q[2], q[3]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) dst[k] = q[k];
-      }
-    }
-  }
-}
-
-template <int C, int KIND>
-static int launch_resize_pad(const uint8_t *data, long long data_bytes, const long long *desc, int N, const void *index,
-                             int index_i64, int B, int H, int W, int flags, float rescale, int binarize, void *out,
-                             hipStream_t st) {
-  // 16 B per plane and thread where the rows allow it (every row start is then 16-B aligned as well)
-  const bool vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0);
-  const long long groups = (long long)H * (W / (vec4 ? 4 : 1));
-  const long long bps = (groups + RP_T - 1) / RP_T;
-  SMPLR_REQUIRE(bps * B < (1ll << 31), "smplr_resize_pad: %d samples x %lld workgroups exceed the grid", B, bps);
-  const dim3 grid((unsigned)(bps * B)), block(RP_T);
-  if (vec4)
-    hipLaunchKernelGGL((resize_pad_kernel<C, KIND, 4>), grid, block, 0, st, data, data_bytes, desc, N, index, index_i64, H,
-                       W, (int)bps, flags, rescale, binarize, out);
-  else
-    hipLaunchKernelGGL((resize_pad_kernel<C, KIND, 1>), grid, block, 0, st, data, data_bytes, desc, N, index, index_i64, H,
-                       W, (int)bps, flags, rescale, binarize, out);
-  SMPLR_LAUNCH_CHECK("smplr_resize_pad");
-  return 0;
+  gather_store<C, VEC, KIND == 2, KIND == 1>(v, b, r, c0, H, W, rescale, binarize, out);   // (bilinear has rescaled)
 }
 
 }  // namespace smplr
@@ -200,26 +141,17 @@ static int launch_resize_pad(const uint8_t *data, long long data_bytes, const lo
 int smplr_resize_pad(const uint8_t *data, long long data_bytes, const long long *desc, int N, int C, const void *index,
                      int index_i64, int B, int H, int W, int mode, int flags, float rescale, void *out, void *stream) {
   using namespace smplr;
-  SMPLR_REQUIRE(mode >= SMPLR_RESIZE_IMAGE_BILINEAR && mode <= SMPLR_RESIZE_LABEL_BINARY,
-                "smplr_resize_pad: mode %d is none of image bilinear (0), image nearest (1), label (2), binary label (3)",
-                mode);
+  if (const int e = gather_check("smplr_resize_pad", "image bilinear (0), image nearest (1)", mode, C, B, N, H, W)) return e;
   SMPLR_REQUIRE((flags & ~(SMPLR_RESIZE_PAD | SMPLR_RESIZE_SWAP_RB | SMPLR_RESIZE_QUANTIZE | SMPLR_RESIZE_PIL)) == 0,
                 "smplr_resize_pad: flags 0x%x hold bits other than pad (1), swap_rb (2), quantize (4), pil rule (8)", flags);
-  SMPLR_REQUIRE(B >= 0 && N >= 1, "smplr_resize_pad: bad sizes B=%d N=%d (B >= 0, N >= 1)", B, N);
-  SMPLR_REQUIRE(H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "smplr_resize_pad: output %d x %d outside 1..4096", H, W);
   SMPLR_REQUIRE(data_bytes >= 1 && data_bytes <= (1ll << 48), "smplr_resize_pad: data_bytes %lld outside 1..2^48", data_bytes);
-  const bool label = mode >= SMPLR_RESIZE_LABEL;
-  SMPLR_REQUIRE(label ? C == 1 : (C == 1 || C == 3), "smplr_resize_pad: C=%d channels (images 1 or 3, labels 1)", C);
   if (B == 0) return 0;
   SMPLR_REQUIRE(data && desc && out, "smplr_resize_pad: null pointer (data, desc, out)");
-  hipStream_t st = as_stream(stream);
-  const int i64 = index_i64 ? 1 : 0;
-  if (label)
-    return launch_resize_pad<1, 2>(data, data_bytes, desc, N, index, i64, B, H, W, flags, 1.f, mode == SMPLR_RESIZE_LABEL_BINARY,
-                                   out, st);
-  if (mode == SMPLR_RESIZE_IMAGE_NEAREST)
-    return C == 3 ? launch_resize_pad<3, 1>(data, data_bytes, desc, N, index, i64, B, H, W, flags, rescale, 0, out, st)
-                  : launch_resize_pad<1, 1>(data, data_bytes, desc, N, index, i64, B, H, W, flags, rescale, 0, out, st);
-  return C == 3 ? launch_resize_pad<3, 0>(data, data_bytes, desc, N, index, i64, B, H, W, flags, rescale, 0, out, st)
-                : launch_resize_pad<1, 0>(data, data_bytes, desc, N, index, i64, B, H, W, flags, rescale, 0, out, st);
+  const int i64 = index_i64 ? 1 : 0, binarize = mode == SMPLR_RESIZE_LABEL_BINARY;
+  if (mode >= SMPLR_RESIZE_LABEL) rescale = 1.f;
+  return gather_dispatch("smplr_resize_pad", mode, C, B, H, W, out, [&](auto c, auto kind, auto vec, dim3 grid, int bps) {
+    hipLaunchKernelGGL((resize_pad_kernel<decltype(c)::value, decltype(kind)::value, decltype(vec)::value>), grid,
+                       dim3(SG_T), 0, as_stream(stream), data, data_bytes, desc, N, index, i64, H, W, bps, flags, rescale,
+                       binarize, out);
+  });
 }

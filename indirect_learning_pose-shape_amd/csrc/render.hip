@@ -24,11 +24,11 @@
 #include "common.h"
 
 #pragma clang fp contract(off)
+#include "key_tile.h"
 
 namespace smplr {
 
 constexpr int MR_T = 256;        // threads per workgroup, both kernels
-constexpr int MR_TILE = 64;      // raster tile side: 64 x 64 uint64 keys = 32 KB of LDS
 constexpr int MR_MAX_LIGHTS = 8;
 constexpr float MR_GUARD = 32768.f;   // |x|, |y| <= 2^15 px: fixed-point coordinates <= 2^23, edge products < 2^49
 
@@ -42,7 +42,6 @@ struct MeshParams {
   float lcol[MR_MAX_LIGHTS][3];
 };
 
-__device__ __forceinline__ bool finitef(float x) { return x - x == 0.f; }
 __device__ __forceinline__ float clip01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
 
 // E(a, b, s) = (b - a) x (s - a): positive on the left of a -> b, exact in int64
@@ -52,15 +51,6 @@ __device__ __forceinline__ long long edge_fn(int ax, int ay, int bx, int by, int
 // top-left rule: a sample on an edge belongs to the face iff the edge direction (dx, dy) lies in this half-open half
 // plane; the face on the other side runs the edge the other way and does not own it
 __device__ __forceinline__ long long edge_bias(int dx, int dy) { return (dy > 0 || (dy == 0 && dx < 0)) ? 0 : 1; }
-
-// float -> uint32 with the order of the floats (-0 < +0 is avoided by the caller: it passes 0 - d)
-__device__ __forceinline__ unsigned ordered_bits(float x) {
-  const unsigned u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float unordered_bits(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 __global__ __launch_bounds__(MR_T) void mesh_vertex_kernel(const float *__restrict__ verts, const float *__restrict__ cam,
                                                            const float *__restrict__ trans, int B, int V, MeshParams p,
@@ -164,13 +154,10 @@ __global__ __launch_bounds__(MR_T) void mesh_raster_kernel(const int4 *__restric
                                                            unsigned char *__restrict__ part_out,
                                                            unsigned char *__restrict__ alpha_out,
                                                            float *__restrict__ rgb_out) {
-  __shared__ unsigned long long zb[MR_TILE * MR_TILE];
-  const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
-  const int tx0 = (tile % tiles_x) * MR_TILE, ty0 = (tile / tiles_x) * MR_TILE;
-  const int tx1 = min(tx0 + MR_TILE, W) - 1, ty1 = min(ty0 + MR_TILE, H) - 1;
-  for (int i = threadIdx.x; i < MR_TILE * MR_TILE; i += MR_T) zb[i] = ~0ull;
-  __syncthreads();
-  const int4 *g = geom + (long long)b * V;
+  __shared__ unsigned long long zb[KT_TILE * KT_TILE];
+  const KeyTile t = key_tile(tiles_x, ntiles, H, W);
+  key_tile_fill<MR_T>(zb, ~0ull);
+  const int4 *g = geom + (long long)t.b * V;
 
   for (int f = threadIdx.x; f < F; f += MR_T) {
     const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
@@ -180,15 +167,15 @@ __global__ __launch_bounds__(MR_T) void mesh_raster_kernel(const int4 *__restric
     if (!(a.w & c1.w & c2.w)) continue;
     const int minx = min(a.x, min(c1.x, c2.x)), maxx = max(a.x, max(c1.x, c2.x));
     const int miny = min(a.y, min(c1.y, c2.y)), maxy = max(a.y, max(c1.y, c2.y));
-    const int j0 = max((minx + 255) >> 8, tx0), j1 = min(maxx >> 8, tx1);
-    const int r0 = max((miny + 255) >> 8, ty0), r1 = min(maxy >> 8, ty1);
+    const int j0 = max((minx + 255) >> 8, t.tx0), j1 = min(maxx >> 8, t.tx1);
+    const int r0 = max((miny + 255) >> 8, t.ty0), r1 = min(maxy >> 8, t.ty1);
     if (j0 > j1 || r0 > r1) continue;
     long long A = edge_fn(a.x, a.y, c1.x, c1.y, c2.x, c2.y);
     if (A == 0) continue;
     if (A < 0) {
-      const int4 t = c1;
+      const int4 c = c1;
       c1 = c2;
-      c2 = t;
+      c2 = c;
       A = -A;
     }
     const float fA = (float)A;
@@ -202,7 +189,7 @@ __global__ __launch_bounds__(MR_T) void mesh_raster_kernel(const int4 *__restric
       long long e0 = edge_fn(c1.x, c1.y, c2.x, c2.y, j0 * 256, r * 256);
       long long e1 = edge_fn(c2.x, c2.y, a.x, a.y, j0 * 256, r * 256);
       long long e2 = edge_fn(a.x, a.y, c1.x, c1.y, j0 * 256, r * 256);
-      unsigned long long *row = zb + (r - ty0) * MR_TILE - tx0;
+      unsigned long long *row = key_tile_row(zb, t, r);
       for (int j = j0; j <= j1; ++j) {
         if (e0 >= b0 && e1 >= b1 && e2 >= b2) {
           const float d = (((float)e0 * q0 + (float)e1 * q1) + (float)e2 * q2) / fA;
@@ -219,12 +206,8 @@ __global__ __launch_bounds__(MR_T) void mesh_raster_kernel(const int4 *__restric
   }
   __syncthreads();
 
-  const float4 *cb = col + (long long)b * V;
-  for (int k = threadIdx.x; k < MR_TILE * MR_TILE; k += MR_T) {
-    const int r = ty0 + k / MR_TILE, j = tx0 + k % MR_TILE;
-    if (r > ty1 || j > tx1) continue;
-    const long long o = ((long long)b * H + r) * W + j;
-    const unsigned long long key = zb[k];
+  const float4 *cb = col + (long long)t.b * V;
+  key_tile_visit<MR_T>(zb, t, H, W, [&](int r, int j, long long o, unsigned long long key) {
     if (key == ~0ull) {
       if (face_out) face_out[o] = -1;
       if (depth_out) depth_out[o] = 0.f;
@@ -235,7 +218,7 @@ __global__ __launch_bounds__(MR_T) void mesh_raster_kernel(const int4 *__restric
         rgb_out[3 * o + 1] = bg ? bg[3 * o + 1] : 1.f;
         rgb_out[3 * o + 2] = bg ? bg[3 * o + 2] : 1.f;
       }
-      continue;
+      return;
     }
     const int f = (int)(unsigned)(key & 0xffffffffu);
     const float d = 0.f - unordered_bits((unsigned)(key >> 32));
@@ -248,9 +231,9 @@ __global__ __launch_bounds__(MR_T) void mesh_raster_kernel(const int4 *__restric
       const int4 a = g[i0];
       int4 c1 = g[i1], c2 = g[i2];
       if (edge_fn(a.x, a.y, c1.x, c1.y, c2.x, c2.y) < 0) {
-        const int4 t = c1;
+        const int4 c = c1;
         c1 = c2;
-        c2 = t;
+        c2 = c;
         const int ti = i1;
         i1 = i2;
         i2 = ti;
@@ -269,7 +252,7 @@ __global__ __launch_bounds__(MR_T) void mesh_raster_kernel(const int4 *__restric
       rgb_out[3 * o + 1] = clip01(((w0 * k0.y + w1 * k1.y) + w2 * k2.y) / ws);
       rgb_out[3 * o + 2] = clip01(((w0 * k0.z + w1 * k1.z) + w2 * k2.z) / ws);
     }
-  }
+  });
 }
 
 }  // namespace smplr
@@ -329,9 +312,10 @@ int smplr_mesh_raster(const void *vbuf, const int32_t *faces, const uint8_t *fac
                       int W, int mode, const float *bg, int32_t *face, float *depth, uint8_t *part, uint8_t *alpha,
                       float *rgb, void *stream) {
   using namespace smplr;
+  int tx, ntiles;
   SMPLR_REQUIRE(B >= 0 && V >= 1 && V <= (1 << 24) && F >= 0 && F <= (1 << 24),
                 "smplr_mesh_raster: bad sizes B=%d V=%d F=%d (B >= 0, 1 <= V <= 2^24, F <= 2^24)", B, V, F);
-  SMPLR_REQUIRE(H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "smplr_mesh_raster: image %d x %d outside 1..4096", H, W);
+  if (const int e = key_tile_grid("smplr_mesh_raster", B, H, W, &tx, &ntiles)) return e;
   SMPLR_REQUIRE(mode == SMPLR_MESH_ORTHO || mode == SMPLR_MESH_PERSPECTIVE,
                 "smplr_mesh_raster: mode %d is neither ortho (0) nor perspective (1)", mode);
   if (B == 0) return 0;
@@ -339,10 +323,8 @@ int smplr_mesh_raster(const void *vbuf, const int32_t *faces, const uint8_t *fac
   if (!face && !depth && !part && !alpha && !rgb) return 0;
   const int4 *geom = reinterpret_cast<const int4 *>(vbuf);
   const float4 *col = reinterpret_cast<const float4 *>(geom + (size_t)B * V);
-  const int tx = (W + MR_TILE - 1) / MR_TILE, ty = (H + MR_TILE - 1) / MR_TILE;
-  SMPLR_REQUIRE((long long)B * tx * ty < (1ll << 31), "smplr_mesh_raster: %d meshes x %d tiles exceed the grid", B, tx * ty);
-  hipLaunchKernelGGL(mesh_raster_kernel, dim3((unsigned)(B * tx * ty)), dim3(MR_T), 0, as_stream(stream), geom, col, faces,
-                     face_part, V, F, H, W, mode, tx, tx * ty, bg, face, depth, part, alpha, rgb);
+  hipLaunchKernelGGL(mesh_raster_kernel, dim3((unsigned)(B * ntiles)), dim3(MR_T), 0, as_stream(stream), geom, col, faces,
+                     face_part, V, F, H, W, mode, tx, ntiles, bg, face, depth, part, alpha, rgb);
   SMPLR_LAUNCH_CHECK("smplr_mesh_raster");
   return 0;
 }

@@ -581,34 +581,47 @@ std::vector<Tensor> mesh_render_meta(const Tensor &verts, const Tensor &cam, con
   return mesh_render_outputs(verts, H, W);
 }
 
+// ---- the half of their checks that the two per-sample gathers below share: the mode, the label / channel rule, out's rank,
+// dtype, channels and sizes, index.  Each op gives the words in which its messages differ; returns B = out.size(0).
+struct GatherWords {
+  const char *image_modes;                  // what modes 0 and 1 are
+  const char *channels_head, *channels_tail;  // around the channel count
+  const char *channels_owner;               // whose channel count out has to match
+  bool index_names_B;                       // the index message ends with B
+};
+int64_t gather_check(const Tensor &out, const c10::optional<Tensor> &index, int64_t mode, int64_t C, const GatherWords &w) {
+  TORCH_CHECK(mode >= 0 && mode <= 3, "mode must be ", w.image_modes, ", 2 (label) or 3 (binary label)");
+  const bool label = mode >= 2;
+  TORCH_CHECK(label ? C == 1 : (C == 1 || C == 3), w.channels_head, C, w.channels_tail, " (images 1 or 3, labels 1)");
+  TORCH_CHECK(out.dim() == (label ? 3 : 4), "out must be ", label ? "(B, H, W)" : "(B, C, H, W)");
+  TORCH_CHECK(out.scalar_type() == (label ? at::kInt : at::kFloat), "out must be ", label ? "int32" : "float32");
+  TORCH_CHECK(label || out.size(1) == C, "out has ", out.size(1), " channels, ", w.channels_owner, " ", C);
+  const int64_t B = out.size(0), H = out.size(-2), W = out.size(-1);
+  TORCH_CHECK(H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "H and W of out must be in 1..4096");
+  TORCH_CHECK(B <= INT32_MAX, "out holds too many samples");
+  TORCH_CHECK(!index || (index->dim() == 1 && index->size(0) == B &&
+                         (index->scalar_type() == at::kInt || index->scalar_type() == at::kLong)),
+              "index must be (B,) int32 or int64", w.index_names_B ? " with B = out.size(0) = " + std::to_string(B) : "");
+  return B;
+}
+
 // ---- data generator (train.py:96-143): pool (N, Hs, Ws[, C]) uint8 + matrices (B, 2, 3) -> out, in place ---------------
 // mode 0 / 1: images, nearest / bilinear, out (B, C, H, W) fp32 = texel * rescale; mode 2 / 3: labels / labels > 0, out
 // (B, H, W) int32.  index (B,) int32 / int64 rows of the pool (None: 0..B-1); its VALUES are clamped by the kernel, not
 // read here (that would be a host synchronisation).
 void affine_warp_check(const Tensor &pool, const Tensor &matrices, const c10::optional<Tensor> &index, const Tensor &out,
                        int64_t mode) {
-  TORCH_CHECK(mode >= 0 && mode <= 3, "mode must be 0 (image nearest), 1 (image bilinear), 2 (label) or 3 (binary label)");
   TORCH_CHECK(pool.scalar_type() == at::kByte, "pool must be uint8");
   TORCH_CHECK(pool.dim() == 3 || pool.dim() == 4, "pool must be (N, Hs, Ws) or (N, Hs, Ws, C)");
-  const int64_t C = pool.dim() == 4 ? pool.size(3) : 1;
-  const bool label = mode >= 2;
-  TORCH_CHECK(label ? C == 1 : (C == 1 || C == 3), "pool has ", C, " channels (images 1 or 3, labels 1)");
+  const int64_t B = gather_check(out, index, mode, pool.dim() == 4 ? pool.size(3) : 1,
+                                 {"0 (image nearest), 1 (image bilinear)", "pool has ", " channels", "the pool", false});
   TORCH_CHECK(pool.size(0) >= 1 && pool.size(0) <= INT32_MAX, "pool must hold 1..2^31-1 samples");
   TORCH_CHECK(pool.size(1) >= 1 && pool.size(1) <= 8192 && pool.size(2) >= 1 && pool.size(2) <= 8192,
               "pool planes must be 1..8192 on a side");
-  TORCH_CHECK(out.dim() == (label ? 3 : 4), "out must be ", label ? "(B, H, W)" : "(B, C, H, W)");
-  TORCH_CHECK(out.scalar_type() == (label ? at::kInt : at::kFloat), "out must be ", label ? "int32" : "float32");
-  TORCH_CHECK(label || out.size(1) == C, "out has ", out.size(1), " channels, the pool ", C);
-  const int64_t B = out.size(0), H = out.size(-2), W = out.size(-1);
-  TORCH_CHECK(H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "H and W of out must be in 1..4096");
-  TORCH_CHECK(B <= INT32_MAX, "out holds too many samples");
   TORCH_CHECK(matrices.dim() == 3 && matrices.size(0) == B && matrices.size(1) == 2 && matrices.size(2) == 3,
               "matrices must be (B, 2, 3) with B = out.size(0) = ", B);
   TORCH_CHECK(matrices.scalar_type() == at::kFloat, "matrices must be float32");
-  TORCH_CHECK(!index || (index->dim() == 1 && index->size(0) == B &&
-                         (index->scalar_type() == at::kInt || index->scalar_type() == at::kLong)),
-              "index must be (B,) int32 or int64");
-  TORCH_CHECK(mode != 1 || (pool.size(1) == H && pool.size(2) == W), "bilinear needs pool size = output size");
+  TORCH_CHECK(mode != 1 || (pool.size(1) == out.size(-2) && pool.size(2) == out.size(-1)), "bilinear needs pool size = output size");
 }
 void affine_warp(const Tensor &pool, const Tensor &matrices, const c10::optional<Tensor> &index, Tensor &out, int64_t mode,
                  double rescale) {
@@ -639,24 +652,13 @@ void affine_warp_meta(const Tensor &pool, const Tensor &matrices, const c10::opt
 // checked / clamped by the kernel, not read here (that would be a host synchronisation).
 void resize_pad_check(const Tensor &data, const Tensor &desc, const c10::optional<Tensor> &index, const Tensor &out,
                       int64_t channels, int64_t mode, int64_t flags) {
-  TORCH_CHECK(mode >= 0 && mode <= 3, "mode must be 0 (image bilinear), 1 (image nearest), 2 (label) or 3 (binary label)");
   TORCH_CHECK(flags >= 0 && flags <= 15, "flags must be a sum of 1 (pad), 2 (swap_rb), 4 (quantize), 8 (pil rule)");
   TORCH_CHECK(data.scalar_type() == at::kByte, "data must be uint8");
   TORCH_CHECK(data.numel() >= 1, "data must hold at least one byte");
-  const bool label = mode >= 2;
-  TORCH_CHECK(label ? channels == 1 : (channels == 1 || channels == 3), "channels = ", channels, " (images 1 or 3, labels 1)");
   TORCH_CHECK(desc.scalar_type() == at::kLong, "desc must be int64");
   TORCH_CHECK(desc.dim() == 2 && desc.size(1) == 4 && desc.size(0) >= 1 && desc.size(0) <= INT32_MAX,
               "desc must be (N, 4) with N >= 1: byte offset, pitch, height, width per image");
-  TORCH_CHECK(out.dim() == (label ? 3 : 4), "out must be ", label ? "(B, H, W)" : "(B, C, H, W)");
-  TORCH_CHECK(out.scalar_type() == (label ? at::kInt : at::kFloat), "out must be ", label ? "int32" : "float32");
-  TORCH_CHECK(label || out.size(1) == channels, "out has ", out.size(1), " channels, the call names ", channels);
-  const int64_t B = out.size(0), H = out.size(-2), W = out.size(-1);
-  TORCH_CHECK(H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "H and W of out must be in 1..4096");
-  TORCH_CHECK(B <= INT32_MAX, "out holds too many samples");
-  TORCH_CHECK(!index || (index->dim() == 1 && index->size(0) == B &&
-                         (index->scalar_type() == at::kInt || index->scalar_type() == at::kLong)),
-              "index must be (B,) int32 or int64 with B = out.size(0) = ", B);
+  gather_check(out, index, mode, channels, {"0 (image bilinear), 1 (image nearest)", "channels = ", "", "the call names", true});
 }
 void resize_pad(const Tensor &data, const Tensor &desc, const c10::optional<Tensor> &index, Tensor &out, int64_t channels,
                 int64_t mode, int64_t flags, double rescale) {

@@ -19,27 +19,13 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
+from . import _gather, _lib
+from ._gather import MAX_OUT, _out_hw
 from ._lib import check, ptr, stream
 
 IMAGE_BILINEAR, IMAGE_NEAREST, LABEL, LABEL_BINARY = 0, 1, 2, 3      # SMPLR_RESIZE_* modes of include/smplraster.h
 PAD, SWAP_RB, QUANTIZE, PIL_RULE = 1, 2, 4, 8                        # ... and flags
-MAX_OUT, MAX_SIDE = 4096, 8192
-
-
-def _hw(size):
-    if isinstance(size, (tuple, list)):
-        if len(size) != 2:
-            raise ValueError("a size is H or (H, W)")
-        return int(size[0]), int(size[1])
-    return int(size), int(size)
-
-
-def _out_hw(out_hw):
-    H, W = _hw(out_hw)
-    if not (1 <= H <= MAX_OUT and 1 <= W <= MAX_OUT):
-        raise ValueError("out_hw must be 1..%d on a side" % MAX_OUT)
-    return H, W
+MAX_SIDE = 8192
 
 
 def pad_geometry(h, w, pad=True):
@@ -185,24 +171,10 @@ def _resize(data, ragged, index, out, shape, dtype, mode, flags, rescale):
     if not desc.is_cuda or desc.device != dev:
         raise RuntimeError("desc lives on %s, data on %s" % (desc.device, dev))
     if index is not None:
-        if not isinstance(index, torch.Tensor) or index.dtype not in (torch.int32, torch.int64):
-            raise TypeError("index must be an int32 or int64 tensor")
-        index = _lib.require_cuda(index, "index", index.dtype)
-        if index.dim() != 1:
-            raise ValueError("index must be (B,)")
-        if index.device != dev:
-            raise RuntimeError("index lives on %s, the images on %s" % (index.device, dev))
-        B = int(index.shape[0])
-    else:
-        B = len(ragged)
+        index = _gather._index(index, None, dev, "the images")
+    B = len(ragged) if index is None else int(index.shape[0])
     shape = (B,) + shape
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device=dev)
-    else:
-        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != dev:
-            raise RuntimeError("out must live on the images' device")
-        if out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
-            raise ValueError("out must be a contiguous %s tensor of shape %s" % (dtype, shape))
+    out = _gather._out(out, shape, dtype, dev, "the images'")
     if B == 0:
         return out
     check(_lib.load().smplr_resize_pad(ptr(data), int(data.numel()), ptr(desc), len(ragged), ragged.channels, ptr(index),

@@ -22,34 +22,15 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 import ilps_amd  # noqa: E402,F401
 from ilps_amd import augment  # noqa: E402
+import gather_timing  # noqa: E402
 
 HBM_TBPS = 6.3                     # achievable HBM rate of an MI355X
 REF = dict(rotation_range=10, width_shift_range=0.05, height_shift_range=0.05, shear_range=0.15, zoom_range=0.15)
 S, W, NPOOL = 256, 48, 256
-
-
-def timed_pair(fa, fb, iters, warm=10):
-    """us per call of fa and fb, measured in alternating blocks of iters / 4 calls."""
-    for _ in range(warm):
-        fa()
-        fb()
-    torch.cuda.synchronize()
-    tot = [0.0, 0.0]
-    blocks, n = 4, max(1, iters // 4)
-    for _ in range(blocks):
-        for k, fn in enumerate((fa, fb)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(n):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            tot[k] += e0.elapsed_time(e1) * 1000.0
-    return tot[0] / (blocks * n), tot[1] / (blocks * n)
 
 
 def hip_bytes(B):
@@ -67,20 +48,7 @@ def stock_bytes(B):
 def trace_medians(path):
     """Median duration (us) and count of the affine_warp dispatches of a rocprofv3 kernel trace, per (kernel, grid):
     the grid tells the batch (B * ceil(H * W / 1024) workgroups of 256 threads)."""
-    import csv
-    groups = {}
-    with open(path, newline="") as f:
-        for row in csv.DictReader(f):
-            name = row.get("Kernel_Name", "")
-            if "affine_warp_kernel" not in name:
-                continue
-            key = (name.split("affine_warp_kernel")[1].split(">")[0] + ">", int(row.get("Grid_Size_X", row.get("Grid_Size", 0))))
-            groups.setdefault(key, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
-    out = {}
-    for (name, grid), v in sorted(groups.items()):
-        v.sort()
-        out["%s grid %d" % (name, grid)] = {"n": len(v), "median_us": round(v[len(v) // 2], 2), "min_us": round(v[0], 2)}
-    return out
+    return gather_timing.trace_medians(path, "affine_warp_kernel")
 
 
 def main():
@@ -132,8 +100,8 @@ def main():
         batches = iter(augment.DeviceBatches(pool_i, pool_l, B, S, W, gen, generator=g))
         r, w = hip_bytes(B)
         row = {"MB_read_max": round(r / 1e6, 2), "MB_written": round(w / 1e6, 2), "stock_MB_moved": round(stock_bytes(B) / 1e6, 1)}
-        us, stock_us = timed_pair(warps, stock, a.iters)
-        us_bl, batch_us = timed_pair(lambda: warps("bilinear"), lambda: next(batches), a.iters)
+        us, stock_us = gather_timing.timed_pair(warps, stock, a.iters, warm=10)
+        us_bl, batch_us = gather_timing.timed_pair(lambda: warps("bilinear"), lambda: next(batches), a.iters, warm=10)
         row.update(warps_us=round(us, 1), warps_bilinear_us=round(us_bl, 1), batch_us=round(batch_us, 1),
                    stock_us=round(stock_us, 1), TB_per_s=round((r + w) / us / 1e6, 3),
                    share_of_6p3=round((r + w) / us / 1e6 / HBM_TBPS, 3), stock_over_hip=round(stock_us / us, 1),

@@ -25,7 +25,9 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
+
+import gather_timing  # noqa: E402
 
 N_IMAGES, LO, HI, S, W = 128, 200, 1000, 256, 48
 FRAME = (720, 1280)
@@ -58,40 +60,7 @@ def workloads():
 
 def trace_medians(path):
     """Median duration (us) and count of the resize_pad dispatches of a rocprofv3 kernel trace, per (kernel, grid)."""
-    import csv
-    groups = {}
-    with open(path, newline="") as f:
-        for row in csv.DictReader(f):
-            name = row.get("Kernel_Name", "")
-            if "resize_pad_kernel" not in name:
-                continue
-            key = (name.split("resize_pad_kernel")[1].split(">")[0] + ">", int(row.get("Grid_Size_X", row.get("Grid_Size", 0))))
-            groups.setdefault(key, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
-    out = {}
-    for (name, grid), v in sorted(groups.items()):
-        v.sort()
-        out["%s grid %d" % (name, grid)] = {"n": len(v), "median_us": round(v[len(v) // 2], 2), "min_us": round(v[0], 2)}
-    return out
-
-
-def timed_pair(fa, fb, iters, warm=3):
-    """us per call of fa and fb, measured in alternating blocks of iters / 4 calls."""
-    for _ in range(warm):
-        fa()
-        fb()
-    torch.cuda.synchronize()
-    tot = [0.0, 0.0]
-    blocks, n = 4, max(1, iters // 4)
-    for _ in range(blocks):
-        for k, fn in enumerate((fa, fb)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(n):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            tot[k] += e0.elapsed_time(e1) * 1000.0
-    return tot[0] / (blocks * n), tot[1] / (blocks * n)
+    return gather_timing.trace_medians(path, "resize_pad_kernel")
 
 
 def main():
@@ -151,7 +120,7 @@ def main():
     res = {}
     for name, args in workloads().items():
         r, w = hip_bytes(*args)
-        us, stock_us = timed_pair(runs[name][0], runs[name][1], a.iters)
+        us, stock_us = gather_timing.timed_pair(runs[name][0], runs[name][1], a.iters, warm=3)
         res[name] = {"MB_read_min": round(r / 1e6, 3), "MB_written": round(w / 1e6, 3), "hip_us": round(us, 1),
                      "stock_us": round(stock_us, 1), "TB_per_s_min": round((r + w) / us / 1e6, 3),
                      "stock_over_hip": round(stock_us / us, 1)}
