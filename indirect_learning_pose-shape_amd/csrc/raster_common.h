@@ -87,6 +87,19 @@ static int lds_attr(size_t lds, const char *file = __builtin_FILE()) {
   return ensure_lds_attr(reinterpret_cast<const void *>(Kernel), lds, &memo, file);
 }
 
+// The two together: raise Kernel's attribute for `at.lds`, launch it with `args`, return lds_attr's rc (0: launched;
+// the caller's SMPLR_LAUNCH_CHECK follows).  lds_launch<&k<true>>({grid, block, lds, stream}, args...)
+struct LdsLaunch {
+  dim3 grid, block; size_t lds; hipStream_t st; const char *file;
+  LdsLaunch(dim3 g, dim3 b, size_t l, hipStream_t s, const char *f = __builtin_FILE()) : grid(g), block(b), lds(l), st(s), file(f) {}
+};
+template <auto Kernel, class... Args>
+static int lds_launch(const LdsLaunch &at, Args... args) {
+  if (int rc = lds_attr<Kernel>(at.lds, at.file)) return rc;
+  hipLaunchKernelGGL(Kernel, at.grid, at.block, at.lds, at.st, args...);
+  return 0;
+}
+
 struct SegWs {
   size_t goff_off, lstart_off, lrec_off, total;
 };

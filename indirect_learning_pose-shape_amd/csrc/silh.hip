@@ -2,9 +2,10 @@
 // and mesh size: silh_px_kernel (one lane per pixel, W <= 48), silh_fused_kernel<ONEWORD> (four lanes per pixel, W <= 96)
 // and the brute force silh_prep_kernel + silh_fwd_kernel; all give the same bits.  silh_bwd_kernel is the backward.
 // smplr_silh_fwd_loss adds the silhouette loss head (silh_loss_device.h): silh_px_kernel<true>'s epilogue, or
-// silh_loss.hip's stand-alone kernel behind any form.
+// silh_loss.hip's stand-alone kernel behind any form.  What the kernels share - the key, the pixel's write-out, the front
+// of the two pruned kernels, the backward's body and launcher - is silh_device.h's.
 // Reference: keras_smpl/projects_to_silhouette.py:20-42.
-#include "raster_common.h"
+#include "silh_device.h"
 #include "silh_loss_device.h"
 
 namespace smplr {
@@ -48,23 +49,12 @@ __global__ __launch_bounds__(RT) void silh_fwd_kernel(const float4 *__restrict__
       const float4 a = S[k + j];
       const int v = __float_as_int(a.w);
       const float du = a.x - fc, dv = a.y - fr;
-      const unsigned long long key =
-          v < 0 ? ~0ull : ((unsigned long long)__float_as_uint(fmaf(du, du, dv * dv)) << 32) | (unsigned int)v;
+      const unsigned long long key = v < 0 ? ~0ull : silh_key(du, dv, v);
       best = key < best ? key : best;
     }
   }
-  int pos = -1;
-  float score = 0.0f;
-  if (best != ~0ull) {
-    score = expf(-sqrtf(__uint_as_float((unsigned int)(best >> 32))) / 1.2f);
-    pos = (int)(best & 0xffffffffull);
-  }
-  if (live) {
-    const size_t o = ((size_t)n * W + (W - 1 - r)) * W + c;   // rows flipped (:42)
-    out[o * 2 + 0] = 1.0f - score;
-    out[o * 2 + 1] = score;
-    arg_out[o] = pos;
-  }
+  const SilhPx px = silh_decode(best);
+  if (live) silh_store(out, arg_out, silh_out_offset(n, W, r, c), px);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -85,9 +75,7 @@ __global__ __launch_bounds__(RT) void silh_fwd_kernel(const float4 *__restrict__
 // loads from global memory (any lane's candidate was everybody's work, and every record group cost
 // an L2 round trip): 57 + 212 us at B = 128.  Ties go to the lowest vertex index, as the dense
 // formulation's arg-max does (keys are packed (d^2 bits, index) and compared as 64-bit integers).
-constexpr int SM = 8;            // margin of the cell window around the image
 constexpr int SILH_WMAX = 96;    // (W + 16)^2 cell offsets + the vertex records must fit LDS
-constexpr int SF_T = 1024;
 
 static size_t silh_fused_lds(int VP, int W) {
   const int GW = W + 2 * SM;
@@ -154,12 +142,7 @@ __global__ __launch_bounds__(SF_T) void silh_fused_kernel(const float *__restric
   const float *pj = proj + (size_t)n * VP * 3;
   // ---- binning: every vertex requested up front
   float pu[IPT_MAX], pv[IPT_MAX];
-#pragma unroll
-  for (int j = 0; j < IPT_MAX; ++j) {
-    const int v = min(tid + j * SF_T, VP - 1);
-    pu[j] = pj[v * 3];
-    pv[j] = pj[v * 3 + 1];
-  }
+  silh_prefetch(pj, VP, pu, pv);
   for (int i = tid; i < cells; i += SF_T) s_cnt[i] = 0;
   for (int i = tid; i < 2 * GW; i += SF_T) rowmask[i] = 0ull;
   if (tid == 0) s_nout = 0;
@@ -167,19 +150,12 @@ __global__ __launch_bounds__(SF_T) void silh_fused_kernel(const float *__restric
   int pc[IPT_MAX];
 #pragma unroll
   for (int j = 0; j < IPT_MAX; ++j) {
-    const int v = tid + j * SF_T;
-    pc[j] = -2;                                  // no vertex
-    if (v < VP) {
-      const float cx = rintf(pu[j]) + (float)SM, cy = rintf(pv[j]) + (float)SM;
-      if (cx >= 0.0f && cx < (float)GW && cy >= 0.0f && cy < (float)GW) {
-        pc[j] = (int)cy * GW + (int)cx;
-        atomicAdd(&s_cnt[pc[j]], 1);
-        atomicOr(&rowmask[2 * (int)cy + ((int)cx >> 6)], 1ull << ((int)cx & 63));
-      } else {
-        pc[j] = -1;                              // outlier (also NaN positions)
-        atomicAdd(&s_nout, 1);
-      }
-    }
+    pc[j] = silh_bin(tid + j * SF_T < VP, pu[j], pv[j], GW, GW,
+                     [&](const SilhBin &b) {
+                       atomicAdd(&s_cnt[b.cell], 1);
+                       atomicOr(&rowmask[2 * (int)b.cy + ((int)b.cx >> 6)], 1ull << ((int)b.cx & 63));
+                     },
+                     [&] { atomicAdd(&s_nout, 1); });
   }
   __syncthreads();
   // exclusive scan of the counts -> placement cursors; after placement s_cnt[e] = end of cell e
@@ -215,21 +191,12 @@ __global__ __launch_bounds__(SF_T) void silh_fused_kernel(const float *__restric
   const int tpr = (W + 3) / 4, ntile = tpr * ((W + TH - 1) / TH);
 #define SMPLR_SILH_VERTEX(i_)                                                                   \
   {                                                                                             \
-    const float du_ = sU[i_] - fc, dv_ = sV[i_] - fr;                                           \
-    const unsigned long long k_ =                                                               \
-        ((unsigned long long)__float_as_uint(fmaf(du_, du_, dv_ * dv_)) << 32) | (unsigned int)sI[i_]; \
+    const unsigned long long k_ = silh_key(sU[i_] - fc, sV[i_] - fr, sI[i_]);                   \
     best = k_ < best ? k_ : best;                                                               \
   }
-  // Tiles are handed out through a counter in LDS, not round-robin: tiles over the body cost several times a
-  // background tile, and the workgroup waits for its slowest wave (W = 48: 51.5 -> 48.5 us, W = 64: 107 -> 76 us at
-  // B = 128; in image order - starting at the middle rows measured the same, from both ends inwards 4 us worse).
-  const int nloc = (ntile - (int)blockIdx.y + (int)gridDim.y - 1) / (int)gridDim.y;
   for (;;) {
-    int t = 0;
-    if (lane == 0) t = atomicAdd(&s_next_tile, 1);
-    t = __builtin_amdgcn_readfirstlane(t);
-    if (t >= nloc) break;
-    const int tile = t * (int)gridDim.y + (int)blockIdx.y;
+    int tile;
+    if (!silh_next_tile(&s_next_tile, lane, ntile, tile)) break;
     const int ty = tile / tpr, tx = tile - ty * tpr;
     const int r_ = ty * TH + (pq >> 2), c_ = tx * 4 + (pq & 3);
     const bool live = r_ < W && c_ < W;
@@ -252,8 +219,7 @@ __global__ __launch_bounds__(SF_T) void silh_fused_kernel(const float *__restric
         if ((m0 | m1) == 0ull) continue;
         const int off = ONEWORD ? nearest_bit1(m0, cx) : nearest_bit(m0, m1, cx);
         const float dx = (float)off;
-        const unsigned long long kk =
-            ((unsigned long long)__float_as_uint(fmaf(dx, dx, fk * fk)) << 32) | (unsigned int)(y * GW + cx + off);
+        const unsigned long long kk = silh_key(dx, fk, y * GW + cx + off);
         near = kk < near ? kk : near;
       }
     }
@@ -300,18 +266,7 @@ __global__ __launch_bounds__(SF_T) void silh_fused_kernel(const float *__restric
     }
     for (int i = tot_v + sub; i < tot_v + nout; i += LPP) SMPLR_SILH_VERTEX(i)     // outliers: always
     best = quad_min(best);
-    if (live && sub == 0) {
-      float score = 0.0f;
-      int pos = -1;
-      if (best != ~0ull) {
-        score = expf(-sqrtf(__uint_as_float((unsigned int)(best >> 32))) / 1.2f);
-        pos = (int)(best & 0xffffffffull);
-      }
-      const size_t o = ((size_t)n * W + (W - 1 - r)) * W + c;   // rows flipped (:42)
-      out[o * 2 + 0] = 1.0f - score;
-      out[o * 2 + 1] = score;
-      arg_out[o] = pos;
-    }
+    if (live && sub == 0) silh_store(out, arg_out, silh_out_offset(n, W, r, c), silh_decode(best));
   }
 #undef SMPLR_SILH_VERTEX
 }
@@ -403,12 +358,7 @@ __global__ __launch_bounds__(SF_T) void silh_px_kernel(const float *__restrict__
   const float *pj = proj + (size_t)n * VP * 3;
   // ---- binning: every vertex requested up front
   float pu[IPT_MAX], pv[IPT_MAX];
-#pragma unroll
-  for (int j = 0; j < IPT_MAX; ++j) {
-    const int v = min(tid + j * SF_T, VP - 1);
-    pu[j] = pj[v * 3];
-    pv[j] = pj[v * 3 + 1];
-  }
+  silh_prefetch(pj, VP, pu, pv);
   for (int i = tid; i <= cells; i += SF_T) s_cnt[i] = 0;
   for (int i = tid; i < W * WP; i += SF_T) own[i] = ~0ull;
   if (tid < GW) rowmask[tid] = 0ull;
@@ -419,25 +369,15 @@ __global__ __launch_bounds__(SF_T) void silh_px_kernel(const float *__restrict__
 #pragma unroll
   for (int j = 0; j < IPT_MAX; ++j) {
     const int v = tid + j * SF_T;
-    pc[j] = -2;                                  // no vertex
     rank[j] = 0;
-    if (v < VP) {
-      const float ru = rintf(pu[j]), rv = rintf(pv[j]);
-      const float cx = ru + (float)SM, cy = rv + (float)SM;
-      if (cx >= 0.0f && cx < (float)GW && cy >= 0.0f && cy < (float)GW) {
-        pc[j] = (int)cy * GWP + (int)cx;
-        rank[j] = atomicAdd(&s_cnt[pc[j]], 1);              // arrival order within the cell
-        if (ru >= 0.0f && ru < (float)W && rv >= 0.0f && rv < (float)W) {
-          // the pixel at this cell's centre: its key for this vertex, as the pixel itself would compute it
-          const float du = pu[j] - ru, dv = pv[j] - rv;
-          atomicMin(&own[(int)rv * WP + (int)ru],
-                    ((unsigned long long)__float_as_uint(fmaf(du, du, dv * dv)) << 32) | (unsigned int)v);
-        }
-      } else {
-        pc[j] = -1;                              // outlier (also NaN positions)
-        rank[j] = atomicAdd(&s_nout, 1);
-      }
-    }
+    pc[j] = silh_bin(v < VP, pu[j], pv[j], GW, GWP,
+                     [&](const SilhBin &b) {
+                       rank[j] = atomicAdd(&s_cnt[b.cell], 1);            // arrival order within the cell
+                       // the pixel at this cell's centre: its key for this vertex, as the pixel itself would compute it
+                       if (b.ru >= 0.0f && b.ru < (float)W && b.rv >= 0.0f && b.rv < (float)W)
+                         atomicMin(&own[(int)b.rv * WP + (int)b.ru], silh_key(pu[j] - b.ru, pv[j] - b.rv, v));
+                     },
+                     [&] { rank[j] = atomicAdd(&s_nout, 1); });
   }
   __syncthreads();
   SMPLR_TL_STAMP(2);
@@ -496,10 +436,7 @@ __global__ __launch_bounds__(SF_T) void silh_px_kernel(const float *__restrict__
   // ---- pixels: a wave takes 8 x 8 tiles, handed out through a counter (tiles on the outline cost more)
   const int lane = tid & 63;
   const int tpr = (W + SPX_TILE - 1) / SPX_TILE, ntile = tpr * tpr;
-  const int nloc = (ntile - (int)blockIdx.y + (int)gridDim.y - 1) / (int)gridDim.y;
-#define SMPLR_SPX_KEY(rec_)                                                                               \
-  (((unsigned long long)__float_as_uint(fmaf((rec_).x - fc, (rec_).x - fc, ((rec_).y - fr) * ((rec_).y - fr))) << 32) | \
-   (unsigned int)__float_as_int((rec_).z))
+#define SMPLR_SPX_KEY(rec_) silh_key((rec_).x - fc, (rec_).y - fr, __float_as_int((rec_).z))
   // records [i0_, i1_) (wave-uniform, i0_ < i1_) against every lane's pixel: four broadcast reads in flight per
   // step; a step's surplus slots repeat the range's last record (the same key again: harmless)
 #define SMPLR_SPX_RANGE(i0_, i1_)                                                                         \
@@ -512,11 +449,8 @@ __global__ __launch_bounds__(SF_T) void silh_px_kernel(const float *__restrict__
     best = k4_ < best ? k4_ : best;                                                                       \
   }
   for (;;) {
-    int t = 0;
-    if (lane == 0) t = atomicAdd(&s_next_tile, 1);
-    t = __builtin_amdgcn_readfirstlane(t);
-    if (t >= nloc) break;
-    const int tile = t * (int)gridDim.y + (int)blockIdx.y;
+    int tile;
+    if (!silh_next_tile(&s_next_tile, lane, ntile, tile)) break;
     const int ty = tile / tpr, tx = tile - ty * tpr;
     const int r_ = ty * SPX_TILE + (lane >> 3), c_ = tx * SPX_TILE + (lane & 7);
     const bool live = r_ < W && c_ < W;
@@ -531,9 +465,9 @@ __global__ __launch_bounds__(SF_T) void silh_px_kernel(const float *__restrict__
     unsigned long long rows = 0ull;
     float lim = -1.0f;                                      // squared search radius (< 0: nothing to search)
     float hs = 0.0f;                                        // the hint's score for this pixel (0: none)
-    if (hint) hs = hint[((size_t)n * W + (W - 1 - r)) * W + c];
+    if (hint) hs = hint[silh_out_offset(n, W, r, c)];
     int lab = 0;
-    if (LOSS) lab = io.labels[((size_t)n * W + (W - 1 - r)) * W + c];   // (clamped lanes: a border pixel's, unused)
+    if (LOSS) lab = io.labels[silh_out_offset(n, W, r, c)];   // (clamped lanes: a border pixel's, unused)
     if (best != ~0ull) {
       // (1) own cell occupied: other cells matter only if the nearest own vertex is farther than half a cell
       const float d2 = __uint_as_float((unsigned int)(best >> 32));
@@ -648,16 +582,11 @@ __global__ __launch_bounds__(SF_T) void silh_px_kernel(const float *__restrict__
     if (nout > 0) SMPLR_SPX_RANGE(tot_v, tot_v + nout)       // outliers: always
     float score_l = 0.0f;                                   // (LOSS) the live lane's score, for the counts below
     if (live) {
-      float score = 0.0f;
-      int pos = -1;
-      if (best != ~0ull) {
-        score = expf(-sqrtf(__uint_as_float((unsigned int)(best >> 32))) / 1.2f);
-        pos = (int)(best & 0xffffffffull);
-      }
-      score_l = score;
-      const size_t o = ((size_t)n * W + (W - 1 - r)) * W + c;   // rows flipped (:42)
+      const SilhPx px = silh_decode(best);
+      const float score = score_l = px.score;
+      const size_t o = silh_out_offset(n, W, r, c);
       *reinterpret_cast<float2 *>(out + o * 2) = make_float2(1.0f - score, score);
-      arg_out[o] = pos;
+      arg_out[o] = px.pos;
       if (LOSS) {
         const SilhLossPx lp = silh_loss_px(1.0f - score, score, lab, lw0, lw1, io.gamma);
         io.loss[o] = lp.loss;
@@ -696,77 +625,17 @@ __global__ __launch_bounds__(SF_T) void silh_px_kernel(const float *__restrict__
 #undef SMPLR_TL_CLK
 }
 
-// DET: the per-vertex sums as 64-bit fixed point (see seg_flush_det): bit-reproducible whatever the order in which
-// the 1 024 threads' pixels reach a vertex' accumulator.
+// The backward for a gradient of the two channels (silh_device.h's body with g = dsilh[1] - dsilh[0])
 template <bool DET>
 __global__ __launch_bounds__(1024) void silh_bwd_kernel(const float *__restrict__ dsilh,
                                                         const float *__restrict__ silh,
                                                         const int *__restrict__ arg,
                                                         const float *__restrict__ proj, int VP, int W,
                                                         float *__restrict__ dproj) {
-  // gridDim.y workgroups share a mesh: each owns a contiguous range of VERTICES (its accumulators, its rows of
-  // dproj) and walks all the pixels, taking those whose arg-max vertex is its own - with fewer meshes than compute
-  // units what there is to spread is the zeroing and the 82 KB of dproj per mesh, the pixel walk is short
-  extern __shared__ __attribute__((aligned(16))) float acc[];
-  unsigned long long *acc64 = reinterpret_cast<unsigned long long *>(acc);
-  __shared__ unsigned s_gmax;
-  const int n = blockIdx.x, tid = threadIdx.x;
-  const int per = (VP + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int v0 = (int)blockIdx.y * per, v1 = min(VP, v0 + per), nv = max(v1 - v0, 0);
-  if (DET) {
-    for (int i = tid; i < nv * 2; i += 1024) acc64[i] = 0ull;
-    if (tid == 0) s_gmax = 0u;
-  } else {
-    for (int i = tid; i < nv * 2; i += 1024) acc[i] = 0.0f;
-  }
-  __syncthreads();
-  const int npix = W * W;
-  float scale = 1.0f, inv_scale = 1.0f;
-  if (DET) {
-    unsigned gm = 0u;
-    for (int i = tid; i < npix * 2; i += 1024) gm = max(gm, __float_as_uint(fabsf(dsilh[(size_t)n * npix * 2 + i])));
-    atomicMax(&s_gmax, gm);
-    __syncthreads();
-    int eg, terms = 1;
-    frexpf(__uint_as_float(s_gmax), &eg);
-    while ((1 << terms) < npix) ++terms;
-    // a term is |g1 - g0| s / 1.2 |du| / d < 2^(1 + eg); a vertex collects at most W^2 <= 2^terms of them
-    const int e = min(max(60 - eg - terms, -100), 100);
-    scale = ldexpf(1.0f, e);
-    inv_scale = ldexpf(1.0f, -e);
-  }
-  const float *pj = proj + (size_t)n * VP * 3;
-  for (int o = tid; o < npix; o += 1024) {
-    const size_t po = (size_t)n * npix + o;
-    const int v = arg[po];
-    if (v < v0 || v >= v1) continue;                       // (-1: no vertex) another workgroup's vertex
-    const float g = dsilh[po * 2 + 1] - dsilh[po * 2];
-    const float sc = silh[po * 2 + 1];
-    const int ro = o / W, cc = o - ro * W;
-    const float fr = (float)(W - 1 - ro), fc = (float)cc;
-    const float du = pj[v * 3] - fc, dv = pj[v * 3 + 1] - fr;
-    const float d = sqrtf(fmaf(du, du, dv * dv));
-    const float k = -g * sc / 1.2f;
-    if (d > 0.0f && k != 0.0f) {
-      const float kk = k / d;
-      const int a = (v - v0) * 2;
-      if (DET) {
-        atomicAdd(&acc64[a], (unsigned long long)__float2ll_rn(kk * du * scale));
-        atomicAdd(&acc64[a + 1], (unsigned long long)__float2ll_rn(kk * dv * scale));
-      } else {
-        atomicAdd(&acc[a], kk * du);
-        atomicAdd(&acc[a + 1], kk * dv);
-      }
-    }
-  }
-  __syncthreads();
-  float *o = dproj + ((size_t)n * VP + v0) * 3;
-  for (int i = tid; i < nv * 3; i += 1024) {
-    const int v = i / 3, c = i - v * 3;
-    if (DET) o[i] = (c < 2) ? (float)(long long)acc64[v * 2 + c] * inv_scale : 0.0f;
-    else o[i] = (c < 2) ? acc[v * 2 + c] : 0.0f;
-  }
+  silh_bwd_body<DET>(SilhGradChannels{dsilh}, silh, arg, proj, VP, W, dproj);
 }
+
+static int silh_fwd_nsplit(int B) { return B >= 256 ? 1 : (B >= 128 ? 2 : 4); }   // one workgroup per CU (256 CUs)
 }  // namespace smplr
 
 extern "C" {
@@ -797,32 +666,18 @@ static int silh_fwd_launch(const float *proj, const float *hint, int B, int VP, 
   const int form = smplr_silh_fwd_form(VP, W);
   if (form == 0) {
     const SpxLds L = silh_px_layout(VP, W);
-    const int nsplit = B >= 256 ? 1 : (B >= 128 ? 2 : 4);      // one workgroup per CU (256 CUs)
-    if (io) {
-      int rc = lds_attr<&silh_px_kernel<true>>(L.total);
-      if (rc) return rc;
-      hipLaunchKernelGGL(silh_px_kernel<true>, dim3(B, nsplit), dim3(SF_T), L.total, st, proj, VP, W, L, silh, arg, hint, *io);
-    } else {
-      int rc = lds_attr<&silh_px_kernel<false>>(L.total);
-      if (rc) return rc;
-      hipLaunchKernelGGL(silh_px_kernel<false>, dim3(B, nsplit), dim3(SF_T), L.total, st, proj, VP, W, L, silh, arg, hint,
-                         SilhLossIO{});
-    }
+    const LdsLaunch at(dim3(B, silh_fwd_nsplit(B)), dim3(SF_T), L.total, st);
+    if (int rc = io ? lds_launch<&silh_px_kernel<true>>(at, proj, VP, W, L, silh, arg, hint, *io)
+                    : lds_launch<&silh_px_kernel<false>>(at, proj, VP, W, L, silh, arg, hint, SilhLossIO{}))
+      return rc;
     SMPLR_LAUNCH_CHECK("smplr_silh_fwd");
     return 0;
   }
   if (form == 1 || form == 2) {
-    const size_t lds = silh_fused_lds(VP, W);
-    const int nsplit = B >= 256 ? 1 : (B >= 128 ? 2 : 4);      // one workgroup per CU (256 CUs)
-    if (form == 1) {
-      int rc = lds_attr<&silh_fused_kernel<true>>(lds);
-      if (rc) return rc;
-      hipLaunchKernelGGL(silh_fused_kernel<true>, dim3(B, nsplit), dim3(SF_T), lds, st, proj, VP, W, silh, arg);
-    } else {
-      int rc = lds_attr<&silh_fused_kernel<false>>(lds);
-      if (rc) return rc;
-      hipLaunchKernelGGL(silh_fused_kernel<false>, dim3(B, nsplit), dim3(SF_T), lds, st, proj, VP, W, silh, arg);
-    }
+    const LdsLaunch at(dim3(B, silh_fwd_nsplit(B)), dim3(SF_T), silh_fused_lds(VP, W), st);
+    if (int rc = form == 1 ? lds_launch<&silh_fused_kernel<true>>(at, proj, VP, W, silh, arg)
+                           : lds_launch<&silh_fused_kernel<false>>(at, proj, VP, W, silh, arg))
+      return rc;
     SMPLR_LAUNCH_CHECK("smplr_silh_fwd");
     return 0;
   }
@@ -877,23 +732,8 @@ int smplr_silh_bwd(const float *dsilh, const float *silh, const int32_t *arg, co
   SMPLR_REQUIRE(B >= 0 && VP > 0 && W > 0 && W <= 1024, "smplr_silh_bwd: bad sizes B=%d VP=%d W=%d", B, VP, W);
   if (B == 0) return 0;
   SMPLR_REQUIRE(dsilh && silh && arg && proj && dproj, "smplr_silh_bwd: null pointer");
-  const int nsplit = B >= 512 ? 1 : (B >= 128 ? 2 : 4);      // workgroups per mesh (vertex ranges)
-  const int per = (VP + nsplit - 1) / nsplit;
-  const size_t lds = (size_t)per * 2 * (deterministic ? sizeof(unsigned long long) : sizeof(float));
-  SMPLR_REQUIRE(lds <= 150 * 1024, "smplr_silh_bwd: VP=%d needs %zu B of LDS", VP, lds);
-  if (deterministic) {
-    int rc = lds_attr<&silh_bwd_kernel<true>>(lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(silh_bwd_kernel<true>, dim3(B, nsplit), dim3(1024), lds, as_stream(stream), dsilh, silh, arg, proj,
-                       VP, W, dproj);
-  } else {
-    int rc = lds_attr<&silh_bwd_kernel<false>>(lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(silh_bwd_kernel<false>, dim3(B, nsplit), dim3(1024), lds, as_stream(stream), dsilh, silh, arg, proj,
-                       VP, W, dproj);
-  }
-  SMPLR_LAUNCH_CHECK("smplr_silh_bwd");
-  return 0;
+  return silh_bwd_launch<&silh_bwd_kernel<true>, &silh_bwd_kernel<false>>("smplr_silh_bwd", __FILE__, B, VP, deterministic,
+                                                                          as_stream(stream), dsilh, silh, arg, proj, VP, W, dproj);
 }
 
 }  // extern "C"

@@ -3,9 +3,9 @@
 // silhouette rasteriser.  The arithmetic is silh_loss_device.h's, shared with silh_px_kernel's epilogue (silh.hip).
 //   silh_loss_fwd_kernel      silh (B,W,W,2) + labels -> loss, k = dL/ds (B, W*W) [+ (3, 2) confusion counts]: one lane per
 //                             pixel, for any W and any form of the silhouette forward
-//   silh_loss_bwd_kernel<DET> silh_bwd_kernel (silh.hip) fed g = dloss * k instead of dsilh[1] - dsilh[0]: the gradient
-//                             of the two silhouette channels never exists in memory
-#include "raster_common.h"
+//   silh_loss_bwd_kernel<DET> silh_bwd_kernel's body (silh_device.h) fed g = dloss * k instead of dsilh[1] - dsilh[0]: the
+//                             gradient of the two silhouette channels never exists in memory
+#include "silh_device.h"
 #include "silh_loss_device.h"
 #pragma clang fp contract(off)
 
@@ -53,75 +53,16 @@ void launch_silh_loss_fwd(const float *silh, SilhLossIO io, long long npix, hipS
   hipLaunchKernelGGL(silh_loss_fwd_kernel, dim3((unsigned)blocks), dim3(SL_T), 0, st, silh, io, npix);
 }
 
-// silh_bwd_kernel (silh.hip) with the loss gradient inside: same vertex ranges per workgroup, same LDS accumulators,
-// same 64-bit fixed point when DET and the same scale rule (from the mesh's max |g|) - with g = dloss * k formed here,
-// one fp32 multiply, it gives the bits silh_bwd_kernel gives for dsilh = (0, g).
+// The backward with the loss gradient inside: silh_device.h's body - what silh_bwd_kernel (silh.hip) runs - with
+// g = dloss * k formed per pixel, one fp32 multiply, and the deterministic scale from the mesh's max |g|: the bits
+// silh_bwd_kernel gives for dsilh = (0, g).
 template <bool DET>
 __global__ __launch_bounds__(1024) void silh_loss_bwd_kernel(const float *__restrict__ dloss, const float *__restrict__ kk_in,
                                                              const float *__restrict__ silh,
                                                              const int *__restrict__ arg,
                                                              const float *__restrict__ proj, int VP, int W,
                                                              float *__restrict__ dproj) {
-  extern __shared__ __attribute__((aligned(16))) float acc[];
-  unsigned long long *acc64 = reinterpret_cast<unsigned long long *>(acc);
-  __shared__ unsigned s_gmax;
-  const int n = blockIdx.x, tid = threadIdx.x;
-  const int per = (VP + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int v0 = (int)blockIdx.y * per, v1 = min(VP, v0 + per), nv = max(v1 - v0, 0);
-  if (DET) {
-    for (int i = tid; i < nv * 2; i += 1024) acc64[i] = 0ull;
-    if (tid == 0) s_gmax = 0u;
-  } else {
-    for (int i = tid; i < nv * 2; i += 1024) acc[i] = 0.0f;
-  }
-  __syncthreads();
-  const int npix = W * W;
-  const float *dl = dloss + (size_t)n * npix, *kp = kk_in + (size_t)n * npix;
-  float scale = 1.0f, inv_scale = 1.0f;
-  if (DET) {
-    unsigned gm = 0u;
-    for (int i = tid; i < npix; i += 1024) gm = max(gm, __float_as_uint(fabsf(dl[i] * kp[i])));
-    atomicMax(&s_gmax, gm);
-    __syncthreads();
-    int eg, terms = 1;
-    frexpf(__uint_as_float(s_gmax), &eg);
-    while ((1 << terms) < npix) ++terms;
-    // a term is |g| s / 1.2 |du| / d < 2^(1 + eg); a vertex collects at most W^2 <= 2^terms of them
-    const int e = min(max(60 - eg - terms, -100), 100);
-    scale = ldexpf(1.0f, e);
-    inv_scale = ldexpf(1.0f, -e);
-  }
-  const float *pj = proj + (size_t)n * VP * 3;
-  for (int o = tid; o < npix; o += 1024) {
-    const size_t po = (size_t)n * npix + o;
-    const int v = arg[po];
-    if (v < v0 || v >= v1) continue;                       // (-1: no vertex) another workgroup's vertex
-    const float g = dl[o] * kp[o];
-    const float sc = silh[po * 2 + 1];
-    const int ro = o / W, cc = o - ro * W;
-    const float fr = (float)(W - 1 - ro), fc = (float)cc;
-    const float du = pj[v * 3] - fc, dv = pj[v * 3 + 1] - fr;
-    const float d = sqrtf(fmaf(du, du, dv * dv));
-    const float k = -g * sc / 1.2f;
-    if (d > 0.0f && k != 0.0f) {
-      const float kk = k / d;
-      const int a = (v - v0) * 2;
-      if (DET) {
-        atomicAdd(&acc64[a], (unsigned long long)__float2ll_rn(kk * du * scale));
-        atomicAdd(&acc64[a + 1], (unsigned long long)__float2ll_rn(kk * dv * scale));
-      } else {
-        atomicAdd(&acc[a], kk * du);
-        atomicAdd(&acc[a + 1], kk * dv);
-      }
-    }
-  }
-  __syncthreads();
-  float *o = dproj + ((size_t)n * VP + v0) * 3;
-  for (int i = tid; i < nv * 3; i += 1024) {
-    const int v = i / 3, c = i - v * 3;
-    if (DET) o[i] = (c < 2) ? (float)(long long)acc64[v * 2 + c] * inv_scale : 0.0f;
-    else o[i] = (c < 2) ? acc[v * 2 + c] : 0.0f;
-  }
+  silh_bwd_body<DET>(SilhGradLoss{dloss, kk_in}, silh, arg, proj, VP, W, dproj);
 }
 }  // namespace smplr
 
@@ -146,23 +87,8 @@ int smplr_silh_loss_bwd(const float *dloss, const float *k, const float *silh, c
   SMPLR_REQUIRE(B >= 0 && VP > 0 && W > 0 && W <= 1024, "smplr_silh_loss_bwd: bad sizes B=%d VP=%d W=%d", B, VP, W);
   if (B == 0) return 0;
   SMPLR_REQUIRE(dloss && k && silh && arg && proj && dproj, "smplr_silh_loss_bwd: null pointer");
-  const int nsplit = B >= 512 ? 1 : (B >= 128 ? 2 : 4);      // workgroups per mesh (vertex ranges), as smplr_silh_bwd
-  const int per = (VP + nsplit - 1) / nsplit;
-  const size_t lds = (size_t)per * 2 * (deterministic ? sizeof(unsigned long long) : sizeof(float));
-  SMPLR_REQUIRE(lds <= 150 * 1024, "smplr_silh_loss_bwd: VP=%d needs %zu B of LDS", VP, lds);
-  if (deterministic) {
-    int rc = lds_attr<&silh_loss_bwd_kernel<true>>(lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(silh_loss_bwd_kernel<true>, dim3(B, nsplit), dim3(1024), lds, as_stream(stream), dloss, k, silh, arg,
-                       proj, VP, W, dproj);
-  } else {
-    int rc = lds_attr<&silh_loss_bwd_kernel<false>>(lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(silh_loss_bwd_kernel<false>, dim3(B, nsplit), dim3(1024), lds, as_stream(stream), dloss, k, silh, arg,
-                       proj, VP, W, dproj);
-  }
-  SMPLR_LAUNCH_CHECK("smplr_silh_loss_bwd");
-  return 0;
+  return silh_bwd_launch<&silh_loss_bwd_kernel<true>, &silh_loss_bwd_kernel<false>>(
+      "smplr_silh_loss_bwd", __FILE__, B, VP, deterministic, as_stream(stream), dloss, k, silh, arg, proj, VP, W, dproj);
 }
 
 }  // extern "C"

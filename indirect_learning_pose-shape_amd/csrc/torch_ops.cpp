@@ -170,37 +170,51 @@ Tensor seg_bwd_meta(const Tensor &dseg, const Tensor &, const Tensor &, int64_t 
 }
 
 // ---- projects_to_silhouette -------------------------------------------------------------------------------
+// The outputs, by shape alone (the meta functions allocate the same): silh (B,W,W,2), arg (B,W,W) int32; loss, k (B, W*W)
+std::tuple<Tensor, Tensor> silh_outputs(const Tensor &like, int64_t B, int64_t W) {
+  return {at::empty({B, W, W, 2}, like.options()), at::empty({B, W, W}, like.options().dtype(at::kInt))};
+}
+std::tuple<Tensor, Tensor> silh_loss_outputs(const Tensor &like, int64_t B, int64_t W) {
+  return {at::empty({B, W * W}, like.options()), at::empty({B, W * W}, like.options())};
+}
 std::tuple<Tensor, Tensor> silh_fwd(const Tensor &proj, int64_t W) {
   dev_f32(proj, "proj");
   TORCH_CHECK(proj.dim() == 3 && proj.size(2) == 3, "proj must be (B, VP, 3)");
   TORCH_CHECK(W > 0, "silh_fwd: W > 0");
   DeviceGuard g(proj.device());
   const int64_t B = proj.size(0), VP = proj.size(1);
-  Tensor silh = f32({B, W, W, 2}, proj), sarg = at::empty({B, W, W}, proj.options().dtype(at::kInt));
+  auto [silh, sarg] = silh_outputs(proj, B, W);
   Tensor ws = bytes(smplr_silh_workspace((int)B, (int)VP, (int)W), proj);
   ok(smplr_silh_fwd(fp(proj), (int)B, (int)VP, (int)W, fpm(silh), sarg.data_ptr<int32_t>(), ws.data_ptr(), cur_stream()),
      "smplr_silh_fwd");
   return {silh, sarg};
 }
-std::tuple<Tensor, Tensor> silh_fwd_meta(const Tensor &proj, int64_t W) {
-  return {at::empty({proj.size(0), W, W, 2}, proj.options()), at::empty({proj.size(0), W, W}, proj.options().dtype(at::kInt))};
-}
-Tensor silh_bwd(const Tensor &dsilh, const Tensor &silh, const Tensor &sarg, const Tensor &proj, bool deterministic) {
-  dev_f32(dsilh, "dsilh");
+std::tuple<Tensor, Tensor> silh_fwd_meta(const Tensor &proj, int64_t W) { return silh_outputs(proj, proj.size(0), W); }
+// What the two backward ops share: proj (B,VP,3), silh (B,W,W,2) and arg (B,W,W) int32 as `from` returned them, and the
+// op's float32 gradient operands `grads`, all on proj's device -> B, VP, W
+struct SilhDims { int64_t B, VP, W; };
+SilhDims silh_bwd_check(std::initializer_list<std::pair<const char *, const Tensor *>> grads, const Tensor &silh,
+                        const Tensor &sarg, const Tensor &proj, const char *from) {
+  for (const auto &nt : grads) dev_f32(*nt.second, nt.first);
   dev_f32(silh, "silh");
   dev_typed(sarg, at::kInt, "arg");
   dev_f32(proj, "proj");
   TORCH_CHECK(proj.dim() == 3 && proj.size(2) == 3, "proj must be (B, VP, 3)");
   TORCH_CHECK(silh.dim() == 4 && silh.size(0) == proj.size(0) && silh.size(1) == silh.size(2) && silh.size(3) == 2,
-              "silh must be (B,W,W,2) as silh_fwd returned it");
+              "silh must be (B,W,W,2) as ", from, " returned it");
+  const SilhDims d{proj.size(0), proj.size(1), silh.size(1)};
+  TORCH_CHECK(sarg.dim() == 3 && sarg.size(0) == d.B && sarg.size(1) == d.W && sarg.size(2) == d.W,
+              "arg must be (B,W,W) int32 as ", from, " returned it");
+  same_device(proj, grads);
+  same_device(proj, {{"silh", &silh}, {"arg", &sarg}});
+  return d;
+}
+Tensor silh_bwd(const Tensor &dsilh, const Tensor &silh, const Tensor &sarg, const Tensor &proj, bool deterministic) {
+  const SilhDims d = silh_bwd_check({{"dsilh", &dsilh}}, silh, sarg, proj, "silh_fwd");
   TORCH_CHECK(dsilh.sizes() == silh.sizes(), "dsilh must have silh's shape");
-  TORCH_CHECK(sarg.dim() == 3 && sarg.size(0) == silh.size(0) && sarg.size(1) == silh.size(1) && sarg.size(2) == silh.size(2),
-              "arg must be (B,W,W) int32 as silh_fwd returned it");
-  same_device(proj, {{"dsilh", &dsilh}, {"silh", &silh}, {"arg", &sarg}});
   DeviceGuard g(proj.device());
-  const int64_t B = proj.size(0), VP = proj.size(1), W = silh.size(1);
-  Tensor dproj = f32({B, VP, 3}, proj);
-  ok(smplr_silh_bwd(fp(dsilh), fp(silh), sarg.data_ptr<int32_t>(), fp(proj), (int)B, (int)VP, (int)W, fpm(dproj),
+  Tensor dproj = f32({d.B, d.VP, 3}, proj);
+  ok(smplr_silh_bwd(fp(dsilh), fp(silh), sarg.data_ptr<int32_t>(), fp(proj), (int)d.B, (int)d.VP, (int)d.W, fpm(dproj),
                     deterministic ? 1 : 0, cur_stream()), "smplr_silh_bwd");
   return dproj;
 }
@@ -239,15 +253,14 @@ std::tuple<Tensor, Tensor> silh_loss_fwd(const Tensor &silh, const Tensor &label
   TORCH_CHECK(W > 0, "silh_loss_fwd: W > 0");
   const SilhLossArgs a = silh_loss_check(silh, B, W, labels, class_w, gamma, conf);
   DeviceGuard g(silh.device());
-  Tensor loss = f32({B, W * W}, silh), k = f32({B, W * W}, silh);
+  auto [loss, k] = silh_loss_outputs(silh, B, W);
   ok(smplr_silh_loss_fwd(fp(silh), a.labels, a.class_w, (float)gamma, (int)B, (int)W, fpm(loss), fpm(k), a.conf, cur_stream()),
      "smplr_silh_loss_fwd");
   return {loss, k};
 }
 std::tuple<Tensor, Tensor> silh_loss_fwd_meta(const Tensor &silh, const Tensor &, const c10::optional<Tensor> &, double,
                                               const c10::optional<Tensor> &) {
-  const int64_t B = silh.size(0), W = silh.size(1);
-  return {at::empty({B, W * W}, silh.options()), at::empty({B, W * W}, silh.options())};
+  return silh_loss_outputs(silh, silh.size(0), silh.size(1));
 }
 // -> silh (B,W,W,2), arg (B,W,W) int32, loss, k (B, W*W); hint (B,W,W) or None as smplr_silh_fwd_hint takes it
 std::tuple<Tensor, Tensor, Tensor, Tensor> silh_fwd_loss(const Tensor &proj, const c10::optional<Tensor> &hint, const Tensor &labels,
@@ -264,8 +277,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> silh_fwd_loss(const Tensor &proj, con
     same_device(proj, {{"hint", &*hint}});
   }
   DeviceGuard g(proj.device());
-  Tensor silh = f32({B, W, W, 2}, proj), sarg = at::empty({B, W, W}, proj.options().dtype(at::kInt));
-  Tensor loss = f32({B, W * W}, proj), k = f32({B, W * W}, proj);
+  auto [silh, sarg] = silh_outputs(proj, B, W);
+  auto [loss, k] = silh_loss_outputs(proj, B, W);
   Tensor ws = bytes(smplr_silh_workspace((int)B, (int)VP, (int)W), proj);
   ok(smplr_silh_fwd_loss(fp(proj), hint ? fp(*hint) : nullptr, a.labels, a.class_w, (float)gamma, (int)B, (int)VP, (int)W,
                          fpm(silh), sarg.data_ptr<int32_t>(), fpm(loss), fpm(k), a.conf, ws.data_ptr(), cur_stream()),
@@ -275,30 +288,17 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> silh_fwd_loss(const Tensor &proj, con
 std::tuple<Tensor, Tensor, Tensor, Tensor> silh_fwd_loss_meta(const Tensor &proj, const c10::optional<Tensor> &, const Tensor &,
                                                               const c10::optional<Tensor> &, double, int64_t W,
                                                               const c10::optional<Tensor> &) {
-  const int64_t B = proj.size(0);
-  return {at::empty({B, W, W, 2}, proj.options()), at::empty({B, W, W}, proj.options().dtype(at::kInt)),
-          at::empty({B, W * W}, proj.options()), at::empty({B, W * W}, proj.options())};
+  return std::tuple_cat(silh_outputs(proj, proj.size(0), W), silh_loss_outputs(proj, proj.size(0), W));
 }
 Tensor silh_loss_bwd(const Tensor &dloss, const Tensor &k, const Tensor &silh, const Tensor &sarg, const Tensor &proj,
                      bool deterministic) {
-  dev_f32(dloss, "dloss");
-  dev_f32(k, "k");
-  dev_f32(silh, "silh");
-  dev_typed(sarg, at::kInt, "arg");
-  dev_f32(proj, "proj");
-  TORCH_CHECK(proj.dim() == 3 && proj.size(2) == 3, "proj must be (B, VP, 3)");
-  TORCH_CHECK(silh.dim() == 4 && silh.size(0) == proj.size(0) && silh.size(1) == silh.size(2) && silh.size(3) == 2,
-              "silh must be (B,W,W,2) as silh_fwd_loss returned it");
-  const int64_t B = proj.size(0), VP = proj.size(1), W = silh.size(1);
-  TORCH_CHECK(dloss.dim() == 2 && dloss.size(0) == B && dloss.size(1) == W * W, "dloss must be (B, W*W)");
+  const SilhDims d = silh_bwd_check({{"dloss", &dloss}, {"k", &k}}, silh, sarg, proj, "silh_fwd_loss");
+  TORCH_CHECK(dloss.dim() == 2 && dloss.size(0) == d.B && dloss.size(1) == d.W * d.W, "dloss must be (B, W*W)");
   TORCH_CHECK(k.sizes() == dloss.sizes(), "k must have dloss' shape");
-  TORCH_CHECK(sarg.dim() == 3 && sarg.size(0) == B && sarg.size(1) == W && sarg.size(2) == W,
-              "arg must be (B,W,W) int32 as silh_fwd_loss returned it");
-  same_device(proj, {{"dloss", &dloss}, {"k", &k}, {"silh", &silh}, {"arg", &sarg}});
   DeviceGuard g(proj.device());
-  Tensor dproj = f32({B, VP, 3}, proj);
-  ok(smplr_silh_loss_bwd(fp(dloss), fp(k), fp(silh), sarg.data_ptr<int32_t>(), fp(proj), (int)B, (int)VP, (int)W, fpm(dproj),
-                         deterministic ? 1 : 0, cur_stream()), "smplr_silh_loss_bwd");
+  Tensor dproj = f32({d.B, d.VP, 3}, proj);
+  ok(smplr_silh_loss_bwd(fp(dloss), fp(k), fp(silh), sarg.data_ptr<int32_t>(), fp(proj), (int)d.B, (int)d.VP, (int)d.W,
+                         fpm(dproj), deterministic ? 1 : 0, cur_stream()), "smplr_silh_loss_bwd");
   return dproj;
 }
 Tensor silh_loss_bwd_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &proj, bool) {

@@ -306,6 +306,34 @@ def test_known_answers_in_every_form(kind):
     assert seen == ({0, 3} if kind == "w1" else {0, 1, 2, 3})
 
 
+def test_deterministic_scale_scans_every_entry_of_dsilh():
+    """A known answer for silh_bwd_kernel<true>'s scale rule, the one place where it differs from silh_loss_bwd_kernel on
+    purpose: the maximum is taken over all 2 W^2 entries of |dsilh|, not over the pixels' g = dsilh[1] - dsilh[0].  One
+    pixel holds (2^40, 2^40): its g is exactly 0 and it contributes nothing, but frexp(2^40) gives eg = 41, W^2 = 256
+    gives terms = 8, so every term is rounded to 2^-(60 - 41 - 8) = 2^-11 (a scan of |g| would round to about 2^-49)."""
+    from ilps_amd import ops
+    from oracle import np_oracle as o
+    W, VP = 16, 64
+    rng = np.random.default_rng(41)
+    p = np.zeros((1, VP, 3), np.float32)
+    p[0, :, :2] = rng.uniform(0.0, W - 1.0, (VP, 2))
+    g = rng.normal(0.0, 1.0, (1, W, W, 2)).astype(np.float32)
+    g[0, 5, 9] = 2.0 ** 40
+    proj = t(p)
+    silh, arg = ops._silh_fwd(proj, W)
+    got = ops._silh_bwd(t(g), silh, arg, proj, W, True).cpu().numpy().astype(np.float64)
+    a = arg.cpu().numpy()
+    assert np.all(got * 2.0 ** 11 == np.rint(got * 2.0 ** 11)), "an element is no multiple of 2^-11"
+    assert np.any(got != 0)
+    want, abs_sum = o.silhouette_vjp(p.astype(np.float64), g, W, a)
+    count = np.bincount(a[0][a[0] >= 0], minlength=VP)
+    bar = count[None, :, None] * 2.0 ** -12 + VJP_C * abs_sum + VJP_FLOOR
+    ratio = float((np.abs(got[..., :2] - want[..., :2]) / bar).max())
+    print("deterministic scale: %d vertices win pixels, dproj worst err/bar %.3g (bar: 2^-12 per pixel won + 2^-18 sum|term|)"
+          % (int((count > 0).sum()), ratio))
+    assert np.all(got[..., 2] == 0) and ratio <= 1.0, "gradient error %.3g x the bar" % ratio
+
+
 # ------------------------------------------------------------------------------------------------ NaN positions
 def nan_runs(p48, p64, fill):
     """The forms for a mesh given at W = 48 and at W = 64: px, fused<true> (padded), brute (padded), fused<false>,
