@@ -616,6 +616,13 @@ int smplr_prelu_fwd(const float *x, const float *w, long long N, int C, int HW, 
 size_t smplr_prelu_bwd_workspace(long long N, int C, int HW);
 int smplr_prelu_bwd(const float *x, const float *w, const float *gy, long long N, int C, int HW,
                     float *gx, float *gw, void *workspace, void *stream);
+/* The same on bf16 tensors (smplr_prelu_fwd_bf16 / smplr_prelu_bwd_bf16): x, y, gy, gx are bfloat16 (2-byte
+ * elements), w and gw stay fp32.  An element is widened to fp32 (exact), the expressions above run in fp32 and the
+ * result is rounded once on store: to nearest even, NaN stays NaN, +-Inf stays +-Inf.  Same sizes, same workspace,
+ * same refusals.                                                                                  */
+int smplr_prelu_fwd_bf16(const void *x, const float *w, long long N, int C, int HW, void *y, void *stream);
+int smplr_prelu_bwd_bf16(const void *x, const float *w, const void *gy, long long N, int C, int HW,
+                         void *gx, float *gw, void *workspace, void *stream);
 
 /* ---- BatchNormalization (+ PReLU) of the ENet encoder, training mode:
  *      encoders/encoder_enet_simple.py:19-21,35-37,48-50,56-58,76 ---------- */
@@ -648,6 +655,29 @@ int smplr_bn_res_bwd(const float *x, const float *gamma, const float *beta, cons
                      const float *save_rstd, const float *dout, long long N, int C, int HW,
                      float *dx, float *dother, float *dgamma, float *dbeta, float *dslope,
                      void *workspace, void *stream);
+
+/* The four calls above on bf16 tensors: x, other, z / out, dz / dout, dx and dother are bfloat16 (2-byte elements);
+ * gamma, beta, slope, plane_scale, the running and the saved statistics, dgamma, dbeta, dslope and the workspace stay
+ * fp32, and smplr_bn_workspace() sizes the workspace for both.  An element is widened to fp32 (exact), all arithmetic
+ * is the fp32 calls', and z / out, dx, dother are rounded once on store (to nearest even; NaN and +-Inf stay).  The
+ * statistics are those of the bf16 values of x.                                                                  */
+int smplr_bn_fwd_bf16(const void *x, const float *gamma, const float *beta, const float *slope,
+                      long long N, int C, int HW, float eps, float momentum,
+                      float *running_mean, float *running_var, void *z, float *save_mean, float *save_rstd,
+                      void *workspace, void *stream);
+int smplr_bn_bwd_bf16(const void *x, const float *gamma, const float *beta, const float *slope,
+                      const float *save_mean, const float *save_rstd, const void *dz,
+                      long long N, int C, int HW, void *dx, float *dgamma, float *dbeta, float *dslope,
+                      void *workspace, void *stream);
+int smplr_bn_res_fwd_bf16(const void *x, const float *gamma, const float *beta, const float *plane_scale,
+                          const void *other, const float *slope, long long N, int C, int HW, float eps,
+                          float momentum, float *running_mean, float *running_var, void *out,
+                          float *save_mean, float *save_rstd, void *workspace, void *stream);
+int smplr_bn_res_bwd_bf16(const void *x, const float *gamma, const float *beta, const float *plane_scale,
+                          const void *other, const float *slope, const float *save_mean,
+                          const float *save_rstd, const void *dout, long long N, int C, int HW,
+                          void *dx, void *dother, float *dgamma, float *dbeta, float *dslope,
+                          void *workspace, void *stream);
 
 #ifdef __cplusplus
 }

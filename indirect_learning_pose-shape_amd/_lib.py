@@ -106,6 +106,13 @@ SIGNATURES = {
     "smplr_bn_bwd": (c_int, [P, P, P, P, P, P, P, c_longlong, I, I, P, P, P, P, P, P]),
     "smplr_bn_res_fwd": (c_int, [P, P, P, P, P, P, c_longlong, I, I, c_float, c_float, P, P, P, P, P, P, P]),
     "smplr_bn_res_bwd": (c_int, [P, P, P, P, P, P, P, P, P, c_longlong, I, I, P, P, P, P, P, P, P]),
+    # the bf16 twins of the six encoder calls: the same argument lists, the streamed tensors bfloat16
+    "smplr_prelu_fwd_bf16": (c_int, [P, P, c_longlong, I, I, P, P]),
+    "smplr_prelu_bwd_bf16": (c_int, [P, P, P, c_longlong, I, I, P, P, P, P]),
+    "smplr_bn_fwd_bf16": (c_int, [P, P, P, P, c_longlong, I, I, c_float, c_float, P, P, P, P, P, P, P]),
+    "smplr_bn_bwd_bf16": (c_int, [P, P, P, P, P, P, P, c_longlong, I, I, P, P, P, P, P, P]),
+    "smplr_bn_res_fwd_bf16": (c_int, [P, P, P, P, P, P, c_longlong, I, I, c_float, c_float, P, P, P, P, P, P, P]),
+    "smplr_bn_res_bwd_bf16": (c_int, [P, P, P, P, P, P, P, P, P, c_longlong, I, I, P, P, P, P, P, P, P]),
 }
 
 _lib = None

@@ -6,34 +6,58 @@
 // 1.16 ms per call, 67 calls per step).  Here one pass reads x and dy, writes dx and keeps the
 // slope gradient in registers: a workgroup owns one (image, channel) plane chunk, reduces its
 // sum and stores ONE partial; a second kernel adds the partials of a channel in a fixed order.
-// NCHW, fp32.  HBM-bound: forward 8 B/element, backward 12 B/element.
+// NCHW.  HBM-bound: forward 8 B/element, backward 12 B/element in fp32, half of that in bf16.
+// x, y, gy and gx are fp32 or bf16 (the element type T of plane_walk.h: loaded into fp32, the product a * x taken in
+// fp32 and rounded once on store); the slope, its gradient and the partials are fp32 whatever T is.  One body per
+// kernel over T with two entry points, prelu_* for fp32 and preluh_* for bf16 (names of their own, as in norm.hip).
 #include "plane_walk.h"
 
 namespace smplr {
 
-__global__ __launch_bounds__(PW_T) void prelu_fwd_kernel(const float *__restrict__ x, const float *__restrict__ w,
-                                                         int C, int HW, int chunks, float *__restrict__ y) {
+template <typename T>
+__device__ __forceinline__ void prelu_fwd_body(const T *__restrict__ x, const float *__restrict__ w, int C, int HW,
+                                               int chunks, T *__restrict__ y) {
   const PlaneChunk pc = plane_chunk(C, HW, chunks);
   const float a = w[pc.c];
-  const float *in[1] = {x};
-  float *out[1] = {y};
-  plane_walk<1, 1>(pc, HW, in, out, [&](const float *v, float *o) { o[0] = v[0] > 0.f ? v[0] : a * v[0]; });
+  const T *in[1] = {x};
+  T *out[1] = {y};
+  plane_walk<T, 1, 1>(pc, HW, in, out, [&](const float *v, float *o) { o[0] = v[0] > 0.f ? v[0] : a * v[0]; });
 }
 
-__global__ __launch_bounds__(PW_T) void prelu_bwd_kernel(const float *__restrict__ x, const float *__restrict__ w,
-                                                         const float *__restrict__ gy, int C, int HW, int chunks,
-                                                         float *__restrict__ gx, float *__restrict__ part) {
+template <typename T>
+__device__ __forceinline__ void prelu_bwd_body(const T *__restrict__ x, const float *__restrict__ w,
+                                               const T *__restrict__ gy, int C, int HW, int chunks, T *__restrict__ gx,
+                                               float *__restrict__ part) {
   __shared__ float red[12];
   const PlaneChunk pc = plane_chunk(C, HW, chunks);
   const float a = w[pc.c];
-  const float *in[2] = {x, gy};
-  float *out[1] = {gx};
+  const T *in[2] = {x, gy};
+  T *out[1] = {gx};
   float s = 0.f;
-  plane_walk<2, 1>(pc, HW, in, out, [&](const float *v, float *o) {
+  plane_walk<T, 2, 1>(pc, HW, in, out, [&](const float *v, float *o) {
     o[0] = v[0] > 0.f ? v[1] : a * v[1];
     s += v[0] > 0.f ? 0.f : v[1] * v[0];
   });
   block_store3(s, 0.f, 0.f, red, part + blockIdx.x, 1);
+}
+
+__global__ __launch_bounds__(PW_T) void prelu_fwd_kernel(const float *__restrict__ x, const float *__restrict__ w,
+                                                         int C, int HW, int chunks, float *__restrict__ y) {
+  prelu_fwd_body(x, w, C, HW, chunks, y);
+}
+__global__ __launch_bounds__(PW_T) void preluh_fwd_kernel(const bf16 *__restrict__ x, const float *__restrict__ w,
+                                                          int C, int HW, int chunks, bf16 *__restrict__ y) {
+  prelu_fwd_body(x, w, C, HW, chunks, y);
+}
+__global__ __launch_bounds__(PW_T) void prelu_bwd_kernel(const float *__restrict__ x, const float *__restrict__ w,
+                                                         const float *__restrict__ gy, int C, int HW, int chunks,
+                                                         float *__restrict__ gx, float *__restrict__ part) {
+  prelu_bwd_body(x, w, gy, C, HW, chunks, gx, part);
+}
+__global__ __launch_bounds__(PW_T) void preluh_bwd_kernel(const bf16 *__restrict__ x, const float *__restrict__ w,
+                                                          const bf16 *__restrict__ gy, int C, int HW, int chunks,
+                                                          bf16 *__restrict__ gx, float *__restrict__ part) {
+  prelu_bwd_body(x, w, gy, C, HW, chunks, gx, part);
 }
 
 // gw[c] = sum over images n and chunks of part[(n*C + c)*chunks + chunk], in index order
@@ -50,19 +74,56 @@ __global__ __launch_bounds__(64) void prelu_bwd_reduce_kernel(const float *__res
   if (lane == 0) gw[c] = s;
 }
 
+// the error of a launch, with the entry point and which of its launches it was
+static int prelu_launched(const char *fn, const char *stage) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) set_error("%s(%s): launch failed: %s", fn, stage, hipGetErrorString(e));
+  return (int)e;
+}
+
+// the launches of smplr_prelu_fwd / smplr_prelu_bwd and of their bf16 twins
+template <typename T>
+static int prelu_fwd_impl(const char *fn, void (*kernel)(const T *, const float *, int, int, int, T *), const T *x,
+                          const float *w, long long N, int C, int HW, T *y, void *stream) {
+  SMPLR_REQUIRE(plane_sizes_ok(N, C, HW), "%s: bad sizes N=%lld C=%d HW=%d", fn, N, C, HW);
+  if (N == 0) return 0;
+  SMPLR_REQUIRE(x && w && y, "%s: null pointer", fn);
+  const int chunks = plane_chunks(HW);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(N * C * chunks)), dim3(PW_T), 0, as_stream(stream), x, w, C, HW, chunks, y);
+  return prelu_launched(fn, "main");
+}
+
+template <typename T>
+static int prelu_bwd_impl(const char *fn, void (*kernel)(const T *, const float *, const T *, int, int, int, T *, float *),
+                          const T *x, const float *w, const T *gy, long long N, int C, int HW, T *gx, float *gw,
+                          void *workspace, void *stream) {
+  SMPLR_REQUIRE(plane_sizes_ok(N, C, HW), "%s: bad sizes N=%lld C=%d HW=%d", fn, N, C, HW);
+  SMPLR_REQUIRE(gw != nullptr, "%s: null gw", fn);
+  if (N == 0) {
+    SMPLR_HIP(hipMemsetAsync(gw, 0, (size_t)C * sizeof(float), as_stream(stream)));
+    return 0;
+  }
+  SMPLR_REQUIRE(x && w && gy && gx && workspace, "%s: null pointer", fn);
+  const int chunks = plane_chunks(HW);
+  float *part = reinterpret_cast<float *>(workspace);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(N * C * chunks)), dim3(PW_T), 0, as_stream(stream), x, w, gy, C, HW, chunks,
+                     gx, part);
+  if (int e = prelu_launched(fn, "main")) return e;
+  hipLaunchKernelGGL(prelu_bwd_reduce_kernel, dim3(C), dim3(64), 0, as_stream(stream), part, N, C, chunks, gw);
+  return prelu_launched(fn, "reduce");
+  return 0;
+}
+
 }  // namespace smplr
 
 extern "C" int smplr_prelu_fwd(const float *x, const float *w, long long N, int C, int HW, float *y, void *stream) {
-  using namespace smplr;
-  SMPLR_REQUIRE(plane_sizes_ok(N, C, HW),
-                "smplr_prelu_fwd: bad sizes N=%lld C=%d HW=%d", N, C, HW);
-  if (N == 0) return 0;
-  SMPLR_REQUIRE(x && w && y, "smplr_prelu_fwd: null pointer");
-  const int chunks = plane_chunks(HW);
-  hipLaunchKernelGGL(prelu_fwd_kernel, dim3((unsigned)(N * C * chunks)), dim3(PW_T), 0, as_stream(stream), x, w, C, HW,
-                     chunks, y);
-  SMPLR_LAUNCH_CHECK("smplr_prelu_fwd");
-  return 0;
+  return smplr::prelu_fwd_impl("smplr_prelu_fwd", smplr::prelu_fwd_kernel, x, w, N, C, HW, y, stream);
+}
+
+extern "C" int smplr_prelu_fwd_bf16(const void *x, const float *w, long long N, int C, int HW, void *y, void *stream) {
+  using smplr::bf16;
+  return smplr::prelu_fwd_impl("smplr_prelu_fwd_bf16", smplr::preluh_fwd_kernel, (const bf16 *)x, w, N, C, HW, (bf16 *)y,
+                               stream);
 }
 
 extern "C" size_t smplr_prelu_bwd_workspace(long long N, int C, int HW) {
@@ -72,21 +133,12 @@ extern "C" size_t smplr_prelu_bwd_workspace(long long N, int C, int HW) {
 
 extern "C" int smplr_prelu_bwd(const float *x, const float *w, const float *gy, long long N, int C, int HW, float *gx,
                                float *gw, void *workspace, void *stream) {
-  using namespace smplr;
-  SMPLR_REQUIRE(plane_sizes_ok(N, C, HW),
-                "smplr_prelu_bwd: bad sizes N=%lld C=%d HW=%d", N, C, HW);
-  SMPLR_REQUIRE(gw != nullptr, "smplr_prelu_bwd: null gw");
-  if (N == 0) {
-    SMPLR_HIP(hipMemsetAsync(gw, 0, (size_t)C * sizeof(float), as_stream(stream)));
-    return 0;
-  }
-  SMPLR_REQUIRE(x && w && gy && gx && workspace, "smplr_prelu_bwd: null pointer");
-  const int chunks = plane_chunks(HW);
-  float *part = reinterpret_cast<float *>(workspace);
-  hipLaunchKernelGGL(prelu_bwd_kernel, dim3((unsigned)(N * C * chunks)), dim3(PW_T), 0, as_stream(stream), x, w, gy, C,
-                     HW, chunks, gx, part);
-  SMPLR_LAUNCH_CHECK("smplr_prelu_bwd");
-  hipLaunchKernelGGL(prelu_bwd_reduce_kernel, dim3(C), dim3(64), 0, as_stream(stream), part, N, C, chunks, gw);
-  SMPLR_LAUNCH_CHECK("smplr_prelu_bwd(reduce)");
-  return 0;
+  return smplr::prelu_bwd_impl("smplr_prelu_bwd", smplr::prelu_bwd_kernel, x, w, gy, N, C, HW, gx, gw, workspace, stream);
+}
+
+extern "C" int smplr_prelu_bwd_bf16(const void *x, const float *w, const void *gy, long long N, int C, int HW, void *gx,
+                                    float *gw, void *workspace, void *stream) {
+  using smplr::bf16;
+  return smplr::prelu_bwd_impl("smplr_prelu_bwd_bf16", smplr::preluh_bwd_kernel, (const bf16 *)x, w, (const bf16 *)gy, N,
+                               C, HW, (bf16 *)gx, gw, workspace, stream);
 }

@@ -12,7 +12,13 @@
 //   backward: with x_hat and y recomputed from x (nothing but mean / rstd is saved),
 //             dy = dz (y > 0 ? 1 : a);  partial sums of dy, dy x_hat, dz y [y <= 0] -> finalize ->
 //             dx = gamma rstd (dy - mean(dy) - x_hat mean(dy x_hat)).
-// NCHW, fp32, HBM-bound: forward 3 passes over the tensor, backward 5 (the unfused pair: 5 and 8).
+// NCHW, HBM-bound: forward 3 passes over the tensor, backward 5 (the unfused pair: 5 and 8).
+// The tensors that are streamed (x, other, z / out, dz / dout, dx, dother) are fp32 or bf16 - the element type T of
+// plane_walk.h: loaded into fp32, stored with one rounding - and everything per channel or per plane (gamma, beta,
+// slope, plane_scale, the running and the saved statistics, dgamma, dbeta, dslope, the workspace partials) is fp32
+// whatever T is, so the finalize kernels and the workspace sizes serve both.  Every kernel below is ONE body over T
+// with two entry points: bn_* for fp32 and bnh_* for bf16 (names of their own, not template arguments of bn_*:
+// tests/test_encoder_regimes_cpu.py counts the library's bn_* kernels by name).
 // Every reduction has a fixed order (no atomics): results are run-to-run identical.
 // The sums are taken about the pivot K because E[x^2] - mean^2 on fp32 chunk sums loses mean^2 / var of its digits,
 // and a channel whose offset is large against its spread is ordinary after a biased convolution.  About K the loss is
@@ -28,24 +34,33 @@ namespace smplr {
 
 // part[(plane * chunks + chunk) * 2 + {0, 1}] = sum (x - K), sum (x - K)^2 of the chunk, K = x[0, c, 0]: the pivot
 // of channel c, which every workgroup of the channel (and the finalize) reads from the same place.
-// (Its own loop, not plane_walk's: the float4 path adds (x + y) + (z + w), and that association is in the result's bits.)
-__global__ __launch_bounds__(PW_T) void bn_stats_kernel(const float *__restrict__ x, int C, int HW, int chunks,
-                                                        float *__restrict__ part) {
+// (Its own loop, not plane_walk's: the vector path adds a vector's elements as pw_tree_sum does - a float4's
+// (x + y) + (z + w), the eight of a bf16 vector ((a + b) + (c + d)) + ((e + f) + (g + h)) - and that association is in
+// the result's bits.)
+template <typename T>
+__device__ __forceinline__ void bn_stats_body(const T *__restrict__ x, int C, int HW, int chunks, float *__restrict__ part) {
+  typedef PwElem<T> E;
+  constexpr int VN = E::VN;
   __shared__ float red[12];
   const PlaneChunk pc = plane_chunk(C, HW, chunks);
-  const float K = x[(size_t)pc.c * HW];
+  const float K = E::load(x[(size_t)pc.c * HW]);
   float s = 0.f, q = 0.f;
-  if (((HW | pc.e0) & 3) == 0) {
-    const float4 *xv = reinterpret_cast<const float4 *>(x + pc.base);
-    for (int i = pc.e0 / 4 + threadIdx.x; i < pc.e1 / 4; i += PW_T) {
-      float4 v = xv[i];
-      v.x -= K; v.y -= K; v.z -= K; v.w -= K;
-      s += (v.x + v.y) + (v.z + v.w);
-      q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+  if (((HW | pc.e0) & (VN - 1)) == 0) {
+    const typename E::Vec *xv = reinterpret_cast<const typename E::Vec *>(x + pc.base);
+    for (int i = pc.e0 / VN + threadIdx.x; i < pc.e1 / VN; i += PW_T) {
+      const typename E::Vec raw = xv[i];
+      float v[VN], vv[VN];
+#pragma unroll
+      for (int j = 0; j < VN; ++j) {
+        v[j] = E::get(raw, j) - K;
+        vv[j] = v[j] * v[j];
+      }
+      s += pw_tree_sum<VN>(v);
+      q += pw_tree_sum<VN>(vv);
     }
   } else {
     for (int i = pc.e0 + threadIdx.x; i < pc.e1; i += PW_T) {
-      const float v = x[pc.base + i] - K;
+      const float v = E::load(x[pc.base + i]) - K;
       s += v;
       q += v * v;
     }
@@ -53,8 +68,18 @@ __global__ __launch_bounds__(PW_T) void bn_stats_kernel(const float *__restrict_
   block_store3(s, q, 0.f, red, part + (size_t)blockIdx.x * 2, 2);
 }
 
+__global__ __launch_bounds__(PW_T) void bn_stats_kernel(const float *__restrict__ x, int C, int HW, int chunks,
+                                                        float *__restrict__ part) {
+  bn_stats_body(x, C, HW, chunks, part);
+}
+__global__ __launch_bounds__(PW_T) void bnh_stats_kernel(const bf16 *__restrict__ x, int C, int HW, int chunks,
+                                                         float *__restrict__ part) {
+  bn_stats_body(x, C, HW, chunks, part);
+}
+
 // per channel: the chunk sums of all images in index order (thread-strided, then a fixed tree), in double
-__global__ __launch_bounds__(PW_T) void bn_finalize_kernel(const float *__restrict__ x, int HW,
+// (x: fp32, or with x_bf16 the bf16 tensor - read for the channel's pivot only, so one kernel serves both)
+__global__ __launch_bounds__(PW_T) void bn_finalize_kernel(const void *__restrict__ x, int x_bf16, int HW,
                                                            const float *__restrict__ part, long long N, int C,
                                                            int chunks, long long M, float eps, float momentum,
                                                            float *__restrict__ mean, float *__restrict__ rstd,
@@ -82,7 +107,9 @@ __global__ __launch_bounds__(PW_T) void bn_finalize_kernel(const float *__restri
   }
   if (threadIdx.x == 0) {
     const double d = rs[0] / (double)M;                 // mean - K: small against the spread unless K is an outlier
-    const double m = (double)x[(size_t)c * HW] + d;
+    const float K = x_bf16 ? PwElem<bf16>::load(static_cast<const bf16 *>(x)[(size_t)c * HW])
+                           : static_cast<const float *>(x)[(size_t)c * HW];
+    const double m = (double)K + d;
     double var = rq[0] / (double)M - d * d;             // biased (population) variance normalises
     if (var < 0.0) var = 0.0;
     mean[c] = (float)m;
@@ -136,30 +163,39 @@ struct BnElem {
   }
 };
 
+// The two entry points of bn_<STEM>_body<T, FORM>: bn_<STEM>_kernel<FORM> for fp32 and bnh_<STEM>_kernel<FORM> for bf16
+// (PARAMS(T): the kernel's parameter list for element type T; ARGS: the same names, as the body takes them).
+#define SMPLR_BN_ENTRY(STEM, PARAMS, ARGS)                                                                  \
+  template <BnForm FORM>                                                                                    \
+  __global__ __launch_bounds__(PW_T) void bn_##STEM##_kernel PARAMS(float) { bn_##STEM##_body<float, FORM> ARGS; } \
+  template <BnForm FORM>                                                                                    \
+  __global__ __launch_bounds__(PW_T) void bnh_##STEM##_kernel PARAMS(bf16) { bn_##STEM##_body<bf16, FORM> ARGS; }
+
 // other (and dother below): the RES form's, NULL otherwise
-template <BnForm FORM>
-__global__ __launch_bounds__(PW_T) void bn_apply_kernel(BnArgs p, const float *__restrict__ x,
-                                                        const float *__restrict__ other, float *__restrict__ z) {
+template <typename T, BnForm FORM>
+__device__ __forceinline__ void bn_apply_body(const BnArgs &p, const T *__restrict__ x, const T *__restrict__ other,
+                                              T *__restrict__ z) {
   const PlaneChunk pc = plane_chunk(p.C, p.HW, p.chunks);
   const BnElem<FORM> e(p, pc);
-  const float *in[2] = {x, other};
-  float *out[1] = {z};
-  plane_walk<FORM == RES ? 2 : 1, 1>(pc, p.HW, in, out,
-                                     [&](const float *v, float *o) { o[0] = e.fwd(v[0], v[FORM == RES]); });
+  const T *in[2] = {x, other};
+  T *out[1] = {z};
+  plane_walk<T, FORM == RES ? 2 : 1, 1>(pc, p.HW, in, out,
+                                        [&](const float *v, float *o) { o[0] = e.fwd(v[0], v[FORM == RES]); });
 }
+#define BN_APPLY_PARAMS(T) (BnArgs p, const T *__restrict__ x, const T *__restrict__ other, T *__restrict__ z)
+SMPLR_BN_ENTRY(apply, BN_APPLY_PARAMS, (p, x, other, z))
 
 // part[(plane * chunks + chunk) * 3 + {0, 1, 2}] = sum dy, sum dy x_hat, sum dz pre [pre <= 0]
-template <BnForm FORM>
-__global__ __launch_bounds__(PW_T) void bn_bwd_stats_kernel(BnArgs p, const float *__restrict__ x,
-                                                            const float *__restrict__ other,
-                                                            const float *__restrict__ dz, float *__restrict__ part) {
+template <typename T, BnForm FORM>
+__device__ __forceinline__ void bn_bwd_stats_body(const BnArgs &p, const T *__restrict__ x, const T *__restrict__ other,
+                                                  const T *__restrict__ dz, float *__restrict__ part) {
   __shared__ float red[12];
   const PlaneChunk pc = plane_chunk(p.C, p.HW, p.chunks);
   const BnElem<FORM> e(p, pc);
   constexpr int NIN = FORM == RES ? 3 : 2;
-  const float *in[3] = {x, FORM == RES ? other : dz, dz};     // x, (RES: other,) dz
+  const T *in[3] = {x, FORM == RES ? other : dz, dz};         // x, (RES: other,) dz
   float s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  plane_walk<NIN, 0>(pc, p.HW, in, nullptr, [&](const float *v, float *) {
+  plane_walk<T, NIN, 0>(pc, p.HW, in, nullptr, [&](const float *v, float *) {
     float xh, dpre, dy, da;
     e.bwd(v[0], v[1], v[NIN - 1], xh, dpre, dy, da);
     s1 += dy;
@@ -168,6 +204,9 @@ __global__ __launch_bounds__(PW_T) void bn_bwd_stats_kernel(BnArgs p, const floa
   });
   block_store3(s1, s2, s3, red, part + (size_t)blockIdx.x * 3, 3);
 }
+#define BN_BWD_STATS_PARAMS(T) \
+  (BnArgs p, const T *__restrict__ x, const T *__restrict__ other, const T *__restrict__ dz, float *__restrict__ part)
+SMPLR_BN_ENTRY(bwd_stats, BN_BWD_STATS_PARAMS, (p, x, other, dz, part))
 
 __global__ __launch_bounds__(PW_T) void bn_bwd_finalize_kernel(const float *__restrict__ part, long long N, int C,
                                                                int chunks, long long M,
@@ -204,31 +243,43 @@ __global__ __launch_bounds__(PW_T) void bn_bwd_finalize_kernel(const float *__re
   }
 }
 
-template <BnForm FORM>
-__global__ __launch_bounds__(PW_T) void bn_bwd_apply_kernel(BnArgs p, const float *__restrict__ x,
-                                                            const float *__restrict__ other,
-                                                            const float *__restrict__ dz, float *__restrict__ dx,
-                                                            float *__restrict__ dother) {
+template <typename T, BnForm FORM>
+__device__ __forceinline__ void bn_bwd_apply_body(const BnArgs &p, const T *__restrict__ x, const T *__restrict__ other,
+                                                  const T *__restrict__ dz, T *__restrict__ dx, T *__restrict__ dother) {
   const PlaneChunk pc = plane_chunk(p.C, p.HW, p.chunks);
   const BnElem<FORM> e(p, pc);
   constexpr int NIN = FORM == RES ? 3 : 2;
-  const float *in[3] = {x, FORM == RES ? other : dz, dz};
-  float *out[2] = {dx, dother};
+  const T *in[3] = {x, FORM == RES ? other : dz, dz};
+  T *out[2] = {dx, dother};
   const float k1 = p.k12[2 * pc.c], k2 = p.k12[2 * pc.c + 1];
-  plane_walk<NIN, FORM == RES ? 2 : 1>(pc, p.HW, in, out, [&](const float *v, float *o) {
+  plane_walk<T, NIN, FORM == RES ? 2 : 1>(pc, p.HW, in, out, [&](const float *v, float *o) {
     float xh, dpre, dy, da;
     e.bwd(v[0], v[1], v[NIN - 1], xh, dpre, dy, da);
     o[0] = e.sc * ((dy - k1) - xh * k2);
     if (FORM == RES) o[1] = dpre;
   });
 }
+#define BN_BWD_APPLY_PARAMS(T)                                                                                   \
+  (BnArgs p, const T *__restrict__ x, const T *__restrict__ other, const T *__restrict__ dz, T *__restrict__ dx, \
+   T *__restrict__ dother)
+SMPLR_BN_ENTRY(bwd_apply, BN_BWD_APPLY_PARAMS, (p, x, other, dz, dx, dother))
 
-// the instantiations by form
-static decltype(&bn_apply_kernel<BN>) const BN_APPLY[3] = {bn_apply_kernel<BN>, bn_apply_kernel<ACT>, bn_apply_kernel<RES>};
-static decltype(&bn_bwd_stats_kernel<BN>) const BN_BWD_STATS[3] = {bn_bwd_stats_kernel<BN>, bn_bwd_stats_kernel<ACT>,
-                                                                   bn_bwd_stats_kernel<RES>};
-static decltype(&bn_bwd_apply_kernel<BN>) const BN_BWD_APPLY[3] = {bn_bwd_apply_kernel<BN>, bn_bwd_apply_kernel<ACT>,
-                                                                   bn_bwd_apply_kernel<RES>};
+// the entry points by element type and form
+template <typename T>
+struct BnKernels;
+#define SMPLR_BN_TABLE(T, PRE)                                                                                       \
+  template <>                                                                                                        \
+  struct BnKernels<T> {                                                                                              \
+    static constexpr auto stats = PRE##_stats_kernel;                                                                \
+    static constexpr decltype(&PRE##_apply_kernel<BN>) apply[3] = {PRE##_apply_kernel<BN>, PRE##_apply_kernel<ACT>,  \
+                                                                   PRE##_apply_kernel<RES>};                         \
+    static constexpr decltype(&PRE##_bwd_stats_kernel<BN>) bwd_stats[3] = {                                          \
+        PRE##_bwd_stats_kernel<BN>, PRE##_bwd_stats_kernel<ACT>, PRE##_bwd_stats_kernel<RES>};                       \
+    static constexpr decltype(&PRE##_bwd_apply_kernel<BN>) bwd_apply[3] = {                                          \
+        PRE##_bwd_apply_kernel<BN>, PRE##_bwd_apply_kernel<ACT>, PRE##_bwd_apply_kernel<RES>};                       \
+  };
+SMPLR_BN_TABLE(float, bn)
+SMPLR_BN_TABLE(bf16, bnh)
 
 static int bn_launched(const char *fn, const char *stage) {
   const hipError_t e = hipGetLastError();
@@ -239,9 +290,10 @@ static int bn_launched(const char *fn, const char *stage) {
 static size_t bn_ws_floats(long long N, int C, int HW) { return (size_t)N * C * plane_chunks(HW) * 3 + (size_t)C * 2; }
 
 // smplr_bn_fwd (res = false: scale and other are NULL, slope may be) and smplr_bn_res_fwd
-static int bn_fwd_impl(const char *fn, bool res, const float *x, const float *gamma, const float *beta,
-                       const float *scale, const float *other, const float *slope, long long N, int C, int HW, float eps,
-                       float momentum, float *running_mean, float *running_var, float *z, float *save_mean,
+template <typename T>
+static int bn_fwd_impl(const char *fn, bool res, const T *x, const float *gamma, const float *beta,
+                       const float *scale, const T *other, const float *slope, long long N, int C, int HW, float eps,
+                       float momentum, float *running_mean, float *running_var, T *z, float *save_mean,
                        float *save_rstd, void *workspace, void *stream) {
   SMPLR_REQUIRE(plane_sizes_ok(N, C, HW) && eps > 0.0f, "%s: bad sizes N=%lld C=%d HW=%d eps=%g", fn, N, C, HW,
                 (double)eps);
@@ -252,19 +304,21 @@ static int bn_fwd_impl(const char *fn, bool res, const float *x, const float *ga
   const unsigned grid = (unsigned)(N * C * a.chunks);
   float *part = reinterpret_cast<float *>(workspace);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(bn_stats_kernel, dim3(grid), dim3(PW_T), 0, st, x, C, HW, a.chunks, part);
+  hipLaunchKernelGGL(BnKernels<T>::stats, dim3(grid), dim3(PW_T), 0, st, x, C, HW, a.chunks, part);
   if (int e = bn_launched(fn, "stats")) return e;
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(PW_T), 0, st, x, HW, part, N, C, a.chunks, N * (long long)HW, eps,
-                     momentum, save_mean, save_rstd, running_mean, running_var);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(PW_T), 0, st, static_cast<const void *>(x), (int)PwElem<T>::IS_BF16,
+                     HW, part, N, C, a.chunks, N * (long long)HW, eps, momentum, save_mean, save_rstd, running_mean,
+                     running_var);
   if (int e = bn_launched(fn, "finalize")) return e;
-  hipLaunchKernelGGL(BN_APPLY[res ? RES : slope ? ACT : BN], dim3(grid), dim3(PW_T), 0, st, a, x, other, z);
+  hipLaunchKernelGGL(BnKernels<T>::apply[res ? RES : slope ? ACT : BN], dim3(grid), dim3(PW_T), 0, st, a, x, other, z);
   return bn_launched(fn, "apply");
 }
 
 // smplr_bn_bwd (res = false: scale, other and dother are NULL, slope may be) and smplr_bn_res_bwd
-static int bn_bwd_impl(const char *fn, bool res, const float *x, const float *gamma, const float *beta,
-                       const float *scale, const float *other, const float *slope, const float *save_mean,
-                       const float *save_rstd, const float *dz, long long N, int C, int HW, float *dx, float *dother,
+template <typename T>
+static int bn_bwd_impl(const char *fn, bool res, const T *x, const float *gamma, const float *beta,
+                       const float *scale, const T *other, const float *slope, const float *save_mean,
+                       const float *save_rstd, const T *dz, long long N, int C, int HW, T *dx, T *dother,
                        float *dgamma, float *dbeta, float *dslope, void *workspace, void *stream) {
   SMPLR_REQUIRE(plane_sizes_ok(N, C, HW), "%s: bad sizes N=%lld C=%d HW=%d", fn, N, C, HW);
   SMPLR_REQUIRE(dgamma && dbeta && (dslope || !(res || slope)), "%s: null gradient output", fn);
@@ -283,12 +337,12 @@ static int bn_bwd_impl(const char *fn, bool res, const float *x, const float *ga
   float *part = reinterpret_cast<float *>(workspace);
   float *k12 = part + (size_t)N * C * chunks * 3;
   const BnArgs a{gamma, beta, slope, scale, save_mean, save_rstd, k12, C, HW, chunks};
-  hipLaunchKernelGGL(BN_BWD_STATS[form], dim3(grid), dim3(PW_T), 0, st, a, x, other, dz, part);
+  hipLaunchKernelGGL(BnKernels<T>::bwd_stats[form], dim3(grid), dim3(PW_T), 0, st, a, x, other, dz, part);
   if (int e = bn_launched(fn, "stats")) return e;
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(PW_T), 0, st, part, N, C, chunks, N * (long long)HW, dgamma,
                      dbeta, slope ? dslope : nullptr, k12);
   if (int e = bn_launched(fn, "finalize")) return e;
-  hipLaunchKernelGGL(BN_BWD_APPLY[form], dim3(grid), dim3(PW_T), 0, st, a, x, other, dz, dx, dother);
+  hipLaunchKernelGGL(BnKernels<T>::bwd_apply[form], dim3(grid), dim3(PW_T), 0, st, a, x, other, dz, dx, dother);
   return bn_launched(fn, "apply");
 }
 
@@ -304,14 +358,14 @@ size_t smplr_bn_workspace(long long N, int C, int HW) {
 int smplr_bn_fwd(const float *x, const float *gamma, const float *beta, const float *slope, long long N, int C,
                  int HW, float eps, float momentum, float *running_mean, float *running_var, float *z,
                  float *save_mean, float *save_rstd, void *workspace, void *stream) {
-  return smplr::bn_fwd_impl("smplr_bn_fwd", false, x, gamma, beta, nullptr, nullptr, slope, N, C, HW, eps, momentum,
+  return smplr::bn_fwd_impl<float>("smplr_bn_fwd", false, x, gamma, beta, nullptr, nullptr, slope, N, C, HW, eps, momentum,
                             running_mean, running_var, z, save_mean, save_rstd, workspace, stream);
 }
 
 int smplr_bn_bwd(const float *x, const float *gamma, const float *beta, const float *slope, const float *save_mean,
                  const float *save_rstd, const float *dz, long long N, int C, int HW, float *dx, float *dgamma,
                  float *dbeta, float *dslope, void *workspace, void *stream) {
-  return smplr::bn_bwd_impl("smplr_bn_bwd", false, x, gamma, beta, nullptr, nullptr, slope, save_mean, save_rstd, dz, N,
+  return smplr::bn_bwd_impl<float>("smplr_bn_bwd", false, x, gamma, beta, nullptr, nullptr, slope, save_mean, save_rstd, dz, N,
                             C, HW, dx, nullptr, dgamma, dbeta, dslope, workspace, stream);
 }
 
@@ -319,7 +373,7 @@ int smplr_bn_res_fwd(const float *x, const float *gamma, const float *beta, cons
                      const float *other, const float *slope, long long N, int C, int HW, float eps, float momentum,
                      float *running_mean, float *running_var, float *out, float *save_mean, float *save_rstd,
                      void *workspace, void *stream) {
-  return smplr::bn_fwd_impl("smplr_bn_res_fwd", true, x, gamma, beta, plane_scale, other, slope, N, C, HW, eps, momentum,
+  return smplr::bn_fwd_impl<float>("smplr_bn_res_fwd", true, x, gamma, beta, plane_scale, other, slope, N, C, HW, eps, momentum,
                             running_mean, running_var, out, save_mean, save_rstd, workspace, stream);
 }
 
@@ -327,8 +381,47 @@ int smplr_bn_res_bwd(const float *x, const float *gamma, const float *beta, cons
                      const float *other, const float *slope, const float *save_mean, const float *save_rstd,
                      const float *dout, long long N, int C, int HW, float *dx, float *dother, float *dgamma,
                      float *dbeta, float *dslope, void *workspace, void *stream) {
-  return smplr::bn_bwd_impl("smplr_bn_res_bwd", true, x, gamma, beta, plane_scale, other, slope, save_mean, save_rstd,
+  return smplr::bn_bwd_impl<float>("smplr_bn_res_bwd", true, x, gamma, beta, plane_scale, other, slope, save_mean, save_rstd,
                             dout, N, C, HW, dx, dother, dgamma, dbeta, dslope, workspace, stream);
+}
+
+// The bf16 twins: the streamed tensors are bf16 (void *: 2-byte elements), everything else as above.
+int smplr_bn_fwd_bf16(const void *x, const float *gamma, const float *beta, const float *slope, long long N, int C,
+                      int HW, float eps, float momentum, float *running_mean, float *running_var, void *z,
+                      float *save_mean, float *save_rstd, void *workspace, void *stream) {
+  using smplr::bf16;
+  return smplr::bn_fwd_impl<bf16>("smplr_bn_fwd_bf16", false, (const bf16 *)x, gamma, beta, nullptr, nullptr, slope, N, C,
+                                  HW, eps, momentum, running_mean, running_var, (bf16 *)z, save_mean, save_rstd, workspace,
+                                  stream);
+}
+
+int smplr_bn_bwd_bf16(const void *x, const float *gamma, const float *beta, const float *slope, const float *save_mean,
+                      const float *save_rstd, const void *dz, long long N, int C, int HW, void *dx, float *dgamma,
+                      float *dbeta, float *dslope, void *workspace, void *stream) {
+  using smplr::bf16;
+  return smplr::bn_bwd_impl<bf16>("smplr_bn_bwd_bf16", false, (const bf16 *)x, gamma, beta, nullptr, nullptr, slope,
+                                  save_mean, save_rstd, (const bf16 *)dz, N, C, HW, (bf16 *)dx, nullptr, dgamma, dbeta,
+                                  dslope, workspace, stream);
+}
+
+int smplr_bn_res_fwd_bf16(const void *x, const float *gamma, const float *beta, const float *plane_scale,
+                          const void *other, const float *slope, long long N, int C, int HW, float eps, float momentum,
+                          float *running_mean, float *running_var, void *out, float *save_mean, float *save_rstd,
+                          void *workspace, void *stream) {
+  using smplr::bf16;
+  return smplr::bn_fwd_impl<bf16>("smplr_bn_res_fwd_bf16", true, (const bf16 *)x, gamma, beta, plane_scale,
+                                  (const bf16 *)other, slope, N, C, HW, eps, momentum, running_mean, running_var,
+                                  (bf16 *)out, save_mean, save_rstd, workspace, stream);
+}
+
+int smplr_bn_res_bwd_bf16(const void *x, const float *gamma, const float *beta, const float *plane_scale,
+                          const void *other, const float *slope, const float *save_mean, const float *save_rstd,
+                          const void *dout, long long N, int C, int HW, void *dx, void *dother, float *dgamma,
+                          float *dbeta, float *dslope, void *workspace, void *stream) {
+  using smplr::bf16;
+  return smplr::bn_bwd_impl<bf16>("smplr_bn_res_bwd_bf16", true, (const bf16 *)x, gamma, beta, plane_scale,
+                                  (const bf16 *)other, slope, save_mean, save_rstd, (const bf16 *)dout, N, C, HW,
+                                  (bf16 *)dx, (bf16 *)dother, dgamma, dbeta, dslope, workspace, stream);
 }
 
 }  // extern "C"

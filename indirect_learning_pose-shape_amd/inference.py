@@ -5,17 +5,20 @@ from __future__ import annotations
 
 import torch
 
-from .model import FullModel
+from .training import regress
 
 
 @torch.no_grad()
-def predict_batch(smpl_model, decoder, images):
+def predict_batch(smpl_model, decoder, images, amp=None):
     """images (N,3,H,W) or (N,H,W,3) on the HIP device -> dict(smpl (N,86), verts (N,6890,3),
-    projects (N,V',3), segs (N,W,W,32) raw scores, seg_maps (N,W,W) int64 = argmax over channels)."""
+    projects (N,V',3), segs (N,W,W,32) raw scores, seg_maps (N,W,W) int64 = argmax over channels).
+    amp = "bf16": the encoder + regressor run under torch.autocast(bfloat16) (`training.amp_dtype`); the 86-vector and
+    everything the decoder makes of it stay fp32.  amp = None: fp32 throughout."""
     was_training = smpl_model.training
     smpl_model.eval()
     try:
-        out = FullModel(smpl_model, decoder, "all")(images)
+        param = regress(smpl_model, images, amp)               # (amp = None: smpl_model(images) itself)
+        out = dict(decoder(param), smpl=param)                 # what FullModel(smpl_model, decoder, "all") returns
     finally:
         smpl_model.train(was_training)
     return {"smpl": out["smpl"], "verts": out["verts"], "projects": out["projects"], "segs": out["seg"],
@@ -45,10 +48,10 @@ class GraphedPredictor:
     `predictor(images)` copies the images into the static input and returns views of the static outputs
     (valid until the next call).  `predictor.input` is that static input: whatever writes into it in place
     (`preprocess.load_images(frame, 256, ..., out=predictor.input)`) followed by `predictor.replay()` is the per-frame
-    path of predict_realtime.py:52-64 without the copy."""
+    path of predict_realtime.py:52-64 without the copy.  amp: as `predict_batch` takes it (the autocast is captured)."""
 
-    def __init__(self, smpl_model, decoder, example_images, warmup=3):
-        self.smpl_model, self.decoder = smpl_model, decoder
+    def __init__(self, smpl_model, decoder, example_images, warmup=3, amp=None):
+        self.smpl_model, self.decoder, self.amp = smpl_model, decoder, amp
         self._in = example_images.detach().clone()
         was_training = smpl_model.training
         smpl_model.eval()
@@ -57,12 +60,12 @@ class GraphedPredictor:
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side), torch.no_grad():
                 for _ in range(max(1, warmup)):                    # MIOpen picks its solvers outside the capture
-                    predict_batch(smpl_model, decoder, self._in)
+                    predict_batch(smpl_model, decoder, self._in, amp)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             self._graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._graph), torch.no_grad():
-                self._out = predict_batch(smpl_model, decoder, self._in)
+                self._out = predict_batch(smpl_model, decoder, self._in, amp)
         finally:
             smpl_model.train(was_training)
 

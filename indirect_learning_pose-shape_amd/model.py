@@ -29,7 +29,8 @@ class PReLU(nn.PReLU):
         super().__init__(num_parameters, init=init, **kw)
 
     def forward(self, x):
-        if (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 2 and self.weight.numel() == x.shape[1]
+        if (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and self.weight.dtype == torch.float32
+                and x.dim() >= 2 and self.weight.numel() == x.shape[1]
                 and x.is_contiguous()):           # (NCHW planes; a channels_last tensor takes the stock op)
             from . import ops
             return ops.PReLUFn.apply(x.contiguous(), self.weight)
@@ -99,7 +100,10 @@ class ENetEncoder(nn.Module):
 
     def forward(self, x):
         from .ops import batch_norm_act
-        x = torch.cat([self.init_conv(x), F.max_pool2d(x, 2)], dim=1)
+        # (the pooled image in the convolution's dtype: a no-op in fp32; under torch.autocast it keeps the 16-channel
+        # 128 x 128 map, the encoder's largest activation, in bf16 instead of promoting the cat to fp32)
+        y = self.init_conv(x)
+        x = torch.cat([y, F.max_pool2d(x, 2).to(y.dtype)], dim=1)
         return self.blocks(batch_norm_act(x, self.init_bn, self.init_act))
 
 

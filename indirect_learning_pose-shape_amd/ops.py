@@ -783,21 +783,41 @@ def softmax_probs(scores):
     return probs.reshape(scores.shape[0], -1, C)
 
 
+ENCODER_DTYPES = (torch.float32, torch.bfloat16)     # what the encoder's batch-norm / PReLU kernels stream
+
+
+def _encoder_entry(lib, name, x):
+    """The entry point `name` of csrc/norm.hip / csrc/act.hip for x's element type: smplr_<name> for fp32,
+    smplr_<name>_bf16 for bfloat16 (the same argument list; only the streamed tensors are bf16).  Any other dtype is
+    an error: there is no kernel for it and nothing else stands in."""
+    if x.dtype not in ENCODER_DTYPES:
+        raise RuntimeError("the encoder kernels take float32 or bfloat16 tensors (got %s)" % x.dtype)
+    full = "smplr_" + name + ("_bf16" if x.dtype == torch.bfloat16 else "")
+    return getattr(lib, full), full
+
+
+def _encoder_grad(g, x, name):
+    """The incoming gradient of an encoder op as its kernel reads it: dense NCHW, of x's dtype."""
+    return require_cuda(g if g.dtype == x.dtype else g.to(x.dtype), name, x.dtype)
+
+
 class PReLUFn(torch.autograd.Function):
-    """Per-channel PReLU on NCHW fp32 (the ENet encoder's activation, encoders/encoder_enet_simple.py:21):
-    smplr_prelu_fwd / smplr_prelu_bwd.  x (N, C, ...) and weight (C,)."""
+    """Per-channel PReLU on NCHW fp32 or bf16 (the ENet encoder's activation, encoders/encoder_enet_simple.py:21):
+    smplr_prelu_fwd / smplr_prelu_bwd or their _bf16 twins, by x.dtype.  x (N, C, ...) and weight (C,) fp32; y and
+    the gradient of x have x's dtype (bf16: the fp32 product rounded once, to nearest even), the weight's is fp32."""
 
     @staticmethod
     @on_device
     def forward(ctx, x, weight):
-        x = require_cuda(x, "x")
+        fwd, fname = _encoder_entry(_lib.load(), "prelu_fwd", x)
+        x = require_cuda(x, "x", x.dtype)
         weight = require_cuda(weight, "weight")
         N, C = x.shape[0], x.shape[1]
         if weight.numel() != C:
             raise RuntimeError("PReLU weight has %d entries for %d channels" % (weight.numel(), C))
         HW = x.numel() // (N * C) if N * C else 1
         y = torch.empty_like(x)
-        check(_lib.load().smplr_prelu_fwd(ptr(x), ptr(weight), N, C, HW, ptr(y), stream()), "smplr_prelu_fwd")
+        check(fwd(ptr(x), ptr(weight), N, C, HW, ptr(y), stream()), fname)
         ctx.save_for_backward(x, weight)
         ctx.dims = (N, C, HW)
         return y
@@ -807,25 +827,27 @@ class PReLUFn(torch.autograd.Function):
     def backward(ctx, gy):
         x, weight = ctx.saved_tensors
         N, C, HW = ctx.dims
-        gy = require_cuda(gy, "gy")
+        gy = _encoder_grad(gy, x, "gy")
         lib = _lib.load()
+        bwd, bname = _encoder_entry(lib, "prelu_bwd", x)
         gx, gw = torch.empty_like(x), torch.empty_like(weight)
         ws = _workspace(lib.smplr_prelu_bwd_workspace(N, C, HW), x)
-        check(lib.smplr_prelu_bwd(ptr(x), ptr(weight), ptr(gy), N, C, HW, ptr(gx), ptr(gw), ptr(ws), stream()),
-              "smplr_prelu_bwd")
+        check(bwd(ptr(x), ptr(weight), ptr(gy), N, C, HW, ptr(gx), ptr(gw), ptr(ws), stream()), bname)
         return gx, gw
 
 
 class BatchNormActFn(torch.autograd.Function):
-    """Training-mode BatchNorm2d (+ per-channel PReLU) on NCHW fp32: smplr_bn_fwd / smplr_bn_bwd (the ENet
-    encoder's `BatchNormalization` + `PReLU(shared_axes=[1, 2])` pairs, encoders/encoder_enet_simple.py:19-21).
-    running_mean / running_var are updated in place like torch.nn.BatchNorm2d; slope = None: no activation."""
+    """Training-mode BatchNorm2d (+ per-channel PReLU) on NCHW fp32 or bf16: smplr_bn_fwd / smplr_bn_bwd or their
+    _bf16 twins, by x.dtype (the ENet encoder's `BatchNormalization` + `PReLU(shared_axes=[1, 2])` pairs,
+    encoders/encoder_enet_simple.py:19-21).  running_mean / running_var are updated in place like torch.nn.BatchNorm2d;
+    slope = None: no activation.  z and dx have x's dtype; parameters, statistics and their gradients are fp32."""
 
     @staticmethod
     @on_device
     def forward(ctx, x, gamma, beta, slope, running_mean, running_var, eps, momentum):
         lib = _lib.load()
-        x = require_cuda(x, "x")
+        fwd, fname = _encoder_entry(lib, "bn_fwd", x)
+        x = require_cuda(x, "x", x.dtype)
         gamma, beta = require_cuda(gamma, "gamma"), require_cuda(beta, "beta")
         slope = require_cuda(slope, "slope") if slope is not None else None
         N, C = x.shape[0], x.shape[1]
@@ -835,9 +857,8 @@ class BatchNormActFn(torch.autograd.Function):
         z = torch.empty_like(x)
         mean, rstd = _empty((C,), x), _empty((C,), x)
         ws = _workspace(lib.smplr_bn_workspace(N, C, HW), x)
-        check(lib.smplr_bn_fwd(ptr(x), ptr(gamma), ptr(beta), ptr(slope), N, C, HW, float(eps), float(momentum),
-                               ptr(running_mean), ptr(running_var), ptr(z), ptr(mean), ptr(rstd), ptr(ws), stream()),
-              "smplr_bn_fwd")
+        check(fwd(ptr(x), ptr(gamma), ptr(beta), ptr(slope), N, C, HW, float(eps), float(momentum),
+                  ptr(running_mean), ptr(running_var), ptr(z), ptr(mean), ptr(rstd), ptr(ws), stream()), fname)
         ctx.save_for_backward(x, gamma, beta, slope, mean, rstd)
         ctx.dims = (N, C, HW)
         return z
@@ -848,25 +869,28 @@ class BatchNormActFn(torch.autograd.Function):
         lib = _lib.load()
         x, gamma, beta, slope, mean, rstd = ctx.saved_tensors
         N, C, HW = ctx.dims
-        dz = require_cuda(dz, "dz")
+        dz = _encoder_grad(dz, x, "dz")
+        bwd, bname = _encoder_entry(lib, "bn_bwd", x)
         dx = torch.empty_like(x)
         dg, db = torch.empty_like(gamma), torch.empty_like(beta)
         ds = torch.empty_like(slope) if slope is not None else None
         ws = _workspace(lib.smplr_bn_workspace(N, C, HW), x)
-        check(lib.smplr_bn_bwd(ptr(x), ptr(gamma), ptr(beta), ptr(slope), ptr(mean), ptr(rstd), ptr(dz), N, C, HW,
-                               ptr(dx), ptr(dg), ptr(db), ptr(ds), ptr(ws), stream()), "smplr_bn_bwd")
+        check(bwd(ptr(x), ptr(gamma), ptr(beta), ptr(slope), ptr(mean), ptr(rstd), ptr(dz), N, C, HW,
+                  ptr(dx), ptr(dg), ptr(db), ptr(ds), ptr(ws), stream()), bname)
         return dx, dg, db, ds, None, None, None, None
 
 
 class BatchNormResActFn(torch.autograd.Function):
     """out = prelu(plane_scale * bn(x) + other, slope): the tail of an ENet bottleneck (BatchNormalization ->
-    SpatialDropout2D -> Add -> PReLU, encoders/encoder_enet_simple.py:56-79) as one op (smplr_bn_res_fwd/bwd)."""
+    SpatialDropout2D -> Add -> PReLU, encoders/encoder_enet_simple.py:56-79) as one op (smplr_bn_res_fwd/bwd, or their
+    _bf16 twins by x.dtype).  x and other share one dtype, fp32 or bf16; out, dx and dother have it too."""
 
     @staticmethod
     @on_device
     def forward(ctx, x, other, gamma, beta, slope, plane_scale, running_mean, running_var, eps, momentum):
         lib = _lib.load()
-        x, other = require_cuda(x, "x"), require_cuda(other, "other")
+        fwd, fname = _encoder_entry(lib, "bn_res_fwd", x)
+        x, other = require_cuda(x, "x", x.dtype), require_cuda(other, "other", x.dtype)
         if other.shape != x.shape:
             raise RuntimeError("other must have the shape of x")
         N, C = x.shape[0], x.shape[1]
@@ -874,9 +898,9 @@ class BatchNormResActFn(torch.autograd.Function):
         out = torch.empty_like(x)
         mean, rstd = _empty((C,), x), _empty((C,), x)
         ws = _workspace(lib.smplr_bn_workspace(N, C, HW), x)
-        check(lib.smplr_bn_res_fwd(ptr(x), ptr(gamma), ptr(beta), ptr(plane_scale), ptr(other), ptr(slope), N, C, HW,
-                                   float(eps), float(momentum), ptr(running_mean), ptr(running_var), ptr(out),
-                                   ptr(mean), ptr(rstd), ptr(ws), stream()), "smplr_bn_res_fwd")
+        check(fwd(ptr(x), ptr(gamma), ptr(beta), ptr(plane_scale), ptr(other), ptr(slope), N, C, HW,
+                  float(eps), float(momentum), ptr(running_mean), ptr(running_var), ptr(out),
+                  ptr(mean), ptr(rstd), ptr(ws), stream()), fname)
         ctx.save_for_backward(x, other, gamma, beta, slope, plane_scale, mean, rstd)
         ctx.dims = (N, C, HW)
         return out
@@ -887,29 +911,40 @@ class BatchNormResActFn(torch.autograd.Function):
         lib = _lib.load()
         x, other, gamma, beta, slope, plane_scale, mean, rstd = ctx.saved_tensors
         N, C, HW = ctx.dims
-        dout = require_cuda(dout, "dout")
+        dout = _encoder_grad(dout, x, "dout")
+        bwd, bname = _encoder_entry(lib, "bn_res_bwd", x)
         dx, dother = torch.empty_like(x), torch.empty_like(x)
         dg, db, ds = torch.empty_like(gamma), torch.empty_like(beta), torch.empty_like(slope)
         ws = _workspace(lib.smplr_bn_workspace(N, C, HW), x)
-        check(lib.smplr_bn_res_bwd(ptr(x), ptr(gamma), ptr(beta), ptr(plane_scale), ptr(other), ptr(slope), ptr(mean),
-                                   ptr(rstd), ptr(dout), N, C, HW, ptr(dx), ptr(dother), ptr(dg), ptr(db), ptr(ds),
-                                   ptr(ws), stream()), "smplr_bn_res_bwd")
+        check(bwd(ptr(x), ptr(gamma), ptr(beta), ptr(plane_scale), ptr(other), ptr(slope), ptr(mean),
+                  ptr(rstd), ptr(dout), N, C, HW, ptr(dx), ptr(dother), ptr(dg), ptr(db), ptr(ds),
+                  ptr(ws), stream()), bname)
         return dx, dother, dg, db, ds, None, None, None, None, None
 
 
 def _bn_fusable(x, bn):
     # (x.is_contiguous(): the kernels read NCHW planes - a channels_last tensor, the opt-in SMPLR_ENCODER_LAYOUT of
     # training.py, takes the stock modules instead of being transposed back for them)
-    return (bn.training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and bn.affine and x.is_contiguous()
+    # (bf16 activations with fp32 parameters are what torch.autocast leaves a BatchNorm2d with; a module whose own
+    # parameters are not fp32 takes the stock path)
+    return (bn.training and x.is_cuda and x.dtype in ENCODER_DTYPES and x.dim() == 4 and bn.affine and x.is_contiguous()
             and bn.track_running_stats and bn.momentum is not None and x.shape[2] * x.shape[3] >= 256
-            and x.shape[0] > 0)
+            and x.shape[0] > 0 and bn.weight.dtype == torch.float32 and bn.bias.dtype == torch.float32)
+
+
+def _slope_fusable(act, x):
+    return act.weight.numel() == x.shape[1] and act.weight.dtype == torch.float32
 
 
 def batch_norm_residual_act(x, bn, dropout, other, act, plane_scale=None):
     """`act(dropout(bn(x)) + other)` for nn.BatchNorm2d, nn.Dropout2d (or None), a tensor and a per-channel
     nn.PReLU: one HIP op when training on a HIP device, the stock modules otherwise.  plane_scale (N, C): the
-    dropout factors to use instead of drawing them (tests)."""
-    if not (_bn_fusable(x, bn) and act.weight.numel() == x.shape[1] and other.shape == x.shape):
+    dropout factors to use instead of drawing them (tests).
+    The op runs in x's dtype (fp32 or bf16) and returns it: an `other` of another dtype is converted with
+    `other.to(x.dtype)` first, and autograd hands its gradient back in other's own dtype.  With a bf16 x under
+    torch.autocast this keeps the residual stream in bf16, where the stock chain's `bn(x) + other` would promote a
+    mixed pair to fp32 and pay a cast in front of every following convolution."""
+    if not (_bn_fusable(x, bn) and _slope_fusable(act, x) and other.shape == x.shape):
         y = bn(x)
         if dropout is not None:
             y = dropout(y)
@@ -919,6 +954,8 @@ def batch_norm_residual_act(x, bn, dropout, other, act, plane_scale=None):
         plane_scale = torch.empty(x.shape[0], x.shape[1], device=x.device, dtype=torch.float32).bernoulli_(keep).div_(keep)
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
+    if other.dtype != x.dtype:
+        other = other.to(x.dtype)
     return BatchNormResActFn.apply(x.contiguous(), other.contiguous(), bn.weight, bn.bias, act.weight,
                                    plane_scale.contiguous() if plane_scale is not None else None,
                                    bn.running_mean, bn.running_var, bn.eps, bn.momentum)
@@ -926,9 +963,9 @@ def batch_norm_residual_act(x, bn, dropout, other, act, plane_scale=None):
 
 def batch_norm_act(x, bn, act=None):
     """`act(bn(x))` for a torch.nn.BatchNorm2d and an optional per-channel nn.PReLU.  Training mode on a HIP
-    device with planes of >= 256 elements runs the fused HIP kernels; everything else (eval mode, CPU, tiny
-    planes, other dtypes) takes the stock modules.  Parameters, buffers and state dict are the modules' own."""
-    if not (_bn_fusable(x, bn) and (act is None or act.weight.numel() == x.shape[1])):
+    device with planes of >= 256 elements runs the fused HIP kernels, in x's dtype (fp32, or bf16 with fp32
+    parameters); everything else (eval mode, CPU, tiny planes, other dtypes) takes the stock modules.  Parameters, buffers and state dict are the modules' own."""
+    if not (_bn_fusable(x, bn) and (act is None or _slope_fusable(act, x))):
         y = bn(x)
         return act(y) if act is not None else y
     if bn.num_batches_tracked is not None:

@@ -34,12 +34,47 @@ def configure_conv_backend():
     torch.backends.cudnn.benchmark = True
 
 
+def amp_dtype(amp):
+    """The `amp` option of SegTrainer, inference.predict_batch and inference.GraphedPredictor -> the autocast dtype:
+    None (fp32 throughout, the default) or torch.bfloat16 for "bf16" / torch.bfloat16.  Anything else is a ValueError;
+    fp16 in particular needs loss scaling, which is not offered."""
+    if amp is None:
+        return None
+    if amp is torch.bfloat16 or (isinstance(amp, str) and amp == "bf16"):
+        return torch.bfloat16
+    if amp is torch.float16 or (isinstance(amp, str) and amp.lower() in ("fp16", "float16", "half")):
+        raise ValueError("amp=%r: fp16 needs loss scaling and no loss scaling is offered; use amp='bf16'" % (amp,))
+    raise ValueError("amp must be None, 'bf16' or torch.bfloat16 (got %r)" % (amp,))
+
+
+def regress(net, images, amp):
+    """net(images) -> the (N, 86) vector in fp32.  With amp, that forward alone runs under torch.autocast(device type,
+    bfloat16) and the vector is `.float()`ed on the way out; amp = None is net(images) itself."""
+    dt = amp_dtype(amp)
+    if dt is None:
+        return net(images)
+    with torch.autocast(images.device.type, dtype=dt):
+        param = net(images)
+    return param.float()
+
+
 class SegTrainer:
-    """One optimiser step = `segs_model.fit` on one batch with the focal loss (train.py:207-242)."""
+    """One optimiser step = `segs_model.fit` on one batch with the focal loss (train.py:207-242).
+    amp = "bf16" (or torch.bfloat16): mixed precision for the encoder + regressor - that forward alone runs under
+    torch.autocast(bfloat16), where the convolutions and linears take bf16 and the package's batch-norm / PReLU kernels
+    stream bf16 activations; the 86-vector comes out as fp32, and decoder, loss heads, backward's accumulation into the
+    parameters, Adam, the DDP buckets and the checkpoints are the fp32 ones of amp = None (bf16 has fp32's exponent: no
+    GradScaler).  amp = None, the default, is the fp32 step unchanged."""
 
     def __init__(self, smpl_path=None, input_wh=256, output_wh=48, encoder_architecture="enet", use_IEF=True,
                  weight_classes=True, gamma=2.0, lr=1e-4, device=None, ddp=False, bucket_mb=25,
-                 with_silhouette=False, silh_wh=None, fused_loss=True, fused_silh_loss=False):
+                 with_silhouette=False, silh_wh=None, fused_loss=True, fused_silh_loss=False, amp=None):
+        amp_dtype(amp)                                                # (ValueError before anything is built)
+        if amp is not None and os.environ.get("SMPLR_ENCODER_LAYOUT", "").lower() == "channels_last":
+            # that layout runs torch's own BatchNorm2d (the package's kernels read NCHW planes), and torch 2.10 / ROCm 7.0's
+            # training-mode batch norm is not safe on a bf16 channels_last tensor: it ends the process (DESIGN.md section 15)
+            raise ValueError("amp and SMPLR_ENCODER_LAYOUT=channels_last do not go together")
+        self.amp = amp
         if fused_silh_loss and not with_silhouette:
             raise ValueError("fused_silh_loss needs with_silhouette=True")
         self.device = (torch.device(device) if device is not None
@@ -99,7 +134,7 @@ class SegTrainer:
         self.opt.zero_grad(set_to_none=True)
         if self.channels_last and images.dim() == 4 and images.shape[1] == 3:
             images = images.contiguous(memory_format=torch.channels_last)
-        param = self.net(images)
+        param = regress(self.net, images, self.amp)
         mark("encoder_fwd")
         if _marks is not None and param.requires_grad:
             param.register_hook(lambda g: (mark("decoder_bwd"), g)[1])     # fires between the decoder's and the encoder's backward
@@ -167,7 +202,7 @@ class SegTrainer:
         was_training = self.smpl_model.training
         self.smpl_model.eval()
         try:
-            param = self.smpl_model(images)
+            param = regress(self.smpl_model, images, self.amp)
             out = dict(self.monitor_decoder(param))
         finally:
             self.smpl_model.train(was_training)
