@@ -413,6 +413,7 @@ std::vector<Tensor> decoder_fwd(const Tensor &x, const std::vector<Tensor> &cons
   const Consts c = unpack(consts);
   const PartDims d = part_dims(part_pos, part_off);
   TORCH_CHECK(x.dim() == 2 && x.size(1) == num_cam + 82, "x must be (B, num_cam + 82)");
+  TORCH_CHECK(num_cam >= 4 && num_cam <= 16, "decoder_fwd: the projection reads 4 camera columns, num_cam must be in 4..16");
   TORCH_CHECK(grid_wh > 0 && grid_wh <= 128 && W > 0 && W <= 160, "decoder_fwd: 0 < grid_wh <= 128, 0 < W <= 160");
   same_device(x, {{"consts", &c.vt}, {"part_pos", &part_pos}, {"part_off", &part_off}});
   DeviceGuard g(x.device());

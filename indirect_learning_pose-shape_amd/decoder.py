@@ -105,6 +105,11 @@ class SMPLDecoder(nn.Module):
         written), else by the confusion kernel on `seg`.  Needs `labels`; the returned dict is unchanged."""
         if x.dim() != 2 or x.shape[1] != self.num_cam + 82:
             raise RuntimeError("SMPLDecoder expects x of shape (B, %d)" % (self.num_cam + 82))
+        if not 4 <= self.num_cam <= 16:
+            # (the projection reads columns 0..3 of x as the camera whatever num_cam says: with fewer, the first joint
+            # angles would be taken for it - no launcher sees that, a row of num_cam + 82 >= 4 floats is all they ask)
+            raise RuntimeError("SMPLDecoder projects with the 4 camera columns in front of x: num_cam must be in 4..16, "
+                               "got %d" % self.num_cam)
         c = self.constants(x.device)
         pt = ops.get_part_table(self.vs, x.device, c.V)
         # gradient-free forward of the plain decoder (predict.py:99-118): ONE host call into the at::Tensor layer

@@ -1090,6 +1090,9 @@ class DecoderFn(torch.autograd.Function):
         Ws = 0 if not with_silh else (W if with_silh is True else int(with_silh))
         if not opts.seg and not with_silh:
             raise RuntimeError("DecoderFn: no head asked for (opts.seg = False needs a silhouette)")
+        if not 4 <= int(num_cam) <= 16:
+            raise RuntimeError("DecoderFn: the projection needs the 4 camera columns, num_cam must be in 4..16 (got %r)"
+                               % (num_cam,))
         # (smplr_seg_bin reads grid_wh <= 0 as "the mask is an INPUT": the decoder always computes it, so a bad value
         # would rasterise from an uninitialised mask on the two-call path - refuse it here for every path)
         if opts.seg and not 0 < int(grid_wh) <= 128:
