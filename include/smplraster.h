@@ -160,6 +160,8 @@ int smplr_skin_bwd(const float *dverts, const float *dproj,
  * 24 while the batch gives every CU one to four row blocks).  The skinning backward then gathers
  * d(seg)/d(proj) by vertex, summing the row blocks in the order the merge kernel would have (bit-identical),
  * and adds it to dproj (if given): one launch and one (B,VP,3) round trip less.
+ * With seg_part given (and no dverts / dproj), a vertex whose summed slot gradient is exactly (0, 0) is treated
+ * like a vertex without a record: a zero dv_posed row, no term in dA or the camera sums.
  * workspace: smplr_smpl_bwd_workspace(B,V) bytes.                                              */
 size_t smplr_smpl_bwd_workspace(int B, int V);
 int smplr_smpl_bwd(const float *dverts, const float *dproj,

@@ -359,45 +359,63 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const float *__restric
 }
 
 // ------------------------------------------------------------------------------------------------
-// The skinning backward over RECORDS instead of vertices (round 5).  When the only gradient that reaches the vertices is
-// the part rasteriser's (seg_bwd's slot sums; no d verts, no merged d proj: the decoder's training step), a vertex without
-// a record - hidden and further than 0.208 px from every pixel centre: 78 % of them - has g = 0: its dv_posed row is
-// zero and it adds nothing to dA or the camera sums, yet skin_bwd_kernel loads its weights and v_posed row, blends its T
-// and feeds it to the dA product like any other.  Here a workgroup takes 1 024 consecutive vertices, compacts those with
-// a record ((vertex, slot) in vertex order: ballots + prefix sums, no atomics, so the order - and with it every sum - is
-// the same on every launch) and runs skin_bwd_kernel's arithmetic on the compact list alone: the slot sums straight by
-// slot (one hop instead of vertex -> slot -> sums), T rows 0 and 1 (row 2 multiplies g_z = 0), the dA tile on the matrix
-// cores with the weights operand rebuilt from the records' (weight, joint) quadruples in LDS.  dv_posed is bit for bit
-// skin_bwd_kernel's (rows without a record are stored as zeros); dA and the camera sums add the same terms in another
-// order.  Measured (rocprofv3, same box): B = 128 19.3-20.1 -> 16.1 us, B = 2 048 233-236 -> 138 us; the step 0.1253 ->
-// 0.1229 ms and 1.404 -> 1.297 ms (1.58 M meshes/s).  What the in-kernel stamps taught on the way
-// (tools/probes/skinrec_timeline.py): gfx950 counts loads and stores in ONE in-order counter, so the zero rows stored
-// during the compaction and the records' rows stored before the dA product made the next loads' waits 11.5 k and 4.7 k
-// clocks long - every store now comes behind the kernel's last load; gathering the dense weight rows per record (as
-// skin_bwd_kernel reads them) was a third dependent round trip of 5 k clocks.  A wave-private variant (no workgroup
-// barriers before the final sum) and 512- / 2 048-vertex workgroups were slower (tools: SMPLR_SKIN_BWD_REC=0 runs the
-// per-vertex kernel for A/B).
+// The skinning backward over the LIVE RECORDS instead of over the vertices.  When the only gradient that reaches the
+// vertices is the part rasteriser's (seg_bwd's slot sums; no d verts, no merged d proj: the decoder's training step), a
+// vertex has g = 0 - a zero dv_posed row, nothing for dA or the camera sums - unless it owns a record AND that record won
+// an arg-min somewhere.  78 % of the vertices own no record (hidden and further than 0.208 px from every pixel centre);
+// of the ~1 450 records per mesh the 400-670 "global" ones (visible vertices) nearly all win a pixel, but the 820-900
+// "local" ones (hidden, near a pixel centre, scoring exp(-500 d)) win only where they beat the part's best visible
+// vertex, which is rare: their slot sum is EXACTLY (0, 0) (tools/probes/live_records.py counts them on the bench input;
+// profiles/skin_bwd_live_records.txt).  skin_bwd_kernel loads every vertex' weights and v_posed row, blends its T and
+// feeds it to the dA product like any other.  Here a workgroup takes 1 024 consecutive vertices and
+//   1. loads their slots and, as soon as a slot is known, its sums over seg_bwd's row blocks (same addresses, same block
+//      order as skin_bwd_kernel's gather: same bits);
+//   2. compacts the live ones - slot >= 0 and not (sx == 0 and sy == 0): a NaN or inf sum is not zero and stays on the
+//      list, so a hostile row propagates as it always did - as (vertex, sum) pairs in vertex order (ballots + prefix
+//      sums, no atomics: the order, and with it every sum, is the same on every launch and in every batch);
+//   3. per live record gathers top4 and v_posed, blends T rows 0 and 1 (row 2 multiplies g_z = 0), and runs the dA tile
+//      on the matrix cores with the weights operand rebuilt from the records' (weight, joint) quadruples in LDS;
+//   4. stores the records' dv_posed rows, and zeros for every other vertex: no record, or a dead one (whose row
+//      skin_bwd_kernel computes as fma(t, +0, +0) = +0).
+// dv_posed is bit for bit skin_bwd_kernel's; dA and the camera sums add the same non-zero terms in another fixed order.
+// SMPLR_SKIN_BWD_LIVE=0 puts every record with slot >= 0 on the list again (the form before the filter; A/B runs on one
+// build), SMPLR_SKIN_BWD_REC=0 runs the per-vertex kernel.  Timings of both and of the 2 048-vertex workgroup
+// (-DSMPLR_SKR_VPT=8, slower at either density): profiles/skin_bwd_live_timings.txt, DESIGN.md section 3.
+// Resources: FIVE workgroups per CU (<= 96 registers for five waves per SIMD, <= 32 000 B of LDS: the list keeps a
+// vertex as its 16-bit offset in the chunk and the waves' partial sums reuse the weights' LDS) - the large batch is
+// bound by the workgroups in flight, not by bytes: B = 2 048 143 -> 127 us against four per CU (105 registers, 34.5 KB).
+// What the in-kernel stamps taught earlier (tools/probes/skinrec_timeline.py, profiles/r05_timelines.txt): gfx950 counts
+// loads and stores in ONE in-order counter, so zero rows stored during the compaction and records' rows stored before
+// the dA product made the next loads' waits 11.5 k and 4.7 k clocks long - every store comes behind the kernel's last
+// load; gathering the dense weight rows per record (as skin_bwd_kernel reads them) was one more dependent round trip of
+// 5 k clocks; a wave-private variant (no workgroup barriers before the final sum) was slower.
 #ifdef SMPLR_TL
 constexpr int TL_SKINREC_WG = 896;
 __device__ unsigned g_tl_skinrec[TL_SKINREC_WG * 4 * 32];
 #endif
 constexpr int SKR_T = 256;         // threads
-constexpr int SKR_VPT = 4;         // vertices per thread in the compaction pass
+#ifndef SMPLR_SKR_VPT
+#define SMPLR_SKR_VPT 4            // (a variant build with 8 is what the 2 048-vertex workgroup was measured with)
+#endif
+constexpr int SKR_VPT = SMPLR_SKR_VPT;   // vertices per thread in the compaction pass
 constexpr int SKR_CHUNK = SKR_T * SKR_VPT;
 
-__global__ __launch_bounds__(SKR_T) __attribute__((amdgpu_waves_per_eu(4, 8))) void skin_bwd_rec_kernel(
+__global__ __launch_bounds__(SKR_T) __attribute__((amdgpu_waves_per_eu(5, 8))) void skin_bwd_rec_kernel(
     const float *__restrict__ v_posed, const float *__restrict__ top4,
     const float *__restrict__ A, const float *__restrict__ cam, int x_stride, int B, int V, int vs, int VP,
     float *__restrict__ dv_posed, float *__restrict__ part, const float *__restrict__ seg_part,
-    const short *__restrict__ seg_vslot, int seg_nsplit) {
+    const short *__restrict__ seg_vslot, int seg_nsplit, int live_only) {
   __shared__ float sG[SKR_T][4];    // (g_x, g_y) per record of the round
   __shared__ float sP[SKR_T][4];    // [v_posed; 1]
-  __shared__ float4 sW[SKR_T];      // its (up to) four skinning weights (zeros for a lane past the list) ...
-  __shared__ float4 sJ[SKR_T];      // ... and their joints
-  __shared__ float sRed[SKR_T / 64][SKB_PART];
+  __shared__ float4 sWJ[2 * SKR_T];
+  float4 *sW = sWJ;                 // its (up to) four skinning weights (zeros for a lane past the list) ...
+  float4 *sJ = sWJ + SKR_T;         // ... and their joints
+  // (the waves' partial sums take the weights' place once the rounds are over: five workgroups per CU need <= 32 000 B)
+  float (*sRed)[SKB_PART] = reinterpret_cast<float (*)[SKB_PART]>(sWJ);
+  static_assert(sizeof(float) * (SKR_T / 64) * SKB_PART <= sizeof(float4) * 2 * SKR_T, "sRed inside sWJ");
   __shared__ float4 sAj[72];
-  __shared__ int sVid[SKR_CHUNK];
-  __shared__ short sSlot[SKR_CHUNK];
+  __shared__ unsigned short sVid[SKR_CHUNK];   // the compact list: vertex (its offset in the chunk) ...
+  __shared__ float2 sSum[SKR_CHUNK];   // ... and its slot sum
   __shared__ int sCnt[SKR_VPT * (SKR_T / 64)];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int n = blockIdx.y, v0 = blockIdx.x * SKR_CHUNK;
@@ -416,19 +434,55 @@ __global__ __launch_bounds__(SKR_T) __attribute__((amdgpu_waves_per_eu(4, 8))) v
   }
   if (tid < 72) sAj[tid] = aj;
   SMPLR_TL_STAMP(1);
+  // each slot's sums over seg_bwd's row blocks, in block order (skin_bwd_kernel's gather), as soon as the slot is known
+  // (a vertex without a slot reads slot 0 of its mesh and is not looked at)
+  float sx[SKR_VPT], sy[SKR_VPT];
+#pragma unroll
+  for (int i = 0; i < SKR_VPT; ++i) {
+    const int sl = max(slot[i], 0);
+    const int win = sl / SB_SLOTS;
+    const float *sp = seg_part + ((size_t)n * seg_nsplit * SB_NWIN + win) * (SB_SLOTS * 2) + (sl - win * SB_SLOTS) * 2;
+    sx[i] = 0.0f; sy[i] = 0.0f;
+    if (seg_nsplit <= 2) {
+      const float2 t0 = *reinterpret_cast<const float2 *>(sp);
+      const float2 t1 = *reinterpret_cast<const float2 *>(sp + (size_t)(seg_nsplit - 1) * (SB_NWIN * SB_SLOTS * 2));
+      sx[i] = t0.x + (seg_nsplit > 1 ? t1.x : 0.0f);
+      sy[i] = t0.y + (seg_nsplit > 1 ? t1.y : 0.0f);
+    } else {
+      constexpr int GC = 6;
+      for (int s0 = 0; s0 < seg_nsplit; s0 += GC) {
+        float2 t[GC];
+#pragma unroll
+        for (int u = 0; u < GC; ++u)
+          t[u] = *reinterpret_cast<const float2 *>(sp + (size_t)min(s0 + u, seg_nsplit - 1) * (SB_NWIN * SB_SLOTS * 2));
+#pragma unroll
+        for (int u = 0; u < GC; ++u) {
+          sx[i] += (s0 + u < seg_nsplit) ? t[u].x : 0.0f;
+          sy[i] += (s0 + u < seg_nsplit) ? t[u].y : 0.0f;
+        }
+      }
+    }
+  }
+  // live: a record whose sum is not exactly (0, 0) (NaN and inf are not zero: such a row propagates as it always did)
+  unsigned livem = 0, zerom = 0;           // bit i: vertex i of this thread is on the list / gets a zero row
   int pre[SKR_VPT];
 #pragma unroll
   for (int i = 0; i < SKR_VPT; ++i) {
-    const unsigned long long m = __ballot(slot[i] >= 0);
+    const bool live = slot[i] >= 0 && !(live_only && sx[i] == 0.0f && sy[i] == 0.0f);
+    const unsigned long long m = __ballot(live);
     pre[i] = __popcll(m & ((1ull << lane) - 1ull));
     if (lane == 0) sCnt[i * (SKR_T / 64) + wave] = __popcll(m);
+    if (live) livem |= 1u << i;
+    else if (v0 + i * SKR_T + tid < V) zerom |= 1u << i;
   }
   SMPLR_TL_STAMP(2);
   __syncthreads();
   SMPLR_TL_STAMP(3);
   int R = 0;
   {
-    int base[SKR_VPT] = {0, 0, 0, 0};
+    int base[SKR_VPT];
+#pragma unroll
+    for (int i = 0; i < SKR_VPT; ++i) base[i] = 0;
 #pragma unroll
     for (int k = 0; k < SKR_VPT * (SKR_T / 64); ++k) {
       const int c = sCnt[k];
@@ -439,10 +493,9 @@ __global__ __launch_bounds__(SKR_T) __attribute__((amdgpu_waves_per_eu(4, 8))) v
     }
 #pragma unroll
     for (int i = 0; i < SKR_VPT; ++i) {
-      const int v = v0 + i * SKR_T + tid;
-      if (slot[i] >= 0) {
-        sVid[base[i] + pre[i]] = v;
-        sSlot[base[i] + pre[i]] = (short)slot[i];
+      if (livem >> i & 1u) {
+        sVid[base[i] + pre[i]] = (unsigned short)(i * SKR_T + tid);
+        sSum[base[i] + pre[i]] = make_float2(sx[i], sy[i]);
       }
     }
   }
@@ -457,35 +510,13 @@ __global__ __launch_bounds__(SKR_T) __attribute__((amdgpu_waves_per_eu(4, 8))) v
   for (int r0 = 0; r0 < R; r0 += SKR_T) {                  // (block-uniform; one round for up to 256 records)
     const int idx = r0 + tid;
     const bool valid = idx < R;
-    const int vid = sVid[min(idx, R - 1)], sl = sSlot[min(idx, R - 1)];
+    const int vid = v0 + sVid[min(idx, R - 1)];
+    const float2 sm = sSum[min(idx, R - 1)];
     const float4 *tp = reinterpret_cast<const float4 *>(top4 + (size_t)vid * 8);
     const float4 ww = tp[0], jj = tp[1];
     const float *vp = v_posed + ((size_t)n * V + vid) * 3;
     const float p0 = vp[0], p1 = vp[1], p2 = vp[2];
-    // the slot's sums over seg_bwd's row blocks, in block order (skin_bwd_kernel's gather, without the vertex -> slot hop)
-    const int win = sl / SB_SLOTS;
-    const float *sp = seg_part + ((size_t)n * seg_nsplit * SB_NWIN + win) * (SB_SLOTS * 2) + (sl - win * SB_SLOTS) * 2;
-    float sx = 0.0f, sy = 0.0f;
-    if (seg_nsplit <= 2) {
-      const float2 t0 = *reinterpret_cast<const float2 *>(sp);
-      const float2 t1 = *reinterpret_cast<const float2 *>(sp + (size_t)(seg_nsplit - 1) * (SB_NWIN * SB_SLOTS * 2));
-      sx = t0.x + (seg_nsplit > 1 ? t1.x : 0.0f);
-      sy = t0.y + (seg_nsplit > 1 ? t1.y : 0.0f);
-    } else {
-      constexpr int GC = 6;
-      for (int s0 = 0; s0 < seg_nsplit; s0 += GC) {
-        float2 t[GC];
-#pragma unroll
-        for (int u = 0; u < GC; ++u)
-          t[u] = *reinterpret_cast<const float2 *>(sp + (size_t)min(s0 + u, seg_nsplit - 1) * (SB_NWIN * SB_SLOTS * 2));
-#pragma unroll
-        for (int u = 0; u < GC; ++u) {
-          sx += (s0 + u < seg_nsplit) ? t[u].x : 0.0f;
-          sy += (s0 + u < seg_nsplit) ? t[u].y : 0.0f;
-        }
-      }
-    }
-    const float gp0 = valid ? sx : 0.0f, gp1 = valid ? sy : 0.0f;
+    const float gp0 = valid ? sm.x : 0.0f, gp1 = valid ? sm.y : 0.0f;
     const float g0 = fmaf(ck0, gp0, 0.0f), g1 = fmaf(ck1, gp1, 0.0f);
     const float w4[4] = {ww.x, ww.y, ww.z, ww.w};
     const int jx[4] = {(int)jj.x, (int)jj.y, (int)jj.z, (int)jj.w};
@@ -540,11 +571,11 @@ __global__ __launch_bounds__(SKR_T) __attribute__((amdgpu_waves_per_eu(4, 8))) v
     SMPLR_TL_STAMP(8);
     __syncthreads();                                       // (sG / sP / sRv are rewritten by the next round)
   }
-  // the rows of the vertices without a record
+  // the rows of the vertices that are not on the list: no record, or a dead one
 #pragma unroll
   for (int i = 0; i < SKR_VPT; ++i) {
     const int v = v0 + i * SKR_T + tid;
-    if (slot[i] < 0 && v < V) {
+    if (zerom >> i & 1u) {
       float *o = dv_posed + ((size_t)n * V + v) * 3;
       o[0] = 0.0f; o[1] = 0.0f; o[2] = 0.0f;
     }
@@ -585,10 +616,12 @@ int launch_skin_bwd_partials(const float *dverts, const float *dproj, SegGrad sg
   const int VP = (V + vs - 1) / vs;
   // SMPLR_SKIN_BWD_REC=0: the per-vertex kernel for every case (A/B runs)
   static const bool rec_on = !(getenv("SMPLR_SKIN_BWD_REC") && atoi(getenv("SMPLR_SKIN_BWD_REC")) == 0);
+  // SMPLR_SKIN_BWD_LIVE=0: every record is walked, also those whose slot sum is exactly zero (A/B runs on one build)
+  static const bool live_on = !(getenv("SMPLR_SKIN_BWD_LIVE") && atoi(getenv("SMPLR_SKIN_BWD_LIVE")) == 0);
   if (rec_on && !dverts && !dproj && sg.part && lbs_top4) {
     const dim3 grid((V + SKR_CHUNK - 1) / SKR_CHUNK, B);
     hipLaunchKernelGGL(skin_bwd_rec_kernel, grid, dim3(SKR_T), 0, st, v_posed, lbs_top4, A, cam, x_stride, B, V, vs, VP,
-                       dv_posed, part, sg.part, reinterpret_cast<const short *>(sg.vslot), sg.nsplit);
+                       dv_posed, part, sg.part, reinterpret_cast<const short *>(sg.vslot), sg.nsplit, live_on ? 1 : 0);
     SMPLR_LAUNCH_CHECK("skin_bwd_rec_kernel");
     *nblk_out = (int)grid.x;
     return 0;
