@@ -1,11 +1,14 @@
 // Segmentation forward, stage 2: raster2_fwd_kernel, the soft rasteriser of the 31 part channels over what seg_bin_kernel
 // (seg_bin.hip) left - per (pixel, part) the first arg-min of the key over the part's far-reaching records from a table in
 // LDS, score = exp(-sqrt(key)), then the merge of the pixel's local records and the NHWC write-out - with the loss head's
-// forward and the metrics as optional epilogues.  Also here: the entry points that bin and then rasterise.
-// raster1.hip holds the one-pixel-per-lane kernel this one replaced (SMPLR_RASTER=1), seg_bwd.hip the backward.
-#include <hip/hip_ext.h>
+// forward and the metrics as optional epilogues.  Also here: the block geometry (raster2_block, raster2_arena,
+// raster2_group_rows, trec_of) that kernel, launcher and smplr_seg_raster_plan share, and the entry points: seg_raster_impl
+// rasterises a binned workspace, seg_fwd_impl bins (and optionally skins) first.
+// raster1.hip holds the one-pixel-per-lane kernel this one replaced (SMPLR_RASTER=1), raster_device.h what the two share
+// on the device (merge, loss head's end, quad exchanges), seg_bwd.hip the backward.
 #include <algorithm>
-#include "raster_common.h"
+#include <tuple>
+#include "raster_device.h"
 
 namespace smplr {
 #ifdef SMPLR_TL
@@ -34,10 +37,10 @@ __device__ unsigned g_tl_raster[TL_RASTER_WG * 16 * 32];
 //  * two block shapes, PL pair-lanes x NG2 part ranges: 128 x 8 (two blocks per CU) and 64 x 10 (three) for batches
 //    that would not fill two rounds of the large one (raster2_shape).
 // Keys, tie rules, merge and write-out are raster_fwd_kernel's, expression for expression: outputs are bit-identical
-// (tools/probes/seg_hash.py).  A list longer than the table (TREC(R) records) goes through it in chunks (round 5:
-// scan2_parts_chunk below - rounds 1-4 walked such lists with scalar loads, 1.7 x slower at 3 000 records); blocks with a
-// weight other than 1 in the list, or more than 10 image rows under them, still walk the global record list with scalar
-// loads - exact, slow, and not what the reference's masks ({1, 500}) or sizes (48, 64) produce.
+// (tools/probes/seg_hash.py).  A list longer than the table (trec_of(AR, R) records) goes through it in chunks (round 5:
+// scan2_parts<.., CHUNK = true> below - rounds 1-4 walked such lists with scalar loads, 1.7 x slower at 3 000 records);
+// blocks with a weight other than 1 in the list, or more than 10 image rows under them, still walk the global record list
+// with scalar loads - exact, slow, and not what the reference's masks ({1, 500}) or sizes (48, 64) produce.
 constexpr int PLN = 128;                 // pair-lanes per block: 2 x 64 (the large-batch shape)
 // The block shape by batch: 1 = 128 pair-lanes x 8 part ranges (two blocks per CU), 2 = 64 x 10 (three per CU).  The
 // small blocks cost a second table build per 256 pixels and pay while the large ones would leave CUs idle or
@@ -52,7 +55,21 @@ __host__ inline int raster2_shape(int B, int W, int K) {
 }
 constexpr int R2_STATIC = 1;             // parts a wave takes by the static deal before it draws from the shared list (1..4)
 constexpr int R2_MAX = 11;               // table rows + 1 of the largest instantiation
-__host__ __device__ constexpr int trec_of(int AR, int R) { return (AR / (4 * R)) * 4; }   // records an arena of AR floats holds at R rows per group
+
+// The block's geometry, for the kernel, its launcher (seg_raster_impl) and smplr_seg_raster_plan alike.
+struct R2Block { int pl, ng; };          // pair-lanes x part ranges
+// by shape id (SMPLR_RASTER_SHAPE, raster2_shape): 1 = 128 x 8, 2 = 64 x 10, 3 = 128 x 4 (by the environment only)
+__host__ __device__ constexpr R2Block raster2_block(int shape) {
+  return shape == 2 ? R2Block{64, 10} : shape == 3 ? R2Block{PLN, 4} : R2Block{PLN, 8};
+}
+// floats of the table's arena (three 64-lane blocks per CU: 51 KB each)
+__host__ __device__ constexpr int raster2_arena(int pl) { return pl == 64 ? 6144 : ARENA; }
+// table rows per group under a block with `nrows` image rows: the smallest instantiation that holds them
+__host__ __device__ constexpr int raster2_group_rows(int nrows) {
+  return nrows <= 4 ? 5 : nrows <= 6 ? 7 : nrows <= 8 ? 9 : R2_MAX;
+}
+// records an arena of AR floats holds at R rows per group
+__host__ __device__ constexpr int trec_of(int AR, int R) { return (AR / (4 * R)) * 4; }
 
 template <int R>
 __device__ __forceinline__ void scan2_body(const char *tb, unsigned vu, unsigned vt, int off, int gid, f32x2 fc2,
@@ -73,6 +90,34 @@ __device__ __forceinline__ void scan2_body(const char *tb, unsigned vu, unsigned
   bestB = nb;
 }
 
+// the table's groups gid .. gid + ngrp - 1 against the lane's two pixels, four groups per trip
+template <int R>
+__device__ __forceinline__ void scan2_groups(const char *tb, int gid, int ngrp, unsigned va, f32x2 fc2, float &bestA,
+                                             float &bestB, int &gA, int &gB) {
+  constexpr int GB = R * 16;             // bytes per group
+  unsigned vu = (unsigned)gid * GB, vt = vu + va;
+  asm volatile("" : "+v"(vu));
+  asm volatile("" : "+v"(vt));
+  int k = 0;
+  for (; k + 4 <= ngrp; k += 4) {
+    scan2_body<R>(tb, vu, vt, 0, gid, fc2, bestA, bestB, gA, gB);
+    scan2_body<R>(tb, vu, vt, GB, gid + 1, fc2, bestA, bestB, gA, gB);
+    scan2_body<R>(tb, vu, vt, 2 * GB, gid + 2, fc2, bestA, bestB, gA, gB);
+    scan2_body<R>(tb, vu, vt, 3 * GB, gid + 3, fc2, bestA, bestB, gA, gB);
+    vu += 4 * GB;
+    vt += 4 * GB;
+    gid += 4;
+  }
+  if ((ngrp - k) & 2) {
+    scan2_body<R>(tb, vu, vt, 0, gid, fc2, bestA, bestB, gA, gB);
+    scan2_body<R>(tb, vu, vt, GB, gid + 1, fc2, bestA, bestB, gA, gB);
+    vu += 2 * GB;
+    vt += 2 * GB;
+    gid += 2;
+  }
+  if ((ngrp - k) & 1) scan2_body<R>(tb, vu, vt, 0, gid, fc2, bestA, bestB, gA, gB);
+}
+
 // first record of group g (table row ra) whose key equals best -> its slot
 template <int R>
 __device__ __forceinline__ int rescan2(const char *tb, int g, unsigned va, f32x2 fc2, float best) {
@@ -86,97 +131,53 @@ __device__ __forceinline__ int rescan2(const char *tb, int g, unsigned va, f32x2
   return (best < INFINITY) ? w : -1;
 }
 
-// A wave's parts for its 64 pair-lanes, unit weights, table mode.  offv: the part offsets, one per lane; ordv: the parts
-// by size, one per lane.  Wave g of NG takes the list entries g, 2 NG - 1 - g, ... (boustrophedon) for its first
-// R2_STATIC parts and the rest from the counter the block's waves of this pixel half share (asked for before the part
-// in hand is scanned: the answer is there when it is needed).
-template <int R, int NG>
-__device__ __forceinline__ int scan2_parts(const char *tb, int offv, int ordv, int *ctr, int g, int P, bool lane0,
-                                           unsigned va, f32x2 fc2, float *myS, short *myA) {
-  constexpr int GB = R * 16;             // bytes per group
-  int done = 1, r = g;
-  while (r < P) {
-    // (the draw as a bare ds_add_rtn_u32 from lane 0: through __hip_atomic_fetch_add the compiler's wave-aggregation of
-    // atomics - mbcnt, a second exec detour, a count, a broadcast - wrapped it in a dozen instructions and, worse, waited
-    // for the answer on the spot; here nothing waits before the part in hand has been scanned.  LDS operations return in
-    // order, so every wait the compiler places for its own reads covers this older one too.)
-    int rn = 0;
-    if (done >= R2_STATIC) {
-      if (lane0) {
-        const unsigned ca = (unsigned)(size_t)(__attribute__((address_space(3))) int *)ctr;
-        asm volatile("ds_add_rtn_u32 %0, %1, %2" : "=v"(rn) : "v"(ca), "v"(1) : "memory");
-      }
-    }
-    const int p = __builtin_amdgcn_readlane(ordv, r);
-    const int beg = __builtin_amdgcn_readlane(offv, p), end = __builtin_amdgcn_readlane(offv, p + 1);
-    float bestA = INFINITY, bestB = INFINITY;
-    int sA_ = -1, sB_ = -1;
-    if (beg < end) {
-      int gid = beg >> 2;
-      const int ngrp = (end - beg) >> 2;
-      int gA = gid, gB = gid;
-      unsigned vu = (unsigned)gid * GB, vt = vu + va;
-      asm volatile("" : "+v"(vu));
-      asm volatile("" : "+v"(vt));
-      int g = 0;
-      for (; g + 4 <= ngrp; g += 4) {
-        scan2_body<R>(tb, vu, vt, 0, gid, fc2, bestA, bestB, gA, gB);
-        scan2_body<R>(tb, vu, vt, GB, gid + 1, fc2, bestA, bestB, gA, gB);
-        scan2_body<R>(tb, vu, vt, 2 * GB, gid + 2, fc2, bestA, bestB, gA, gB);
-        scan2_body<R>(tb, vu, vt, 3 * GB, gid + 3, fc2, bestA, bestB, gA, gB);
-        vu += 4 * GB;
-        vt += 4 * GB;
-        gid += 4;
-      }
-      if ((ngrp - g) & 2) {
-        scan2_body<R>(tb, vu, vt, 0, gid, fc2, bestA, bestB, gA, gB);
-        scan2_body<R>(tb, vu, vt, GB, gid + 1, fc2, bestA, bestB, gA, gB);
-        vu += 2 * GB;
-        vt += 2 * GB;
-        gid += 2;
-      }
-      if ((ngrp - g) & 1) scan2_body<R>(tb, vu, vt, 0, gid, fc2, bestA, bestB, gA, gB);
-      sA_ = rescan2<R>(tb, gA, va, fc2, bestA);
-      sB_ = rescan2<R>(tb, gB, va + 16, fc2, bestB);
-    }
-    // (no test for an empty part: sqrt(inf) = inf and v_exp_f32(-inf) = +0 exactly)
-    myS[p] = fast_exp_neg(fast_sqrt(bestA));
-    myS[SLD + p] = fast_exp_neg(fast_sqrt(bestB));
-    myA[p] = (short)sA_;
-    myA[ALD + p] = (short)sB_;
-    const int sn = (done & 1) ? (done + 1) * NG - 1 - g : done * NG + g;       // the wave's done-th entry of the static deal
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rn) : : "memory");               // (the draw has long returned)
-    r = (done < R2_STATIC) ? sn : __builtin_amdgcn_readfirstlane(rn);
-    ++done;
+// The draw of the next part from the counter the block's waves of a pixel half share, as a bare ds_add_rtn_u32 from lane
+// 0: through __hip_atomic_fetch_add the compiler's wave-aggregation of atomics - mbcnt, a second exec detour, a count, a
+// broadcast - wrapped it in a dozen instructions and, worse, waited for the answer on the spot; here nothing waits before
+// the part in hand has been scanned.  LDS operations return in order, so every wait the compiler places for its own reads
+// covers this older one too.  rn is IN FLIGHT until part_next's wait (by reference: no copy may touch it before;
+// tests/test_isa_audit.py reads the assembly for that).
+__device__ __forceinline__ void part_draw(int &rn, int *ctr, bool lane0) {
+  if (lane0) {
+    const unsigned ca = (unsigned)(size_t)(__attribute__((address_space(3))) int *)ctr;
+    asm volatile("ds_add_rtn_u32 %0, %1, %2" : "=v"(rn) : "v"(ca), "v"(1) : "memory");
   }
-  return done - 1;
+}
+// the list entry wave g of NG takes after its done-th part: the static deal (g, 2 NG - 1 - g, ...: boustrophedon) for the
+// first R2_STATIC parts, then the draw's answer
+template <int NG>
+__device__ __forceinline__ int part_next(int done, int g, int &rn) {
+  const int sn = (done & 1) ? (done + 1) * NG - 1 - g : done * NG + g;
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rn) : : "memory");               // (the draw has long returned)
+  return (done < R2_STATIC) ? sn : __builtin_amdgcn_readfirstlane(rn);
 }
 
-// The same for a record list LONGER than the table (round 5): the list goes through the table in chunks of `trec`
+// A wave's parts for its 64 pair-lanes, unit weights, table mode.  offv: the part offsets, one per lane; ordv: the parts
+// by size, one per lane.  Wave g of NG takes its first R2_STATIC parts by the static deal and the rest from the shared
+// counter (asked for before the part in hand is scanned: the answer is there when it is needed).
+//
+// CHUNK = false, the hot form: the whole list is in the table, [c0, c1) is not looked at.  No test for an empty part
+// (sqrt(inf) = inf and v_exp_f32(-inf) = +0 exactly), the tracked group starts as the part's first and the winner
+// re-scan is unconditional, nothing is read back from the tiles.
+//
+// CHUNK = true, a record list LONGER than the table (round 5): the list goes through the table in chunks of `trec`
 // records, [c0, c1) this time, and a (pixel, part)'s running (smallest key, its record slot) waits in the block's score /
 // arg tiles between chunks.  A part is STARTED by the chunk its first record lies in (the last chunk also starts the parts
 // that begin at the very end of the list: the empty ones), CONTINUED by every later chunk it reaches into, and FINISHED -
-// its key turned into the score - by the chunk its last record lies in.  Keys, the strict '<' across groups and the
-// first-equal rule inside the winning group are scan2_parts': the winner over the chunks is the first record in list order
-// that attains the minimum, bit for bit what one pass over a table of the whole list (or raster_fwd_kernel) gives.  The
-// waves draw the parts as above in every chunk; parts the chunk does not touch cost a draw and two compares.
-template <int R, int NG>
-__device__ __forceinline__ int scan2_parts_chunk(const char *tb, int offv, int ordv, int *ctr, int g, int P, bool lane0,
-                                                 unsigned va, f32x2 fc2, float *myS, short *myA, int c0, int c1,
-                                                 bool last) {
-  constexpr int GB = R * 16;
+// its key turned into the score - by the chunk its last record lies in.  The winner over the chunks is the first record
+// in list order that attains the minimum, bit for bit what one pass over a table of the whole list (or
+// raster_fwd_kernel) gives.  The waves draw the parts in every chunk; parts the chunk does not touch cost a draw and two
+// compares.
+template <int R, int NG, bool CHUNK>
+__device__ __forceinline__ int scan2_parts(const char *tb, int offv, int ordv, int *ctr, int g, int P, bool lane0,
+                                           unsigned va, f32x2 fc2, float *myS, short *myA, int c0, int c1, bool last) {
   int done = 1, r = g;
   while (r < P) {
     int rn = 0;
-    if (done >= R2_STATIC) {
-      if (lane0) {
-        const unsigned ca = (unsigned)(size_t)(__attribute__((address_space(3))) int *)ctr;
-        asm volatile("ds_add_rtn_u32 %0, %1, %2" : "=v"(rn) : "v"(ca), "v"(1) : "memory");
-      }
-    }
+    if (done >= R2_STATIC) part_draw(rn, ctr, lane0);
     const int p = __builtin_amdgcn_readlane(ordv, r);
     const int beg = __builtin_amdgcn_readlane(offv, p), end = __builtin_amdgcn_readlane(offv, p + 1);
-    const bool start = beg >= c0 && (beg < c1 || last), cont = beg < c0 && end > c0;       // wave-uniform
+    const bool start = !CHUNK || (beg >= c0 && (beg < c1 || last)), cont = CHUNK && beg < c0 && end > c0;   // wave-uniform
     if (start || cont) {
       float bestA = INFINITY, bestB = INFINITY;
       int sA_ = -1, sB_ = -1;
@@ -186,49 +187,38 @@ __device__ __forceinline__ int scan2_parts_chunk(const char *tb, int offv, int o
         sA_ = myA[p];
         sB_ = myA[ALD + p];
       }
-      const int b = max(beg, c0), e = min(end, c1);
+      const int b = CHUNK ? max(beg, c0) : beg, e = CHUNK ? min(end, c1) : end;
       if (b < e) {
-        int gid = (b - c0) >> 2;                             // group of the TABLE (chunk-relative)
-        const int ngrp = (e - b) >> 2;
-        int gA = -1, gB = -1;                                // no group of this chunk has lowered the minimum yet
-        unsigned vu = (unsigned)gid * GB, vt = vu + va;
-        asm volatile("" : "+v"(vu));
-        asm volatile("" : "+v"(vt));
-        int k = 0;
-        for (; k + 4 <= ngrp; k += 4) {
-          scan2_body<R>(tb, vu, vt, 0, gid, fc2, bestA, bestB, gA, gB);
-          scan2_body<R>(tb, vu, vt, GB, gid + 1, fc2, bestA, bestB, gA, gB);
-          scan2_body<R>(tb, vu, vt, 2 * GB, gid + 2, fc2, bestA, bestB, gA, gB);
-          scan2_body<R>(tb, vu, vt, 3 * GB, gid + 3, fc2, bestA, bestB, gA, gB);
-          vu += 4 * GB;
-          vt += 4 * GB;
-          gid += 4;
-        }
-        if ((ngrp - k) & 2) {
-          scan2_body<R>(tb, vu, vt, 0, gid, fc2, bestA, bestB, gA, gB);
-          scan2_body<R>(tb, vu, vt, GB, gid + 1, fc2, bestA, bestB, gA, gB);
-          vu += 2 * GB;
-          vt += 2 * GB;
-          gid += 2;
-        }
-        if ((ngrp - k) & 1) scan2_body<R>(tb, vu, vt, 0, gid, fc2, bestA, bestB, gA, gB);
-        // (a lane whose minimum this chunk did not lower keeps the slot it came with: the earlier record wins a tie)
-        const int nA = rescan2<R>(tb, max(gA, 0), va, fc2, bestA), nB = rescan2<R>(tb, max(gB, 0), va + 16, fc2, bestB);
-        sA_ = gA >= 0 ? nA + c0 : sA_;
-        sB_ = gB >= 0 ? nB + c0 : sB_;
+        const int gid = CHUNK ? (b - c0) >> 2 : b >> 2;      // group of the TABLE (chunk-relative)
+        int gA = CHUNK ? -1 : gid, gB = gA;                  // CHUNK: no group of this chunk has lowered the minimum yet
+        scan2_groups<R>(tb, gid, (e - b) >> 2, va, fc2, bestA, bestB, gA, gB);
+        // (CHUNK: a lane whose minimum this chunk did not lower keeps the slot it came with: the earlier record wins a tie)
+        const int nA = rescan2<R>(tb, CHUNK ? max(gA, 0) : gA, va, fc2, bestA);
+        const int nB = rescan2<R>(tb, CHUNK ? max(gB, 0) : gB, va + 16, fc2, bestB);
+        sA_ = !CHUNK ? nA : gA >= 0 ? nA + c0 : sA_;
+        sB_ = !CHUNK ? nB : gB >= 0 ? nB + c0 : sB_;
       }
-      const bool fin = end <= c1;                            // (the last chunk ends at the list's end: always)
+      const bool fin = !CHUNK || end <= c1;                  // (the last chunk ends at the list's end: always)
       myS[p] = fin ? fast_exp_neg(fast_sqrt(bestA)) : bestA;
       myS[SLD + p] = fin ? fast_exp_neg(fast_sqrt(bestB)) : bestB;
       myA[p] = (short)sA_;
       myA[ALD + p] = (short)sB_;
     }
-    const int sn = (done & 1) ? (done + 1) * NG - 1 - g : done * NG + g;
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rn) : : "memory");
-    r = (done < R2_STATIC) ? sn : __builtin_amdgcn_readfirstlane(rn);
+    r = part_next<NG>(done, g, rn);
     ++done;
   }
   return done - 1;
+}
+
+// one pass of the block's waves over the table at Rb rows per group ([c0, c1), last: the chunked form's)
+template <int NG, bool CHUNK>
+__device__ __forceinline__ int scan2_pass(int Rb, const char *tb, int offv, int ordv, int *ctr, int g, int P, bool lane0,
+                                          unsigned va, f32x2 fc2, float *myS, short *myA, int c0 = 0, int c1 = 0,
+                                          bool last = true) {
+  if (Rb == 5) return scan2_parts<5, NG, CHUNK>(tb, offv, ordv, ctr, g, P, lane0, va, fc2, myS, myA, c0, c1, last);
+  if (Rb == 7) return scan2_parts<7, NG, CHUNK>(tb, offv, ordv, ctr, g, P, lane0, va, fc2, myS, myA, c0, c1, last);
+  if (Rb == 9) return scan2_parts<9, NG, CHUNK>(tb, offv, ordv, ctr, g, P, lane0, va, fc2, myS, myA, c0, c1, last);
+  return scan2_parts<11, NG, CHUNK>(tb, offv, ordv, ctr, g, P, lane0, va, fc2, myS, myA, c0, c1, last);
 }
 
 // MET (with LOSS): the metrics epilogue - each pixel's arg-max over the 32 scores seg would receive, counted by (label,
@@ -245,7 +235,7 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
   constexpr int PW = PL / 64;            // waves per part range (64 pair-lanes each)
   __shared__ float sS[TS * SLD];
   __shared__ short sA[TS * ALD];
-  constexpr int AR = PL == 64 ? 6144 : ARENA;            // floats of the table's arena (three 64-lane blocks per CU: 51 KB each)
+  constexpr int AR = raster2_arena(PL);
   __shared__ f32x4 sTab[AR / 4];         // [group][row 0 = u | rows 1.. = (v - row)^2][4 records]
   __shared__ int sCtr[PW];               // next free entry of the part list, per 64 pair-lanes
   const int bid = blockIdx.x;
@@ -262,10 +252,9 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
   // this lane's pixel pair: pair-lane L = Q W + c -> pixels (2Q, c), (2Q + 1, c)
   const int Lb = pw * 64 + lane;
   const int L = min(tile * PL + Lb, nl - 1);
-  const int Q = (int)(((unsigned)L * wmagic) >> 24), c = L - Q * W;     // L < W^2 <= 25600: exact (see raster_fwd_kernel)
+  const int Q = div_w(L, wmagic), c = L - Q * W;
   // rows under the block: pairs Qf .. Ql
-  const int Qf = (int)(((unsigned)min(tile * PL, nl - 1) * wmagic) >> 24);
-  const int Ql = (int)(((unsigned)min(tile * PL + PL - 1, nl - 1) * wmagic) >> 24);
+  const int Qf = div_w(min(tile * PL, nl - 1), wmagic), Ql = div_w(min(tile * PL + PL - 1, nl - 1), wmagic);
   const int row0 = 2 * Qf, nrows = 2 * (Ql - Qf + 1);    // (an odd W's last pair has a phantom row W: built, never written out)
   const float4 *Gn = G + (size_t)n * S;
   const int *goffn = goff + (size_t)n * goff_stride(P);
@@ -277,8 +266,7 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
   const bool unit_m = goffn[P + 1] == 0;                 // every far-reaching weight is 1 (block-uniform)
   const int goffv = goffn[min(lane, P)];                 // the part offsets, one per lane, in every wave
   const int ordv = goffn[P + 2 + (lane & 31)];           // ... and the parts by size (seg_bin_kernel)
-  // table rows per group at this block: the smallest instantiation that holds its image rows
-  const int Rb = nrows <= 4 ? 5 : nrows <= 6 ? 7 : nrows <= 8 ? 9 : 11;
+  const int Rb = raster2_group_rows(nrows);              // table rows per group at this block
   const int trec = trec_of(AR, Rb);
   // thread i asks for record i (and i + NT ... while the arena could hold it) before the list length is known: the
   // records share the block's first round trip to memory; slots beyond the list hold stale bytes nobody reads
@@ -288,7 +276,7 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
   for (int h = 0; h < NH; ++h)
     rcs[h] = (h == 0 || tid + h * NT < trec) ? Gn[min(tid + h * NT, S - 1)] : make_float4(0.f, 0.f, 0.f, 0.f);
   // block-uniform: the table form (unit weights, at most 10 image rows under the block); a list longer than the table
-  // goes through it in chunks of trec records (scan2_parts_chunk)
+  // goes through it in chunks of trec records (scan2_parts<.., CHUNK = true>)
   const bool tblm = unit_m && nrows <= R2_MAX - 1;
   const bool tbl = tblm && lbase <= trec, chunked = tblm && !tbl;
   // merge / write-out items: item e = it * NT + tid is tile pixel e / 4 (= 2 x pair-lane + row of the pair); its lane
@@ -304,7 +292,7 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
     const int pl = (it * NT + tid) >> 2;
     const int Li = tile * PL + (pl >> 1);
     const int Lc = min(Li, nl - 1);
-    const int Qi = (int)(((unsigned)Lc * wmagic) >> 24), ci = Lc - Qi * W;
+    const int Qi = div_w(Lc, wmagic), ci = Lc - Qi * W;
     const int ri = 2 * Qi + (pl & 1);
     const bool ok = Li < nl && ri < W && (TS * 4 % NT == 0 || pl < TS);       // (threads past the tile's items: none)
     const int qq = ok ? ri * W + ci : -1;                // the item's pixel (row-major, unflipped), -1: none
@@ -369,20 +357,13 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
     const char *tb = reinterpret_cast<const char *>(sTab);
     const unsigned va = (unsigned)(1 + 2 * (Q - Qf)) * 16u;      // byte offset of the upper pixel's table row in a group
     if (tbl) {
-      if (Rb == 5) ndone = scan2_parts<5, NG2>(tb, offv, ordv, &sCtr[pw], g, P, lane == 0, va, fc2, myS, myA);
-      else if (Rb == 7) ndone = scan2_parts<7, NG2>(tb, offv, ordv, &sCtr[pw], g, P, lane == 0, va, fc2, myS, myA);
-      else if (Rb == 9) ndone = scan2_parts<9, NG2>(tb, offv, ordv, &sCtr[pw], g, P, lane == 0, va, fc2, myS, myA);
-      else ndone = scan2_parts<11, NG2>(tb, offv, ordv, &sCtr[pw], g, P, lane == 0, va, fc2, myS, myA);
+      ndone = scan2_pass<NG2, false>(Rb, tb, offv, ordv, &sCtr[pw], g, P, lane == 0, va, fc2, myS, myA);
     } else if (chunked) {
       for (int c0 = 0;;) {
         const int c1 = min(c0 + trec, lbase);
         const bool last = c1 == lbase;
-        int nd;
-        if (Rb == 5) nd = scan2_parts_chunk<5, NG2>(tb, offv, ordv, &sCtr[pw], g, P, lane == 0, va, fc2, myS, myA, c0, c1, last);
-        else if (Rb == 7) nd = scan2_parts_chunk<7, NG2>(tb, offv, ordv, &sCtr[pw], g, P, lane == 0, va, fc2, myS, myA, c0, c1, last);
-        else if (Rb == 9) nd = scan2_parts_chunk<9, NG2>(tb, offv, ordv, &sCtr[pw], g, P, lane == 0, va, fc2, myS, myA, c0, c1, last);
-        else nd = scan2_parts_chunk<11, NG2>(tb, offv, ordv, &sCtr[pw], g, P, lane == 0, va, fc2, myS, myA, c0, c1, last);
-        ndone += nd;
+        ndone += scan2_pass<NG2, true>(Rb, tb, offv, ordv, &sCtr[pw], g, P, lane == 0, va, fc2, myS, myA, c0, c1,
+                                       last);
         if (last) break;
         c0 = c1;
         // the next chunk's records (asked for here, not before the scan: eight registers the scan would have to hold
@@ -431,48 +412,18 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
   if (MET) {
     for (int i = tid; i < NCONF; i += NT) hist[i] = 0u;
   }
-  // Merge of the local records and write-out.  raster_fwd_kernel's scheme (LDS atomic max on the score bits, ties keep
-  // the earlier winner, global before local) with FOUR lanes per pixel: a lane takes every 4th record of the pixel's list,
-  // then the channel chunks sub and sub + 4.  The background's sum keeps raster_fwd_kernel's tree bit for bit: chunk sums
+  // Merge of the local records and write-out.  raster_fwd_kernel's scheme (merge_local: global before local) with FOUR
+  // lanes per pixel: a lane takes every 4th record of the pixel's list, then the channel chunks sub and sub + 4.  The background's sum keeps raster_fwd_kernel's tree bit for bit: chunk sums
   // s_j = (v0 + v1) + (v2 + v3); Qlo = (s0 + s1) + (s2 + s3), Qhi = (s4 + s5) + (s6 + s7) by two quad exchanges each
   // (there: the 8-lane tree's first two steps); sum = Qlo + Qhi (there: lane 0 + lane 7 of the half-mirror step, and
   // fp32 addition commutes).
-  auto quad_sum = [](float v) {
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));    // quad_perm 1,0,3,2
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));    // quad_perm 2,3,0,1
-    return v;
-  };
-  auto quad_max = [](float v) {
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false)));
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false)));
-    return v;
-  };
-  float den_[NIT], st_[NIT], eg_[NIT];
-  unsigned po_[NIT];
+  LossPx px[NIT];                                          // LOSS: what each merge step's pixel needs for its loss
   int pred_[NIT];                                          // MET: the pixel's arg-max channel, in all 4 of its lanes
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int e = it * NT + tid;
     const int pl = (TS * 4 % NT == 0) ? (e >> 2) : min(e >> 2, TS - 1), cA = sub * 4, cB = 16 + sub * 4;
-    {
-      int *rowS = reinterpret_cast<int *>(&sS[pl * SLD + 1]);
-      short *rowA = &sA[pl * ALD + 1];
-      const int l1 = l1a[it];
-      int i = l0a[it] + sub;
-      uint2 rec = lr0[it];
-      while (__any(i < l1)) {
-        const uint2 nxt = lrecn[min(i + 4, K - 1)];        // next step's record, in flight during this one
-        if (i < l1) {
-          const int sc = __float_as_int(fast_exp_neg(__uint_as_float(rec.x)));
-          const int p = (int)rec.y;
-          const int old = atomicMax(&rowS[p], sc);
-          const int fin = __hip_atomic_load(&rowS[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);   // (a ds_read, not a flat load)
-          if (old < sc && fin == sc) rowA[p] = (short)(lbase + i);
-        }
-        rec = nxt;
-        i += 4;
-      }
-    }
+    merge_local<4>(sS, sA, pl, lrecn, l0a[it] + sub, l1a[it], lr0[it], lbase, K);
     const float *ts = &sS[pl * SLD];
     const short *ta = &sA[pl * ALD];
     float va[4], vb[4];
@@ -503,7 +454,7 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
     const int qq = qqa[it];
     if (MET) {
       // over exactly the values seg receives (channel 0 = the background): the lane's 8 channels in ascending order,
-      // then (value, channel) across the pixel's 4 lanes by two quad exchanges (all lanes take part)
+      // then (value, channel) across the pixel's 4 lanes (all lanes take part)
       float bv = va[0];
       int bi = cA;
 #pragma unroll
@@ -512,32 +463,28 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
 #pragma unroll
       for (int t = 0; t < 4; ++t)
         if (argmax_beats(vb[t], cB + t, bv, bi)) { bv = vb[t]; bi = cB + t; }
-      const float ov1 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(bv), 0xB1, 0xF, 0xF, false));
-      const int oi1 = __builtin_amdgcn_update_dpp(0, bi, 0xB1, 0xF, 0xF, false);       // quad_perm 1,0,3,2
-      if (argmax_beats(ov1, oi1, bv, bi)) { bv = ov1; bi = oi1; }
-      const float ov2 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(bv), 0x4E, 0xF, 0xF, false));
-      const int oi2 = __builtin_amdgcn_update_dpp(0, bi, 0x4E, 0xF, 0xF, false);       // quad_perm 2,3,0,1
-      if (argmax_beats(ov2, oi2, bv, bi)) bi = oi2;
-      pred_[it] = bi;
+      pred_[it] = quad_argmax(bv, bi);
     }
     if (LOSS) {                                            // (C == 32: checked by the launcher; all lanes take part)
-      den_[it] = quad_sum((__expf(va[0]) + __expf(va[1])) + (__expf(va[2]) + __expf(va[3]))) +
+      px[it].den = quad_sum((__expf(va[0]) + __expf(va[1])) + (__expf(va[2]) + __expf(va[3]))) +
                  quad_sum((__expf(vb[0]) + __expf(vb[1])) + (__expf(vb[2]) + __expf(vb[3])));
       const int t = lab[it];
       const float vta = (t & 2) ? ((t & 1) ? va[3] : va[2]) : ((t & 1) ? va[1] : va[0]);
       const float vtb = (t & 2) ? ((t & 1) ? vb[3] : vb[2]) : ((t & 1) ? vb[1] : vb[0]);
       // the labelled class' score in all 4 lanes (+ exact zeros)
-      st_[it] = quad_sum(cA == (t & ~3) ? vta : 0.0f) + quad_sum(cB == (t & ~3) ? vtb : 0.0f);
+      px[it].st = quad_sum(cA == (t & ~3) ? vta : 0.0f) + quad_sum(cB == (t & ~3) ? vtb : 0.0f);
       // the background's exp where the clip's gate is open, else a negative number, from the pixel's lane 0 to all 4
       const float eg = aa[0] ? __expf(va[0]) : -1.0f;
-      eg_[it] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(eg), 0x00, 0xF, 0xF, false));
+      px[it].eg = dpp_f<0x00>(eg);
+      px[it].w = wlab[it];
+      px[it].t = t;
     }
     unsigned po = ~0u;
     if (qq >= 0) {
-      const int rr = (int)(((unsigned)qq * wmagic) >> 24), cc = qq - rr * W;
+      const int rr = div_w(qq, wmagic), cc = qq - rr * W;
       po = (unsigned)((W - 1 - rr) * W + cc);              // rows flipped (:68); mesh base + 32-bit offset
     }
-    if (LOSS) po_[it] = po;
+    if (LOSS) px[it].po = po;
     if (qq >= 0) {
       if (lo.vmax && sub == 0) lo.vmax[(size_t)n * npix + po] = vmx;
       float *so = seg + (size_t)n * npix * C + po * (unsigned)C;
@@ -559,34 +506,7 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
       *reinterpret_cast<short4 *>(ao + cB) = o4;
     }
   }
-  if (LOSS) {
-    // the per-pixel end of the loss once for all merge steps of the lane: lane `it` of a pixel's 4 finishes step `it`
-    static_assert(!LOSS || NIT <= 4, "a pixel has four lanes");
-    float den = den_[0], st = st_[0], eg = eg_[0], w = wlab[0];
-    int t = lab[0];
-    unsigned po = po_[0];
-#pragma unroll
-    for (int it = 1; it < NIT; ++it) {
-      if (sub == it) {
-        den = den_[it]; st = st_[it]; eg = eg_[it]; w = wlab[it];
-        t = lab[it];
-        po = po_[it];
-      }
-    }
-    const float inv = __builtin_amdgcn_rcpf(den);
-    const float sm = __expf(st) * inv;
-    const float p = fminf(fmaxf(sm, K_EPS), 1.0f - K_EPS);                     // focal_loss.py:17
-    const bool inside = sm >= K_EPS && sm <= 1.0f - K_EPS && (unsigned)t < 32u;  // (a label outside the classes: no loss)
-    const float om = 1.0f - p, lg = __builtin_amdgcn_logf(p) * 0.6931471806f;
-    const float pg = pow_gamma(om, lo.gamma);
-    const float ls = (unsigned)t < 32u ? pg * ((-lg) * w) : 0.0f;              // :18, :41, :43-44
-    const float k1 = inside ? (w * (dpow_gamma(om, lo.gamma) * lg - pg * __builtin_amdgcn_rcpf(p))) * sm : 0.0f;
-    const float gbu = eg >= 0.0f ? ((t == 0 ? 1.0f : 0.0f) - eg * inv) : 0.0f;
-    if (sub < NIT && po != ~0u) {
-      lo.loss[(size_t)n * npix + po] = ls;
-      lo.stats[(size_t)n * npix + po] = make_float4(k1 * inv, k1 * gbu, k1, __int_as_float(t));
-    }
-  }
+  if (LOSS) loss_px_end(px, sub, lo, (size_t)n * npix);
   if (MET) {
     // (label, prediction) of every pixel of the tile into the block's counts (row 32: a label outside [0, 32)), then
     // one 64-bit atomic add per non-zero count into conf
@@ -612,10 +532,33 @@ __global__ __launch_bounds__(PL * NG2, (PL * NG2 > 512 ? 8 : 4)) SMPLR_RASTER_SG
 #endif
 }
 
+// SMPLR_RASTER=1: the one-pixel-per-lane kernel of rounds 1-3 (raster1.hip, kept for A/B runs)
+static int raster_version() {
+  static const int version = getenv("SMPLR_RASTER") ? atoi(getenv("SMPLR_RASTER")) : 2;
+  return version;
+}
+// SMPLR_RASTER_SHAPE: the two-pixel kernel's block, 0 = by batch (raster2_shape), else raster2_block's shape id
+static int raster2_shape_id(int B, int W, int K) {
+  static const int shape_env = getenv("SMPLR_RASTER_SHAPE") ? atoi(getenv("SMPLR_RASTER_SHAPE")) : 0;
+  return shape_env ? shape_env : raster2_shape(B, W, K);
+}
+
+template <bool LOSS, bool MET, int SHAPE, class Args>
+static void raster2_launch_shape(EvLaunch at, const Args &args) {
+  constexpr R2Block b = raster2_block(SHAPE);
+  at.block = dim3(b.pl * b.ng);
+  std::apply([&](auto... a) { ev_launch<&raster2_fwd_kernel<LOSS, b.ng, b.pl, MET>>(at, a...); }, args);
+}
+template <bool LOSS, bool MET, class Args>
+static void raster2_launch(int shape, const EvLaunch &at, const Args &args) {
+  if (shape == 2) raster2_launch_shape<LOSS, MET, 2>(at, args);
+  else if (shape == 3) raster2_launch_shape<LOSS, MET, 3>(at, args);
+  else raster2_launch_shape<LOSS, MET, 1>(at, args);
+}
+
 // stage 2: the pair loop + merge + write-out over a binned workspace
-// kernel_ms != NULL: the launch carries start / stop events (hipExtLaunchKernel) and the call WAITS for the kernel and
-// returns its own duration - begin to end on the device, what rocprofv3's kernel trace reports, without the dispatch
-// gap an event pair around a launch includes.  A measurement aid for bench.py's roofline only.
+// kernel_ms != NULL: the launch carries start / stop events (ev_launch) and the call WAITS for the kernel and returns its
+// own duration - what rocprofv3's kernel trace reports.  A measurement aid for bench.py's roofline only.
 static int seg_raster_impl(const char *fn, int B, int W, int P, int K, const void *workspace, const float *rec,
                            float *seg, int16_t *arg, void *stream, LossOut lo = LossOut{}, float *kernel_ms = nullptr,
                            uint64_t *conf = nullptr) {
@@ -631,12 +574,8 @@ static int seg_raster_impl(const char *fn, int B, int W, int P, int K, const voi
   const SegWs ws = seg_ws_layout(B, W, P, K);
   const int S = seg_slots(P, K);
   const char *base = reinterpret_cast<const char *>(workspace);
-  // SMPLR_RASTER=1: the one-pixel-per-lane kernel of rounds 1-3 (raster1.hip, kept for A/B runs); SMPLR_RASTER_SHAPE: the
-  // two-pixel kernel's block, 0 = by batch (below), 1 = 128 pair-lanes x 8 part ranges, 2 = 64 x 10, 3 = 128 x 4
-  static const int version = getenv("SMPLR_RASTER") ? atoi(getenv("SMPLR_RASTER")) : 2;
-  static const int shape_env = getenv("SMPLR_RASTER_SHAPE") ? atoi(getenv("SMPLR_RASTER_SHAPE")) : 0;
-  SMPLR_REQUIRE(!conf || version != 1, "%s: the metrics epilogue (conf) exists in the default rasteriser only, not with "
-                "SMPLR_RASTER=1", fn);
+  SMPLR_REQUIRE(!conf || raster_version() != 1, "%s: the metrics epilogue (conf) exists in the default rasteriser only, "
+                "not with SMPLR_RASTER=1", fn);
   unsigned long long *confp = reinterpret_cast<unsigned long long *>(conf);
   const float4 *Gp = reinterpret_cast<const float4 *>(rec);
   const int *goffp = reinterpret_cast<const int *>(base + ws.goff_off);
@@ -648,34 +587,16 @@ static int seg_raster_impl(const char *fn, int B, int W, int P, int K, const voi
     SMPLR_HIP(hipEventCreate(&e0));
     SMPLR_HIP(hipEventCreate(&e1));
   }
-  if (version == 1) {
+  if (raster_version() == 1) {
     raster1_launch(Gp, goffp, lsp, lrp, P, K, S, W, B, seg, argp, lo, as_stream(stream), e0, e1);
   } else {
-    const int shape = shape_env ? shape_env : raster2_shape(B, W, K);
-    const int pl = shape == 2 ? 64 : PLN;
+    const int shape = raster2_shape_id(B, W, K), pl = raster2_block(shape).pl;
     const int nl = ((W + 1) / 2) * W, nt2 = (nl + pl - 1) / pl;
-    const int grid2 = 8 * ((B + 7) / 8) * nt2;
-    const unsigned wm = (unsigned)(((1u << 24) + W - 1) / W);
-#define SMPLR_RASTER2_LAUNCH(LOSS_, MET_, NG_, PL_)                                                                 \
-  {                                                                                                                 \
-    if (kernel_ms)                                                                                                  \
-      hipExtLaunchKernelGGL((raster2_fwd_kernel<LOSS_, NG_, PL_, MET_>), dim3(grid2), dim3(PL_ * NG_), 0,            \
-                            as_stream(stream), e0, e1, 0, Gp, goffp, lsp, lrp, P, K, S, W, B, nt2, seg, argp, wm, lo, \
-                            confp);                                                                                 \
-    else                                                                                                            \
-      hipLaunchKernelGGL((raster2_fwd_kernel<LOSS_, NG_, PL_, MET_>), dim3(grid2), dim3(PL_ * NG_), 0,               \
-                         as_stream(stream), Gp, goffp, lsp, lrp, P, K, S, W, B, nt2, seg, argp, wm, lo, confp);     \
-  }
-#define SMPLR_RASTER2_SHAPES(LOSS_, MET_)                                                                           \
-  {                                                                                                                 \
-    if (shape == 2) SMPLR_RASTER2_LAUNCH(LOSS_, MET_, 10, 64)                                                       \
-    else if (shape == 3) SMPLR_RASTER2_LAUNCH(LOSS_, MET_, 4, 128)                                                  \
-    else SMPLR_RASTER2_LAUNCH(LOSS_, MET_, 8, 128)                                                                  \
-  }
-    if (conf) SMPLR_RASTER2_SHAPES(true, true) else if (with_loss) SMPLR_RASTER2_SHAPES(true, false)
-    else SMPLR_RASTER2_SHAPES(false, false)
-#undef SMPLR_RASTER2_SHAPES
-#undef SMPLR_RASTER2_LAUNCH
+    const EvLaunch at{dim3(8 * ((B + 7) / 8) * nt2), dim3(), as_stream(stream), e0, e1};
+    const auto args = std::make_tuple(Gp, goffp, lsp, lrp, P, K, S, W, B, nt2, seg, argp, w_magic(W), lo, confp);
+    if (conf) raster2_launch<true, true>(shape, at, args);
+    else if (with_loss) raster2_launch<true, false>(shape, at, args);
+    else raster2_launch<false, false>(shape, at, args);
   }
   SMPLR_LAUNCH_CHECK(fn);
   if (kernel_ms) {
@@ -687,14 +608,22 @@ static int seg_raster_impl(const char *fn, int B, int W, int P, int K, const voi
   return 0;
 }
 
-static int seg_fwd_impl(const char *fn, const float *proj, float *mask, bool fuse_vis, int grid_wh, int ref_compat,
-                        int B, int VP, int W, const int32_t *part_pos, const int32_t *part_off, int P, int K,
-                        void *workspace, float *seg, int16_t *arg, float *rec, int16_t *vslot, void *stream) {
-  SMPLR_REQUIRE(B == 0 || (seg && arg), "%s: null pointer", fn);
+// The forward pass of every entry point that bins: optionally skin (sk != NULL: seg_bin_kernel skins its own vertices),
+// bin, then rasterise with the optional loss (lo) and metrics (conf) epilogues.
+static int seg_fwd_impl(const char *fn, const SkinIn *sk, const float *proj, float *mask, bool fuse_vis, int grid_wh,
+                        int ref_compat, int B, int VP, int W, const int32_t *part_pos, const int32_t *part_off, int P,
+                        int K, void *workspace, float *seg, int16_t *arg, float *rec, int16_t *vslot, void *stream,
+                        LossOut lo = LossOut{}, uint64_t *conf = nullptr) {
+  if (sk) SMPLR_REQUIRE(B <= 0 || (sk->v_posed && sk->top4 && sk->A && sk->cam), "%s: null pointer", fn);
+  else SMPLR_REQUIRE(B == 0 || (seg && arg), "%s: null pointer", fn);
+  // (before the binning launch: a refused conf must not leave half a pass behind)
+  SMPLR_REQUIRE(!conf || lo.loss, "%s: the metrics epilogue (conf) needs the loss epilogue", fn);
+  SMPLR_REQUIRE(!conf || raster_version() != 1, "%s: the metrics epilogue (conf) exists in the default rasteriser only, "
+                "not with SMPLR_RASTER=1", fn);
   int rc = seg_bin_impl(fn, proj, mask, fuse_vis, grid_wh, ref_compat, B, VP, W, part_pos, part_off, P, K, workspace,
-                        rec, vslot, stream);
+                        rec, vslot, stream, sk ? *sk : SkinIn{});
   if (rc) return rc;
-  return seg_raster_impl(fn, B, W, P, K, workspace, rec, seg, arg, stream);
+  return seg_raster_impl(fn, B, W, P, K, workspace, rec, seg, arg, stream, lo, nullptr, conf);
 }
 }  // namespace smplr
 
@@ -708,14 +637,14 @@ int smplr_seg_raster(int B, int W, int P, int K, const void *workspace, const fl
 int smplr_seg_fwd(const float *proj, const float *mask, int B, int VP, int W, const int32_t *part_pos,
                   const int32_t *part_off, int P, int K, void *workspace, float *seg, int16_t *arg,
                   float *rec, int16_t *vslot, void *stream) {
-  return smplr::seg_fwd_impl("smplr_seg_fwd", proj, const_cast<float *>(mask), false, 0, 0, B, VP, W, part_pos,
+  return smplr::seg_fwd_impl("smplr_seg_fwd", nullptr, proj, const_cast<float *>(mask), false, 0, 0, B, VP, W, part_pos,
                              part_off, P, K, workspace, seg, arg, rec, vslot, stream);
 }
 
 int smplr_vis_seg_fwd(const float *proj, int B, int VP, int W, int grid_wh, int ref_compat,
                       const int32_t *part_pos, const int32_t *part_off, int P, int K, void *workspace,
                       float *mask, float *seg, int16_t *arg, float *rec, int16_t *vslot, void *stream) {
-  return smplr::seg_fwd_impl("smplr_vis_seg_fwd", proj, mask, true, grid_wh, ref_compat, B, VP, W, part_pos,
+  return smplr::seg_fwd_impl("smplr_vis_seg_fwd", nullptr, proj, mask, true, grid_wh, ref_compat, B, VP, W, part_pos,
                              part_off, P, K, workspace, seg, arg, rec, vslot, stream);
 }
 
@@ -723,13 +652,9 @@ int smplr_skin_vis_seg_fwd(const float *v_posed, const float *lbs_top4, const fl
                            int B, int V, int W, int grid_wh, int ref_compat, const int32_t *part_pos,
                            const int32_t *part_off, int P, int K, void *workspace, float *verts, float *proj,
                            float *mask, float *seg, int16_t *arg, float *rec, int16_t *vslot, void *stream) {
-  using namespace smplr;
-  SMPLR_REQUIRE(B <= 0 || (v_posed && lbs_top4 && A && cam), "smplr_skin_vis_seg_fwd: null pointer");
-  const SkinIn sk{v_posed, lbs_top4, A, cam, x_stride, verts, proj};
-  int rc = seg_bin_impl("smplr_skin_vis_seg_fwd", proj, mask, true, grid_wh, ref_compat, B, V, W, part_pos, part_off, P,
-                        K, workspace, rec, vslot, stream, sk);
-  if (rc) return rc;
-  return seg_raster_impl("smplr_skin_vis_seg_fwd", B, W, P, K, workspace, rec, seg, arg, stream);
+  const smplr::SkinIn sk{v_posed, lbs_top4, A, cam, x_stride, verts, proj};
+  return smplr::seg_fwd_impl("smplr_skin_vis_seg_fwd", &sk, proj, mask, true, grid_wh, ref_compat, B, V, W, part_pos,
+                             part_off, P, K, workspace, seg, arg, rec, vslot, stream);
 }
 
 int smplr_seg_raster_timed(int B, int W, int P, int K, const void *workspace, const float *rec, float *seg, int16_t *arg,
@@ -742,22 +667,19 @@ int smplr_seg_raster_timed(int B, int W, int P, int K, const void *workspace, co
 int smplr_seg_raster_plan(int B, int W, int P, int K, int32_t *info, int32_t *tile_records) {
   using namespace smplr;
   if (B <= 0 || W <= 0 || W > 160 || P < 1 || P > 31 || K <= 0 || K > BIN_T * IPT_MAX) return 0;
-  static const int shape_env = getenv("SMPLR_RASTER_SHAPE") ? atoi(getenv("SMPLR_RASTER_SHAPE")) : 0;
-  const int shape = shape_env ? shape_env : raster2_shape(B, W, K);
-  const int pl = shape == 2 ? 64 : PLN, ng = shape == 2 ? 10 : shape == 3 ? 4 : 8;
-  const int ar = pl == 64 ? 6144 : ARENA;                  // raster2_fwd_kernel's AR
+  const R2Block b = raster2_block(raster2_shape_id(B, W, K));
+  const int pl = b.pl, ar = raster2_arena(pl);
   const int nq = (W + 1) / 2, nl = nq * W, nt = (nl + pl - 1) / pl;
   int tmax = 0, tmin = 1 << 30, tall = 0;
   for (int t = 0; t < nt; ++t) {                           // the kernel's own row count per tile
     const int Qf = std::min(t * pl, nl - 1) / W, Ql = std::min(t * pl + pl - 1, nl - 1) / W;
     const int nrows = 2 * (Ql - Qf + 1);
-    const int Rb = nrows <= 4 ? 5 : nrows <= 6 ? 7 : nrows <= 8 ? 9 : 11;
-    const int tr = nrows <= R2_MAX - 1 ? trec_of(ar, Rb) : 0;
+    const int tr = nrows <= R2_MAX - 1 ? trec_of(ar, raster2_group_rows(nrows)) : 0;
     if (tile_records) tile_records[t] = tr;
     if (tr) { tmax = std::max(tmax, tr); tmin = std::min(tmin, tr); } else tall = 1;
   }
   if (info) {
-    info[0] = pl; info[1] = ng; info[2] = nt; info[3] = goff_stride(P);
+    info[0] = pl; info[1] = b.ng; info[2] = nt; info[3] = goff_stride(P);
     info[4] = tmax; info[5] = tmin == (1 << 30) ? 0 : tmin; info[6] = tall; info[7] = 0;
   }
   return nt;
@@ -795,19 +717,10 @@ int smplr_skin_vis_seg_fwd_ex_conf(const float *v_posed, const float *lbs_top4, 
                                    const int32_t *labels, const float *class_w, float gamma, float *verts, float *proj,
                                    float *mask, float *seg, int16_t *arg, float *rec, int16_t *vslot, float *loss,
                                    float *stats, float *vmax, uint64_t *conf, void *stream) {
-  using namespace smplr;
-  SMPLR_REQUIRE(B <= 0 || (v_posed && lbs_top4 && A && cam), "smplr_skin_vis_seg_fwd_ex: null pointer");
-  // (before the binning launch: a refused conf must not leave half a pass behind)
-  SMPLR_REQUIRE(!conf || loss, "smplr_skin_vis_seg_fwd_ex: the metrics epilogue (conf) needs the loss epilogue");
-  SMPLR_REQUIRE(!conf || !(getenv("SMPLR_RASTER") && atoi(getenv("SMPLR_RASTER")) == 1),
-                "smplr_skin_vis_seg_fwd_ex: the metrics epilogue (conf) exists in the default rasteriser only, not with "
-                "SMPLR_RASTER=1");
-  const SkinIn sk{v_posed, lbs_top4, A, cam, x_stride, verts, proj};
-  int rc = seg_bin_impl("smplr_skin_vis_seg_fwd_ex", proj, mask, true, grid_wh, ref_compat, B, V, W, part_pos, part_off,
-                        P, K, workspace, rec, vslot, stream, sk);
-  if (rc) return rc;
-  return seg_raster_impl("smplr_skin_vis_seg_fwd_ex", B, W, P, K, workspace, rec, seg, arg, stream,
-                         LossOut{labels, class_w, gamma, loss, reinterpret_cast<float4 *>(stats), vmax}, nullptr, conf);
+  const smplr::SkinIn sk{v_posed, lbs_top4, A, cam, x_stride, verts, proj};
+  return smplr::seg_fwd_impl("smplr_skin_vis_seg_fwd_ex", &sk, proj, mask, true, grid_wh, ref_compat, B, V, W, part_pos,
+                             part_off, P, K, workspace, seg, arg, rec, vslot, stream,
+                             smplr::LossOut{labels, class_w, gamma, loss, reinterpret_cast<float4 *>(stats), vmax}, conf);
 }
 
 }  // extern "C"

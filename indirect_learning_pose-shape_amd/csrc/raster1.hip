@@ -8,9 +8,9 @@
 // re-evaluated once per (pixel, part) for the first arg-min; score = exp(-sqrt(key)) into a pixel-major LDS tile.  After
 // one barrier all waves merge the pixels' local records (8 lanes per pixel, LDS atomic max on the score bits) and write
 // the NHWC outputs as whole 128-B / 64-B pixel rows.  Record lists too long for the tables use the plain LDS copy, those
-// too long for LDS scalar loads.
-#include <hip/hip_ext.h>
-#include "raster_common.h"
+// too long for LDS scalar loads.  The scans are this kernel's own; merge, quad exchanges and the loss head's per-pixel end
+// are raster_device.h's, shared with raster2_fwd_kernel.
+#include "raster_device.h"
 
 namespace smplr {
 constexpr int NG = 4;            // waves per 64-pixel group, each walking a contiguous range of parts (8: 55.7 us, 4: 48 us)
@@ -175,19 +175,14 @@ __device__ __forceinline__ void scan_parts_tbl(const char *base, int offv, int p
   }
 }
 
-// Sum over each aligned group of 8 lanes, the same bits in all 8 (fixed tree: lane^1, lane^2, other quad).
+// Sum / max over each aligned group of 8 lanes, the same bits in all 8 (fixed tree: lane^1, lane^2, other quad).
 __device__ __forceinline__ float sum8_dpp(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));    // quad_perm 1,0,3,2
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));    // quad_perm 2,3,0,1
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));   // row_half_mirror
-  return v;
+  v = quad_sum(v);
+  return v + dpp_f<0x141>(v);
 }
-
 __device__ __forceinline__ float max8_dpp(float v) {
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false)));
-  return v;
+  v = quad_max(v);
+  return fmaxf(v, dpp_f<0x141>(v));
 }
 
 // Block = 256 pixels of one mesh x 4 part ranges = 16 waves: wave (g, w) evaluates the parts of range g
@@ -222,9 +217,7 @@ __global__ __launch_bounds__(RTS * NG) SMPLR_RASTER_SGPRS void raster_fwd_kernel
   const int npix = W * W;
   const int q = tile * RTS + pt;
   const int qc = q < npix ? q : npix - 1;
-  // q / W for q < W^2 <= 25600 as a multiply and a shift (wmagic = ceil(2^24 / W), exact there): the
-  // compiler's sequence for a division by a run-time W is ~20 instructions, three times per lane
-  const int r = (int)(((unsigned)qc * wmagic) >> 24), c = qc - r * W;
+  const int r = div_w(qc, wmagic), c = qc - r * W;
   const float fc = (float)c, fr = (float)r;
   const float4 *Gn = G + (size_t)n * S;
   const int *goffn = goff + (size_t)n * goff_stride(P);
@@ -246,7 +239,7 @@ __global__ __launch_bounds__(RTS * NG) SMPLR_RASTER_SGPRS void raster_fwd_kernel
     lab[it] = 0;
     if (LOSS) {                                          // labels lie as the output does: rows flipped
       const int qs = qq < npix ? qq : npix - 1;
-      const int rr = (int)(((unsigned)qs * wmagic) >> 24), cc = qs - rr * W;
+      const int rr = div_w(qs, wmagic), cc = qs - rr * W;
       lab[it] = lo.labels[(size_t)n * npix + (unsigned)((W - 1 - rr) * W + cc)];
     }
   }
@@ -272,8 +265,8 @@ __global__ __launch_bounds__(RTS * NG) SMPLR_RASTER_SGPRS void raster_fwd_kernel
   const bool in_lds = lbase <= NREC;                     // block-uniform
   // (v - row)^2 of every record for the image rows this block touches (6 at W = 48), so that a pair costs
   // a subtract and an fma instead of two subtracts, a multiply and an fma; used when the tables fit
-  const int row0 = (int)(((unsigned)min(tile * RTS, npix - 1) * wmagic) >> 24);
-  const int nrows = (int)(((unsigned)min(tile * RTS + RTS - 1, npix - 1) * wmagic) >> 24) - row0 + 1;
+  const int row0 = div_w(min(tile * RTS, npix - 1), wmagic);
+  const int nrows = div_w(min(tile * RTS + RTS - 1, npix - 1), wmagic) - row0 + 1;
   // table row stride: consecutive rows (the most a 16-lane read group spans) must not share banks
   const int lb4 = (lbase + 3) & ~3;
   const int RS = ((lb4 & 63) >= 4 && (lb4 & 63) <= 60) ? lb4 : lb4 + 4;
@@ -377,37 +370,13 @@ __global__ __launch_bounds__(RTS * NG) SMPLR_RASTER_SGPRS void raster_fwd_kernel
   __syncthreads();
   // The tile now holds every part's best visible vertex.  All 16 waves merge the local records (invisible
   // vertices that round to the pixel) and write the tile out: 8 lanes per pixel, each taking every 8th record
-  // of the pixel's list, then 4 channels of its row (coalesced 128-B / 64-B pixel rows).  A record replaces the
-  // tile's score only if strictly larger (ties keep the earlier winner, global before local): an LDS atomic max
-  // on the score bits (scores are >= 0, so the integer order is the float order) whose return value tells the
-  // lane whether it raised the slot; the slot read back tells it whether a later lane of the same step raised
-  // it further.  LDS operations of one wave execute in order, so no barrier separates merge and write-out.
-  // LOSS: what the pixel of merge step `it` needs for its loss, in all 8 of its lanes; finished after the loop
-  float den_[NIT], st_[NIT], eg_[NIT];
-  unsigned po_[NIT];
+  // of the pixel's list (merge_local), then 4 channels of its row (coalesced 128-B / 64-B pixel rows).
+  LossPx px[NIT];                                          // LOSS: what each merge step's pixel needs; finished after the loop
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int e = it * (RTS * NG) + tid;
     const int pl = e >> 3, c4 = (e & 7) * 4;
-    {
-      int *rowS = reinterpret_cast<int *>(&sS[pl * SLD + 1]);
-      short *rowA = &sA[pl * ALD + 1];
-      const int l1 = l1a[it];
-      int i = l0a[it] + sub;
-      uint2 rec = lr0[it];
-      while (__any(i < l1)) {
-        const uint2 nxt = lrecn[min(i + 8, K - 1)];        // next step's record, in flight during this one
-        if (i < l1) {
-          const int sc = __float_as_int(fast_exp_neg(__uint_as_float(rec.x)));
-          const int p = (int)rec.y;
-          const int old = atomicMax(&rowS[p], sc);
-          const int fin = __hip_atomic_load(&rowS[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);   // (a ds_read, not a flat load)
-          if (old < sc && fin == sc) rowA[p] = (short)(lbase + i);
-        }
-        rec = nxt;
-        i += 8;
-      }
-    }
+    merge_local<8>(sS, sA, pl, lrecn, l0a[it] + sub, l1a[it], lr0[it], lbase, K);
     const float *ts = &sS[pl * SLD + c4];
     const short *ta = &sA[pl * ALD + c4];
     float v[4];
@@ -436,21 +405,23 @@ __global__ __launch_bounds__(RTS * NG) SMPLR_RASTER_SGPRS void raster_fwd_kernel
     }
     const int qq = tile * RTS + pl;
     if (LOSS) {                                            // (C == 32: checked by the launcher; all lanes take part)
-      den_[it] = sum8_dpp((__expf(v[0]) + __expf(v[1])) + (__expf(v[2]) + __expf(v[3])));
+      px[it].den = sum8_dpp((__expf(v[0]) + __expf(v[1])) + (__expf(v[2]) + __expf(v[3])));
       const int t = lab[it];
       const float vt = (t & 2) ? ((t & 1) ? v[3] : v[2]) : ((t & 1) ? v[1] : v[0]);
-      st_[it] = sum8_dpp(c4 == (t & ~3) ? vt : 0.0f);      // the labelled class' score in all 8 lanes (+ exact zeros)
-      // the background's exp (what it contributes to every channel's gradient) where the clip's gate is open, else a
-      // negative number, from the pixel's lane 0 to its lanes 0 .. 3 (quad_perm 0,0,0,0)
+      px[it].st = sum8_dpp(c4 == (t & ~3) ? vt : 0.0f);      // the labelled class' score in all 8 lanes (+ exact zeros)
+      // the background's exp where the clip's gate is open, else a negative number, from the pixel's lane 0 to its
+      // lanes 0 .. 3
       const float eg = a[0] ? __expf(v[0]) : -1.0f;
-      eg_[it] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(eg), 0x00, 0xF, 0xF, false));
+      px[it].eg = dpp_f<0x00>(eg);
+      px[it].w = wlab[it];
+      px[it].t = t;
     }
     unsigned po = ~0u;
     if (qq < npix) {
-      const int rr = (int)(((unsigned)qq * wmagic) >> 24), cc = qq - rr * W;
+      const int rr = div_w(qq, wmagic), cc = qq - rr * W;
       po = (unsigned)((W - 1 - rr) * W + cc);              // rows flipped (:68); mesh base + 32-bit offset
     }
-    if (LOSS) po_[it] = po;
+    if (LOSS) px[it].po = po;
     if (qq < npix && c4 < C) {
       if (lo.vmax && c4 == 0) lo.vmax[(size_t)n * npix + po] = vmx;
       float *so = seg + (size_t)n * npix * C + (po * (unsigned)C + (unsigned)c4);
@@ -466,60 +437,16 @@ __global__ __launch_bounds__(RTS * NG) SMPLR_RASTER_SGPRS void raster_fwd_kernel
       *reinterpret_cast<short4 *>(arg + (size_t)n * npix * 32 + (po * 32u + (unsigned)c4)) = o4;
     }
   }
-  if (LOSS) {
-    // The per-pixel end of the loss (a dozen transcendental and clip steps) once for all merge steps of the lane: lane
-    // `it` of a pixel's 8 finishes the pixel of step `it`, so the NIT pixels share one pass of the instructions
-    // instead of running them NIT times in 8 lanes each.
-    static_assert(NIT <= 4, "the background's lane reaches its quad only");
-    float den = den_[0], st = st_[0], eg = eg_[0], w = wlab[0];
-    int t = lab[0];
-    unsigned po = po_[0];
-#pragma unroll
-    for (int it = 1; it < NIT; ++it) {
-      if (sub == it) {
-        den = den_[it]; st = st_[it]; eg = eg_[it]; w = wlab[it];
-        t = lab[it];
-        po = po_[it];
-      }
-    }
-    // (v_rcp_f32 / v_log_f32: 1 ulp and ~1e-7 absolute in log2 on p in [1e-7, 1) - far inside the loss head's 1e-4
-    // bar - where the IEEE division and logf() were a fifth of this phase's instructions; the raw instruction, not
-    // __logf(): p >= 1e-7 is never denormal, and the library form spends 12 instructions on that case and on a
-    // two-term product with ln 2)
-    const float inv = __builtin_amdgcn_rcpf(den);
-    const float sm = __expf(st) * inv;
-    const float p = fminf(fmaxf(sm, K_EPS), 1.0f - K_EPS);                     // focal_loss.py:17
-    const bool inside = sm >= K_EPS && sm <= 1.0f - K_EPS && (unsigned)t < 32u;  // (a label outside the classes: no loss)
-    const float om = 1.0f - p, lg = __builtin_amdgcn_logf(p) * 0.6931471806f;
-    const float pg = pow_gamma(om, lo.gamma);
-    const float ls = (unsigned)t < 32u ? pg * ((-lg) * w) : 0.0f;              // :18, :41, :43-44
-    // d loss / d softmax_t (the clip passes gradient on [eps, 1 - eps] only) x softmax_t: with it
-    // d loss / d score_c = (q_t softmax_t) (delta_ct - softmax_c)
-    const float k1 = inside ? (w * (dpow_gamma(om, lo.gamma) * lg - pg * __builtin_amdgcn_rcpf(p))) * sm : 0.0f;
-    // what the background contributes to every channel's gradient where the clip's gate is open, per unit of k1
-    const float gbu = eg >= 0.0f ? ((t == 0 ? 1.0f : 0.0f) - eg * inv) : 0.0f;
-    if (sub < NIT && po != ~0u) {
-      lo.loss[(size_t)n * npix + po] = ls;
-      lo.stats[(size_t)n * npix + po] = make_float4(k1 * inv, k1 * gbu, k1, __int_as_float(t));
-    }
-  }
+  if (LOSS) loss_px_end(px, sub, lo, (size_t)n * npix);
 }
 
 void raster1_launch(const float4 *G, const int *goff, const int *lstart, const uint2 *lrec, int P, int K, int S, int W,
                     int B, float *seg, short *arg, LossOut lo, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
   const int ntiles = (W * W + RTS - 1) / RTS;
   const int grid = 8 * ((B + 7) / 8) * ntiles;
-  const unsigned wm = (unsigned)(((1u << 24) + W - 1) / W);
-#define SMPLR_RASTER_LAUNCH(LOSS_)                                                                                    \
-  {                                                                                                                   \
-    if (e0)                                                                                                           \
-      hipExtLaunchKernelGGL(raster_fwd_kernel<LOSS_>, dim3(grid), dim3(RTS * NG), 0, st, e0, e1, 0, G, goff, lstart,   \
-                            lrec, P, K, S, W, B, ntiles, seg, arg, wm, lo);                                           \
-    else                                                                                                              \
-      hipLaunchKernelGGL(raster_fwd_kernel<LOSS_>, dim3(grid), dim3(RTS * NG), 0, st, G, goff, lstart, lrec, P, K, S,  \
-                         W, B, ntiles, seg, arg, wm, lo);                                                             \
-  }
-  if (lo.loss) SMPLR_RASTER_LAUNCH(true) else SMPLR_RASTER_LAUNCH(false)
-#undef SMPLR_RASTER_LAUNCH
+  const EvLaunch at{dim3(grid), dim3(RTS * NG), st, e0, e1};
+  const unsigned wm = w_magic(W);
+  if (lo.loss) ev_launch<&raster_fwd_kernel<true>>(at, G, goff, lstart, lrec, P, K, S, W, B, ntiles, seg, arg, wm, lo);
+  else ev_launch<&raster_fwd_kernel<false>>(at, G, goff, lstart, lrec, P, K, S, W, B, ntiles, seg, arg, wm, lo);
 }
 }  // namespace smplr

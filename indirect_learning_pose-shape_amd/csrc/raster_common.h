@@ -1,4 +1,5 @@
-// What the stages of the soft rasterisers share.  Each stage is a source file of its own and they meet only in global
+// What the stages of the soft rasterisers share on the host and in memory (raster_device.h: what the two part rasterisers
+// share on the device).  Each stage is a source file of its own and they meet only in global
 // memory: seg_bin.hip (binning) -> raster.hip (31-part forward; raster1.hip: its one-pixel reference) -> seg_bwd.hip
 // (backward), and silh.hip (silhouette, forward and backward).  Here: the layout of what they hand over, and the few
 // constants and helpers that two or more of them use.
@@ -13,6 +14,7 @@
 // workspace per mesh (seg_ws_layout): goff = part offsets [P + 1] | unit-weight flag | parts by size [32];
 // lstart[npix + 1] = the pixels' ranges of local records; lrec[K] = (x bits, part) per local record.
 #pragma once
+#include <hip/hip_ext.h>
 #include "common.h"
 
 namespace smplr {
@@ -99,6 +101,18 @@ static int lds_launch(const LdsLaunch &at, Args... args) {
   hipLaunchKernelGGL(Kernel, at.grid, at.block, at.lds, at.st, args...);
   return 0;
 }
+
+// ... and the launch that optionally carries a start / stop event pair (hipExtLaunchKernel: the kernel's own duration,
+// begin to end on the device, without the dispatch gap an event pair around a launch includes)
+struct EvLaunch { dim3 grid, block; hipStream_t st; hipEvent_t e0, e1; };
+template <auto Kernel, class... Args>
+static void ev_launch(const EvLaunch &at, Args... args) {
+  if (at.e0) hipExtLaunchKernelGGL(Kernel, at.grid, at.block, 0, at.st, at.e0, at.e1, 0, args...);
+  else hipLaunchKernelGGL(Kernel, at.grid, at.block, 0, at.st, args...);
+}
+
+// ceil(2^24 / W): the rasterisers' q / W as a multiply and a shift (raster_device.h: div_w), exact for q < W^2 <= 25600
+inline unsigned w_magic(int W) { return (unsigned)(((1u << 24) + W - 1) / W); }
 
 struct SegWs {
   size_t goff_off, lstart_off, lrec_off, total;

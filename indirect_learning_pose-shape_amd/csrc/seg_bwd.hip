@@ -7,6 +7,7 @@
 // runs of pixels that share an arg-min are summed in registers and reach the block's LDS slot
 // accumulators (ds_add_f32) only at run boundaries; per-block slot sums are merged in a fixed
 // order and scattered to the vertices with plain stores (no global atomics, no memset).
+// Written once for the five row walks: RunSum (the run accumulator, fp32 or fixed point) and seg_px (one pixel's factor).
 #include "raster_common.h"
 
 namespace smplr {
@@ -33,26 +34,66 @@ __device__ unsigned g_tl_segbwd[TL_SEGBWD_WG * 12 * 32];
 constexpr int SB_U = 8;          // pixels in flight per lane
 constexpr int SB_PF = 12;        // pixels of a row requested at kernel entry (>= SB_U)
 
-// (unconditional: a run that ends has a non-zero sum except by cancellation, and the walk starts on slot 0 with a sum
-// of zero, so the tests that used to guard this - slot valid, sum non-zero - only cost their instructions, in a kernel
-// whose SIMDs are 88 % busy issuing)
-// (cur >= 0 by construction for finite cotangents; a NaN / inf in dseg makes kk of a masked pixel (slot -1) a NaN,
-// which passes `kk != 0`: the max keeps that garbage sum inside the accumulators instead of in front of them)
-__device__ __forceinline__ void seg_flush(float *acc, int cur, float sx, float sy) {
-  cur = max(cur, 0);
-  atomicAdd(&acc[cur * 2], sx);
-  atomicAdd(&acc[cur * 2 + 1], sy);
-}
+// A lane's run of pixels that share an arg-min slot: summed in registers (cur, sx, sy), it reaches the block's LDS slot
+// accumulators only when the slot changes and at the row's end.  The walk starts on slot 0 with a sum of zero: the first
+// flush adds nothing.
+//  * flush() is unconditional: a run that ends has a non-zero sum except by cancellation, so the tests that used to guard
+//    it - slot valid, sum non-zero - only cost their instructions, in a kernel whose SIMDs are 88 % busy issuing.
+//    cur >= 0 by construction for finite cotangents; a NaN / inf in dseg makes kk of a masked pixel (slot -1) a NaN,
+//    which passes `kk != 0`: the max keeps that garbage sum inside the accumulators instead of in front of them.
+//  * DET, the deterministic form: the run sums are added as 64-bit fixed-point integers (ds_add_u64).  Integer addition
+//    is associative, so the slot sums do not depend on the order in which the block's strips reach an accumulator - bit
+//    for bit the same result on every launch - and `scale` (a power of two chosen per block from max|dseg| and the
+//    largest record weight, see seg_bwd_kernel) keeps 2^-41 of the largest possible term as the resolution, far below an
+//    fp32 sum's own rounding.
+//  * add(): kk != 0 says it all - a masked slot (-1) read a record of zeros (m^2 = 0), and exp underflows beyond 104.
+template <bool DET>
+struct RunSum {
+  float *acc;
+  float scale;
+  int cur = 0;
+  float sx = 0.0f, sy = 0.0f;
+  __device__ __forceinline__ void flush() const {
+    const int c = max(cur, 0);
+    if (DET) {
+      unsigned long long *acc64 = reinterpret_cast<unsigned long long *>(acc);
+      atomicAdd(&acc64[c * 2], (unsigned long long)__float2ll_rn(sx * scale));
+      atomicAdd(&acc64[c * 2 + 1], (unsigned long long)__float2ll_rn(sy * scale));
+    } else {
+      atomicAdd(&acc[c * 2], sx);
+      atomicAdd(&acc[c * 2 + 1], sy);
+    }
+  }
+  __device__ __forceinline__ void add(int slot, float kk, float du, float dv) {
+    if (kk != 0.0f && slot != cur) {
+      flush();
+      cur = slot;
+      sx = 0.0f;
+      sy = 0.0f;
+    }
+    sx = fmaf(kk, du, sx);
+    sy = fmaf(kk, dv, sy);
+  }
+};
 
-// Deterministic form: the run sums are added as 64-bit fixed-point integers (ds_add_u64).  Integer addition is
-// associative, so the slot sums do not depend on the order in which the block's strips reach an accumulator - bit
-// for bit the same result on every launch - and `scale` (a power of two chosen per block from max|dseg| and the
-// largest record weight, see seg_bwd_kernel) keeps 2^-41 of the largest possible term as the resolution, far
-// below an fp32 sum's own rounding.
-__device__ __forceinline__ void seg_flush_det(unsigned long long *acc, int cur, float sx, float sy, float scale) {
-  cur = max(cur, 0);
-  atomicAdd(&acc[cur * 2], (unsigned long long)__float2ll_rn(sx * scale));
-  atomicAdd(&acc[cur * 2 + 1], (unsigned long long)__float2ll_rn(sy * scale));
+// One pixel (column fc, row fr) against its arg-min record (ru, rv, m2 = m^2): du, dv and kk, the factor of (du, dv) in the
+// pixel's contribution to the record's gradient.  d score / d(u,v) = -score m (p - q) / d, score = exp(-m d).  With t =
+// (m d)^2 and r = 1 / sqrt(t): m d = t r and m / d = m^2 r - two transcendental instructions per pixel (v_rsq, v_exp)
+// instead of three (v_sqrt, v_exp, v_rcp): they issue at a quarter of the rate and were a third of the vector time of
+// this vector-bound loop.  d = 0: t is lifted to 1e-37, kk is large but finite and multiplies du = dv = 0: the gradient
+// is 0, not NaN.  A masked slot read a record of zeros: m^2 = 0, kk = 0.
+// The score's cotangent g: c1 itself, or with the loss head fused in (LOSS) c1 - c2 exp(score) - see LossIn.
+template <bool LOSS>
+__device__ __forceinline__ float seg_px(float ru, float rv, float m2, float fc, float fr, float c1, float c2, float &du,
+                                        float &dv) {
+  du = ru - fc;
+  dv = rv - fr;
+  const float d2 = fmaf(du, du, dv * dv);
+  const float t = d2 * m2;
+  const float r = __builtin_amdgcn_rsqf(fmaxf(t, 1e-37f));
+  const float sc = fast_exp_neg(t * r);
+  const float g = LOSS ? c1 - c2 * __expf(sc) : c1;
+  return (-g * sc) * (m2 * r);
 }
 
 // One row strip (a 32-lane group, lane = channel) over its W pixels for one slot window.  MW =
@@ -72,15 +113,13 @@ __device__ __forceinline__ void seg_bwd_row(const float *__restrict__ dseg, cons
                                             const float4 *__restrict__ R, int rbytes, float *acc, size_t row0,
                                             int W, int C, int ch, float fr, int base, float scale,
                                             const int *pa, const float *pg) {
-  unsigned long long *acc64 = reinterpret_cast<unsigned long long *>(acc);
   const int chc = FAST ? ch : min(ch, C - 1);
   const bool chok = ch >= 1 && ch < C;
   const __amdgpu_buffer_rsrc_t rrs =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(R), 0, rbytes, 0x00020000);
   const short *arow = arg + row0 * 32 + ch;                    // FAST: + 32 (c0 + u) shorts
   const float *grow = dseg + row0 * 32 + ch;                   // FAST (C == 32): + 32 (c0 + u) floats
-  int cur = 0;                                   // (slot 0 with a sum of zero: the first flush adds nothing)
-  float sx = 0.0f, sy = 0.0f;
+  RunSum<DET> run{acc, scale};
   SMPLR_TL_ROW
   for (int c0 = 0; c0 < W; c0 += SB_U) {
     int a[SB_U];
@@ -126,34 +165,15 @@ __device__ __forceinline__ void seg_bwd_row(const float *__restrict__ dseg, cons
     if (FAST && !chok) continue;                  // channel 0 has no part (its lanes have served the broadcast above)
 #pragma unroll
     for (int u = 0; u < SB_U; ++u) {
-      const float fc = (float)(c0 + u);
-      const float du = rv[u].x - fc, dv = rv[u].y - fr;
-      const float d2 = fmaf(du, du, dv * dv);
-      // d score / d(u,v) = -score m (p - q) / d, score = exp(-m d).  With t = (m d)^2 and r = 1 / sqrt(t): m d = t r
-      // and m / d = m^2 r - two transcendental instructions per pixel (v_rsq, v_exp) instead of three (v_sqrt, v_exp,
-      // v_rcp): they issue at a quarter of the rate and were a third of the vector time of this vector-bound loop.
-      // d = 0: t is lifted to 1e-37, kk is large but finite and multiplies du = dv = 0: the gradient is 0, not NaN.
-      const float t = d2 * rv[u].z;
-      const float r = __builtin_amdgcn_rsqf(fmaxf(t, 1e-37f));
-      float kk = (-g[u] * fast_exp_neg(t * r)) * (rv[u].z * r);
-      // kk != 0 says it all: a masked slot (-1) read a record of zeros (m^2 = 0); exp underflows beyond 104
-      // (with slot windows a slot below the window is a valid record of another window: tested there)
+      float du, dv;
+      float kk = seg_px<false>(rv[u].x, rv[u].y, rv[u].z, (float)(c0 + u), fr, g[u], 0.0f, du, dv);
+      // (with slot windows a slot below the window is a valid record of another window: tested here)
       if (MW && a[u] < 0) kk = 0.0f;
-      const bool on = kk != 0.0f;
-      if (on && a[u] != cur) {
-        if (DET) seg_flush_det(acc64, cur, sx, sy, scale);
-        else seg_flush(acc, cur, sx, sy);
-        cur = a[u];
-        sx = 0.0f;
-        sy = 0.0f;
-      }
-      sx = fmaf(kk, du, sx);
-      sy = fmaf(kk, dv, sy);
+      run.add(a[u], kk, du, dv);
     }
     SMPLR_TL_STAMP(4 + c0 / SB_U * 2);
   }
-  if (DET) seg_flush_det(acc64, cur, sx, sy, scale);
-  else seg_flush(acc, cur, sx, sy);
+  run.flush();
 }
 
 // The FAST row walk (C == 32, W = 8 NB) as a software pipeline over its NB batches of SB_U pixels (round 4).  The
@@ -169,7 +189,6 @@ template <int U, int NB, bool DET>
 __device__ __forceinline__ void seg_bwd_row_pipe(const float *__restrict__ dseg, const short *__restrict__ arg,
                                                  const float4 *__restrict__ R, int rbytes, float *acc, size_t row0,
                                                  int ch, float fr, float scale, const int *pa, const float *pg) {
-  unsigned long long *acc64 = reinterpret_cast<unsigned long long *>(acc);
   const bool chok = ch >= 1;
   const __amdgpu_buffer_rsrc_t rrs =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(R), 0, rbytes, 0x00020000);
@@ -179,8 +198,7 @@ __device__ __forceinline__ void seg_bwd_row_pipe(const float *__restrict__ dseg,
   float g[NB][U];
   // (u, v, m^2): 12 of a record's 16 bytes - the vertex id is not used here (round 5: B = 2 048 285 -> 282 us)
   f32x3g rv[NB][U];
-  int cur = 0;                                   // (slot 0 with a sum of zero: the first flush adds nothing)
-  float sx = 0.0f, sy = 0.0f;
+  RunSum<DET> run{acc, scale};
 #ifdef SMPLR_TL
   constexpr int W = U * NB;                      // (the stamp macro's window test)
 #endif
@@ -228,30 +246,16 @@ __device__ __forceinline__ void seg_bwd_row_pipe(const float *__restrict__ dseg,
       asm volatile("" : "+v"(fb));
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const float fc = fb + (float)u;
-        const float du = rv[b][u].x - fc, dv = rv[b][u].y - fr;
-        const float d2 = fmaf(du, du, dv * dv);
-        const float t = d2 * rv[b][u].z;
-        const float r = __builtin_amdgcn_rsqf(fmaxf(t, 1e-37f));      // (see seg_bwd_row: m d = t r, m / d = m^2 r)
-        const float kk = (-g[b][u] * fast_exp_neg(t * r)) * (rv[b][u].z * r);
-        const bool on = kk != 0.0f;
-        if (on && a[b][u] != cur) {
-          if (DET) seg_flush_det(acc64, cur, sx, sy, scale);
-          else seg_flush(acc, cur, sx, sy);
-          cur = a[b][u];
-          sx = 0.0f;
-          sy = 0.0f;
-        }
-        sx = fmaf(kk, du, sx);
-        sy = fmaf(kk, dv, sy);
+        float du, dv;
+        const float kk = seg_px<false>(rv[b][u].x, rv[b][u].y, rv[b][u].z, fb + (float)u, fr, g[b][u], 0.0f, du, dv);
+        run.add(a[b][u], kk, du, dv);
       }
     }
     SMPLR_TL_STAMP(4 + b * 2);
   }
 #undef SMPLR_SB_LOAD
 #undef SMPLR_SB_GATHER
-  if (DET) seg_flush_det(acc64, cur, sx, sy, scale);
-  else seg_flush(acc, cur, sx, sy);
+  run.flush();
 }
 
 // The row walk when the loss head's backward is fused in (seg_bwd_kernel<.., LOSS = true>): d loss / d score of a
@@ -266,10 +270,8 @@ struct LossIn { const float *dloss; const float4 *stats; };
 // one batch of SB_U pixels of a row: a = arg-min slots, dl = dloss, st = stats of the pixels c0 .. c0 + SB_U - 1
 template <bool MW, bool DET>
 __device__ __forceinline__ void seg_bwd_batch_loss(int c0, int (&a)[SB_U], const float (&dl)[SB_U],
-                                                   const float4 (&st)[SB_U], __amdgpu_buffer_rsrc_t rrs, float *acc,
-                                                   int W, bool chok, int ch, float fr, int base, float scale, int &cur,
-                                                   float &sx, float &sy) {
-  unsigned long long *acc64 = reinterpret_cast<unsigned long long *>(acc);
+                                                   const float4 (&st)[SB_U], __amdgpu_buffer_rsrc_t rrs, int W,
+                                                   bool chok, int ch, float fr, int base, RunSum<DET> &run) {
   float c1[SB_U], c2[SB_U];
   float4 rv[SB_U];
 #pragma unroll
@@ -287,25 +289,10 @@ __device__ __forceinline__ void seg_bwd_batch_loss(int c0, int (&a)[SB_U], const
   }
 #pragma unroll
   for (int u = 0; u < SB_U; ++u) {
-    const float fc = (float)(c0 + u);
-    const float du = rv[u].x - fc, dv = rv[u].y - fr;
-    const float d2 = fmaf(du, du, dv * dv);
-    const float t = d2 * rv[u].z;
-    const float r = __builtin_amdgcn_rsqf(fmaxf(t, 1e-37f));      // (see seg_bwd_row: m d = t r, m / d = m^2 r)
-    const float sc = fast_exp_neg(t * r);
-    const float g = c1[u] - c2[u] * __expf(sc);
-    float kk = (-g * sc) * (rv[u].z * r);                          // (a masked slot read zeros: m^2 = 0, kk = 0)
+    float du, dv;
+    float kk = seg_px<true>(rv[u].x, rv[u].y, rv[u].z, (float)(c0 + u), fr, c1[u], c2[u], du, dv);
     if (MW && a[u] < 0) kk = 0.0f;
-    const bool on = kk != 0.0f;
-    if (on && a[u] != cur) {
-      if (DET) seg_flush_det(acc64, cur, sx, sy, scale);
-      else seg_flush(acc, cur, sx, sy);
-      cur = a[u];
-      sx = 0.0f;
-      sy = 0.0f;
-    }
-    sx = fmaf(kk, du, sx);
-    sy = fmaf(kk, dv, sy);
+    run.add(a[u], kk, du, dv);
   }
 }
 
@@ -323,8 +310,7 @@ __device__ __forceinline__ void seg_bwd_row_loss(LossIn li, const short *__restr
   const short *arow = arg + row0 * 32 + ch;
   const float *drow = li.dloss + row0;
   const float4 *srow = li.stats + row0;
-  int cur = 0;                                   // (slot 0 with a sum of zero: the first flush adds nothing)
-  float sx = 0.0f, sy = 0.0f;
+  RunSum<DET> run{acc, scale};
   for (int c0 = 0; c0 < W; c0 += SB_U) {
     int a[SB_U];
     float dl[SB_U];
@@ -353,11 +339,9 @@ __device__ __forceinline__ void seg_bwd_row_loss(LossIn li, const short *__restr
         st[u] = srow[cc];
       }
     }
-    seg_bwd_batch_loss<MW, DET>(c0, a, dl, st, rrs, acc, W, chok, ch, fr, base, scale, cur, sx, sy);
+    seg_bwd_batch_loss<MW, DET>(c0, a, dl, st, rrs, W, chok, ch, fr, base, run);
   }
-  unsigned long long *acc64 = reinterpret_cast<unsigned long long *>(acc);
-  if (DET) seg_flush_det(acc64, cur, sx, sy, scale);
-  else seg_flush(acc, cur, sx, sy);
+  run.flush();
 }
 
 // seg_bwd_row_pipe for the fused loss head: per pixel the lane needs its arg-min slot (2 B), dloss (4 B) and stats
@@ -368,7 +352,6 @@ template <int U, int NB, bool DET>
 __device__ __forceinline__ void seg_bwd_row_loss_pipe(LossIn li, const short *__restrict__ arg, const float4 *__restrict__ R,
                                                       int rbytes, float *acc, size_t row0, int ch, float fr, float scale,
                                                       const int *pa, const float *pg) {
-  unsigned long long *acc64 = reinterpret_cast<unsigned long long *>(acc);
   const bool chok = ch >= 1;
   const __amdgpu_buffer_rsrc_t rrs =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(R), 0, rbytes, 0x00020000);
@@ -379,8 +362,7 @@ __device__ __forceinline__ void seg_bwd_row_loss_pipe(LossIn li, const short *__
   int a[NB][U];
   float dl[NB][U], c1[NB][U], c2[NB][U];
   float4 st[NB][U], rv[NB][U];
-  int cur = 0;                                   // (slot 0 with a sum of zero: the first flush adds nothing)
-  float sx = 0.0f, sy = 0.0f;
+  RunSum<DET> run{acc, scale};
 #define SMPLR_SBL_LOAD(b_, first_)                                          \
   {                                                                         \
     int o_ = (b_) * U;                                                      \
@@ -417,30 +399,14 @@ __device__ __forceinline__ void seg_bwd_row_loss_pipe(LossIn li, const short *__
     asm volatile("" : "+v"(fb));
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const float fc = fb + (float)u;
-      const float du = rv[b][u].x - fc, dv = rv[b][u].y - fr;
-      const float d2 = fmaf(du, du, dv * dv);
-      const float t = d2 * rv[b][u].z;
-      const float r = __builtin_amdgcn_rsqf(fmaxf(t, 1e-37f));      // (see seg_bwd_row: m d = t r, m / d = m^2 r)
-      const float sc = fast_exp_neg(t * r);
-      const float g = c1[b][u] - c2[b][u] * __expf(sc);
-      const float kk = (-g * sc) * (rv[b][u].z * r);                 // (a masked slot read zeros: m^2 = 0, kk = 0)
-      const bool on = kk != 0.0f;
-      if (on && a[b][u] != cur) {
-        if (DET) seg_flush_det(acc64, cur, sx, sy, scale);
-        else seg_flush(acc, cur, sx, sy);
-        cur = a[b][u];
-        sx = 0.0f;
-        sy = 0.0f;
-      }
-      sx = fmaf(kk, du, sx);
-      sy = fmaf(kk, dv, sy);
+      float du, dv;
+      const float kk = seg_px<true>(rv[b][u].x, rv[b][u].y, rv[b][u].z, fb + (float)u, fr, c1[b][u], c2[b][u], du, dv);
+      run.add(a[b][u], kk, du, dv);
     }
   }
 #undef SMPLR_SBL_LOAD
 #undef SMPLR_SBL_GATHER
-  if (DET) seg_flush_det(acc64, cur, sx, sy, scale);
-  else seg_flush(acc, cur, sx, sy);
+  run.flush();
 }
 
 template <bool DET, bool LOSS>

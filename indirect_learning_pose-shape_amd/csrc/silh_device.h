@@ -111,7 +111,7 @@ struct SilhGradLoss {            // dloss, k (B, W * W): g = dloss * k, one fp32
 // gridDim.y workgroups share a mesh: each owns a contiguous range of VERTICES (its accumulators, its rows of dproj) and
 // walks all the pixels, taking those whose arg-max vertex is its own - with fewer meshes than compute units what there is
 // to spread is the zeroing and the 82 KB of dproj per mesh, the pixel walk is short.
-// DET: the per-vertex sums as 64-bit fixed point (see seg_flush_det): bit-reproducible whatever the order in which the
+// DET: the per-vertex sums as 64-bit fixed point (see seg_bwd.hip: RunSum): bit-reproducible whatever the order in which the
 // 1 024 threads' pixels reach a vertex' accumulator.  The scale is 2^(60 - eg - terms), max scan() < 2^eg over the mesh,
 // W^2 <= 2^terms.
 template <bool DET, class Grad>

@@ -32,6 +32,20 @@ def test_raster_fwd_keeps_two_blocks_per_cu(kernels):
         assert k["scratch"] == 0, name
 
 
+@pytest.mark.parametrize("shape,blocks,exact", [("ELi8ELi128E", 2, True), ("ELi10ELi64E", 3, False)])
+def test_raster2_fwd_keeps_its_blocks_per_cu(kernels, shape, blocks, exact):
+    """The kernel that runs by default: 128 pair-lanes x 8 part ranges = two blocks of 16 waves per CU (8 per SIMD), and
+    64 x 10 = three blocks of 10 waves (7.5 per SIMD).  The 128 x 4 shape (the environment's only) has no bar."""
+    hit = {n: k for n, k in _match(kernels, "raster2_fwd_kernel").items() if shape in n}
+    assert len(hit) >= 3, "no raster2_fwd_kernel<.., %s ..> instantiations" % shape
+    for name, k in hit.items():
+        assert k["sgpr"] <= 80, "%s: %d SGPRs - 7 waves per SIMD" % (name, k["sgpr"])
+        w = kr.waves_per_simd(k)
+        assert (w == 8) if exact else (w >= 8), "%s: %d waves per SIMD" % (name, w)
+        assert blocks * k["lds"] <= 160 * 1024, "%s: %d B of LDS per block" % (name, k["lds"])
+        assert k["scratch"] == 0, name
+
+
 @pytest.mark.parametrize("pat,threads,blocks", [
     ("seg_bin_kernel", 1024, 1), ("silh_px_kernel", 1024, 1), ("seg_bwd_kernel", 768, 1), ("skin_bwd_kernelILb1E", 256, 7),
     ("pose_blend3_fwd_kernel", 512, 1), ("blend3_bwd_kernelILi3ELi1ELi2E", 256, 1), ("pose_bwd_kernel", 512, 1),
