@@ -547,6 +547,38 @@ int smplr_fit_step(float *x, const float *g, float *m, float *v, int32_t *t, int
                    const float *silh_loss, int Ns, float silh_weight, const float *col_scale, float *history, int H, int B,
                    int P, float lr, float beta1, float beta2, float eps, float gscale, int mode, int patience, void *stream);
 
+/* ---- pose and shape priors for the fit (SMPLify's regularisers; beyond the reference); INTEGRATION.md 4k ----------------
+ * Row b of x (B, P), P = num_cam + 82: theta = x[num_cam : num_cam + 72], beta = x[num_cam + 72 :], theta' = theta[3:72] (D = 69).
+ * The prior's data, fp32 device memory: mean (K, 69); factor (K, 69, 69) dense row-major A_k with A_k^T A_k = inverse
+ * covariance; offset (K) c_k; angle_idx (A) int32 in 0..71 and angle_scale (A); shape_mean (10); weights (3) = w_pose,
+ * w_angle, w_shape (device memory: a captured graph sees a change).
+ *   d_k = theta' - mean_k, y_k = A_k d_k, E_k = 1/2 |y_k|^2 + c_k; k* = the first minimum over k (a NaN at k = 0 stays chosen);
+ *   E_pose = E_k*, gradient A_k*^T y_k* on theta'.
+ *   E_angle = sum_a exp(angle_scale[a] theta[angle_idx[a]]), gradient angle_scale[a] exp(.) added to that theta column in
+ *   the order of a; an index outside 0..71 is skipped.
+ *   E_shape = sum_i (beta_i - shape_mean_i)^2, gradient 2 (beta_i - shape_mean_i).
+ *   E = w_pose E_pose + w_angle E_angle + w_shape E_shape and its gradient likewise; a term whose weight is exactly 0 is not
+ *   evaluated (0 to E and the gradient, its energy reported as 0).  Every other column's gradient is exactly 0.
+ * All arithmetic is fp64 on the fp32 operands in a fixed order; each output is rounded to fp32 once: a row's results are
+ * the same bits on every launch and in any batch.
+ * smplr_prior_energy: energy (B, 4) = E_pose, E_angle, E_shape (unweighted), E; comp (B) int32 = k* (0 when w_pose = 0);
+ *   grad (B, P) or NULL, every column written.  One launch of B workgroups.
+ * smplr_fit_step_prior: smplr_fit_step with L = fp32(L_data + E) (L_data in fp64, E the fp32 value above) and
+ *   g[b, j] + dE/dx[b, j] (one fp32 addition, before gscale) in place of L and g; a non-finite E or gradient entry makes the
+ *   call a bad call (step 3).  Still one launch.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): P = num_cam + 82 <= 256, num_cam >= 0; 1 <= K <= 16; 0 <= A <= 16; no
+ * null pointer (angle_idx, angle_scale may be NULL with A = 0; grad, silh_loss, history as above); smplr_fit_step's own
+ * limits; B = 0 is a no-op.                                                                                              */
+int smplr_prior_energy(const float *x, int B, int P, int num_cam, const float *mean, const float *factor, const float *offset,
+                       const int32_t *angle_idx, const float *angle_scale, const float *shape_mean, int K, int A,
+                       const float *weights, float *energy, int32_t *comp, float *grad, void *stream);
+int smplr_fit_step_prior(float *x, const float *g, float *m, float *v, int32_t *t, int32_t *calls, int32_t *stall, int32_t *bad,
+                         int32_t *best_step, uint8_t *active, float *best_loss, float *best_x, const float *loss, int N,
+                         const float *silh_loss, int Ns, float silh_weight, const float *col_scale, float *history, int H,
+                         int B, int P, float lr, float beta1, float beta2, float eps, float gscale, int mode, int patience,
+                         int num_cam, const float *mean, const float *factor, const float *offset, const int32_t *angle_idx,
+                         const float *angle_scale, const float *shape_mean, int K, int A, const float *weights, void *stream);
+
 /* ---- projects_to_silhouette: keras_smpl/projects_to_silhouette.py:14-44 ----------------- */
 /* silh (B,W,W,2) = [1-s, s], s = max_v exp(-|proj_v-(c,r)|/1.2) over ALL VP vertices, rows
  * flipped; arg (B,W,W) int32 = maximising vertex.  workspace: smplr_silh_workspace(B,VP,W) B.  */

@@ -88,6 +88,9 @@ SIGNATURES = {
     "smplr_scatter_points": (c_int, [P, P, P, I, P, I, I, I, I, c_float, I, I, I, I, P, P, P]),
     "smplr_fit_step": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, c_float, P, P, I, I, I, c_float, c_float, c_float,
                                c_float, c_float, I, I, P]),
+    "smplr_prior_energy": (c_int, [P, I, I, I, P, P, P, P, P, P, I, I, P, P, P, P, P]),
+    "smplr_fit_step_prior": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, c_float, P, P, I, I, I, c_float, c_float,
+                                     c_float, c_float, c_float, I, I, I, P, P, P, P, P, P, I, I, P, P]),
     "smplr_silh_workspace": (c_size_t, [I, I, I]),
     "smplr_silh_fwd": (c_int, [P, I, I, I, P, P, P, P]),
     "smplr_silh_fwd_hint": (c_int, [P, P, I, I, I, P, P, P, P]),

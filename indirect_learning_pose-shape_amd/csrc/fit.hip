@@ -23,7 +23,16 @@
 // "any g not finite" vote, takes the same decisions from them, and thread 0 alone writes them back after it.
 // FMA contraction is off for the file and the two fused operations are spelled out, so that the rounding count behind the
 // test's bars (tests/test_gpu_fitting.py) is the one written here: m 3 roundings, v 4, the step at most 13.
+//
+//  fit_step_kernel<true>   the same call with the priors of prior_device.h in the energy (smplr_fit_step_prior): after g is
+//                    read and before the decisions of step 1 the workgroup evaluates the row's prior E and its gradient (both
+//                    rounded to fp32 once, as they leave the routine), then L = fp32(Ld + (double)E) and g_j = g_j + dE_j (one
+//                    fp32 addition, before gscale); steps 2 - 5 act on these totals, so a non-finite E or dE_j is a bad call.
+//                    <false> is the kernel behind smplr_fit_step: none of the prior's code, LDS or arguments is in it.
+//  prior_kernel      the prior alone (smplr_prior_energy): energy (B, 4) = E_pose, E_angle, E_shape unweighted and the
+//                    weighted E; comp (B) = k*; grad (B, P) or NULL, every column written.
 #include "common.h"
+#include "prior_device.h"
 
 #pragma clang fp contract(off)
 
@@ -38,13 +47,15 @@ __device__ __forceinline__ float ft_strided_sum(const float *__restrict__ p, int
   return s;
 }
 
+// PA: one PriorArgs with PRIOR, nothing without: <false> has smplr_fit_step's arguments and no others
+template <bool PRIOR, typename... PA>
 __global__ __launch_bounds__(FT_T) void fit_step_kernel(
     float *__restrict__ x, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
     int *__restrict__ t, int *__restrict__ calls, int *__restrict__ stall, int *__restrict__ bad,
     int *__restrict__ best_step, unsigned char *__restrict__ active, float *__restrict__ best_loss,
     float *__restrict__ best_x, const float *__restrict__ loss, int N, const float *__restrict__ silh_loss, int Ns,
     float silh_weight, const float *__restrict__ col_scale, float *__restrict__ history, int H, int B, int P, float lr,
-    float beta1, float beta2, float eps, float gscale, int mode, int patience) {
+    float beta1, float beta2, float eps, float gscale, int mode, int patience, PA... pa) {
   __shared__ double swave[2][FT_NW];
   const int b = blockIdx.x, j = threadIdx.x;
   const int lane = j & (WAVE - 1), wave = j / WAVE;
@@ -63,10 +74,18 @@ __global__ __launch_bounds__(FT_T) void fit_step_kernel(
     swave[1][wave] = wq;
   }
   const bool col = j < P;
-  const float gj = col ? g[row + j] : 0.f;
+  float gj = col ? g[row + j] : 0.f;
+  float Ep = 0.f;
+  if constexpr (PRIOR) {
+    __shared__ PriorLds sprior;
+    const PriorOut po = prior_row(x + row, P, pa..., sprior);
+    Ep = po.e_total;
+    if (col) gj = gj + po.grad;
+  }
   const int g_bad = __syncthreads_or(!finitef(gj));                       // (the barrier that publishes swave)
   double Ld = ((swave[0][0] + swave[0][1]) + (swave[0][2] + swave[0][3])) / (double)N;
   if (silh_loss) Ld += (double)silh_weight * (((swave[1][0] + swave[1][1]) + (swave[1][2] + swave[1][3])) / (double)Ns);
+  if constexpr (PRIOR) Ld += (double)Ep;
   const float L = (float)Ld;
 
   // 2. the trace
@@ -114,30 +133,106 @@ __global__ __launch_bounds__(FT_T) void fit_step_kernel(
   x[row + j] = xj - (step * cs) * __fdiv_rn(m1, den);
 }
 
+__global__ __launch_bounds__(FT_T) void prior_kernel(const float *__restrict__ x, int P, PriorArgs pa, float *__restrict__ energy,
+                                                     int *__restrict__ comp, float *__restrict__ grad) {
+  __shared__ PriorLds sprior;
+  const int b = blockIdx.x, j = threadIdx.x;
+  const long long row = (long long)b * P;
+  const PriorOut po = prior_row(x + row, P, pa, sprior);
+  if (j == 0) {
+    energy[4 * b] = po.e_pose;
+    energy[4 * b + 1] = po.e_angle;
+    energy[4 * b + 2] = po.e_shape;
+    energy[4 * b + 3] = po.e_total;
+    comp[b] = po.comp;
+  }
+  if (grad && j < P) grad[row + j] = po.grad;
+}
+
+// the checks the two prior launchers share; 0 or SMPLR_EINVAL with the message set
+static int prior_args_check(const char *who, int P, int num_cam, const float *mean, const float *factor, const float *offset,
+                            const int32_t *angle_idx, const float *angle_scale, const float *shape_mean, int K, int A,
+                            const float *weights, bool launches) {
+  SMPLR_REQUIRE(num_cam >= 0 && P == num_cam + 82 && P <= FT_T, "%s: P=%d is not num_cam + 82 (num_cam=%d, 0..%d)", who, P,
+                num_cam, FT_T - 82);
+  SMPLR_REQUIRE(K >= 1 && K <= PR_KMAX, "%s: K=%d mixture components (1..%d)", who, K, PR_KMAX);
+  SMPLR_REQUIRE(A >= 0 && A <= PR_AMAX, "%s: A=%d angle terms (0..%d)", who, A, PR_AMAX);
+  SMPLR_REQUIRE(!launches || (mean && factor && offset && shape_mean && weights && (A == 0 || (angle_idx && angle_scale))),
+                "%s: null pointer among the prior's arrays (angle_idx and angle_scale may be NULL with A = 0)", who);
+  return 0;
+}
+
 }  // namespace smplr
+
+int smplr_prior_energy(const float *x, int B, int P, int num_cam, const float *mean, const float *factor, const float *offset,
+                       const int32_t *angle_idx, const float *angle_scale, const float *shape_mean, int K, int A,
+                       const float *weights, float *energy, int32_t *comp, float *grad, void *stream) {
+  using namespace smplr;
+  SMPLR_REQUIRE(B >= 0, "smplr_prior_energy: negative batch B=%d", B);
+  if (int rc = prior_args_check("smplr_prior_energy", P, num_cam, mean, factor, offset, angle_idx, angle_scale, shape_mean, K, A,
+                                weights, B > 0))
+    return rc;
+  if (B == 0) return 0;
+  SMPLR_REQUIRE(x && energy && comp, "smplr_prior_energy: null pointer (only grad may be NULL)");
+  const PriorArgs pa{mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, K, A, num_cam};
+  hipLaunchKernelGGL(prior_kernel, dim3((unsigned)B), dim3(FT_T), 0, as_stream(stream), x, P, pa, energy, comp, grad);
+  SMPLR_LAUNCH_CHECK("smplr_prior_energy");
+  return 0;
+}
+
+// prior = NULL: smplr_fit_step; else smplr_fit_step_prior (`who` names the entry point in messages)
+static int fit_step_launch(const char *who, float *x, const float *g, float *m, float *v, int32_t *t, int32_t *calls,
+                           int32_t *stall, int32_t *bad, int32_t *best_step, uint8_t *active, float *best_loss, float *best_x,
+                           const float *loss, int N, const float *silh_loss, int Ns, float silh_weight, const float *col_scale,
+                           float *history, int H, int B, int P, float lr, float beta1, float beta2, float eps, float gscale,
+                           int mode, int patience, const smplr::PriorArgs *prior, void *stream) {
+  using namespace smplr;
+  SMPLR_REQUIRE(B >= 0, "%s: negative batch B=%d", who, B);
+  SMPLR_REQUIRE(P >= 1 && P <= FT_T, "%s: P=%d columns (1..%d)", who, P, FT_T);
+  SMPLR_REQUIRE(N >= 1, "%s: N=%d loss values per row (N >= 1)", who, N);
+  SMPLR_REQUIRE(!silh_loss || Ns >= 1, "%s: Ns=%d silhouette loss values per row (Ns >= 1)", who, Ns);
+  SMPLR_REQUIRE(mode == SMPLR_FIT_KERAS || mode == SMPLR_FIT_TORCH, "%s: mode %d is neither keras (0) nor torch (1)", who, mode);
+  SMPLR_REQUIRE(H >= 0 && patience >= 0, "%s: negative history length H=%d or patience %d", who, H, patience);
+  SMPLR_REQUIRE(!history || (long long)H * B < (1ll << 40), "%s: history of %d x %d entries", who, H, B);
+  SMPLR_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "%s: beta1, beta2 must lie in [0, 1)", who);
+  SMPLR_REQUIRE(eps >= 0.f && lr - lr == 0.f && gscale - gscale == 0.f && silh_weight - silh_weight == 0.f,
+                "%s: eps must be >= 0 and lr, gscale, silh_weight finite", who);
+  if (prior)
+    if (int rc = prior_args_check(who, P, prior->num_cam, prior->mean, prior->factor, prior->offset, prior->angle_idx,
+                                  prior->angle_scale, prior->shape_mean, prior->K, prior->A, prior->weights, B > 0))
+      return rc;
+  if (B == 0) return 0;
+  SMPLR_REQUIRE(x && g && m && v && t && calls && stall && bad && best_step && active && best_loss && best_x && loss && col_scale,
+                "%s: null pointer (only silh_loss and history may be NULL)", who);
+  if (prior)
+    hipLaunchKernelGGL((fit_step_kernel<true, PriorArgs>), dim3((unsigned)B), dim3(FT_T), 0, as_stream(stream), x, g, m, v, t, calls, stall,
+                       bad, best_step, active, best_loss, best_x, loss, N, silh_loss, Ns, silh_weight, col_scale, history,
+                       history ? H : 0, B, P, lr, beta1, beta2, eps, gscale, mode, patience, *prior);
+  else
+    hipLaunchKernelGGL(fit_step_kernel<false>, dim3((unsigned)B), dim3(FT_T), 0, as_stream(stream), x, g, m, v, t, calls, stall,
+                       bad, best_step, active, best_loss, best_x, loss, N, silh_loss, Ns, silh_weight, col_scale, history,
+                       history ? H : 0, B, P, lr, beta1, beta2, eps, gscale, mode, patience);
+  SMPLR_LAUNCH_CHECK(who);
+  return 0;
+}
 
 int smplr_fit_step(float *x, const float *g, float *m, float *v, int32_t *t, int32_t *calls, int32_t *stall, int32_t *bad,
                    int32_t *best_step, uint8_t *active, float *best_loss, float *best_x, const float *loss, int N,
                    const float *silh_loss, int Ns, float silh_weight, const float *col_scale, float *history, int H, int B,
                    int P, float lr, float beta1, float beta2, float eps, float gscale, int mode, int patience, void *stream) {
-  using namespace smplr;
-  SMPLR_REQUIRE(B >= 0, "smplr_fit_step: negative batch B=%d", B);
-  SMPLR_REQUIRE(P >= 1 && P <= FT_T, "smplr_fit_step: P=%d columns (1..%d)", P, FT_T);
-  SMPLR_REQUIRE(N >= 1, "smplr_fit_step: N=%d loss values per row (N >= 1)", N);
-  SMPLR_REQUIRE(!silh_loss || Ns >= 1, "smplr_fit_step: Ns=%d silhouette loss values per row (Ns >= 1)", Ns);
-  SMPLR_REQUIRE(mode == SMPLR_FIT_KERAS || mode == SMPLR_FIT_TORCH, "smplr_fit_step: mode %d is neither keras (0) nor torch (1)",
-                mode);
-  SMPLR_REQUIRE(H >= 0 && patience >= 0, "smplr_fit_step: negative history length H=%d or patience %d", H, patience);
-  SMPLR_REQUIRE(!history || (long long)H * B < (1ll << 40), "smplr_fit_step: history of %d x %d entries", H, B);
-  SMPLR_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "smplr_fit_step: beta1, beta2 must lie in [0, 1)");
-  SMPLR_REQUIRE(eps >= 0.f && lr - lr == 0.f && gscale - gscale == 0.f && silh_weight - silh_weight == 0.f,
-                "smplr_fit_step: eps must be >= 0 and lr, gscale, silh_weight finite");
-  if (B == 0) return 0;
-  SMPLR_REQUIRE(x && g && m && v && t && calls && stall && bad && best_step && active && best_loss && best_x && loss && col_scale,
-                "smplr_fit_step: null pointer (only silh_loss and history may be NULL)");
-  hipLaunchKernelGGL(fit_step_kernel, dim3((unsigned)B), dim3(FT_T), 0, as_stream(stream), x, g, m, v, t, calls, stall, bad,
-                     best_step, active, best_loss, best_x, loss, N, silh_loss, Ns, silh_weight, col_scale, history,
-                     history ? H : 0, B, P, lr, beta1, beta2, eps, gscale, mode, patience);
-  SMPLR_LAUNCH_CHECK("smplr_fit_step");
-  return 0;
+  return fit_step_launch("smplr_fit_step", x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, N,
+                         silh_loss, Ns, silh_weight, col_scale, history, H, B, P, lr, beta1, beta2, eps, gscale, mode, patience,
+                         nullptr, stream);
+}
+
+int smplr_fit_step_prior(float *x, const float *g, float *m, float *v, int32_t *t, int32_t *calls, int32_t *stall, int32_t *bad,
+                         int32_t *best_step, uint8_t *active, float *best_loss, float *best_x, const float *loss, int N,
+                         const float *silh_loss, int Ns, float silh_weight, const float *col_scale, float *history, int H, int B,
+                         int P, float lr, float beta1, float beta2, float eps, float gscale, int mode, int patience, int num_cam,
+                         const float *mean, const float *factor, const float *offset, const int32_t *angle_idx,
+                         const float *angle_scale, const float *shape_mean, int K, int A, const float *weights, void *stream) {
+  const smplr::PriorArgs pa{mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, K, A, num_cam};
+  return fit_step_launch("smplr_fit_step_prior", x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, N,
+                         silh_loss, Ns, silh_weight, col_scale, history, H, B, P, lr, beta1, beta2, eps, gscale, mode, patience,
+                         &pa, stream);
 }

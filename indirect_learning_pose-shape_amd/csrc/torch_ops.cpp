@@ -851,12 +851,11 @@ void fit_step_check(const Tensor &x, const Tensor &g, const Tensor &m, const Ten
   TORCH_CHECK(mode == 0 || mode == 1, "mode must be 0 (keras) or 1 (torch)");
   TORCH_CHECK(patience >= 0 && patience <= INT32_MAX && B <= INT32_MAX, "patience must be >= 0");
 }
-void fit_step(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
-              Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
-              const c10::optional<Tensor> &silh_loss, const Tensor &col_scale, c10::optional<Tensor> history, double lr,
-              double beta1, double beta2, double eps, double gscale, double silh_weight, int64_t mode, int64_t patience) {
-  fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
-                 patience);
+// every operand of a fit_step / fit_step_prior launch: on the device, its dtype, contiguous, and on x's device
+void fit_step_on_device(const Tensor &x, const Tensor &g, const Tensor &m, const Tensor &v, const Tensor &t, const Tensor &calls,
+                        const Tensor &stall, const Tensor &bad, const Tensor &best_step, const Tensor &active,
+                        const Tensor &best_loss, const Tensor &best_x, const Tensor &loss, const c10::optional<Tensor> &silh_loss,
+                        const Tensor &col_scale, const c10::optional<Tensor> &history) {
   dev_f32(x, "x"); dev_f32(g, "g"); dev_f32(m, "m"); dev_f32(v, "v"); dev_f32(best_x, "best_x"); dev_f32(best_loss, "best_loss");
   dev_f32(loss, "loss"); dev_f32(col_scale, "col_scale");
   dev_typed(t, at::kInt, "t"); dev_typed(calls, at::kInt, "calls"); dev_typed(stall, at::kInt, "stall");
@@ -867,6 +866,14 @@ void fit_step(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, Tenso
   same_device(x, {{"g", &g}, {"m", &m}, {"v", &v}, {"t", &t}, {"calls", &calls}, {"stall", &stall}, {"bad", &bad},
                   {"best_step", &best_step}, {"active", &active}, {"best_loss", &best_loss}, {"best_x", &best_x}, {"loss", &loss},
                   {"silh_loss", silh_loss ? &*silh_loss : &none}, {"col_scale", &col_scale}, {"history", history ? &*history : &none}});
+}
+void fit_step(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
+              Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
+              const c10::optional<Tensor> &silh_loss, const Tensor &col_scale, c10::optional<Tensor> history, double lr,
+              double beta1, double beta2, double eps, double gscale, double silh_weight, int64_t mode, int64_t patience) {
+  fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
+                 patience);
+  fit_step_on_device(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history);
   DeviceGuard guard(x.device());
   if (x.size(0) == 0) return;
   const bool hist = history && history->numel() > 0;
@@ -885,6 +892,102 @@ void fit_step_meta(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, 
                    double, double, double, double, int64_t mode, int64_t patience) {
   fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
                  patience);
+}
+
+// ---- pose and shape priors (csrc/prior_device.h): the prior alone, and fit_step with the prior inside the same launch ----
+// mean (K, 69), factor (K, 69, 69), offset (K), angle_idx (A) int32, angle_scale (A), shape_mean (10), weights (3): fp32.
+void prior_check(const Tensor &x, const Tensor &mean, const Tensor &factor, const Tensor &offset, const Tensor &angle_idx,
+                 const Tensor &angle_scale, const Tensor &shape_mean, const Tensor &weights, int64_t num_cam) {
+  TORCH_CHECK(x.dim() == 2 && x.scalar_type() == at::kFloat && num_cam >= 0 && num_cam <= 256 - 82 && x.size(1) == num_cam + 82,
+              "x must be (B, num_cam + 82) float32 with num_cam in 0..174");
+  TORCH_CHECK(x.size(0) <= INT32_MAX, "too many rows");
+  TORCH_CHECK(mean.dim() == 2 && mean.size(0) >= 1 && mean.size(0) <= 16 && mean.size(1) == 69 && mean.scalar_type() == at::kFloat,
+              "mean must be (K, 69) float32, 1 <= K <= 16");
+  const int64_t K = mean.size(0);
+  TORCH_CHECK(factor.dim() == 3 && factor.size(0) == K && factor.size(1) == 69 && factor.size(2) == 69 &&
+                  factor.scalar_type() == at::kFloat, "factor must be (K, 69, 69) float32");
+  TORCH_CHECK(offset.dim() == 1 && offset.size(0) == K && offset.scalar_type() == at::kFloat, "offset must be (K,) float32");
+  TORCH_CHECK(angle_idx.dim() == 1 && angle_idx.size(0) <= 16 && angle_idx.scalar_type() == at::kInt,
+              "angle_idx must be (A,) int32, A <= 16");
+  TORCH_CHECK(angle_scale.dim() == 1 && angle_scale.size(0) == angle_idx.size(0) && angle_scale.scalar_type() == at::kFloat,
+              "angle_scale must be (A,) float32");
+  TORCH_CHECK(shape_mean.dim() == 1 && shape_mean.size(0) == 10 && shape_mean.scalar_type() == at::kFloat,
+              "shape_mean must be (10,) float32");
+  TORCH_CHECK(weights.dim() == 1 && weights.size(0) == 3 && weights.scalar_type() == at::kFloat, "weights must be (3,) float32");
+}
+void prior_on_device(const Tensor &x, const Tensor &mean, const Tensor &factor, const Tensor &offset, const Tensor &angle_idx,
+                     const Tensor &angle_scale, const Tensor &shape_mean, const Tensor &weights) {
+  dev_f32(mean, "mean"); dev_f32(factor, "factor"); dev_f32(offset, "offset"); dev_typed(angle_idx, at::kInt, "angle_idx");
+  dev_f32(angle_scale, "angle_scale"); dev_f32(shape_mean, "shape_mean"); dev_f32(weights, "weights");
+  same_device(x, {{"mean", &mean}, {"factor", &factor}, {"offset", &offset}, {"angle_idx", &angle_idx},
+                  {"angle_scale", &angle_scale}, {"shape_mean", &shape_mean}, {"weights", &weights}});
+}
+// -> energy (B, 4) = E_pose, E_angle, E_shape, E; comp (B) int32; grad (B, P), or (0, P) with with_grad = False
+std::tuple<Tensor, Tensor, Tensor> prior_energy(const Tensor &x, const Tensor &mean, const Tensor &factor, const Tensor &offset,
+                                                const Tensor &angle_idx, const Tensor &angle_scale, const Tensor &shape_mean,
+                                                const Tensor &weights, int64_t num_cam, bool with_grad) {
+  prior_check(x, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, num_cam);
+  dev_f32(x, "x");
+  prior_on_device(x, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights);
+  DeviceGuard guard(x.device());
+  const int64_t B = x.size(0), P = x.size(1), A = angle_idx.size(0);
+  Tensor energy = at::empty({B, 4}, x.options()), comp = at::empty({B}, x.options().dtype(at::kInt));
+  Tensor grad = at::empty({with_grad ? B : 0, P}, x.options());
+  if (B == 0) return {energy, comp, grad};
+  ok(smplr_prior_energy(x.data_ptr<float>(), (int)B, (int)P, (int)num_cam, mean.data_ptr<float>(), factor.data_ptr<float>(),
+                        offset.data_ptr<float>(), A ? angle_idx.data_ptr<int32_t>() : nullptr,
+                        A ? angle_scale.data_ptr<float>() : nullptr, shape_mean.data_ptr<float>(), (int)mean.size(0), (int)A,
+                        weights.data_ptr<float>(), energy.data_ptr<float>(), comp.data_ptr<int32_t>(),
+                        with_grad ? grad.data_ptr<float>() : nullptr, cur_stream()),
+     "smplr_prior_energy");
+  return {energy, comp, grad};
+}
+std::tuple<Tensor, Tensor, Tensor> prior_energy_meta(const Tensor &x, const Tensor &mean, const Tensor &factor,
+                                                     const Tensor &offset, const Tensor &angle_idx, const Tensor &angle_scale,
+                                                     const Tensor &shape_mean, const Tensor &weights, int64_t num_cam,
+                                                     bool with_grad) {
+  prior_check(x, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, num_cam);
+  const int64_t B = x.size(0);
+  return {at::empty({B, 4}, x.options()), at::empty({B}, x.options().dtype(at::kInt)),
+          at::empty({with_grad ? B : 0, x.size(1)}, x.options())};
+}
+void fit_step_prior(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
+                    Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
+                    const c10::optional<Tensor> &silh_loss, const Tensor &col_scale, c10::optional<Tensor> history,
+                    const Tensor &mean, const Tensor &factor, const Tensor &offset, const Tensor &angle_idx,
+                    const Tensor &angle_scale, const Tensor &shape_mean, const Tensor &weights, double lr, double beta1,
+                    double beta2, double eps, double gscale, double silh_weight, int64_t mode, int64_t patience, int64_t num_cam) {
+  fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
+                 patience);
+  prior_check(x, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, num_cam);
+  fit_step_on_device(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history);
+  prior_on_device(x, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights);
+  DeviceGuard guard(x.device());
+  if (x.size(0) == 0) return;
+  const bool hist = history && history->numel() > 0;
+  const int64_t A = angle_idx.size(0);
+  ok(smplr_fit_step_prior(x.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), t.data_ptr<int32_t>(),
+                          calls.data_ptr<int32_t>(), stall.data_ptr<int32_t>(), bad.data_ptr<int32_t>(),
+                          best_step.data_ptr<int32_t>(), active.data_ptr<uint8_t>(), best_loss.data_ptr<float>(),
+                          best_x.data_ptr<float>(), loss.data_ptr<float>(), (int)loss.size(1),
+                          silh_loss ? silh_loss->data_ptr<float>() : nullptr, silh_loss ? (int)silh_loss->size(1) : 0,
+                          (float)silh_weight, col_scale.data_ptr<float>(), hist ? history->data_ptr<float>() : nullptr,
+                          hist ? (int)history->size(0) : 0, (int)x.size(0), (int)x.size(1), (float)lr, (float)beta1, (float)beta2,
+                          (float)eps, (float)gscale, (int)mode, (int)patience, (int)num_cam, mean.data_ptr<float>(),
+                          factor.data_ptr<float>(), offset.data_ptr<float>(), A ? angle_idx.data_ptr<int32_t>() : nullptr,
+                          A ? angle_scale.data_ptr<float>() : nullptr, shape_mean.data_ptr<float>(), (int)mean.size(0), (int)A,
+                          weights.data_ptr<float>(), cur_stream()),
+     "smplr_fit_step_prior");
+}
+void fit_step_prior_meta(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
+                         Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
+                         const c10::optional<Tensor> &silh_loss, const Tensor &col_scale, c10::optional<Tensor> history,
+                         const Tensor &mean, const Tensor &factor, const Tensor &offset, const Tensor &angle_idx,
+                         const Tensor &angle_scale, const Tensor &shape_mean, const Tensor &weights, double, double, double,
+                         double, double, double, int64_t mode, int64_t patience, int64_t num_cam) {
+  fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
+                 patience);
+  prior_check(x, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, num_cam);
 }
 
 int64_t abi_version() { return smplr_abi_version(); }
@@ -932,6 +1035,13 @@ TORCH_LIBRARY(smplraster, m) {
         "Tensor(g!) bad, Tensor(h!) best_step, Tensor(i!) active, Tensor(j!) best_loss, Tensor(k!) best_x, Tensor loss, "
         "Tensor? silh_loss, Tensor col_scale, Tensor(l!)? history, float lr=0.001, float beta1=0.9, float beta2=0.999, "
         "float eps=1e-07, float gscale=1.0, float silh_weight=1.0, int mode=0, int patience=0) -> ()");
+  m.def("prior_energy(Tensor x, Tensor mean, Tensor factor, Tensor offset, Tensor angle_idx, Tensor angle_scale, "
+        "Tensor shape_mean, Tensor weights, int num_cam=4, bool with_grad=True) -> (Tensor, Tensor, Tensor)");
+  m.def("fit_step_prior(Tensor(a!) x, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor(d!) t, Tensor(e!) calls, Tensor(f!) stall, "
+        "Tensor(g!) bad, Tensor(h!) best_step, Tensor(i!) active, Tensor(j!) best_loss, Tensor(k!) best_x, Tensor loss, "
+        "Tensor? silh_loss, Tensor col_scale, Tensor(l!)? history, Tensor mean, Tensor factor, Tensor offset, Tensor angle_idx, "
+        "Tensor angle_scale, Tensor shape_mean, Tensor weights, float lr=0.001, float beta1=0.9, float beta2=0.999, "
+        "float eps=1e-07, float gscale=1.0, float silh_weight=1.0, int mode=0, int patience=0, int num_cam=4) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch key is named CUDA in torch)
@@ -956,6 +1066,8 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("seg_colour", &seg_colour);
   m.impl("scatter_points", &scatter_points);
   m.impl("fit_step", &fit_step);
+  m.impl("prior_energy", &prior_energy);
+  m.impl("fit_step_prior", &fit_step_prior);
 }
 
 TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
@@ -980,4 +1092,6 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("seg_colour", &seg_colour_meta);
   m.impl("scatter_points", &scatter_points_meta);
   m.impl("fit_step", &fit_step_meta);
+  m.impl("prior_energy", &prior_energy_meta);
+  m.impl("fit_step_prior", &fit_step_prior_meta);
 }

@@ -28,10 +28,31 @@ Semantics of one call for row b (the definition; tests/_fitting_oracle.py restat
      with both bias corrections in fp64.  x[b, j] keeps its bits where col_scale[j] = 0 or the new m is 0 (so: frozen
      columns, inactive and bad rows, and entries with g = m = v = 0).
 Stages change col_scale only: step counts, moments and the best iterate run on across them.
+
+Priors (SMPLify's regularisers; csrc/prior_device.h; tests/_prior_oracle.py restates them in NumPy float64).  A part map does
+not determine bends in depth, twist about a limb's axis or the last shape components, so the data term can be paired with
+
+    prior = PosePrior.from_pickle("gmm_08.pkl").with_angles(SMPLIFY_ANGLE_IDX, SMPLIFY_ANGLE_SCALE)
+    result = fitter.fit(labels, init=prediction, stages=[(100, cs), (100, cs)], prior=prior,
+                        prior_weights=[(4.04, 15.2, 1.0), (0.4, 1.5, 0.5)])         # one triple per stage: annealing
+    E = prior_energy(x, prior.to(x.device), (1.0, 1.0, 1.0))                         # (B,), differentiable: a regulariser
+
+For row b, with theta = x[num_cam : num_cam + 72], beta = x[num_cam + 72 :], theta' = theta[3:72] (the global rotation is free):
+  pose   d_k = theta' - mean_k, y_k = A_k d_k, E_k = 1/2 |y_k|^2 + c_k over the K <= 16 components of a Gaussian mixture
+         (A_k^T A_k = the inverse covariance); E_pose = the first minimum over k (max-mixture), gradient A_k*^T y_k*.
+  angle  E_angle = sum_a exp(angle_scale[a] theta[angle_idx[a]]): A <= 16 terms that punish elbows and knees bent backwards.
+  shape  E_shape = sum_i (beta_i - shape_mean_i)^2.
+  E = w_pose E_pose + w_angle E_angle + w_shape E_shape; a term whose weight is exactly 0 is not evaluated.
+Everything is fp64 on the fp32 operands in a fixed order and rounded to fp32 once per output, so a row's E and gradient are
+the same bits on every launch and in any batch.  With a prior, `fit_step` makes ONE smplr_fit_step_prior launch instead of
+smplr_fit_step: L = fp32(L_data + E), g + dE/dx (one fp32 addition) in place of g, steps 2 - 5 on these totals; a non-finite E
+or gradient entry is a bad call.  The weights are a (3,) device tensor that `fit` rewrites at each stage boundary, so a
+captured graph follows them.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, fields
+import math
+from dataclasses import dataclass, fields, replace
 from typing import Optional
 
 import numpy as np
@@ -43,6 +64,13 @@ from ._lib import check, ptr, stream
 THREADS = 256                  # threads of a row's workgroup (csrc/fit.hip FT_T) = the widest row
 MODES = ("keras", "torch")
 KERAS_EPS = 1e-7               # keras.backend.epsilon(): Adam(epsilon=None) of Keras 2
+POSE_DIM = 69                  # theta[3:72]: what the pose prior sees (csrc/prior_device.h PR_D)
+MAX_COMPONENTS = 16            # PR_KMAX
+MAX_ANGLES = 16                # PR_AMAX
+# SMPLify's four bending terms: both elbows and both knees (theta indices), exp(+theta[55]), exp(-theta[58]), exp(-theta[12]),
+# exp(-theta[15])
+SMPLIFY_ANGLE_IDX = (55, 58, 12, 15)
+SMPLIFY_ANGLE_SCALE = (1.0, -1.0, -1.0, -1.0)
 
 
 @dataclass
@@ -115,13 +143,257 @@ def check_stages(stages, P, steps=None):
         out.append((n, cs))
     return out
 
+def _f32(a, shape, name):
+    t = torch.as_tensor(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a, dtype=np.float64))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    t = t.to(torch.float32).contiguous()
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError("%s holds values that are not finite in float32" % name)
+    return t
+
+
+def check_prior_weights(w, name="prior_weights"):
+    """(w_pose, w_angle, w_shape) -> a (3,) float32 CPU tensor; each finite and >= 0."""
+    t = torch.as_tensor(np.asarray(w.detach().cpu() if isinstance(w, torch.Tensor) else w, dtype=np.float64))
+    if tuple(t.shape) != (3,):
+        raise ValueError("%s must be (w_pose, w_angle, w_shape), got %r" % (name, w))
+    t = t.to(torch.float32)
+    if not bool(torch.isfinite(t).all()) or bool((t < 0).any()):
+        raise ValueError("%s must be finite and >= 0, got %r" % (name, w))
+    return t
+
+
+def mixture_terms(covs, mix_weights):
+    """covs (K, D, D), mix_weights (K,) -> float64 (factor (K, D, D), offset (K,)): factor[k] = the upper Cholesky factor of
+    inv(covs[k]), so factor[k]^T factor[k] covs[k] = I; offset[k] = -log w_k + 1/2 (logdet covs[k] - min_j logdet covs[j]) with
+    the weights normalised to sum 1 (so offset >= 0)."""
+    covs = np.asarray(covs, np.float64)
+    w = np.asarray(mix_weights, np.float64)
+    K = covs.shape[0]
+    factor = np.empty_like(covs)
+    logdet = np.empty(K)
+    for k in range(K):
+        try:
+            prec = np.linalg.inv(covs[k])
+            factor[k] = np.linalg.cholesky(0.5 * (prec + prec.T)).T
+        except np.linalg.LinAlgError as e:
+            raise ValueError("covariance %d is not positive definite: %s" % (k, e)) from None
+        sign, logdet[k] = np.linalg.slogdet(covs[k])
+        if sign <= 0:
+            raise ValueError("covariance %d is not positive definite" % k)
+    return factor, np.maximum(-np.log(w / w.sum()) + 0.5 * (logdet - logdet.min()), 0.0)
+
+
+@dataclass
+class PosePrior:
+    """The priors' data as fp32 tensors (built on the CPU and validated there; `.to(device)` for the kernels):
+    mean (K, 69), factor (K, 69, 69) dense row-major A_k with A_k^T A_k = inverse covariance, offset (K,) c_k >= 0,
+    angle_idx (A,) int32 in 0..71 with angle_scale (A,), shape_mean (10,); 1 <= K <= 16, 0 <= A <= 16."""
+    mean: torch.Tensor
+    factor: torch.Tensor
+    offset: torch.Tensor
+    angle_idx: torch.Tensor = None
+    angle_scale: torch.Tensor = None
+    shape_mean: torch.Tensor = None
+
+    def __post_init__(self):
+        # (always: tensors that live on a device are validated through a CPU copy, and the prior built is on the CPU;
+        # only `.to()` makes a device copy, of fields that passed here)
+        K = int(np.shape(self.mean)[0]) if np.ndim(self.mean) == 2 else -1
+        if not 1 <= K <= MAX_COMPONENTS:
+            raise ValueError("mean must be (K, %d) with 1 <= K <= %d, got %s" % (POSE_DIM, MAX_COMPONENTS, tuple(np.shape(self.mean))))
+        self.mean = _f32(self.mean, (K, POSE_DIM), "mean")
+        self.factor = _f32(self.factor, (K, POSE_DIM, POSE_DIM), "factor")
+        self.offset = _f32(self.offset, (K,), "offset")
+        if bool((self.offset < 0).any()):
+            raise ValueError("offset must be >= 0")
+        idx = np.asarray([] if self.angle_idx is None else
+                         (self.angle_idx.detach().cpu() if isinstance(self.angle_idx, torch.Tensor) else self.angle_idx))
+        A = idx.size
+        if idx.ndim != 1 or A > MAX_ANGLES:
+            raise ValueError("angle_idx must be (A,) with A <= %d, got shape %s" % (MAX_ANGLES, idx.shape))
+        if A and (not np.array_equal(idx, np.round(idx)) or idx.min() < 0 or idx.max() > 71):
+            raise ValueError("angle_idx must hold integers in 0..71, got %s" % idx.tolist())
+        self.angle_idx = torch.as_tensor(idx.astype(np.int32)).contiguous()
+        self.angle_scale = _f32([] if self.angle_scale is None else self.angle_scale, (A,), "angle_scale")
+        self.shape_mean = _f32(np.zeros(10) if self.shape_mean is None else self.shape_mean, (10,), "shape_mean")
+
+    @property
+    def K(self):
+        return int(self.mean.shape[0])
+
+    @property
+    def A(self):
+        return int(self.angle_idx.shape[0])
+
+    @property
+    def device(self):
+        return self.mean.device
+
+    def to(self, device):
+        """A copy of the validated fields on `device` (not validated again: no host synchronisation)."""
+        p = object.__new__(PosePrior)
+        for f in fields(self):
+            setattr(p, f.name, getattr(self, f.name).to(device))
+        return p
+
+    def cpu(self):
+        return self if not self.mean.is_cuda else self.to("cpu")
+
+    def with_angles(self, idx=SMPLIFY_ANGLE_IDX, scale=SMPLIFY_ANGLE_SCALE):
+        """The same prior with angle terms exp(scale[a] theta[idx[a]]); idx in 0..71 (theta's own numbering)."""
+        return replace(self.cpu(), angle_idx=list(idx), angle_scale=list(scale))
+
+    def with_shape_mean(self, shape_mean):
+        return replace(self.cpu(), shape_mean=shape_mean)
+
+    # ---- constructors -------------------------------------------------------------------------------------------------
+    @classmethod
+    def mixture(cls, means, covs, mix_weights):
+        """A Gaussian mixture over theta[3:72]: means (K, 69), covs (K, 69, 69) symmetric positive definite, mix_weights (K,)
+        > 0.  A_k = the upper Cholesky factor of inv(cov_k) in float64 (A_k^T A_k = inv(cov_k));
+        c_k = -log w_k + 1/2 (logdet cov_k - min_j logdet cov_j) >= -log w_k.  The (2 pi)^(D/2) constant is left out: it moves
+        neither the arg-min nor the gradient, and E stays on the data term's scale."""
+        means = np.asarray(means, np.float64)
+        covs = np.asarray(covs, np.float64)
+        w = np.asarray(mix_weights, np.float64)
+        K = means.shape[0] if means.ndim == 2 else -1
+        if not 1 <= K <= MAX_COMPONENTS or means.shape != (K, POSE_DIM) or covs.shape != (K, POSE_DIM, POSE_DIM) or w.shape != (K,):
+            raise ValueError("means (K, 69), covs (K, 69, 69), mix_weights (K,) with 1 <= K <= %d; got %s, %s, %s"
+                             % (MAX_COMPONENTS, means.shape, covs.shape, w.shape))
+        if not (np.isfinite(means).all() and np.isfinite(covs).all() and np.isfinite(w).all()) or (w <= 0).any():
+            raise ValueError("means, covs and mix_weights must be finite, the weights > 0")
+        factor, offset = mixture_terms(covs, w)
+        return cls(mean=means, factor=factor, offset=offset)
+
+    @classmethod
+    def gaussian(cls, mean69, cov):
+        return cls.mixture(np.asarray(mean69, np.float64)[None], np.asarray(cov, np.float64)[None], [1.0])
+
+    @classmethod
+    def from_samples(cls, theta69, shrink=0.1):
+        """One Gaussian from poses theta69 (N, 69): the sample mean and the covariance shrunk towards its own diagonal mean,
+        (1 - shrink) S + shrink tr(S) / 69 I (N may be smaller than 69)."""
+        t = np.asarray(theta69, np.float64)
+        if t.ndim != 2 or t.shape[1] != POSE_DIM or t.shape[0] < 2 or not 0.0 < shrink <= 1.0:
+            raise ValueError("theta69 must be (N >= 2, 69) and 0 < shrink <= 1")
+        S = np.cov(t, rowvar=False)
+        return cls.gaussian(t.mean(0), (1.0 - shrink) * S + shrink * np.trace(S) / POSE_DIM * np.eye(POSE_DIM))
+
+    @classmethod
+    def mean_pose(cls, sigma=0.5):
+        """Isotropic, sigma radians about the mean pose of data/mean_params.npz."""
+        from .smpl_model import load_mean_params
+        if not (math.isfinite(sigma) and sigma > 0):
+            raise ValueError("sigma must be > 0")
+        pose, shape = load_mean_params()
+        return cls(mean=pose[None, 3:], factor=(np.eye(POSE_DIM) / sigma)[None], offset=[0.0], shape_mean=np.zeros(10))
+
+    @classmethod
+    def from_pickle(cls, path):
+        """SMPLify's `gmm_08.pkl` layout: a (Python 2) pickle of {'means' (K, 69), 'covars' (K, 69, 69), 'weights' (K,)}, read
+        by a restricted unpickler that refuses every global outside numpy's array reconstruction."""
+        from .smpl_pkl import load_numpy_pickle
+        dd = load_numpy_pickle(path)
+        if not isinstance(dd, dict) or not all(k in dd for k in ("means", "covars", "weights")):
+            raise ValueError("%s: not a dict with 'means', 'covars' and 'weights'" % path)
+        return cls.mixture(dd["means"], dd["covars"], dd["weights"])
+
+
+def check_prior_layout(prior):
+    """What the kernels take on trust, checked without reading a value (no host synchronisation; any device): every field a
+    contiguous tensor of its dtype, mean (K, 69), factor (K, 69, 69), offset (K,) with 1 <= K <= 16, angle_idx and
+    angle_scale (A,) with A <= 16, shape_mean (10,).  The launchers get raw pointers and cannot see any of it."""
+    if not isinstance(prior, PosePrior):
+        raise TypeError("prior must be a PosePrior")
+    mean = prior.mean
+    K = int(mean.shape[0]) if isinstance(mean, torch.Tensor) and mean.dim() == 2 else -1
+    idx = prior.angle_idx
+    A = int(idx.shape[0]) if isinstance(idx, torch.Tensor) and idx.dim() == 1 else -1
+    if not 1 <= K <= MAX_COMPONENTS or not 0 <= A <= MAX_ANGLES:
+        raise RuntimeError("prior.mean must be a (K, %d) tensor with 1 <= K <= %d and prior.angle_idx an (A,) tensor with A <= %d"
+                           % (POSE_DIM, MAX_COMPONENTS, MAX_ANGLES))
+    want = {"mean": (K, POSE_DIM), "factor": (K, POSE_DIM, POSE_DIM), "offset": (K,), "angle_idx": (A,), "angle_scale": (A,),
+            "shape_mean": (10,)}
+    for name, shape in want.items():
+        a = getattr(prior, name)
+        dtype = torch.int32 if name == "angle_idx" else torch.float32
+        if not isinstance(a, torch.Tensor) or tuple(a.shape) != shape or a.dtype != dtype or not a.is_contiguous():
+            raise RuntimeError("prior.%s must be a contiguous %s tensor of shape %s, got %s"
+                               % (name, dtype, shape, "%s %s" % (a.dtype, tuple(a.shape)) if isinstance(a, torch.Tensor) else type(a)))
+    return prior
+
+
+def _prior_operands(prior, weights, x):
+    """Checked operands of a prior launch on x's device: (prior, weights (3,) fp32 device tensor)."""
+    check_prior_layout(prior)
+    for f in fields(prior):
+        a = getattr(prior, f.name)
+        if a.device != x.device:
+            raise RuntimeError("prior.%s lives on %s, x on %s: use prior.to(device)" % (f.name, a.device, x.device))
+        _lib.require_cuda(a, "prior." + f.name, torch.int32 if f.name == "angle_idx" else torch.float32)
+    if isinstance(weights, torch.Tensor) and weights.is_cuda:
+        if tuple(weights.shape) != (3,) or weights.device != x.device:
+            raise RuntimeError("prior weights must be a (3,) tensor on %s" % x.device)
+        w = _lib.require_cuda(weights, "prior_weights")
+    else:
+        w = check_prior_weights((1.0, 1.0, 1.0) if weights is None else weights).to(x.device)
+    return prior, w
+
+
+@_lib.on_device
+def prior_terms(x, prior, weights=None, num_cam=4, with_grad=True):
+    """One smplr_prior_energy launch: x (B, num_cam + 82) -> dict(energy (B, 4) = E_pose, E_angle, E_shape unweighted and the
+    weighted E; comp (B,) int32 = the winning component; grad (B, P) = dE/dx or None)."""
+    x = _lib.require_cuda(x.detach(), "x")
+    if x.dim() != 2 or x.shape[1] != int(num_cam) + 82:
+        raise RuntimeError("x must be (B, num_cam + 82) with num_cam = %d, got %s" % (num_cam, tuple(x.shape)))
+    prior, w = _prior_operands(prior, weights, x)
+    B, P = int(x.shape[0]), int(x.shape[1])
+    energy = torch.empty((B, 4), dtype=torch.float32, device=x.device)
+    comp = torch.empty((B,), dtype=torch.int32, device=x.device)
+    grad = torch.empty((B, P), dtype=torch.float32, device=x.device) if with_grad else None
+    check(_lib.load().smplr_prior_energy(ptr(x), B, P, int(num_cam), ptr(prior.mean), ptr(prior.factor), ptr(prior.offset),
+                                         ptr(prior.angle_idx) if prior.A else None, ptr(prior.angle_scale) if prior.A else None,
+                                         ptr(prior.shape_mean), prior.K, prior.A, ptr(w), ptr(energy), ptr(comp), ptr(grad),
+                                         stream()), "smplr_prior_energy")
+    return {"energy": energy, "comp": comp, "grad": grad}
+
+
+class _PriorEnergy(torch.autograd.Function):
+    """-> E (B,), energy (B, 4), comp (B,), grad (B, P) of one launch; only E is differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, prior, weights, num_cam):
+        out = prior_terms(x, prior, weights, num_cam, with_grad=True)
+        ctx.save_for_backward(out["grad"])
+        ctx.mark_non_differentiable(out["energy"], out["comp"], out["grad"])
+        return out["energy"][:, 3].clone(), out["energy"], out["comp"], out["grad"]
+
+    @staticmethod
+    def backward(ctx, upstream, *_):
+        (grad,) = ctx.saved_tensors
+        return upstream[:, None] * grad, None, None, None
+
+
+def prior_energy(x, prior, weights=None, num_cam=4, return_terms=False):
+    """E (B,) of the rows of x (B, num_cam + 82), differentiable in x: forward is one smplr_prior_energy launch that also
+    saves dE/dx, backward is upstream[:, None] * dE/dx.  weights = (w_pose, w_angle, w_shape) (None: ones) or a (3,) device
+    tensor.  return_terms=True -> (E, dict(energy (B, 4), comp (B,), grad (B, P))): the breakdown of the same launch (constants
+    to autograd; E stays differentiable)."""
+    E, energy, comp, grad = _PriorEnergy.apply(x, prior, weights, num_cam)
+    return (E, {"energy": energy, "comp": comp, "grad": grad}) if return_terms else E
+
 
 @_lib.on_device
 def fit_step(state, grad, loss, silh_loss=None, silh_weight=1.0, col_scale=None, history=None, lr=1e-3, beta1=0.9,
-             beta2=0.999, eps=KERAS_EPS, grad_scale=1.0, mode="keras", patience=0):
+             beta2=0.999, eps=KERAS_EPS, grad_scale=1.0, mode="keras", patience=0, prior=None, prior_weights=None, num_cam=4):
     """One smplr_fit_step launch on `state` (in place; see the module's semantics).  grad (B, P): the gradient of
     sum_b L_b; loss (B, N) and silh_loss (B, Ns): per-pixel losses as `SMPLDecoder(loss=...)` returns them; col_scale (P,)
-    (None: ones); history (H, B) or None.  HIP tensors only."""
+    (None: ones); history (H, B) or None.  HIP tensors only.  With prior (a `PosePrior` on the device) the launch is
+    smplr_fit_step_prior: the prior's E joins L and its gradient joins grad inside the kernel; prior_weights = a triple or
+    a (3,) device tensor (None: ones); P = num_cam + 82."""
     if mode not in MODES:
         raise ValueError("mode %r is none of %s" % (mode, MODES))
     rc = _lib.require_cuda
@@ -168,6 +440,19 @@ def fit_step(state, grad, loss, silh_loss=None, silh_weight=1.0, col_scale=None,
                                                                ("col_scale", col_scale), ("history", history)]:
         if a is not None and a.device != x.device:
             raise RuntimeError("%s lives on %s, x on %s" % (name, a.device, x.device))
+    if prior is not None:
+        prior, w = _prior_operands(prior, prior_weights, x)
+        check(_lib.load().smplr_fit_step_prior(
+            ptr(x), ptr(grad), ptr(state.m), ptr(state.v), ptr(state.t), ptr(state.calls), ptr(state.stall), ptr(state.bad),
+            ptr(state.best_step), ptr(state.active), ptr(state.best_loss), ptr(state.best_x), ptr(loss), int(loss.shape[1]),
+            ptr(silh_loss), Ns, float(silh_weight), ptr(col_scale), ptr(history) if H else None, H, B, P, float(lr), float(beta1),
+            float(beta2), float(eps), float(grad_scale), MODES.index(mode), int(patience), int(num_cam), ptr(prior.mean),
+            ptr(prior.factor), ptr(prior.offset), ptr(prior.angle_idx) if prior.A else None,
+            ptr(prior.angle_scale) if prior.A else None, ptr(prior.shape_mean), prior.K, prior.A, ptr(w), stream()),
+            "smplr_fit_step_prior")
+        return state
+    if prior_weights is not None:
+        raise ValueError("prior_weights without a prior")
     check(_lib.load().smplr_fit_step(ptr(x), ptr(grad), ptr(state.m), ptr(state.v), ptr(state.t), ptr(state.calls),
                                      ptr(state.stall), ptr(state.bad), ptr(state.best_step), ptr(state.active),
                                      ptr(state.best_loss), ptr(state.best_x), ptr(loss), int(loss.shape[1]), ptr(silh_loss), Ns,
@@ -244,10 +529,10 @@ class ParamFitter:
         return _lib.require_cuda(labels.to(torch.int32).reshape(B, W, W), name, torch.int32)
 
     # ---- one iteration ------------------------------------------------------------------------------------------------
-    def losses(self, x, labels, silh_labels=None):
+    def losses(self, x, labels, silh_labels=None, prior=None, prior_weights=None):
         """Per-row loss (B,) fp32 of parameters x (B, P) against the labels: one gradient-free decoder forward reduced by
         the kernel of the loop (a call with a zero gradient on a scratch state), so the bits are those `fit` would record
-        for x in its history."""
+        for x in its history.  With a prior its weighted energy E is part of the loss, as in `fit`."""
         B = int(x.shape[0])
         labels = self._labels(labels, B, self.img_wh, "labels")
         if (silh_labels is not None) != self.with_silhouette:
@@ -259,8 +544,20 @@ class ParamFitter:
             out = self.decoder(x, labels, silh_labels=silh_labels)
             hist = torch.empty((1, B), dtype=torch.float32, device=x.device)
             fit_step(FitState.new(x), torch.zeros_like(x), out["seg_loss"],
-                     out["silh_loss"] if silh_labels is not None else None, self.silh_weight, None, hist)
+                     out["silh_loss"] if silh_labels is not None else None, self.silh_weight, None, hist,
+                     **self._prior_kw(prior, prior_weights, x.device))
         return hist[0]
+
+    def _prior_kw(self, prior, weights, dev):
+        """fit_step's prior arguments: the prior on the device and a (3,) device tensor of weights; {} without a prior."""
+        if prior is None:
+            if weights is not None:
+                raise ValueError("prior_weights without a prior")
+            return {}
+        if not isinstance(prior, PosePrior):
+            raise TypeError("prior must be a PosePrior")
+        return dict(prior=prior.to(dev), prior_weights=check_prior_weights((1.0, 1.0, 1.0) if weights is None else weights).to(dev),
+                    num_cam=self.num_cam)
 
     def _iteration(self, state, labels, silh_labels, gout, sgout, cs, hist, kw):
         x = state.x.detach().requires_grad_(True)                 # (shares x's memory: the kernel updates it in place)
@@ -278,7 +575,7 @@ class ParamFitter:
     # ---- the loop -----------------------------------------------------------------------------------------------------
     def fit(self, labels, init=None, steps=1601, lr=1e-3, mode="keras", stages=None, silh_labels=None, patience=0,
             grad_scale=1.0, graph=False, check_every=0, history=False, beta1=0.9, beta2=0.999, eps=KERAS_EPS,
-            graph_steps=4, generator=None):
+            graph_steps=4, generator=None, prior=None, prior_weights=None):
         """labels (B, W, W) integer part maps on the HIP device -> FitResult.
 
         steps: iterations (decoder_loss_debugging.py:123 runs 1601), or stages = [(steps, column_scale), ...] run one after
@@ -286,7 +583,9 @@ class ParamFitter:
         without a new best (0: never); grad_scale = 1 / B reproduces Keras' batch-mean loss (decoder_loss_debugging.py:125,
         batch_size = num_indices); graph=True replays `graph_steps` iterations per launch of one captured HIP graph;
         check_every = k > 0 reads `active.any()` every k iterations (the loop's only host synchronisation) and stops when
-        no row is active; history=True records every call's loss per row."""
+        no row is active; history=True records every call's loss per row; prior: a `PosePrior` whose energy joins every row's
+        loss inside the same launch, with prior_weights = (w_pose, w_angle, w_shape) (None: ones) or a list of one triple
+        per stage (SMPLify's annealing)."""
         if mode not in MODES:
             raise ValueError("mode %r is none of %s" % (mode, MODES))
         if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
@@ -300,6 +599,15 @@ class ParamFitter:
             silh_labels = self._labels(silh_labels, B, self.silh_wh, "silh_labels")
         stage_list = check_stages(stages, self.P, steps)
         total = sum(n for n, _ in stage_list)
+        if prior is None and prior_weights is not None:
+            raise ValueError("prior_weights without a prior")
+        stage_w = None
+        if prior is not None:
+            pw = (1.0, 1.0, 1.0) if prior_weights is None else prior_weights
+            per_stage = isinstance(pw, (list, tuple)) and len(pw) > 0 and all(np.ndim(w) == 1 for w in pw)
+            if per_stage and len(pw) != len(stage_list):
+                raise ValueError("prior_weights lists %d triples for %d stages" % (len(pw), len(stage_list)))
+            stage_w = [check_prior_weights(w) for w in (pw if per_stage else [pw] * len(stage_list))]
         G = max(1, int(graph_steps))
         check_every = int(check_every)
         with torch.cuda.device(dev):
@@ -312,6 +620,9 @@ class ParamFitter:
             scales = [c.to(dev) for _, c in stage_list]
             kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
                       mode=mode, patience=int(patience))
+            if prior is not None:
+                kw.update(self._prior_kw(prior, stage_w[0], dev))     # (the (3,) tensor is rewritten at each stage boundary)
+                stage_w = [w.to(dev) for w in stage_w]
             one = lambda st, h: self._iteration(st, labels, silh_labels, gout, sgout, cs, h, kw)
             replay = None
             if graph and B > 0 and any(n >= G for n, _ in stage_list):
@@ -330,8 +641,10 @@ class ParamFitter:
                         one(state, hist)
                 replay = g_.replay
             done, stopped = 0, False
-            for (n, _), sc in zip(stage_list, scales):
+            for si, ((n, _), sc) in enumerate(zip(stage_list, scales)):
                 cs.copy_(sc)
+                if prior is not None:
+                    kw["prior_weights"].copy_(stage_w[si])
                 left = n
                 while left > 0 and not stopped:
                     if replay is not None and left >= G:

@@ -65,6 +65,22 @@ class _Restricted(pickle.Unpickler):
         raise pickle.UnpicklingError("SMPL pkl: global %s.%s is not allowed" % (module, name))
 
 
+class _NumpyOnly(_Restricted):
+    """Arrays and plain containers only: no chumpy stub, no scipy."""
+
+    def find_class(self, module, name):
+        if module.startswith("chumpy") or module.startswith("scipy"):
+            raise pickle.UnpicklingError("pickle: global %s.%s is not allowed" % (module, name))
+        return super().find_class(module, name)
+
+
+def load_numpy_pickle(path: str):
+    """A pickle (Python 2 or 3) of dicts / lists / numbers / numpy arrays, e.g. SMPLify's `gmm_08.pkl`; any global outside
+    numpy's array reconstruction raises pickle.UnpicklingError."""
+    with open(path, "rb") as f:
+        return _NumpyOnly(f, encoding="latin1").load()
+
+
 def _arr(v):
     if isinstance(v, _ChStub):
         return np.asarray(v.r, np.float64)

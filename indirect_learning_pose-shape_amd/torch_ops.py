@@ -64,6 +64,16 @@ SCHEMAS = {
                  "Tensor(k!) best_x, Tensor loss, Tensor? silh_loss, Tensor col_scale, Tensor(l!)? history, float lr=0.001, "
                  "float beta1=0.90000000000000002, float beta2=0.999, float eps=9.9999999999999995e-08, float gscale=1., "
                  "float silh_weight=1., int mode=0, int patience=0) -> ()"),
+    "prior_energy": ("smplraster::prior_energy(Tensor x, Tensor mean, Tensor factor, Tensor offset, Tensor angle_idx, "
+                     "Tensor angle_scale, Tensor shape_mean, Tensor weights, int num_cam=4, bool with_grad=True) -> "
+                     "(Tensor, Tensor, Tensor)"),
+    "fit_step_prior": ("smplraster::fit_step_prior(Tensor(a!) x, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor(d!) t, "
+                       "Tensor(e!) calls, Tensor(f!) stall, Tensor(g!) bad, Tensor(h!) best_step, Tensor(i!) active, "
+                       "Tensor(j!) best_loss, Tensor(k!) best_x, Tensor loss, Tensor? silh_loss, Tensor col_scale, "
+                       "Tensor(l!)? history, Tensor mean, Tensor factor, Tensor offset, Tensor angle_idx, Tensor angle_scale, "
+                       "Tensor shape_mean, Tensor weights, float lr=0.001, float beta1=0.90000000000000002, float beta2=0.999, "
+                       "float eps=9.9999999999999995e-08, float gscale=1., float silh_weight=1., int mode=0, int patience=0, "
+                       "int num_cam=4) -> ()"),
 }
 
 _ns = None

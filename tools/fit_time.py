@@ -1,5 +1,5 @@
 """Iterations per second of fitting SMPL parameters to label maps, three loops at the same commit, one GPU:
-    python tools/fit_time.py [--batch 128] [--iters 1600] [--rounds 3] [--launches]
+    python tools/fit_time.py [--batch 128] [--iters 1600] [--rounds 3] [--launches] [--prior K [--angles A]] [--loops fitter,graph]
 At B = 128, W = 48 (the reference's decoder_loss_debugging.py runs the loop at W = 48), targets = the arg-max part maps
 of seeded parameters, start = those parameters with pose noise and a camera shift:
     stock     the loop a user of the decoder writes with stock torch: the same `SMPLDecoder(loss=...)`, `seg_loss.mean(1)`,
@@ -9,7 +9,9 @@ of seeded parameters, start = those parameters with pose noise and a camera shif
 Each figure is a host clock around a whole `fit` / `stock_fit` call of --iters iterations that ends in a device
 synchronise (set-up, warm-up and graph capture of that call included: they are part of what a user waits for), taken
 after one untimed call per loop; the loops alternate --rounds times, every round is printed, the median is reported.
---launches counts the device kernels per iteration of each loop with torch.profiler in a short run of its own (tracing
+--prior K adds a seeded K-component pose prior with --angles A angle terms and a shape prior to the fitter's two loops (the
+stock loop has none): the same single launch per iteration, smplr_fit_step_prior in place of smplr_fit_step.  --loops picks
+the loops to run.  --launches counts the device kernels per iteration of each loop with torch.profiler in a short run of its own (tracing
 slows the host: no timing is taken from it)."""
 import argparse
 import json
@@ -70,6 +72,20 @@ def problem(fitter, B, W, seed=0, pose_sigma=0.05, cam_shift=1.5):
     return labels, xs + torch.from_numpy(d).to(dev), xs
 
 
+def seeded_prior(K, A, seed=0):
+    """A K-component mixture about the mean pose (means N(0, 0.3^2) away, upper-triangular factors with diagonal U[2, 6]), A
+    angle terms on distinct theta indices, a shape prior about N(0, 0.5^2)."""
+    from ilps_amd.fitting import PosePrior
+    from ilps_amd.smpl_model import load_mean_params
+    rng = np.random.default_rng(seed)
+    mean = load_mean_params()[0][None, 3:] + rng.normal(0.0, 0.3, (K, 69))
+    factor = np.triu(rng.normal(0.0, 0.3, (K, 69, 69)), 1)
+    for k in range(K):
+        factor[k][np.diag_indices(69)] = rng.uniform(2.0, 6.0, 69)
+    return PosePrior(mean=mean, factor=factor, offset=rng.uniform(0.0, 3.0, K), angle_idx=rng.choice(np.arange(3, 72), A, replace=False),
+                     angle_scale=rng.uniform(-2.0, 2.0, A), shape_mean=rng.normal(0.0, 0.5, 10))
+
+
 def wall(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -103,16 +119,22 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--graph-steps", type=int, default=10)
     ap.add_argument("--launches", action="store_true")
+    ap.add_argument("--prior", type=int, default=0, help="components of a seeded pose prior for the fitter's loops (0: none)")
+    ap.add_argument("--angles", type=int, default=4)
+    ap.add_argument("--loops", default="stock,fitter,graph")
     a = ap.parse_args()
     from ilps_amd import _lib
     from ilps_amd.fitting import ParamFitter
     B, W, G = a.batch, a.wh, a.graph_steps
     fitter = ParamFitter(None, img_wh=W)
     labels, x0, _ = problem(fitter, B, W)
+    pkw = dict(prior=seeded_prior(a.prior, a.angles), prior_weights=(1e-3, 1e-3, 1e-3)) if a.prior > 0 else {}
     loops = {"stock": lambda n: stock_fit(fitter.decoder, labels, x0, n),
-             "fitter": lambda n: fitter.fit(labels, init=x0, steps=n),
-             "graph": lambda n: fitter.fit(labels, init=x0, steps=n, graph=True, graph_steps=G)}
-    res = {"build_id": _lib.build_id()[:16], "B": B, "W": W, "iters": a.iters, "graph_steps": G}
+             "fitter": lambda n: fitter.fit(labels, init=x0, steps=n, **pkw),
+             "graph": lambda n: fitter.fit(labels, init=x0, steps=n, graph=True, graph_steps=G, **pkw)}
+    loops = {k: fn for k, fn in loops.items() if k in a.loops.split(",")}
+    res = {"build_id": _lib.build_id()[:16], "B": B, "W": W, "iters": a.iters, "graph_steps": G, "prior_K": a.prior,
+           "prior_A": a.angles if a.prior > 0 else 0}
     if a.launches:
         for fn in loops.values():
             fn(2 * G)                                               # untimed and untraced: code objects loaded
@@ -130,10 +152,11 @@ def main():
     res["us_per_iteration"] = {k: round(statistics.median(vs), 1) for k, vs in us.items()}
     res["iterations_per_s"] = {k: round(1e6 / statistics.median(vs)) for k, vs in us.items()}
     # the three loops on the same problem: mean best loss against the start's (not the same optimiser: stock is torch's Adam)
-    s = stock_fit(fitter.decoder, labels, x0, n)
-    f = fitter.fit(labels, init=x0, steps=n)
-    res["mean_loss"] = {"start": round(float(fitter.losses(x0, labels).mean()), 6), "stock": round(float(s[1].mean()), 6),
-                        "fitter": round(float(f.loss.mean()), 6)}
+    if "stock" in loops and "fitter" in loops and not pkw:
+        s = stock_fit(fitter.decoder, labels, x0, n)
+        f = fitter.fit(labels, init=x0, steps=n)
+        res["mean_loss"] = {"start": round(float(fitter.losses(x0, labels).mean()), 6), "stock": round(float(s[1].mean()), 6),
+                            "fitter": round(float(f.loss.mean()), 6)}
     print(json.dumps(res))
 
 
