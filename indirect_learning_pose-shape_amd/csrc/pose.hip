@@ -8,8 +8,8 @@
 // :122 (pose_feature), :106-115 (J from v_shaped; here J = J_template + J_dirs*beta, which is
 // the same linear map evaluated in the other association order), :168-228 (global rigid).
 #include <stdarg.h>
-#include "common.h"
 #include "pose_device.h"
+#include "skin_device.h"   // SkinPart: the skinning backward's partial sums
 
 namespace smplr {
 
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(PBW) void pose_bwd_kernel(
     const float *__restrict__ Rs_in, const float *__restrict__ J_in, const float *__restrict__ A_in,
     const float *__restrict__ dcoef, const float *__restrict__ dA, const float *__restrict__ dnewJ,
     const float *__restrict__ dcam, float *__restrict__ dx,
-    // fused mode (dA == nullptr): sum the skinning partials (B,nblk,292) and the split-K partials
+    // fused mode (dA == nullptr): sum the skinning partials (B,nblk,SkinPart::FLOATS) and the split-K partials
     // (ns,nmt,32,224) of the blend GEMM here, in fixed order, instead of in two more launches
     const float *__restrict__ skin_part, int nblk, const float *__restrict__ blend_part, int ns, int nmt,
     int want_dcam) {
@@ -143,12 +143,12 @@ __global__ __launch_bounds__(PBW) void pose_bwd_kernel(
     // reduce kernels.
     constexpr int PB_INFLIGHT = 60;
     for (int e = tid; e < 512; e += PBW) {
-      const bool skin = e < 292;
+      const bool skin = e < SkinPart::FLOATS;
       const int cnt = skin ? nblk : ns;
       const size_t mt = nn >> 5, r = nn & 31;
-      const float *p = skin ? skin_part + (nn * nblk) * 292 + e
-                            : blend_part + (mt * 32 + r) * 224 + min(e - 292, 219);
-      const size_t stride = skin ? (size_t)292 : (size_t)nmt * 32 * 224;
+      const float *p = skin ? skin_part + (nn * nblk) * SkinPart::FLOATS + e
+                            : blend_part + (mt * 32 + r) * 224 + min(e - SkinPart::FLOATS, 219);
+      const size_t stride = skin ? (size_t)SkinPart::FLOATS : (size_t)nmt * 32 * 224;
       float acc = 0.0f;
       for (int s0 = 0; s0 < cnt; s0 += PB_INFLIGHT) {
         float v[PB_INFLIGHT];
@@ -157,9 +157,9 @@ __global__ __launch_bounds__(PBW) void pose_bwd_kernel(
 #pragma unroll
         for (int u = 0; u < PB_INFLIGHT; ++u) acc += (s0 + u < cnt) ? v[u] : 0.0f;
       }
-      if (e < 288) L.dA[e / 12][e % 12] = acc;
-      else if (e < 292) L.dcam[e - 288] = want_dcam ? acc : 0.0f;
-      else if (e - 292 < 220) L.dcoef[e - 292] = acc;
+      if (e < SkinPart::DA) L.dA[e / 12][e % 12] = acc;
+      else if (e < SkinPart::FLOATS) L.dcam[e - SkinPart::DA] = want_dcam ? acc : 0.0f;
+      else if (e - SkinPart::FLOATS < 220) L.dcoef[e - SkinPart::FLOATS] = acc;
     }
   }
   __syncthreads();
@@ -378,7 +378,7 @@ size_t smplr_smpl_bwd_workspace(int B, int V) {
   using namespace smplr;
   if (B <= 0 || V <= 0) return 0;
   const size_t pf = blend_bwd_geom(B, 3 * V).part_floats, pf3 = blend3_bwd_geom(B, 3 * V).part_floats;
-  return align256((size_t)B * V * 3 * sizeof(float)) + align256((size_t)B * skin_bwd_nblk(V) * 292 * sizeof(float)) +
+  return align256((size_t)B * V * 3 * sizeof(float)) + align256(skin_bwd_part_floats(B, V) * sizeof(float)) +
          align256((pf > pf3 ? pf : pf3) * sizeof(float));
 }
 
@@ -407,7 +407,7 @@ int smplr_smpl_bwd(const float *dverts, const float *dproj, const float *seg_par
   float *dv_posed = reinterpret_cast<float *>(base);
   float *skin_part = reinterpret_cast<float *>(base + align256((size_t)B * V * 3 * sizeof(float)));
   float *blend_part = reinterpret_cast<float *>(reinterpret_cast<char *>(skin_part) +
-                                                align256((size_t)B * skin_bwd_nblk(V) * 292 * sizeof(float)));
+                                                align256(skin_bwd_part_floats(B, V) * sizeof(float)));
   int skin_nblk = 0;
   int rc = launch_skin_bwd_partials(dverts, dproj, SegGrad{seg_part, seg_vslot, seg_nsplit}, v_posed, lbs_weights,
                                     lbs_top4, A, has_proj ? x : nullptr, x_stride, B, V, vertex_sampling, dv_posed,

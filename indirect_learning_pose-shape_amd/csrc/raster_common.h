@@ -15,7 +15,7 @@
 // lstart[npix + 1] = the pixels' ranges of local records; lrec[K] = (x bits, part) per local record.
 #pragma once
 #include <hip/hip_ext.h>
-#include "common.h"
+#include "skin_device.h"   // SkinIn (and common.h)
 
 namespace smplr {
 __host__ __device__ constexpr int goff_stride(int P) { return P + 2 + 32; }   // ints per mesh in `goff`

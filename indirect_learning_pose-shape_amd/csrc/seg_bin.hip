@@ -10,6 +10,7 @@
 //      changing a single fp32 result.
 // The rasteriser (raster.hip) and the backward (seg_bwd.hip) read what it leaves; the layout is in raster_common.h.
 #include "raster_common.h"
+#include "skin_device.h"
 
 namespace smplr {
 constexpr int BIN_Q0 = 3;            // seg_bin_kernel<.., SKIN>: vertices per thread whose operands are requested before the first barrier
@@ -62,7 +63,7 @@ __device__ __forceinline__ Slot classify(float u, float v, float m, int pos, int
 // ONE round trip to global memory - its vertices (coalesced) and its part-table slots, requested
 // together at the top - and the per-slot gathers of classification become LDS reads.
 // SKIN = true (with VIS and STAGE): the workgroup skins and projects its mesh's vertices itself (skin_fwd_kernel's
-// arithmetic, common.h) from v_posed, the sparse weights and the joint matrices, writes verts and proj out and goes on
+// arithmetic, skin_device.h) from v_posed, the sparse weights and the joint matrices, writes verts and proj out and goes on
 // with the values in registers: the skinning launch, its ramp and the re-read of proj go away.
 template <bool VIS, bool STAGE, bool SKIN>
 __global__ __launch_bounds__(BIN_T) void seg_bin_kernel(const float *__restrict__ proj,

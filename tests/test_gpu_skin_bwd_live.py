@@ -3,10 +3,6 @@ vertex near a pixel centre that never won an arg-min - is treated like a vertex 
 stored as zeros, it takes no lane of the dA product).  The reference in every case is the per-vertex kernel of the same
 process fed the merged d proj scattered from the same sums (as test_skin_backward_over_records_equals_per_vertex gets
 its reference), at that test's bar: grad_close(..., 2e-5).  V = 6 890: seven 1 024-vertex chunks, the last one ragged."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
@@ -16,7 +12,6 @@ from test_gpu_parity import dev, grad_close, t
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NSLOT = 5 * 4096                       # slots per row block of the partial buffer (SB_NWIN * SB_SLOTS)
 PIPELINE = [(16, 1), (24, 1), (16, 5), (24, 5)]      # (W, vertex sampling): two and three row blocks at B = 3
 BAR = 2e-5
@@ -64,23 +59,6 @@ def pipeline_case(model, W, vs, B=3):
 @pytest.mark.parametrize("W,vs", PIPELINE)
 def test_live_records_real_pipeline(smpl_model, W, vs):
     pipeline_case(smpl_model, W, vs)
-
-
-def test_old_predicate_switch(smpl_model):
-    """SMPLR_SKIN_BWD_LIVE=0 (read once: a fresh process) walks every record again and passes the same cases."""
-    code = ("import sys\n"
-            "sys.path.insert(0, 'tests')\n"
-            "import ilps_amd\n"
-            "import test_gpu_skin_bwd_live as m\n"
-            "from ilps_amd.smpl_model import synthetic_smpl_model\n"
-            "model = synthetic_smpl_model(1234)\n"
-            "for W, vs in m.PIPELINE:\n"
-            "    m.pipeline_case(model, W, vs)\n"
-            "print('all cases passed')\n")
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, SMPLR_SKIN_BWD_LIVE="0"), capture_output=True,
-                       text=True, timeout=300, cwd=ROOT)
-    assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-3000:]
-    assert "all cases passed" in r.stdout, r.stdout
 
 
 # --------------------------------------------------------------------------------- hand-built (part, vslot, nsplit)
