@@ -487,6 +487,43 @@ int smplr_resize_pad(const uint8_t *data, long long data_bytes, const long long 
 int smplr_point_errors(const float *pred, const float *gt, int B, int N, int root, int pp_mode, float *mean_err,
                        float *transform, float *per_point, int32_t *status, void *stream);
 
+/* ---- body measurements of a mesh and their gradient (beyond the reference); INTEGRATION.md 4l ---------------------------
+ * verts (B, V, 3) fp32; faces (F, 3) int32, face_part (F) uint8, vf_off (V + 1) / vf_face (nnz) int32: the vertex -> face
+ * lists (a face once per corner that names the vertex, faces in increasing order), as `MeshTopology` builds them.
+ * planes: K rows [n_x, n_y, n_z, o] fp32, mesh b's at planes + b * plane_bstride (floats; 0 = one set for the batch); the
+ * normal need not be unit length.  part_mask (K) uint32: bit p selects the faces with face_part == p.
+ *   volume (B)     = 1/6 sum_f v0 . (v1 x v2): signed; for an open mesh whatever the formula gives.
+ *   area (B)       = 1/2 sum_f |(v1 - v0) x (v2 - v0)|.
+ *   extent (B, 3)  = max_i v_i[a] - min_i v_i[a] over all V vertices; ext_idx (B, 6) int32 = argmin x, y, z, argmax x, y, z,
+ *                    ties to the lowest index.
+ *   girth (B, K)   : d_i = ((n_x x_i + n_y y_i) + n_z z_i) - o; vertex i is above iff d_i >= 0.  A selected face whose
+ *                    vertices are not all on one side has two edges from an above vertex i to a below vertex j, each with
+ *                    q = v_i + t (v_j - v_i), t = d_i / (d_i - d_j); the face adds |q - q'|.  A zero-length segment adds 0
+ *                    and has zero gradient; a zero-area face has zero area gradient.
+ *   dgirth_dplane (B, K, 4) or NULL: d girth[k] / d (n_x, n_y, n_z, o), summed over the faces as girth is.
+ *   status (B) int32: SMPLR_MM_NONFINITE - a coordinate of the mesh or an entry of its planes is NaN or Inf: its outputs and
+ *                    its dverts rows are NaN, its ext_idx -1.  Other meshes are not affected.
+ * smplr_mesh_measures_bwd: dverts (B, V, 3) = the gradient of sum_b g_volume[b] volume[b] + g_area[b] area[b] + g_extent[b] .
+ *   extent[b] + g_girth[b] . girth[b]; each cotangent (B), (B), (B, 3), (B, K) may be NULL (zero).  One thread per vertex
+ *   gathers over that vertex's faces in vf_off / vf_face order; the extent term goes to the ext_idx vertices of the forward;
+ *   status is the forward's.  Every row is written.
+ * All arithmetic is fp64 on the fp32 operands in a fixed order (no atomics), each output rounded to fp32 once: a mesh's
+ * results are the same bits on every launch and in any batch.  One launch each; no workspace, allocation or
+ * synchronisation.  Indices read from memory are range-checked: a face with a vertex outside [0, V) contributes nothing.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= V <= 2^24, 0 <= F <= 2^24, 0 <= K <= 16, plane_bstride 0 or
+ * >= 4 K, nnz <= 3 * 2^24, B >= 0 (B = 0 is a no-op); no null pointer except dgirth_dplane, the cotangents, and with K = 0
+ * face_part, planes, part_mask, girth.                                                                                   */
+#define SMPLR_MM_NONFINITE 1
+int smplr_mesh_measures(const float *verts, const int32_t *faces, const uint8_t *face_part, const float *planes,
+                        long long plane_bstride, const uint32_t *part_mask, int B, int V, int F, int K, float *volume,
+                        float *area, float *extent, int32_t *ext_idx, float *girth, float *dgirth_dplane, int32_t *status,
+                        void *stream);
+int smplr_mesh_measures_bwd(const float *verts, const int32_t *faces, const int32_t *vf_off, const int32_t *vf_face, int nnz,
+                            const uint8_t *face_part, const float *planes, long long plane_bstride,
+                            const uint32_t *part_mask, const int32_t *ext_idx, const int32_t *status, const float *g_volume,
+                            const float *g_area, const float *g_extent, const float *g_girth, int B, int V, int F, int K,
+                            float *dverts, void *stream);
+
 /* ---- prediction figures: predict.py:28-77 (_seg.png, _projects.png, _verts_overlay.png), train.py:283-290,
  * train_stage2_silhouette.py:318-329, predict_realtime.py:75-96; INTEGRATION.md 4h -------------------------------------
  * One launch each on the caller's stream; no workspace, no allocation, no synchronisation, no global atomics.  Colours

@@ -990,6 +990,133 @@ void fit_step_prior_meta(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tenso
   prior_check(x, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, num_cam);
 }
 
+// ---- body measurements (csrc/measure.hip): verts (B, V, 3), faces (F, 3) int32, face_part (F) uint8, planes (K, 4) or
+// (B, K, 4), part_mask (K) int32 holding the 32 mask bits -> [volume (B), area (B), extent (B, 3), ext_idx (B, 6) int32,
+// girth (B, K), dgirth_dplane (B, K, 4) or (0) without plane_grad, status (B) int32]; K = 0 without planes -----------------
+struct MeasureDims { int64_t B, V, F, K, bstride; };
+MeasureDims measure_check(const Tensor &verts, const Tensor &faces, const c10::optional<Tensor> &face_part,
+                          const c10::optional<Tensor> &planes, const c10::optional<Tensor> &part_mask) {
+  TORCH_CHECK(verts.dim() == 3 && verts.size(2) == 3 && verts.scalar_type() == at::kFloat, "verts must be (B, V, 3) float32");
+  TORCH_CHECK(faces.dim() == 2 && faces.size(1) == 3 && faces.scalar_type() == at::kInt, "faces must be (F, 3) int32");
+  MeasureDims d{verts.size(0), verts.size(1), faces.size(0), 0, 0};
+  TORCH_CHECK(d.V >= 1 && d.V <= (1 << 24) && d.F <= (1 << 24), "V must be in 1..2^24 and F at most 2^24");
+  TORCH_CHECK(d.B <= INT32_MAX, "too many meshes");
+  if (planes && planes->numel() > 0) {
+    const Tensor &p = *planes;
+    TORCH_CHECK(p.scalar_type() == at::kFloat && ((p.dim() == 2 && p.size(1) == 4) || (p.dim() == 3 && p.size(0) == d.B && p.size(2) == 4)),
+                "planes must be (K, 4) or (B, K, 4) float32");
+    d.K = p.size(p.dim() - 2);
+    d.bstride = p.dim() == 3 ? d.K * 4 : 0;
+    TORCH_CHECK(d.K <= 16, "at most 16 planes (got ", d.K, ")");
+    TORCH_CHECK(part_mask && part_mask->dim() == 1 && part_mask->size(0) == d.K && part_mask->scalar_type() == at::kInt,
+                "part_mask must be (K,) int32 (the 32 mask bits)");
+    TORCH_CHECK(face_part && face_part->dim() == 1 && face_part->size(0) == d.F && face_part->scalar_type() == at::kByte,
+                "face_part must be (F,) uint8");
+  }
+  return d;
+}
+const void *opt_ptr(const c10::optional<Tensor> &t) { return t && t->defined() && t->numel() ? t->data_ptr() : nullptr; }
+void measure_on_device(const Tensor &verts, const Tensor &faces, const c10::optional<Tensor> &face_part,
+                       const c10::optional<Tensor> &planes, const c10::optional<Tensor> &part_mask, int64_t K) {
+  dev_f32(verts, "verts");
+  dev_typed(faces, at::kInt, "faces");
+  if (K > 0) {
+    dev_f32(*planes, "planes");
+    dev_typed(*part_mask, at::kInt, "part_mask");
+    dev_typed(*face_part, at::kByte, "face_part");
+    same_device(verts, {{"planes", &*planes}, {"part_mask", &*part_mask}, {"face_part", &*face_part}});
+  }
+  same_device(verts, {{"faces", &faces}});
+}
+std::vector<Tensor> measure_outputs(const Tensor &verts, const MeasureDims &d, bool plane_grad) {
+  const auto f = verts.options().dtype(at::kFloat), i = verts.options().dtype(at::kInt);
+  return {at::empty({d.B}, f), at::empty({d.B}, f), at::empty({d.B, 3}, f), at::empty({d.B, 6}, i), at::empty({d.B, d.K}, f),
+          plane_grad ? at::empty({d.B, d.K, 4}, f) : at::empty({0}, f), at::empty({d.B}, i)};
+}
+std::vector<Tensor> mesh_measures(const Tensor &verts, const Tensor &faces, const c10::optional<Tensor> &face_part,
+                                  const c10::optional<Tensor> &planes, const c10::optional<Tensor> &part_mask, bool plane_grad) {
+  const MeasureDims d = measure_check(verts, faces, face_part, planes, part_mask);
+  measure_on_device(verts, faces, face_part, planes, part_mask, d.K);
+  DeviceGuard g(verts.device());
+  std::vector<Tensor> o = measure_outputs(verts, d, plane_grad);
+  if (d.B == 0) return o;
+  ok(smplr_mesh_measures(verts.data_ptr<float>(), d.F ? faces.data_ptr<int32_t>() : nullptr,
+                         d.K ? static_cast<const uint8_t *>(opt_ptr(face_part)) : nullptr,
+                         d.K ? static_cast<const float *>(opt_ptr(planes)) : nullptr, d.bstride,
+                         d.K ? static_cast<const uint32_t *>(opt_ptr(part_mask)) : nullptr, (int)d.B, (int)d.V, (int)d.F, (int)d.K,
+                         o[0].data_ptr<float>(), o[1].data_ptr<float>(), o[2].data_ptr<float>(), o[3].data_ptr<int32_t>(),
+                         fpm(o[4]), fpm(o[5]), o[6].data_ptr<int32_t>(), cur_stream()),
+     "smplr_mesh_measures");
+  return o;
+}
+std::vector<Tensor> mesh_measures_meta(const Tensor &verts, const Tensor &faces, const c10::optional<Tensor> &face_part,
+                                       const c10::optional<Tensor> &planes, const c10::optional<Tensor> &part_mask,
+                                       bool plane_grad) {
+  return measure_outputs(verts, measure_check(verts, faces, face_part, planes, part_mask), plane_grad);
+}
+// The gradient with respect to verts; each cotangent - g_volume (B), g_area (B), g_extent (B, 3), g_girth (B, K) - may be None.
+MeasureDims measure_bwd_check(const Tensor &verts, const Tensor &faces, const Tensor &vf_off, const Tensor &vf_face,
+                              const c10::optional<Tensor> &face_part, const c10::optional<Tensor> &planes,
+                              const c10::optional<Tensor> &part_mask, const Tensor &ext_idx, const Tensor &status,
+                              const c10::optional<Tensor> &g_volume, const c10::optional<Tensor> &g_area,
+                              const c10::optional<Tensor> &g_extent, const c10::optional<Tensor> &g_girth) {
+  const MeasureDims d = measure_check(verts, faces, face_part, planes, part_mask);
+  TORCH_CHECK(vf_off.dim() == 1 && vf_off.size(0) == d.V + 1 && vf_off.scalar_type() == at::kInt, "vf_off must be (V + 1,) int32");
+  TORCH_CHECK(vf_face.dim() == 1 && vf_face.size(0) <= 3 * (1 << 24) && vf_face.scalar_type() == at::kInt,
+              "vf_face must be (nnz,) int32, nnz <= 3 * 2^24");
+  TORCH_CHECK(ext_idx.dim() == 2 && ext_idx.size(0) == d.B && ext_idx.size(1) == 6 && ext_idx.scalar_type() == at::kInt,
+              "ext_idx must be (B, 6) int32");
+  TORCH_CHECK(status.dim() == 1 && status.size(0) == d.B && status.scalar_type() == at::kInt, "status must be (B,) int32");
+  auto shaped = [&](const c10::optional<Tensor> &t, std::vector<int64_t> shape, const char *name) {
+    TORCH_CHECK(!t || (t->scalar_type() == at::kFloat && t->sizes() == at::IntArrayRef(shape)), name, " has the wrong shape or dtype");
+  };
+  shaped(g_volume, {d.B}, "g_volume (B,)");
+  shaped(g_area, {d.B}, "g_area (B,)");
+  shaped(g_extent, {d.B, 3}, "g_extent (B, 3)");
+  shaped(g_girth, {d.B, d.K}, "g_girth (B, K)");
+  return d;
+}
+Tensor mesh_measures_bwd(const Tensor &verts, const Tensor &faces, const Tensor &vf_off, const Tensor &vf_face,
+                         const c10::optional<Tensor> &face_part, const c10::optional<Tensor> &planes,
+                         const c10::optional<Tensor> &part_mask, const Tensor &ext_idx, const Tensor &status,
+                         const c10::optional<Tensor> &g_volume, const c10::optional<Tensor> &g_area,
+                         const c10::optional<Tensor> &g_extent, const c10::optional<Tensor> &g_girth) {
+  const MeasureDims d = measure_bwd_check(verts, faces, vf_off, vf_face, face_part, planes, part_mask, ext_idx, status, g_volume,
+                                          g_area, g_extent, g_girth);
+  measure_on_device(verts, faces, face_part, planes, part_mask, d.K);
+  dev_typed(vf_off, at::kInt, "vf_off"); dev_typed(vf_face, at::kInt, "vf_face");
+  dev_typed(ext_idx, at::kInt, "ext_idx"); dev_typed(status, at::kInt, "status");
+  same_device(verts, {{"vf_off", &vf_off}, {"vf_face", &vf_face}, {"ext_idx", &ext_idx}, {"status", &status}});
+  for (const auto *t : {&g_volume, &g_area, &g_extent, &g_girth}) {
+    if (!*t) continue;
+    dev_f32(**t, "a cotangent");
+    same_device(verts, {{"a cotangent", &**t}});
+  }
+  DeviceGuard g(verts.device());
+  Tensor dverts = f32({d.B, d.V, 3}, verts);
+  if (d.B == 0) return dverts;
+  ok(smplr_mesh_measures_bwd(verts.data_ptr<float>(), d.F ? faces.data_ptr<int32_t>() : nullptr, vf_off.data_ptr<int32_t>(),
+                             vf_face.numel() ? vf_face.data_ptr<int32_t>() : nullptr, (int)vf_face.numel(),
+                             d.K ? static_cast<const uint8_t *>(opt_ptr(face_part)) : nullptr,
+                             d.K ? static_cast<const float *>(opt_ptr(planes)) : nullptr, d.bstride,
+                             d.K ? static_cast<const uint32_t *>(opt_ptr(part_mask)) : nullptr, ext_idx.data_ptr<int32_t>(),
+                             status.data_ptr<int32_t>(), static_cast<const float *>(opt_ptr(g_volume)),
+                             static_cast<const float *>(opt_ptr(g_area)), static_cast<const float *>(opt_ptr(g_extent)),
+                             static_cast<const float *>(opt_ptr(g_girth)), (int)d.B, (int)d.V, (int)d.F, (int)d.K,
+                             dverts.data_ptr<float>(), cur_stream()),
+     "smplr_mesh_measures_bwd");
+  return dverts;
+}
+Tensor mesh_measures_bwd_meta(const Tensor &verts, const Tensor &faces, const Tensor &vf_off, const Tensor &vf_face,
+                              const c10::optional<Tensor> &face_part, const c10::optional<Tensor> &planes,
+                              const c10::optional<Tensor> &part_mask, const Tensor &ext_idx, const Tensor &status,
+                              const c10::optional<Tensor> &g_volume, const c10::optional<Tensor> &g_area,
+                              const c10::optional<Tensor> &g_extent, const c10::optional<Tensor> &g_girth) {
+  const MeasureDims d = measure_bwd_check(verts, faces, vf_off, vf_face, face_part, planes, part_mask, ext_idx, status, g_volume,
+                                          g_area, g_extent, g_girth);
+  return at::empty({d.B, d.V, 3}, verts.options());
+}
+
 int64_t abi_version() { return smplr_abi_version(); }
 #ifndef SMPLR_TORCH_OPS_ID
 #define SMPLR_TORCH_OPS_ID "unknown"
@@ -1042,6 +1169,11 @@ TORCH_LIBRARY(smplraster, m) {
         "Tensor? silh_loss, Tensor col_scale, Tensor(l!)? history, Tensor mean, Tensor factor, Tensor offset, Tensor angle_idx, "
         "Tensor angle_scale, Tensor shape_mean, Tensor weights, float lr=0.001, float beta1=0.9, float beta2=0.999, "
         "float eps=1e-07, float gscale=1.0, float silh_weight=1.0, int mode=0, int patience=0, int num_cam=4) -> ()");
+  m.def("mesh_measures(Tensor verts, Tensor faces, Tensor? face_part=None, Tensor? planes=None, Tensor? part_mask=None, "
+        "bool plane_grad=True) -> Tensor[]");
+  m.def("mesh_measures_bwd(Tensor verts, Tensor faces, Tensor vf_off, Tensor vf_face, Tensor? face_part, Tensor? planes, "
+        "Tensor? part_mask, Tensor ext_idx, Tensor status, Tensor? g_volume, Tensor? g_area, Tensor? g_extent, "
+        "Tensor? g_girth) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch key is named CUDA in torch)
@@ -1068,6 +1200,8 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("fit_step", &fit_step);
   m.impl("prior_energy", &prior_energy);
   m.impl("fit_step_prior", &fit_step_prior);
+  m.impl("mesh_measures", &mesh_measures);
+  m.impl("mesh_measures_bwd", &mesh_measures_bwd);
 }
 
 TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
@@ -1094,4 +1228,6 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("fit_step", &fit_step_meta);
   m.impl("prior_energy", &prior_energy_meta);
   m.impl("fit_step_prior", &fit_step_prior_meta);
+  m.impl("mesh_measures", &mesh_measures_meta);
+  m.impl("mesh_measures_bwd", &mesh_measures_bwd_meta);
 }

@@ -4,12 +4,15 @@ style of `inference.predict_batch`.  With a decoder built with a fused loss (`SM
 the counting runs inside the rasteriser's loss epilogue and the (N, W, W, 32) scores are never written; a decoder without
 one writes them and the confusion kernel counts them.  `evaluate_3d` adds what `evaluate3d.py` leaves out: the distance between the
 predicted and the ground-truth surface and joints in metres, raw and after translation, scale and Procrustes alignment
-(eval3d.py, csrc/eval3d.hip), and the pose-parameter MSE in the same pass."""
+(eval3d.py, csrc/eval3d.hip), and the pose-parameter MSE in the same pass; `evaluate_measurements` compares what a tape
+measure would: volume, surface area, extents and girths of the predicted and the ground-truth body (measure.py,
+csrc/measure.hip), which needs ground-truth parameters but no ground-truth vertices."""
 from __future__ import annotations
 
 import torch
 
 from .eval3d import Eval3D
+from .measure import mesh_measures
 from .metrics import SegConfusion
 
 
@@ -114,3 +117,49 @@ def evaluate_3d(smpl_model, smpl_layer, batches, root_joint=None):
         j = ev_j.result()
         out.update(mpjpe=j["none"], mpjpe_root=j["translation"], mpjpe_pa=j["similarity"], joint_count=j["count"])
     return out
+
+
+@torch.no_grad()
+def evaluate_measurements(smpl_model, smpl_layer, batches, spec, tpose=True):
+    """The loop of `evaluate_3d` with gt = (gt_pose (N, 72), gt_shape (N, 10)), comparing body measurements instead of
+    vertices: prediction and ground truth are decoded by the same `smpl_layer` and measured by `mesh_measures(verts, spec)`
+    (`spec`: a `measure.MeasureSpec` on the layer's topology, with its planes).  tpose=True sets the pose to zero in both, so
+    that fixed planes cut the same places of every body and only shape is compared.
+    -> dict of mean absolute errors: volume (m^3), area (m^2), extent (3) and girth (K) (m), + names (the spec's), count =
+    bodies counted, nonfinite = bodies left out because either mesh or a plane held a NaN or Inf.  Sums are float64 on the
+    device; nothing synchronises before the end."""
+    K = spec.num_planes
+    state = None                                        # 1 + 1 + 3 + K sums, count, nonfinite
+    was_training = smpl_model.training
+    smpl_model.eval()
+    try:
+        for images, gt in batches:
+            smpl = smpl_model(images)
+            dev = smpl.device
+            gt_pose, gt_shape = (torch.as_tensor(t, device=dev) for t in gt)
+            n, nc = int(smpl.shape[0]), smpl_layer.num_cam
+            if gt_pose.dim() != 2 or gt_pose.shape[1] != 72 or gt_pose.shape[0] != n:
+                raise ValueError("gt_pose must be (N, 72) with N = the batch's images")
+            if gt_shape.shape != (n, 10):
+                raise ValueError("gt_shape must be (N, 10) with N = the batch's images")
+            xp = smpl.float().clone()
+            xg = torch.cat([smpl[:, :nc].float(), gt_pose.float(), gt_shape.float()], 1)
+            if tpose:
+                xp[:, nc:nc + 72] = 0
+                xg[:, nc:nc + 72] = 0
+            mp, mg = mesh_measures(smpl_layer(xp), spec), mesh_measures(smpl_layer(xg), spec)
+            ok = (mp["status"] == 0) & (mg["status"] == 0)
+            err = torch.cat([(mp[k] - mg[k]).abs().reshape(n, -1) for k in ("volume", "area", "extent", "girth")], 1)
+            err = torch.where(ok[:, None], err, torch.zeros_like(err)).to(torch.float64).sum(0)
+            n_ok = ok.sum().to(torch.float64)
+            row = torch.cat([err, n_ok[None], (n - n_ok)[None]])
+            state = row if state is None else state + row
+    finally:
+        smpl_model.train(was_training)
+    if state is None:
+        raise ValueError("evaluate_measurements: no batches")
+    st = state.cpu()
+    cnt = float(st[5 + K])
+    mean = [(float(x) / cnt if cnt else float("nan")) for x in st[:5 + K]]
+    return {"volume": mean[0], "area": mean[1], "extent": mean[2:5], "girth": mean[5:5 + K], "names": spec.names,
+            "count": int(st[5 + K]), "nonfinite": int(st[6 + K])}

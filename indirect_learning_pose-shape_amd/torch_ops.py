@@ -74,6 +74,11 @@ SCHEMAS = {
                        "Tensor shape_mean, Tensor weights, float lr=0.001, float beta1=0.90000000000000002, float beta2=0.999, "
                        "float eps=9.9999999999999995e-08, float gscale=1., float silh_weight=1., int mode=0, int patience=0, "
                        "int num_cam=4) -> ()"),
+    "mesh_measures": ("smplraster::mesh_measures(Tensor verts, Tensor faces, Tensor? face_part=None, Tensor? planes=None, "
+                      "Tensor? part_mask=None, bool plane_grad=True) -> Tensor[]"),
+    "mesh_measures_bwd": ("smplraster::mesh_measures_bwd(Tensor verts, Tensor faces, Tensor vf_off, Tensor vf_face, "
+                          "Tensor? face_part, Tensor? planes, Tensor? part_mask, Tensor ext_idx, Tensor status, "
+                          "Tensor? g_volume, Tensor? g_area, Tensor? g_extent, Tensor? g_girth) -> Tensor"),
 }
 
 _ns = None
