@@ -13,24 +13,15 @@
 // against the TRANSPOSED constant blendT (N3 x 224) so that no operand of the big matrix needs a
 // transpose; the 4 waves split the slice, are summed in LDS in a fixed order, and the per-slice
 // partials are summed by a second kernel in slice order (deterministic, no atomics).
-#include "common.h"
+#include "blend_device.h"
 
 namespace smplr {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int KP = SMPLR_KPAD;  // 220
 constexpr int FW_BM = 32;
-constexpr int FW_NT = 3;      // column tiles (accumulators) per wave: B is loaded NT columns per lane
-constexpr int FW_BN = 32 * FW_NT;
+constexpr int FW_NT = BL_CPL; // column tiles (accumulators) per wave: B is loaded NT columns per lane
+constexpr int FW_BN = BL_BN;
 constexpr int FW_NB = 5;      // k-steps (of 2 rows) per register batch: 22 batches x 5 x 2 = 220
 constexpr int FW_DEPTH = 6;   // batches in flight ahead of the one being multiplied (60 loads <= 63)
-
-template <int N> struct VecN;
-template <> struct VecN<1> { typedef float type; };
-template <> struct VecN<2> { typedef float type __attribute__((ext_vector_type(2), aligned(4))); };
-template <> struct VecN<3> { typedef float type __attribute__((ext_vector_type(3), aligned(4))); };
-template <> struct VecN<4> { typedef float type __attribute__((ext_vector_type(4), aligned(4))); };
 
 // Forward: grid (column tiles of 96, groups of 128 meshes); workgroup = 4 waves = the 4 mesh tiles
 // of ONE column tile, each wave three 32x32 accumulators.  Both operands are read straight from
@@ -56,7 +47,7 @@ __global__ __launch_bounds__(256) void blend_fwd_kernel(const float *__restrict_
   if (m0 >= B) return;                                   // this wave's mesh tile is empty
   const int i = lane & 31, h = lane >> 5;
   const int c = blockIdx.x * FW_BN + FW_NT * i;
-  const int cc = c + FW_NT <= N3 ? c : N3 - FW_NT;       // clamped; discarded in the epilogue
+  const int cc = c + FW_NT <= N3 ? c : N3 - FW_NT;       // clamped to the last whole load (see `sh` below)
   const float *ap = coef + (size_t)h * ldc + m0 + i;     // m0 + i < ldc (padded columns are never stored)
   const float *bp = blend + (size_t)h * N3 + cc;
   const size_t arow = (size_t)ldc, brow = (size_t)N3;
@@ -94,27 +85,16 @@ __global__ __launch_bounds__(256) void blend_fwd_kernel(const float *__restrict_
   }
 #undef SMPLR_LOAD_BATCH
 
-  float base[FW_NT];
+  // The lane that straddles the end of the matrix (N3 % 3 != 0 only: never for 3 V columns) loaded the columns
+  // cc = N3 - 3 .. N3 - 1, so its column c + t sits in accumulator t + (c - cc); every other lane has cc == c.
+  const int sh = c - cc;
+  fwd_tile_out<FW_NT>(out, vt, B, N3, m0, c, h, [&](int t, int r) {
+    float v = acc[t][r];
+    if (c + FW_NT <= N3) return v;                       // (the write-out's own test: its vector store sees no select)
 #pragma unroll
-  for (int t = 0; t < FW_NT; ++t) base[t] = vt[min(c + t, N3 - 1)];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-    const int m = m0 + row;
-    if (m < B) {
-      float *o = out + (size_t)m * N3 + c;
-      if (c + FW_NT <= N3) {
-        bvec v;
-#pragma unroll
-        for (int t = 0; t < FW_NT; ++t) v[t] = acc[t][r] + base[t];
-        *reinterpret_cast<bvec *>(o) = v;
-      } else {
-#pragma unroll
-        for (int t = 0; t < FW_NT; ++t)
-          if (c + t < N3) o[t] = acc[t][r] + base[t];
-      }
-    }
-  }
+    for (int s = 1; s < FW_NT; ++s) v = (sh == s && t + s < FW_NT) ? acc[min(t + s, FW_NT - 1)][r] : v;
+    return v;
+  });
 }
 
 // ---------------------------------------------------------------- backward (split-K)
@@ -128,24 +108,18 @@ __global__ __launch_bounds__(256) void blend_fwd_kernel(const float *__restrict_
 // of matrix work) run ahead of the one being multiplied.  The 4 waves of a block split the block's
 // column slice and are summed in LDS in a fixed order; per-slice partials are summed in slice
 // order by pose_bwd (fused path) or blend_bwd_reduce_kernel: deterministic, no atomics.
-constexpr int BW_NT = 7;             // 7 x 32 = 224 >= 220 outputs
-constexpr int BW_NO = 224;           // blendT row stride and partial row stride
+constexpr int BW_NT = BL_NT;         // 7 x 32 = 224 >= 220 outputs
+constexpr int BW_NO = BL_NO;         // blendT row stride and partial row stride
 constexpr int BW_G = 8;              // columns per group
 constexpr int BW_DEPTH = 5;          // groups in flight ahead of the one being multiplied
-
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x3u __attribute__((ext_vector_type(3), aligned(4)));
 
 __global__ __launch_bounds__(256) void blend_bwd_kernel(const float *__restrict__ dvp,
                                                         const float *__restrict__ blendT, int B, int N3,
                                                         int cols_per_block, int nslices, int nmt,
                                                         float *__restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) float sR[];   // 4 x [32][224] floats = 114,688 B: one tile per wave
-  // XCD-aware map: the nmt mesh tiles of one column slice (same blendT rows) share an XCD's L2.
-  const int bid = blockIdx.x;
-  const int group = bid / (8 * nmt), within = bid % (8 * nmt);
-  const int slice = group * 8 + (within & 7), mt = within >> 3;
-  if (slice >= nslices) return;
+  int slice, mt;
+  if (!splitk_block(blockIdx.x, nmt, nslices, &slice, &mt)) return;
   const int m0 = mt * 32;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int i = lane & 31, h = lane >> 5;
@@ -228,10 +202,7 @@ __global__ __launch_bounds__(256) void blend_bwd_kernel(const float *__restrict_
 #pragma unroll
   for (int t = 0; t < BW_NT; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-      mine[row * BW_NO + 7 * i + t] = acc[t][r];
-    }
+    for (int r = 0; r < 16; ++r) mine[acc_row(r, h) * BW_NO + 7 * i + t] = acc[t][r];
   __syncthreads();
   float *dst = part + ((size_t)slice * nmt + mt) * (32 * BW_NO);
   for (int e = tid * 4; e < 32 * BW_NO; e += 256 * 4) {
@@ -263,28 +234,24 @@ __global__ __launch_bounds__(256) void blend_bwd_reduce_kernel(const float *__re
   dcoef[e] = acc;
 }
 
-static void bwd_geometry(int B, int N3, int *nslices, int *cols_per_block) {
-  const int nmt = (B + 31) / 32;
-  int target = (256 + nmt - 1) / nmt;          // ~one block per CU
-  if (target < 8) target = 8;
-  int cpb = (N3 + target - 1) / target;
-  cpb = (cpb + 4 * BW_G - 1) / (4 * BW_G) * (4 * BW_G);   // 4 waves x groups of 8 columns
-  *cols_per_block = cpb;
-  *nslices = (N3 + cpb - 1) / cpb;
-}
-
-BlendBwdGeom blend_bwd_geom(int B, int N3) {
-  BlendBwdGeom g;
+struct BlendGeom : SplitKGeom { int cols_per_block; };
+static BlendGeom blend_geom(int B, int N3) {
+  BlendGeom g;
   g.nmt = (B + 31) / 32;
-  bwd_geometry(B, N3, &g.nslices, &g.cols_per_block);
+  int target = (256 + g.nmt - 1) / g.nmt;      // ~one block per CU
+  if (target < 8) target = 8;
+  const int cpb = (N3 + target - 1) / target;
+  g.cols_per_block = (cpb + 4 * BW_G - 1) / (4 * BW_G) * (4 * BW_G);   // 4 waves x groups of 8 columns
+  g.nslices = (N3 + g.cols_per_block - 1) / g.cols_per_block;
   g.part_floats = (size_t)g.nslices * g.nmt * 32 * BW_NO;
   return g;
 }
+SplitKGeom blend_bwd_geom(int B, int N3) { return blend_geom(B, N3); }
 
 int launch_blend_bwd_partials(const float *dv_posed, const float *blend_t, int B, int N3, float *part,
                               hipStream_t st) {
-  const BlendBwdGeom g = blend_bwd_geom(B, N3);
-  const int grid = ((g.nslices + 7) / 8) * 8 * g.nmt;
+  const BlendGeom g = blend_geom(B, N3);
+  const int grid = splitk_grid(g.nslices, g.nmt);
   const size_t lds = (size_t)4 * 32 * BW_NO * sizeof(float);
   static LdsAttrMemo memo = {};                       // once per (kernel, device): common.h
   {
@@ -324,9 +291,7 @@ int smplr_blend_fwd(const float *coef, const float *blend, const float *v_templa
 size_t smplr_blend_bwd_workspace(int B, int N3) {
   using namespace smplr;
   if (B <= 0 || N3 <= 0) return 0;
-  int ns, cpb;
-  bwd_geometry(B, N3, &ns, &cpb);
-  return (size_t)ns * ((B + 31) / 32) * 32 * BW_NO * sizeof(float);
+  return blend_bwd_geom(B, N3).part_floats * sizeof(float);
 }
 
 int smplr_blend_bwd(const float *dv_posed, const float *blend_t, int B, int N3, float *dcoef,
@@ -335,12 +300,12 @@ int smplr_blend_bwd(const float *dv_posed, const float *blend_t, int B, int N3, 
   SMPLR_REQUIRE(B >= 0 && N3 > 0, "smplr_blend_bwd: bad sizes B=%d N3=%d", B, N3);
   if (B == 0) return 0;
   SMPLR_REQUIRE(dv_posed && blend_t && dcoef && workspace, "smplr_blend_bwd: null pointer");
-  const BlendBwdGeom g = blend_bwd_geom(B, N3);
-  const int ns = g.nslices, nmt = g.nmt;
+  const SplitKGeom g = blend_bwd_geom(B, N3);
   int rc = launch_blend_bwd_partials(dv_posed, blend_t, B, N3, reinterpret_cast<float *>(workspace),
                                      as_stream(stream));
   if (rc) return rc;
-  return launch_blend_bwd_reduce(reinterpret_cast<const float *>(workspace), B, ns, nmt, dcoef, as_stream(stream));
+  return launch_blend_bwd_reduce(reinterpret_cast<const float *>(workspace), B, g.nslices, g.nmt, dcoef,
+                                 as_stream(stream));
 }
 
 }  // extern "C"

@@ -26,80 +26,42 @@
 // operands: the forward's coef arrives already split, as A-fragments written by pose_fwd (coef3:
 // once per mesh instead of once per column tile); the backward's dv_posed is fp32 in memory and
 // split in registers (v_cvt_pk_bf16_f32 + exact fp32 residuals).
-//   forward operand  [96-col tile][k-tile 14][t 3][split 3][lane 64][8 bf16]:
-//       element j of lane (i, h) = split_s(blend[16 kt + 8h + j][96 ct + 3i + t])
-//   backward operand [k-tile ceil(N3/16)][out tile 7][split 3][lane 64][8 bf16]:
-//       element j of lane (i, h) = split_s(blend[32u + i][16 kt + 8h + j])
-// (zeros beyond row 219 / column N3 - 1).
-#include "common.h"
+// The three fragment layouts (coef3, forward and backward constant), their strides and the shared device pieces
+// (fragment I/O, the k-tile multiply, the tile write-out, the split-K block map): blend_device.h.
 #include "pose_device.h"
 
 namespace smplr {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x3u __attribute__((ext_vector_type(3), aligned(4)));
-
-constexpr int KP = SMPLR_KPAD;       // 220
-constexpr int NKT = 14;              // forward k-tiles of 16 (224 >= 220)
-constexpr int F3_BN = 96;            // forward column tile (3 MFMA tiles; lane i owns columns 3i..3i+2)
-constexpr int B3_NO = 224;           // backward outputs (7 tiles) = partial row stride
-
-#define SMPLR_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-// the six partial products of one (A fragment, B fragment triple); smallest first into `lo`
-#define SMPLR_MFMA_X3(A, bh, bm, bl, hi, lo) \
-  lo = SMPLR_MFMA16(A.l, bh, lo);            \
-  lo = SMPLR_MFMA16(A.h, bl, lo);            \
-  lo = SMPLR_MFMA16(A.m, bm, lo);            \
-  lo = SMPLR_MFMA16(A.m, bh, lo);            \
-  lo = SMPLR_MFMA16(A.h, bm, lo);            \
-  hi = SMPLR_MFMA16(A.h, bh, hi);
-
 // ------------------------------------------------------------------------------------------------
 // one-off packing of the constant (not on the hot path)
 __global__ __launch_bounds__(256) void blend3_pack_fwd_kernel(const float *__restrict__ blend, int N3, int ntile,
-                                                              uint4 *__restrict__ pk) {
+                                                              u32x4 *__restrict__ pk) {
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;           // (ct, kt, t, lane)
-  if (e >= (size_t)ntile * NKT * 3 * 64) return;
-  const int lane = e & 63, t = (e >> 6) % 3, kt = (e / 192) % NKT, ct = e / (192 * NKT);
+  if (e >= (size_t)ntile * NKT * BL_CPL * 64) return;
+  const int lane = e & 63, t = (e >> 6) % BL_CPL, kt = (e / (BL_CPL * 64)) % NKT, ct = e / (BL_CPL * 64 * NKT);
   const int i = lane & 31, h = lane >> 5;
-  const int col = ct * F3_BN + 3 * i + t;
-  float x[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
+  const int col = ct * BL_BN + BL_CPL * i + t;
+  pack_frag3([&](int j) {
     const int k = kt * 16 + 8 * h + j;
-    x[j] = (k < KP && col < N3) ? blend[(size_t)k * N3 + col] : 0.0f;
-  }
-  const Frag3 f = split8(x);
-  uint4 *o = pk + ((size_t)(ct * NKT + kt) * 9 + t * 3) * 64 + lane;
-  o[0] = __builtin_bit_cast(uint4, f.h);
-  o[64] = __builtin_bit_cast(uint4, f.m);
-  o[128] = __builtin_bit_cast(uint4, f.l);
+    return (k < KP && col < N3) ? blend[(size_t)k * N3 + col] : 0.0f;
+  }, [&] { return pk + (size_t)(ct * NKT + kt) * PKF_KT + t * BL_SPLITS * 64 + lane; });
 }
 
 __global__ __launch_bounds__(256) void blend3_pack_bwd_kernel(const float *__restrict__ blend, int N3, int nkt,
-                                                              uint4 *__restrict__ pk) {
+                                                              u32x4 *__restrict__ pk) {
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;           // (kt, u, lane)
-  if (e >= (size_t)nkt * 7 * 64) return;
-  const int lane = e & 63, u = (e >> 6) % 7, kt = e / (64 * 7);
+  if (e >= (size_t)nkt * BL_NT * 64) return;
+  const int lane = e & 63, u = (e >> 6) % BL_NT, kt = e / (64 * BL_NT);
   const int i = lane & 31, h = lane >> 5;
   const int o_ = 32 * u + i;
-  float x[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
+  pack_frag3([&](int j) {
     const int c = kt * 16 + 8 * h + j;
-    x[j] = (o_ < KP && c < N3) ? blend[(size_t)o_ * N3 + c] : 0.0f;
-  }
-  const Frag3 f = split8(x);
-  uint4 *o = pk + ((size_t)(kt * 7 + u) * 3) * 64 + lane;
-  o[0] = __builtin_bit_cast(uint4, f.h);
-  o[64] = __builtin_bit_cast(uint4, f.m);
-  o[128] = __builtin_bit_cast(uint4, f.l);
+    return (o_ < KP && c < N3) ? blend[(size_t)o_ * N3 + c] : 0.0f;
+  }, [&] { return pk + (size_t)kt * PKB_KT + u * PKB_T + lane; });
 }
 
 // ------------------------------------------------------------------------------------------------
 // coef (220, ld) k-major fp32 -> coef3, the A-fragment layout smplr_pose_fwd writes directly
-// ([mesh tile][k-tile 14][split 3][lane 64] x 16 B; lane (i, h) = mesh 32 mt + i, k = 16 kt + 8h + j).
 __global__ __launch_bounds__(256) void coef3_pack_kernel(const float *__restrict__ coef, int B, int ldc,
                                                          u32x4 *__restrict__ coef3) {
   const int e = blockIdx.x * 256 + threadIdx.x;                      // (mt, kt, lane)
@@ -107,17 +69,10 @@ __global__ __launch_bounds__(256) void coef3_pack_kernel(const float *__restrict
   if (e >= nmt * NKT * 64) return;
   const int lane = e & 63, kt = (e >> 6) % NKT, mt = e / (64 * NKT);
   const int i = lane & 31, h = lane >> 5, m = mt * 32 + i;
-  float x[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
+  pack_frag3([&](int j) {
     const int k = kt * 16 + 8 * h + j;
-    x[j] = (k < KP && m < B) ? coef[(size_t)k * ldc + m] : 0.0f;
-  }
-  const Frag3 f = split8(x);
-  u32x4 *o = coef3 + ((size_t)(mt * NKT + kt) * 3) * 64 + lane;
-  o[0] = __builtin_bit_cast(u32x4, f.h);
-  o[64] = __builtin_bit_cast(u32x4, f.m);
-  o[128] = __builtin_bit_cast(u32x4, f.l);
+    return (k < KP && m < B) ? coef[(size_t)k * ldc + m] : 0.0f;
+  }, [&] { return coef3 + (size_t)(mt * NKT + kt) * A3_KT + lane; });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -146,21 +101,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int m0 = (blockIdx.y * 4 + wave) * 32;
   if (m0 >= B) return;                                   // this wave's mesh tile is empty
   const int i = lane & 31, h = lane >> 5;
-  const int c = blockIdx.x * F3_BN + 3 * i;
-  const u32x4 *ap = coef3 + (size_t)(m0 >> 5) * (NKT * 3 * 64) + lane;
-  const u32x4 *bp = pk + (size_t)blockIdx.x * (NKT * 9 * 64) + lane;
+  const int c = blockIdx.x * BL_BN + BL_CPL * i;
+  const u32x4 *ap = coef3 + (size_t)(m0 >> 5) * A3_MT + lane;
+  const u32x4 *bp = pk + (size_t)blockIdx.x * PKF_CT + lane;
 
-  f32x16 hi[3], lo[3];
-#pragma unroll
-  for (int t = 0; t < 3; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { hi[t][r] = 0.0f; lo[t][r] = 0.0f; }
+  f32x16 hi[BL_CPL], lo[BL_CPL];
+  clear_acc3(hi, lo);
 
-  u32x4 a[F3_DEPTH + 1][3], b[F3_DEPTH + 1][9];
-#define SMPLR_LOAD_KT(slot, kt)                                                         \
-  {                                                                                     \
-    _Pragma("unroll") for (int s_ = 0; s_ < 3; ++s_) a[slot][s_] = ap[((kt) * 3 + s_) * 64]; \
-    _Pragma("unroll") for (int j_ = 0; j_ < 9; ++j_) b[slot][j_] = bp[((kt) * 9 + j_) * 64]; \
+  u32x4 a[F3_DEPTH + 1][BL_SPLITS], b[F3_DEPTH + 1][BL_CPL * BL_SPLITS];
+#define SMPLR_LOAD_KT(slot, kt)                                                                              \
+  {                                                                                                          \
+    _Pragma("unroll") for (int s_ = 0; s_ < BL_SPLITS; ++s_) a[slot][s_] = ap[((kt) * BL_SPLITS + s_) * 64]; \
+    load_pkf(b[slot], bp, kt);                                                                               \
   }
 #pragma unroll
   for (int kt = 0; kt < F3_DEPTH; ++kt) { SMPLR_LOAD_KT(kt % (F3_DEPTH + 1), kt) }
@@ -174,38 +126,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     A.h = __builtin_bit_cast(bf16x8, a[s][0]);
     A.m = __builtin_bit_cast(bf16x8, a[s][1]);
     A.l = __builtin_bit_cast(bf16x8, a[s][2]);
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      const bf16x8 bh = __builtin_bit_cast(bf16x8, b[s][t * 3 + 0]);
-      const bf16x8 bm = __builtin_bit_cast(bf16x8, b[s][t * 3 + 1]);
-      const bf16x8 bl = __builtin_bit_cast(bf16x8, b[s][t * 3 + 2]);
-      SMPLR_MFMA_X3(A, bh, bm, bl, hi[t], lo[t])
-    }
+    mul_frag3<BL_CPL>(A, b[s], hi, lo);
     __builtin_amdgcn_sched_barrier(0);
   }
 #undef SMPLR_LOAD_KT
 
-  float base[3];
-#pragma unroll
-  for (int t = 0; t < 3; ++t) base[t] = vt[min(c + t, N3 - 1)];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-    const int m = m0 + row;
-    if (m < B) {
-      float *o = out + (size_t)m * N3 + c;
-      if (c + 3 <= N3) {
-        f32x3u v;
-#pragma unroll
-        for (int t = 0; t < 3; ++t) v[t] = (hi[t][r] + lo[t][r]) + base[t];
-        *reinterpret_cast<f32x3u *>(o) = v;
-      } else {
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-          if (c + t < N3) o[t] = (hi[t][r] + lo[t][r]) + base[t];
-      }
-    }
-  }
+  fwd_tile_out<BL_CPL>(out, vt, B, N3, m0, c, h, [&](int t, int r) { return hi[t][r] + lo[t][r]; });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -259,14 +185,12 @@ __global__ __launch_bounds__(512) void pose_blend3_fwd_kernel(
   // ---- phase 1, all eight waves: the coefficient rows.  Lane (i, h) takes joint 2 s + 1 + h of mesh i in step s; the
   // multiplier wave w does steps 0..5 of its tile (after requesting its first fragments of the constant), its
   // partner w + 4 steps 6..11 and the betas / padding (rows beyond B repeat mesh B - 1)
-  const int c = ct * F3_BN + 3 * i;
-  const u32x4 *bp = pk + (size_t)ct * (NKT * 9 * 64) + lane;
-  u32x4 b[F3F_DEPTH + 1][9];
-#define SMPLR_LOAD_B(slot, kt) \
-  { _Pragma("unroll") for (int j_ = 0; j_ < 9; ++j_) b[slot][j_] = bp[((kt) * 9 + j_) * 64]; }
+  const int c = ct * BL_BN + BL_CPL * i;
+  const u32x4 *bp = pk + (size_t)ct * PKF_CT + lane;
+  u32x4 b[F3F_DEPTH + 1][BL_CPL * BL_SPLITS];
   if (wave < 4) {
 #pragma unroll
-    for (int kt = 0; kt < F3F_DEPTH; ++kt) { SMPLR_LOAD_B(kt % (F3F_DEPTH + 1), kt) }
+    for (int kt = 0; kt < F3F_DEPTH; ++kt) load_pkf(b[kt % (F3F_DEPTH + 1)], bp, kt);
   }
   __builtin_amdgcn_sched_barrier(0);
   {
@@ -313,11 +237,8 @@ __global__ __launch_bounds__(512) void pose_blend3_fwd_kernel(
   __syncthreads();
   if (wave >= 4) return;
   // ---- phase 2, waves 0..3: multiply
-  f32x16 hi[3], lo[3];
-#pragma unroll
-  for (int t = 0; t < 3; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { hi[t][r] = 0.0f; lo[t][r] = 0.0f; }
+  f32x16 hi[BL_CPL], lo[BL_CPL];
+  clear_acc3(hi, lo);
   const float *arow = sc + i * FC_LD + 8 * h;
   // the eight coefficients of k-tile kt for this lane
 #define SMPLR_WAIT_READ(kt, x0_, x1_)                                                                       \
@@ -329,45 +250,18 @@ __global__ __launch_bounds__(512) void pose_blend3_fwd_kernel(
   SMPLR_WAIT_READ(0, x0, x1)
 #pragma unroll
   for (int kt = 0; kt < NKT; ++kt) {
-    if (kt + F3F_DEPTH < NKT) { SMPLR_LOAD_B((kt + F3F_DEPTH) % (F3F_DEPTH + 1), kt + F3F_DEPTH) }
+    if (kt + F3F_DEPTH < NKT) load_pkf(b[(kt + F3F_DEPTH) % (F3F_DEPTH + 1)], bp, kt + F3F_DEPTH);
     __builtin_amdgcn_sched_barrier(0);
     const int s = kt % (F3F_DEPTH + 1);
     const float xk[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
     const Frag3 A = split8(xk);
     if (kt + 1 < NKT) SMPLR_WAIT_READ(kt + 1, x0, x1)        // the next tile's values arrive under this tile's MFMAs
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      const bf16x8 bh = __builtin_bit_cast(bf16x8, b[s][t * 3 + 0]);
-      const bf16x8 bm = __builtin_bit_cast(bf16x8, b[s][t * 3 + 1]);
-      const bf16x8 bl = __builtin_bit_cast(bf16x8, b[s][t * 3 + 2]);
-      SMPLR_MFMA_X3(A, bh, bm, bl, hi[t], lo[t])
-    }
+    mul_frag3<BL_CPL>(A, b[s], hi, lo);
     __builtin_amdgcn_sched_barrier(0);
   }
 #undef SMPLR_WAIT_READ
-#undef SMPLR_LOAD_B
 
-  float base[3];
-#pragma unroll
-  for (int t = 0; t < 3; ++t) base[t] = vt[min(c + t, N3 - 1)];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-    const int m = m0 + row;
-    if (m < B) {
-      float *o = out + (size_t)m * N3 + c;
-      if (c + 3 <= N3) {
-        f32x3u v;
-#pragma unroll
-        for (int t = 0; t < 3; ++t) v[t] = (hi[t][r] + lo[t][r]) + base[t];
-        *reinterpret_cast<f32x3u *>(o) = v;
-      } else {
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-          if (c + t < N3) o[t] = (hi[t][r] + lo[t][r]) + base[t];
-      }
-    }
-  }
+  fwd_tile_out<BL_CPL>(out, vt, B, N3, m0, c, h, [&](int t, int r) { return hi[t][r] + lo[t][r]; });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -394,16 +288,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
   // MT mesh tiles of 32 per workgroup (nmt counts the workgroups' tile GROUPS): every fragment of the constant a wave
   // requests meets MT fragments of dv_posed - from 512 meshes on the kernel is bound by what L2 delivers of the
   // constant (each XCD streams its slices' 3.4 MB once per tile group), and two tiles per group halve that.
-  // XCD-aware map: the nmt tile groups of one column slice (same constant rows) share an XCD's L2.
-  const int bid = blockIdx.x;
-  const int group = bid / (8 * nmt), within = bid % (8 * nmt);
-  const int slice = group * 8 + (within & 7), mt = within >> 3;
-  if (slice >= nslices) return;
+  int slice, mt;
+  if (!splitk_block(blockIdx.x, nmt, nslices, &slice, &mt)) return;
   const int m0 = mt * 32 * MT;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i = lane & 31, h = lane >> 5;
-  const int u0 = wave, u1 = wave + 4 < 7 ? wave + 4 : 6;      // wave 3: second tile is a discarded copy of tile 6
+  const int u0 = wave, u1 = wave + 4 < BL_NT ? wave + 4 : BL_NT - 1;      // wave 3: second tile is a discarded copy of tile 6
   const int nkt = (N3 + 15) / 16, nfull = N3 / 16;
   const int kt_beg = slice * ktps;
   const int kt_end = min(kt_beg + ktps, nkt);
@@ -412,11 +303,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 
   f32x16 hi[MT][2], lo[MT][2];
 #pragma unroll
-  for (int j = 0; j < MT; ++j)
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { hi[j][t][r] = 0.0f; lo[j][t][r] = 0.0f; }
+  for (int j = 0; j < MT; ++j) clear_acc3(hi[j], lo[j]);
 
   const float *arow[MT];
   int mr[MT];
@@ -425,7 +312,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     mr[j] = min(m0 + 32 * j + i, B - 1);                      // rows beyond B: clamped, never stored
     arow[j] = dvp + (size_t)mr[j] * N3 + 8 * h;
   }
-  const u32x4 *b0 = pk + (size_t)u0 * 192 + lane, *b1 = pk + (size_t)u1 * 192 + lane;
+  const u32x4 *b0 = pk + (size_t)u0 * PKB_T + lane, *b1 = pk + (size_t)u1 * PKB_T + lane;
 
   f32x4u ra0[B3_DEPTH + 1][MT], ra1[B3_DEPTH + 1][MT];
   u32x4 rb[B3_DEPTH + 1][6];
@@ -438,8 +325,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
       ra1[slot][j_] = *reinterpret_cast<const f32x4u *>(arow[j_] + (size_t)kt_ * 16 + 4); \
     }                                                                             \
     _Pragma("unroll") for (int s_ = 0; s_ < 3; ++s_) {                            \
-      rb[slot][s_] = b0[((size_t)kt_ * 21 + s_) * 64];                            \
-      rb[slot][3 + s_] = b1[((size_t)kt_ * 21 + s_) * 64];                        \
+      rb[slot][s_] = b0[(size_t)kt_ * PKB_KT + s_ * 64];                          \
+      rb[slot][3 + s_] = b1[(size_t)kt_ * PKB_KT + s_ * 64];                      \
     }                                                                             \
   }
 #define SMPLR_MMA_KT(slot)                                                         \
@@ -448,12 +335,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
       const float x_[8] = {ra0[slot][j_][0], ra0[slot][j_][1], ra0[slot][j_][2], ra0[slot][j_][3],  \
                            ra1[slot][j_][0], ra1[slot][j_][1], ra1[slot][j_][2], ra1[slot][j_][3]}; \
       const Frag3 A = split8(x_);                                                 \
-      _Pragma("unroll") for (int t_ = 0; t_ < 2; ++t_) {                          \
-        const bf16x8 bh = __builtin_bit_cast(bf16x8, rb[slot][3 * t_ + 0]);       \
-        const bf16x8 bm = __builtin_bit_cast(bf16x8, rb[slot][3 * t_ + 1]);       \
-        const bf16x8 bl = __builtin_bit_cast(bf16x8, rb[slot][3 * t_ + 2]);       \
-        SMPLR_MFMA_X3(A, bh, bm, bl, hi[j_][t_], lo[j_][t_])                      \
-      }                                                                           \
+      mul_frag3<2>(A, rb[slot], hi[j_], lo[j_]);                                  \
     }                                                                             \
   }
 #pragma unroll
@@ -484,41 +366,37 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         x[q] = dvp[(size_t)mr[j] * N3 + min(cc, N3 - 1)];
       }
       const Frag3 A = split8(x);
+      u32x4 bt[6];                             // (addressed from pk, not from b0 / b1: those would stay live over the loop)
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const u32x4 *bq = pk + ((size_t)kt * 21 + (t == 0 ? u0 : u1) * 3) * 64 + lane;
-        const bf16x8 bh = __builtin_bit_cast(bf16x8, bq[0]);
-        const bf16x8 bm = __builtin_bit_cast(bf16x8, bq[64]);
-        const bf16x8 bl = __builtin_bit_cast(bf16x8, bq[128]);
-        SMPLR_MFMA_X3(A, bh, bm, bl, hi[j][t], lo[j][t])
-      }
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int s = 0; s < 3; ++s) bt[3 * t + s] = pk[(size_t)kt * PKB_KT + (t == 0 ? u0 : u1) * PKB_T + s * 64 + lane];
+      mul_frag3<2>(A, bt, hi[j], lo[j]);
     }
   }
-  // accumulator register r of lane (i, h) = mesh row (r&3) + 8(r>>2) + 4h, output 32u + i; the partials keep their
-  // layout (slice, mesh tile of 32, 32, B3_NO) whatever MT
+  // accumulator register r of lane (i, h) = mesh row acc_row(r, h), output 32u + i; the partials keep their
+  // layout (slice, mesh tile of 32, 32, BL_NO) whatever MT
   const int ntile = (B + 31) / 32;
 #pragma unroll
   for (int j = 0; j < MT; ++j) {
     const int tile = mt * MT + j;
     if (tile >= ntile) break;                  // block-uniform: the last group of an odd tile count
-    float *dst = part + ((size_t)slice * ntile + tile) * (32 * B3_NO);
+    float *dst = part + ((size_t)slice * ntile + tile) * (32 * BL_NO);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      if (t == 1 && wave + 4 >= 7) break;      // wave-uniform
+      if (t == 1 && wave + 4 >= BL_NT) break;  // wave-uniform
       const int u = t == 0 ? u0 : u1;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-        dst[row * B3_NO + 32 * u + i] = hi[j][t][r] + lo[j][t][r];
-      }
+      for (int r = 0; r < 16; ++r) dst[acc_row(r, h) * BL_NO + 32 * u + i] = hi[j][t][r] + lo[j][t][r];
     }
   }
 }
 
 // k-tiles per slice: about one workgroup per CU, and at most 60 slices so that pose_bwd sums a
 // mesh's partials with one batch of loads.
-Blend3BwdGeom blend3_bwd_geom(int B, int N3) {
-  Blend3BwdGeom g;
+struct Blend3Geom : SplitKGeom { int ktps; };
+static Blend3Geom blend3_geom(int B, int N3) {
+  Blend3Geom g;
   g.nmt = (B + 31) / 32;
   const int nkt = (N3 + 15) / 16;
   const int ngrp = B >= 512 ? (g.nmt + 1) / 2 : g.nmt;     // workgroups per slice (two mesh tiles each from 512 meshes on)
@@ -527,21 +405,20 @@ Blend3BwdGeom blend3_bwd_geom(int B, int N3) {
   if (target > 60) target = 60;
   g.ktps = (nkt + target - 1) / target;
   g.nslices = (nkt + g.ktps - 1) / g.ktps;
-  g.part_floats = (size_t)g.nslices * g.nmt * 32 * B3_NO;
+  g.part_floats = (size_t)g.nslices * g.nmt * 32 * BL_NO;
   return g;
 }
+SplitKGeom blend3_bwd_geom(int B, int N3) { return blend3_geom(B, N3); }
 
 int launch_blend3_bwd_partials(const float *dv_posed, const void *pk_bwd, int B, int N3, float *part,
                                hipStream_t st) {
-  const Blend3BwdGeom g = blend3_bwd_geom(B, N3);
+  const Blend3Geom g = blend3_geom(B, N3);
   if (B < 512) {
-    const int grid = ((g.nslices + 7) / 8) * 8 * g.nmt;
-    hipLaunchKernelGGL((blend3_bwd_kernel<2, 2, 1>), dim3(grid), dim3(256), 0, st, dv_posed,
+    hipLaunchKernelGGL((blend3_bwd_kernel<2, 2, 1>), dim3(splitk_grid(g.nslices, g.nmt)), dim3(256), 0, st, dv_posed,
                        reinterpret_cast<const u32x4 *>(pk_bwd), B, N3, g.ktps, g.nslices, g.nmt, part);
   } else {
     const int ngrp = (g.nmt + 1) / 2;          // two mesh tiles per workgroup
-    const int grid = ((g.nslices + 7) / 8) * 8 * ngrp;
-    hipLaunchKernelGGL((blend3_bwd_kernel<B3_BIG_DEPTH, 1, 2>), dim3(grid), dim3(256), 0, st, dv_posed,
+    hipLaunchKernelGGL((blend3_bwd_kernel<B3_BIG_DEPTH, 1, 2>), dim3(splitk_grid(g.nslices, ngrp)), dim3(256), 0, st, dv_posed,
                        reinterpret_cast<const u32x4 *>(pk_bwd), B, N3, g.ktps, g.nslices, ngrp, part);
   }
   SMPLR_LAUNCH_CHECK("blend3_bwd_kernel");
@@ -555,12 +432,12 @@ extern "C" {
 size_t smplr_blend3_fwd_bytes(int N3) {
   using namespace smplr;
   if (N3 <= 0) return 0;
-  return (size_t)((N3 + F3_BN - 1) / F3_BN) * NKT * 9 * 64 * sizeof(uint4);
+  return (size_t)((N3 + BL_BN - 1) / BL_BN) * PKF_CT * sizeof(u32x4);
 }
 
 size_t smplr_blend3_bwd_bytes(int N3) {
   if (N3 <= 0) return 0;
-  return (size_t)((N3 + 15) / 16) * 7 * 3 * 64 * sizeof(uint4);
+  return (size_t)((N3 + 15) / 16) * smplr::PKB_KT * sizeof(smplr::u32x4);
 }
 
 int smplr_blend3_pack(const float *blend, int N3, void *pk_fwd, void *pk_bwd, void *stream) {
@@ -568,17 +445,17 @@ int smplr_blend3_pack(const float *blend, int N3, void *pk_fwd, void *pk_bwd, vo
   SMPLR_REQUIRE(N3 > 0, "smplr_blend3_pack: bad size N3=%d", N3);
   SMPLR_REQUIRE(blend && (pk_fwd || pk_bwd), "smplr_blend3_pack: null pointer");
   if (pk_fwd) {
-    const int ntile = (N3 + F3_BN - 1) / F3_BN;
-    const size_t n = (size_t)ntile * NKT * 3 * 64;
+    const int ntile = (N3 + BL_BN - 1) / BL_BN;
+    const size_t n = (size_t)ntile * NKT * BL_CPL * 64;
     hipLaunchKernelGGL(blend3_pack_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream),
-                       blend, N3, ntile, reinterpret_cast<uint4 *>(pk_fwd));
+                       blend, N3, ntile, reinterpret_cast<u32x4 *>(pk_fwd));
     SMPLR_LAUNCH_CHECK("smplr_blend3_pack(fwd)");
   }
   if (pk_bwd) {
     const int nkt = (N3 + 15) / 16;
-    const size_t n = (size_t)nkt * 7 * 64;
+    const size_t n = (size_t)nkt * BL_NT * 64;
     hipLaunchKernelGGL(blend3_pack_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream),
-                       blend, N3, nkt, reinterpret_cast<uint4 *>(pk_bwd));
+                       blend, N3, nkt, reinterpret_cast<u32x4 *>(pk_bwd));
     SMPLR_LAUNCH_CHECK("smplr_blend3_pack(bwd)");
   }
   return 0;
@@ -602,7 +479,7 @@ int smplr_blend3_fwd(const void *coef3, const void *pk_fwd, const float *v_templ
   SMPLR_REQUIRE(B >= 0 && N3 > 0, "smplr_blend3_fwd: bad sizes B=%d N3=%d", B, N3);
   if (B == 0) return 0;
   SMPLR_REQUIRE(coef3 && pk_fwd && v_template && v_posed, "smplr_blend3_fwd: null pointer");
-  const int ntiles = (N3 + F3_BN - 1) / F3_BN, ngroups = (B + 127) / 128;
+  const int ntiles = (N3 + BL_BN - 1) / BL_BN, ngroups = (B + 127) / 128;
   hipLaunchKernelGGL(blend3_fwd_kernel, dim3(ntiles, ngroups), dim3(256), 0, as_stream(stream),
                      reinterpret_cast<const u32x4 *>(coef3), reinterpret_cast<const u32x4 *>(pk_fwd), v_template, B,
                      N3, v_posed);
@@ -619,7 +496,7 @@ int smplr_pose_blend3_fwd(const float *x, int x_stride, int num_cam, int B, cons
   if (B == 0) return 0;
   SMPLR_REQUIRE(x && J_template && J_dirs && parents && pk_fwd && v_template && Rs && J && A && J_transformed && v_posed,
                 "smplr_pose_blend3_fwd: null pointer");
-  const int ntiles = (N3 + F3_BN - 1) / F3_BN, ngroups = (B + 127) / 128, npose = (B + PB_MPB - 1) / PB_MPB;
+  const int ntiles = (N3 + BL_BN - 1) / BL_BN, ngroups = (B + 127) / 128, npose = (B + PB_MPB - 1) / PB_MPB;
   const size_t lds_gemm = (size_t)4 * 32 * FC_LD * sizeof(float);
   const size_t lds_pose = (PB_MPB * sizeof(PoseLds) + 15) / 16 * 16 + (size_t)PB_MPB * 224 * sizeof(float);
   const size_t lds = lds_gemm > lds_pose ? lds_gemm : lds_pose;
@@ -649,7 +526,7 @@ int smplr_blend3_bwd(const float *dv_posed, const void *pk_bwd, int B, int N3, f
   int rc = launch_blend3_bwd_partials(dv_posed, pk_bwd, B, N3, reinterpret_cast<float *>(workspace),
                                       as_stream(stream));
   if (rc) return rc;
-  const Blend3BwdGeom g = blend3_bwd_geom(B, N3);
+  const SplitKGeom g = blend3_bwd_geom(B, N3);
   return launch_blend_bwd_reduce(reinterpret_cast<const float *>(workspace), B, g.nslices, g.nmt, dcoef,
                                  as_stream(stream));
 }

@@ -101,14 +101,14 @@ int ensure_lds_attr(const void *fn, size_t lds, LdsAttrMemo *memo, const char *w
 
 // Internal pieces of the fused SMPL backward (smplr_smpl_bwd, pose.hip): the partial-sum producers
 // without their stand-alone reduction kernels.
-struct BlendBwdGeom { int nslices, cols_per_block, nmt; size_t part_floats; };
-BlendBwdGeom blend_bwd_geom(int B, int N3);
+// Split-K geometry of either blend backward: partials (nslices, nmt mesh tiles, 32, 224) = part_floats floats.
+struct SplitKGeom { int nslices, nmt; size_t part_floats; };
+SplitKGeom blend_bwd_geom(int B, int N3);
 int launch_blend_bwd_partials(const float *dv_posed, const float *blend_t, int B, int N3, float *part,
                               hipStream_t st);
 int launch_blend_bwd_reduce(const float *part, int B, int nslices, int nmt, float *dcoef, hipStream_t st);
 // the same GEMM on the bf16 matrix cores with 3-way split operands (blend3.hip)
-struct Blend3BwdGeom { int nslices, ktps, nmt; size_t part_floats; };
-Blend3BwdGeom blend3_bwd_geom(int B, int N3);
+SplitKGeom blend3_bwd_geom(int B, int N3);
 int launch_blend3_bwd_partials(const float *dv_posed, const void *pk_bwd, int B, int N3, float *part,
                                hipStream_t st);
 int skin_bwd_nblk(int V);

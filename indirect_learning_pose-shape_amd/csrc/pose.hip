@@ -338,7 +338,7 @@ int smplr_debug_lds_attr_sets(void) { return smplr::g_lds_attr_sets; }
 const char *smplr_last_error(void) { return smplr::g_err; }
 
 int smplr_coef_ld(int B) { return B > 0 ? (B + 31) / 32 * 32 : 0; }
-size_t smplr_coef3_bytes(int B) { return B > 0 ? (size_t)((B + 31) / 32) * 14 * 3 * 64 * 16 : 0; }
+size_t smplr_coef3_bytes(int B) { return B > 0 ? (size_t)((B + 31) / 32) * smplr::A3_MT * sizeof(smplr::u32x4) : 0; }
 
 int smplr_pose_fwd(const float *x, int x_stride, int num_cam, int B, const float *J_template,
                    const float *J_dirs, const int32_t *parents, float *coef, void *coef3, float *Rs, float *J,
@@ -413,22 +413,14 @@ int smplr_smpl_bwd(const float *dverts, const float *dproj, const float *seg_par
                                     lbs_top4, A, has_proj ? x : nullptr, x_stride, B, V, vertex_sampling, dv_posed,
                                     skin_part, st, &skin_nblk);
   if (rc) return rc;
-  int nslices, nmt;
-  if (blend3_bwd) {                              // bf16x3 operands (blend3.hip); else the fp32 matrix-core GEMM
-    rc = launch_blend3_bwd_partials(dv_posed, blend3_bwd, B, 3 * V, blend_part, st);
-    const Blend3BwdGeom g3 = blend3_bwd_geom(B, 3 * V);
-    nslices = g3.nslices;
-    nmt = g3.nmt;
-  } else {
-    rc = launch_blend_bwd_partials(dv_posed, blend_t, B, 3 * V, blend_part, st);
-    const BlendBwdGeom g = blend_bwd_geom(B, 3 * V);
-    nslices = g.nslices;
-    nmt = g.nmt;
-  }
+  // bf16x3 operands (blend3.hip); else the fp32 matrix-core GEMM
+  const SplitKGeom g = blend3_bwd ? blend3_bwd_geom(B, 3 * V) : blend_bwd_geom(B, 3 * V);
+  rc = blend3_bwd ? launch_blend3_bwd_partials(dv_posed, blend3_bwd, B, 3 * V, blend_part, st)
+                  : launch_blend_bwd_partials(dv_posed, blend_t, B, 3 * V, blend_part, st);
   if (rc) return rc;
   hipLaunchKernelGGL(pose_bwd_kernel, dim3(B), dim3(PBW), 0, st, x, x_stride, num_cam, B,
                      J_dirs, parents, Rs, J, A, (const float *)nullptr, (const float *)nullptr, dJ_transformed,
-                     (const float *)nullptr, dx, skin_part, skin_nblk, blend_part, nslices, nmt,
+                     (const float *)nullptr, dx, skin_part, skin_nblk, blend_part, g.nslices, g.nmt,
                      has_proj ? 1 : 0);
   SMPLR_LAUNCH_CHECK("smplr_smpl_bwd(pose)");
   return 0;

@@ -1,7 +1,7 @@
 // Device pieces of the pose forward shared by pose.hip (pose_fwd_kernel) and blend3.hip (the fused pose + blend
 // kernel): LDS layout, wave-level sync, the SMPL tree by levels, Rodrigues, and the forward of one mesh on one wave.
 #pragma once
-#include "common.h"
+#include "blend_device.h"
 
 namespace smplr {
 
@@ -153,16 +153,10 @@ __device__ __forceinline__ void pose_fwd_wave(
   wave_sync();
   if (live && coef3 && lane < 28) {
     // the same column as bf16x3 MFMA A-fragments (blend3.hip): lane = (k-tile, half) of this mesh's row
-    // of its 32-mesh tile; [mesh tile][k-tile 14][split 3][lane 64] x 16 B
+    // of its 32-mesh tile (the coef3 layout of blend_device.h)
     const int kt = lane >> 1, hh = lane & 1;
-    float xk[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) xk[j] = sc[kt * 16 + 8 * hh + j];
-    const Frag3 f = split8(xk);
-    u32x4 *o = coef3 + ((size_t)((n >> 5) * 14 + kt) * 3) * 64 + hh * 32 + (n & 31);
-    o[0] = __builtin_bit_cast(u32x4, f.h);
-    o[64] = __builtin_bit_cast(u32x4, f.m);
-    o[128] = __builtin_bit_cast(u32x4, f.l);
+    pack_frag3([&](int j) { return sc[kt * 16 + 8 * hh + j]; },
+               [&] { return coef3 + (size_t)((n >> 5) * NKT + kt) * A3_KT + hh * 32 + (n & 31); });
   }
   // root
   if (live && lane < 12) {
