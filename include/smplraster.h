@@ -349,6 +349,25 @@ int smplr_skin_vis_seg_fwd_ex_conf(const float *v_posed, const float *lbs_top4, 
                                    float *mask, float *seg, int16_t *arg, float *rec, int16_t *vslot, float *loss,
                                    float *stats, float *vmax, uint64_t *conf, void *stream);
 
+/* smplr_skin_vis_seg_fwd_ex_conf (and with it the two entry points it extends: labels, vmax, conf may be NULL) for a part
+ * table that lists no vertex twice, as the reference's: given the table by vertex, the binning workgroup classifies and
+ * places each vertex' slot from the registers it skinned the vertex in, instead of staging every (u, v) in LDS and
+ * gathering by table slot.  Same outputs, the order of the records inside one pixel's nearest-pixel list apart (either
+ * form leaves that to an LDS atomic).
+ *   part_inv (V) int32     vertex v: s | p << 16 where part_pos[s] = v and p is slot s' part; -1 where no part lists v.
+ *                          Topology: built once per table (indirect_learning_pose-shape_amd/ops.py).
+ *   top4_packed (V, 8)     32-bit words per vertex: lbs_top4's four weights | its four joints as the bytes of one
+ *                          word, lowest first | three unused
+ * part_inv = top4_packed = NULL, or SMPLR_SEG_BIN_WALK=0 in the environment (read at every call), runs
+ * smplr_skin_vis_seg_fwd_ex_conf as it is.                                                                        */
+int smplr_skin_vis_seg_fwd_inv(const float *v_posed, const float *lbs_top4, const float *A, const float *cam,
+                               int x_stride, int B, int V, int W, int grid_wh, int ref_compat,
+                               const int32_t *part_pos, const int32_t *part_off, int P, int K, const int32_t *part_inv,
+                               const float *top4_packed, void *workspace, const int32_t *labels, const float *class_w,
+                               float gamma, float *verts, float *proj, float *mask, float *seg, int16_t *arg,
+                               float *rec, int16_t *vslot, float *loss, float *stats, float *vmax, uint64_t *conf,
+                               void *stream);
+
 /* ---- triangle renderer: renderer.py:33-115 (SMPLRenderer), 146-237 (Lambertian point lights / part colours) --------
  * B meshes (B, V, 3) fp32 sharing one faces (F, 3) int32 -> per-pixel face id, depth, part, coverage and colour.  Not
  * differentiable, no anti-aliasing, no near-plane clipping.  Pixel [i, j] samples (x, y) = (j, i) of sample space.

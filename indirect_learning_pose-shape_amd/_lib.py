@@ -77,6 +77,8 @@ SIGNATURES = {
     "smplr_seg_raster_ex_conf": (c_int, [I, I, I, I, P, P, P, P, c_float, P, P, P, P, P, P, P]),
     "smplr_skin_vis_seg_fwd_ex_conf": (c_int, [P, P, P, P, I, I, I, I, I, I, P, P, I, I, P, P, P, c_float, P, P, P, P, P,
                                                P, P, P, P, P, P, P]),
+    "smplr_skin_vis_seg_fwd_inv": (c_int, [P, P, P, P, I, I, I, I, I, I, P, P, I, I, P, P, P, P, P, c_float, P, P, P, P,
+                                           P, P, P, P, P, P, P, P]),
     "smplr_mesh_vbuf_bytes": (c_size_t, [I, I]),
     "smplr_mesh_vertex": (c_int, [P, P, P, I, I, I, c_float, I, I, c_float, c_float, I, P, I, P, P, I, P, I, P, c_longlong,
                                   P, P]),

@@ -723,6 +723,20 @@ int smplr_skin_vis_seg_fwd_ex_conf(const float *v_posed, const float *lbs_top4, 
                              smplr::LossOut{labels, class_w, gamma, loss, reinterpret_cast<float4 *>(stats), vmax}, conf);
 }
 
+int smplr_skin_vis_seg_fwd_inv(const float *v_posed, const float *lbs_top4, const float *A, const float *cam,
+                                int x_stride, int B, int V, int W, int grid_wh, int ref_compat, const int32_t *part_pos,
+                                const int32_t *part_off, int P, int K, const int32_t *part_inv, const float *top4_packed,
+                                void *workspace, const int32_t *labels, const float *class_w, float gamma, float *verts,
+                                float *proj, float *mask, float *seg, int16_t *arg, float *rec, int16_t *vslot,
+                                float *loss, float *stats, float *vmax, uint64_t *conf, void *stream) {
+  SMPLR_REQUIRE((part_inv == nullptr) == (top4_packed == nullptr),
+                "smplr_skin_vis_seg_fwd_inv: part_inv and top4_packed come together");
+  const smplr::SkinIn sk{v_posed, lbs_top4, A, cam, x_stride, verts, proj, part_inv, top4_packed};
+  return smplr::seg_fwd_impl("smplr_skin_vis_seg_fwd_inv", &sk, proj, mask, true, grid_wh, ref_compat, B, V, W, part_pos,
+                             part_off, P, K, workspace, seg, arg, rec, vslot, stream,
+                             smplr::LossOut{labels, class_w, gamma, loss, reinterpret_cast<float4 *>(stats), vmax}, conf);
+}
+
 }  // extern "C"
 
 #ifdef SMPLR_TL

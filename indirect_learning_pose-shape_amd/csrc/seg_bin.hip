@@ -381,6 +381,291 @@ __global__ __launch_bounds__(BIN_T) void seg_bin_kernel(const float *__restrict_
   SMPLR_TL_STAMP(18);
 }
 
+// The skinning form that classifies from registers (SkinIn::inv: for each vertex its slot of the part table and its part,
+// which exist where no vertex is listed twice).  Thread tid owns vertices q BIN_T + tid as in seg_bin_kernel<true, true,
+// true>, and stays their owner to the end: it skins, projects, z-buffers, then takes its own vertex' visibility bit,
+// writes its mask value and classifies and places the vertex' slot from the (u, v) it still holds.  Against that form,
+// which classifies in table order: no (u, v) staged in LDS and gathered back per slot, no second pass over the vertices
+// for the mask, no part-table load behind the output stores (every global load is requested at the top or right behind
+// the first barrier, in front of the first store), the slot's part from the table word instead of a search, and 6
+// barriers for 8.  Loads and stores stay in vertex order, coalesced.  Same arithmetic in the same order per vertex
+// (skin_device.h, classify), the same z-buffer keys and the same ranks: what it leaves is what that form leaves, the
+// order of the records inside one pixel's list apart (an LDS atomic hands it out in both).
+// Far-reaching records keep table order whoever owns them: the owner sets bit `slot` of a bitmap in LDS, one wave scans
+// the bitmap's words, and a slot's rank is its word's base + the set bits below it; a part's first rank is the same
+// expression at part_off[p].
+// (Measured and dropped: the same kernel walking the mesh in table order - slot-major ownership, ranks by ballot.  The
+// kernel's own chain was 0.6 us shorter, but verts, proj and mask then leave as partial cache lines, and their drain
+// at the kernel's end cost 3.3 us at B = 128: HISTORY.md.)
+constexpr int OWN_Q = 7;                         // vertices per thread: VP <= 7 BIN_T, as the skinning form
+constexpr int OWN_FW = OWN_Q * BIN_T / 32;       // words of the far-reaching bitmap (K <= VP)
+constexpr int INV_SLOT = 0xffff;                 // inv word: slot | part << 16 (K <= 8192, P <= 31); < 0: in no part
+static_assert(OWN_FW <= 4 * 64, "one wave scans the bitmap, four words per lane");
+
+__global__ __launch_bounds__(BIN_T) void seg_bin_own_kernel(float *__restrict__ mask, const int *__restrict__ part_off,
+                                                            int P, int K, int VP, int W, int S, float4 *__restrict__ G,
+                                                            int *__restrict__ goff, int *__restrict__ lstart,
+                                                            uint2 *__restrict__ lrec, int vgrid, int ref_compat,
+                                                            short *__restrict__ vslot, SkinIn sk) {
+  extern __shared__ __attribute__((aligned(16))) int s_cnt[];   // npix | z-buffer keys | visible flags
+  __shared__ int s_poff[33], s_gstart[33], s_gpad[33], s_wave[BIN_T / 64], s_fbase[OWN_FW + 1];
+  __shared__ unsigned s_far[OWN_FW];
+  __shared__ int s_any_empty;
+  __shared__ float4 sAj[72];
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  SMPLR_TL_WAVE(g_tl_bin, BIN_T / 64, n, TL_BIN_WG)
+  const int npix = W * W;
+  const int cells = vgrid * vgrid, words = (VP + 31) / 32;
+  unsigned long long *zbuf = reinterpret_cast<unsigned long long *>(s_cnt + ((npix + 1) & ~1));
+  unsigned int *vis = reinterpret_cast<unsigned int *>(zbuf + cells);
+
+  // ---- every global operand of the block: the table words, the matrices, the camera and the first BIN_Q0 vertices' rows
+  // here, the other vertices' rows behind the barrier (as the table-order form: the address unit)
+  int sw[OWN_Q];
+#pragma unroll
+  for (int q = 0; q < OWN_Q; ++q) sw[q] = sk.inv[min(tid + q * BIN_T, VP - 1)];
+  const float4 aj = reinterpret_cast<const float4 *>(sk.A + (size_t)n * 288)[tid < 72 ? tid : 71];
+  const float *cm = sk.cam + (size_t)n * sk.x_stride;
+  const float c0 = cm[0], c1 = cm[1], c2 = cm[2], c3 = cm[3];
+  const float *vp = sk.v_posed + (size_t)n * VP * 3;
+  float vu[OWN_Q], vv[OWN_Q], vz[OWN_Q];
+  float4 tw[OWN_Q];
+  unsigned tj[OWN_Q];                                // (four joints in one word: SkinIn::top4p)
+#pragma unroll
+  for (int q = 0; q < BIN_Q0; ++q) {
+    const int v = min(tid + q * BIN_T, VP - 1);
+    const float4 *tp = reinterpret_cast<const float4 *>(sk.top4p + (size_t)v * 8);
+    tw[q] = tp[0];
+    tj[q] = __float_as_uint(tp[1].x);
+    vu[q] = vp[v * 3 + 0];                           // the posed vertex for now
+    vv[q] = vp[v * 3 + 1];
+    vz[q] = vp[v * 3 + 2];
+  }
+  if (tid <= P) s_poff[tid] = part_off[tid];
+  if (tid == 0) s_any_empty = 0;
+  for (int i = tid; i < npix; i += BIN_T) s_cnt[i] = 0;
+  for (int i = tid; i < cells; i += BIN_T) zbuf[i] = 0ull;
+  for (int i = tid; i < words; i += BIN_T) vis[i] = 0u;
+  if (tid < OWN_FW) s_far[tid] = 0u;
+  if (tid < 72) sAj[tid] = aj;
+  SMPLR_TL_STAMP(1);
+  __syncthreads();
+  SMPLR_TL_STAMP(2);
+#pragma unroll
+  for (int q = BIN_Q0; q < OWN_Q; ++q) {
+    const int v = min(tid + q * BIN_T, VP - 1);
+    const float4 *tp = reinterpret_cast<const float4 *>(sk.top4p + (size_t)v * 8);
+    tw[q] = tp[0];
+    tj[q] = __float_as_uint(tp[1].x);
+    vu[q] = vp[v * 3 + 0];
+    vv[q] = vp[v * 3 + 1];
+    vz[q] = vp[v * 3 + 2];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  {
+    float *vo = sk.verts + (size_t)n * VP * 3, *po = sk.proj + (size_t)n * VP * 3;
+    const float fG = (float)vgrid;
+#pragma unroll
+    for (int q = 0; q < OWN_Q; ++q) {
+      const int v = tid + q * BIN_T;
+      float T[12], X, Y, Z;
+      skin_T_sparse(sAj, tw[q], tj[q], T);
+      skin_apply(T, vu[q], vv[q], vz[q], X, Y, Z);
+      vu[q] = project_u(X, c0, c2);
+      vv[q] = project_u(Y, c1, c3);
+      if (v < VP) {                                  // (either output may be NULL: block-uniform)
+        if (sk.verts) { SMPLR_OUT_STORE(&vo[v * 3 + 0], X); SMPLR_OUT_STORE(&vo[v * 3 + 1], Y); SMPLR_OUT_STORE(&vo[v * 3 + 2], Z); }
+        if (sk.proj) { SMPLR_OUT_STORE(&po[v * 3 + 0], vu[q]); SMPLR_OUT_STORE(&po[v * 3 + 1], vv[q]); SMPLR_OUT_STORE(&po[v * 3 + 2], Z); }
+        const float pu = rintf(vu[q]);               // round half to even, like tf.round (compute_mask.py:22)
+        const float pv = rintf(vv[q]);
+        if (pu >= 0.0f && pu < fG && pv >= 0.0f && pv < fG) {
+          const int cell = (int)pv * vgrid + (int)pu;
+          const unsigned long long key = ((unsigned long long)orderable(Z) << 32) |
+                                         (unsigned long long)(0xFFFFFFFFu - (unsigned)v);
+          atomicMax(&zbuf[cell], key);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);             // one vertex at a time: seven T matrices at once do not fit the registers
+    }
+  }
+  SMPLR_TL_STAMP(3);
+  __syncthreads();
+  SMPLR_TL_STAMP(4);
+  {
+    int empty = 0;
+    for (int i = tid; i < cells; i += BIN_T) {
+      const unsigned long long key = zbuf[i];
+      if (key == 0ull) {
+        empty = 1;
+      } else {
+        const unsigned int v = 0xFFFFFFFFu - (unsigned int)(key & 0xFFFFFFFFull);
+        atomicOr(&vis[v >> 5], 1u << (v & 31));
+      }
+    }
+    if (empty) s_any_empty = 1;   // benign same-value race
+  }
+  SMPLR_TL_STAMP(5);
+  __syncthreads();
+  SMPLR_TL_STAMP(6);
+  SMPLR_TL_STAMP(7);                             // (stamps as seg_bin_kernel numbers them; phases this form lacks are empty)
+  const bool vertex1 = s_any_empty && ref_compat && VP > 1;   // an empty cell makes vertex 1 visible (compute_mask.py:99)
+  float *mk = mask ? mask + (size_t)n * VP : nullptr;
+  short *vsl = vslot ? vslot + (size_t)n * VP : nullptr;
+  float4 *Gn = G + (size_t)n * S;
+  int *goffn = goff + (size_t)n * goff_stride(P);
+  int *lstartn = lstart + (size_t)n * (npix + 1);
+  uint2 *lrecn = lrec + (size_t)n * K;
+
+  // pass 1: each vertex' mask value and its slot's class from the owner's registers; far-reaching flags into the bitmap,
+  // nearest-pixel counts in LDS.  pk = class | pixel << 2
+  int pk[OWN_Q];
+  float lx[OWN_Q];
+#pragma unroll
+  for (int q = 0; q < OWN_Q; ++q) {
+    const int v = tid + q * BIN_T, slot = min(sw[q] & INV_SLOT, K - 1);   // (a table from anywhere else stays inside)
+    const bool on = v < VP;
+    const int vb = on ? v : 0;
+    const float m = (((vis[vb >> 5] >> (vb & 31)) & 1u) || (vertex1 && v == 1)) ? 1.0f : 500.0f;
+    if (mk && on) SMPLR_OUT_STORE(&mk[v], m);         // (NULL when the caller does not want it: block-uniform)
+    int cls = 0, pix = 0;
+    lx[q] = 0.f;
+    if (on && sw[q] >= 0) {
+      const Slot c = classify(vu[q], vv[q], m, v, W);
+      cls = c.cls;
+      pix = c.pix;
+      lx[q] = c.x;
+    }
+    if (cls == 1) atomicOr(&s_far[slot >> 5], 1u << (slot & 31));
+    if (cls == 2) atomicAdd(&s_cnt[pix], 1);
+    // a vertex without a record: in no part, or out of every pixel's reach (the backward's gather by vertex skips it)
+    if (vsl && cls == 0 && on) vsl[v] = -1;
+    pk[q] = cls | (pix << 2);
+  }
+  SMPLR_TL_STAMP(8);
+  __syncthreads();                               // pixel counters and the bitmap complete
+  SMPLR_TL_STAMP(9);
+  // the two prefixes, side by side: local records per thread's pixel range (every wave, then over the waves), and
+  // far-reaching records per word of the bitmap, in slot order (the last wave; s_fbase[OWN_FW] = their total)
+  const int ept = (npix + BIN_T - 1) / BIN_T;
+  const int e0 = tid * ept, e1 = min(npix, e0 + ept);
+  int loc = 0;
+  for (int e = e0; e < e1; ++e) loc += s_cnt[e];
+  int linc = loc;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(linc, o, 64);
+    if (lane >= o) linc += t;
+  }
+  if (lane == 63) s_wave[tid >> 6] = linc;
+  if (tid >= BIN_T - 64) {
+    int c[4], inc = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      c[i] = 4 * lane + i < OWN_FW ? __popc(s_far[4 * lane + i]) : 0;
+      inc += c[i];
+    }
+    const int own = inc;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += t;
+    }
+    int run = inc - own;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (4 * lane + i < OWN_FW) s_fbase[4 * lane + i] = run;
+      run += c[i];
+    }
+    if (lane == 63) s_fbase[OWN_FW] = inc;
+  }
+  SMPLR_TL_STAMP(10);
+  SMPLR_TL_STAMP(11);
+  __syncthreads();
+  SMPLR_TL_STAMP(12);
+  int ltotal = 0;
+  {
+    int run = linc - loc;                        // counting sort offsets over pixels
+    for (int w = 0; w < BIN_T / 64; ++w) {
+      const int t = s_wave[w];
+      if (w < (tid >> 6)) run += t;
+      ltotal += t;
+    }
+    for (int e = e0; e < e1; ++e) {
+      const int c = s_cnt[e];
+      s_cnt[e] = run;            // becomes the placement cursor
+      lstartn[e] = run;
+      run += c;
+    }
+    if (tid == 0) lstartn[npix] = ltotal;
+  }
+  if (tid < 128) {
+    // global prefix at each part's first slot: its word's base + the far-reaching flags below it in the word
+    // (empty parts share a slot; parts that start at K take the total); then the padded part offsets (P <= 31)
+    const int l = tid & 63;
+    int gs = s_fbase[OWN_FW];
+    const int kk = s_poff[l <= P ? l : P];
+    if (l < P && kk < K) gs = s_fbase[kk >> 5] + __popc(s_far[kk >> 5] & ((1u << (kk & 31)) - 1u));
+    const int gnext = __shfl_down(gs, 1, 64);
+    const int cnt = (l < P) ? (gnext - gs + GP - 1) / GP * GP : 0;
+    if (tid < 64) {
+      int inc = cnt;
+#pragma unroll
+      for (int o = 1; o < 32; o <<= 1) {
+        const int t = __shfl_up(inc, o, 64);
+        if (tid >= o) inc += t;
+      }
+      if (tid <= P) {
+        s_gstart[tid] = gs;
+        s_gpad[tid] = inc - cnt;               // tid == P: cnt = 0, inc = total
+        goffn[tid] = inc - cnt;
+      }
+    } else {
+      // the block's second wave, beside the prefix: the parts in order of record count (largest first, ties by part
+      // number) for the rasteriser, whose waves take them from this list as they become free (raster2_fwd_kernel)
+      const int key = l < P ? ((cnt << 5) | (31 - l)) : -1;                    // distinct keys; cnt < 2^16
+      int rank = 0;
+#pragma unroll
+      for (int q = 0; q < 31; ++q) rank += (__builtin_amdgcn_readlane(key, q) > key) ? 1 : 0;
+      if (l < P) goffn[P + 2 + rank] = l;
+    }
+  }
+  SMPLR_TL_STAMP(13);
+  __syncthreads();
+  SMPLR_TL_STAMP(14);
+  // pass 2: placement
+#pragma unroll
+  for (int q = 0; q < OWN_Q; ++q) {
+    const int v = tid + q * BIN_T, cls = pk[q] & 3, slot = min(sw[q] & INV_SLOT, K - 1), p = min((sw[q] >> 16) & 31, P - 1);
+    if (cls == 1) {                              // (cls != 0 only for a vertex of the mesh that a part lists)
+      const int rank = s_fbase[slot >> 5] + __popc(s_far[slot >> 5] & ((1u << (slot & 31)) - 1u));
+      const int dst = s_gpad[p] + (rank - s_gstart[p]);
+      Gn[dst] = make_float4(vu[q], vv[q], 1.0f, __int_as_float(v));
+      if (vsl) vsl[v] = (short)dst;
+    } else if (cls == 2) {
+      const int dst = atomicAdd(&s_cnt[pk[q] >> 2], 1);
+      lrecn[dst] = make_uint2(__float_as_uint(lx[q]), (unsigned)p);
+      Gn[s_gpad[P] + dst] = make_float4(vu[q], vv[q], 500.0f * 500.0f, __int_as_float(v));
+      if (vsl) vsl[v] = (short)(s_gpad[P] + dst);
+    }
+  }
+  SMPLR_TL_STAMP(15);
+  // header: used slots | 0: every far-reaching record has weight 1 (the mask's values are 1 and 500) | length of the
+  // far-reaching list, padded per part - as seg_bin_kernel
+  if (tid == 0) goffn[P + 1] = 0;
+  if (tid == 0)
+    Gn[S - 1] = make_float4(__int_as_float(s_gpad[P] + ltotal), __int_as_float(0), __int_as_float(s_gpad[P]),
+                            __int_as_float(-1));
+  // sentinels in the padding
+  if (tid < P) {
+    const int cnt = s_gstart[tid + 1] - s_gstart[tid];
+    for (int i = s_gpad[tid] + cnt; i < s_gpad[tid + 1]; ++i)
+      Gn[i] = make_float4(INFINITY, INFINITY, 1.0f, __int_as_float(-1));
+  }
+  SMPLR_TL_STAMP(16);
+  SMPLR_TL_STAMP(17);
+  SMPLR_TL_STAMP(18);
+}
+
 // LDS of the binning workgroup: pixel counters [+ z-buffer keys and visible flags with the fused mask] = base,
 // and - when it still fits - every vertex' (u, v) (stage).
 struct BinLds { size_t base, total; bool stage; };
@@ -430,7 +715,17 @@ int seg_bin_impl(const char *fn, const float *proj, float *mask, bool fuse_vis, 
                        ref_compat, reinterpret_cast<short *>(vslot), sk);                                     \
   }
   SMPLR_REQUIRE(!skin || stage, "%s: the skinning form needs the staged (u, v) to fit LDS", fn);
-  if (skin) SMPLR_BIN_LAUNCH(true, true, true)
+  // the skinning form that classifies from registers, where the caller has the part table by vertex (no vertex listed
+  // twice: ops.build_walk_table); SMPLR_SEG_BIN_WALK=0 keeps the table-order form (read per call: both forms can be timed
+  // and compared on one library in one process)
+  const char *own_env = (skin && sk.inv) ? getenv("SMPLR_SEG_BIN_WALK") : nullptr;
+  if (skin && sk.inv && !(own_env && atoi(own_env) == 0)) {
+    SMPLR_REQUIRE(sk.top4p && K <= VP, "%s: the table by vertex comes with the packed skinning rows and K <= V", fn);
+    if (int rc = lds_launch<&seg_bin_own_kernel>(LdsLaunch(dim3(B), dim3(BIN_T), bl.base, st), mask, part_off, P, K, VP, W,
+                                                 S, G, goff, lstart, lrec, grid_wh, ref_compat,
+                                                 reinterpret_cast<short *>(vslot), sk))
+      return rc;
+  } else if (skin) SMPLR_BIN_LAUNCH(true, true, true)
   else if (fuse_vis && stage) SMPLR_BIN_LAUNCH(true, true, false)
   else if (fuse_vis) SMPLR_BIN_LAUNCH(true, false, false)
   else if (stage) SMPLR_BIN_LAUNCH(false, true, false)

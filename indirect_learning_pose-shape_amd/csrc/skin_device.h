@@ -17,9 +17,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // Linear-blend skinning of one vertex from its <= 4 (weight, joint) pairs against the mesh's 24 x 12 joint matrix in
 // LDS (sAj: 72 float4), then the orthographic projection.  One definition for the two kernels that must
 // agree bit for bit: skin_fwd_kernel (skin.hip) and the binning kernel that skins its own vertices (seg_bin.hip).
-__device__ __forceinline__ void skin_T_sparse(const float4 *sAj, const float4 ww, const float4 jj, float T[12]) {
+__device__ __forceinline__ void skin_T_sparse(const float4 *sAj, const float4 ww, const int jx[4], float T[12]) {
   const float w[4] = {ww.x, ww.y, ww.z, ww.w};
-  const int jx[4] = {(int)jj.x, (int)jj.y, (int)jj.z, (int)jj.w};
 #pragma unroll
   for (int e = 0; e < 12; ++e) T[e] = 0.0f;
 #pragma unroll
@@ -30,6 +29,16 @@ __device__ __forceinline__ void skin_T_sparse(const float4 *sAj, const float4 ww
     T[4] = fmaf(wj, r1.x, T[4]); T[5] = fmaf(wj, r1.y, T[5]); T[6] = fmaf(wj, r1.z, T[6]); T[7] = fmaf(wj, r1.w, T[7]);
     T[8] = fmaf(wj, r2.x, T[8]); T[9] = fmaf(wj, r2.y, T[9]); T[10] = fmaf(wj, r2.z, T[10]); T[11] = fmaf(wj, r2.w, T[11]);
   }
+}
+// ... with the joints as top4 holds them (floats), or as one word of four bytes (SkinIn::top4p:
+// a vertex' row is in flight with six others, and the registers it lands in are the binning kernel's peak)
+__device__ __forceinline__ void skin_T_sparse(const float4 *sAj, const float4 ww, const float4 jj, float T[12]) {
+  const int jx[4] = {(int)jj.x, (int)jj.y, (int)jj.z, (int)jj.w};
+  skin_T_sparse(sAj, ww, jx, T);
+}
+__device__ __forceinline__ void skin_T_sparse(const float4 *sAj, const float4 ww, const unsigned jp, float T[12]) {
+  const int jx[4] = {(int)(jp & 255u), (int)((jp >> 8) & 255u), (int)((jp >> 16) & 255u), (int)(jp >> 24)};
+  skin_T_sparse(sAj, ww, jx, T);
 }
 // (Plain expressions on purpose: hipcc contracts them the same way in both kernels - checked in the ISA, and
 // test_skinning_inside_the_binning_kernel_equals_separate_calls compares the outputs bit for bit at five sizes - and
@@ -44,7 +53,9 @@ __device__ __forceinline__ void skin_apply(const float T[12], float p0, float p1
 __device__ __forceinline__ float project_u(float X, float c0, float c2) { return c2 + X * c0; }
 
 // What the binning kernel needs to skin its own vertices (smplr_skin_vis_seg_fwd); all NULL otherwise.
-struct SkinIn { const float *v_posed, *top4, *A, *cam; int x_stride; float *verts, *proj; };
+// inv / top4p (both or neither): for each vertex its slot of the part table | its part << 16, < 0 where no part lists it
+// (seg_bin_own_kernel), and top4 as (V, 8) words: w0..w3 | the four joints as bytes of one word | unused.
+struct SkinIn { const float *v_posed, *top4, *A, *cam; int x_stride; float *verts, *proj; const int *inv; const float *top4p; };
 
 // Vertex sampling: every vs-th vertex is projected, as row vpi of the mesh's VP = vp_count(V, vs) proj rows.
 inline int vp_count(int V, int vs) { return (V + vs - 1) / vs; }

@@ -126,9 +126,71 @@ class PartTable:
     part_pos: torch.Tensor   # (K,) int32 positions into the (strided) vertex list
     part_off: torch.Tensor   # (P+1,) int32 CSR offsets
     VP: int
+    # (VP,) int32, or None: the table by vertex (_part_inv) - what lets the binning kernel that skins its own vertices
+    # classify each of them from the registers it skinned it in
+    inv: Optional[torch.Tensor] = None
+    top4_packed: Optional[tuple] = None   # (lbs_top4, its rows as the kernel reads them): filled at the first call, _inv_rows
 
 
 _part_tables = {}
+WALK_MAX = 0x7fff                       # vertices a walk table takes: the mesh of one binning workgroup and then some
+
+
+def build_walk_table(part_pos, VP):
+    """The part table as an order of ALL the mesh's vertices: its K slots, then the vertices no part lists, ascending
+    -> (VP,) int32, a permutation of 0..VP-1; None where the table cannot give one (a position listed twice or out of
+    range, an empty table, more than WALK_MAX vertices).  Where it exists every vertex has at most one slot, and the
+    binning kernel can take a vertex' slot and part from a table by vertex (_part_inv)."""
+    pos = np.asarray(part_pos, np.int64).reshape(-1)
+    if pos.size == 0 or VP > WALK_MAX or pos.min() < 0 or pos.max() >= VP:
+        return None
+    owned = np.zeros(VP, bool)
+    owned[pos] = True
+    if int(owned.sum()) != pos.size:
+        return None
+    walk = np.concatenate([pos, np.flatnonzero(~owned)])
+    assert walk.size == VP and np.array_equal(np.sort(walk), np.arange(VP))
+    return walk.astype(np.int32)
+
+
+def _part_inv(part_pos, off, VP):
+    """The part table by vertex (csrc/seg_bin.hip, seg_bin_own_kernel): vertex v -> s | p << 16 with part_pos[s] = v
+    and p the part of slot s; -1 for a vertex no part lists.  None where build_walk_table gives None."""
+    walk = build_walk_table(part_pos, VP)
+    if walk is None:
+        return None
+    K = len(part_pos)
+    part = np.repeat(np.arange(len(off) - 1), np.diff(np.asarray(off, np.int64)))
+    inv = np.full(VP, -1, np.int32)
+    inv[walk[:K]] = np.arange(K) | (part << 16)
+    return inv
+
+
+def _inv_rows(pt: PartTable, c: SMPLConstants):
+    """-> (pt.inv, lbs_top4 with each row's four joints packed into one word), or (None, None) where the table has no
+    inv: the second is made once per (table, constants) - both are topology - and kept with the table."""
+    if pt.inv is None or c.lbs_top4 is None or pt.VP != c.V:
+        return None, None
+    if pt.top4_packed is None or pt.top4_packed[0] is not c.lbs_top4:
+        j = c.lbs_top4[:, 4:].to(torch.int32)
+        words = torch.zeros((c.V, 8), dtype=torch.int32, device=c.lbs_top4.device)
+        words[:, :4] = c.lbs_top4[:, :4].contiguous().view(torch.int32)     # the weights' bits
+        words[:, 4] = j[:, 0] | (j[:, 1] << 8) | (j[:, 2] << 16) | (j[:, 3] << 24)
+        pt.top4_packed = (c.lbs_top4, words)
+    return pt.inv, pt.top4_packed[1]
+
+
+def _skin_vis_seg_call(v_posed, A, c: SMPLConstants, cam, W, pt: PartTable, grid_wh, ref_compat, ws, labels=None,
+                       class_w=None, gamma=0.0, verts=None, proj=None, mask=None, seg=None, arg=None, rec=None, vslot=None,
+                       loss=None, stats=None, vmax=None, conf=None):
+    """The one call behind _skin_vis_seg_fwd, _skin_vis_seg_fwd_ex and _skin_vis_seg_opt (smplr_skin_vis_seg_fwd_inv:
+    the `_ex_conf` entry point, classifying from registers where the table has its inverse)."""
+    inv, top4p = _inv_rows(pt, c)
+    check(_lib.load().smplr_skin_vis_seg_fwd_inv(
+        ptr(v_posed), ptr(c.lbs_top4), ptr(A), ptr(cam), cam.shape[1], v_posed.shape[0], c.V, int(W), int(grid_wh),
+        1 if ref_compat else 0, ptr(pt.part_pos), ptr(pt.part_off), pt.P, pt.K, ptr(inv), ptr(top4p), ptr(ws), ptr(labels),
+        ptr(class_w), float(gamma), ptr(verts), ptr(proj), ptr(mask), ptr(seg), ptr(arg), ptr(rec), ptr(vslot), ptr(loss),
+        ptr(stats), ptr(vmax), ptr(conf), stream()), "smplr_skin_vis_seg_fwd_inv")
 
 
 def build_part_table(ids, off, vertex_sampling, num_verts, device) -> PartTable:
@@ -142,9 +204,11 @@ def build_part_table(ids, off, vertex_sampling, num_verts, device) -> PartTable:
         # reference's three tables (part_vertices.pkl, 2_/5_sampled_part_vertices.pkl) are partitions
         raise ValueError("part table lists a vertex position more than once (after // vertex_sampling): "
                          "each vertex may belong to at most one part")
+    inv = _part_inv(part_pos, off, VP)
     return PartTable(P=P, K=int(len(part_pos)),
                      part_pos=torch.as_tensor(part_pos).to(device),
-                     part_off=torch.as_tensor(np.asarray(off, np.int32)).to(device), VP=VP)
+                     part_off=torch.as_tensor(np.asarray(off, np.int32)).to(device), VP=VP,
+                     inv=None if inv is None else torch.as_tensor(inv).to(device))
 
 
 def get_part_table(vertex_sampling, device, num_verts=6890) -> PartTable:
@@ -355,10 +419,8 @@ def _skin_vis_seg_fwd(v_posed, A, c: SMPLConstants, cam, W, pt: PartTable, grid_
         seg = _empty((B, W, W, pt.P + 1), v_posed)
         arg = _empty((B, W, W, 32), v_posed, torch.int16)
         rec = _empty((B, lib.smplr_seg_slots(pt.P, pt.K), 4), v_posed)
-    check(lib.smplr_skin_vis_seg_fwd(ptr(v_posed), ptr(c.lbs_top4), ptr(A), ptr(cam), cam.shape[1], B, V, W,
-                                     int(grid_wh), 1 if ref_compat else 0, ptr(pt.part_pos), ptr(pt.part_off), pt.P,
-                                     pt.K, ptr(ws), ptr(verts), ptr(proj), ptr(mask), ptr(seg), ptr(arg), ptr(rec),
-                                     ptr(vslot), stream()), "smplr_skin_vis_seg_fwd")
+    _skin_vis_seg_call(v_posed, A, c, cam, W, pt, grid_wh, ref_compat, ws, verts=verts, proj=proj, mask=mask, seg=seg,
+                       arg=arg, rec=rec, vslot=vslot)
     return verts, proj, mask, seg, arg, rec
 
 
@@ -386,19 +448,8 @@ def _skin_vis_seg_fwd_ex(v_posed, A, c: SMPLConstants, cam, W, pt: PartTable, la
         stats = _empty((B, W * W, 4), v_posed) if stats is None else stats
     else:
         loss = stats = None
-    if conf is not None:
-        check(lib.smplr_skin_vis_seg_fwd_ex_conf(ptr(v_posed), ptr(c.lbs_top4), ptr(A), ptr(cam), cam.shape[1], B, V, W,
-                                                 int(grid_wh), 1 if ref_compat else 0, ptr(pt.part_pos),
-                                                 ptr(pt.part_off), pt.P, pt.K, ptr(ws), ptr(labels), ptr(class_w),
-                                                 float(gamma), ptr(verts), ptr(proj), ptr(mask), ptr(seg), ptr(arg),
-                                                 ptr(rec), ptr(vslot), ptr(loss), ptr(stats), ptr(vmax), ptr(conf),
-                                                 stream()), "smplr_skin_vis_seg_fwd_ex_conf")
-        return loss, stats, arg, rec
-    check(lib.smplr_skin_vis_seg_fwd_ex(ptr(v_posed), ptr(c.lbs_top4), ptr(A), ptr(cam), cam.shape[1], B, V, W,
-                                        int(grid_wh), 1 if ref_compat else 0, ptr(pt.part_pos), ptr(pt.part_off),
-                                        pt.P, pt.K, ptr(ws), ptr(labels), ptr(class_w), float(gamma), ptr(verts),
-                                        ptr(proj), ptr(mask), ptr(seg), ptr(arg), ptr(rec), ptr(vslot), ptr(loss),
-                                        ptr(stats), ptr(vmax), stream()), "smplr_skin_vis_seg_fwd_ex")
+    _skin_vis_seg_call(v_posed, A, c, cam, W, pt, grid_wh, ref_compat, ws, labels, class_w, gamma, verts, proj, mask, seg,
+                       arg, rec, vslot, loss, stats, vmax, conf)
     return loss, stats, arg, rec
 
 
@@ -1281,7 +1332,5 @@ def _skin_vis_seg_opt(v_posed, A, c, cam, W, pt, grid_wh, ref_compat, verts, pro
     lib = _lib.load()
     B, V = v_posed.shape[0], c.V
     ws = _workspace(lib.smplr_seg_workspace(B, V, W, pt.P, pt.K), v_posed)
-    check(lib.smplr_skin_vis_seg_fwd(ptr(v_posed), ptr(c.lbs_top4), ptr(A), ptr(cam), cam.shape[1], B, V, W,
-                                     int(grid_wh), 1 if ref_compat else 0, ptr(pt.part_pos), ptr(pt.part_off), pt.P,
-                                     pt.K, ptr(ws), ptr(verts), ptr(proj), ptr(mask), ptr(seg), ptr(arg), ptr(rec),
-                                     ptr(vslot), stream()), "smplr_skin_vis_seg_fwd")
+    _skin_vis_seg_call(v_posed, A, c, cam, W, pt, grid_wh, ref_compat, ws, verts=verts, proj=proj, mask=mask, seg=seg,
+                       arg=arg, rec=rec, vslot=vslot)
