@@ -9,8 +9,9 @@
 //      This drops the pair count from 2304 x 6879 to 2304 x (#visible ~ 570) per mesh without
 //      changing a single fp32 result.
 // The rasteriser (raster.hip) and the backward (seg_bwd.hip) read what it leaves; the layout is in raster_common.h.
-#include "raster_common.h"
-#include "skin_device.h"
+// What the two kernels here (and visibility_kernel) do alike - skinning a vertex, the z-buffer, the offsets over pixels
+// and parts, a record's stores and the tail - is written once in bin_device.h.
+#include "bin_device.h"
 
 namespace smplr {
 constexpr int BIN_Q0 = 3;            // seg_bin_kernel<.., SKIN>: vertices per thread whose operands are requested before the first barrier
@@ -115,16 +116,7 @@ __global__ __launch_bounds__(BIN_T) void seg_bin_kernel(const float *__restrict_
     // (the first BIN_Q0 vertices' operands here, the rest behind the barrier: the CU's address unit takes 7.5 k clocks
     // for all 35 requests of every thread, and the skinning that follows is bound by LDS reads - the later vertices'
     // requests are worked off under the first ones' skinning instead of in front of the barrier)
-#pragma unroll
-    for (int q = 0; q < BIN_Q0; ++q) {
-      const int v = min(tid + q * BIN_T, VP - 1);
-      const float4 *tp = reinterpret_cast<const float4 *>(sk.top4 + (size_t)v * 8);
-      tw[q] = tp[0];
-      tj[q] = tp[1];
-      vu[q] = vp[v * 3 + 0];                    // the posed vertex for now
-      vv[q] = vp[v * 3 + 1];
-      vz[q] = vp[v * 3 + 2];
-    }
+    skin_rows_load<false, 0, BIN_Q0>(sk, vp, VP, tw, tj, vu, vv, vz);
   } else if (VIS || STAGE) {
 #pragma unroll
     for (int q = 0; q < VPT; ++q) {
@@ -149,40 +141,20 @@ __global__ __launch_bounds__(BIN_T) void seg_bin_kernel(const float *__restrict_
   SMPLR_TL_STAMP(2);
   if (SKIN) {
     const float *vp = sk.v_posed + (size_t)n * VP * 3;
-#pragma unroll
-    for (int q = BIN_Q0; q < VPT; ++q) {
-      const int v = min(tid + q * BIN_T, VP - 1);
-      const float4 *tp = reinterpret_cast<const float4 *>(sk.top4 + (size_t)v * 8);
-      tw[q] = tp[0];
-      tj[q] = tp[1];
-      vu[q] = vp[v * 3 + 0];
-      vv[q] = vp[v * 3 + 1];
-      vz[q] = vp[v * 3 + 2];
-    }
+    skin_rows_load<false, BIN_Q0, VPT>(sk, vp, VP, tw, tj, vu, vv, vz);
     if (vslot)                                                // block-uniform
       for (int i = tid; i < VP; i += BIN_T) vsl[i] = -1;
     __builtin_amdgcn_sched_barrier(0);
     float *vo = sk.verts + (size_t)n * VP * 3, *po = sk.proj + (size_t)n * VP * 3;
 #pragma unroll
     for (int q = 0; q < VPT; ++q) {
-      const int v = tid + q * BIN_T;
-      float T[12], X, Y, Z;
-      skin_T_sparse(sAj, tw[q], tj[q], T);
-      skin_apply(T, vu[q], vv[q], vz[q], X, Y, Z);
-      vu[q] = project_u(X, c0, c2);
-      vv[q] = project_u(Y, c1, c3);
-      vz[q] = Z;
-      if (v < VP) {                                // (either output may be NULL: block-uniform)
-        if (sk.verts) { SMPLR_OUT_STORE(&vo[v * 3 + 0], X); SMPLR_OUT_STORE(&vo[v * 3 + 1], Y); SMPLR_OUT_STORE(&vo[v * 3 + 2], Z); }
-        if (sk.proj) { SMPLR_OUT_STORE(&po[v * 3 + 0], vu[q]); SMPLR_OUT_STORE(&po[v * 3 + 1], vv[q]); SMPLR_OUT_STORE(&po[v * 3 + 2], Z); }
-      }
+      vz[q] = skin_vertex(sAj, tw[q], tj[q], c0, c1, c2, c3, vu[q], vv[q], vz[q], sk, vo, po, tid + q * BIN_T, VP);
       __builtin_amdgcn_sched_barrier(0);          // one vertex at a time: seven T matrices at once do not fit the registers
     }
 #pragma unroll
     for (int j = 0; j < IPT_MAX; ++j) pos[j] = (j < ipt) ? part_pos[min(k0 + j, K - 1)] : 0;
   }
   if (VIS || STAGE) {
-    const float fG = (float)vgrid;
     for (int base = 0; base < VP; base += VPT * BIN_T) {
       if (base > 0) {                           // VP > 8192: further trips (block-uniform)
 #pragma unroll
@@ -198,16 +170,7 @@ __global__ __launch_bounds__(BIN_T) void seg_bin_kernel(const float *__restrict_
         const int v = base + tid + q * BIN_T;
         if (v < VP) {
           if (STAGE) { sU[v] = vu[q]; sV[v] = vv[q]; }
-          if (VIS) {
-            const float pu = rintf(vu[q]);      // round half to even, like tf.round (compute_mask.py:22)
-            const float pv = rintf(vv[q]);
-            if (pu >= 0.0f && pu < fG && pv >= 0.0f && pv < fG) {
-              const int cell = (int)pv * vgrid + (int)pu;
-              const unsigned long long key = ((unsigned long long)orderable(vz[q]) << 32) |
-                                             (unsigned long long)(0xFFFFFFFFu - (unsigned)v);
-              atomicMax(&zbuf[cell], key);
-            }
-          }
+          if (VIS) zbuf_insert(zbuf, vgrid, vu[q], vv[q], vz[q], v);
         }
       }
     }
@@ -217,24 +180,14 @@ __global__ __launch_bounds__(BIN_T) void seg_bin_kernel(const float *__restrict_
   }
   bool vertex1 = false;                          // an empty cell makes vertex 1 visible (compute_mask.py:99)
   if (VIS) {
-    int empty = 0;
-    for (int i = tid; i < cells; i += BIN_T) {
-      const unsigned long long key = zbuf[i];
-      if (key == 0ull) {
-        empty = 1;
-      } else {
-        const unsigned int v = 0xFFFFFFFFu - (unsigned int)(key & 0xFFFFFFFFull);
-        atomicOr(&vis[v >> 5], 1u << (v & 31));
-      }
-    }
-    if (empty) s_any_empty = 1;   // benign same-value race
+    if (zbuf_resolve(zbuf, cells, vis, BIN_T)) s_any_empty = 1;   // benign same-value race
     SMPLR_TL_STAMP(5);
     __syncthreads();
     SMPLR_TL_STAMP(6);
     vertex1 = s_any_empty && ref_compat && VP > 1;
     if (mask)                                      // (NULL with SKIN when the caller does not want it: block-uniform)
       for (int v = tid; v < VP; v += BIN_T)
-        SMPLR_OUT_STORE(&mk[v], (((vis[v >> 5] >> (v & 31)) & 1u) || (vertex1 && v == 1)) ? 1.0f : 500.0f);
+        SMPLR_OUT_STORE(&mk[v], mask_value(vis, v, vertex1));
   }
   SMPLR_TL_STAMP(7);
   float4 *Gn = G + (size_t)n * S;
@@ -253,7 +206,7 @@ __global__ __launch_bounds__(BIN_T) void seg_bin_kernel(const float *__restrict_
     sl[j].cls = 0;
     if (j < ipt && k < k1) {
       const int ps = pos[j];
-      const float m = VIS ? ((((vis[ps >> 5] >> (ps & 31)) & 1u) || (vertex1 && ps == 1)) ? 1.0f : 500.0f) : mk[ps];
+      const float m = VIS ? mask_value(vis, ps, vertex1) : mk[ps];
       const float u = STAGE ? sU[ps] : pj[ps * 3], v = STAGE ? sV[ps] : pj[ps * 3 + 1];
       sl[j] = classify(u, v, m, ps, W);
     }
@@ -289,54 +242,16 @@ __global__ __launch_bounds__(BIN_T) void seg_bin_kernel(const float *__restrict_
   const int gbase = base2 & 0xffff, gtotal = tot2 & 0xffff, ltotal = tot2 >> 16;
   SMPLR_TL_STAMP(10);
   s_gb[tid] = gbase | (int)(gbits << 16);
-  {
-    int run = base2 >> 16;                       // counting sort offsets over pixels
-    for (int e = e0; e < e1; ++e) {
-      const int c = s_cnt[e];
-      s_cnt[e] = run;            // becomes the placement cursor
-      lstartn[e] = run;
-      run += c;
-    }
-    if (tid == 0) lstartn[npix] = ltotal;
-  }
+  pixel_offsets(s_cnt, lstartn, e0, e1, base2 >> 16, npix, ltotal);
   SMPLR_TL_STAMP(11);
   __syncthreads();
   SMPLR_TL_STAMP(12);
-  if (tid < 128) {
-    // global prefix at each part's first slot: the owning thread's base + its global flags below that slot
-    // (empty parts share a slot; parts that start at K take the total); then the padded part offsets (P <= 31)
-    const int l = tid & 63;
-    int gs = gtotal;
-    const int kk = s_poff[l <= P ? l : P];
-    if (l < P && kk < K) {
-      const int t = kk / ipt, j = kk - t * ipt;
-      const int w = s_gb[t];
-      gs = (w & 0xffff) + __popc(((unsigned)w >> 16) & ((1u << j) - 1u));
-    }
-    const int gnext = __shfl_down(gs, 1, 64);
-    const int cnt = (l < P) ? (gnext - gs + GP - 1) / GP * GP : 0;
-    if (tid < 64) {
-      int inc = cnt;
-#pragma unroll
-      for (int o = 1; o < 32; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (tid >= o) inc += t;
-      }
-      if (tid <= P) {
-        s_gstart[tid] = gs;
-        s_gpad[tid] = inc - cnt;               // tid == P: cnt = 0, inc = total
-        goffn[tid] = inc - cnt;
-      }
-    } else {
-      // the block's second wave, beside the prefix: the parts in order of record count (largest first, ties by part
-      // number) for the rasteriser, whose waves take them from this list as they become free (raster2_fwd_kernel)
-      const int key = l < P ? ((cnt << 5) | (31 - l)) : -1;                    // distinct keys; cnt < 2^16
-      int rank = 0;
-#pragma unroll
-      for (int q = 0; q < 31; ++q) rank += (__builtin_amdgcn_readlane(key, q) > key) ? 1 : 0;
-      if (l < P) goffn[P + 2 + rank] = l;
-    }
-  }
+  // a part's first rank: the owning thread's base + its global flags below that slot
+  part_offsets(s_poff, P, K, gtotal, [&](int kk) {
+    const int t = kk / ipt, j = kk - t * ipt;
+    const int w = s_gb[t];
+    return (w & 0xffff) + __popc(((unsigned)w >> 16) & ((1u << j) - 1u));
+  }, s_gstart, s_gpad, goffn);
   SMPLR_TL_STAMP(13);
   __syncthreads();
   SMPLR_TL_STAMP(14);
@@ -351,31 +266,15 @@ __global__ __launch_bounds__(BIN_T) void seg_bin_kernel(const float *__restrict_
       while (k >= s_poff[p + 1]) ++p;
       const Slot s = sl[j];
       if (s.cls == 1) {
-        const int slot = s_gpad[p] + (run - s_gstart[p]);
-        Gn[slot] = make_float4(s.u, s.v, s.m * s.m, __int_as_float(s.pos));
-        if (vslot) vsl[s.pos] = (short)slot;
+        place_far(Gn, vsl, s_gpad[p] + (run - s_gstart[p]), make_float4(s.u, s.v, s.m * s.m, __int_as_float(s.pos)), s.pos);
         ++run;
       } else if (s.cls == 2) {
-        const int dst = atomicAdd(&s_cnt[s.pix], 1);
-        lrecn[dst] = make_uint2(__float_as_uint(s.x), (unsigned)p);
-        Gn[s_gpad[P] + dst] = make_float4(s.u, s.v, s.m * s.m, __int_as_float(s.pos));
-        if (vslot) vsl[s.pos] = (short)(s_gpad[P] + dst);
+        place_near(Gn, lrecn, vsl, s_cnt, s_gpad[P], s.pix, s.x, p, make_float4(s.u, s.v, s.m * s.m, __int_as_float(s.pos)), s.pos);
       }
     }
   }
   SMPLR_TL_STAMP(15);
-  // header: used slots | 1 if some far-reaching record has a weight other than 1 (else the pair loop skips m^2) | length
-  // of the far-reaching list, padded per part (what the rasteriser's table has to hold: smplr_seg_raster_plan)
-  if (tid == 0) goffn[P + 1] = s_nonunit;
-  if (tid == 0)
-    Gn[S - 1] = make_float4(__int_as_float(s_gpad[P] + lstartn[npix]), __int_as_float(s_nonunit), __int_as_float(s_gpad[P]),
-                            __int_as_float(-1));
-  // sentinels in the padding
-  if (tid < P) {
-    const int cnt = s_gstart[tid + 1] - s_gstart[tid];
-    for (int i = s_gpad[tid] + cnt; i < s_gpad[tid + 1]; ++i)
-      Gn[i] = make_float4(INFINITY, INFINITY, 1.0f, __int_as_float(-1));
-  }
+  bin_tail(Gn, goffn, s_gstart, s_gpad, P, S, s_nonunit, ltotal);
   SMPLR_TL_STAMP(16);
   SMPLR_TL_STAMP(17);
   SMPLR_TL_STAMP(18);
@@ -431,16 +330,7 @@ __global__ __launch_bounds__(BIN_T) void seg_bin_own_kernel(float *__restrict__ 
   float vu[OWN_Q], vv[OWN_Q], vz[OWN_Q];
   float4 tw[OWN_Q];
   unsigned tj[OWN_Q];                                // (four joints in one word: SkinIn::top4p)
-#pragma unroll
-  for (int q = 0; q < BIN_Q0; ++q) {
-    const int v = min(tid + q * BIN_T, VP - 1);
-    const float4 *tp = reinterpret_cast<const float4 *>(sk.top4p + (size_t)v * 8);
-    tw[q] = tp[0];
-    tj[q] = __float_as_uint(tp[1].x);
-    vu[q] = vp[v * 3 + 0];                           // the posed vertex for now
-    vv[q] = vp[v * 3 + 1];
-    vz[q] = vp[v * 3 + 2];
-  }
+  skin_rows_load<true, 0, BIN_Q0>(sk, vp, VP, tw, tj, vu, vv, vz);
   if (tid <= P) s_poff[tid] = part_off[tid];
   if (tid == 0) s_any_empty = 0;
   for (int i = tid; i < npix; i += BIN_T) s_cnt[i] = 0;
@@ -451,59 +341,22 @@ __global__ __launch_bounds__(BIN_T) void seg_bin_own_kernel(float *__restrict__ 
   SMPLR_TL_STAMP(1);
   __syncthreads();
   SMPLR_TL_STAMP(2);
-#pragma unroll
-  for (int q = BIN_Q0; q < OWN_Q; ++q) {
-    const int v = min(tid + q * BIN_T, VP - 1);
-    const float4 *tp = reinterpret_cast<const float4 *>(sk.top4p + (size_t)v * 8);
-    tw[q] = tp[0];
-    tj[q] = __float_as_uint(tp[1].x);
-    vu[q] = vp[v * 3 + 0];
-    vv[q] = vp[v * 3 + 1];
-    vz[q] = vp[v * 3 + 2];
-  }
+  skin_rows_load<true, BIN_Q0, OWN_Q>(sk, vp, VP, tw, tj, vu, vv, vz);
   __builtin_amdgcn_sched_barrier(0);
   {
     float *vo = sk.verts + (size_t)n * VP * 3, *po = sk.proj + (size_t)n * VP * 3;
-    const float fG = (float)vgrid;
 #pragma unroll
     for (int q = 0; q < OWN_Q; ++q) {
       const int v = tid + q * BIN_T;
-      float T[12], X, Y, Z;
-      skin_T_sparse(sAj, tw[q], tj[q], T);
-      skin_apply(T, vu[q], vv[q], vz[q], X, Y, Z);
-      vu[q] = project_u(X, c0, c2);
-      vv[q] = project_u(Y, c1, c3);
-      if (v < VP) {                                  // (either output may be NULL: block-uniform)
-        if (sk.verts) { SMPLR_OUT_STORE(&vo[v * 3 + 0], X); SMPLR_OUT_STORE(&vo[v * 3 + 1], Y); SMPLR_OUT_STORE(&vo[v * 3 + 2], Z); }
-        if (sk.proj) { SMPLR_OUT_STORE(&po[v * 3 + 0], vu[q]); SMPLR_OUT_STORE(&po[v * 3 + 1], vv[q]); SMPLR_OUT_STORE(&po[v * 3 + 2], Z); }
-        const float pu = rintf(vu[q]);               // round half to even, like tf.round (compute_mask.py:22)
-        const float pv = rintf(vv[q]);
-        if (pu >= 0.0f && pu < fG && pv >= 0.0f && pv < fG) {
-          const int cell = (int)pv * vgrid + (int)pu;
-          const unsigned long long key = ((unsigned long long)orderable(Z) << 32) |
-                                         (unsigned long long)(0xFFFFFFFFu - (unsigned)v);
-          atomicMax(&zbuf[cell], key);
-        }
-      }
+      const float Z = skin_vertex(sAj, tw[q], tj[q], c0, c1, c2, c3, vu[q], vv[q], vz[q], sk, vo, po, v, VP);
+      if (v < VP) zbuf_insert(zbuf, vgrid, vu[q], vv[q], Z, v);
       __builtin_amdgcn_sched_barrier(0);             // one vertex at a time: seven T matrices at once do not fit the registers
     }
   }
   SMPLR_TL_STAMP(3);
   __syncthreads();
   SMPLR_TL_STAMP(4);
-  {
-    int empty = 0;
-    for (int i = tid; i < cells; i += BIN_T) {
-      const unsigned long long key = zbuf[i];
-      if (key == 0ull) {
-        empty = 1;
-      } else {
-        const unsigned int v = 0xFFFFFFFFu - (unsigned int)(key & 0xFFFFFFFFull);
-        atomicOr(&vis[v >> 5], 1u << (v & 31));
-      }
-    }
-    if (empty) s_any_empty = 1;   // benign same-value race
-  }
+  if (zbuf_resolve(zbuf, cells, vis, BIN_T)) s_any_empty = 1;   // benign same-value race
   SMPLR_TL_STAMP(5);
   __syncthreads();
   SMPLR_TL_STAMP(6);
@@ -524,8 +377,7 @@ __global__ __launch_bounds__(BIN_T) void seg_bin_own_kernel(float *__restrict__ 
   for (int q = 0; q < OWN_Q; ++q) {
     const int v = tid + q * BIN_T, slot = min(sw[q] & INV_SLOT, K - 1);   // (a table from anywhere else stays inside)
     const bool on = v < VP;
-    const int vb = on ? v : 0;
-    const float m = (((vis[vb >> 5] >> (vb & 31)) & 1u) || (vertex1 && v == 1)) ? 1.0f : 500.0f;
+    const float m = mask_value(vis, on ? v : 0, vertex1);   // (vertex 1 exists where vertex1 is set)
     if (mk && on) SMPLR_OUT_STORE(&mk[v], m);         // (NULL when the caller does not want it: block-uniform)
     int cls = 0, pix = 0;
     lx[q] = 0.f;
@@ -584,51 +436,18 @@ __global__ __launch_bounds__(BIN_T) void seg_bin_own_kernel(float *__restrict__ 
   SMPLR_TL_STAMP(12);
   int ltotal = 0;
   {
-    int run = linc - loc;                        // counting sort offsets over pixels
+    int run = linc - loc;
     for (int w = 0; w < BIN_T / 64; ++w) {
       const int t = s_wave[w];
       if (w < (tid >> 6)) run += t;
       ltotal += t;
     }
-    for (int e = e0; e < e1; ++e) {
-      const int c = s_cnt[e];
-      s_cnt[e] = run;            // becomes the placement cursor
-      lstartn[e] = run;
-      run += c;
-    }
-    if (tid == 0) lstartn[npix] = ltotal;
+    pixel_offsets(s_cnt, lstartn, e0, e1, run, npix, ltotal);
   }
-  if (tid < 128) {
-    // global prefix at each part's first slot: its word's base + the far-reaching flags below it in the word
-    // (empty parts share a slot; parts that start at K take the total); then the padded part offsets (P <= 31)
-    const int l = tid & 63;
-    int gs = s_fbase[OWN_FW];
-    const int kk = s_poff[l <= P ? l : P];
-    if (l < P && kk < K) gs = s_fbase[kk >> 5] + __popc(s_far[kk >> 5] & ((1u << (kk & 31)) - 1u));
-    const int gnext = __shfl_down(gs, 1, 64);
-    const int cnt = (l < P) ? (gnext - gs + GP - 1) / GP * GP : 0;
-    if (tid < 64) {
-      int inc = cnt;
-#pragma unroll
-      for (int o = 1; o < 32; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (tid >= o) inc += t;
-      }
-      if (tid <= P) {
-        s_gstart[tid] = gs;
-        s_gpad[tid] = inc - cnt;               // tid == P: cnt = 0, inc = total
-        goffn[tid] = inc - cnt;
-      }
-    } else {
-      // the block's second wave, beside the prefix: the parts in order of record count (largest first, ties by part
-      // number) for the rasteriser, whose waves take them from this list as they become free (raster2_fwd_kernel)
-      const int key = l < P ? ((cnt << 5) | (31 - l)) : -1;                    // distinct keys; cnt < 2^16
-      int rank = 0;
-#pragma unroll
-      for (int q = 0; q < 31; ++q) rank += (__builtin_amdgcn_readlane(key, q) > key) ? 1 : 0;
-      if (l < P) goffn[P + 2 + rank] = l;
-    }
-  }
+  // a part's first rank: its word's base + the far-reaching flags below it in the word
+  part_offsets(s_poff, P, K, s_fbase[OWN_FW], [&](int kk) {
+    return s_fbase[kk >> 5] + __popc(s_far[kk >> 5] & ((1u << (kk & 31)) - 1u));
+  }, s_gstart, s_gpad, goffn);
   SMPLR_TL_STAMP(13);
   __syncthreads();
   SMPLR_TL_STAMP(14);
@@ -638,29 +457,14 @@ __global__ __launch_bounds__(BIN_T) void seg_bin_own_kernel(float *__restrict__ 
     const int v = tid + q * BIN_T, cls = pk[q] & 3, slot = min(sw[q] & INV_SLOT, K - 1), p = min((sw[q] >> 16) & 31, P - 1);
     if (cls == 1) {                              // (cls != 0 only for a vertex of the mesh that a part lists)
       const int rank = s_fbase[slot >> 5] + __popc(s_far[slot >> 5] & ((1u << (slot & 31)) - 1u));
-      const int dst = s_gpad[p] + (rank - s_gstart[p]);
-      Gn[dst] = make_float4(vu[q], vv[q], 1.0f, __int_as_float(v));
-      if (vsl) vsl[v] = (short)dst;
+      place_far(Gn, vsl, s_gpad[p] + (rank - s_gstart[p]), make_float4(vu[q], vv[q], 1.0f, __int_as_float(v)), v);
     } else if (cls == 2) {
-      const int dst = atomicAdd(&s_cnt[pk[q] >> 2], 1);
-      lrecn[dst] = make_uint2(__float_as_uint(lx[q]), (unsigned)p);
-      Gn[s_gpad[P] + dst] = make_float4(vu[q], vv[q], 500.0f * 500.0f, __int_as_float(v));
-      if (vsl) vsl[v] = (short)(s_gpad[P] + dst);
+      place_near(Gn, lrecn, vsl, s_cnt, s_gpad[P], pk[q] >> 2, lx[q], p, make_float4(vu[q], vv[q], 500.0f * 500.0f, __int_as_float(v)), v);
     }
   }
   SMPLR_TL_STAMP(15);
-  // header: used slots | 0: every far-reaching record has weight 1 (the mask's values are 1 and 500) | length of the
-  // far-reaching list, padded per part - as seg_bin_kernel
-  if (tid == 0) goffn[P + 1] = 0;
-  if (tid == 0)
-    Gn[S - 1] = make_float4(__int_as_float(s_gpad[P] + ltotal), __int_as_float(0), __int_as_float(s_gpad[P]),
-                            __int_as_float(-1));
-  // sentinels in the padding
-  if (tid < P) {
-    const int cnt = s_gstart[tid + 1] - s_gstart[tid];
-    for (int i = s_gpad[tid] + cnt; i < s_gpad[tid + 1]; ++i)
-      Gn[i] = make_float4(INFINITY, INFINITY, 1.0f, __int_as_float(-1));
-  }
+  // (flag 0: every far-reaching record has weight 1 - the mask's values are 1 and 500)
+  bin_tail(Gn, goffn, s_gstart, s_gpad, P, S, 0, ltotal);
   SMPLR_TL_STAMP(16);
   SMPLR_TL_STAMP(17);
   SMPLR_TL_STAMP(18);
@@ -672,8 +476,8 @@ struct BinLds { size_t base, total; bool stage; };
 static BinLds bin_lds(int VP, int W, int grid_wh /* 0: mask not fused */) {
   BinLds b;
   b.base = (size_t)((W * W + 1) & ~1) * sizeof(int);
-  if (grid_wh > 0) b.base += (size_t)grid_wh * grid_wh * 8 + (size_t)((VP + 31) / 32) * 4;
-  b.stage = b.base + (size_t)VP * 8 <= 150 * 1024;
+  if (grid_wh > 0) b.base += fused_mask_lds(VP, grid_wh);
+  b.stage = b.base + (size_t)VP * 8 <= LDS_CAP;
   b.total = b.base + (b.stage ? (size_t)VP * 8 : 0);
   return b;
 }
@@ -703,34 +507,40 @@ int seg_bin_impl(const char *fn, const float *proj, float *mask, bool fuse_vis, 
   uint2 *lrec = reinterpret_cast<uint2 *>(base + ws.lrec_off);
   // LDS: pixel counters | fused mask: z-buffer keys + visible flags | staged (u, v) of every vertex
   const BinLds bl = bin_lds(VP, W, fuse_vis ? grid_wh : 0);
-  SMPLR_REQUIRE(bl.base <= 150 * 1024, "%s: pixel counters + grid + flags need %zu B of LDS (max 153600)", fn, bl.base);
+  SMPLR_REQUIRE(bl.base <= LDS_CAP, "%s: pixel counters + grid + flags need %zu B of LDS (max %zu)", fn, bl.base, LDS_CAP);
   const bool stage = bl.stage;
-  const size_t lds = bl.total;
-#define SMPLR_BIN_LAUNCH(VIS_, STAGE_, SKIN_)                                                                 \
-  {                                                                                                           \
-    int rc = lds_attr<&seg_bin_kernel<VIS_, STAGE_, SKIN_>>(lds);          \
-    if (rc) return rc;                                                                                        \
-    hipLaunchKernelGGL((seg_bin_kernel<VIS_, STAGE_, SKIN_>), dim3(B), dim3(BIN_T), lds, st, proj, mask,      \
-                       part_pos, part_off, P, K, VP, W, S, G, goff, lstart, lrec, fuse_vis ? grid_wh : 1,     \
-                       ref_compat, reinterpret_cast<short *>(vslot), sk);                                     \
-  }
   SMPLR_REQUIRE(!skin || stage, "%s: the skinning form needs the staged (u, v) to fit LDS", fn);
   // the skinning form that classifies from registers, where the caller has the part table by vertex (no vertex listed
   // twice: ops.build_walk_table); SMPLR_SEG_BIN_WALK=0 keeps the table-order form (read per call: both forms can be timed
   // and compared on one library in one process)
   const char *own_env = (skin && sk.inv) ? getenv("SMPLR_SEG_BIN_WALK") : nullptr;
-  if (skin && sk.inv && !(own_env && atoi(own_env) == 0)) {
+  const bool own = skin && sk.inv && !(own_env && atoi(own_env) == 0);
+  short *vs = reinterpret_cast<short *>(vslot);
+  int rc;
+  if (own) {
     SMPLR_REQUIRE(sk.top4p && K <= VP, "%s: the table by vertex comes with the packed skinning rows and K <= V", fn);
-    if (int rc = lds_launch<&seg_bin_own_kernel>(LdsLaunch(dim3(B), dim3(BIN_T), bl.base, st), mask, part_off, P, K, VP, W,
-                                                 S, G, goff, lstart, lrec, grid_wh, ref_compat,
-                                                 reinterpret_cast<short *>(vslot), sk))
-      return rc;
-  } else if (skin) SMPLR_BIN_LAUNCH(true, true, true)
-  else if (fuse_vis && stage) SMPLR_BIN_LAUNCH(true, true, false)
-  else if (fuse_vis) SMPLR_BIN_LAUNCH(true, false, false)
-  else if (stage) SMPLR_BIN_LAUNCH(false, true, false)
-  else SMPLR_BIN_LAUNCH(false, false, false)
-#undef SMPLR_BIN_LAUNCH
+    rc = lds_launch<&seg_bin_own_kernel>(LdsLaunch(dim3(B), dim3(BIN_T), bl.base, st), mask, part_off, P, K, VP, W, S, G, goff,
+                                         lstart, lrec, grid_wh, ref_compat, vs, sk);
+  } else {
+    const LdsLaunch at(dim3(B), dim3(BIN_T), bl.total, st);
+    const int vgrid = fuse_vis ? grid_wh : 1;
+    if (skin)
+      rc = lds_launch<&seg_bin_kernel<true, true, true>>(at, proj, mask, part_pos, part_off, P, K, VP, W, S, G, goff, lstart,
+                                                          lrec, vgrid, ref_compat, vs, sk);
+    else if (fuse_vis && stage)
+      rc = lds_launch<&seg_bin_kernel<true, true, false>>(at, proj, mask, part_pos, part_off, P, K, VP, W, S, G, goff, lstart,
+                                                           lrec, vgrid, ref_compat, vs, sk);
+    else if (fuse_vis)
+      rc = lds_launch<&seg_bin_kernel<true, false, false>>(at, proj, mask, part_pos, part_off, P, K, VP, W, S, G, goff, lstart,
+                                                            lrec, vgrid, ref_compat, vs, sk);
+    else if (stage)
+      rc = lds_launch<&seg_bin_kernel<false, true, false>>(at, proj, mask, part_pos, part_off, P, K, VP, W, S, G, goff, lstart,
+                                                            lrec, vgrid, ref_compat, vs, sk);
+    else
+      rc = lds_launch<&seg_bin_kernel<false, false, false>>(at, proj, mask, part_pos, part_off, P, K, VP, W, S, G, goff, lstart,
+                                                             lrec, vgrid, ref_compat, vs, sk);
+  }
+  if (rc) return rc;
   SMPLR_LAUNCH_CHECK(fn);
   return 0;
 }
@@ -755,7 +565,7 @@ int smplr_seg_bin(const float *proj, float *mask, int B, int VP, int W, int grid
 int smplr_skin_vis_seg_fits(int V, int W, int grid_wh) {
   if (V <= 0 || V > 7 * smplr::BIN_T || W <= 0 || W > 160 || grid_wh <= 0 || grid_wh > 128) return 0;
   const smplr::BinLds b = smplr::bin_lds(V, W, grid_wh);
-  return (b.base <= 150 * 1024 && b.stage) ? 1 : 0;
+  return (b.base <= smplr::LDS_CAP && b.stage) ? 1 : 0;
 }
 
 }  // extern "C"

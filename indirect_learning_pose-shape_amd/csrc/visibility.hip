@@ -7,7 +7,9 @@
 // winners = 1 (:65-70).  The reference's nested map_fn (4096 sequential cell scans of all
 // vertices, :59-63) becomes one 64-bit LDS atomicMax per vertex on the key
 // (orderable(z) << 32 | ~index) followed by one scan of the cells.
-#include "common.h"
+// The z-buffer's three steps (zbuf_insert, zbuf_resolve, mask_value) are bin_device.h's, shared with the binning kernels
+// that fuse this mask in front (seg_bin.hip).
+#include "bin_device.h"
 
 namespace smplr {
 
@@ -23,34 +25,13 @@ __global__ __launch_bounds__(1024) void visibility_kernel(const float *__restric
   if (tid == 0) any_empty = 0;
   __syncthreads();
   const float *p = proj + (size_t)n * VP * 3;
-  const float fG = (float)G;
-  for (int v = tid; v < VP; v += 1024) {
-    const float pu = rintf(p[v * 3 + 0]);   // round half to even, like tf.round
-    const float pv = rintf(p[v * 3 + 1]);
-    if (pu >= 0.0f && pu < fG && pv >= 0.0f && pv < fG) {
-      const int cell = (int)pv * G + (int)pu;
-      const unsigned long long key =
-          ((unsigned long long)orderable(p[v * 3 + 2]) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)v);
-      atomicMax(&zbuf[cell], key);
-    }
-  }
+  for (int v = tid; v < VP; v += 1024) zbuf_insert(zbuf, G, p[v * 3 + 0], p[v * 3 + 1], p[v * 3 + 2], v);
   __syncthreads();
-  int empty = 0;
-  for (int i = tid; i < cells; i += 1024) {
-    const unsigned long long key = zbuf[i];
-    if (key == 0ull) {
-      empty = 1;
-    } else {
-      const unsigned int v = 0xFFFFFFFFu - (unsigned int)(key & 0xFFFFFFFFull);
-      atomicOr(&vis[v >> 5], 1u << (v & 31));
-    }
-  }
-  if (empty) any_empty = 1;   // benign same-value race
+  if (zbuf_resolve(zbuf, cells, vis, 1024)) any_empty = 1;   // benign same-value race
   __syncthreads();
-  if (tid == 0 && any_empty && ref_compat && VP > 1) atomicOr(&vis[0], 2u);   // vertex 1
-  __syncthreads();
+  const bool vertex1 = any_empty && ref_compat && VP > 1;
   float *m = mask + (size_t)n * VP;
-  for (int v = tid; v < VP; v += 1024) m[v] = ((vis[v >> 5] >> (v & 31)) & 1u) ? 1.0f : 500.0f;
+  for (int v = tid; v < VP; v += 1024) m[v] = mask_value(vis, v, vertex1);
 }
 
 }  // namespace smplr
@@ -62,15 +43,11 @@ extern "C" int smplr_visibility(const float *proj, int B, int VP, int grid_wh, i
                 "smplr_visibility: bad sizes B=%d VP=%d grid_wh=%d (max 128)", B, VP, grid_wh);
   if (B == 0) return 0;
   SMPLR_REQUIRE(proj && mask, "smplr_visibility: null pointer");
-  const size_t lds = (size_t)grid_wh * grid_wh * 8 + (size_t)((VP + 31) / 32) * 4;
-  SMPLR_REQUIRE(lds <= 150 * 1024, "smplr_visibility: grid + flags need %zu B of LDS (max 153600)", lds);
-  if (lds > 48 * 1024) {
-    static LdsAttrMemo memo = {};                     // once per (kernel, device): common.h
-    int rc = ensure_lds_attr(reinterpret_cast<const void *>(visibility_kernel), lds, &memo, "visibility_kernel");
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(visibility_kernel, dim3(B), dim3(1024), lds, as_stream(stream), proj, VP, grid_wh,
-                     ref_compat, mask);
+  const size_t lds = fused_mask_lds(VP, grid_wh);
+  SMPLR_REQUIRE(lds <= LDS_CAP, "smplr_visibility: grid + flags need %zu B of LDS (max %zu)", lds, LDS_CAP);
+  if (int rc = lds_launch<&visibility_kernel>(LdsLaunch(dim3(B), dim3(1024), lds, as_stream(stream)), proj, VP, grid_wh,
+                                              ref_compat, mask))
+    return rc;
   SMPLR_LAUNCH_CHECK("smplr_visibility");
   return 0;
 }

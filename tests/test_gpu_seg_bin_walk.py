@@ -27,7 +27,7 @@ def _ws_views(ws, B, W, P, K):
             raw[o2:o2 + B * K * 2].reshape(B, K, 2))
 
 
-def _bin(monkeypatch, on, v_posed, A, c, cam, W, pt):
+def _bin(monkeypatch, on, v_posed, A, c, cam, W, pt, grid_wh=64, ref_compat=True):
     """One call of the skinning + binning + raster entry point -> every output and the workspace, on the host."""
     from ilps_amd import _lib, ops
     monkeypatch.setenv("SMPLR_SEG_BIN_WALK", "1" if on else "0")
@@ -39,7 +39,7 @@ def _bin(monkeypatch, on, v_posed, A, c, cam, W, pt):
              arg=e((B, W, W, 32), torch.int16), rec=e((B, lib.smplr_seg_slots(pt.P, pt.K), 4)),
              vslot=e((B, V), torch.int16))
     with torch.cuda.device(v_posed.device):
-        ops._skin_vis_seg_call(v_posed, A, c, cam, W, pt, 64, True, ws, **o)
+        ops._skin_vis_seg_call(v_posed, A, c, cam, W, pt, grid_wh, ref_compat, ws, **o)
         torch.cuda.synchronize()
     out = {k: t.cpu().numpy() for k, t in o.items()}
     out["goff"], out["lstart"], out["lrec"] = _ws_views(ws, B, W, pt.P, pt.K)
@@ -74,10 +74,10 @@ def _same_binning(a, b, P, W):
         assert np.array_equal(a["vslot"][n][fa], b["vslot"][n][fa])
 
 
-def _against_oracle(out, ids, off, W):
+def _against_oracle(out, ids, off, W, grid_wh=64, ref_compat=True):
     from oracle import np_oracle as o
     proj = out["proj"].astype(np.float64)
-    mask = o.compute_mask(proj)
+    mask = o.compute_mask(proj, grid_wh, ref_compat)
     assert np.array_equal(mask, out["mask"])
     # (the oracle takes a maximum over each part's vertices: an empty part, whose channel is 0 everywhere, is left out
     # of its table and put back as zeros)
@@ -140,11 +140,12 @@ def test_reference_topology_gradient(monkeypatch, smpl_model, deterministic):
         grad_close(grads[0][1], grads[1][1], 2e-5, "dx (from registers) vs dx (table order)")
 
 
-def _toy(V=300, B=2, W=8, seed=5):
+def _toy(V=300, B=2, W=8, seed=5, off=(0, 60, 60, 127, 200, 280)):
     """A mesh whose projection is chosen directly: one joint of weight 1 (or two of 1/2) per vertex, every joint matrix
     [I | t_j], camera (1, 1, 0, 0) -> proj = v_posed + t_j.  Parts 0..4 over a random order of the vertices: part 1
-    empty, part 2 of 67 slots, 20 vertices in no part.  In mesh 0 an un-owned vertex lies in front of an owned one in
-    grid cell (3, 4)."""
+    empty, part 2 of 67 slots, 20 vertices in no part (`off`: another layout over the first off[-1] of that order).  In
+    mesh 0 an un-owned vertex lies in front of an owned one in grid cell (3, 4), where the table leaves eleven un-owned
+    (else b is None)."""
     rng = np.random.default_rng(seed)
     top4 = np.zeros((V, 8), np.float32)
     top4[:, 0] = 1.0
@@ -158,15 +159,20 @@ def _toy(V=300, B=2, W=8, seed=5):
     A[..., 3] = tj
     target = np.concatenate([rng.uniform(-1.0, W + 1.0, (B, V, 2)), rng.normal(0, 1, (B, V, 1))], axis=2).astype(np.float32)
     perm = rng.permutation(V)
-    off = [0, 60, 60, 127, 200, 280]
-    ids = [int(v) for v in perm[:280]]
-    a, b = int(perm[3]), int(perm[290])
-    target[0, a] = [3.2, 4.1, 0.0]
-    target[0, b] = [2.9, 3.8, 5.0]
+    off = list(off)
+    K = off[-1]
+    ids = [int(v) for v in perm[:K]]
+    a, b = int(perm[3]), (int(perm[K + 10]) if V > K + 10 else None)
+    if b is not None:
+        target[0, a] = [3.2, 4.1, 0.0]
+        target[0, b] = [2.9, 3.8, 5.0]
     shift = top4[:, 0:1] * tj[top4[:, 4].astype(int)] + top4[:, 1:2] * tj[top4[:, 5].astype(int)]
     v_posed = target - shift[None]
     cam = np.tile(np.array([1.0, 1.0, 0.0, 0.0], np.float32), (B, 1))
-    c = types.SimpleNamespace(V=V, lbs_top4=torch.tensor(top4, device=DEV))
+    dense = np.zeros((V, 24), np.float32)                  # (the separate skinning launch wants the dense rows beside top4)
+    np.add.at(dense, (np.arange(V), top4[:, 4].astype(int)), top4[:, 0])
+    np.add.at(dense, (np.arange(V), top4[:, 5].astype(int)), top4[:, 1])
+    c = types.SimpleNamespace(V=V, lbs_top4=torch.tensor(top4, device=DEV), lbs_weights=torch.tensor(dense, device=DEV))
     td = lambda x: torch.tensor(np.ascontiguousarray(x), device=DEV)
     return c, td(v_posed), td(A.reshape(B, 24, 12)), td(cam), ids, off, target, (a, b)
 
