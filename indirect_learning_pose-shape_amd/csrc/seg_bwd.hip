@@ -7,7 +7,9 @@
 // runs of pixels that share an arg-min are summed in registers and reach the block's LDS slot
 // accumulators (ds_add_f32) only at run boundaries; per-block slot sums are merged in a fixed
 // order and scattered to the vertices with plain stores (no global atomics, no memset).
-// Written once for the five row walks: RunSum (the run accumulator, fp32 or fixed point) and seg_px (one pixel's factor).
+// Written once for the row walks - ten selections in seg_bwd_kernel: pipelined 48- and 64-wide, FAST, general and
+// multi-window, each plain and with the loss head - RunSum (the run accumulator, fp32 or fixed point) and seg_px (one
+// pixel's factor).
 #include "raster_common.h"
 
 namespace smplr {
@@ -16,8 +18,8 @@ constexpr int TL_SEGBWD_WG = 256;
 __device__ unsigned g_tl_segbwd[TL_SEGBWD_WG * 12 * 32];
 #endif
 
-// Segmentation backward.  grid (ceil(W/rows), B), rows = 8 or 24 strips x 32 channels (block b of a mesh takes rows
-// b, b + nblocks, ...): a 32-lane
+// Segmentation backward.  grid (ceil(W/rows), B), rows = 8 strips x 32 channels, or at larger batches the even height
+// in 12 .. 24 that divides W, else 24 (seg_bwd_rows, common.h; block b of a mesh takes rows b, b + nblocks, ...): a 32-lane
 // group walks one output row at a time, lane = channel, so dseg/arg are read as whole 128-B /
 // 64-B pixel rows (coalesced) and neighbouring lanes hit different parts.  Along a row the
 // arg-min of a part changes rarely, so each lane sums the run of pixels that share a slot in
@@ -30,7 +32,7 @@ __device__ unsigned g_tl_segbwd[TL_SEGBWD_WG * 12 * 32];
 // global atomic).  A mesh with more than SB_SLOTS records (only when most vertices are marked
 // visible) is walked once per window of SB_SLOTS slots.  Run-to-run differences are confined to
 // the order in which a block's strips reach a slot's LDS accumulator (last-ulp rounding).
-// (SB_SLOTS = 4096 accumulators per window, SB_NWIN = 5 windows, 8 or 24 rows per block by batch size: common.h)
+// (SB_SLOTS = 4096 accumulators per window, SB_NWIN = 5 windows, 8 or 12 .. 24 rows per block by batch size: common.h)
 constexpr int SB_U = 8;          // pixels in flight per lane
 constexpr int SB_PF = 12;        // pixels of a row requested at kernel entry (>= SB_U)
 
@@ -82,7 +84,11 @@ struct RunSum {
 // instead of three (v_sqrt, v_exp, v_rcp): they issue at a quarter of the rate and were a third of the vector time of
 // this vector-bound loop.  d = 0: t is lifted to 1e-37, kk is large but finite and multiplies du = dv = 0: the gradient
 // is 0, not NaN.  A masked slot read a record of zeros: m^2 = 0, kk = 0.
-// The score's cotangent g: c1 itself, or with the loss head fused in (LOSS) c1 - c2 exp(score) - see LossIn.
+// The score's cotangent g: c1 itself, or with the loss head fused in (LOSS) c1 - c2 exp(score) - see LossIn.  That one
+// is written as ONE fma over the rounded c1: left as `c1 - c2 * exp` the compiler contracted it pixel by pixel as it
+// could pack the multiplies - here c1 and c2 exp rounded and subtracted, there c1's own product dloss (..) fused
+// unrounded into the difference - so a pixel's g depended on its place in the unrolled walk, and the pipelined and the
+// unpipelined walk differed in the last bit (tests/test_gpu_seg_bwd_forms.py compares their hashes).
 template <bool LOSS>
 __device__ __forceinline__ float seg_px(float ru, float rv, float m2, float fc, float fr, float c1, float c2, float &du,
                                         float &dv) {
@@ -92,7 +98,7 @@ __device__ __forceinline__ float seg_px(float ru, float rv, float m2, float fc, 
   const float t = d2 * m2;
   const float r = __builtin_amdgcn_rsqf(fmaxf(t, 1e-37f));
   const float sc = fast_exp_neg(t * r);
-  const float g = LOSS ? c1 - c2 * __expf(sc) : c1;
+  const float g = LOSS ? fmaf(-c2, __expf(sc), c1) : c1;
   return (-g * sc) * (m2 * r);
 }
 
