@@ -635,6 +635,42 @@ int smplr_fit_step_prior(float *x, const float *g, float *m, float *v, int32_t *
                          int num_cam, const float *mean, const float *factor, const float *offset, const int32_t *angle_idx,
                          const float *angle_scale, const float *shape_mean, int K, int A, const float *weights, void *stream);
 
+/* ---- several views or frames of one body: tied columns in the fit step; INTEGRATION.md 4m -----------------------------
+ * Rows come in groups of G consecutive rows (group k = rows kG .. kG + G - 1; 1 <= G <= 16, B a multiple of G): ONE launch
+ * of B / G workgroups, each walking its group's rows.  The state keeps its layout; a group's rows carry copies.
+ * Operands beyond smplr_fit_step_prior's: tie (P) uint8 - 1 = column j is ONE unknown for the whole group; smooth (P) fp32
+ * >= 0 or NULL - the weight of a first-difference penalty between consecutive rows of a group, per column; ignored where
+ * tie[j] is set or smooth[j] = 0.  The prior's seven arrays may be NULL together: no prior (num_cam, K, A are not looked at).
+ * For the rows r = 0 .. G - 1 of a group, in order:
+ *   a. L_r: the row's loss exactly as smplr_fit_step / smplr_fit_step_prior computes it (the same bits).
+ *   b. g_r[j]: the incoming gradient, + dE_r/dx_j with a prior (one fp32 addition).
+ *   c. with smooth: E_s = sum_j smooth[j] sum_{r >= 1} (x_r[j] - x_{r-1}[j])^2 and
+ *      s_r[j] = 2 smooth[j] ((x_r - x_{r-1})[r > 0] - (x_{r+1} - x_r)[r < G - 1]), fp64 on the fp32 operands - thread j's serial
+ *      sum over r, then the loss's fixed tree over j - each rounded to fp32 once; g_r[j] += s_r[j] (one fp32 addition).
+ *      A penalty on differences of axis-angle entries (and camera or shape columns): meant for neighbouring frames, where
+ *      these are small; it is not a distance between rotations.
+ *   d. L = fp32(sum_r (double)L_r + (double)E_s), rows in order.
+ *   e. history[calls[b], b] = L_r, the row's own loss, while calls[b] < H; calls[b] += 1 - every row.
+ *   f. L or any g_r[j] of the group not finite: bad += 1 on every row of the group, nothing else of the group changes.
+ *   g. best iterate and stop: decided once on L from t, stall, active, best_loss of the group's FIRST row, by
+ *      smplr_fit_step's rules 4, and written identically to all G rows; best_x[r] = x[r] for every row on a new best.
+ *   h. an untied column of row r: smplr_fit_step's update 5 with g_r[j] on the row's own m, v, x.  A tied column: the same
+ *      update with g = fp32(sum_r (double)g_r[j]) (rows in order) on m, v, x of the group's first row, the new m, v (and x,
+ *      where it moves) written to all G rows: tied columns that enter equal stay bit-equal across the group.  The caller is
+ *      expected to pass them equal (the decoder consumed each row's own x); otherwise the first row's value wins wherever
+ *      the column moves, and a column that does not move (col_scale = 0 or new m = 0) keeps every row's bits.
+ * G = 1 with smooth = NULL leaves every state tensor and the history with the bits of smplr_fit_step (or _prior).
+ * No atomics: the same bits on every launch and for any batch around the group.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= G <= 16; B % G = 0; tie not NULL; with a prior smplr_fit_step_prior's
+ * limits, else smplr_fit_step's; B = 0 is a no-op.                                                                       */
+int smplr_fit_step_group(float *x, const float *g, float *m, float *v, int32_t *t, int32_t *calls, int32_t *stall, int32_t *bad,
+                         int32_t *best_step, uint8_t *active, float *best_loss, float *best_x, const float *loss, int N,
+                         const float *silh_loss, int Ns, float silh_weight, const float *col_scale, float *history, int H,
+                         int B, int P, float lr, float beta1, float beta2, float eps, float gscale, int mode, int patience,
+                         int num_cam, const float *mean, const float *factor, const float *offset, const int32_t *angle_idx,
+                         const float *angle_scale, const float *shape_mean, int K, int A, const float *weights, int G,
+                         const uint8_t *tie, const float *smooth, void *stream);
+
 /* ---- projects_to_silhouette: keras_smpl/projects_to_silhouette.py:14-44 ----------------- */
 /* silh (B,W,W,2) = [1-s, s], s = max_v exp(-|proj_v-(c,r)|/1.2) over ALL VP vertices, rows
  * flipped; arg (B,W,W) int32 = maximising vertex.  workspace: smplr_silh_workspace(B,VP,W) B.  */

@@ -29,6 +29,18 @@
 //                    rounded to fp32 once, as they leave the routine), then L = fp32(Ld + (double)E) and g_j = g_j + dE_j (one
 //                    fp32 addition, before gscale); steps 2 - 5 act on these totals, so a non-finite E or dE_j is a bad call.
 //                    <false> is the kernel behind smplr_fit_step: none of the prior's code, LDS or arguments is in it.
+//  fit_group_kernel  rows in groups of G <= 16 consecutive rows - views or frames of one body (smplr_fit_step_group): one
+//                    workgroup per group walks its rows.  Thread j owns column j, so coupling the ROWS of a column is
+//                    thread-local: a tied column (tie[j]) is one unknown of the group, updated once with the fp64 sum of the
+//                    rows' gradients (rounded to fp32 once) on the first row's m, v, x and written to all rows; smooth[j]
+//                    weighs a first-difference penalty between consecutive rows (energy and gradient in fp64, rounded once
+//                    each; thread j's serial sum over the rows, then the loss's tree over j).  Every row's loss, prior and
+//                    trace are fit_step_kernel's own - the row-loss tree and the Adam update exist once, as device functions
+//                    both kernels call - while the decisions (bad call, best iterate, stop) are taken once per group on
+//                    L = fp32(sum_r L_r + E_s) from the first row's scalars and written to all G rows.  The rows' gradients
+//                    wait in LDS (16 x 256 floats), never in a register array indexed by the row: no scratch.  <true> / <false>
+//                    as above; G = 1 without smooth leaves the bits of fit_step_kernel.  include/smplraster.h has the
+//                    definition a - h, tests/_fit_group_oracle.py restates it.
 //  prior_kernel      the prior alone (smplr_prior_energy): energy (B, 4) = E_pose, E_angle, E_shape unweighted and the
 //                    weighted E; comp (B) = k*; grad (B, P) or NULL, every column written.
 #include "common.h"
@@ -40,11 +52,77 @@ namespace smplr {
 
 constexpr int FT_T = 256;      // threads per workgroup = the widest row
 constexpr int FT_NW = FT_T / WAVE;
+constexpr int FT_GMAX = 16;    // rows of a group (fit_group_kernel's gradient stash: FT_GMAX x FT_T floats of LDS)
 
 __device__ __forceinline__ float ft_strided_sum(const float *__restrict__ p, int n) {
+  // (eight loads in flight, added in the order of the plain loop: the same bits, a quarter of the round trips to memory)
   float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += FT_T) s += p[i];
+  int i = threadIdx.x;
+  for (; i < n - 7 * FT_T; i += 8 * FT_T) {
+    float a[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) a[u] = p[i + u * FT_T];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += a[u];
+  }
+  for (; i < n; i += FT_T) s += p[i];
   return s;
+}
+
+// The row-loss tree, written once for fit_step_kernel and fit_group_kernel.  ft_loss_partials: the wave's fp64 sums of the
+// threads' fp32 strided sums into sw[0..1][wave]; ft_loss_total, behind a barrier: the four waves' sums in the fixed order
+// (0 + 1) + (2 + 3), the mean, + silh_weight times the silhouette's mean - fp64, not yet rounded.
+__device__ __forceinline__ void ft_loss_partials(const float *__restrict__ loss, int N, const float *__restrict__ silh_loss, int Ns,
+                                                 int b, double (&sw)[2][FT_NW]) {
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+  const double ws = wave_sum_f64((double)ft_strided_sum(loss + (long long)b * N, N));
+  const double wq = silh_loss ? wave_sum_f64((double)ft_strided_sum(silh_loss + (long long)b * Ns, Ns)) : 0.0;
+  if (lane == 0) {
+    sw[0][wave] = ws;
+    sw[1][wave] = wq;
+  }
+}
+
+__device__ __forceinline__ double ft_loss_total(const double (&sw)[2][FT_NW], int N, bool silh, int Ns, float silh_weight) {
+  double Ld = ((sw[0][0] + sw[0][1]) + (sw[0][2] + sw[0][3])) / (double)N;
+  if (silh) Ld += (double)silh_weight * (((sw[1][0] + sw[1][1]) + (sw[1][2] + sw[1][3])) / (double)Ns);
+  return Ld;
+}
+
+// The per-column Adam update, written once for both kernels.  FtBias: the two bias-corrected factors of update t1, fp64 and
+// rounded to fp32 once.  ft_adam: the new m, v and x of one column from its gradient g (before gscale); `move` is false where
+// x keeps its bits (col_scale = 0 or the new m is 0), and x1 is not to be stored then.
+struct FtBias {
+  float step, rc2;
+};
+
+__device__ __forceinline__ FtBias ft_bias(float lr, float beta1, float beta2, int mode, int t1) {
+  const double c1 = 1.0 - pow((double)beta1, (double)t1), c2 = 1.0 - pow((double)beta2, (double)t1);
+  FtBias o;
+  o.step = mode == 0 ? (float)((double)lr * sqrt(c2) / c1) : (float)((double)lr / c1);
+  o.rc2 = (float)sqrt(c2);
+  return o;
+}
+
+struct FtNew {
+  float m, v, x;
+  bool move;
+};
+
+__device__ __forceinline__ FtNew ft_adam(float gj, float m0, float v0, float xj, float cs, const FtBias &bc, float beta1, float beta2,
+                                         float eps, float gscale, int mode) {
+  FtNew o;
+  const float gh = gscale * gj;
+  o.m = fmaf(beta1, m0, (1.0f - beta1) * gh);
+  o.v = fmaf((1.0f - beta2) * gh, gh, beta2 * v0);
+  o.x = xj;
+  o.move = !(cs == 0.f || o.m == 0.f);
+  if (o.move) {
+    const float sv = __fsqrt_rn(o.v);
+    const float den = (mode == 0 ? sv : __fdiv_rn(sv, bc.rc2)) + eps;
+    o.x = xj - (bc.step * cs) * __fdiv_rn(o.m, den);
+  }
+  return o;
 }
 
 // PA: one PriorArgs with PRIOR, nothing without: <false> has smplr_fit_step's arguments and no others
@@ -58,7 +136,6 @@ __global__ __launch_bounds__(FT_T) void fit_step_kernel(
     float beta1, float beta2, float eps, float gscale, int mode, int patience, PA... pa) {
   __shared__ double swave[2][FT_NW];
   const int b = blockIdx.x, j = threadIdx.x;
-  const int lane = j & (WAVE - 1), wave = j / WAVE;
   const long long row = (long long)b * P;
 
   // the row's scalars, read by every thread before anything of the row is written
@@ -67,12 +144,7 @@ __global__ __launch_bounds__(FT_T) void fit_step_kernel(
   const float best0 = best_loss[b];
 
   // 1. the row's loss
-  const double ws = wave_sum_f64((double)ft_strided_sum(loss + (long long)b * N, N));
-  const double wq = silh_loss ? wave_sum_f64((double)ft_strided_sum(silh_loss + (long long)b * Ns, Ns)) : 0.0;
-  if (lane == 0) {
-    swave[0][wave] = ws;
-    swave[1][wave] = wq;
-  }
+  ft_loss_partials(loss, N, silh_loss, Ns, b, swave);
   const bool col = j < P;
   float gj = col ? g[row + j] : 0.f;
   float Ep = 0.f;
@@ -83,8 +155,7 @@ __global__ __launch_bounds__(FT_T) void fit_step_kernel(
     if (col) gj = gj + po.grad;
   }
   const int g_bad = __syncthreads_or(!finitef(gj));                       // (the barrier that publishes swave)
-  double Ld = ((swave[0][0] + swave[0][1]) + (swave[0][2] + swave[0][3])) / (double)N;
-  if (silh_loss) Ld += (double)silh_weight * (((swave[1][0] + swave[1][1]) + (swave[1][2] + swave[1][3])) / (double)Ns);
+  double Ld = ft_loss_total(swave, N, silh_loss != nullptr, Ns, silh_weight);
   if constexpr (PRIOR) Ld += (double)Ep;
   const float L = (float)Ld;
 
@@ -117,20 +188,154 @@ __global__ __launch_bounds__(FT_T) void fit_step_kernel(
   // 5. the update
   const int t1 = t0 + 1;
   if (j == 0) t[b] = t1;
-  const double c1 = 1.0 - pow((double)beta1, (double)t1), c2 = 1.0 - pow((double)beta2, (double)t1);
-  const float step = mode == 0 ? (float)((double)lr * sqrt(c2) / c1) : (float)((double)lr / c1);
-  const float rc2 = (float)sqrt(c2);
+  const FtBias bc = ft_bias(lr, beta1, beta2, mode, t1);
   if (!col) return;
-  const float gh = gscale * gj;
-  const float m1 = fmaf(beta1, m[row + j], (1.0f - beta1) * gh);
-  const float v1 = fmaf((1.0f - beta2) * gh, gh, beta2 * v[row + j]);
-  m[row + j] = m1;
-  v[row + j] = v1;
-  const float cs = col_scale[j];
-  if (cs == 0.f || m1 == 0.f) return;
-  const float sv = __fsqrt_rn(v1);
-  const float den = (mode == 0 ? sv : __fdiv_rn(sv, rc2)) + eps;
-  x[row + j] = xj - (step * cs) * __fdiv_rn(m1, den);
+  const FtNew n = ft_adam(gj, m[row + j], v[row + j], xj, col_scale[j], bc, beta1, beta2, eps, gscale, mode);
+  m[row + j] = n.m;
+  v[row + j] = n.v;
+  if (n.move) x[row + j] = n.x;
+}
+
+// What fit_group_kernel needs only after it has walked the rows.  Thread 0 parks these operands in LDS and every thread takes
+// them back behind the loop: held in scalar registers across prior_row they overflow the register file (55 spilled SGPRs
+// and a scratch frame).
+struct FtLate {
+  float *m, *v;
+  int *t, *stall, *bad, *best_step;
+  unsigned char *active;
+  float *best_loss, *best_x;
+  const float *col_scale;
+  float lr, beta1, beta2, eps, gscale;
+  int mode, patience;
+};
+
+// Rows in groups of G consecutive rows (views or frames of one body): one workgroup per group walks its rows.  Row r's loss and
+// prior are fit_step_kernel's own; its gradient (+ dE/dx, + the smoothness share) waits in LDS, sg[r][j], written and read by
+// thread j alone.  One barrier per row (the vote), so the loss tree's LDS alternates between two copies: row r + 2 writes the
+// copy of row r only behind row r + 1's barrier, which every wave reaches after it has read row r's.  prior_row's own LDS is
+// free again behind the same barrier.  The decisions are taken once, on the group's loss and the first row's scalars.
+template <bool PRIOR, typename... PA>
+__global__ __launch_bounds__(FT_T) void fit_group_kernel(
+    float *__restrict__ x, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+    int *__restrict__ t, int *__restrict__ calls, int *__restrict__ stall, int *__restrict__ bad,
+    int *__restrict__ best_step, unsigned char *__restrict__ active, float *__restrict__ best_loss,
+    float *__restrict__ best_x, const float *__restrict__ loss, int N, const float *__restrict__ silh_loss, int Ns,
+    float silh_weight, const float *__restrict__ col_scale, float *__restrict__ history, int H, int B, int P, float lr,
+    float beta1, float beta2, float eps, float gscale, int mode, int patience, int G,
+    const unsigned char *__restrict__ tie, const float *__restrict__ smooth, PA... pa) {
+  __shared__ double swave[2][2][FT_NW];
+  __shared__ double ssm[FT_NW];
+  __shared__ float sg[FT_GMAX][FT_T];
+  __shared__ FtLate slate;
+  const int b0 = blockIdx.x * G, j = threadIdx.x;
+  const int lane = j & (WAVE - 1), wave = j / WAVE;
+  const bool col = j < P;
+  const long long row0 = (long long)b0 * P;
+
+  // the first row's scalars decide for the group; read by every thread before anything of the group is written
+  const int t0 = t[b0], stall0 = stall[b0];
+  const bool active0 = active[b0] != 0;
+  const float best0 = best_loss[b0];
+  const bool tied = col && tie[j] != 0;
+  const float sm = (smooth && col && !tied) ? smooth[j] : 0.f;
+  if (j == 0)
+    slate = FtLate{m, v, t, stall, bad, best_step, active, best_loss, best_x, col_scale, lr, beta1, beta2, eps, gscale, mode, patience};
+
+  // a - c. every row's loss and gradient
+  double Lsum = 0.0, es = 0.0;
+  int g_bad = 0;
+  float xp = 0.f, xc = col ? x[row0 + j] : 0.f;
+#pragma unroll 1
+  for (int r = 0; r < G; ++r) {
+    const int b = b0 + r;
+    const long long row = (long long)b * P;
+    const int calls0 = j == 0 ? calls[b] : 0;                           // (early: its latency hides behind the row's work)
+    ft_loss_partials(loss, N, silh_loss, Ns, b, swave[r & 1]);
+    float gj = col ? g[row + j] : 0.f;
+    const float xn = (col && r + 1 < G) ? x[row + P + j] : 0.f;
+    float Ep = 0.f;
+    if constexpr (PRIOR) {
+      __shared__ PriorLds sprior;
+      const PriorOut po = prior_row(x + row, P, pa..., sprior);
+      Ep = po.e_total;
+      if (col) gj = gj + po.grad;
+    }
+    if (sm != 0.f) {                                                     // first differences in fp64, rounded once
+      const double d0 = r > 0 ? (double)xc - (double)xp : 0.0, d1 = r + 1 < G ? (double)xn - (double)xc : 0.0;
+      es += (double)sm * (d0 * d0);
+      gj = gj + (float)(2.0 * (double)sm * (d0 - d1));
+    }
+    sg[r][j] = gj;
+    xp = xc;
+    xc = xn;
+    g_bad |= __syncthreads_or(!finitef(gj));                            // (the barrier that publishes swave[r & 1])
+    double Ld = ft_loss_total(swave[r & 1], N, silh_loss != nullptr, Ns, silh_weight);
+    if constexpr (PRIOR) Ld += (double)Ep;
+    const float L = (float)Ld;
+    Lsum += (double)L;
+    // e. the trace: the row's own loss
+    if (j == 0) {
+      if (history && (unsigned)calls0 < (unsigned)H) history[(long long)calls0 * B + b] = L;
+      calls[b] = calls0 + 1;
+    }
+  }
+  // c, d. the smoothness energy by the loss's tree over the threads, and the group's loss
+  if (smooth) {
+    const double we = wave_sum_f64(es);
+    if (lane == 0) ssm[wave] = we;
+    __syncthreads();
+    Lsum += (double)(float)((ssm[0] + ssm[1]) + (ssm[2] + ssm[3]));
+  }
+  const float L = (float)Lsum;
+  const FtLate a = slate;                      // (written before the loop's barriers: G >= 1)
+  // f. a bad call
+  if (g_bad || !finitef(L)) {
+    if (j == 0)
+      for (int r = 0; r < G; ++r) a.bad[b0 + r] += 1;
+    return;
+  }
+  if (!active0) return;
+  // g. the best iterate, the stop: once, written to every row
+  const bool better = L < best0;
+  const int stall1 = better ? 0 : stall0 + 1;
+  const bool go = !(a.patience > 0 && stall1 >= a.patience);
+  const int t1 = t0 + 1;
+  if (j == 0)
+    for (int r = 0; r < G; ++r) {
+      if (better) {
+        a.best_loss[b0 + r] = L;
+        a.best_step[b0 + r] = t0;
+      }
+      a.stall[b0 + r] = stall1;
+      if (!go) a.active[b0 + r] = 0;
+      else a.t[b0 + r] = t1;
+    }
+  if (!col) return;
+  if (better)
+    for (int r = 0; r < G; ++r) a.best_x[row0 + (long long)r * P + j] = x[row0 + (long long)r * P + j];
+  if (!go) return;
+  // h. the update
+  const FtBias bc = ft_bias(a.lr, a.beta1, a.beta2, a.mode, t1);
+  const float cs = a.col_scale[j];
+  if (tied) {                                  // one unknown: the summed gradient on the first row's m, v, x, written to all
+    double gs = (double)sg[0][j];              // (from the first row's value, not from 0: a lone -0 keeps its sign)
+    for (int r = 1; r < G; ++r) gs += (double)sg[r][j];
+    const FtNew n = ft_adam((float)gs, a.m[row0 + j], a.v[row0 + j], x[row0 + j], cs, bc, a.beta1, a.beta2, a.eps, a.gscale, a.mode);
+    for (int r = 0; r < G; ++r) {
+      const long long at = row0 + (long long)r * P + j;
+      a.m[at] = n.m;
+      a.v[at] = n.v;
+      if (n.move) x[at] = n.x;
+    }
+  } else {
+    for (int r = 0; r < G; ++r) {
+      const long long at = row0 + (long long)r * P + j;
+      const FtNew n = ft_adam(sg[r][j], a.m[at], a.v[at], x[at], cs, bc, a.beta1, a.beta2, a.eps, a.gscale, a.mode);
+      a.m[at] = n.m;
+      a.v[at] = n.v;
+      if (n.move) x[at] = n.x;
+    }
+  }
 }
 
 __global__ __launch_bounds__(FT_T) void prior_kernel(const float *__restrict__ x, int P, PriorArgs pa, float *__restrict__ energy,
@@ -180,14 +385,24 @@ int smplr_prior_energy(const float *x, int B, int P, int num_cam, const float *m
   return 0;
 }
 
-// prior = NULL: smplr_fit_step; else smplr_fit_step_prior (`who` names the entry point in messages)
+// the operands smplr_fit_step_group adds
+struct FitGroup {
+  int G;
+  const uint8_t *tie;
+  const float *smooth;
+};
+
+// prior = NULL: smplr_fit_step; else smplr_fit_step_prior (`who` names the entry point in messages); grp: smplr_fit_step_group,
+// with or without a prior
 static int fit_step_launch(const char *who, float *x, const float *g, float *m, float *v, int32_t *t, int32_t *calls,
                            int32_t *stall, int32_t *bad, int32_t *best_step, uint8_t *active, float *best_loss, float *best_x,
                            const float *loss, int N, const float *silh_loss, int Ns, float silh_weight, const float *col_scale,
                            float *history, int H, int B, int P, float lr, float beta1, float beta2, float eps, float gscale,
-                           int mode, int patience, const smplr::PriorArgs *prior, void *stream) {
+                           int mode, int patience, const smplr::PriorArgs *prior, void *stream, const FitGroup *grp = nullptr) {
   using namespace smplr;
   SMPLR_REQUIRE(B >= 0, "%s: negative batch B=%d", who, B);
+  SMPLR_REQUIRE(!grp || (grp->G >= 1 && grp->G <= FT_GMAX), "%s: G=%d rows per group (1..%d)", who, grp ? grp->G : 0, FT_GMAX);
+  SMPLR_REQUIRE(!grp || B % grp->G == 0, "%s: B=%d is no multiple of G=%d", who, B, grp ? grp->G : 0);
   SMPLR_REQUIRE(P >= 1 && P <= FT_T, "%s: P=%d columns (1..%d)", who, P, FT_T);
   SMPLR_REQUIRE(N >= 1, "%s: N=%d loss values per row (N >= 1)", who, N);
   SMPLR_REQUIRE(!silh_loss || Ns >= 1, "%s: Ns=%d silhouette loss values per row (Ns >= 1)", who, Ns);
@@ -204,6 +419,20 @@ static int fit_step_launch(const char *who, float *x, const float *g, float *m, 
   if (B == 0) return 0;
   SMPLR_REQUIRE(x && g && m && v && t && calls && stall && bad && best_step && active && best_loss && best_x && loss && col_scale,
                 "%s: null pointer (only silh_loss and history may be NULL)", who);
+  if (grp) {
+    SMPLR_REQUIRE(grp->tie, "%s: null pointer tie (only smooth, silh_loss, history and the prior's arrays together may be NULL)", who);
+    const dim3 grid((unsigned)(B / grp->G));
+    if (prior)
+      hipLaunchKernelGGL((fit_group_kernel<true, PriorArgs>), grid, dim3(FT_T), 0, as_stream(stream), x, g, m, v, t, calls, stall, bad,
+                         best_step, active, best_loss, best_x, loss, N, silh_loss, Ns, silh_weight, col_scale, history,
+                         history ? H : 0, B, P, lr, beta1, beta2, eps, gscale, mode, patience, grp->G, grp->tie, grp->smooth, *prior);
+    else
+      hipLaunchKernelGGL(fit_group_kernel<false>, grid, dim3(FT_T), 0, as_stream(stream), x, g, m, v, t, calls, stall, bad,
+                         best_step, active, best_loss, best_x, loss, N, silh_loss, Ns, silh_weight, col_scale, history,
+                         history ? H : 0, B, P, lr, beta1, beta2, eps, gscale, mode, patience, grp->G, grp->tie, grp->smooth);
+    SMPLR_LAUNCH_CHECK(who);
+    return 0;
+  }
   if (prior)
     hipLaunchKernelGGL((fit_step_kernel<true, PriorArgs>), dim3((unsigned)B), dim3(FT_T), 0, as_stream(stream), x, g, m, v, t, calls, stall,
                        bad, best_step, active, best_loss, best_x, loss, N, silh_loss, Ns, silh_weight, col_scale, history,
@@ -235,4 +464,19 @@ int smplr_fit_step_prior(float *x, const float *g, float *m, float *v, int32_t *
   return fit_step_launch("smplr_fit_step_prior", x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, N,
                          silh_loss, Ns, silh_weight, col_scale, history, H, B, P, lr, beta1, beta2, eps, gscale, mode, patience,
                          &pa, stream);
+}
+
+int smplr_fit_step_group(float *x, const float *g, float *m, float *v, int32_t *t, int32_t *calls, int32_t *stall, int32_t *bad,
+                         int32_t *best_step, uint8_t *active, float *best_loss, float *best_x, const float *loss, int N,
+                         const float *silh_loss, int Ns, float silh_weight, const float *col_scale, float *history, int H, int B,
+                         int P, float lr, float beta1, float beta2, float eps, float gscale, int mode, int patience, int num_cam,
+                         const float *mean, const float *factor, const float *offset, const int32_t *angle_idx,
+                         const float *angle_scale, const float *shape_mean, int K, int A, const float *weights, int G,
+                         const uint8_t *tie, const float *smooth, void *stream) {
+  const bool prior = mean || factor || offset || angle_idx || angle_scale || shape_mean || weights;      // all NULL: no prior
+  const smplr::PriorArgs pa{mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, K, A, num_cam};
+  const FitGroup grp{G, tie, smooth};
+  return fit_step_launch("smplr_fit_step_group", x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, N,
+                         silh_loss, Ns, silh_weight, col_scale, history, H, B, P, lr, beta1, beta2, eps, gscale, mode, patience,
+                         prior ? &pa : nullptr, stream, &grp);
 }

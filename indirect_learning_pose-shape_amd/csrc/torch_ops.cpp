@@ -990,6 +990,76 @@ void fit_step_prior_meta(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tenso
   prior_check(x, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, num_cam);
 }
 
+// ---- rows in groups of `group_size` (views or frames of one body): tie (P) uint8, smooth (P) fp32 or None; the prior's seven
+// tensors all given or all None (smplr_fit_step_group) -------------------------------------------------------------------
+bool fit_step_group_check(const Tensor &x, const Tensor &tie, const c10::optional<Tensor> &smooth, const c10::optional<Tensor> &mean,
+                          const c10::optional<Tensor> &factor, const c10::optional<Tensor> &offset,
+                          const c10::optional<Tensor> &angle_idx, const c10::optional<Tensor> &angle_scale,
+                          const c10::optional<Tensor> &shape_mean, const c10::optional<Tensor> &weights, int64_t group_size,
+                          int64_t num_cam) {
+  const int64_t B = x.size(0), P = x.size(1);
+  TORCH_CHECK(group_size >= 1 && group_size <= 16, "group_size must lie in 1..16");
+  TORCH_CHECK(B % group_size == 0, "the batch must be a multiple of group_size");
+  TORCH_CHECK(tie.dim() == 1 && tie.size(0) == P && tie.scalar_type() == at::kByte, "tie must be (P,) uint8");
+  TORCH_CHECK(!smooth || (smooth->dim() == 1 && smooth->size(0) == P && smooth->scalar_type() == at::kFloat),
+              "smooth must be (P,) float32");
+  const int given = !!mean + !!factor + !!offset + !!angle_idx + !!angle_scale + !!shape_mean + !!weights;
+  TORCH_CHECK(given == 0 || given == 7, "the prior's tensors (mean, factor, offset, angle_idx, angle_scale, shape_mean, weights) "
+                                        "go together: all or none");
+  if (given) prior_check(x, *mean, *factor, *offset, *angle_idx, *angle_scale, *shape_mean, *weights, num_cam);
+  return given != 0;
+}
+void fit_step_group(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
+                    Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
+                    const c10::optional<Tensor> &silh_loss, const Tensor &col_scale, c10::optional<Tensor> history,
+                    const Tensor &tie, const c10::optional<Tensor> &smooth, const c10::optional<Tensor> &mean,
+                    const c10::optional<Tensor> &factor, const c10::optional<Tensor> &offset,
+                    const c10::optional<Tensor> &angle_idx, const c10::optional<Tensor> &angle_scale,
+                    const c10::optional<Tensor> &shape_mean, const c10::optional<Tensor> &weights, int64_t group_size, double lr,
+                    double beta1, double beta2, double eps, double gscale, double silh_weight, int64_t mode, int64_t patience,
+                    int64_t num_cam) {
+  fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
+                 patience);
+  const bool prior = fit_step_group_check(x, tie, smooth, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights,
+                                          group_size, num_cam);
+  fit_step_on_device(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history);
+  dev_typed(tie, at::kByte, "tie");
+  if (smooth) dev_f32(*smooth, "smooth");
+  const Tensor none;
+  same_device(x, {{"tie", &tie}, {"smooth", smooth ? &*smooth : &none}});
+  if (prior) prior_on_device(x, *mean, *factor, *offset, *angle_idx, *angle_scale, *shape_mean, *weights);
+  DeviceGuard guard(x.device());
+  if (x.size(0) == 0) return;
+  const bool hist = history && history->numel() > 0;
+  const int64_t A = prior ? angle_idx->size(0) : 0;
+  ok(smplr_fit_step_group(x.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), t.data_ptr<int32_t>(),
+                          calls.data_ptr<int32_t>(), stall.data_ptr<int32_t>(), bad.data_ptr<int32_t>(),
+                          best_step.data_ptr<int32_t>(), active.data_ptr<uint8_t>(), best_loss.data_ptr<float>(),
+                          best_x.data_ptr<float>(), loss.data_ptr<float>(), (int)loss.size(1),
+                          silh_loss ? silh_loss->data_ptr<float>() : nullptr, silh_loss ? (int)silh_loss->size(1) : 0,
+                          (float)silh_weight, col_scale.data_ptr<float>(), hist ? history->data_ptr<float>() : nullptr,
+                          hist ? (int)history->size(0) : 0, (int)x.size(0), (int)x.size(1), (float)lr, (float)beta1, (float)beta2,
+                          (float)eps, (float)gscale, (int)mode, (int)patience, (int)num_cam,
+                          prior ? mean->data_ptr<float>() : nullptr, prior ? factor->data_ptr<float>() : nullptr,
+                          prior ? offset->data_ptr<float>() : nullptr, A ? angle_idx->data_ptr<int32_t>() : nullptr,
+                          A ? angle_scale->data_ptr<float>() : nullptr, prior ? shape_mean->data_ptr<float>() : nullptr,
+                          prior ? (int)mean->size(0) : 0, (int)A, prior ? weights->data_ptr<float>() : nullptr, (int)group_size,
+                          tie.data_ptr<uint8_t>(), smooth ? smooth->data_ptr<float>() : nullptr, cur_stream()),
+     "smplr_fit_step_group");
+}
+void fit_step_group_meta(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
+                         Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
+                         const c10::optional<Tensor> &silh_loss, const Tensor &col_scale, c10::optional<Tensor> history,
+                         const Tensor &tie, const c10::optional<Tensor> &smooth, const c10::optional<Tensor> &mean,
+                         const c10::optional<Tensor> &factor, const c10::optional<Tensor> &offset,
+                         const c10::optional<Tensor> &angle_idx, const c10::optional<Tensor> &angle_scale,
+                         const c10::optional<Tensor> &shape_mean, const c10::optional<Tensor> &weights, int64_t group_size, double,
+                         double, double, double, double, double, int64_t mode, int64_t patience, int64_t num_cam) {
+  fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
+                 patience);
+  fit_step_group_check(x, tie, smooth, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, group_size, num_cam);
+}
+
 // ---- body measurements (csrc/measure.hip): verts (B, V, 3), faces (F, 3) int32, face_part (F) uint8, planes (K, 4) or
 // (B, K, 4), part_mask (K) int32 holding the 32 mask bits -> [volume (B), area (B), extent (B, 3), ext_idx (B, 6) int32,
 // girth (B, K), dgirth_dplane (B, K, 4) or (0) without plane_grad, status (B) int32]; K = 0 without planes -----------------
@@ -1169,6 +1239,12 @@ TORCH_LIBRARY(smplraster, m) {
         "Tensor? silh_loss, Tensor col_scale, Tensor(l!)? history, Tensor mean, Tensor factor, Tensor offset, Tensor angle_idx, "
         "Tensor angle_scale, Tensor shape_mean, Tensor weights, float lr=0.001, float beta1=0.9, float beta2=0.999, "
         "float eps=1e-07, float gscale=1.0, float silh_weight=1.0, int mode=0, int patience=0, int num_cam=4) -> ()");
+  m.def("fit_step_group(Tensor(a!) x, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor(d!) t, Tensor(e!) calls, Tensor(f!) stall, "
+        "Tensor(g!) bad, Tensor(h!) best_step, Tensor(i!) active, Tensor(j!) best_loss, Tensor(k!) best_x, Tensor loss, "
+        "Tensor? silh_loss, Tensor col_scale, Tensor(l!)? history, Tensor tie, Tensor? smooth, Tensor? mean, Tensor? factor, "
+        "Tensor? offset, Tensor? angle_idx, Tensor? angle_scale, Tensor? shape_mean, Tensor? weights, int group_size=1, "
+        "float lr=0.001, float beta1=0.9, float beta2=0.999, float eps=1e-07, float gscale=1.0, float silh_weight=1.0, "
+        "int mode=0, int patience=0, int num_cam=4) -> ()");
   m.def("mesh_measures(Tensor verts, Tensor faces, Tensor? face_part=None, Tensor? planes=None, Tensor? part_mask=None, "
         "bool plane_grad=True) -> Tensor[]");
   m.def("mesh_measures_bwd(Tensor verts, Tensor faces, Tensor vf_off, Tensor vf_face, Tensor? face_part, Tensor? planes, "
@@ -1200,6 +1276,7 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("fit_step", &fit_step);
   m.impl("prior_energy", &prior_energy);
   m.impl("fit_step_prior", &fit_step_prior);
+  m.impl("fit_step_group", &fit_step_group);
   m.impl("mesh_measures", &mesh_measures);
   m.impl("mesh_measures_bwd", &mesh_measures_bwd);
 }
@@ -1228,6 +1305,7 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("fit_step", &fit_step_meta);
   m.impl("prior_energy", &prior_energy_meta);
   m.impl("fit_step_prior", &fit_step_prior_meta);
+  m.impl("fit_step_group", &fit_step_group_meta);
   m.impl("mesh_measures", &mesh_measures_meta);
   m.impl("mesh_measures_bwd", &mesh_measures_bwd_meta);
 }

@@ -48,6 +48,32 @@ the same bits on every launch and in any batch.  With a prior, `fit_step` makes 
 smplr_fit_step: L = fp32(L_data + E), g + dE/dx (one fp32 addition) in place of g, steps 2 - 5 on these totals; a non-finite E
 or gradient entry is a bad call.  The weights are a (3,) device tensor that `fit` rewrites at each stage boundary, so a
 captured graph follows them.
+
+Several views or frames of one body (csrc/fit.hip fit_group_kernel; tests/_fit_group_oracle.py restates it in NumPy float64):
+
+    r = fitter.fit(labels, group_size=2, tie=("shape", "pose"))                      # front + side: one beta, one body pose
+    r = fitter.fit(frames, group_size=8, tie=("shape",), smooth=smooth_weights(cam=0.1, global_rot=1.0, pose=1.0))   # a clip
+
+Rows come in groups of G = group_size consecutive rows (B a multiple of G, 1 <= G <= 16); `tie` (P,) uint8 marks the columns
+that are ONE unknown for a group, `smooth` (P,) fp32 >= 0 weighs a first-difference penalty between consecutive rows of a
+group, per column (ignored where tie is set or the weight is 0).  ONE smplr_fit_step_group launch, one workgroup per group:
+  a. L_r: every row's loss exactly as above (with a prior fp32(L_data + E_r)): the same bits.
+  b. g_r[j]: the incoming gradient (+ dE_r/dx_j, one fp32 addition).
+  c. E_s = sum_j smooth[j] sum_{r>=1} (x_r[j] - x_{r-1}[j])^2; s_r[j] = 2 smooth[j] ((x_r - x_{r-1})[r>0] - (x_{r+1} - x_r)[r<G-1]);
+     fp64 on the fp32 operands in a fixed order, each rounded to fp32 once; g_r[j] += s_r[j] (one fp32 addition).  This is a
+     penalty on differences of axis-angle (and camera, shape) entries, meant for neighbouring frames where they are small: it
+     is no distance between rotations.
+  d. L = fp32(sum_r L_r + E_s), rows in order.
+  e. history[calls[b], b] = L_r, the row's own loss; calls[b] += 1 - every row.
+  f. L or any g_r[j] of the group not finite: bad += 1 on every row of the group, nothing else of it changes.
+  g. step 4's decisions once per group, on L, from t, stall, active, best_loss of the group's first row; written to all G rows
+     alike; best_x[r] = x[r] for every row on a new best.
+  h. an untied column of row r: step 5 with g_r[j] on the row's own m, v, x.  A tied column: step 5 with
+     g = fp32(sum_r g_r[j]) (rows in order) on m, v, x of the group's first row, written to all G rows, so tied columns that
+     start equal stay bit-equal (`fit` starts them at the group's mean).  Passed unequal, the first row's value wins wherever
+     the column moves.
+G = 1 without `smooth` is the plain call (and `fit_step` makes the plain launch then).  `FitState` keeps its layout: a group's
+rows carry copies of the group's scalars.
 """
 from __future__ import annotations
 
@@ -71,6 +97,8 @@ MAX_ANGLES = 16                # PR_AMAX
 # exp(-theta[15])
 SMPLIFY_ANGLE_IDX = (55, 58, 12, 15)
 SMPLIFY_ANGLE_SCALE = (1.0, -1.0, -1.0, -1.0)
+MAX_GROUP = 16                 # rows of a group (csrc/fit.hip FT_GMAX)
+TIE_NAMES = ("cam", "global_rot", "pose", "shape")
 
 
 @dataclass
@@ -120,6 +148,83 @@ def column_scale(cam=1.0, pose=1.0, shape=1.0, num_cam=4):
     if not bool(torch.isfinite(s).all()) or bool((s < 0).any()):
         raise ValueError("column scales must be finite and >= 0, got cam=%r pose=%r shape=%r" % (cam, pose, shape))
     return s
+
+
+def _blocks(num_cam):
+    """Column ranges of x = [cam | global_rot (theta[0:3]) | pose (theta[3:72]) | shape] for `num_cam` camera columns."""
+    num_cam = int(num_cam)
+    if num_cam < 0 or num_cam + 82 > THREADS:
+        raise ValueError("num_cam must lie in 0..%d, got %r" % (THREADS - 82, num_cam))
+    return {"cam": (0, num_cam), "global_rot": (num_cam, num_cam + 3), "pose": (num_cam + 3, num_cam + 72),
+            "shape": (num_cam + 72, num_cam + 82)}
+
+
+def tie_mask(shape=True, pose=False, global_rot=False, cam=False, num_cam=4):
+    """(P,) uint8 mask of the columns that are one unknown for a whole group of rows (`fit(group_size=...)`): 1 on the
+    blocks named.  pose = theta[3:72] (the body pose), global_rot = theta[0:3]; a sibling of `column_scale`."""
+    blocks = _blocks(num_cam)
+    tie = torch.zeros(int(num_cam) + 82, dtype=torch.uint8)
+    for name, on in (("shape", shape), ("pose", pose), ("global_rot", global_rot), ("cam", cam)):
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError("%s must be True or False, got %r" % (name, on))
+        if on:
+            lo, hi = blocks[name]
+            tie[lo:hi] = 1
+    return tie
+
+
+def smooth_weights(cam=0.0, global_rot=0.0, pose=0.0, shape=0.0, num_cam=4):
+    """(P,) float32 weights of the first-difference penalty between consecutive rows of a group, per column block; each
+    finite and >= 0 (0: no penalty).  On the rotation columns it weighs differences of axis-angle entries: meant for
+    neighbouring frames."""
+    blocks = _blocks(num_cam)
+    s = torch.empty(int(num_cam) + 82, dtype=torch.float32)
+    for name, w in (("cam", cam), ("global_rot", global_rot), ("pose", pose), ("shape", shape)):
+        w = float(w)
+        if not math.isfinite(w) or w < 0 or w > float(np.finfo(np.float32).max):
+            raise ValueError("smoothing weights must be finite and >= 0, got %s=%r" % (name, w))
+        lo, hi = blocks[name]
+        s[lo:hi] = w
+    return s
+
+
+def check_tie(tie, P, num_cam=4):
+    """Block names ("cam", "global_rot", "pose", "shape") or a (P,) mask -> a (P,) uint8 CPU tensor of 0 / 1."""
+    if isinstance(tie, str):
+        tie = (tie,)
+    if isinstance(tie, (tuple, list)) and all(isinstance(n, str) for n in tie):
+        for n in tie:
+            if n not in TIE_NAMES:
+                raise ValueError("tie names %r; the blocks are %s" % (n, TIE_NAMES))
+        m = tie_mask(**{n: n in tie for n in TIE_NAMES}, num_cam=num_cam)
+    else:
+        a = np.asarray(tie.detach().cpu() if isinstance(tie, torch.Tensor) else tie)
+        if a.shape != (P,) or not (a.dtype == np.bool_ or np.issubdtype(a.dtype, np.integer)) or not np.isin(a, (0, 1)).all():
+            raise ValueError("tie must be block names or a (%d,) mask of 0 / 1, got %r" % (P, tie))
+        m = torch.as_tensor(a.astype(np.uint8))
+    if tuple(m.shape) != (P,):
+        raise ValueError("tie covers %d columns, x has %d" % (m.shape[0], P))
+    return m.contiguous()
+
+
+def check_smooth(smooth, P):
+    """A (P,) array of weights -> a (P,) float32 CPU tensor; each finite and >= 0."""
+    a = np.asarray(smooth.detach().cpu() if isinstance(smooth, torch.Tensor) else smooth, dtype=np.float64)
+    if a.shape != (P,):
+        raise ValueError("smooth must be (%d,), got %s" % (P, a.shape))
+    s = torch.as_tensor(a).to(torch.float32).contiguous()
+    if not bool(torch.isfinite(s).all()) or bool((s < 0).any()):
+        raise ValueError("smoothing weights must be finite and >= 0")
+    return s
+
+
+def check_group(B, group_size):
+    G = int(group_size)
+    if not 1 <= G <= MAX_GROUP:
+        raise ValueError("group_size must lie in 1..%d, got %r" % (MAX_GROUP, group_size))
+    if B % G:
+        raise ValueError("%d rows are no multiple of group_size = %d" % (B, G))
+    return G
 
 
 def check_stages(stages, P, steps=None):
@@ -388,12 +493,16 @@ def prior_energy(x, prior, weights=None, num_cam=4, return_terms=False):
 
 @_lib.on_device
 def fit_step(state, grad, loss, silh_loss=None, silh_weight=1.0, col_scale=None, history=None, lr=1e-3, beta1=0.9,
-             beta2=0.999, eps=KERAS_EPS, grad_scale=1.0, mode="keras", patience=0, prior=None, prior_weights=None, num_cam=4):
+             beta2=0.999, eps=KERAS_EPS, grad_scale=1.0, mode="keras", patience=0, prior=None, prior_weights=None, num_cam=4,
+             group_size=1, tie=None, smooth=None):
     """One smplr_fit_step launch on `state` (in place; see the module's semantics).  grad (B, P): the gradient of
     sum_b L_b; loss (B, N) and silh_loss (B, Ns): per-pixel losses as `SMPLDecoder(loss=...)` returns them; col_scale (P,)
     (None: ones); history (H, B) or None.  HIP tensors only.  With prior (a `PosePrior` on the device) the launch is
     smplr_fit_step_prior: the prior's E joins L and its gradient joins grad inside the kernel; prior_weights = a triple or
-    a (3,) device tensor (None: ones); P = num_cam + 82."""
+    a (3,) device tensor (None: ones); P = num_cam + 82.  group_size = G > 1 or a `smooth`: ONE smplr_fit_step_group launch over
+    groups of G consecutive rows (the module's semantics a - h), with or without a prior; tie (P,) uint8 and smooth (P,) fp32
+    are device tensors (tie None: nothing tied), checked for shape, dtype and device only - no value is read.  group_size = 1
+    without `smooth` makes the plain launch."""
     if mode not in MODES:
         raise ValueError("mode %r is none of %s" % (mode, MODES))
     rc = _lib.require_cuda
@@ -440,6 +549,33 @@ def fit_step(state, grad, loss, silh_loss=None, silh_weight=1.0, col_scale=None,
                                                                ("col_scale", col_scale), ("history", history)]:
         if a is not None and a.device != x.device:
             raise RuntimeError("%s lives on %s, x on %s" % (name, a.device, x.device))
+    if int(group_size) != 1 or smooth is not None:
+        G = check_group(B, group_size)
+        if tie is None:
+            tie = torch.zeros(P, dtype=torch.uint8, device=x.device)
+        for name, a, dt in (("tie", tie, torch.uint8), ("smooth", smooth, torch.float32)):
+            if a is None:
+                continue
+            if not isinstance(a, torch.Tensor) or tuple(a.shape) != (P,) or not a.is_contiguous():
+                raise RuntimeError("%s must be a contiguous (%d,) tensor" % (name, P))
+            rc(a, name, dt)
+            if a.device != x.device:
+                raise RuntimeError("%s lives on %s, x on %s" % (name, a.device, x.device))
+        if prior is not None:
+            prior, w = _prior_operands(prior, prior_weights, x)
+            pargs = (int(num_cam), ptr(prior.mean), ptr(prior.factor), ptr(prior.offset), ptr(prior.angle_idx) if prior.A else None,
+                     ptr(prior.angle_scale) if prior.A else None, ptr(prior.shape_mean), prior.K, prior.A, ptr(w))
+        elif prior_weights is not None:
+            raise ValueError("prior_weights without a prior")
+        else:
+            pargs = (int(num_cam), None, None, None, None, None, None, 0, 0, None)
+        check(_lib.load().smplr_fit_step_group(
+            ptr(x), ptr(grad), ptr(state.m), ptr(state.v), ptr(state.t), ptr(state.calls), ptr(state.stall), ptr(state.bad),
+            ptr(state.best_step), ptr(state.active), ptr(state.best_loss), ptr(state.best_x), ptr(loss), int(loss.shape[1]),
+            ptr(silh_loss), Ns, float(silh_weight), ptr(col_scale), ptr(history) if H else None, H, B, P, float(lr), float(beta1),
+            float(beta2), float(eps), float(grad_scale), MODES.index(mode), int(patience), *pargs, G, ptr(tie), ptr(smooth),
+            stream()), "smplr_fit_step_group")
+        return state
     if prior is not None:
         prior, w = _prior_operands(prior, prior_weights, x)
         check(_lib.load().smplr_fit_step_prior(
@@ -468,7 +604,8 @@ class FitResult:
     final_x (B, P): where the row stood at the end; nonfinite (B,) int32: calls that met a non-finite loss or gradient (and
     changed nothing); active (B,) bool: rows the patience rule had not stopped; history (steps run, B) fp32 loss trace or
     None; steps: iterations run (fewer than asked for when `check_every` found every row stopped); state: the whole
-    `FitState` the loop ended with (moments and counters included)."""
+    `FitState` the loop ended with (moments and counters included); group_size: rows per group - with groups, loss, step and
+    active are the group's, repeated on each of its rows (history holds every row's own loss)."""
     x: torch.Tensor
     loss: torch.Tensor
     step: torch.Tensor
@@ -478,6 +615,7 @@ class FitResult:
     history: Optional[torch.Tensor]
     steps: int
     state: Optional[FitState] = None
+    group_size: int = 1
 
 
 class ParamFitter:
@@ -575,7 +713,7 @@ class ParamFitter:
     # ---- the loop -----------------------------------------------------------------------------------------------------
     def fit(self, labels, init=None, steps=1601, lr=1e-3, mode="keras", stages=None, silh_labels=None, patience=0,
             grad_scale=1.0, graph=False, check_every=0, history=False, beta1=0.9, beta2=0.999, eps=KERAS_EPS,
-            graph_steps=4, generator=None, prior=None, prior_weights=None):
+            graph_steps=4, generator=None, prior=None, prior_weights=None, group_size=1, tie=("shape",), smooth=None):
         """labels (B, W, W) integer part maps on the HIP device -> FitResult.
 
         steps: iterations (decoder_loss_debugging.py:123 runs 1601), or stages = [(steps, column_scale), ...] run one after
@@ -585,12 +723,24 @@ class ParamFitter:
         check_every = k > 0 reads `active.any()` every k iterations (the loop's only host synchronisation) and stops when
         no row is active; history=True records every call's loss per row; prior: a `PosePrior` whose energy joins every row's
         loss inside the same launch, with prior_weights = (w_pose, w_angle, w_shape) (None: ones) or a list of one triple
-        per stage (SMPLify's annealing)."""
+        per stage (SMPLify's annealing).
+
+        group_size = G > 1: rows kG .. kG + G - 1 of labels are views or frames of ONE body (B a multiple of G).  tie: the
+        column blocks that are one unknown per group - names among "cam", "global_rot", "pose", "shape", or a (P,) mask of
+        0 / 1 (`tie_mask`); the start's tied columns are replaced by their mean over the group (also with init=prediction), so
+        they are equal within a group and stay bit-equal.  smooth: (P,) weights (`smooth_weights`) of a first-difference
+        penalty between consecutive rows of a group, for clips.  Still one launch per iteration after the decoder's backward,
+        and graph=True replays as before (tie and smooth are static device tensors).  loss, step and active of the result are
+        the group's, repeated per row.  With group_size = 1 and no smooth, tie has no effect."""
         if mode not in MODES:
             raise ValueError("mode %r is none of %s" % (mode, MODES))
         if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
             raise ValueError("labels must be a (B, W, W) integer tensor")
         B, W = int(labels.shape[0]), self.img_wh
+        grp = check_group(B, group_size)
+        grouped = grp != 1 or smooth is not None
+        tie_m = check_tie(tie, self.P, self.num_cam) if grouped else None
+        smooth_w = check_smooth(smooth, self.P) if smooth is not None else None
         labels = self._labels(labels, B, W, "labels")
         dev = labels.device
         if (silh_labels is not None) != self.with_silhouette:
@@ -611,7 +761,13 @@ class ParamFitter:
         G = max(1, int(graph_steps))
         check_every = int(check_every)
         with torch.cuda.device(dev):
-            state = FitState.new(self.initial(B, init, generator, dev))
+            x0 = self.initial(B, init, generator, dev)
+            if grouped:
+                tie_m = tie_m.to(dev)
+                if grp > 1:                                           # a group starts with one value in every tied column
+                    mean = x0.reshape(B // grp, grp, self.P).mean(1, keepdim=True).expand(-1, grp, -1).reshape(B, self.P)
+                    x0 = torch.where(tie_m.bool(), mean, x0)
+            state = FitState.new(x0)
             hist = torch.full((total, B), float("nan"), dtype=torch.float32, device=dev) if history and total else None
             N, Ns = W * W, self.silh_wh * self.silh_wh
             gout = torch.full((B, N), 1.0 / N, dtype=torch.float32, device=dev)
@@ -620,6 +776,8 @@ class ParamFitter:
             scales = [c.to(dev) for _, c in stage_list]
             kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
                       mode=mode, patience=int(patience))
+            if grouped:
+                kw.update(group_size=grp, tie=tie_m, smooth=smooth_w.to(dev) if smooth_w is not None else None)
             if prior is not None:
                 kw.update(self._prior_kw(prior, stage_w[0], dev))     # (the (3,) tensor is rewritten at each stage boundary)
                 stage_w = [w.to(dev) for w in stage_w]
@@ -662,4 +820,4 @@ class ParamFitter:
             torch.cuda.synchronize()
         return FitResult(x=state.best_x, loss=state.best_loss, step=state.best_step, final_x=state.x, nonfinite=state.bad,
                          active=state.active.bool(), history=hist[:done] if hist is not None else None, steps=done,
-                         state=state)
+                         state=state, group_size=grp)

@@ -74,6 +74,13 @@ SCHEMAS = {
                        "Tensor shape_mean, Tensor weights, float lr=0.001, float beta1=0.90000000000000002, float beta2=0.999, "
                        "float eps=9.9999999999999995e-08, float gscale=1., float silh_weight=1., int mode=0, int patience=0, "
                        "int num_cam=4) -> ()"),
+    "fit_step_group": ("smplraster::fit_step_group(Tensor(a!) x, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor(d!) t, "
+                       "Tensor(e!) calls, Tensor(f!) stall, Tensor(g!) bad, Tensor(h!) best_step, Tensor(i!) active, "
+                       "Tensor(j!) best_loss, Tensor(k!) best_x, Tensor loss, Tensor? silh_loss, Tensor col_scale, "
+                       "Tensor(l!)? history, Tensor tie, Tensor? smooth, Tensor? mean, Tensor? factor, Tensor? offset, "
+                       "Tensor? angle_idx, Tensor? angle_scale, Tensor? shape_mean, Tensor? weights, int group_size=1, "
+                       "float lr=0.001, float beta1=0.90000000000000002, float beta2=0.999, float eps=9.9999999999999995e-08, "
+                       "float gscale=1., float silh_weight=1., int mode=0, int patience=0, int num_cam=4) -> ()"),
     "mesh_measures": ("smplraster::mesh_measures(Tensor verts, Tensor faces, Tensor? face_part=None, Tensor? planes=None, "
                       "Tensor? part_mask=None, bool plane_grad=True) -> Tensor[]"),
     "mesh_measures_bwd": ("smplraster::mesh_measures_bwd(Tensor verts, Tensor faces, Tensor vf_off, Tensor vf_face, "

@@ -1,5 +1,5 @@
 """Iterations per second of fitting SMPL parameters to label maps, three loops at the same commit, one GPU:
-    python tools/fit_time.py [--batch 128] [--iters 1600] [--rounds 3] [--launches] [--prior K [--angles A]] [--loops fitter,graph]
+    python tools/fit_time.py [--batch 128] [--iters 1600] [--rounds 3] [--launches] [--prior K [--angles A]] [--group G [--smooth]] [--loops fitter,graph]
 At B = 128, W = 48 (the reference's decoder_loss_debugging.py runs the loop at W = 48), targets = the arg-max part maps
 of seeded parameters, start = those parameters with pose noise and a camera shift:
     stock     the loop a user of the decoder writes with stock torch: the same `SMPLDecoder(loss=...)`, `seg_loss.mean(1)`,
@@ -10,7 +10,10 @@ Each figure is a host clock around a whole `fit` / `stock_fit` call of --iters i
 synchronise (set-up, warm-up and graph capture of that call included: they are part of what a user waits for), taken
 after one untimed call per loop; the loops alternate --rounds times, every round is printed, the median is reported.
 --prior K adds a seeded K-component pose prior with --angles A angle terms and a shape prior to the fitter's two loops (the
-stock loop has none): the same single launch per iteration, smplr_fit_step_prior in place of smplr_fit_step.  --loops picks
+stock loop has none): the same single launch per iteration, smplr_fit_step_prior in place of smplr_fit_step.  --group G fits
+the rows in groups of G consecutive rows with the shape tied within a group, --smooth adds the first-difference penalty between a
+group's rows (the fitter's two loops; still one launch per iteration, smplr_fit_step_group; the problem's rows stay the seeded,
+unrelated ones: the figure is a time, not a fit).  --loops picks
 the loops to run.  --launches counts the device kernels per iteration of each loop with torch.profiler in a short run of its own (tracing
 slows the host: no timing is taken from it)."""
 import argparse
@@ -72,6 +75,25 @@ def problem(fitter, B, W, seed=0, pose_sigma=0.05, cam_shift=1.5):
     return labels, xs + torch.from_numpy(d).to(dev), xs
 
 
+def group_problem(fitter, K, G, W, seed=0, turn=0.5, cam_shift=1.0):
+    """K bodies seen G times each: xs (K G, 86) = seeded parameters with one beta and one body pose per group and, for view r,
+    the global rotation turned by r `turn` radians about the vertical axis and the camera translation moved by r `cam_shift`
+    pixels; labels (K G, W, W) int32 = arg-max of the decoder's scores at xs.  A group's rows are consecutive."""
+    from _inputs import make_x
+    from ilps_amd.decoder import SMPLDecoder
+    dev = torch.device("cuda:0")
+    x = np.repeat(make_x(K, W, seed=seed), G, axis=0)
+    r = np.tile(np.arange(G, dtype=np.float32), K)
+    x[:, 5] += turn * r
+    x[:, 2] += cam_shift * r
+    x[:, 3] -= cam_shift * r
+    xs = torch.from_numpy(x.astype(np.float32)).to(dev)
+    plain = SMPLDecoder(fitter.decoder._model, img_wh=W, outputs=()).share_constants(fitter.decoder)
+    with torch.no_grad():
+        labels = plain(xs)["seg"].argmax(-1).to(torch.int32)
+    return labels, xs
+
+
 def seeded_prior(K, A, seed=0):
     """A K-component mixture about the mean pose (means N(0, 0.3^2) away, upper-triangular factors with diagonal U[2, 6]), A
     angle terms on distinct theta indices, a shape prior about N(0, 0.5^2)."""
@@ -122,6 +144,8 @@ def main():
     ap.add_argument("--prior", type=int, default=0, help="components of a seeded pose prior for the fitter's loops (0: none)")
     ap.add_argument("--angles", type=int, default=4)
     ap.add_argument("--loops", default="stock,fitter,graph")
+    ap.add_argument("--group", type=int, default=1, help="rows per group for the fitter's loops: shape tied within a group (1: none)")
+    ap.add_argument("--smooth", action="store_true", help="with --group: a first-difference penalty on camera, global rotation and pose")
     a = ap.parse_args()
     from ilps_amd import _lib
     from ilps_amd.fitting import ParamFitter
@@ -129,12 +153,17 @@ def main():
     fitter = ParamFitter(None, img_wh=W)
     labels, x0, _ = problem(fitter, B, W)
     pkw = dict(prior=seeded_prior(a.prior, a.angles), prior_weights=(1e-3, 1e-3, 1e-3)) if a.prior > 0 else {}
+    if a.group > 1 or a.smooth:
+        from ilps_amd.fitting import smooth_weights
+        pkw.update(group_size=a.group, tie=("shape",))
+        if a.smooth:
+            pkw.update(smooth=smooth_weights(cam=0.01, global_rot=0.1, pose=0.1))
     loops = {"stock": lambda n: stock_fit(fitter.decoder, labels, x0, n),
              "fitter": lambda n: fitter.fit(labels, init=x0, steps=n, **pkw),
              "graph": lambda n: fitter.fit(labels, init=x0, steps=n, graph=True, graph_steps=G, **pkw)}
     loops = {k: fn for k, fn in loops.items() if k in a.loops.split(",")}
     res = {"build_id": _lib.build_id()[:16], "B": B, "W": W, "iters": a.iters, "graph_steps": G, "prior_K": a.prior,
-           "prior_A": a.angles if a.prior > 0 else 0}
+           "prior_A": a.angles if a.prior > 0 else 0, "group": a.group, "smooth": bool(a.smooth)}
     if a.launches:
         for fn in loops.values():
             fn(2 * G)                                               # untimed and untraced: code objects loaded
