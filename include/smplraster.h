@@ -543,6 +543,38 @@ int smplr_mesh_measures_bwd(const float *verts, const int32_t *faces, const int3
                             const float *g_area, const float *g_extent, const float *g_girth, int B, int V, int F, int K,
                             float *dverts, void *stream);
 
+/* ---- scan distances: a point cloud against a mesh's surface, both ways, and their gradient (beyond the reference);
+ * INTEGRATION.md 4n ---------------------------------------------------------------------------------------------------------
+ * verts (B, V, 3) fp32, faces (F, 3) int32, points (B, N, 3) fp32, counts (B) int32 or NULL: mesh b uses its points
+ * 0 .. counts[b] - 1 (clamped to 0 .. N; NULL: all N).
+ * smplr_scan_p2m, per point: d2 (B, N) = min over the faces of the squared distance to the closed triangle (a zero-area
+ *   face is a segment or a point), face (B, N) int32 the nearest face (ties to the lower index), bary (B, N, 3) >= 0 the
+ *   weights of its closest point q, resid (B, N, 3) = p - q.
+ * smplr_scan_m2p, per vertex: vd2 (B, V) = min over the mesh's used, finite points of |v - p|^2, vpoint (B, V) int32 (ties to
+ *   the lower index).
+ * Both search in fp32 in coordinates relative to the point (vertex) and recompute the winner in fp64 on the fp32 inputs, each
+ * output rounded to fp32 once.
+ *   status (B) int32: SMPLR_SCAN_NONFINITE - a coordinate of the mesh is NaN or Inf: every float output of that mesh (and
+ *   every dverts row) is NaN, every index -1.  Other meshes are not affected.  A non-finite point: d2, bary, resid NaN, face
+ *   -1, no gradient, no candidate of m2p.  Points at or beyond counts[b]: d2 0, face -1, bary and resid 0.  No usable point:
+ *   vd2 +Inf, vpoint -1.  No usable face: d2 +Inf, face -1, bary and resid 0.
+ * smplr_scan_bwd: dverts[b, i] = sum over (n, k) with faces[face[b, n], k] = i of -2 g_d2[b, n] bary[b, n, k] resid[b, n], in
+ *   point order then corner order, + 2 g_vd2[b, i] (v_i - points[b, vpoint[b, i]]); fp64 sums rounded once, no atomics: the
+ *   same bits on every launch and in any batch.  g_d2 (B, N) and g_vd2 (B, V) may be NULL (zero); face, bary, resid, vpoint
+ *   and status are the forward's.  Every row is written.
+ * One launch each; no workspace, allocation or synchronisation.  Indices read from memory are range-checked: a face with a
+ * corner outside [0, V) is skipped, a recorded face outside [0, F) or point outside [0, N) adds nothing.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= V <= 2^24, 0 <= F <= 2^24, 0 <= N <= 2^24, B >= 0 (B = 0 is a
+ * no-op); no null pointer except counts, the cotangents and what only a NULL cotangent's term reads.                     */
+#define SMPLR_SCAN_NONFINITE 1
+int smplr_scan_p2m(const float *verts, const int32_t *faces, const float *points, const int32_t *counts, int B, int V, int F,
+                   int N, float *d2, int32_t *face, float *bary, float *resid, int32_t *status, void *stream);
+int smplr_scan_m2p(const float *verts, const float *points, const int32_t *counts, int B, int V, int N, float *vd2,
+                   int32_t *vpoint, int32_t *status, void *stream);
+int smplr_scan_bwd(const float *verts, const int32_t *faces, const float *points, const int32_t *face, const float *bary,
+                   const float *resid, const int32_t *vpoint, const int32_t *status, const float *g_d2, const float *g_vd2,
+                   int B, int V, int F, int N, float *dverts, void *stream);
+
 /* ---- prediction figures: predict.py:28-77 (_seg.png, _projects.png, _verts_overlay.png), train.py:283-290,
  * train_stage2_silhouette.py:318-329, predict_realtime.py:75-96; INTEGRATION.md 4h -------------------------------------
  * One launch each on the caller's stream; no workspace, no allocation, no synchronisation, no global atomics.  Colours

@@ -88,6 +88,9 @@ SIGNATURES = {
     "smplr_point_errors": (c_int, [P, P, I, I, I, I, P, P, P, P, P]),
     "smplr_mesh_measures": (c_int, [P, P, P, P, c_longlong, P, I, I, I, I, P, P, P, P, P, P, P, P]),
     "smplr_mesh_measures_bwd": (c_int, [P, P, P, P, I, P, P, c_longlong, P, P, P, P, P, P, P, I, I, I, I, P, P]),
+    "smplr_scan_p2m": (c_int, [P, P, P, P, I, I, I, I, P, P, P, P, P, P]),
+    "smplr_scan_m2p": (c_int, [P, P, P, I, I, I, P, P, P, P]),
+    "smplr_scan_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P]),
     "smplr_seg_colour": (c_int, [P, P, I, I, I, I, P, I, I, P, I, I, I, P, P]),
     "smplr_scatter_points": (c_int, [P, P, P, I, P, I, I, I, I, c_float, I, I, I, I, P, P, P]),
     "smplr_fit_step": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, c_float, P, P, I, I, I, c_float, c_float, c_float,

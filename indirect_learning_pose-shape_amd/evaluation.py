@@ -6,7 +6,8 @@ one writes them and the confusion kernel counts them.  `evaluate_3d` adds what `
 predicted and the ground-truth surface and joints in metres, raw and after translation, scale and Procrustes alignment
 (eval3d.py, csrc/eval3d.hip), and the pose-parameter MSE in the same pass; `evaluate_measurements` compares what a tape
 measure would: volume, surface area, extents and girths of the predicted and the ground-truth body (measure.py,
-csrc/measure.hip), which needs ground-truth parameters but no ground-truth vertices."""
+csrc/measure.hip), which needs ground-truth parameters but no ground-truth vertices; `evaluate_scans` compares with point clouds that have no
+correspondences at all (scan.py, csrc/scan.hip)."""
 from __future__ import annotations
 
 import torch
@@ -163,3 +164,46 @@ def evaluate_measurements(smpl_model, smpl_layer, batches, spec, tpose=True):
     mean = [(float(x) / cnt if cnt else float("nan")) for x in st[:5 + K]]
     return {"volume": mean[0], "area": mean[1], "extent": mean[2:5], "girth": mean[5:5 + K], "names": spec.names,
             "count": int(st[5 + K]), "nonfinite": int(st[6 + K])}
+
+
+@torch.no_grad()
+def evaluate_scans(smpl_model, smpl_layer, batches, topo):
+    """The loop of `evaluate_3d` against point clouds: batches: an iterable of (images, (points (N, Np, 3), counts (N,) or
+    None)) on the model's device, the points in the frame of smpl_layer's vertices (metres); `topo`: the layer's
+    `render.MeshTopology`.  Per batch one `scan.surface_distance(smpl_layer(smpl), topo, points, counts)`.
+    -> dict(scan_to_mesh = the mean over the used, finite points of their distance to the predicted surface, mesh_to_scan =
+    the mean over the vertices of their distance to the nearest used, finite point (both in metres, the square roots of the
+    op's d2 and vd2), points = points counted, vertices = vertices counted (those of meshes with a usable point), count =
+    meshes counted, nonfinite = meshes left out because they held a NaN or Inf).  Sums are float64 on the device; nothing
+    synchronises before the end."""
+    from .scan import surface_distance
+    state = None
+    was_training = smpl_model.training
+    smpl_model.eval()
+    try:
+        for images, gt in batches:
+            smpl = smpl_model(images)
+            dev = smpl.device
+            points, counts = gt if isinstance(gt, (tuple, list)) else (gt, None)
+            points = torch.as_tensor(points, device=dev).float()
+            n = int(smpl.shape[0])
+            if points.dim() != 3 or points.shape[0] != n or points.shape[2] != 3:
+                raise ValueError("points must be (N, Np, 3) with N = the batch's images")
+            if counts is not None:
+                counts = torch.as_tensor(counts).to(dev)
+            out = surface_distance(smpl_layer(smpl.float()).contiguous(), topo, points.contiguous(), counts)
+            ok = out["status"] == 0
+            hit, vhit = (out["face"] >= 0) & ok[:, None], (out["vpoint"] >= 0) & ok[:, None]
+            f64 = lambda d, m: torch.where(m, d, torch.zeros_like(d)).to(torch.float64).sqrt().sum()
+            n_ok = ok.sum().to(torch.float64)
+            row = torch.stack([f64(out["d2"], hit), hit.sum().to(torch.float64), f64(out["vd2"], vhit),
+                               vhit.sum().to(torch.float64), n_ok, n - n_ok])
+            state = row if state is None else state + row
+    finally:
+        smpl_model.train(was_training)
+    if state is None:
+        raise ValueError("evaluate_scans: no batches")
+    st = [float(x) for x in state.cpu()]
+    nan = float("nan")
+    return {"scan_to_mesh": st[0] / st[1] if st[1] else nan, "mesh_to_scan": st[2] / st[3] if st[3] else nan,
+            "points": int(st[1]), "vertices": int(st[3]), "count": int(st[4]), "nonfinite": int(st[5])}

@@ -618,6 +618,89 @@ class FitResult:
     group_size: int = 1
 
 
+def _stage_prior_weights(prior, prior_weights, stage_list):
+    """`fit`'s prior_weights (None, one triple, or a list of one triple per stage) -> one (3,) CPU tensor per stage; None
+    without a prior."""
+    if prior is None:
+        if prior_weights is not None:
+            raise ValueError("prior_weights without a prior")
+        return None
+    pw = (1.0, 1.0, 1.0) if prior_weights is None else prior_weights
+    per_stage = isinstance(pw, (list, tuple)) and len(pw) > 0 and all(np.ndim(w) == 1 for w in pw)
+    if per_stage and len(pw) != len(stage_list):
+        raise ValueError("prior_weights lists %d triples for %d stages" % (len(pw), len(stage_list)))
+    return [check_prior_weights(w) for w in (pw if per_stage else [pw] * len(stage_list))]
+
+
+def _run_fit(fitter, B, dev, x0_of, make_one, stage_list, stage_w, prior, grp, tie_m, smooth_w, kw, graph, graph_steps,
+             check_every, history):
+    """The loop `ParamFitter.fit` and `ScanFitter.fit` share, on checked arguments: the start from x0_of() (tied columns set
+    to their group's mean), the state, the stages with their column scales and prior weights, graph capture and replay, the
+    stop on `check_every`.  make_one(cs, kw) -> one(state, hist): one iteration (forward, backward, `fit_step`) of the
+    caller's data term; tie_m is None for ungrouped fits."""
+    P = fitter.P
+    total = sum(n for n, _ in stage_list)
+    G = max(1, int(graph_steps))
+    check_every = int(check_every)
+    grouped = tie_m is not None
+    with torch.cuda.device(dev):
+        x0 = x0_of()
+        if grouped:
+            tie_m = tie_m.to(dev)
+            if grp > 1:                                           # a group starts with one value in every tied column
+                mean = x0.reshape(B // grp, grp, P).mean(1, keepdim=True).expand(-1, grp, -1).reshape(B, P)
+                x0 = torch.where(tie_m.bool(), mean, x0)
+        state = FitState.new(x0)
+        hist = torch.full((total, B), float("nan"), dtype=torch.float32, device=dev) if history and total else None
+        cs = torch.ones(P, dtype=torch.float32, device=dev)
+        scales = [c.to(dev) for _, c in stage_list]
+        if grouped:
+            kw.update(group_size=grp, tie=tie_m, smooth=smooth_w.to(dev) if smooth_w is not None else None)
+        if prior is not None:
+            kw.update(fitter._prior_kw(prior, stage_w[0], dev))   # (the (3,) tensor is rewritten at each stage boundary)
+            stage_w = [w.to(dev) for w in stage_w]
+        one = make_one(cs, kw)
+        replay = None
+        if graph and B > 0 and any(n >= G for n, _ in stage_list):
+            # warm-up on a side stream and on a scratch state, then G iterations of the real state in one graph
+            scratch = state.clone()
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(3):
+                    one(scratch, None)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            g_ = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g_):
+                for _ in range(G):
+                    one(state, hist)
+            replay = g_.replay
+        done, stopped = 0, False
+        for si, ((n, _), sc) in enumerate(zip(stage_list, scales)):
+            cs.copy_(sc)
+            if prior is not None:
+                kw["prior_weights"].copy_(stage_w[si])
+            left = n
+            while left > 0 and not stopped:
+                if replay is not None and left >= G:
+                    replay()
+                    k = G
+                else:
+                    one(state, hist)
+                    k = 1
+                left -= k
+                if check_every > 0 and B > 0 and (done + k) // check_every > done // check_every:
+                    stopped = not bool(state.active.any())
+                done += k
+            if stopped:
+                break
+        torch.cuda.synchronize()
+    return FitResult(x=state.best_x, loss=state.best_loss, step=state.best_step, final_x=state.x, nonfinite=state.bad,
+                     active=state.active.bool(), history=hist[:done] if hist is not None else None, steps=done,
+                     state=state, group_size=grp)
+
+
 class ParamFitter:
     """Owns an `SMPLDecoder(outputs=(), loss=softmax_focal_loss(gamma, weight_classes)[, silh_loss=...])` and fits its
     input to label maps.  The defaults are those of decoder_loss_debugging.py:117-118: focal loss with gamma = 5, no class
@@ -748,76 +831,175 @@ class ParamFitter:
         if silh_labels is not None:
             silh_labels = self._labels(silh_labels, B, self.silh_wh, "silh_labels")
         stage_list = check_stages(stages, self.P, steps)
-        total = sum(n for n, _ in stage_list)
-        if prior is None and prior_weights is not None:
-            raise ValueError("prior_weights without a prior")
-        stage_w = None
-        if prior is not None:
-            pw = (1.0, 1.0, 1.0) if prior_weights is None else prior_weights
-            per_stage = isinstance(pw, (list, tuple)) and len(pw) > 0 and all(np.ndim(w) == 1 for w in pw)
-            if per_stage and len(pw) != len(stage_list):
-                raise ValueError("prior_weights lists %d triples for %d stages" % (len(pw), len(stage_list)))
-            stage_w = [check_prior_weights(w) for w in (pw if per_stage else [pw] * len(stage_list))]
-        G = max(1, int(graph_steps))
-        check_every = int(check_every)
-        with torch.cuda.device(dev):
-            x0 = self.initial(B, init, generator, dev)
-            if grouped:
-                tie_m = tie_m.to(dev)
-                if grp > 1:                                           # a group starts with one value in every tied column
-                    mean = x0.reshape(B // grp, grp, self.P).mean(1, keepdim=True).expand(-1, grp, -1).reshape(B, self.P)
-                    x0 = torch.where(tie_m.bool(), mean, x0)
-            state = FitState.new(x0)
-            hist = torch.full((total, B), float("nan"), dtype=torch.float32, device=dev) if history and total else None
+        stage_w = _stage_prior_weights(prior, prior_weights, stage_list)
+        kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
+                  mode=mode, patience=int(patience))
+
+        def make_one(cs, kw):
             N, Ns = W * W, self.silh_wh * self.silh_wh
             gout = torch.full((B, N), 1.0 / N, dtype=torch.float32, device=dev)
             sgout = torch.full((B, Ns), self.silh_weight / Ns, dtype=torch.float32, device=dev) if self.with_silhouette else None
-            cs = torch.ones(self.P, dtype=torch.float32, device=dev)
-            scales = [c.to(dev) for _, c in stage_list]
-            kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
-                      mode=mode, patience=int(patience))
-            if grouped:
-                kw.update(group_size=grp, tie=tie_m, smooth=smooth_w.to(dev) if smooth_w is not None else None)
-            if prior is not None:
-                kw.update(self._prior_kw(prior, stage_w[0], dev))     # (the (3,) tensor is rewritten at each stage boundary)
-                stage_w = [w.to(dev) for w in stage_w]
-            one = lambda st, h: self._iteration(st, labels, silh_labels, gout, sgout, cs, h, kw)
-            replay = None
-            if graph and B > 0 and any(n >= G for n, _ in stage_list):
-                # warm-up on a side stream and on a scratch state, then G iterations of the real state in one graph
-                scratch = state.clone()
-                side = torch.cuda.Stream(device=dev)
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(3):
-                        one(scratch, None)
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                g_ = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_):
-                    for _ in range(G):
-                        one(state, hist)
-                replay = g_.replay
-            done, stopped = 0, False
-            for si, ((n, _), sc) in enumerate(zip(stage_list, scales)):
-                cs.copy_(sc)
-                if prior is not None:
-                    kw["prior_weights"].copy_(stage_w[si])
-                left = n
-                while left > 0 and not stopped:
-                    if replay is not None and left >= G:
-                        replay()
-                        k = G
-                    else:
-                        one(state, hist)
-                        k = 1
-                    left -= k
-                    if check_every > 0 and B > 0 and (done + k) // check_every > done // check_every:
-                        stopped = not bool(state.active.any())
-                    done += k
-                if stopped:
-                    break
-            torch.cuda.synchronize()
-        return FitResult(x=state.best_x, loss=state.best_loss, step=state.best_step, final_x=state.x, nonfinite=state.bad,
-                         active=state.active.bool(), history=hist[:done] if hist is not None else None, steps=done,
-                         state=state, group_size=grp)
+            return lambda st, h: self._iteration(st, labels, silh_labels, gout, sgout, cs, h, kw)
+        return _run_fit(self, B, dev, lambda: self.initial(B, init, generator, dev), make_one, stage_list, stage_w, prior, grp,
+                        tie_m, smooth_w, kw, graph, graph_steps, check_every, history)
+
+
+def robust_rho(d2, sigma):
+    """Geman-McClure on squared distances: rho(d2) = sigma^2 d2 / (sigma^2 + d2) - d2 for small residuals, sigma^2 for
+    outliers (points of a scan that belong to no part of the body)."""
+    s2 = float(sigma) ** 2
+    return s2 * d2 / (s2 + d2)
+
+
+class ScanFitter:
+    """`ParamFitter`'s loop with `SMPLLayer -> s verts + t -> scan.surface_distance` in place of decoder + rasteriser: fits
+    x (B, 86) to point clouds without correspondences.  Columns 4..85 are pose and shape; the four columns the image fit
+    uses for the camera hold (s, t_x, t_y, t_z), the similarity that places the body in the scan's frame (`SMPLLayer`
+    ignores them).  Row b's data term is
+
+        L_b = sum_n rho(d2[b, n]) / counts[b]  +  m2p_weight sum_i rho(vd2[b, i]) / V
+
+    (rho = `robust_rho` with `sigma`, the identity when sigma is None), handed to `fit_step` as per-term losses: `loss` = the
+    p2m terms scaled by N / counts[b] (fit_step takes the mean over all N columns; the columns beyond counts[b] are 0),
+    `silh_loss` = the m2p terms with `silh_weight` = m2p_weight; the gradient comes from constant cotangents 1 / N and
+    m2p_weight / V.  A row without a usable point has an infinite m2p term and counts as a bad call (nothing changes).
+    Every launch of an iteration reproduces its bits, so two fits from the same start agree bit for bit.
+
+        fitter = ScanFitter(smpl_path, topo)                        # topo: a render.MeshTopology of the model's faces
+        r = fitter.fit(points, counts, init=x0, steps=200, lr=0.02, mode="torch", prior=prior, prior_weights=(1, 1, 1))
+    """
+
+    def __init__(self, smpl_path=None, topo=None, m2p_weight=1.0, sigma=None, directions=("p2m", "m2p")):
+        from .keras_smpl.batch_smpl import SMPLLayer
+        from .render import MeshTopology
+        self.layer = smpl_path if isinstance(smpl_path, SMPLLayer) else SMPLLayer(smpl_path)
+        self.num_cam = self.layer.num_cam
+        if self.num_cam != 4:
+            raise ValueError("ScanFitter keeps (s, t_x, t_y, t_z) in four leading columns")
+        self.P = self.num_cam + 82
+        if topo is None:
+            faces = self.layer._model.faces
+            if faces is None:
+                raise ValueError("this SMPL model carries no faces: pass topo=MeshTopology(faces, num_verts)")
+            topo = MeshTopology(faces, self.layer._model.num_verts)
+        if topo.num_verts != self.layer._model.num_verts:
+            raise ValueError("the topology has %d vertices, the model %d" % (topo.num_verts, self.layer._model.num_verts))
+        self.topo = topo
+        self.directions = (directions,) if isinstance(directions, str) else tuple(directions)
+        if not self.directions or any(d not in ("p2m", "m2p") for d in self.directions):
+            raise ValueError("directions must name \"p2m\" and / or \"m2p\"")
+        self.m2p_weight = float(m2p_weight)
+        if sigma is not None and not (math.isfinite(sigma) and sigma > 0):
+            raise ValueError("sigma must be > 0 (or None: no robust function)")
+        self.sigma = sigma
+
+    def initial(self, B, init=None, device=None):
+        """(B, 86) float32 start: None = scale 1, no shift, the mean pose and shape; a (B, 86) tensor as it is."""
+        from .smpl_model import mean86
+        if isinstance(init, torch.Tensor):
+            if tuple(init.shape) != (B, self.P):
+                raise ValueError("init must be (%d, %d), got %s" % (B, self.P, tuple(init.shape)))
+            x0 = init.detach().to(torch.float32)
+        elif init is None:
+            row = mean86(1.0)
+            row[:4] = (1.0, 0.0, 0.0, 0.0)
+            x0 = torch.as_tensor(row, dtype=torch.float32).repeat(B, 1)
+        else:
+            raise ValueError("init must be None or a (B, %d) tensor, got %r" % (self.P, init))
+        return x0.to(device) if device is not None else x0
+
+    def place(self, x):
+        """x (B, 86) -> the body in the scan's frame: x[:, 0] SMPLLayer(x) + x[:, 1:4]; differentiable."""
+        return x[:, 0, None, None] * self.layer(x) + x[:, None, 1:4]
+
+    def terms(self, x, points, counts=None):
+        """-> (p2m terms (B, N) scaled by N / counts or None, m2p terms (B, V) or None, the op's dict): what `fit_step`
+        gets as `loss` and `silh_loss`; differentiable in x."""
+        from .scan import surface_distance
+        out = surface_distance(self.place(x), self.topo, points, counts, self.directions)
+        rho = (lambda d: d) if self.sigma is None else (lambda d: robust_rho(d, self.sigma))
+        N = int(points.shape[1])
+        p2m = m2p = None
+        if "d2" in out:
+            p2m = rho(out["d2"])
+            if counts is not None:
+                p2m = p2m * (float(N) / counts.to(torch.float32).clamp(min=1.0))[:, None]
+        if "vd2" in out:
+            m2p = rho(out["vd2"])
+        return p2m, m2p, out
+
+    def _cotangents(self, B, N, dev):
+        V = self.topo.num_verts
+        gout = torch.full((B, N), 1.0 / N, dtype=torch.float32, device=dev) if "p2m" in self.directions else None
+        sgout = torch.full((B, V), 1.0 / V, dtype=torch.float32, device=dev) if "m2p" in self.directions else None
+        if gout is not None and sgout is not None:
+            sgout = sgout * self.m2p_weight
+        return gout, sgout
+
+    def _iteration(self, state, points, counts, gout, sgout, cs, hist, kw):
+        x = state.x.detach().requires_grad_(True)                 # (shares x's memory: the kernel updates it in place)
+        p2m, m2p, _ = self.terms(x, points, counts)
+        if p2m is not None and m2p is not None:
+            (g,) = torch.autograd.grad([p2m, m2p], [x], grad_outputs=[gout, sgout])
+            fit_step(state, g.contiguous(), p2m.detach().contiguous(), m2p.detach().contiguous(), self.m2p_weight, cs, hist, **kw)
+        else:
+            only, go = (p2m, gout) if p2m is not None else (m2p, sgout)
+            (g,) = torch.autograd.grad([only], [x], grad_outputs=[go])
+            fit_step(state, g.contiguous(), only.detach().contiguous(), None, 1.0, cs, hist, **kw)
+
+    _prior_kw = ParamFitter._prior_kw                             # (reads self.num_cam only)
+
+    def _points(self, points, counts):
+        if not isinstance(points, torch.Tensor) or points.dim() != 3 or points.shape[2] != 3 or points.shape[1] < 1:
+            raise ValueError("points must be a (B, N, 3) tensor with N >= 1")
+        points = _lib.require_cuda(points.detach(), "points")
+        B, N = int(points.shape[0]), int(points.shape[1])
+        if counts is not None:
+            c = torch.as_tensor(counts)
+            if tuple(c.shape) != (B,) or c.is_floating_point():
+                raise ValueError("counts must be (%d,) integers" % B)
+            if not c.is_cuda and B and (int(c.min()) < 0 or int(c.max()) > N):
+                raise ValueError("counts must lie in 0 .. %d" % N)
+            counts = c.to(device=points.device, dtype=torch.int32).contiguous()
+        return points, counts
+
+    def losses(self, x, points, counts=None, prior=None, prior_weights=None):
+        """Per-row loss (B,) of parameters x against the scans, reduced by the kernel of the loop (a call with a zero
+        gradient on a scratch state): the bits `fit` would record for x in its history."""
+        points, counts = self._points(points, counts)
+        x = _lib.require_cuda(x.detach(), "x")
+        B = int(x.shape[0])
+        with torch.no_grad(), torch.cuda.device(x.device):
+            p2m, m2p, _ = self.terms(x, points, counts)
+            hist = torch.empty((1, B), dtype=torch.float32, device=x.device)
+            first, second = (p2m, m2p) if p2m is not None else (m2p, None)
+            fit_step(FitState.new(x), torch.zeros_like(x), first.contiguous(), None if second is None else second.contiguous(),
+                     self.m2p_weight, None, hist, **self._prior_kw(prior, prior_weights, x.device))
+        return hist[0]
+
+    def fit(self, points, counts=None, init=None, steps=200, lr=1e-2, mode="torch", stages=None, patience=0, grad_scale=1.0,
+            graph=False, check_every=0, history=False, beta1=0.9, beta2=0.999, eps=KERAS_EPS, graph_steps=4, prior=None,
+            prior_weights=None, group_size=1, tie=("shape",), smooth=None):
+        """points (B, N, 3) fp32 on the HIP device, counts (B,) or None -> FitResult.  Everything else as `ParamFitter.fit`:
+        steps or stages = [(steps, column_scale), ...] (`column_scale(cam=...)` scales the (s, t) columns), patience,
+        grad_scale, graph / graph_steps, check_every, history, prior and prior_weights (one triple or one per stage),
+        group_size / tie / smooth for several scans of one body (tie="cam" would tie the placement as well)."""
+        if mode not in MODES:
+            raise ValueError("mode %r is none of %s" % (mode, MODES))
+        points, counts = self._points(points, counts)
+        B, N = int(points.shape[0]), int(points.shape[1])
+        dev = points.device
+        grp = check_group(B, group_size)
+        grouped = grp != 1 or smooth is not None
+        tie_m = check_tie(tie, self.P, self.num_cam) if grouped else None
+        smooth_w = check_smooth(smooth, self.P) if smooth is not None else None
+        stage_list = check_stages(stages, self.P, steps)
+        stage_w = _stage_prior_weights(prior, prior_weights, stage_list)
+        kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
+                  mode=mode, patience=int(patience))
+
+        def make_one(cs, kw):
+            gout, sgout = self._cotangents(B, N, dev)
+            return lambda st, h: self._iteration(st, points, counts, gout, sgout, cs, h, kw)
+        return _run_fit(self, B, dev, lambda: self.initial(B, init, dev), make_one, stage_list, stage_w, prior, grp, tie_m,
+                        smooth_w, kw, graph, graph_steps, check_every, history)
