@@ -43,6 +43,7 @@
 //                    definition a - h, tests/_fit_group_oracle.py restates it.
 //  prior_kernel      the prior alone (smplr_prior_energy): energy (B, 4) = E_pose, E_angle, E_shape unweighted and the
 //                    weighted E; comp (B) = k*; grad (B, P) or NULL, every column written.
+#include <tuple>
 #include "common.h"
 #include "prior_device.h"
 
@@ -355,16 +356,21 @@ __global__ __launch_bounds__(FT_T) void prior_kernel(const float *__restrict__ x
 }
 
 // the checks the two prior launchers share; 0 or SMPLR_EINVAL with the message set
-static int prior_args_check(const char *who, int P, int num_cam, const float *mean, const float *factor, const float *offset,
-                            const int32_t *angle_idx, const float *angle_scale, const float *shape_mean, int K, int A,
-                            const float *weights, bool launches) {
-  SMPLR_REQUIRE(num_cam >= 0 && P == num_cam + 82 && P <= FT_T, "%s: P=%d is not num_cam + 82 (num_cam=%d, 0..%d)", who, P,
-                num_cam, FT_T - 82);
-  SMPLR_REQUIRE(K >= 1 && K <= PR_KMAX, "%s: K=%d mixture components (1..%d)", who, K, PR_KMAX);
-  SMPLR_REQUIRE(A >= 0 && A <= PR_AMAX, "%s: A=%d angle terms (0..%d)", who, A, PR_AMAX);
-  SMPLR_REQUIRE(!launches || (mean && factor && offset && shape_mean && weights && (A == 0 || (angle_idx && angle_scale))),
+static int prior_args_check(const char *who, int P, const PriorArgs &pa, bool launches) {
+  SMPLR_REQUIRE(pa.num_cam >= 0 && P == pa.num_cam + 82 && P <= FT_T, "%s: P=%d is not num_cam + 82 (num_cam=%d, 0..%d)", who, P,
+                pa.num_cam, FT_T - 82);
+  SMPLR_REQUIRE(pa.K >= 1 && pa.K <= PR_KMAX, "%s: K=%d mixture components (1..%d)", who, pa.K, PR_KMAX);
+  SMPLR_REQUIRE(pa.A >= 0 && pa.A <= PR_AMAX, "%s: A=%d angle terms (0..%d)", who, pa.A, PR_AMAX);
+  SMPLR_REQUIRE(!launches || (pa.mean && pa.factor && pa.offset && pa.shape_mean && pa.weights &&
+                              (pa.A == 0 || (pa.angle_idx && pa.angle_scale))),
                 "%s: null pointer among the prior's arrays (angle_idx and angle_scale may be NULL with A = 0)", who);
   return 0;
+}
+
+// One launch of a fit kernel: `args` holds the kernel's arguments in its own order.
+template <auto Kernel, class Args>
+static void ft_launch(unsigned blocks, void *stream, const Args &args) {
+  std::apply([&](auto... a) { hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(FT_T), 0, as_stream(stream), a...); }, args);
 }
 
 }  // namespace smplr
@@ -374,18 +380,30 @@ int smplr_prior_energy(const float *x, int B, int P, int num_cam, const float *m
                        const float *weights, float *energy, int32_t *comp, float *grad, void *stream) {
   using namespace smplr;
   SMPLR_REQUIRE(B >= 0, "smplr_prior_energy: negative batch B=%d", B);
-  if (int rc = prior_args_check("smplr_prior_energy", P, num_cam, mean, factor, offset, angle_idx, angle_scale, shape_mean, K, A,
-                                weights, B > 0))
-    return rc;
+  const PriorArgs pa{mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, K, A, num_cam};
+  if (int rc = prior_args_check("smplr_prior_energy", P, pa, B > 0)) return rc;
   if (B == 0) return 0;
   SMPLR_REQUIRE(x && energy && comp, "smplr_prior_energy: null pointer (only grad may be NULL)");
-  const PriorArgs pa{mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, K, A, num_cam};
   hipLaunchKernelGGL(prior_kernel, dim3((unsigned)B), dim3(FT_T), 0, as_stream(stream), x, P, pa, energy, comp, grad);
   SMPLR_LAUNCH_CHECK("smplr_prior_energy");
   return 0;
 }
 
-// the operands smplr_fit_step_group adds
+// The operands every fit entry point has, in smplr_fit_step's order, and the ones smplr_fit_step_group adds.
+struct FitArgs {
+  float *x;
+  const float *g;
+  float *m, *v;
+  int32_t *t, *calls, *stall, *bad, *best_step;
+  uint8_t *active;
+  float *best_loss, *best_x;
+  const float *loss;       int N;                         // (B, N)
+  const float *silh_loss;  int Ns;  float silh_weight;    // (B, Ns) or NULL
+  const float *col_scale;                                 // (P)
+  float *history;          int H, B, P;                   // (H, B) or NULL
+  float lr, beta1, beta2, eps, gscale;
+  int mode, patience;
+};
 struct FitGroup {
   int G;
   const uint8_t *tie;
@@ -393,54 +411,36 @@ struct FitGroup {
 };
 
 // prior = NULL: smplr_fit_step; else smplr_fit_step_prior (`who` names the entry point in messages); grp: smplr_fit_step_group,
-// with or without a prior
-static int fit_step_launch(const char *who, float *x, const float *g, float *m, float *v, int32_t *t, int32_t *calls,
-                           int32_t *stall, int32_t *bad, int32_t *best_step, uint8_t *active, float *best_loss, float *best_x,
-                           const float *loss, int N, const float *silh_loss, int Ns, float silh_weight, const float *col_scale,
-                           float *history, int H, int B, int P, float lr, float beta1, float beta2, float eps, float gscale,
-                           int mode, int patience, const smplr::PriorArgs *prior, void *stream, const FitGroup *grp = nullptr) {
+// with or without a prior.  The kernels' common arguments are one tuple; the group's and the prior's are appended to it.
+static int fit_step_launch(const char *who, const FitArgs &a, const smplr::PriorArgs *prior, void *stream, const FitGroup *grp = nullptr) {
   using namespace smplr;
-  SMPLR_REQUIRE(B >= 0, "%s: negative batch B=%d", who, B);
+  SMPLR_REQUIRE(a.B >= 0, "%s: negative batch B=%d", who, a.B);
   SMPLR_REQUIRE(!grp || (grp->G >= 1 && grp->G <= FT_GMAX), "%s: G=%d rows per group (1..%d)", who, grp ? grp->G : 0, FT_GMAX);
-  SMPLR_REQUIRE(!grp || B % grp->G == 0, "%s: B=%d is no multiple of G=%d", who, B, grp ? grp->G : 0);
-  SMPLR_REQUIRE(P >= 1 && P <= FT_T, "%s: P=%d columns (1..%d)", who, P, FT_T);
-  SMPLR_REQUIRE(N >= 1, "%s: N=%d loss values per row (N >= 1)", who, N);
-  SMPLR_REQUIRE(!silh_loss || Ns >= 1, "%s: Ns=%d silhouette loss values per row (Ns >= 1)", who, Ns);
-  SMPLR_REQUIRE(mode == SMPLR_FIT_KERAS || mode == SMPLR_FIT_TORCH, "%s: mode %d is neither keras (0) nor torch (1)", who, mode);
-  SMPLR_REQUIRE(H >= 0 && patience >= 0, "%s: negative history length H=%d or patience %d", who, H, patience);
-  SMPLR_REQUIRE(!history || (long long)H * B < (1ll << 40), "%s: history of %d x %d entries", who, H, B);
-  SMPLR_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "%s: beta1, beta2 must lie in [0, 1)", who);
-  SMPLR_REQUIRE(eps >= 0.f && lr - lr == 0.f && gscale - gscale == 0.f && silh_weight - silh_weight == 0.f,
+  SMPLR_REQUIRE(!grp || a.B % grp->G == 0, "%s: B=%d is no multiple of G=%d", who, a.B, grp ? grp->G : 0);
+  SMPLR_REQUIRE(a.P >= 1 && a.P <= FT_T, "%s: P=%d columns (1..%d)", who, a.P, FT_T);
+  SMPLR_REQUIRE(a.N >= 1, "%s: N=%d loss values per row (N >= 1)", who, a.N);
+  SMPLR_REQUIRE(!a.silh_loss || a.Ns >= 1, "%s: Ns=%d silhouette loss values per row (Ns >= 1)", who, a.Ns);
+  SMPLR_REQUIRE(a.mode == SMPLR_FIT_KERAS || a.mode == SMPLR_FIT_TORCH, "%s: mode %d is neither keras (0) nor torch (1)", who, a.mode);
+  SMPLR_REQUIRE(a.H >= 0 && a.patience >= 0, "%s: negative history length H=%d or patience %d", who, a.H, a.patience);
+  SMPLR_REQUIRE(!a.history || (long long)a.H * a.B < (1ll << 40), "%s: history of %d x %d entries", who, a.H, a.B);
+  SMPLR_REQUIRE(a.beta1 >= 0.f && a.beta1 < 1.f && a.beta2 >= 0.f && a.beta2 < 1.f, "%s: beta1, beta2 must lie in [0, 1)", who);
+  SMPLR_REQUIRE(a.eps >= 0.f && a.lr - a.lr == 0.f && a.gscale - a.gscale == 0.f && a.silh_weight - a.silh_weight == 0.f,
                 "%s: eps must be >= 0 and lr, gscale, silh_weight finite", who);
-  if (prior)
-    if (int rc = prior_args_check(who, P, prior->num_cam, prior->mean, prior->factor, prior->offset, prior->angle_idx,
-                                  prior->angle_scale, prior->shape_mean, prior->K, prior->A, prior->weights, B > 0))
-      return rc;
-  if (B == 0) return 0;
-  SMPLR_REQUIRE(x && g && m && v && t && calls && stall && bad && best_step && active && best_loss && best_x && loss && col_scale,
+  if (int rc = prior ? prior_args_check(who, a.P, *prior, a.B > 0) : 0) return rc;
+  if (a.B == 0) return 0;
+  SMPLR_REQUIRE(a.x && a.g && a.m && a.v && a.t && a.calls && a.stall && a.bad && a.best_step && a.active && a.best_loss &&
+                    a.best_x && a.loss && a.col_scale,
                 "%s: null pointer (only silh_loss and history may be NULL)", who);
-  if (grp) {
-    SMPLR_REQUIRE(grp->tie, "%s: null pointer tie (only smooth, silh_loss, history and the prior's arrays together may be NULL)", who);
-    const dim3 grid((unsigned)(B / grp->G));
-    if (prior)
-      hipLaunchKernelGGL((fit_group_kernel<true, PriorArgs>), grid, dim3(FT_T), 0, as_stream(stream), x, g, m, v, t, calls, stall, bad,
-                         best_step, active, best_loss, best_x, loss, N, silh_loss, Ns, silh_weight, col_scale, history,
-                         history ? H : 0, B, P, lr, beta1, beta2, eps, gscale, mode, patience, grp->G, grp->tie, grp->smooth, *prior);
-    else
-      hipLaunchKernelGGL(fit_group_kernel<false>, grid, dim3(FT_T), 0, as_stream(stream), x, g, m, v, t, calls, stall, bad,
-                         best_step, active, best_loss, best_x, loss, N, silh_loss, Ns, silh_weight, col_scale, history,
-                         history ? H : 0, B, P, lr, beta1, beta2, eps, gscale, mode, patience, grp->G, grp->tie, grp->smooth);
-    SMPLR_LAUNCH_CHECK(who);
-    return 0;
-  }
-  if (prior)
-    hipLaunchKernelGGL((fit_step_kernel<true, PriorArgs>), dim3((unsigned)B), dim3(FT_T), 0, as_stream(stream), x, g, m, v, t, calls, stall,
-                       bad, best_step, active, best_loss, best_x, loss, N, silh_loss, Ns, silh_weight, col_scale, history,
-                       history ? H : 0, B, P, lr, beta1, beta2, eps, gscale, mode, patience, *prior);
-  else
-    hipLaunchKernelGGL(fit_step_kernel<false>, dim3((unsigned)B), dim3(FT_T), 0, as_stream(stream), x, g, m, v, t, calls, stall,
-                       bad, best_step, active, best_loss, best_x, loss, N, silh_loss, Ns, silh_weight, col_scale, history,
-                       history ? H : 0, B, P, lr, beta1, beta2, eps, gscale, mode, patience);
+  const auto args = std::make_tuple(a.x, a.g, a.m, a.v, a.t, a.calls, a.stall, a.bad, a.best_step, a.active, a.best_loss, a.best_x,
+                                    a.loss, a.N, a.silh_loss, a.Ns, a.silh_weight, a.col_scale, a.history, a.history ? a.H : 0, a.B,
+                                    a.P, a.lr, a.beta1, a.beta2, a.eps, a.gscale, a.mode, a.patience);
+  SMPLR_REQUIRE(!grp || grp->tie, "%s: null pointer tie (only smooth, silh_loss, history and the prior's arrays together may be NULL)", who);
+  const unsigned blocks = (unsigned)(grp ? a.B / grp->G : a.B);
+  const auto gx = grp ? std::make_tuple(grp->G, grp->tie, grp->smooth) : std::tuple<int, const uint8_t *, const float *>();
+  if (grp && prior) ft_launch<&fit_group_kernel<true, PriorArgs>>(blocks, stream, std::tuple_cat(args, gx, std::make_tuple(*prior)));
+  else if (grp) ft_launch<&fit_group_kernel<false>>(blocks, stream, std::tuple_cat(args, gx));
+  else if (prior) ft_launch<&fit_step_kernel<true, PriorArgs>>(blocks, stream, std::tuple_cat(args, std::make_tuple(*prior)));
+  else ft_launch<&fit_step_kernel<false>>(blocks, stream, args);
   SMPLR_LAUNCH_CHECK(who);
   return 0;
 }
@@ -449,9 +449,9 @@ int smplr_fit_step(float *x, const float *g, float *m, float *v, int32_t *t, int
                    int32_t *best_step, uint8_t *active, float *best_loss, float *best_x, const float *loss, int N,
                    const float *silh_loss, int Ns, float silh_weight, const float *col_scale, float *history, int H, int B,
                    int P, float lr, float beta1, float beta2, float eps, float gscale, int mode, int patience, void *stream) {
-  return fit_step_launch("smplr_fit_step", x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, N,
-                         silh_loss, Ns, silh_weight, col_scale, history, H, B, P, lr, beta1, beta2, eps, gscale, mode, patience,
-                         nullptr, stream);
+  const FitArgs a{x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, N, silh_loss, Ns, silh_weight,
+                  col_scale, history, H, B, P, lr, beta1, beta2, eps, gscale, mode, patience};
+  return fit_step_launch("smplr_fit_step", a, nullptr, stream);
 }
 
 int smplr_fit_step_prior(float *x, const float *g, float *m, float *v, int32_t *t, int32_t *calls, int32_t *stall, int32_t *bad,
@@ -460,10 +460,10 @@ int smplr_fit_step_prior(float *x, const float *g, float *m, float *v, int32_t *
                          int P, float lr, float beta1, float beta2, float eps, float gscale, int mode, int patience, int num_cam,
                          const float *mean, const float *factor, const float *offset, const int32_t *angle_idx,
                          const float *angle_scale, const float *shape_mean, int K, int A, const float *weights, void *stream) {
+  const FitArgs a{x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, N, silh_loss, Ns, silh_weight,
+                  col_scale, history, H, B, P, lr, beta1, beta2, eps, gscale, mode, patience};
   const smplr::PriorArgs pa{mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, K, A, num_cam};
-  return fit_step_launch("smplr_fit_step_prior", x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, N,
-                         silh_loss, Ns, silh_weight, col_scale, history, H, B, P, lr, beta1, beta2, eps, gscale, mode, patience,
-                         &pa, stream);
+  return fit_step_launch("smplr_fit_step_prior", a, &pa, stream);
 }
 
 int smplr_fit_step_group(float *x, const float *g, float *m, float *v, int32_t *t, int32_t *calls, int32_t *stall, int32_t *bad,
@@ -473,10 +473,10 @@ int smplr_fit_step_group(float *x, const float *g, float *m, float *v, int32_t *
                          const float *mean, const float *factor, const float *offset, const int32_t *angle_idx,
                          const float *angle_scale, const float *shape_mean, int K, int A, const float *weights, int G,
                          const uint8_t *tie, const float *smooth, void *stream) {
+  const FitArgs a{x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, N, silh_loss, Ns, silh_weight,
+                  col_scale, history, H, B, P, lr, beta1, beta2, eps, gscale, mode, patience};
   const bool prior = mean || factor || offset || angle_idx || angle_scale || shape_mean || weights;      // all NULL: no prior
   const smplr::PriorArgs pa{mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, K, A, num_cam};
   const FitGroup grp{G, tie, smooth};
-  return fit_step_launch("smplr_fit_step_group", x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, N,
-                         silh_loss, Ns, silh_weight, col_scale, history, H, B, P, lr, beta1, beta2, eps, gscale, mode, patience,
-                         prior ? &pa : nullptr, stream, &grp);
+  return fit_step_launch("smplr_fit_step_group", a, prior ? &pa : nullptr, stream, &grp);
 }

@@ -827,126 +827,155 @@ std::tuple<Tensor, Tensor> scatter_points_meta(const Tensor &proj, const c10::op
 // ---- fitting parameters to label maps (decoder_loss_debugging.py:103-125; csrc/fit.hip): one launch per iteration ------
 // state, all changed in place: x, m, v, best_x (B, P) fp32; t, calls, stall, bad, best_step (B) int32; active (B) uint8;
 // best_loss (B) fp32.  g (B, P); loss (B, N); silh_loss (B, Ns) or None; col_scale (P); history (H, B) or None.
-void fit_step_check(const Tensor &x, const Tensor &g, const Tensor &m, const Tensor &v, const Tensor &t, const Tensor &calls,
-                    const Tensor &stall, const Tensor &bad, const Tensor &best_step, const Tensor &active,
-                    const Tensor &best_loss, const Tensor &best_x, const Tensor &loss, const c10::optional<Tensor> &silh_loss,
-                    const Tensor &col_scale, const c10::optional<Tensor> &history, int64_t mode, int64_t patience) {
-  TORCH_CHECK(x.dim() == 2 && x.size(1) >= 1 && x.size(1) <= 256 && x.scalar_type() == at::kFloat, "x must be (B, P) float32, 1 <= P <= 256");
-  const int64_t B = x.size(0), P = x.size(1);
-  for (const auto &nt : {std::make_pair("g", &g), std::make_pair("m", &m), std::make_pair("v", &v), std::make_pair("best_x", &best_x)})
-    TORCH_CHECK(nt.second->sizes() == x.sizes() && nt.second->scalar_type() == at::kFloat, nt.first, " must be (B, P) float32 as x");
-  for (const auto &nt : {std::make_pair("t", &t), std::make_pair("calls", &calls), std::make_pair("stall", &stall),
-                         std::make_pair("bad", &bad), std::make_pair("best_step", &best_step)})
-    TORCH_CHECK(nt.second->dim() == 1 && nt.second->size(0) == B && nt.second->scalar_type() == at::kInt, nt.first, " must be (B,) int32");
-  TORCH_CHECK(active.dim() == 1 && active.size(0) == B && active.scalar_type() == at::kByte, "active must be (B,) uint8");
-  TORCH_CHECK(best_loss.dim() == 1 && best_loss.size(0) == B && best_loss.scalar_type() == at::kFloat, "best_loss must be (B,) float32");
-  TORCH_CHECK(loss.dim() == 2 && loss.size(0) == B && loss.size(1) >= 1 && loss.size(1) <= INT32_MAX && loss.scalar_type() == at::kFloat,
-              "loss must be (B, N) float32, N >= 1");
-  TORCH_CHECK(!silh_loss || (silh_loss->dim() == 2 && silh_loss->size(0) == B && silh_loss->size(1) >= 1 &&
-                             silh_loss->size(1) <= INT32_MAX && silh_loss->scalar_type() == at::kFloat),
-              "silh_loss must be (B, Ns) float32, Ns >= 1");
-  TORCH_CHECK(col_scale.dim() == 1 && col_scale.size(0) == P && col_scale.scalar_type() == at::kFloat, "col_scale must be (P,) float32");
-  TORCH_CHECK(!history || (history->dim() == 2 && history->size(1) == B && history->size(0) <= INT32_MAX &&
-                           history->scalar_type() == at::kFloat), "history must be (H, B) float32");
-  TORCH_CHECK(mode == 0 || mode == 1, "mode must be 0 (keras) or 1 (torch)");
-  TORCH_CHECK(patience >= 0 && patience <= INT32_MAX && B <= INT32_MAX, "patience must be >= 0");
-}
-// every operand of a fit_step / fit_step_prior launch: on the device, its dtype, contiguous, and on x's device
-void fit_step_on_device(const Tensor &x, const Tensor &g, const Tensor &m, const Tensor &v, const Tensor &t, const Tensor &calls,
-                        const Tensor &stall, const Tensor &bad, const Tensor &best_step, const Tensor &active,
-                        const Tensor &best_loss, const Tensor &best_x, const Tensor &loss, const c10::optional<Tensor> &silh_loss,
-                        const Tensor &col_scale, const c10::optional<Tensor> &history) {
-  dev_f32(x, "x"); dev_f32(g, "g"); dev_f32(m, "m"); dev_f32(v, "v"); dev_f32(best_x, "best_x"); dev_f32(best_loss, "best_loss");
-  dev_f32(loss, "loss"); dev_f32(col_scale, "col_scale");
-  dev_typed(t, at::kInt, "t"); dev_typed(calls, at::kInt, "calls"); dev_typed(stall, at::kInt, "stall");
-  dev_typed(bad, at::kInt, "bad"); dev_typed(best_step, at::kInt, "best_step"); dev_typed(active, at::kByte, "active");
-  if (silh_loss) dev_f32(*silh_loss, "silh_loss");
-  if (history) dev_f32(*history, "history");
-  const Tensor none;
-  same_device(x, {{"g", &g}, {"m", &m}, {"v", &v}, {"t", &t}, {"calls", &calls}, {"stall", &stall}, {"bad", &bad},
-                  {"best_step", &best_step}, {"active", &active}, {"best_loss", &best_loss}, {"best_x", &best_x}, {"loss", &loss},
-                  {"silh_loss", silh_loss ? &*silh_loss : &none}, {"col_scale", &col_scale}, {"history", history ? &*history : &none}});
-}
+// FitTensors: the 16 tensors of a fit call, by reference.  An op (and its meta function) builds one from its own parameters and
+// asks it for the checks and for the launch, so the list of operands the launchers share is spelled once, in `launch`.
+struct FitTensors {
+  const Tensor &x, &g, &m, &v, &t, &calls, &stall, &bad, &best_step, &active, &best_loss, &best_x, &loss;
+  const c10::optional<Tensor> &silh_loss;
+  const Tensor &col_scale;
+  const c10::optional<Tensor> &history;
+
+  void check(int64_t mode, int64_t patience) const {
+    TORCH_CHECK(x.dim() == 2 && x.size(1) >= 1 && x.size(1) <= 256 && x.scalar_type() == at::kFloat, "x must be (B, P) float32, 1 <= P <= 256");
+    const int64_t B = x.size(0), P = x.size(1);
+    for (const auto &nt : {std::make_pair("g", &g), std::make_pair("m", &m), std::make_pair("v", &v), std::make_pair("best_x", &best_x)})
+      TORCH_CHECK(nt.second->sizes() == x.sizes() && nt.second->scalar_type() == at::kFloat, nt.first, " must be (B, P) float32 as x");
+    for (const auto &nt : {std::make_pair("t", &t), std::make_pair("calls", &calls), std::make_pair("stall", &stall),
+                           std::make_pair("bad", &bad), std::make_pair("best_step", &best_step)})
+      TORCH_CHECK(nt.second->dim() == 1 && nt.second->size(0) == B && nt.second->scalar_type() == at::kInt, nt.first, " must be (B,) int32");
+    TORCH_CHECK(active.dim() == 1 && active.size(0) == B && active.scalar_type() == at::kByte, "active must be (B,) uint8");
+    TORCH_CHECK(best_loss.dim() == 1 && best_loss.size(0) == B && best_loss.scalar_type() == at::kFloat, "best_loss must be (B,) float32");
+    TORCH_CHECK(loss.dim() == 2 && loss.size(0) == B && loss.size(1) >= 1 && loss.size(1) <= INT32_MAX && loss.scalar_type() == at::kFloat,
+                "loss must be (B, N) float32, N >= 1");
+    TORCH_CHECK(!silh_loss || (silh_loss->dim() == 2 && silh_loss->size(0) == B && silh_loss->size(1) >= 1 &&
+                               silh_loss->size(1) <= INT32_MAX && silh_loss->scalar_type() == at::kFloat),
+                "silh_loss must be (B, Ns) float32, Ns >= 1");
+    TORCH_CHECK(col_scale.dim() == 1 && col_scale.size(0) == P && col_scale.scalar_type() == at::kFloat, "col_scale must be (P,) float32");
+    TORCH_CHECK(!history || (history->dim() == 2 && history->size(1) == B && history->size(0) <= INT32_MAX &&
+                             history->scalar_type() == at::kFloat), "history must be (H, B) float32");
+    TORCH_CHECK(mode == 0 || mode == 1, "mode must be 0 (keras) or 1 (torch)");
+    TORCH_CHECK(patience >= 0 && patience <= INT32_MAX && B <= INT32_MAX, "patience must be >= 0");
+  }
+  // every operand of a launch: on the device, its dtype, contiguous, and on x's device
+  void on_device() const {
+    dev_f32(x, "x"); dev_f32(g, "g"); dev_f32(m, "m"); dev_f32(v, "v"); dev_f32(best_x, "best_x"); dev_f32(best_loss, "best_loss");
+    dev_f32(loss, "loss"); dev_f32(col_scale, "col_scale");
+    dev_typed(t, at::kInt, "t"); dev_typed(calls, at::kInt, "calls"); dev_typed(stall, at::kInt, "stall");
+    dev_typed(bad, at::kInt, "bad"); dev_typed(best_step, at::kInt, "best_step"); dev_typed(active, at::kByte, "active");
+    if (silh_loss) dev_f32(*silh_loss, "silh_loss");
+    if (history) dev_f32(*history, "history");
+    const Tensor none;
+    same_device(x, {{"g", &g}, {"m", &m}, {"v", &v}, {"t", &t}, {"calls", &calls}, {"stall", &stall}, {"bad", &bad},
+                    {"best_step", &best_step}, {"active", &active}, {"best_loss", &best_loss}, {"best_x", &best_x}, {"loss", &loss},
+                    {"silh_loss", silh_loss ? &*silh_loss : &none}, {"col_scale", &col_scale}, {"history", history ? &*history : &none}});
+  }
+  // launcher(the operands every launcher starts with, extra..., stream); `extra`: a tuple of what follows patience in this one
+  template <class Launcher, class Extra>
+  void launch(Launcher launcher, const char *name, double lr, double beta1, double beta2, double eps, double gscale, double silh_weight,
+              int64_t mode, int64_t patience, const Extra &extra) const {
+    const bool hist = history && history->numel() > 0;
+    std::apply([&](auto... e) {
+      ok(launcher(x.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), t.data_ptr<int32_t>(),
+                  calls.data_ptr<int32_t>(), stall.data_ptr<int32_t>(), bad.data_ptr<int32_t>(), best_step.data_ptr<int32_t>(),
+                  active.data_ptr<uint8_t>(), best_loss.data_ptr<float>(), best_x.data_ptr<float>(), loss.data_ptr<float>(),
+                  (int)loss.size(1), silh_loss ? silh_loss->data_ptr<float>() : nullptr, silh_loss ? (int)silh_loss->size(1) : 0,
+                  (float)silh_weight, col_scale.data_ptr<float>(), hist ? history->data_ptr<float>() : nullptr,
+                  hist ? (int)history->size(0) : 0, (int)x.size(0), (int)x.size(1), (float)lr, (float)beta1, (float)beta2, (float)eps,
+                  (float)gscale, (int)mode, (int)patience, e..., cur_stream()),
+         name);
+    }, extra);
+  }
+};
 void fit_step(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
               Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
               const c10::optional<Tensor> &silh_loss, const Tensor &col_scale, c10::optional<Tensor> history, double lr,
               double beta1, double beta2, double eps, double gscale, double silh_weight, int64_t mode, int64_t patience) {
-  fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
-                 patience);
-  fit_step_on_device(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history);
+  const FitTensors f{x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history};
+  f.check(mode, patience);
+  f.on_device();
   DeviceGuard guard(x.device());
   if (x.size(0) == 0) return;
-  const bool hist = history && history->numel() > 0;
-  ok(smplr_fit_step(x.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), t.data_ptr<int32_t>(),
-                    calls.data_ptr<int32_t>(), stall.data_ptr<int32_t>(), bad.data_ptr<int32_t>(), best_step.data_ptr<int32_t>(),
-                    active.data_ptr<uint8_t>(), best_loss.data_ptr<float>(), best_x.data_ptr<float>(), loss.data_ptr<float>(),
-                    (int)loss.size(1), silh_loss ? silh_loss->data_ptr<float>() : nullptr, silh_loss ? (int)silh_loss->size(1) : 0,
-                    (float)silh_weight, col_scale.data_ptr<float>(), hist ? history->data_ptr<float>() : nullptr,
-                    hist ? (int)history->size(0) : 0, (int)x.size(0), (int)x.size(1), (float)lr, (float)beta1, (float)beta2, (float)eps,
-                    (float)gscale, (int)mode, (int)patience, cur_stream()),
-     "smplr_fit_step");
+  f.launch(smplr_fit_step, "smplr_fit_step", lr, beta1, beta2, eps, gscale, silh_weight, mode, patience, std::make_tuple());
 }
 void fit_step_meta(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
                    Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
                    const c10::optional<Tensor> &silh_loss, const Tensor &col_scale, c10::optional<Tensor> history, double, double,
                    double, double, double, double, int64_t mode, int64_t patience) {
-  fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
-                 patience);
+  FitTensors{x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history}.check(mode, patience);
 }
 
 // ---- pose and shape priors (csrc/prior_device.h): the prior alone, and fit_step with the prior inside the same launch ----
 // mean (K, 69), factor (K, 69, 69), offset (K), angle_idx (A) int32, angle_scale (A), shape_mean (10), weights (3): fp32.
-void prior_check(const Tensor &x, const Tensor &mean, const Tensor &factor, const Tensor &offset, const Tensor &angle_idx,
-                 const Tensor &angle_scale, const Tensor &shape_mean, const Tensor &weights, int64_t num_cam) {
-  TORCH_CHECK(x.dim() == 2 && x.scalar_type() == at::kFloat && num_cam >= 0 && num_cam <= 256 - 82 && x.size(1) == num_cam + 82,
-              "x must be (B, num_cam + 82) float32 with num_cam in 0..174");
-  TORCH_CHECK(x.size(0) <= INT32_MAX, "too many rows");
-  TORCH_CHECK(mean.dim() == 2 && mean.size(0) >= 1 && mean.size(0) <= 16 && mean.size(1) == 69 && mean.scalar_type() == at::kFloat,
-              "mean must be (K, 69) float32, 1 <= K <= 16");
-  const int64_t K = mean.size(0);
-  TORCH_CHECK(factor.dim() == 3 && factor.size(0) == K && factor.size(1) == 69 && factor.size(2) == 69 &&
-                  factor.scalar_type() == at::kFloat, "factor must be (K, 69, 69) float32");
-  TORCH_CHECK(offset.dim() == 1 && offset.size(0) == K && offset.scalar_type() == at::kFloat, "offset must be (K,) float32");
-  TORCH_CHECK(angle_idx.dim() == 1 && angle_idx.size(0) <= 16 && angle_idx.scalar_type() == at::kInt,
-              "angle_idx must be (A,) int32, A <= 16");
-  TORCH_CHECK(angle_scale.dim() == 1 && angle_scale.size(0) == angle_idx.size(0) && angle_scale.scalar_type() == at::kFloat,
-              "angle_scale must be (A,) float32");
-  TORCH_CHECK(shape_mean.dim() == 1 && shape_mean.size(0) == 10 && shape_mean.scalar_type() == at::kFloat,
-              "shape_mean must be (10,) float32");
-  TORCH_CHECK(weights.dim() == 1 && weights.size(0) == 3 && weights.scalar_type() == at::kFloat, "weights must be (3,) float32");
-}
-void prior_on_device(const Tensor &x, const Tensor &mean, const Tensor &factor, const Tensor &offset, const Tensor &angle_idx,
-                     const Tensor &angle_scale, const Tensor &shape_mean, const Tensor &weights) {
-  dev_f32(mean, "mean"); dev_f32(factor, "factor"); dev_f32(offset, "offset"); dev_typed(angle_idx, at::kInt, "angle_idx");
-  dev_f32(angle_scale, "angle_scale"); dev_f32(shape_mean, "shape_mean"); dev_f32(weights, "weights");
-  same_device(x, {{"mean", &mean}, {"factor", &factor}, {"offset", &offset}, {"angle_idx", &angle_idx},
-                  {"angle_scale", &angle_scale}, {"shape_mean", &shape_mean}, {"weights", &weights}});
-}
+// PriorTensors: the seven, from an op's Tensor or Tensor? parameters - all given, or (fit_step_group) none.
+struct PriorTensors {
+  const Tensor *mean, *factor, *offset, *angle_idx, *angle_scale, *shape_mean, *weights;
+  static const Tensor *at(const Tensor &t) { return &t; }
+  static const Tensor *at(const c10::optional<Tensor> &t) { return t ? &*t : nullptr; }
+  template <class T>
+  PriorTensors(const T &mean, const T &factor, const T &offset, const T &angle_idx, const T &angle_scale, const T &shape_mean,
+               const T &weights)
+      : mean(at(mean)), factor(at(factor)), offset(at(offset)), angle_idx(at(angle_idx)), angle_scale(at(angle_scale)),
+        shape_mean(at(shape_mean)), weights(at(weights)) {}
+  int given() const { return !!mean + !!factor + !!offset + !!angle_idx + !!angle_scale + !!shape_mean + !!weights; }
+
+  void check(const Tensor &x, int64_t num_cam) const {
+    TORCH_CHECK(x.dim() == 2 && x.scalar_type() == at::kFloat && num_cam >= 0 && num_cam <= 256 - 82 && x.size(1) == num_cam + 82,
+                "x must be (B, num_cam + 82) float32 with num_cam in 0..174");
+    TORCH_CHECK(x.size(0) <= INT32_MAX, "too many rows");
+    TORCH_CHECK(mean->dim() == 2 && mean->size(0) >= 1 && mean->size(0) <= 16 && mean->size(1) == 69 && mean->scalar_type() == at::kFloat,
+                "mean must be (K, 69) float32, 1 <= K <= 16");
+    const int64_t K = mean->size(0);
+    TORCH_CHECK(factor->dim() == 3 && factor->size(0) == K && factor->size(1) == 69 && factor->size(2) == 69 &&
+                    factor->scalar_type() == at::kFloat, "factor must be (K, 69, 69) float32");
+    TORCH_CHECK(offset->dim() == 1 && offset->size(0) == K && offset->scalar_type() == at::kFloat, "offset must be (K,) float32");
+    TORCH_CHECK(angle_idx->dim() == 1 && angle_idx->size(0) <= 16 && angle_idx->scalar_type() == at::kInt,
+                "angle_idx must be (A,) int32, A <= 16");
+    TORCH_CHECK(angle_scale->dim() == 1 && angle_scale->size(0) == angle_idx->size(0) && angle_scale->scalar_type() == at::kFloat,
+                "angle_scale must be (A,) float32");
+    TORCH_CHECK(shape_mean->dim() == 1 && shape_mean->size(0) == 10 && shape_mean->scalar_type() == at::kFloat,
+                "shape_mean must be (10,) float32");
+    TORCH_CHECK(weights->dim() == 1 && weights->size(0) == 3 && weights->scalar_type() == at::kFloat, "weights must be (3,) float32");
+  }
+  void on_device(const Tensor &x) const {
+    dev_f32(*mean, "mean"); dev_f32(*factor, "factor"); dev_f32(*offset, "offset"); dev_typed(*angle_idx, at::kInt, "angle_idx");
+    dev_f32(*angle_scale, "angle_scale"); dev_f32(*shape_mean, "shape_mean"); dev_f32(*weights, "weights");
+    same_device(x, {{"mean", mean}, {"factor", factor}, {"offset", offset}, {"angle_idx", angle_idx},
+                    {"angle_scale", angle_scale}, {"shape_mean", shape_mean}, {"weights", weights}});
+  }
+  // the launchers' ten arguments from num_cam to weights: angle_idx and angle_scale NULL with A = 0; no prior: NULL and 0
+  auto args(int64_t num_cam) const {
+    const int64_t A = mean ? angle_idx->size(0) : 0;
+    return std::make_tuple((int)num_cam, mean ? mean->data_ptr<float>() : nullptr, mean ? factor->data_ptr<float>() : nullptr,
+                           mean ? offset->data_ptr<float>() : nullptr, A ? angle_idx->data_ptr<int32_t>() : nullptr,
+                           A ? angle_scale->data_ptr<float>() : nullptr, mean ? shape_mean->data_ptr<float>() : nullptr,
+                           mean ? (int)mean->size(0) : 0, (int)A, mean ? weights->data_ptr<float>() : nullptr);
+  }
+};
 // -> energy (B, 4) = E_pose, E_angle, E_shape, E; comp (B) int32; grad (B, P), or (0, P) with with_grad = False
 std::tuple<Tensor, Tensor, Tensor> prior_energy(const Tensor &x, const Tensor &mean, const Tensor &factor, const Tensor &offset,
                                                 const Tensor &angle_idx, const Tensor &angle_scale, const Tensor &shape_mean,
                                                 const Tensor &weights, int64_t num_cam, bool with_grad) {
-  prior_check(x, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, num_cam);
+  const PriorTensors p(mean, factor, offset, angle_idx, angle_scale, shape_mean, weights);
+  p.check(x, num_cam);
   dev_f32(x, "x");
-  prior_on_device(x, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights);
+  p.on_device(x);
   DeviceGuard guard(x.device());
-  const int64_t B = x.size(0), P = x.size(1), A = angle_idx.size(0);
+  const int64_t B = x.size(0), P = x.size(1);
   Tensor energy = at::empty({B, 4}, x.options()), comp = at::empty({B}, x.options().dtype(at::kInt));
   Tensor grad = at::empty({with_grad ? B : 0, P}, x.options());
   if (B == 0) return {energy, comp, grad};
-  ok(smplr_prior_energy(x.data_ptr<float>(), (int)B, (int)P, (int)num_cam, mean.data_ptr<float>(), factor.data_ptr<float>(),
-                        offset.data_ptr<float>(), A ? angle_idx.data_ptr<int32_t>() : nullptr,
-                        A ? angle_scale.data_ptr<float>() : nullptr, shape_mean.data_ptr<float>(), (int)mean.size(0), (int)A,
-                        weights.data_ptr<float>(), energy.data_ptr<float>(), comp.data_ptr<int32_t>(),
-                        with_grad ? grad.data_ptr<float>() : nullptr, cur_stream()),
-     "smplr_prior_energy");
+  std::apply([&](auto... pa) {
+    ok(smplr_prior_energy(x.data_ptr<float>(), (int)B, (int)P, pa..., energy.data_ptr<float>(), comp.data_ptr<int32_t>(),
+                          with_grad ? grad.data_ptr<float>() : nullptr, cur_stream()),
+       "smplr_prior_energy");
+  }, p.args(num_cam));
   return {energy, comp, grad};
 }
 std::tuple<Tensor, Tensor, Tensor> prior_energy_meta(const Tensor &x, const Tensor &mean, const Tensor &factor,
                                                      const Tensor &offset, const Tensor &angle_idx, const Tensor &angle_scale,
                                                      const Tensor &shape_mean, const Tensor &weights, int64_t num_cam,
                                                      bool with_grad) {
-  prior_check(x, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, num_cam);
+  PriorTensors(mean, factor, offset, angle_idx, angle_scale, shape_mean, weights).check(x, num_cam);
   const int64_t B = x.size(0);
   return {at::empty({B, 4}, x.options()), at::empty({B}, x.options().dtype(at::kInt)),
           at::empty({with_grad ? B : 0, x.size(1)}, x.options())};
@@ -957,27 +986,15 @@ void fit_step_prior(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t,
                     const Tensor &mean, const Tensor &factor, const Tensor &offset, const Tensor &angle_idx,
                     const Tensor &angle_scale, const Tensor &shape_mean, const Tensor &weights, double lr, double beta1,
                     double beta2, double eps, double gscale, double silh_weight, int64_t mode, int64_t patience, int64_t num_cam) {
-  fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
-                 patience);
-  prior_check(x, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, num_cam);
-  fit_step_on_device(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history);
-  prior_on_device(x, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights);
+  const FitTensors f{x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history};
+  const PriorTensors p(mean, factor, offset, angle_idx, angle_scale, shape_mean, weights);
+  f.check(mode, patience);
+  p.check(x, num_cam);
+  f.on_device();
+  p.on_device(x);
   DeviceGuard guard(x.device());
   if (x.size(0) == 0) return;
-  const bool hist = history && history->numel() > 0;
-  const int64_t A = angle_idx.size(0);
-  ok(smplr_fit_step_prior(x.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), t.data_ptr<int32_t>(),
-                          calls.data_ptr<int32_t>(), stall.data_ptr<int32_t>(), bad.data_ptr<int32_t>(),
-                          best_step.data_ptr<int32_t>(), active.data_ptr<uint8_t>(), best_loss.data_ptr<float>(),
-                          best_x.data_ptr<float>(), loss.data_ptr<float>(), (int)loss.size(1),
-                          silh_loss ? silh_loss->data_ptr<float>() : nullptr, silh_loss ? (int)silh_loss->size(1) : 0,
-                          (float)silh_weight, col_scale.data_ptr<float>(), hist ? history->data_ptr<float>() : nullptr,
-                          hist ? (int)history->size(0) : 0, (int)x.size(0), (int)x.size(1), (float)lr, (float)beta1, (float)beta2,
-                          (float)eps, (float)gscale, (int)mode, (int)patience, (int)num_cam, mean.data_ptr<float>(),
-                          factor.data_ptr<float>(), offset.data_ptr<float>(), A ? angle_idx.data_ptr<int32_t>() : nullptr,
-                          A ? angle_scale.data_ptr<float>() : nullptr, shape_mean.data_ptr<float>(), (int)mean.size(0), (int)A,
-                          weights.data_ptr<float>(), cur_stream()),
-     "smplr_fit_step_prior");
+  f.launch(smplr_fit_step_prior, "smplr_fit_step_prior", lr, beta1, beta2, eps, gscale, silh_weight, mode, patience, p.args(num_cam));
 }
 void fit_step_prior_meta(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
                          Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
@@ -985,28 +1002,24 @@ void fit_step_prior_meta(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tenso
                          const Tensor &mean, const Tensor &factor, const Tensor &offset, const Tensor &angle_idx,
                          const Tensor &angle_scale, const Tensor &shape_mean, const Tensor &weights, double, double, double,
                          double, double, double, int64_t mode, int64_t patience, int64_t num_cam) {
-  fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
-                 patience);
-  prior_check(x, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, num_cam);
+  FitTensors{x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history}.check(mode, patience);
+  PriorTensors(mean, factor, offset, angle_idx, angle_scale, shape_mean, weights).check(x, num_cam);
 }
 
 // ---- rows in groups of `group_size` (views or frames of one body): tie (P) uint8, smooth (P) fp32 or None; the prior's seven
 // tensors all given or all None (smplr_fit_step_group) -------------------------------------------------------------------
-bool fit_step_group_check(const Tensor &x, const Tensor &tie, const c10::optional<Tensor> &smooth, const c10::optional<Tensor> &mean,
-                          const c10::optional<Tensor> &factor, const c10::optional<Tensor> &offset,
-                          const c10::optional<Tensor> &angle_idx, const c10::optional<Tensor> &angle_scale,
-                          const c10::optional<Tensor> &shape_mean, const c10::optional<Tensor> &weights, int64_t group_size,
-                          int64_t num_cam) {
+bool fit_step_group_check(const Tensor &x, const Tensor &tie, const c10::optional<Tensor> &smooth, const PriorTensors &p,
+                          int64_t group_size, int64_t num_cam) {
   const int64_t B = x.size(0), P = x.size(1);
   TORCH_CHECK(group_size >= 1 && group_size <= 16, "group_size must lie in 1..16");
   TORCH_CHECK(B % group_size == 0, "the batch must be a multiple of group_size");
   TORCH_CHECK(tie.dim() == 1 && tie.size(0) == P && tie.scalar_type() == at::kByte, "tie must be (P,) uint8");
   TORCH_CHECK(!smooth || (smooth->dim() == 1 && smooth->size(0) == P && smooth->scalar_type() == at::kFloat),
               "smooth must be (P,) float32");
-  const int given = !!mean + !!factor + !!offset + !!angle_idx + !!angle_scale + !!shape_mean + !!weights;
+  const int given = p.given();
   TORCH_CHECK(given == 0 || given == 7, "the prior's tensors (mean, factor, offset, angle_idx, angle_scale, shape_mean, weights) "
                                         "go together: all or none");
-  if (given) prior_check(x, *mean, *factor, *offset, *angle_idx, *angle_scale, *shape_mean, *weights, num_cam);
+  if (given) p.check(x, num_cam);
   return given != 0;
 }
 void fit_step_group(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
@@ -1018,34 +1031,21 @@ void fit_step_group(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t,
                     const c10::optional<Tensor> &shape_mean, const c10::optional<Tensor> &weights, int64_t group_size, double lr,
                     double beta1, double beta2, double eps, double gscale, double silh_weight, int64_t mode, int64_t patience,
                     int64_t num_cam) {
-  fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
-                 patience);
-  const bool prior = fit_step_group_check(x, tie, smooth, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights,
-                                          group_size, num_cam);
-  fit_step_on_device(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history);
+  const FitTensors f{x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history};
+  const PriorTensors p(mean, factor, offset, angle_idx, angle_scale, shape_mean, weights);
+  f.check(mode, patience);
+  const bool prior = fit_step_group_check(x, tie, smooth, p, group_size, num_cam);
+  f.on_device();
   dev_typed(tie, at::kByte, "tie");
   if (smooth) dev_f32(*smooth, "smooth");
   const Tensor none;
   same_device(x, {{"tie", &tie}, {"smooth", smooth ? &*smooth : &none}});
-  if (prior) prior_on_device(x, *mean, *factor, *offset, *angle_idx, *angle_scale, *shape_mean, *weights);
+  if (prior) p.on_device(x);
   DeviceGuard guard(x.device());
   if (x.size(0) == 0) return;
-  const bool hist = history && history->numel() > 0;
-  const int64_t A = prior ? angle_idx->size(0) : 0;
-  ok(smplr_fit_step_group(x.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), t.data_ptr<int32_t>(),
-                          calls.data_ptr<int32_t>(), stall.data_ptr<int32_t>(), bad.data_ptr<int32_t>(),
-                          best_step.data_ptr<int32_t>(), active.data_ptr<uint8_t>(), best_loss.data_ptr<float>(),
-                          best_x.data_ptr<float>(), loss.data_ptr<float>(), (int)loss.size(1),
-                          silh_loss ? silh_loss->data_ptr<float>() : nullptr, silh_loss ? (int)silh_loss->size(1) : 0,
-                          (float)silh_weight, col_scale.data_ptr<float>(), hist ? history->data_ptr<float>() : nullptr,
-                          hist ? (int)history->size(0) : 0, (int)x.size(0), (int)x.size(1), (float)lr, (float)beta1, (float)beta2,
-                          (float)eps, (float)gscale, (int)mode, (int)patience, (int)num_cam,
-                          prior ? mean->data_ptr<float>() : nullptr, prior ? factor->data_ptr<float>() : nullptr,
-                          prior ? offset->data_ptr<float>() : nullptr, A ? angle_idx->data_ptr<int32_t>() : nullptr,
-                          A ? angle_scale->data_ptr<float>() : nullptr, prior ? shape_mean->data_ptr<float>() : nullptr,
-                          prior ? (int)mean->size(0) : 0, (int)A, prior ? weights->data_ptr<float>() : nullptr, (int)group_size,
-                          tie.data_ptr<uint8_t>(), smooth ? smooth->data_ptr<float>() : nullptr, cur_stream()),
-     "smplr_fit_step_group");
+  f.launch(smplr_fit_step_group, "smplr_fit_step_group", lr, beta1, beta2, eps, gscale, silh_weight, mode, patience,
+           std::tuple_cat(p.args(num_cam), std::make_tuple((int)group_size, tie.data_ptr<uint8_t>(),
+                                                           smooth ? smooth->data_ptr<float>() : nullptr)));
 }
 void fit_step_group_meta(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
                          Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
@@ -1055,9 +1055,9 @@ void fit_step_group_meta(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tenso
                          const c10::optional<Tensor> &angle_idx, const c10::optional<Tensor> &angle_scale,
                          const c10::optional<Tensor> &shape_mean, const c10::optional<Tensor> &weights, int64_t group_size, double,
                          double, double, double, double, double, int64_t mode, int64_t patience, int64_t num_cam) {
-  fit_step_check(x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history, mode,
-                 patience);
-  fit_step_group_check(x, tie, smooth, mean, factor, offset, angle_idx, angle_scale, shape_mean, weights, group_size, num_cam);
+  FitTensors{x, g, m, v, t, calls, stall, bad, best_step, active, best_loss, best_x, loss, silh_loss, col_scale, history}.check(mode, patience);
+  fit_step_group_check(x, tie, smooth, PriorTensors(mean, factor, offset, angle_idx, angle_scale, shape_mean, weights), group_size,
+                       num_cam);
 }
 
 // ---- body measurements (csrc/measure.hip): verts (B, V, 3), faces (F, 3) int32, face_part (F) uint8, planes (K, 4) or

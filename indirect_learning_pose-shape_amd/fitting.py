@@ -447,6 +447,15 @@ def _prior_operands(prior, weights, x):
     return prior, w
 
 
+def _prior_args(prior, w, num_cam):
+    """The ten arguments every launcher takes from num_cam to weights, of `_prior_operands`' pair (the caller holds on to w
+    until it has launched); prior None: no prior, all NULL and 0."""
+    if prior is None:
+        return (int(num_cam), None, None, None, None, None, None, 0, 0, None)
+    return (int(num_cam), ptr(prior.mean), ptr(prior.factor), ptr(prior.offset), ptr(prior.angle_idx) if prior.A else None,
+            ptr(prior.angle_scale) if prior.A else None, ptr(prior.shape_mean), prior.K, prior.A, ptr(w))
+
+
 @_lib.on_device
 def prior_terms(x, prior, weights=None, num_cam=4, with_grad=True):
     """One smplr_prior_energy launch: x (B, num_cam + 82) -> dict(energy (B, 4) = E_pose, E_angle, E_shape unweighted and the
@@ -459,10 +468,8 @@ def prior_terms(x, prior, weights=None, num_cam=4, with_grad=True):
     energy = torch.empty((B, 4), dtype=torch.float32, device=x.device)
     comp = torch.empty((B,), dtype=torch.int32, device=x.device)
     grad = torch.empty((B, P), dtype=torch.float32, device=x.device) if with_grad else None
-    check(_lib.load().smplr_prior_energy(ptr(x), B, P, int(num_cam), ptr(prior.mean), ptr(prior.factor), ptr(prior.offset),
-                                         ptr(prior.angle_idx) if prior.A else None, ptr(prior.angle_scale) if prior.A else None,
-                                         ptr(prior.shape_mean), prior.K, prior.A, ptr(w), ptr(energy), ptr(comp), ptr(grad),
-                                         stream()), "smplr_prior_energy")
+    check(_lib.load().smplr_prior_energy(ptr(x), B, P, *_prior_args(prior, w, num_cam), ptr(energy), ptr(comp), ptr(grad), stream()),
+          "smplr_prior_energy")
     return {"energy": energy, "comp": comp, "grad": grad}
 
 
@@ -549,7 +556,8 @@ def fit_step(state, grad, loss, silh_loss=None, silh_weight=1.0, col_scale=None,
                                                                ("col_scale", col_scale), ("history", history)]:
         if a is not None and a.device != x.device:
             raise RuntimeError("%s lives on %s, x on %s" % (name, a.device, x.device))
-    if int(group_size) != 1 or smooth is not None:
+    grouped = int(group_size) != 1 or smooth is not None
+    if grouped:
         G = check_group(B, group_size)
         if tie is None:
             tie = torch.zeros(P, dtype=torch.uint8, device=x.device)
@@ -561,40 +569,24 @@ def fit_step(state, grad, loss, silh_loss=None, silh_weight=1.0, col_scale=None,
             rc(a, name, dt)
             if a.device != x.device:
                 raise RuntimeError("%s lives on %s, x on %s" % (name, a.device, x.device))
-        if prior is not None:
-            prior, w = _prior_operands(prior, prior_weights, x)
-            pargs = (int(num_cam), ptr(prior.mean), ptr(prior.factor), ptr(prior.offset), ptr(prior.angle_idx) if prior.A else None,
-                     ptr(prior.angle_scale) if prior.A else None, ptr(prior.shape_mean), prior.K, prior.A, ptr(w))
-        elif prior_weights is not None:
-            raise ValueError("prior_weights without a prior")
-        else:
-            pargs = (int(num_cam), None, None, None, None, None, None, 0, 0, None)
-        check(_lib.load().smplr_fit_step_group(
-            ptr(x), ptr(grad), ptr(state.m), ptr(state.v), ptr(state.t), ptr(state.calls), ptr(state.stall), ptr(state.bad),
-            ptr(state.best_step), ptr(state.active), ptr(state.best_loss), ptr(state.best_x), ptr(loss), int(loss.shape[1]),
-            ptr(silh_loss), Ns, float(silh_weight), ptr(col_scale), ptr(history) if H else None, H, B, P, float(lr), float(beta1),
-            float(beta2), float(eps), float(grad_scale), MODES.index(mode), int(patience), *pargs, G, ptr(tie), ptr(smooth),
-            stream()), "smplr_fit_step_group")
-        return state
+    w = None
     if prior is not None:
         prior, w = _prior_operands(prior, prior_weights, x)
-        check(_lib.load().smplr_fit_step_prior(
-            ptr(x), ptr(grad), ptr(state.m), ptr(state.v), ptr(state.t), ptr(state.calls), ptr(state.stall), ptr(state.bad),
-            ptr(state.best_step), ptr(state.active), ptr(state.best_loss), ptr(state.best_x), ptr(loss), int(loss.shape[1]),
-            ptr(silh_loss), Ns, float(silh_weight), ptr(col_scale), ptr(history) if H else None, H, B, P, float(lr), float(beta1),
-            float(beta2), float(eps), float(grad_scale), MODES.index(mode), int(patience), int(num_cam), ptr(prior.mean),
-            ptr(prior.factor), ptr(prior.offset), ptr(prior.angle_idx) if prior.A else None,
-            ptr(prior.angle_scale) if prior.A else None, ptr(prior.shape_mean), prior.K, prior.A, ptr(w), stream()),
-            "smplr_fit_step_prior")
-        return state
-    if prior_weights is not None:
+    elif prior_weights is not None:
         raise ValueError("prior_weights without a prior")
-    check(_lib.load().smplr_fit_step(ptr(x), ptr(grad), ptr(state.m), ptr(state.v), ptr(state.t), ptr(state.calls),
-                                     ptr(state.stall), ptr(state.bad), ptr(state.best_step), ptr(state.active),
-                                     ptr(state.best_loss), ptr(state.best_x), ptr(loss), int(loss.shape[1]), ptr(silh_loss), Ns,
-                                     float(silh_weight), ptr(col_scale), ptr(history) if H else None, H, B, P, float(lr),
-                                     float(beta1), float(beta2), float(eps), float(grad_scale), MODES.index(mode),
-                                     int(patience), stream()), "smplr_fit_step")
+    # what every launcher starts with: smplr_fit_step's own arguments up to the stream
+    common = (ptr(x), ptr(grad), ptr(state.m), ptr(state.v), ptr(state.t), ptr(state.calls), ptr(state.stall), ptr(state.bad),
+              ptr(state.best_step), ptr(state.active), ptr(state.best_loss), ptr(state.best_x), ptr(loss), int(loss.shape[1]),
+              ptr(silh_loss), Ns, float(silh_weight), ptr(col_scale), ptr(history) if H else None, H, B, P, float(lr), float(beta1),
+              float(beta2), float(eps), float(grad_scale), MODES.index(mode), int(patience))
+    lib = _lib.load()
+    if grouped:
+        check(lib.smplr_fit_step_group(*common, *_prior_args(prior, w, num_cam), G, ptr(tie), ptr(smooth), stream()),
+              "smplr_fit_step_group")
+    elif prior is not None:
+        check(lib.smplr_fit_step_prior(*common, *_prior_args(prior, w, num_cam), stream()), "smplr_fit_step_prior")
+    else:
+        check(lib.smplr_fit_step(*common, stream()), "smplr_fit_step")
     return state
 
 
@@ -632,76 +624,117 @@ def _stage_prior_weights(prior, prior_weights, stage_list):
     return [check_prior_weights(w) for w in (pw if per_stage else [pw] * len(stage_list))]
 
 
-def _run_fit(fitter, B, dev, x0_of, make_one, stage_list, stage_w, prior, grp, tie_m, smooth_w, kw, graph, graph_steps,
-             check_every, history):
-    """The loop `ParamFitter.fit` and `ScanFitter.fit` share, on checked arguments: the start from x0_of() (tied columns set
-    to their group's mean), the state, the stages with their column scales and prior weights, graph capture and replay, the
-    stop on `check_every`.  make_one(cs, kw) -> one(state, hist): one iteration (forward, backward, `fit_step`) of the
-    caller's data term; tie_m is None for ungrouped fits."""
-    P = fitter.P
-    total = sum(n for n, _ in stage_list)
-    G = max(1, int(graph_steps))
-    check_every = int(check_every)
-    grouped = tie_m is not None
-    with torch.cuda.device(dev):
-        x0 = x0_of()
-        if grouped:
-            tie_m = tie_m.to(dev)
-            if grp > 1:                                           # a group starts with one value in every tied column
-                mean = x0.reshape(B // grp, grp, P).mean(1, keepdim=True).expand(-1, grp, -1).reshape(B, P)
-                x0 = torch.where(tie_m.bool(), mean, x0)
-        state = FitState.new(x0)
-        hist = torch.full((total, B), float("nan"), dtype=torch.float32, device=dev) if history and total else None
-        cs = torch.ones(P, dtype=torch.float32, device=dev)
-        scales = [c.to(dev) for _, c in stage_list]
-        if grouped:
-            kw.update(group_size=grp, tie=tie_m, smooth=smooth_w.to(dev) if smooth_w is not None else None)
-        if prior is not None:
-            kw.update(fitter._prior_kw(prior, stage_w[0], dev))   # (the (3,) tensor is rewritten at each stage boundary)
-            stage_w = [w.to(dev) for w in stage_w]
-        one = make_one(cs, kw)
-        replay = None
-        if graph and B > 0 and any(n >= G for n, _ in stage_list):
-            # warm-up on a side stream and on a scratch state, then G iterations of the real state in one graph
-            scratch = state.clone()
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(3):
-                    one(scratch, None)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            g_ = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g_):
-                for _ in range(G):
-                    one(state, hist)
-            replay = g_.replay
-        done, stopped = 0, False
-        for si, ((n, _), sc) in enumerate(zip(stage_list, scales)):
-            cs.copy_(sc)
+class _Fitter:
+    """What `ParamFitter` and `ScanFitter` share; a fitter adds its data term (`_iteration`) and sets num_cam and P."""
+
+    def _initial(self, B, init, device, default):
+        """`initial`: a (B, P) tensor as it is, anything else from default(); then the move to the device."""
+        if isinstance(init, torch.Tensor):
+            if tuple(init.shape) != (B, self.P):
+                raise ValueError("init must be (%d, %d), got %s" % (B, self.P, tuple(init.shape)))
+            x0 = init.detach().to(torch.float32)
+        else:
+            x0 = default()
+        return x0.to(device) if device is not None else x0
+
+    def _prior_kw(self, prior, weights, dev):
+        """fit_step's prior arguments: the prior on the device and a (3,) device tensor of weights; {} without a prior."""
+        if prior is None:
+            if weights is not None:
+                raise ValueError("prior_weights without a prior")
+            return {}
+        if not isinstance(prior, PosePrior):
+            raise TypeError("prior must be a PosePrior")
+        return dict(prior=prior.to(dev), prior_weights=check_prior_weights((1.0, 1.0, 1.0) if weights is None else weights).to(dev),
+                    num_cam=self.num_cam)
+
+    def _losses(self, x, loss, silh_loss, silh_weight, prior, prior_weights):
+        """The tail of `losses`: per-term losses of x -> (B,) by the kernel of the loop, a call with a zero gradient on a
+        scratch state that records one row of history."""
+        hist = torch.empty((1, int(x.shape[0])), dtype=torch.float32, device=x.device)
+        fit_step(FitState.new(x), torch.zeros_like(x), loss, silh_loss, silh_weight, None, hist,
+                 **self._prior_kw(prior, prior_weights, x.device))
+        return hist[0]
+
+    def _fit(self, B, dev, start, data, *, steps, lr, mode, stages, patience, grad_scale, graph, check_every, history, beta1, beta2,
+             eps, graph_steps, prior, prior_weights, group_size, tie, smooth):
+        """The rest of `fit` behind a fitter's own look at its inputs (`fit`'s arguments by name; B rows on device dev): the
+        checks of groups, stages and prior weights, the start from start() (tied columns set to their group's mean), the
+        state, the stages with their column scales and prior weights, graph capture and replay, the stop on `check_every`.
+        data() -> make_one, called between the groups' checks and the stages': whatever the fitter checks of its data there;
+        make_one(cs, kw) -> one(state, hist): one iteration (forward, backward, `fit_step`) of its data term."""
+        P = self.P
+        grp = check_group(B, group_size)
+        grouped = grp != 1 or smooth is not None
+        tie_m = check_tie(tie, P, self.num_cam) if grouped else None
+        smooth_w = check_smooth(smooth, P) if smooth is not None else None
+        make_one = data()
+        stage_list = check_stages(stages, P, steps)
+        stage_w = _stage_prior_weights(prior, prior_weights, stage_list)
+        kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
+                  mode=mode, patience=int(patience))
+        total = sum(n for n, _ in stage_list)
+        G = max(1, int(graph_steps))
+        check_every = int(check_every)
+        with torch.cuda.device(dev):
+            x0 = start()
+            if grouped:
+                tie_m = tie_m.to(dev)
+                if grp > 1:                                           # a group starts with one value in every tied column
+                    mean = x0.reshape(B // grp, grp, P).mean(1, keepdim=True).expand(-1, grp, -1).reshape(B, P)
+                    x0 = torch.where(tie_m.bool(), mean, x0)
+            state = FitState.new(x0)
+            hist = torch.full((total, B), float("nan"), dtype=torch.float32, device=dev) if history and total else None
+            cs = torch.ones(P, dtype=torch.float32, device=dev)
+            scales = [c.to(dev) for _, c in stage_list]
+            if grouped:
+                kw.update(group_size=grp, tie=tie_m, smooth=smooth_w.to(dev) if smooth_w is not None else None)
             if prior is not None:
-                kw["prior_weights"].copy_(stage_w[si])
-            left = n
-            while left > 0 and not stopped:
-                if replay is not None and left >= G:
-                    replay()
-                    k = G
-                else:
-                    one(state, hist)
-                    k = 1
-                left -= k
-                if check_every > 0 and B > 0 and (done + k) // check_every > done // check_every:
-                    stopped = not bool(state.active.any())
-                done += k
-            if stopped:
-                break
-        torch.cuda.synchronize()
-    return FitResult(x=state.best_x, loss=state.best_loss, step=state.best_step, final_x=state.x, nonfinite=state.bad,
-                     active=state.active.bool(), history=hist[:done] if hist is not None else None, steps=done,
-                     state=state, group_size=grp)
+                kw.update(self._prior_kw(prior, stage_w[0], dev))     # (the (3,) tensor is rewritten at each stage boundary)
+                stage_w = [w.to(dev) for w in stage_w]
+            one = make_one(cs, kw)
+            replay = None
+            if graph and B > 0 and any(n >= G for n, _ in stage_list):
+                # warm-up on a side stream and on a scratch state, then G iterations of the real state in one graph
+                scratch = state.clone()
+                side = torch.cuda.Stream(device=dev)
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    for _ in range(3):
+                        one(scratch, None)
+                torch.cuda.current_stream().wait_stream(side)
+                torch.cuda.synchronize()
+                g_ = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g_):
+                    for _ in range(G):
+                        one(state, hist)
+                replay = g_.replay
+            done, stopped = 0, False
+            for si, ((n, _), sc) in enumerate(zip(stage_list, scales)):
+                cs.copy_(sc)
+                if prior is not None:
+                    kw["prior_weights"].copy_(stage_w[si])
+                left = n
+                while left > 0 and not stopped:
+                    if replay is not None and left >= G:
+                        replay()
+                        k = G
+                    else:
+                        one(state, hist)
+                        k = 1
+                    left -= k
+                    if check_every > 0 and B > 0 and (done + k) // check_every > done // check_every:
+                        stopped = not bool(state.active.any())
+                    done += k
+                if stopped:
+                    break
+            torch.cuda.synchronize()
+        return FitResult(x=state.best_x, loss=state.best_loss, step=state.best_step, final_x=state.x, nonfinite=state.bad,
+                         active=state.active.bool(), history=hist[:done] if hist is not None else None, steps=done,
+                         state=state, group_size=grp)
 
 
-class ParamFitter:
+class ParamFitter(_Fitter):
     """Owns an `SMPLDecoder(outputs=(), loss=softmax_focal_loss(gamma, weight_classes)[, silh_loss=...])` and fits its
     input to label maps.  The defaults are those of decoder_loss_debugging.py:117-118: focal loss with gamma = 5, no class
     weights; `fit`'s are Keras' Adam (lr 1e-3, eps 1e-7)."""
@@ -728,21 +761,17 @@ class ParamFitter:
         initialiser uniform(-0.05, 0.05) drawn from `generator` (decoder_loss_debugging.py:75-77); a (B, P) tensor as it is
         (an encoder's prediction)."""
         from .smpl_model import mean86
-        if isinstance(init, torch.Tensor):
-            if tuple(init.shape) != (B, self.P):
-                raise ValueError("init must be (%d, %d), got %s" % (B, self.P, tuple(init.shape)))
-            x0 = init.detach().to(torch.float32)
-            return x0.to(device) if device is not None else x0
-        if self.num_cam != 4:
-            raise ValueError("the mean parameters have 4 camera columns")
-        mean = torch.as_tensor(mean86(self.img_wh), dtype=torch.float32).repeat(B, 1)
-        if init is None:
-            x0 = mean
-        elif init == "reference":
-            x0 = mean + (torch.rand(B, self.P, generator=generator) * 0.1 - 0.05)
-        else:
+
+        def default():
+            if self.num_cam != 4:
+                raise ValueError("the mean parameters have 4 camera columns")
+            mean = torch.as_tensor(mean86(self.img_wh), dtype=torch.float32).repeat(B, 1)
+            if init is None:
+                return mean
+            if init == "reference":
+                return mean + (torch.rand(B, self.P, generator=generator) * 0.1 - 0.05)
             raise ValueError("init must be None, 'reference' or a (B, %d) tensor, got %r" % (self.P, init))
-        return x0.to(device) if device is not None else x0
+        return self._initial(B, init, device, default)
 
     def _labels(self, labels, B, W, name):
         if not isinstance(labels, torch.Tensor) or labels.is_floating_point() or labels.numel() != B * W * W:
@@ -763,22 +792,8 @@ class ParamFitter:
         x = _lib.require_cuda(x.detach(), "x")
         with torch.no_grad(), torch.cuda.device(x.device):
             out = self.decoder(x, labels, silh_labels=silh_labels)
-            hist = torch.empty((1, B), dtype=torch.float32, device=x.device)
-            fit_step(FitState.new(x), torch.zeros_like(x), out["seg_loss"],
-                     out["silh_loss"] if silh_labels is not None else None, self.silh_weight, None, hist,
-                     **self._prior_kw(prior, prior_weights, x.device))
-        return hist[0]
-
-    def _prior_kw(self, prior, weights, dev):
-        """fit_step's prior arguments: the prior on the device and a (3,) device tensor of weights; {} without a prior."""
-        if prior is None:
-            if weights is not None:
-                raise ValueError("prior_weights without a prior")
-            return {}
-        if not isinstance(prior, PosePrior):
-            raise TypeError("prior must be a PosePrior")
-        return dict(prior=prior.to(dev), prior_weights=check_prior_weights((1.0, 1.0, 1.0) if weights is None else weights).to(dev),
-                    num_cam=self.num_cam)
+            return self._losses(x, out["seg_loss"], out["silh_loss"] if silh_labels is not None else None, self.silh_weight, prior,
+                                prior_weights)
 
     def _iteration(self, state, labels, silh_labels, gout, sgout, cs, hist, kw):
         x = state.x.detach().requires_grad_(True)                 # (shares x's memory: the kernel updates it in place)
@@ -819,29 +834,24 @@ class ParamFitter:
             raise ValueError("mode %r is none of %s" % (mode, MODES))
         if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
             raise ValueError("labels must be a (B, W, W) integer tensor")
-        B, W = int(labels.shape[0]), self.img_wh
-        grp = check_group(B, group_size)
-        grouped = grp != 1 or smooth is not None
-        tie_m = check_tie(tie, self.P, self.num_cam) if grouped else None
-        smooth_w = check_smooth(smooth, self.P) if smooth is not None else None
-        labels = self._labels(labels, B, W, "labels")
-        dev = labels.device
-        if (silh_labels is not None) != self.with_silhouette:
-            raise ValueError("silh_labels go with ParamFitter(with_silhouette=True), and only with it")
-        if silh_labels is not None:
-            silh_labels = self._labels(silh_labels, B, self.silh_wh, "silh_labels")
-        stage_list = check_stages(stages, self.P, steps)
-        stage_w = _stage_prior_weights(prior, prior_weights, stage_list)
-        kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
-                  mode=mode, patience=int(patience))
+        B, W, dev = int(labels.shape[0]), self.img_wh, labels.device
 
-        def make_one(cs, kw):
-            N, Ns = W * W, self.silh_wh * self.silh_wh
-            gout = torch.full((B, N), 1.0 / N, dtype=torch.float32, device=dev)
-            sgout = torch.full((B, Ns), self.silh_weight / Ns, dtype=torch.float32, device=dev) if self.with_silhouette else None
-            return lambda st, h: self._iteration(st, labels, silh_labels, gout, sgout, cs, h, kw)
-        return _run_fit(self, B, dev, lambda: self.initial(B, init, generator, dev), make_one, stage_list, stage_w, prior, grp,
-                        tie_m, smooth_w, kw, graph, graph_steps, check_every, history)
+        def data():
+            lab = self._labels(labels, B, W, "labels")
+            if (silh_labels is not None) != self.with_silhouette:
+                raise ValueError("silh_labels go with ParamFitter(with_silhouette=True), and only with it")
+            slab = self._labels(silh_labels, B, self.silh_wh, "silh_labels") if silh_labels is not None else None
+
+            def make_one(cs, kw):
+                N, Ns = W * W, self.silh_wh * self.silh_wh
+                gout = torch.full((B, N), 1.0 / N, dtype=torch.float32, device=dev)
+                sgout = torch.full((B, Ns), self.silh_weight / Ns, dtype=torch.float32, device=dev) if self.with_silhouette else None
+                return lambda st, h: self._iteration(st, lab, slab, gout, sgout, cs, h, kw)
+            return make_one
+        return self._fit(B, dev, lambda: self.initial(B, init, generator, dev), data, steps=steps, lr=lr, mode=mode, stages=stages,
+                         patience=patience, grad_scale=grad_scale, graph=graph, check_every=check_every, history=history,
+                         beta1=beta1, beta2=beta2, eps=eps, graph_steps=graph_steps, prior=prior, prior_weights=prior_weights,
+                         group_size=group_size, tie=tie, smooth=smooth)
 
 
 def robust_rho(d2, sigma):
@@ -851,7 +861,7 @@ def robust_rho(d2, sigma):
     return s2 * d2 / (s2 + d2)
 
 
-class ScanFitter:
+class ScanFitter(_Fitter):
     """`ParamFitter`'s loop with `SMPLLayer -> s verts + t -> scan.surface_distance` in place of decoder + rasteriser: fits
     x (B, 86) to point clouds without correspondences.  Columns 4..85 are pose and shape; the four columns the image fit
     uses for the camera hold (s, t_x, t_y, t_z), the similarity that places the body in the scan's frame (`SMPLLayer`
@@ -896,17 +906,14 @@ class ScanFitter:
     def initial(self, B, init=None, device=None):
         """(B, 86) float32 start: None = scale 1, no shift, the mean pose and shape; a (B, 86) tensor as it is."""
         from .smpl_model import mean86
-        if isinstance(init, torch.Tensor):
-            if tuple(init.shape) != (B, self.P):
-                raise ValueError("init must be (%d, %d), got %s" % (B, self.P, tuple(init.shape)))
-            x0 = init.detach().to(torch.float32)
-        elif init is None:
+
+        def default():
+            if init is not None:
+                raise ValueError("init must be None or a (B, %d) tensor, got %r" % (self.P, init))
             row = mean86(1.0)
             row[:4] = (1.0, 0.0, 0.0, 0.0)
-            x0 = torch.as_tensor(row, dtype=torch.float32).repeat(B, 1)
-        else:
-            raise ValueError("init must be None or a (B, %d) tensor, got %r" % (self.P, init))
-        return x0.to(device) if device is not None else x0
+            return torch.as_tensor(row, dtype=torch.float32).repeat(B, 1)
+        return self._initial(B, init, device, default)
 
     def place(self, x):
         """x (B, 86) -> the body in the scan's frame: x[:, 0] SMPLLayer(x) + x[:, 1:4]; differentiable."""
@@ -947,8 +954,6 @@ class ScanFitter:
             (g,) = torch.autograd.grad([only], [x], grad_outputs=[go])
             fit_step(state, g.contiguous(), only.detach().contiguous(), None, 1.0, cs, hist, **kw)
 
-    _prior_kw = ParamFitter._prior_kw                             # (reads self.num_cam only)
-
     def _points(self, points, counts):
         if not isinstance(points, torch.Tensor) or points.dim() != 3 or points.shape[2] != 3 or points.shape[1] < 1:
             raise ValueError("points must be a (B, N, 3) tensor with N >= 1")
@@ -968,14 +973,11 @@ class ScanFitter:
         gradient on a scratch state): the bits `fit` would record for x in its history."""
         points, counts = self._points(points, counts)
         x = _lib.require_cuda(x.detach(), "x")
-        B = int(x.shape[0])
         with torch.no_grad(), torch.cuda.device(x.device):
             p2m, m2p, _ = self.terms(x, points, counts)
-            hist = torch.empty((1, B), dtype=torch.float32, device=x.device)
             first, second = (p2m, m2p) if p2m is not None else (m2p, None)
-            fit_step(FitState.new(x), torch.zeros_like(x), first.contiguous(), None if second is None else second.contiguous(),
-                     self.m2p_weight, None, hist, **self._prior_kw(prior, prior_weights, x.device))
-        return hist[0]
+            return self._losses(x, first.contiguous(), None if second is None else second.contiguous(), self.m2p_weight, prior,
+                                prior_weights)
 
     def fit(self, points, counts=None, init=None, steps=200, lr=1e-2, mode="torch", stages=None, patience=0, grad_scale=1.0,
             graph=False, check_every=0, history=False, beta1=0.9, beta2=0.999, eps=KERAS_EPS, graph_steps=4, prior=None,
@@ -989,17 +991,11 @@ class ScanFitter:
         points, counts = self._points(points, counts)
         B, N = int(points.shape[0]), int(points.shape[1])
         dev = points.device
-        grp = check_group(B, group_size)
-        grouped = grp != 1 or smooth is not None
-        tie_m = check_tie(tie, self.P, self.num_cam) if grouped else None
-        smooth_w = check_smooth(smooth, self.P) if smooth is not None else None
-        stage_list = check_stages(stages, self.P, steps)
-        stage_w = _stage_prior_weights(prior, prior_weights, stage_list)
-        kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
-                  mode=mode, patience=int(patience))
 
         def make_one(cs, kw):
             gout, sgout = self._cotangents(B, N, dev)
             return lambda st, h: self._iteration(st, points, counts, gout, sgout, cs, h, kw)
-        return _run_fit(self, B, dev, lambda: self.initial(B, init, dev), make_one, stage_list, stage_w, prior, grp, tie_m,
-                        smooth_w, kw, graph, graph_steps, check_every, history)
+        return self._fit(B, dev, lambda: self.initial(B, init, dev), lambda: make_one, steps=steps, lr=lr, mode=mode, stages=stages,
+                         patience=patience, grad_scale=grad_scale, graph=graph, check_every=check_every, history=history,
+                         beta1=beta1, beta2=beta2, eps=eps, graph_steps=graph_steps, prior=prior, prior_weights=prior_weights,
+                         group_size=group_size, tie=tie, smooth=smooth)
