@@ -134,7 +134,7 @@ class SMPLDecoder(nn.Module):
         if conf is not None:
             if labels is None or "seg" not in self.heads:
                 raise RuntimeError("confusion counts the seg head's arg-max against labels: needs labels and the seg head")
-            if conf.dtype != torch.int64 or tuple(conf.shape) != (33, 32):
+            if not ops._is_confusion(conf, 32):
                 raise RuntimeError("confusion must count the 32 classes: SegConfusion(32, device) / a (33, 32) int64 tensor")
         fused = self.loss is not None and labels is not None
         if labels is not None and self.loss is None and conf is None:
@@ -148,8 +148,7 @@ class SMPLDecoder(nn.Module):
         if silh_labels is not None:
             from .focal_loss import class_weights
             Ws = self.silh_wh
-            if (silh_labels.numel() != x.shape[0] * Ws * Ws
-                    or silh_labels.dtype not in (torch.int64, torch.int32, torch.int16, torch.uint8)):
+            if not ops._is_class_map(silh_labels, x.shape[0] * Ws * Ws):
                 raise RuntimeError("silh_labels must be an integer map of %d x %d x %d entries" % (x.shape[0], Ws, Ws))
             sw = class_weights(x.device)[:2].contiguous() if self.silh_loss.weight_classes else None
             sspec = (silh_labels.to(torch.int32).reshape(x.shape[0], Ws, Ws), sw, float(self.silh_loss.gamma))

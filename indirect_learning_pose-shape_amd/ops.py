@@ -11,9 +11,27 @@ Reference callables replaced (reference file:line):
   SegRasterFn  - projects_to_seg           keras_smpl/projects_to_seg.py:9-69
   SilhRasterFn - projects_to_silhouette    keras_smpl/projects_to_silhouette.py:14-44
   DecoderFn    - the model.py:108-118 chain of the above as one autograd node
+
+The stage wrappers under the Functions, and the entry point of include/smplraster.h each one reaches:
+  _pose_fwd        smplr_pose_fwd                     _pose_blend_fwd  smplr_pose_blend3_fwd
+  _blend_fwd       smplr_blend3_fwd (+ smplr_coef3_pack) | smplr_blend_fwd, by the constants
+  _skin_fwd        smplr_skin_fwd                     _smpl_bwd        smplr_smpl_bwd
+  visibility       smplr_visibility
+  _seg_fwd         smplr_seg_fwd                      _vis_seg_fwd     smplr_vis_seg_fwd
+  _seg_bin         smplr_seg_bin                      _seg_raster      smplr_seg_raster
+  _seg_raster_ex   smplr_seg_raster_ex_conf (_seg_raster_loss: the same function)
+  _skin_vis_seg    smplr_skin_vis_seg_fwd_inv; _skin_vis_seg_fwd, _skin_vis_seg_call: its forms for tests and probes
+  _seg_bwd         smplr_seg_bwd | smplr_seg_loss_bwd (with stats=); _seg_loss_bwd: its form with stats
+  _silh_fwd_loss   smplr_silh_fwd_hint | smplr_silh_fwd_loss (with labels); _silh_fwd: its form without labels
+  _silh_loss_fwd   smplr_silh_loss_fwd
+  _silh_bwd        smplr_silh_bwd | smplr_silh_loss_bwd (with k=); _silh_loss_bwd: its form with k
+DecoderFn.forward runs them by a DecoderPlan (decoder_plan: host arithmetic only) over operands that
+_decoder_operands has checked.
 """
 from __future__ import annotations
 
+import ctypes
+import dataclasses
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -104,14 +122,12 @@ class SMPLConstants:
 
     def fp32_gemm(self):
         """A view of the same constants that runs the blend GEMMs on the fp32 matrix cores."""
-        import dataclasses
         return dataclasses.replace(self, blend3_fwd=None, blend3_bwd=None)
 
 
 def blend_gemm_mode() -> str:
     """'bf16x3' (default): blend GEMMs on the bf16 matrix cores with 3-way split, fp32-grade operands;
     'f32': v_mfma_f32_32x32x2_f32.  Chosen when the constants are uploaded (env SMPLR_BLEND_GEMM)."""
-    import os
     m = os.environ.get("SMPLR_BLEND_GEMM", "bf16x3").lower()
     if m not in ("bf16x3", "f32"):
         raise RuntimeError("SMPLR_BLEND_GEMM must be bf16x3 or f32, got %r" % m)
@@ -180,19 +196,6 @@ def _inv_rows(pt: PartTable, c: SMPLConstants):
     return pt.inv, pt.top4_packed[1]
 
 
-def _skin_vis_seg_call(v_posed, A, c: SMPLConstants, cam, W, pt: PartTable, grid_wh, ref_compat, ws, labels=None,
-                       class_w=None, gamma=0.0, verts=None, proj=None, mask=None, seg=None, arg=None, rec=None, vslot=None,
-                       loss=None, stats=None, vmax=None, conf=None):
-    """The one call behind _skin_vis_seg_fwd, _skin_vis_seg_fwd_ex and _skin_vis_seg_opt (smplr_skin_vis_seg_fwd_inv:
-    the `_ex_conf` entry point, classifying from registers where the table has its inverse)."""
-    inv, top4p = _inv_rows(pt, c)
-    check(_lib.load().smplr_skin_vis_seg_fwd_inv(
-        ptr(v_posed), ptr(c.lbs_top4), ptr(A), ptr(cam), cam.shape[1], v_posed.shape[0], c.V, int(W), int(grid_wh),
-        1 if ref_compat else 0, ptr(pt.part_pos), ptr(pt.part_off), pt.P, pt.K, ptr(inv), ptr(top4p), ptr(ws), ptr(labels),
-        ptr(class_w), float(gamma), ptr(verts), ptr(proj), ptr(mask), ptr(seg), ptr(arg), ptr(rec), ptr(vslot), ptr(loss),
-        ptr(stats), ptr(vmax), ptr(conf), stream()), "smplr_skin_vis_seg_fwd_inv")
-
-
 def build_part_table(ids, off, vertex_sampling, num_verts, device) -> PartTable:
     vs = 1 if vertex_sampling in (None, 1) else int(vertex_sampling)
     P = len(off) - 1
@@ -225,6 +228,43 @@ def _empty(shape, like, dtype=torch.float32):
 
 def _workspace(nbytes, like):
     return torch.empty(max(int(nbytes), 4) // 4 + 1, dtype=torch.float32, device=like.device)
+
+
+def _seg_buffers(B, W, pt: PartTable, like, seg=True, rec=True):
+    """What the part rasteriser writes for B meshes: seg (B,W,W,P+1) scores, arg (B,W,W,32) int16 record slots of the
+    maximising vertices, rec (B, smplr_seg_slots, 4) records -> seg, arg, rec (None where seg / rec = False)."""
+    return (_empty((B, W, W, pt.P + 1), like) if seg else None, _empty((B, W, W, 32), like, torch.int16),
+            _empty((B, _lib.load().smplr_seg_slots(pt.P, pt.K), 4), like) if rec else None)
+
+
+def _loss_buffers(labels, loss, stats, B, W, like):
+    """What the rasteriser's loss epilogue writes, and when: without labels neither exists; with them loss (B, W*W) and
+    stats (B, W*W, 4) for its backward, each the caller's where passed, else allocated here."""
+    if labels is None:
+        return None, None
+    return (_empty((B, W * W), like) if loss is None else loss, _empty((B, W * W, 4), like) if stats is None else stats)
+
+
+def _check_vp(VP, pt: PartTable):
+    if VP != pt.VP:
+        raise RuntimeError("projects has %d vertices but the part table expects %d" % (VP, pt.VP))
+
+
+_CLASS_MAP_DTYPES = (torch.int64, torch.int32, torch.int16, torch.uint8)
+
+
+def _is_class_map(t, numel=None):
+    """The integer-class-map rule of every loss head's entry point: labels come as int64 / int32 / int16 / uint8 (the
+    caller converts them to the kernels' int32), one entry per pixel where `numel` says how many that is."""
+    return t.dtype in _CLASS_MAP_DTYPES and (numel is None or t.numel() == numel)
+
+
+def _is_confusion(conf, classes, kernel_operand=False):
+    """The confusion-tensor rule: (classes + 1, classes) int64 - (33, 32) for the 32-class head, (3, 2) for the
+    silhouette's (metrics.SegConfusion.counts).  kernel_operand: as a loss epilogue is handed it - on a HIP device and
+    contiguous too."""
+    ok = conf.dtype == torch.int64 and tuple(conf.shape) == (classes + 1, classes)
+    return ok and (not kernel_operand or (conf.is_cuda and conf.is_contiguous()))
 
 
 # --------------------------------------------------------------------------- raw stage calls
@@ -362,15 +402,9 @@ def _seg_fwd(proj, mask, W, pt: PartTable, out=None, vslot=None):
     """vslot (B,VP) int16, optional output: each vertex' record slot, for the gather form of the backward."""
     lib = _lib.load()
     B, VP = proj.shape[0], proj.shape[1]
-    if VP != pt.VP:
-        raise RuntimeError("projects has %d vertices but the part table expects %d" % (VP, pt.VP))
+    _check_vp(VP, pt)
     ws = _workspace(lib.smplr_seg_workspace(B, VP, W, pt.P, pt.K), proj)
-    if out is not None:
-        seg, arg, rec = out
-    else:
-        seg = _empty((B, W, W, pt.P + 1), proj)
-        arg = _empty((B, W, W, 32), proj, torch.int16)
-        rec = _empty((B, lib.smplr_seg_slots(pt.P, pt.K), 4), proj)
+    seg, arg, rec = out if out is not None else _seg_buffers(B, W, pt, proj)
     check(lib.smplr_seg_fwd(ptr(proj), ptr(mask), B, VP, W, ptr(pt.part_pos), ptr(pt.part_off), pt.P,
                             pt.K, ptr(ws), ptr(seg), ptr(arg), ptr(rec), ptr(vslot), stream()), "smplr_seg_fwd")
     return seg, arg, rec
@@ -381,16 +415,9 @@ def _vis_seg_fwd(proj, W, pt: PartTable, grid_wh=64, ref_compat=True, out=None, 
     """compute_mask + projects_to_seg in one call (smplr_vis_seg_fwd): -> mask, seg, arg, rec."""
     lib = _lib.load()
     B, VP = proj.shape[0], proj.shape[1]
-    if VP != pt.VP:
-        raise RuntimeError("projects has %d vertices but the part table expects %d" % (VP, pt.VP))
+    _check_vp(VP, pt)
     ws = _workspace(lib.smplr_seg_workspace(B, VP, W, pt.P, pt.K), proj)
-    if out is not None:
-        mask, seg, arg, rec = out
-    else:
-        mask = _empty((B, VP), proj)
-        seg = _empty((B, W, W, pt.P + 1), proj)
-        arg = _empty((B, W, W, 32), proj, torch.int16)
-        rec = _empty((B, lib.smplr_seg_slots(pt.P, pt.K), 4), proj)
+    mask, seg, arg, rec = out if out is not None else (_empty((B, VP), proj),) + _seg_buffers(B, W, pt, proj)
     check(lib.smplr_vis_seg_fwd(ptr(proj), B, VP, W, int(grid_wh), 1 if ref_compat else 0, ptr(pt.part_pos),
                                 ptr(pt.part_off), pt.P, pt.K, ptr(ws), ptr(mask), ptr(seg), ptr(arg), ptr(rec),
                                 ptr(vslot), stream()), "smplr_vis_seg_fwd")
@@ -398,100 +425,79 @@ def _vis_seg_fwd(proj, W, pt: PartTable, grid_wh=64, ref_compat=True, out=None, 
 
 
 @on_device
-def _skin_vis_seg_fwd(v_posed, A, c: SMPLConstants, cam, W, pt: PartTable, grid_wh=64, ref_compat=True, out=None,
-                      vslot=None):
-    """_skin_fwd + _vis_seg_fwd as one call of two launches (smplr_skin_vis_seg_fwd): the binning workgroups skin
-    their own vertices.  Needs the sparse skinning weights and no vertex sampling.
-    -> verts, proj, mask, seg, arg, rec (bit for bit what the two calls give)."""
+def _skin_vis_seg(v_posed, A, c: SMPLConstants, cam, W, pt: PartTable, grid_wh=64, ref_compat=True, labels=None,
+                  class_w=None, gamma=0.0, conf=None, want=("verts", "proj", "mask", "seg"), fits=None, verts=None,
+                  proj=None, mask=None, seg=None, arg=None, rec=None, vslot=None, loss=None, stats=None, vmax=None, ws=None):
+    """_skin_fwd + _vis_seg_fwd as one call of two launches (smplr_skin_vis_seg_fwd_inv, classifying from registers
+    where the table has its inverse): the binning workgroups skin their own vertices.  The one owner of that entry
+    point.  Needs the sparse skinning weights and no vertex sampling.
+    -> dict of what was written, by name (bit for bit what the two calls give): verts, proj (B,V,3), mask (B,V), seg, arg,
+    rec (_seg_buffers), vslot (B,V) int16, loss, stats (_loss_buffers), vmax (B,W,W) - each pixel's largest part score,
+    the silhouette rasteriser's hint - and ws, the binned workspace; None = not written.
+    Each may be passed in as a buffer.  arg, rec and ws are always written, allocated here where not passed; verts, proj,
+    mask, seg, vslot and vmax are written where passed or named in `want` (allocated then); seg may stay out only with labels.
+    labels (B,W,W) int32: the loss head runs as the rasteriser's epilogue with class_w (32,) or None and gamma -> loss,
+    stats; conf (33, 32) int64, with labels: += the (label, arg-max) counts.
+    fits: smplr_skin_vis_seg_fits(V, W, grid_wh)'s answer where the caller has asked already."""
     lib = _lib.load()
     B, V = v_posed.shape[0], c.V
     if c.lbs_top4 is None or pt.VP != V:
-        raise RuntimeError("_skin_vis_seg_fwd needs <= 4 skinning weights per vertex and vertex_sampling = 1")
-    if not lib.smplr_skin_vis_seg_fits(V, int(W), int(grid_wh)):
-        raise RuntimeError("_skin_vis_seg_fwd: V=%d, W=%d, grid_wh=%d do not fit the binning workgroup's LDS "
+        raise RuntimeError("_skin_vis_seg needs <= 4 skinning weights per vertex and vertex_sampling = 1")
+    if not (lib.smplr_skin_vis_seg_fits(V, int(W), int(grid_wh)) if fits is None else fits):
+        raise RuntimeError("_skin_vis_seg: V=%d, W=%d, grid_wh=%d do not fit the binning workgroup's LDS "
                            "(smplr_skin_vis_seg_fits): call _skin_fwd and _vis_seg_fwd" % (V, W, grid_wh))
-    ws = _workspace(lib.smplr_seg_workspace(B, V, W, pt.P, pt.K), v_posed)
-    if out is not None:
-        verts, proj, mask, seg, arg, rec = out
-    else:
-        verts, proj = _empty((B, V, 3), v_posed), _empty((B, V, 3), v_posed)
-        mask = _empty((B, V), v_posed)
-        seg = _empty((B, W, W, pt.P + 1), v_posed)
-        arg = _empty((B, W, W, 32), v_posed, torch.int16)
-        rec = _empty((B, lib.smplr_seg_slots(pt.P, pt.K), 4), v_posed)
-    _skin_vis_seg_call(v_posed, A, c, cam, W, pt, grid_wh, ref_compat, ws, verts=verts, proj=proj, mask=mask, seg=seg,
-                       arg=arg, rec=rec, vslot=vslot)
-    return verts, proj, mask, seg, arg, rec
+    o = dict(verts=verts, proj=proj, mask=mask, seg=seg, arg=arg, rec=rec, vslot=vslot, vmax=vmax, ws=ws)
+    for name in want:
+        if o[name] is None:
+            shape = {"verts": (B, V, 3), "proj": (B, V, 3), "mask": (B, V), "seg": (B, W, W, pt.P + 1), "vslot": (B, V),
+                     "vmax": (B, W, W)}[name]
+            o[name] = _empty(shape, v_posed, torch.int16 if name == "vslot" else torch.float32)
+    if arg is None or rec is None:
+        _, arg2, rec2 = _seg_buffers(B, W, pt, v_posed, seg=False, rec=rec is None)
+        o["arg"], o["rec"] = (arg2 if arg is None else arg), (rec2 if rec is None else rec)
+    o["loss"], o["stats"] = _loss_buffers(labels, loss, stats, B, W, v_posed)
+    if ws is None:
+        o["ws"] = _workspace(lib.smplr_seg_workspace(B, V, W, pt.P, pt.K), v_posed)
+    inv, top4p = _inv_rows(pt, c)
+    check(lib.smplr_skin_vis_seg_fwd_inv(
+        ptr(v_posed), ptr(c.lbs_top4), ptr(A), ptr(cam), cam.shape[1], B, V, int(W), int(grid_wh),
+        1 if ref_compat else 0, ptr(pt.part_pos), ptr(pt.part_off), pt.P, pt.K, ptr(inv), ptr(top4p), ptr(o["ws"]),
+        ptr(labels), ptr(class_w), float(gamma), ptr(o["verts"]), ptr(o["proj"]), ptr(o["mask"]), ptr(o["seg"]),
+        ptr(o["arg"]), ptr(o["rec"]), ptr(o["vslot"]), ptr(o["loss"]), ptr(o["stats"]), ptr(o["vmax"]), ptr(conf),
+        stream()), "smplr_skin_vis_seg_fwd_inv")
+    return o
 
 
-@on_device
-def _skin_vis_seg_fwd_ex(v_posed, A, c: SMPLConstants, cam, W, pt: PartTable, labels=None, class_w=None, gamma=0.0,
-                         grid_wh=64, ref_compat=True, verts=None, proj=None, mask=None, seg=None, arg=None, rec=None,
-                         vslot=None, loss=None, stats=None, vmax=None, conf=None):
-    """_skin_vis_seg_fwd with optional extras (smplr_skin_vis_seg_fwd_ex): with `labels` (B,W,W) int32 the loss head
-    runs as the rasteriser's epilogue -> loss (B, W*W), stats (B, W*W, 4); `vmax` (B,W,W) receives each pixel's largest
-    part score (the silhouette rasteriser's hint); verts / proj / mask / seg are written only where a tensor is given
-    (seg may be omitted only with labels); `conf` (33, 32) int64 (with labels) += the (label, arg-max) counts
-    (smplr_skin_vis_seg_fwd_ex_conf)."""
-    lib = _lib.load()
-    B, V = v_posed.shape[0], c.V
-    if c.lbs_top4 is None or pt.VP != V or not lib.smplr_skin_vis_seg_fits(V, int(W), int(grid_wh)):
-        raise RuntimeError("_skin_vis_seg_fwd_ex: needs sparse skinning weights, vertex_sampling = 1 and sizes that fit "
-                           "the binning workgroup's LDS (smplr_skin_vis_seg_fits)")
-    ws = _workspace(lib.smplr_seg_workspace(B, V, W, pt.P, pt.K), v_posed)
-    if arg is None:
-        arg = _empty((B, W, W, 32), v_posed, torch.int16)
-    if rec is None:
-        rec = _empty((B, lib.smplr_seg_slots(pt.P, pt.K), 4), v_posed)
-    if labels is not None:
-        loss = _empty((B, W * W), v_posed) if loss is None else loss
-        stats = _empty((B, W * W, 4), v_posed) if stats is None else stats
-    else:
-        loss = stats = None
-    _skin_vis_seg_call(v_posed, A, c, cam, W, pt, grid_wh, ref_compat, ws, labels, class_w, gamma, verts, proj, mask, seg,
-                       arg, rec, vslot, loss, stats, vmax, conf)
-    return loss, stats, arg, rec
+def _skin_vis_seg_fwd(v_posed, A, c: SMPLConstants, cam, W, pt: PartTable, grid_wh=64, ref_compat=True, vslot=None):
+    """_skin_vis_seg with every output allocated -> verts, proj, mask, seg, arg, rec (the name tests and probes call)."""
+    o = _skin_vis_seg(v_posed, A, c, cam, W, pt, grid_wh, ref_compat, vslot=vslot)
+    return tuple(o[k] for k in ("verts", "proj", "mask", "seg", "arg", "rec"))
+
+
+def _skin_vis_seg_call(v_posed, A, c: SMPLConstants, cam, W, pt: PartTable, grid_wh, ref_compat, ws, **buffers):
+    """_skin_vis_seg over the caller's workspace and buffers only: nothing optional is allocated (tests and probes that
+    read the workspace back)."""
+    _skin_vis_seg(v_posed, A, c, cam, W, pt, grid_wh, ref_compat, want=(), ws=ws, **buffers)
 
 
 @on_device
 def _seg_raster_ex(ws, rec, B, W, pt: PartTable, labels=None, class_w=None, gamma=0.0, seg=None, arg=None, loss=None,
                    stats=None, vmax=None, conf=None):
-    """Stage 2 with optional extras (smplr_seg_raster_ex) over a binned workspace -> loss, stats, arg (loss epilogue with
-    `labels`; `vmax`: per-pixel largest part score; `conf` (33, 32) int64, with labels: += the (label, arg-max) counts,
-    smplr_seg_raster_ex_conf)."""
+    """Stage 2 with optional extras (smplr_seg_raster_ex_conf; conf = None is smplr_seg_raster_ex) over a binned workspace
+    -> loss, stats, arg (loss epilogue with `labels`; `vmax`: per-pixel largest part score; `conf` (33, 32) int64, with
+    labels: += the (label, arg-max) counts).  With none of the extras it launches what _seg_raster launches."""
     lib = _lib.load()
     if arg is None:
-        arg = _empty((B, W, W, 32), rec, torch.int16)
-    if labels is not None:
-        loss = _empty((B, W * W), rec) if loss is None else loss
-        stats = _empty((B, W * W, 4), rec) if stats is None else stats
-    else:
-        loss = stats = None
-    if conf is not None:
-        check(lib.smplr_seg_raster_ex_conf(B, W, pt.P, pt.K, ptr(ws), ptr(rec), ptr(labels), ptr(class_w), float(gamma),
-                                           ptr(seg), ptr(arg), ptr(loss), ptr(stats), ptr(vmax), ptr(conf), stream()),
-              "smplr_seg_raster_ex_conf")
-        return loss, stats, arg
-    check(lib.smplr_seg_raster_ex(B, W, pt.P, pt.K, ptr(ws), ptr(rec), ptr(labels), ptr(class_w), float(gamma),
-                                  ptr(seg), ptr(arg), ptr(loss), ptr(stats), ptr(vmax), stream()), "smplr_seg_raster_ex")
+        arg = _seg_buffers(B, W, pt, rec, seg=False, rec=False)[1]
+    loss, stats = _loss_buffers(labels, loss, stats, B, W, rec)
+    # (the library reports either entry point as smplr_seg_raster_ex; the call without conf keeps that name here too)
+    check(lib.smplr_seg_raster_ex_conf(B, W, pt.P, pt.K, ptr(ws), ptr(rec), ptr(labels), ptr(class_w), float(gamma),
+                                       ptr(seg), ptr(arg), ptr(loss), ptr(stats), ptr(vmax), ptr(conf), stream()),
+          "smplr_seg_raster_ex_conf" if conf is not None else "smplr_seg_raster_ex")
     return loss, stats, arg
 
 
-def _seg_raster_loss(ws, rec, B, W, pt, labels, class_w, gamma, seg=None, arg=None, loss=None, stats=None):
-    """The loss-epilogue form of _seg_raster_ex (kept as a name of its own: tests, tools)."""
-    return _seg_raster_ex(ws, rec, B, W, pt, labels, class_w, gamma, seg=seg, arg=arg, loss=loss, stats=stats)
-
-
-@on_device
-def _seg_loss_bwd(dloss, stats, arg, rec, VP, W, pt: PartTable, merge=True, deterministic=False):
-    """_seg_bwd fed with dloss (B, W*W) + the forward's stats instead of dseg (smplr_seg_loss_bwd)."""
-    lib = _lib.load()
-    B = arg.shape[0]
-    ws = _workspace(lib.smplr_seg_bwd_workspace(B, W), dloss)
-    dproj = _empty((B, VP, 3), dloss) if merge else None
-    check(lib.smplr_seg_loss_bwd(ptr(dloss), ptr(stats), ptr(arg), ptr(rec), B, VP, W, pt.P, pt.K, ptr(dproj), ptr(ws),
-                                 1 if deterministic else 0, stream()), "smplr_seg_loss_bwd")
-    return dproj if merge else (ws, int(lib.smplr_seg_bwd_nsplit(B, W)))
+_seg_raster_loss = _seg_raster_ex       # (its loss-epilogue use by the name tests and tools call)
 
 
 @on_device
@@ -500,12 +506,11 @@ def _seg_bin(proj, mask, W, pt: PartTable, grid_wh=0, ref_compat=True, rec=None,
     grid_wh = 0 reads it.  -> (ws, rec): what _seg_raster needs."""
     lib = _lib.load()
     B, VP = proj.shape[0], proj.shape[1]
-    if VP != pt.VP:
-        raise RuntimeError("projects has %d vertices but the part table expects %d" % (VP, pt.VP))
+    _check_vp(VP, pt)
     if ws is None:
         ws = _workspace(lib.smplr_seg_workspace(B, VP, W, pt.P, pt.K), proj)
     if rec is None:
-        rec = _empty((B, lib.smplr_seg_slots(pt.P, pt.K), 4), proj)
+        rec = _seg_buffers(B, W, pt, proj, seg=False)[2]
     check(lib.smplr_seg_bin(ptr(proj), ptr(mask), B, VP, W, int(grid_wh), 1 if ref_compat else 0, ptr(pt.part_pos),
                             ptr(pt.part_off), pt.P, pt.K, ptr(ws), ptr(rec), ptr(vslot), stream()), "smplr_seg_bin")
     return ws, rec
@@ -515,26 +520,32 @@ def _seg_bin(proj, mask, W, pt: PartTable, grid_wh=0, ref_compat=True, rec=None,
 def _seg_raster(ws, rec, B, W, pt: PartTable, out=None):
     """Stage 2 alone (smplr_seg_raster) over a binned workspace -> seg, arg."""
     lib = _lib.load()
-    if out is not None:
-        seg, arg = out
-    else:
-        seg = _empty((B, W, W, pt.P + 1), rec)
-        arg = _empty((B, W, W, 32), rec, torch.int16)
+    seg, arg = out if out is not None else _seg_buffers(B, W, pt, rec, rec=False)[:2]
     check(lib.smplr_seg_raster(B, W, pt.P, pt.K, ptr(ws), ptr(rec), ptr(seg), ptr(arg), stream()), "smplr_seg_raster")
     return seg, arg
 
 
 @on_device
-def _seg_bwd(dseg, arg, rec, VP, W, pt: PartTable, merge=True, deterministic=False):
+def _seg_bwd(dseg, arg, rec, VP, W, pt: PartTable, merge=True, deterministic=False, stats=None):
     """merge=True -> dproj (B,VP,3).  merge=False -> (part, nsplit): the per-row-block slot sums, to be handed
-    to _smpl_bwd(seg_grad=(part, vslot, nsplit)) which gathers them by vertex (no merge launch, no dproj)."""
+    to _smpl_bwd(seg_grad=(part, vslot, nsplit)) which gathers them by vertex (no merge launch, no dproj).
+    stats: the fused loss head's (_seg_raster_ex / _skin_vis_seg with labels) - the first operand is then dloss (B, W*W),
+    the cotangent of that loss, instead of dseg (smplr_seg_loss_bwd)."""
     lib = _lib.load()
     B = arg.shape[0]
     ws = _workspace(lib.smplr_seg_bwd_workspace(B, W), dseg)
     dproj = _empty((B, VP, 3), dseg) if merge else None
-    check(lib.smplr_seg_bwd(ptr(dseg), ptr(arg), ptr(rec), B, VP, W, pt.P, pt.K, ptr(dproj), ptr(ws),
-                            1 if deterministic else 0, stream()), "smplr_seg_bwd")
+    tail = (ptr(arg), ptr(rec), B, VP, W, pt.P, pt.K, ptr(dproj), ptr(ws), 1 if deterministic else 0, stream())
+    if stats is None:
+        check(lib.smplr_seg_bwd(ptr(dseg), *tail), "smplr_seg_bwd")
+    else:
+        check(lib.smplr_seg_loss_bwd(ptr(dseg), ptr(stats), *tail), "smplr_seg_loss_bwd")
     return dproj if merge else (ws, int(lib.smplr_seg_bwd_nsplit(B, W)))
+
+
+def _seg_loss_bwd(dloss, stats, arg, rec, VP, W, pt: PartTable, merge=True, deterministic=False):
+    """_seg_bwd fed with dloss (B, W*W) + the forward's stats instead of dseg."""
+    return _seg_bwd(dloss, arg, rec, VP, W, pt, merge, deterministic, stats=stats)
 
 
 def raster_plan(rec, W, pt: PartTable):
@@ -543,7 +554,6 @@ def raster_plan(rec, W, pt: PartTable):
     -> dict: far_records (B,) = each mesh's far-reaching list, padded per part; tile_records (tiles,) = what one pass
     over a tile's LDS table takes (0: the tile walks the list with scalar loads); passes (B, tiles); blocks,
     blocks_multi_pass, blocks_scalar_walk, passes_max; pair_lanes, part_ranges."""
-    import ctypes
     lib = _lib.load()
     B = rec.shape[0]
     info = (ctypes.c_int32 * 8)()
@@ -572,34 +582,33 @@ def argmin_vertices(arg, rec):
     return torch.where(flat >= 0, got, torch.full_like(got, -1)).reshape(slots.shape)
 
 
-@on_device
 def _silh_fwd(proj, W, out=None, hint=None):
     """hint (B,W,W), optional: the 31-part rasteriser's per-pixel largest score of the same meshes at the same W
     (_seg_raster_ex(vmax=)): bounds the exact search, same outputs bit for bit (smplr_silh_fwd_hint)."""
-    lib = _lib.load()
-    B, VP = proj.shape[0], proj.shape[1]
-    if out is not None:
-        silh, arg = out
-    else:
-        silh = _empty((B, W, W, 2), proj)
-        arg = _empty((B, W, W), proj, torch.int32)
-    ws = _workspace(lib.smplr_silh_workspace(B, VP, W), proj)
-    check(lib.smplr_silh_fwd_hint(ptr(proj), ptr(hint), B, VP, W, ptr(silh), ptr(arg), ptr(ws), stream()),
-          "smplr_silh_fwd_hint")
-    return silh, arg
+    return _silh_fwd_loss(proj, W, out=out, hint=hint)[:2]
 
 
 @on_device
-def _silh_bwd(dsilh, silh, arg, proj, W, deterministic=False):
+def _silh_bwd(dsilh, silh, arg, proj, W, deterministic=False, k=None):
+    """k (B, W*W), the loss head's d loss / d s: the first operand is then dloss (B, W*W), and g = dloss * k stands in
+    for dsilh (smplr_silh_loss_bwd)."""
     lib = _lib.load()
     B, VP = proj.shape[0], proj.shape[1]
     dproj = _empty((B, VP, 3), proj)
-    check(lib.smplr_silh_bwd(ptr(dsilh), ptr(silh), ptr(arg), ptr(proj), B, VP, W, ptr(dproj),
-                             1 if deterministic else 0, stream()), "smplr_silh_bwd")
+    tail = (ptr(silh), ptr(arg), ptr(proj), B, VP, W, ptr(dproj), 1 if deterministic else 0, stream())
+    if k is None:
+        check(lib.smplr_silh_bwd(ptr(dsilh), *tail), "smplr_silh_bwd")
+    else:
+        check(lib.smplr_silh_loss_bwd(ptr(dsilh), ptr(k), *tail), "smplr_silh_loss_bwd")
     return dproj
 
 
-def _silh_loss_args(labels, class_w, conf, B, W, like):
+def _silh_loss_bwd(dloss, k, silh, arg, proj, W, deterministic=False):
+    """_silh_bwd fed g = dloss * k (B, W*W each) instead of dsilh."""
+    return _silh_bwd(dloss, silh, arg, proj, W, deterministic, k=k)
+
+
+def _silh_loss_args(labels, class_w, conf, B, W, device):
     if labels.dtype != torch.int32 or tuple(labels.shape) != (B, W, W):
         raise RuntimeError("silhouette labels must be (%d, %d, %d) int32, got %s %s"
                            % (B, W, W, tuple(labels.shape), labels.dtype))
@@ -608,12 +617,11 @@ def _silh_loss_args(labels, class_w, conf, B, W, like):
         class_w = require_cuda(class_w, "class_w")
         if class_w.numel() != 2:
             raise RuntimeError("the silhouette loss takes 2 class weights, got %d" % class_w.numel())
-    if conf is not None and (not conf.is_cuda or conf.dtype != torch.int64 or tuple(conf.shape) != (3, 2)
-                             or not conf.is_contiguous()):
+    if conf is not None and not _is_confusion(conf, 2, kernel_operand=True):
         raise RuntimeError("the silhouette confusion must be a contiguous (3, 2) int64 device tensor (SegConfusion(2).counts)")
     for name, t in (("labels", labels), ("class_w", class_w), ("confusion", conf)):
-        if t is not None and t.device != like.device:
-            raise RuntimeError("silhouette %s lives on %s, the silhouette on %s" % (name, t.device, like.device))
+        if t is not None and t.device != device:
+            raise RuntimeError("silhouette %s lives on %s, the silhouette on %s" % (name, t.device, device))
     return labels, class_w
 
 
@@ -624,7 +632,7 @@ def _silh_loss_fwd(silh, labels, class_w=None, gamma=0.0, conf=None, out=None):
     lib = _lib.load()
     silh = require_cuda(silh, "silh")
     B, W = silh.shape[0], silh.shape[1]
-    labels, class_w = _silh_loss_args(labels, class_w, conf, B, W, silh)
+    labels, class_w = _silh_loss_args(labels, class_w, conf, B, W, silh.device)
     loss, k = out if out is not None else (_empty((B, W * W), silh), _empty((B, W * W), silh))
     check(lib.smplr_silh_loss_fwd(ptr(silh), ptr(labels), ptr(class_w), float(gamma), B, W, ptr(loss), ptr(k), ptr(conf),
                                   stream()), "smplr_silh_loss_fwd")
@@ -632,32 +640,27 @@ def _silh_loss_fwd(silh, labels, class_w=None, gamma=0.0, conf=None, out=None):
 
 
 @on_device
-def _silh_fwd_loss(proj, W, labels, class_w=None, gamma=0.0, conf=None, out=None, hint=None):
-    """_silh_fwd + _silh_loss_fwd as one call (smplr_silh_fwd_loss: the loss head as the pixel-per-lane kernel's epilogue
-    where that kernel runs, else behind the forward) -> silh, arg, loss, k; the same bits as the two calls."""
+def _silh_fwd_loss(proj, W, labels=None, class_w=None, gamma=0.0, conf=None, out=None, hint=None):
+    """The silhouette forward -> silh, arg, loss, k.  Without labels that is smplr_silh_fwd_hint and loss = k = None
+    (out = (silh, arg)).  With labels: _silh_fwd + _silh_loss_fwd as one call (smplr_silh_fwd_loss: the loss head as the
+    pixel-per-lane kernel's epilogue where that kernel runs, else behind the forward), out = (silh, arg, loss, k); the
+    same bits as the two calls."""
     lib = _lib.load()
     B, VP = proj.shape[0], proj.shape[1]
-    labels, class_w = _silh_loss_args(labels, class_w, conf, B, W, proj)
-    if out is not None:
-        silh, arg, loss, k = out
-    else:
+    silh, arg, loss, k = (tuple(out) + (None, None))[:4] if out is not None else (None,) * 4
+    if silh is None:
         silh, arg = _empty((B, W, W, 2), proj), _empty((B, W, W), proj, torch.int32)
-        loss, k = _empty((B, W * W), proj), _empty((B, W * W), proj)
     ws = _workspace(lib.smplr_silh_workspace(B, VP, W), proj)
+    if labels is None:
+        check(lib.smplr_silh_fwd_hint(ptr(proj), ptr(hint), B, VP, W, ptr(silh), ptr(arg), ptr(ws), stream()),
+              "smplr_silh_fwd_hint")
+        return silh, arg, None, None
+    labels, class_w = _silh_loss_args(labels, class_w, conf, B, W, proj.device)
+    if loss is None:
+        loss, k = _empty((B, W * W), proj), _empty((B, W * W), proj)
     check(lib.smplr_silh_fwd_loss(ptr(proj), ptr(hint), ptr(labels), ptr(class_w), float(gamma), B, VP, W, ptr(silh),
                                   ptr(arg), ptr(loss), ptr(k), ptr(conf), ptr(ws), stream()), "smplr_silh_fwd_loss")
     return silh, arg, loss, k
-
-
-@on_device
-def _silh_loss_bwd(dloss, k, silh, arg, proj, W, deterministic=False):
-    """_silh_bwd fed g = dloss * k (B, W*W each) instead of dsilh (smplr_silh_loss_bwd)."""
-    lib = _lib.load()
-    B, VP = proj.shape[0], proj.shape[1]
-    dproj = _empty((B, VP, 3), proj)
-    check(lib.smplr_silh_loss_bwd(ptr(dloss), ptr(k), ptr(silh), ptr(arg), ptr(proj), B, VP, W, ptr(dproj),
-                                  1 if deterministic else 0, stream()), "smplr_silh_loss_bwd")
-    return dproj
 
 
 # --------------------------------------------------------------------------- autograd nodes
@@ -773,8 +776,8 @@ class SilhRasterFn(torch.autograd.Function):
 
 def _focal_targets(target, npix, C):
     """labels (int class ids, npix) -> (labels, None); dense y_true (npix, C) -> (None, y_true)."""
-    if target.dtype in (torch.int64, torch.int32, torch.int16, torch.uint8):
-        if target.numel() != npix:
+    if _is_class_map(target):
+        if not _is_class_map(target, npix):
             raise RuntimeError("labels hold %d entries for %d pixels" % (target.numel(), npix))
         return require_cuda(target.to(torch.int32), "labels", torch.int32), None
     if target.numel() != npix * C:
@@ -1109,6 +1112,94 @@ FUSE_SKIN_FROM_B = int(os.environ.get("SMPLR_FUSE_SKIN_FROM_B", "768"))
 SILH_HINT_MAX_W = 48     # smplr_silh_fwd_hint uses the hint in silh_px_kernel only (W <= 48, silh.hip)
 
 
+@dataclass(frozen=True)
+class DecoderPlan:
+    """What one DecoderFn.forward computes, writes and launches: decoder_plan's answer, plain values only."""
+    VP: int                  # vertices the rasterisers see: ceil(V / vertex_sampling)
+    seg: bool                # the 31-part head runs
+    loss: bool               # ... with the loss head as its epilogue
+    silh: bool               # the silhouette head runs
+    silh_loss: bool          # ... with its loss head
+    want_verts: bool         # verts / proj / mask / seg are written out (arg, rec and vslot always are, with `seg`)
+    want_proj: bool
+    want_mask: bool
+    want_seg: bool
+    vmax: bool               # the part rasteriser writes each pixel's largest score as the silhouette rasteriser's hint
+    fuse_skin: bool          # the binning workgroups skin their own vertices (_skin_vis_seg), else _skin_fwd + two stages
+    pose_blend_below: int    # chunks of fewer meshes run pose + blend as one launch (0: always two)
+
+    def pose_blend_one_launch(self, n):
+        return n < self.pose_blend_below
+
+
+def decoder_plan(B, W, Ws, V, vs, P, opts: DecoderOpts, bf16x3, sparse_weights, fits) -> DecoderPlan:
+    """The decisions of a decoder pass from plain values (no tensor, no library: it runs without a device).
+    B meshes at W x W, the silhouette at Ws (0: none), V vertices sampled by vs, a part table of P parts, the options;
+    bf16x3 / sparse_weights: whether the constants carry blend3_fwd / lbs_top4; fits: smplr_skin_vis_seg_fits' answer.
+    The thresholds are this module's, read at the call, as are SMPLR_FUSE_SKIN and SMPLR_SILH_HINT."""
+    silh, seg = Ws > 0, bool(opts.seg)
+    loss = seg and opts.loss is not None
+    # both heads at one resolution: the part rasteriser hands the silhouette rasteriser each pixel's largest part
+    # score - an upper bound of the distance to the nearest vertex that spares it its own search for one
+    # (only where the silhouette rasteriser reads it: its pixel-per-lane kernel, W <= SILH_HINT_MAX_W - beyond that
+    # the step would pay for a (B,W,W) store and the slower `_ex` launch shape for a hint nobody uses)
+    vmax = (silh and seg and Ws == W and W <= SILH_HINT_MAX_W and P == 31
+            and os.environ.get("SMPLR_SILH_HINT", "1") != "0")
+    # the binning workgroups skin their own vertices (one launch less) when the skinning rows are sparse, every
+    # vertex is rasterised and the mesh fits the binning workgroup's LDS; SMPLR_FUSE_SKIN=0 keeps the two calls
+    fuse_skin = (seg and bool(sparse_weights) and vs == 1 and bool(fits)
+                 and (B < FUSE_SKIN_BELOW_B or B >= FUSE_SKIN_FROM_B) and os.environ.get("SMPLR_FUSE_SKIN", "1") != "0")
+    return DecoderPlan(
+        VP=(V + vs - 1) // vs, seg=seg, loss=loss, silh=silh, silh_loss=opts.silh_loss is not None,
+        want_verts=bool(opts.want_verts), want_proj=bool(opts.want_proj) or silh, want_mask=bool(opts.want_mask) and seg,
+        want_seg=seg and (bool(opts.want_seg) or not loss), vmax=vmax, fuse_skin=fuse_skin,
+        # (from POSE_BLEND_SPLIT_B on also the bf16x3 constants take two launches: the same bits, see there)
+        pose_blend_below=POSE_BLEND_SPLIT_B if bf16x3 else 0)
+
+
+def _decoder_operands(opts: DecoderOpts, P, B, W, Ws, num_cam, grid_wh, device):
+    """DecoderFn.forward's refusals, in their order, and the loss heads' operands as the kernels read them
+    -> (labels, class_w, gamma, conf), (silh_labels, silh_class_w, silh_gamma, silh_conf); labels None = no such loss."""
+    if not opts.seg and not Ws:
+        raise RuntimeError("DecoderFn: no head asked for (opts.seg = False needs a silhouette)")
+    if not 4 <= int(num_cam) <= 16:
+        raise RuntimeError("DecoderFn: the projection needs the 4 camera columns, num_cam must be in 4..16 (got %r)"
+                           % (num_cam,))
+    # (smplr_seg_bin reads grid_wh <= 0 as "the mask is an INPUT": the decoder always computes it, so a bad value
+    # would rasterise from an uninitialised mask on the two-call path - refuse it here for every path)
+    if opts.seg and not 0 < int(grid_wh) <= 128:
+        raise RuntimeError("DecoderFn: grid_wh must be in 1..128 (got %r)" % (grid_wh,))
+    labels = class_w = None
+    gamma = 0.0
+    if opts.seg and opts.loss is not None:
+        labels, class_w, gamma = opts.loss
+        if P != 31:
+            raise RuntimeError("the fused loss head is the 32-class one (P = 31)")
+        if not _is_class_map(labels, B * W * W):
+            raise RuntimeError("fused loss: labels must be an integer class map of %d x %d x %d entries" % (B, W, W))
+        labels = require_cuda(labels.to(torch.int32).reshape(B, W, W), "labels", torch.int32)
+        if class_w is not None:
+            class_w = require_cuda(class_w, "class_w")
+            if class_w.numel() != 32:
+                raise RuntimeError("class_w needs 32 entries")
+    conf = opts.confusion if opts.seg else None
+    if conf is not None:
+        if labels is None:
+            raise RuntimeError("DecoderOpts.confusion rides on the fused loss: it needs DecoderOpts.loss")
+        if not _is_confusion(conf, 32, kernel_operand=True) or conf.device != device:
+            raise RuntimeError("DecoderOpts.confusion must be a contiguous (33, 32) int64 tensor on %s" % device)
+    sl_labels = sl_w = None
+    sl_gamma, sconf = 0.0, opts.silh_confusion
+    if opts.silh_loss is not None:
+        if not Ws:
+            raise RuntimeError("DecoderOpts.silh_loss needs the silhouette head")
+        sl_labels, sl_w, sl_gamma = opts.silh_loss
+        sl_labels, sl_w = _silh_loss_args(sl_labels, sl_w, sconf, B, Ws, device)
+    elif sconf is not None:
+        raise RuntimeError("DecoderOpts.silh_confusion rides on the fused silhouette loss: it needs DecoderOpts.silh_loss")
+    return (labels, class_w, gamma, conf), (sl_labels, sl_w, sl_gamma, sconf)
+
+
 class DecoderFn(torch.autograd.Function):
     """The model.py:108-118 chain as ONE autograd node.
 
@@ -1133,130 +1224,66 @@ class DecoderFn(torch.autograd.Function):
                 grid_wh, ref_compat, with_silh, nchunk=1, deterministic=False, opts: Optional[DecoderOpts] = None):
         x = require_cuda(x, "x")
         ctx.set_materialize_grads(False)
-        lib = _lib.load()
         opts = opts if opts is not None else DecoderOpts()
         vs, W, B = int(vertex_sampling), int(img_wh), x.shape[0]
         # with_silh: False = no silhouette; True = at img_wh; an int = its own resolution
         # (train_stage2_silhouette.py:72-86 renders the silhouettes at `silhs_output_wh`)
         Ws = 0 if not with_silh else (W if with_silh is True else int(with_silh))
-        if not opts.seg and not with_silh:
-            raise RuntimeError("DecoderFn: no head asked for (opts.seg = False needs a silhouette)")
-        if not 4 <= int(num_cam) <= 16:
-            raise RuntimeError("DecoderFn: the projection needs the 4 camera columns, num_cam must be in 4..16 (got %r)"
-                               % (num_cam,))
-        # (smplr_seg_bin reads grid_wh <= 0 as "the mask is an INPUT": the decoder always computes it, so a bad value
-        # would rasterise from an uninitialised mask on the two-call path - refuse it here for every path)
-        if opts.seg and not 0 < int(grid_wh) <= 128:
-            raise RuntimeError("DecoderFn: grid_wh must be in 1..128 (got %r)" % (grid_wh,))
-        V, VP = consts.V, (consts.V + vs - 1) // vs
-        dev = x.device
-        none = lambda: torch.empty(0, device=dev)
+        (labels, class_w, gamma, conf), (sl_labels, sl_w, sl_gamma, sconf) = _decoder_operands(
+            opts, pt.P, B, W, Ws, num_cam, grid_wh, x.device)
+        V = consts.V
+        fits = opts.seg and bool(_lib.load().smplr_skin_vis_seg_fits(V, W, int(grid_wh)))
+        plan = decoder_plan(B, W, Ws, V, vs, pt.P, opts, consts.blend3_fwd is not None, consts.lbs_top4 is not None, fits)
+        VP = plan.VP
         Rs, J = _empty((B, 24, 9), x), _empty((B, 24, 3), x)
         A, Jt = _empty((B, 24, 12), x), _empty((B, 24, 3), x)
         v_posed = _empty((B, V, 3), x)
-        want_proj = opts.want_proj or bool(with_silh)
-        verts = _empty((B, V, 3), x) if opts.want_verts else None
-        proj = _empty((B, VP, 3), x) if want_proj else None
-        mask = _empty((B, VP), x) if (opts.want_mask and opts.seg) else None
-        loss_spec = opts.loss if opts.seg else None
-        labels = class_w = None
-        gamma = 0.0
-        if loss_spec is not None:
-            labels, class_w, gamma = loss_spec
-            if pt.P != 31:
-                raise RuntimeError("the fused loss head is the 32-class one (P = 31)")
-            if labels.numel() != B * W * W or labels.dtype not in (torch.int64, torch.int32, torch.int16, torch.uint8):
-                raise RuntimeError("fused loss: labels must be an integer class map of %d x %d x %d entries" % (B, W, W))
-            labels = require_cuda(labels.to(torch.int32).reshape(B, W, W), "labels", torch.int32)
-            if class_w is not None:
-                class_w = require_cuda(class_w, "class_w")
-                if class_w.numel() != 32:
-                    raise RuntimeError("class_w needs 32 entries")
-        conf = opts.confusion if opts.seg else None
-        if conf is not None:
-            if loss_spec is None:
-                raise RuntimeError("DecoderOpts.confusion rides on the fused loss: it needs DecoderOpts.loss")
-            if (not conf.is_cuda or conf.device != x.device or conf.dtype != torch.int64
-                    or tuple(conf.shape) != (33, 32) or not conf.is_contiguous()):
-                raise RuntimeError("DecoderOpts.confusion must be a contiguous (33, 32) int64 tensor on %s" % x.device)
-        want_seg = opts.seg and (opts.want_seg or loss_spec is None)
-        seg = _empty((B, W, W, pt.P + 1), x) if want_seg else None
-        if opts.seg:
-            arg = _empty((B, W, W, 32), x, torch.int16)
-            rec = _empty((B, lib.smplr_seg_slots(pt.P, pt.K), 4), x)
-            vslot = _empty((B, VP), x, torch.int16)
-        else:
-            arg = rec = vslot = None
-        loss = _empty((B, W * W), x) if loss_spec is not None else None
-        stats = _empty((B, W * W, 4), x) if loss_spec is not None else None
-        if with_silh:
+        o = dict(verts=_empty((B, V, 3), x) if plan.want_verts else None,
+                 proj=_empty((B, VP, 3), x) if plan.want_proj else None,
+                 mask=_empty((B, VP), x) if plan.want_mask else None,
+                 vslot=_empty((B, VP), x, torch.int16) if plan.seg else None,
+                 vmax=_empty((B, W, W), x) if plan.vmax else None)
+        o["seg"], o["arg"], o["rec"] = _seg_buffers(B, W, pt, x, seg=plan.want_seg) if plan.seg else (None,) * 3
+        o["loss"], o["stats"] = _loss_buffers(labels, None, None, B, W, x)
+        silh = sarg = sloss = sk = None
+        if plan.silh:
             silh, sarg = _empty((B, Ws, Ws, 2), x), _empty((B, Ws, Ws), x, torch.int32)
-        else:
-            silh = sarg = None
-        sl_spec = opts.silh_loss
-        sl_labels = sl_w = sloss = sk = None
-        sl_gamma, sconf = 0.0, opts.silh_confusion
-        if sl_spec is not None:
-            if not with_silh:
-                raise RuntimeError("DecoderOpts.silh_loss needs the silhouette head")
-            sl_labels, sl_w, sl_gamma = sl_spec
-            sl_labels, sl_w = _silh_loss_args(sl_labels, sl_w, sconf, B, Ws, x)
+        if plan.silh_loss:
             sloss, sk = _empty((B, Ws * Ws), x), _empty((B, Ws * Ws), x)
-        elif sconf is not None:
-            raise RuntimeError("DecoderOpts.silh_confusion rides on the fused silhouette loss: it needs DecoderOpts.silh_loss")
-        # both heads at one resolution: the part rasteriser hands the silhouette rasteriser each pixel's largest part
-        # score - an upper bound of the distance to the nearest vertex that spares it its own search for one
-        # (only where the silhouette rasteriser reads it: its pixel-per-lane kernel, W <= SILH_HINT_MAX_W - beyond that
-        # the step would pay for a (B,W,W) store and the slower `_ex` launch shape for a hint nobody uses)
-        vmax = _empty((B, W, W), x) if (with_silh and opts.seg and Ws == W and W <= SILH_HINT_MAX_W and pt.P == 31
-                                        and os.environ.get("SMPLR_SILH_HINT", "1") != "0") else None
-
-        # the binning workgroups skin their own vertices (one launch less) when the skinning rows are sparse, every
-        # vertex is rasterised and the mesh fits the binning workgroup's LDS; SMPLR_FUSE_SKIN=0 keeps the two calls
-        fuse_skin = (opts.seg and consts.lbs_top4 is not None and vs == 1
-                     and bool(lib.smplr_skin_vis_seg_fits(V, W, int(grid_wh)))
-                     and (B < FUSE_SKIN_BELOW_B or B >= FUSE_SKIN_FROM_B) and os.environ.get("SMPLR_FUSE_SKIN", "1") != "0")
-        sl = lambda t, lo, hi: None if t is None else t[lo:hi]
 
         def run(lo, hi):
             xs = x[lo:hi]
             n = hi - lo
-            if consts.blend3_fwd is not None and n < POSE_BLEND_SPLIT_B:
-                _pose_blend_fwd(xs, num_cam, consts, out=(Rs[lo:hi], J[lo:hi], A[lo:hi], Jt[lo:hi]), v_posed=v_posed[lo:hi])
+            pose = (Rs[lo:hi], J[lo:hi], A[lo:hi], Jt[lo:hi])
+            if plan.pose_blend_one_launch(n):
+                _pose_blend_fwd(xs, num_cam, consts, out=pose, v_posed=v_posed[lo:hi])
             else:
-                # (also the bf16x3 constants at large batch: the same bits from two launches, see POSE_BLEND_SPLIT_B)
-                coef = _pose_fwd(xs, num_cam, consts, out=(None, Rs[lo:hi], J[lo:hi], A[lo:hi], Jt[lo:hi]))[0]
+                coef = _pose_fwd(xs, num_cam, consts, out=(None,) + pose)[0]
                 _blend_fwd(coef, consts, n, out=v_posed[lo:hi])
-            if fuse_skin and (loss_spec is not None or vmax is not None):
-                _skin_vis_seg_fwd_ex(
-                    v_posed[lo:hi], A[lo:hi], consts, xs, W, pt, sl(labels, lo, hi), class_w, gamma, grid_wh, ref_compat,
-                    verts=sl(verts, lo, hi), proj=sl(proj, lo, hi), mask=sl(mask, lo, hi), seg=sl(seg, lo, hi),
-                    arg=arg[lo:hi], rec=rec[lo:hi], vslot=vslot[lo:hi], loss=sl(loss, lo, hi), stats=sl(stats, lo, hi),
-                    vmax=sl(vmax, lo, hi), conf=conf)
-            elif fuse_skin:
-                _skin_vis_seg_opt(v_posed[lo:hi], A[lo:hi], consts, xs, W, pt, grid_wh, ref_compat,
-                                  sl(verts, lo, hi), sl(proj, lo, hi), sl(mask, lo, hi), seg[lo:hi], arg[lo:hi],
-                                  rec[lo:hi], vslot[lo:hi])
+            c = {k: None if t is None else t[lo:hi] for k, t in o.items()}       # this chunk's rows of every output
+            lab = labels[lo:hi] if labels is not None else None
+            if plan.fuse_skin:
+                _skin_vis_seg(v_posed[lo:hi], A[lo:hi], consts, xs, W, pt, grid_wh, ref_compat, lab, class_w, gamma, conf,
+                              want=(), fits=True, **c)
             else:
                 # the two-call path needs proj (and the mask) in memory whatever the caller wants back
-                pj = proj[lo:hi] if proj is not None else _empty((n, VP, 3), x)
-                _skin_fwd(v_posed[lo:hi], A[lo:hi], consts, cam=xs, vertex_sampling=vs, want_verts=verts is not None,
-                          out=(sl(verts, lo, hi), pj))
-                if opts.seg:
-                    mk = mask[lo:hi] if mask is not None else _empty((n, VP), x)
-                    if loss_spec is not None or vmax is not None:
-                        ws_, _ = _seg_bin(pj, mk, W, pt, grid_wh, ref_compat, rec=rec[lo:hi], vslot=vslot[lo:hi])
-                        _seg_raster_ex(ws_, rec[lo:hi], n, W, pt, sl(labels, lo, hi), class_w, gamma, seg=sl(seg, lo, hi),
-                                       arg=arg[lo:hi], loss=sl(loss, lo, hi), stats=sl(stats, lo, hi), vmax=sl(vmax, lo, hi),
-                                       conf=conf)
-                    else:
-                        _vis_seg_fwd(pj, W, pt, grid_wh, ref_compat,
-                                     out=(mk, seg[lo:hi], arg[lo:hi], rec[lo:hi]), vslot=vslot[lo:hi])
-            if with_silh and sl_spec is not None:
-                _silh_fwd_loss(proj[lo:hi], Ws, sl_labels[lo:hi], sl_w, sl_gamma, sconf,
-                               out=(silh[lo:hi], sarg[lo:hi], sloss[lo:hi], sk[lo:hi]), hint=sl(vmax, lo, hi))
-            elif with_silh:
-                _silh_fwd(proj[lo:hi], Ws, out=(silh[lo:hi], sarg[lo:hi]), hint=sl(vmax, lo, hi))
+                pj = c["proj"] if plan.want_proj else _empty((n, VP, 3), x)
+                _skin_fwd(v_posed[lo:hi], A[lo:hi], consts, cam=xs, vertex_sampling=vs, want_verts=plan.want_verts,
+                          out=(c["verts"], pj))
+                mk = (c["mask"] if plan.want_mask else _empty((n, VP), x)) if plan.seg else None
+                if plan.seg and (plan.loss or plan.vmax):
+                    ws_, _ = _seg_bin(pj, mk, W, pt, grid_wh, ref_compat, rec=c["rec"], vslot=c["vslot"])
+                    _seg_raster_ex(ws_, c["rec"], n, W, pt, lab, class_w, gamma, seg=c["seg"], arg=c["arg"], loss=c["loss"],
+                                   stats=c["stats"], vmax=c["vmax"], conf=conf)
+                elif plan.seg:
+                    # (the same two launches as _seg_bin + _seg_raster_ex with no extras, from one ctypes call: in eager
+                    # mode the second call showed - about 10 us per step at B = 1)
+                    _vis_seg_fwd(pj, W, pt, grid_wh, ref_compat, out=(mk, c["seg"], c["arg"], c["rec"]), vslot=c["vslot"])
+            if plan.silh_loss:
+                _silh_fwd_loss(c["proj"], Ws, sl_labels[lo:hi], sl_w, sl_gamma, sconf,
+                               out=(silh[lo:hi], sarg[lo:hi], sloss[lo:hi], sk[lo:hi]), hint=c["vmax"])
+            elif plan.silh:
+                _silh_fwd_loss(c["proj"], Ws, out=(silh[lo:hi], sarg[lo:hi]), hint=c["vmax"])
 
         bounds = _chunk_bounds(B, nchunk)
         if B > 0:
@@ -1265,19 +1292,19 @@ class DecoderFn(torch.autograd.Function):
         ctx.Ws, ctx.VP = Ws, VP
         ctx.det = bool(deterministic)
         ctx.bounds = bounds
-        ctx.has_seg, ctx.has_loss, ctx.has_silh_loss = bool(opts.seg), loss_spec is not None, sl_spec is not None
-        E = none
-        saved = [x, Rs, J, A, v_posed, proj if with_silh else E(), arg if opts.seg else E(), rec if opts.seg else E(),
-                 silh if with_silh else E(), sarg if with_silh else E(), vslot if opts.seg else E(),
-                 stats if loss_spec is not None else E()]
-        if sl_spec is not None:
+        ctx.has_seg, ctx.has_loss, ctx.has_silh_loss = plan.seg, plan.loss, plan.silh_loss
+        E = lambda: torch.empty(0, device=x.device)
+        saved = [x, Rs, J, A, v_posed, o["proj"] if plan.silh else E(), o["arg"] if plan.seg else E(),
+                 o["rec"] if plan.seg else E(), silh if plan.silh else E(), sarg if plan.silh else E(),
+                 o["vslot"] if plan.seg else E(), o["stats"] if plan.loss else E()]
+        if plan.silh_loss:
             saved.append(sk)
         ctx.save_for_backward(*saved)
-        outs = [t if t is not None else E() for t in (verts, proj, mask, seg, silh, Jt, loss)]
+        outs = [t if t is not None else E() for t in (o["verts"], o["proj"], o["mask"], o["seg"], silh, Jt, o["loss"])]
         ctx.mark_non_differentiable(outs[2])
-        if loss_spec is not None:
+        if plan.loss:
             ctx.mark_non_differentiable(outs[3])         # with a fused loss the scores are a by-product, not a path
-        if sl_spec is not None:
+        if plan.silh_loss:
             ctx.mark_non_differentiable(outs[4])         # likewise the silhouette (the monitor pass and the backward read it)
             outs.append(sloss)                           # the eighth output exists only with a fused silhouette loss
         return tuple(outs)
@@ -1305,14 +1332,14 @@ class DecoderFn(torch.autograd.Function):
                                         deterministic=ctx.det)
                 seg_grad = (part, vslot[lo:hi], nsplit)
             elif dloss is not None:
-                part, nsplit = _seg_loss_bwd(dloss[lo:hi], stats[lo:hi], arg[lo:hi], rec[lo:hi], VP, ctx.W, ctx.pt,
-                                             merge=False, deterministic=ctx.det)
+                part, nsplit = _seg_bwd(dloss[lo:hi], arg[lo:hi], rec[lo:hi], VP, ctx.W, ctx.pt, merge=False,
+                                        deterministic=ctx.det, stats=stats[lo:hi])
                 seg_grad = (part, vslot[lo:hi], nsplit)
             if dsilh is not None:
                 d2 = _silh_bwd(dsilh[lo:hi], silh[lo:hi], sarg[lo:hi], proj[lo:hi], ctx.Ws, ctx.det)
                 dproj = d2 if dproj is None else dproj + d2
             elif dsloss is not None:
-                dproj = _silh_loss_bwd(dsloss[lo:hi], sk[lo:hi], silh[lo:hi], sarg[lo:hi], proj[lo:hi], ctx.Ws, ctx.det)
+                dproj = _silh_bwd(dsloss[lo:hi], silh[lo:hi], sarg[lo:hi], proj[lo:hi], ctx.Ws, ctx.det, k=sk[lo:hi])
             if dproj_in is not None:
                 dproj = dproj_in[lo:hi] if dproj is None else dproj + dproj_in[lo:hi]
             dv = dverts[lo:hi] if dverts is not None else None
@@ -1324,13 +1351,3 @@ class DecoderFn(torch.autograd.Function):
         if x.shape[0] > 0:
             _run_chunks(ctx.bounds, x.device, run)
         return (dx,) + (None,) * 11
-
-
-@on_device
-def _skin_vis_seg_opt(v_posed, A, c, cam, W, pt, grid_wh, ref_compat, verts, proj, mask, seg, arg, rec, vslot):
-    """smplr_skin_vis_seg_fwd with optional verts / proj / mask (None = not written)."""
-    lib = _lib.load()
-    B, V = v_posed.shape[0], c.V
-    ws = _workspace(lib.smplr_seg_workspace(B, V, W, pt.P, pt.K), v_posed)
-    _skin_vis_seg_call(v_posed, A, c, cam, W, pt, grid_wh, ref_compat, ws, verts=verts, proj=proj, mask=mask, seg=seg,
-                       arg=arg, rec=rec, vslot=vslot)
