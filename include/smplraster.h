@@ -575,6 +575,33 @@ int smplr_scan_bwd(const float *verts, const int32_t *faces, const float *points
                    const float *resid, const int32_t *vpoint, const int32_t *status, const float *g_d2, const float *g_vd2,
                    int B, int V, int F, int N, float *dverts, void *stream);
 
+/* ---- self-penetration of one mesh: nearest vertex of a colliding part, inside test, energy, gradient (beyond the
+ * reference); INTEGRATION.md 4o ------------------------------------------------------------------------------------------------
+ * verts (B, V, 3) fp32; faces (F, 3), vf_off (V + 1), vf_face (3 F) int32: the mesh and its vertex -> face CSR (faces in
+ * increasing id per vertex); part (V) int32 in -1 .. P - 1 (anything else counts as -1); collide (P, P) uint8, row = the
+ * query's part, column = the candidate's, diagonal ignored; perm (nperm) int32 or NULL: the vertices 0 .. V - 1 in
+ * part-major order, each exactly once, every part's run padded with -1 to a multiple of 256 slots (V <= nperm <= 2^25;
+ * penetration.part_major_order builds it), which switches the pruned walk on (NULL, or the environment variable
+ * SMPLR_PEN_UNPRUNED set to anything but "0": the plain walk; the outputs are the same bits either way).
+ * smplr_pen_fwd, per vertex i: near (B, V) int32 = the j with part[i] >= 0, part[j] >= 0, part[i] != part[j],
+ *   collide[part[i], part[j]] != 0 and the smallest |v_i - v_j|^2 (fp32 search relative to v_i, ties to the lower j), d2
+ *   (B, V) that squared distance recomputed in fp64 and rounded once (no candidate: near -1, d2 +Inf); inside (B, V) uint8 =
+ *   ((d_x n_x + d_y n_y) + d_z n_z) < 0 in fp64 with d = v_i - v_near and n = the sum of cross(v_b - v_a, v_c - v_a) over the
+ *   faces incident to near in the CSR's order; e (B, V) = inside ? d2 : 0.
+ * smplr_pen_bwd: dverts[b, k] = 2 g_k inside_k (v_k - v_near(k)) - sum over i with near(i) = k and inside_i, in increasing i, of
+ *   2 g_i (v_i - v_k); fp64, rounded once, no atomics: the same bits on every launch and in any batch.  near, inside and
+ *   status are the forward's; every row is written.
+ * status (B) int32: SMPLR_PEN_NONFINITE when a coordinate of the mesh is NaN / Inf - its e, d2 and dverts rows are NaN, near
+ *   -1, inside 0; other meshes are not affected.  A CSR offset, face or corner outside its range is skipped.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= V <= 2^24, 0 <= F <= 2^24, 0 <= P <= 31, B >= 0 (B = 0 is a no-op);
+ * no null pointer except perm (and faces, vf_face with F = 0, collide with P = 0).                                          */
+#define SMPLR_PEN_NONFINITE 1
+int smplr_pen_fwd(const float *verts, const int32_t *faces, const int32_t *vf_off, const int32_t *vf_face, const int32_t *part,
+                  const uint8_t *collide, const int32_t *perm, int nperm, int B, int V, int F, int P, float *e, float *d2,
+                  int32_t *near, uint8_t *inside, int32_t *status, void *stream);
+int smplr_pen_bwd(const float *verts, const int32_t *near, const uint8_t *inside, const int32_t *status, const float *g, int B,
+                  int V, float *dverts, void *stream);
+
 /* ---- prediction figures: predict.py:28-77 (_seg.png, _projects.png, _verts_overlay.png), train.py:283-290,
  * train_stage2_silhouette.py:318-329, predict_realtime.py:75-96; INTEGRATION.md 4h -------------------------------------
  * One launch each on the caller's stream; no workspace, no allocation, no synchronisation, no global atomics.  Colours

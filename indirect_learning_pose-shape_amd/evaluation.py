@@ -207,3 +207,24 @@ def evaluate_scans(smpl_model, smpl_layer, batches, topo):
     nan = float("nan")
     return {"scan_to_mesh": st[0] / st[1] if st[1] else nan, "mesh_to_scan": st[2] / st[3] if st[3] else nan,
             "points": int(st[1]), "vertices": int(st[3]), "count": int(st[4]), "nonfinite": int(st[5])}
+
+
+def evaluate_penetration(verts, topo, collide=None):
+    """Self-penetration of meshes verts (B, V, 3) fp32 (metres), one `penetration.self_penetration` call: topo the meshes'
+    `render.MeshTopology`, collide None (the default part-pair table) or a (P, P) table of 0 / 1.
+    -> dict(inside (B,) int64 = vertices inside another part per mesh, max_depth (B,) float64 = the largest sqrt(d2) among
+    them in metres (0 without one), total_inside, max_depth_overall, meshes_with_penetration, count = meshes counted,
+    nonfinite = meshes left out because they held a NaN or Inf (their inside and max_depth are 0)).  The per-mesh tensors
+    stay on verts' device; the totals are read back once at the end."""
+    from .penetration import self_penetration
+    with torch.no_grad():
+        _, det = self_penetration(verts, topo, collide, return_details=True)
+    ok = det["status"] == 0
+    ins = det["inside"] & ok[:, None]
+    count = ins.sum(1)
+    depth = torch.where(ins, det["d2"].to(torch.float64), torch.zeros((), dtype=torch.float64, device=verts.device)).sqrt()
+    depth = depth.amax(1) if depth.shape[1] else depth.sum(1)
+    tot = torch.stack([count.sum().to(torch.float64), depth.max() if depth.numel() else depth.sum(),
+                       (count > 0).sum().to(torch.float64), ok.sum().to(torch.float64)]).cpu()
+    return {"inside": count, "max_depth": depth, "total_inside": int(tot[0]), "max_depth_overall": float(tot[1]),
+            "meshes_with_penetration": int(tot[2]), "count": int(tot[3]), "nonfinite": int(verts.shape[0]) - int(tot[3])}

@@ -74,6 +74,17 @@ group, per column (ignored where tie is set or the weight is 0).  ONE smplr_fit_
      the column moves.
 G = 1 without `smooth` is the plain call (and `fit_step` makes the plain launch then).  `FitState` keeps its layout: a group's
 rows carry copies of the group's scalars.
+
+Self-penetration (penetration.py, csrc/penetration.hip; SMPLify's fourth regulariser, the one that needs the mesh):
+
+    fitter = ParamFitter(smpl_path, penetration=True)            # or a render.MeshTopology; ScanFitter(..., penetration=True)
+    r = fitter.fit(labels, stages=[(100, cs), (100, cs)], pen_weight=[0.0, 50.0])   # one float, or one per stage
+
+With E_b = pen_weight mean_V(e[b, :]), e = `self_penetration` of the iteration's vertices: E_b is added to every column of
+the detached loss handed to `fit_step` (so the recorded loss, the best iterate and the patience stop see it), and its gradient
+enters `torch.autograd.grad` through a preallocated cotangent pen_weight / V on e.  The weight lives in a device scalar and the
+cotangent in a device tensor, both rewritten at stage boundaries, so a captured graph follows them.  `fit_step` and
+csrc/fit.hip are untouched; without `penetration` a fitter runs exactly the launches it ran before.
 """
 from __future__ import annotations
 
@@ -624,8 +635,61 @@ def _stage_prior_weights(prior, prior_weights, stage_list):
     return [check_prior_weights(w) for w in (pw if per_stage else [pw] * len(stage_list))]
 
 
+def _stage_pen_weights(pen_weight, stage_list):
+    """`fit`'s pen_weight (None: 1, one float, or a list of one float per stage) -> one float per stage."""
+    pw = 1.0 if pen_weight is None else pen_weight
+    per_stage = isinstance(pw, (list, tuple))
+    if per_stage and len(pw) != len(stage_list):
+        raise ValueError("pen_weight lists %d weights for %d stages" % (len(pw), len(stage_list)))
+    out = [float(w) for w in (pw if per_stage else [pw] * len(stage_list))]
+    if any(not math.isfinite(w) or w < 0 or w > float(np.finfo(np.float32).max) for w in out):
+        raise ValueError("pen_weight must be finite and >= 0, got %r" % (pen_weight,))
+    return out
+
+
 class _Fitter:
     """What `ParamFitter` and `ScanFitter` share; a fitter adds its data term (`_iteration`) and sets num_cam and P."""
+    pen_topo = None            # a render.MeshTopology when the fitter was built with `penetration`
+    pen_collide = None         # its part-pair table (None: `penetration.part_collision_table(topo, 1)`)
+
+    def _pen_init(self, penetration, model, collide=None):
+        """`penetration` of a fitter's constructor: None / False (no term), True (the faces of `model`) or a MeshTopology."""
+        if penetration is None or penetration is False:
+            return
+        from .penetration import check_collide
+        from .render import MeshTopology
+        if penetration is True:
+            if getattr(model, "faces", None) is None:
+                raise ValueError("this SMPL model carries no faces: pass penetration=MeshTopology(faces, num_verts)")
+            penetration = MeshTopology(model.faces, model.num_verts)
+        if not all(hasattr(penetration, a) for a in ("faces", "vf_off", "vf_face", "vertex_part", "num_verts", "on")):
+            raise TypeError("penetration must be True or a render.MeshTopology")
+        if penetration.num_verts != model.num_verts:
+            raise ValueError("the topology has %d vertices, the model %d" % (penetration.num_verts, model.num_verts))
+        self.pen_topo, self.pen_collide = penetration, check_collide(collide, penetration)
+
+    def _pen_state(self, pen_weight, stage_list, B, dev):
+        """None without the term; else dict(w (1,) and cot (B, V) device tensors, stages = one weight per stage, V)."""
+        if self.pen_topo is None:
+            if pen_weight is not None:
+                raise ValueError("pen_weight goes with a fitter built with penetration=...")
+            return None
+        V = self.pen_topo.num_verts
+        return dict(w=torch.zeros(1, dtype=torch.float32, device=dev), cot=torch.zeros((B, V), dtype=torch.float32, device=dev),
+                    stages=_stage_pen_weights(pen_weight, stage_list), V=V)
+
+    @staticmethod
+    def _pen_set(pen, w):
+        """The weight of a stage into the device scalar and the cotangent (outside any captured graph)."""
+        pen["w"].fill_(w)
+        pen["cot"].fill_(w / pen["V"])
+
+    def _pen_term(self, verts, loss, pen):
+        """-> (e (B, V) of `self_penetration(verts)`, differentiable; loss.detach() + w mean_V(e) on every column): three stock
+        launches (mean, product, sum) beside the term's own kernels."""
+        from .penetration import self_penetration
+        e = self_penetration(verts, self.pen_topo, self.pen_collide)
+        return e, loss.detach() + (pen["w"] * e.detach().mean(1))[:, None]
 
     def _initial(self, B, init, device, default):
         """`initial`: a (B, P) tensor as it is, anything else from default(); then the move to the device."""
@@ -648,21 +712,29 @@ class _Fitter:
         return dict(prior=prior.to(dev), prior_weights=check_prior_weights((1.0, 1.0, 1.0) if weights is None else weights).to(dev),
                     num_cam=self.num_cam)
 
-    def _losses(self, x, loss, silh_loss, silh_weight, prior, prior_weights):
+    def _losses(self, x, loss, silh_loss, silh_weight, prior, prior_weights, verts=None, pen_weight=None):
         """The tail of `losses`: per-term losses of x -> (B,) by the kernel of the loop, a call with a zero gradient on a
-        scratch state that records one row of history."""
+        scratch state that records one row of history.  A fitter with `penetration` passes its vertices: the term joins
+        `loss` as in `fit`, with pen_weight (None: 1)."""
+        if self.pen_topo is not None:
+            pen = self._pen_state(pen_weight, [None], int(x.shape[0]), x.device)
+            self._pen_set(pen, pen["stages"][0])
+            loss = self._pen_term(verts, loss, pen)[1].contiguous()
+        elif pen_weight is not None:
+            raise ValueError("pen_weight goes with a fitter built with penetration=...")
         hist = torch.empty((1, int(x.shape[0])), dtype=torch.float32, device=x.device)
         fit_step(FitState.new(x), torch.zeros_like(x), loss, silh_loss, silh_weight, None, hist,
                  **self._prior_kw(prior, prior_weights, x.device))
         return hist[0]
 
     def _fit(self, B, dev, start, data, *, steps, lr, mode, stages, patience, grad_scale, graph, check_every, history, beta1, beta2,
-             eps, graph_steps, prior, prior_weights, group_size, tie, smooth):
+             eps, graph_steps, prior, prior_weights, group_size, tie, smooth, pen_weight=None):
         """The rest of `fit` behind a fitter's own look at its inputs (`fit`'s arguments by name; B rows on device dev): the
         checks of groups, stages and prior weights, the start from start() (tied columns set to their group's mean), the
         state, the stages with their column scales and prior weights, graph capture and replay, the stop on `check_every`.
         data() -> make_one, called between the groups' checks and the stages': whatever the fitter checks of its data there;
-        make_one(cs, kw) -> one(state, hist): one iteration (forward, backward, `fit_step`) of its data term."""
+        make_one(cs, kw, pen) -> one(state, hist): one iteration (forward, backward, `fit_step`) of its data term; pen is
+        `_pen_state`'s dict (None without the term), its tensors rewritten here at each stage boundary."""
         P = self.P
         grp = check_group(B, group_size)
         grouped = grp != 1 or smooth is not None
@@ -671,6 +743,8 @@ class _Fitter:
         make_one = data()
         stage_list = check_stages(stages, P, steps)
         stage_w = _stage_prior_weights(prior, prior_weights, stage_list)
+        if self.pen_topo is None and pen_weight is not None:
+            raise ValueError("pen_weight goes with a fitter built with penetration=...")
         kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
                   mode=mode, patience=int(patience))
         total = sum(n for n, _ in stage_list)
@@ -692,7 +766,10 @@ class _Fitter:
             if prior is not None:
                 kw.update(self._prior_kw(prior, stage_w[0], dev))     # (the (3,) tensor is rewritten at each stage boundary)
                 stage_w = [w.to(dev) for w in stage_w]
-            one = make_one(cs, kw)
+            pen = self._pen_state(pen_weight, stage_list, B, dev)
+            if pen is not None:
+                self._pen_set(pen, pen["stages"][0])
+            one = make_one(cs, kw, pen)
             replay = None
             if graph and B > 0 and any(n >= G for n, _ in stage_list):
                 # warm-up on a side stream and on a scratch state, then G iterations of the real state in one graph
@@ -714,6 +791,8 @@ class _Fitter:
                 cs.copy_(sc)
                 if prior is not None:
                     kw["prior_weights"].copy_(stage_w[si])
+                if pen is not None:
+                    self._pen_set(pen, pen["stages"][si])
                 left = n
                 while left > 0 and not stopped:
                     if replay is not None and left >= G:
@@ -740,17 +819,22 @@ class ParamFitter(_Fitter):
     weights; `fit`'s are Keras' Adam (lr 1e-3, eps 1e-7)."""
 
     def __init__(self, smpl_path=None, img_wh=48, gamma=5.0, weight_classes=False, with_silhouette=False, silh_wh=None,
-                 silh_weight=1.0, vertex_sampling=None, deterministic=False):
+                 silh_weight=1.0, vertex_sampling=None, deterministic=False, penetration=None, collide=None):
         from .decoder import SMPLDecoder
         from .focal_loss import softmax_focal_loss
         self.img_wh = int(img_wh)
         self.with_silhouette = bool(with_silhouette)
         self.silh_weight = float(silh_weight)
+        with_pen = penetration is not None and penetration is not False
+        if with_pen and vertex_sampling not in (None, 1):
+            raise ValueError("penetration needs every vertex: vertex_sampling must be None or 1, got %r" % (vertex_sampling,))
         # (streams=1: one chain of launches, so a captured graph has no parallel branches)
         self.decoder = SMPLDecoder(smpl_path, img_wh=self.img_wh, vertex_sampling=vertex_sampling,
                                    with_silhouette=self.with_silhouette, silh_wh=silh_wh, streams=1,
-                                   deterministic=deterministic, outputs=(), loss=softmax_focal_loss(gamma, weight_classes),
+                                   deterministic=deterministic, outputs=("verts",) if with_pen else (),
+                                   loss=softmax_focal_loss(gamma, weight_classes),
                                    silh_loss=softmax_focal_loss(0.0, False) if self.with_silhouette else None)
+        self._pen_init(penetration, self.decoder._model, collide)
         self.num_cam = self.decoder.num_cam
         self.P = self.num_cam + 82
         self.silh_wh = self.decoder.silh_wh
@@ -779,10 +863,11 @@ class ParamFitter(_Fitter):
         return _lib.require_cuda(labels.to(torch.int32).reshape(B, W, W), name, torch.int32)
 
     # ---- one iteration ------------------------------------------------------------------------------------------------
-    def losses(self, x, labels, silh_labels=None, prior=None, prior_weights=None):
+    def losses(self, x, labels, silh_labels=None, prior=None, prior_weights=None, pen_weight=None):
         """Per-row loss (B,) fp32 of parameters x (B, P) against the labels: one gradient-free decoder forward reduced by
         the kernel of the loop (a call with a zero gradient on a scratch state), so the bits are those `fit` would record
-        for x in its history.  With a prior its weighted energy E is part of the loss, as in `fit`."""
+        for x in its history.  With a prior its weighted energy E is part of the loss, as in `fit`; so is the
+        self-penetration term of a fitter built with `penetration` (pen_weight None: 1)."""
         B = int(x.shape[0])
         labels = self._labels(labels, B, self.img_wh, "labels")
         if (silh_labels is not None) != self.with_silhouette:
@@ -793,25 +878,29 @@ class ParamFitter(_Fitter):
         with torch.no_grad(), torch.cuda.device(x.device):
             out = self.decoder(x, labels, silh_labels=silh_labels)
             return self._losses(x, out["seg_loss"], out["silh_loss"] if silh_labels is not None else None, self.silh_weight, prior,
-                                prior_weights)
+                                prior_weights, out.get("verts"), pen_weight)
 
-    def _iteration(self, state, labels, silh_labels, gout, sgout, cs, hist, kw):
+    def _iteration(self, state, labels, silh_labels, gout, sgout, cs, hist, kw, pen=None):
         x = state.x.detach().requires_grad_(True)                 # (shares x's memory: the kernel updates it in place)
         out = self.decoder(x, labels, silh_labels=silh_labels)
         seg_loss = out["seg_loss"]
-        if silh_labels is None:
-            (g,) = torch.autograd.grad([seg_loss], [x], grad_outputs=[gout])
-            sl = None
-        else:
+        terms, cots, sl = [seg_loss], [gout], None
+        if silh_labels is not None:
             sl = out["silh_loss"]
-            (g,) = torch.autograd.grad([seg_loss, sl], [x], grad_outputs=[gout, sgout])
+            terms, cots = terms + [sl], cots + [sgout]
             sl = sl.detach()
-        fit_step(state, g.contiguous(), seg_loss.detach(), sl, self.silh_weight, cs, hist, **kw)
+        loss = seg_loss.detach()
+        if pen is not None:
+            e, loss = self._pen_term(out["verts"], seg_loss, pen)
+            terms, cots = terms + [e], cots + [pen["cot"]]
+        (g,) = torch.autograd.grad(terms, [x], grad_outputs=cots)
+        fit_step(state, g.contiguous(), loss, sl, self.silh_weight, cs, hist, **kw)
 
     # ---- the loop -----------------------------------------------------------------------------------------------------
     def fit(self, labels, init=None, steps=1601, lr=1e-3, mode="keras", stages=None, silh_labels=None, patience=0,
             grad_scale=1.0, graph=False, check_every=0, history=False, beta1=0.9, beta2=0.999, eps=KERAS_EPS,
-            graph_steps=4, generator=None, prior=None, prior_weights=None, group_size=1, tie=("shape",), smooth=None):
+            graph_steps=4, generator=None, prior=None, prior_weights=None, group_size=1, tie=("shape",), smooth=None,
+            pen_weight=None):
         """labels (B, W, W) integer part maps on the HIP device -> FitResult.
 
         steps: iterations (decoder_loss_debugging.py:123 runs 1601), or stages = [(steps, column_scale), ...] run one after
@@ -829,7 +918,10 @@ class ParamFitter(_Fitter):
         they are equal within a group and stay bit-equal.  smooth: (P,) weights (`smooth_weights`) of a first-difference
         penalty between consecutive rows of a group, for clips.  Still one launch per iteration after the decoder's backward,
         and graph=True replays as before (tie and smooth are static device tensors).  loss, step and active of the result are
-        the group's, repeated per row.  With group_size = 1 and no smooth, tie has no effect."""
+        the group's, repeated per row.  With group_size = 1 and no smooth, tie has no effect.
+
+        pen_weight (a fitter built with `penetration` only; None: 1): the weight of the self-penetration term
+        pen_weight mean_V(e), one float or a list of one per stage."""
         if mode not in MODES:
             raise ValueError("mode %r is none of %s" % (mode, MODES))
         if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
@@ -842,16 +934,16 @@ class ParamFitter(_Fitter):
                 raise ValueError("silh_labels go with ParamFitter(with_silhouette=True), and only with it")
             slab = self._labels(silh_labels, B, self.silh_wh, "silh_labels") if silh_labels is not None else None
 
-            def make_one(cs, kw):
+            def make_one(cs, kw, pen):
                 N, Ns = W * W, self.silh_wh * self.silh_wh
                 gout = torch.full((B, N), 1.0 / N, dtype=torch.float32, device=dev)
                 sgout = torch.full((B, Ns), self.silh_weight / Ns, dtype=torch.float32, device=dev) if self.with_silhouette else None
-                return lambda st, h: self._iteration(st, lab, slab, gout, sgout, cs, h, kw)
+                return lambda st, h: self._iteration(st, lab, slab, gout, sgout, cs, h, kw, pen)
             return make_one
         return self._fit(B, dev, lambda: self.initial(B, init, generator, dev), data, steps=steps, lr=lr, mode=mode, stages=stages,
                          patience=patience, grad_scale=grad_scale, graph=graph, check_every=check_every, history=history,
                          beta1=beta1, beta2=beta2, eps=eps, graph_steps=graph_steps, prior=prior, prior_weights=prior_weights,
-                         group_size=group_size, tie=tie, smooth=smooth)
+                         group_size=group_size, tie=tie, smooth=smooth, pen_weight=pen_weight)
 
 
 def robust_rho(d2, sigma):
@@ -879,7 +971,8 @@ class ScanFitter(_Fitter):
         r = fitter.fit(points, counts, init=x0, steps=200, lr=0.02, mode="torch", prior=prior, prior_weights=(1, 1, 1))
     """
 
-    def __init__(self, smpl_path=None, topo=None, m2p_weight=1.0, sigma=None, directions=("p2m", "m2p")):
+    def __init__(self, smpl_path=None, topo=None, m2p_weight=1.0, sigma=None, directions=("p2m", "m2p"), penetration=None,
+                 collide=None):
         from .keras_smpl.batch_smpl import SMPLLayer
         from .render import MeshTopology
         self.layer = smpl_path if isinstance(smpl_path, SMPLLayer) else SMPLLayer(smpl_path)
@@ -902,6 +995,8 @@ class ScanFitter(_Fitter):
         if sigma is not None and not (math.isfinite(sigma) and sigma > 0):
             raise ValueError("sigma must be > 0 (or None: no robust function)")
         self.sigma = sigma
+        # (penetration=True: the fitter's own topology - the verts the term sees are the ones the scan distances see)
+        self._pen_init(self.topo if penetration is True else penetration, self.layer._model, collide)
 
     def initial(self, B, init=None, device=None):
         """(B, 86) float32 start: None = scale 1, no shift, the mean pose and shape; a (B, 86) tensor as it is."""
@@ -919,11 +1014,11 @@ class ScanFitter(_Fitter):
         """x (B, 86) -> the body in the scan's frame: x[:, 0] SMPLLayer(x) + x[:, 1:4]; differentiable."""
         return x[:, 0, None, None] * self.layer(x) + x[:, None, 1:4]
 
-    def terms(self, x, points, counts=None):
+    def terms(self, x, points, counts=None, verts=None):
         """-> (p2m terms (B, N) scaled by N / counts or None, m2p terms (B, V) or None, the op's dict): what `fit_step`
-        gets as `loss` and `silh_loss`; differentiable in x."""
+        gets as `loss` and `silh_loss`; differentiable in x.  verts: `place(x)` when the caller has it already."""
         from .scan import surface_distance
-        out = surface_distance(self.place(x), self.topo, points, counts, self.directions)
+        out = surface_distance(self.place(x) if verts is None else verts, self.topo, points, counts, self.directions)
         rho = (lambda d: d) if self.sigma is None else (lambda d: robust_rho(d, self.sigma))
         N = int(points.shape[1])
         p2m = m2p = None
@@ -943,16 +1038,20 @@ class ScanFitter(_Fitter):
             sgout = sgout * self.m2p_weight
         return gout, sgout
 
-    def _iteration(self, state, points, counts, gout, sgout, cs, hist, kw):
+    def _iteration(self, state, points, counts, gout, sgout, cs, hist, kw, pen=None):
         x = state.x.detach().requires_grad_(True)                 # (shares x's memory: the kernel updates it in place)
-        p2m, m2p, _ = self.terms(x, points, counts)
-        if p2m is not None and m2p is not None:
-            (g,) = torch.autograd.grad([p2m, m2p], [x], grad_outputs=[gout, sgout])
-            fit_step(state, g.contiguous(), p2m.detach().contiguous(), m2p.detach().contiguous(), self.m2p_weight, cs, hist, **kw)
-        else:
-            only, go = (p2m, gout) if p2m is not None else (m2p, sgout)
-            (g,) = torch.autograd.grad([only], [x], grad_outputs=[go])
-            fit_step(state, g.contiguous(), only.detach().contiguous(), None, 1.0, cs, hist, **kw)
+        verts = self.place(x)
+        p2m, m2p, _ = self.terms(x, points, counts, verts)
+        both = p2m is not None and m2p is not None
+        first, second = (p2m, m2p) if both else ((p2m, None) if p2m is not None else (m2p, None))
+        terms, cots = ([p2m, m2p], [gout, sgout]) if both else ([first], [gout if p2m is not None else sgout])
+        loss = first.detach()
+        if pen is not None:
+            e, loss = self._pen_term(verts, first, pen)
+            terms, cots = terms + [e], cots + [pen["cot"]]
+        (g,) = torch.autograd.grad(terms, [x], grad_outputs=cots)
+        fit_step(state, g.contiguous(), loss.contiguous(), second.detach().contiguous() if both else None,
+                 self.m2p_weight if both else 1.0, cs, hist, **kw)
 
     def _points(self, points, counts):
         if not isinstance(points, torch.Tensor) or points.dim() != 3 or points.shape[2] != 3 or points.shape[1] < 1:
@@ -968,34 +1067,37 @@ class ScanFitter(_Fitter):
             counts = c.to(device=points.device, dtype=torch.int32).contiguous()
         return points, counts
 
-    def losses(self, x, points, counts=None, prior=None, prior_weights=None):
+    def losses(self, x, points, counts=None, prior=None, prior_weights=None, pen_weight=None):
         """Per-row loss (B,) of parameters x against the scans, reduced by the kernel of the loop (a call with a zero
-        gradient on a scratch state): the bits `fit` would record for x in its history."""
+        gradient on a scratch state): the bits `fit` would record for x in its history (the self-penetration term of a
+        fitter built with `penetration` included, pen_weight None: 1)."""
         points, counts = self._points(points, counts)
         x = _lib.require_cuda(x.detach(), "x")
         with torch.no_grad(), torch.cuda.device(x.device):
-            p2m, m2p, _ = self.terms(x, points, counts)
+            verts = self.place(x)
+            p2m, m2p, _ = self.terms(x, points, counts, verts)
             first, second = (p2m, m2p) if p2m is not None else (m2p, None)
             return self._losses(x, first.contiguous(), None if second is None else second.contiguous(), self.m2p_weight, prior,
-                                prior_weights)
+                                prior_weights, verts, pen_weight)
 
     def fit(self, points, counts=None, init=None, steps=200, lr=1e-2, mode="torch", stages=None, patience=0, grad_scale=1.0,
             graph=False, check_every=0, history=False, beta1=0.9, beta2=0.999, eps=KERAS_EPS, graph_steps=4, prior=None,
-            prior_weights=None, group_size=1, tie=("shape",), smooth=None):
+            prior_weights=None, group_size=1, tie=("shape",), smooth=None, pen_weight=None):
         """points (B, N, 3) fp32 on the HIP device, counts (B,) or None -> FitResult.  Everything else as `ParamFitter.fit`:
         steps or stages = [(steps, column_scale), ...] (`column_scale(cam=...)` scales the (s, t) columns), patience,
         grad_scale, graph / graph_steps, check_every, history, prior and prior_weights (one triple or one per stage),
-        group_size / tie / smooth for several scans of one body (tie="cam" would tie the placement as well)."""
+        group_size / tie / smooth for several scans of one body (tie="cam" would tie the placement as well), pen_weight with
+        a fitter built with `penetration`."""
         if mode not in MODES:
             raise ValueError("mode %r is none of %s" % (mode, MODES))
         points, counts = self._points(points, counts)
         B, N = int(points.shape[0]), int(points.shape[1])
         dev = points.device
 
-        def make_one(cs, kw):
+        def make_one(cs, kw, pen):
             gout, sgout = self._cotangents(B, N, dev)
-            return lambda st, h: self._iteration(st, points, counts, gout, sgout, cs, h, kw)
+            return lambda st, h: self._iteration(st, points, counts, gout, sgout, cs, h, kw, pen)
         return self._fit(B, dev, lambda: self.initial(B, init, dev), lambda: make_one, steps=steps, lr=lr, mode=mode, stages=stages,
                          patience=patience, grad_scale=grad_scale, graph=graph, check_every=check_every, history=history,
                          beta1=beta1, beta2=beta2, eps=eps, graph_steps=graph_steps, prior=prior, prior_weights=prior_weights,
-                         group_size=group_size, tie=tie, smooth=smooth)
+                         group_size=group_size, tie=tie, smooth=smooth, pen_weight=pen_weight)
