@@ -18,6 +18,8 @@ Also: the sparse and the dense kernels give equal bits on the sparse weights, an
 import numpy as np
 import pytest
 
+from _smpl_bwd_oracle import oracle, top4_of          # (the float64 restatement: shared with the fused backward's tests)
+
 U = 2.0 ** -24
 B = 2
 XS = 6                                   # row stride of the camera rows (the kernels read columns 0..3)
@@ -26,14 +28,6 @@ GRADS = ["dverts", "dproj", "both"]
 
 
 # ------------------------------------------------------------------------------------------------ inputs and oracle
-def top4_of(w32):
-    """(V, 8) [w0..w3 | j0..j3] as ops.SMPLConstants.from_model lays it out: non-zero joints first, ascending."""
-    order = np.argsort(w32 == 0, axis=1, kind="stable")[:, :4]
-    wv = np.take_along_axis(w32, order, 1)
-    idx = np.where(wv != 0, order, 0)
-    return np.concatenate([wv, idx.astype(np.float32)], axis=1)
-
-
 def make_weights(V, nnz_max, exact, seed):
     """(V, 24) fp32 rows that sum to ~1 with `exact` ? exactly nnz_max : 1..nnz_max non-zeros at random joints."""
     rng = np.random.default_rng(seed)
@@ -52,35 +46,6 @@ def make_case(V, vs, seed=0):
     f = lambda *s: rng.normal(0, 1, s).astype(np.float32)
     return dict(V=V, vs=vs, VP=VP, vp=f(B, V, 3), A=f(B, 24, 12), x=f(B, XS), dverts=f(B, V, 3), dproj=f(B, VP, 3),
                 w_sparse=make_weights(V, 4, False, V), w_dense=make_weights(V, 7, True, V + 1))
-
-
-def oracle(c, w, dverts, dproj):
-    """float64 values and magnitudes (the same expressions on absolute values) of every output."""
-    V, vs = c["V"], c["vs"]
-    out = {}
-    for tag, ab in (("", lambda a: a), ("mag_", np.abs)):
-        w64, A, p = ab(w.astype(np.float64)), ab(c["A"].astype(np.float64)), ab(c["vp"].astype(np.float64))
-        cam = ab(c["x"][:, :4].astype(np.float64))
-        T = np.einsum("vj,bje->bve", w64, A).reshape(B, V, 3, 4)
-        ph = np.concatenate([p, np.ones((B, V, 1))], axis=2)
-        verts = np.einsum("bvrc,bvc->bvr", T, ph)
-        s = verts[:, ::vs]
-        proj = np.stack([cam[:, None, 2] + s[..., 0] * cam[:, None, 0], cam[:, None, 3] + s[..., 1] * cam[:, None, 1],
-                         s[..., 2]], axis=2)
-        g = np.zeros((B, V, 3)) if dverts is None else ab(dverts.astype(np.float64)).copy()
-        dcam = np.zeros((B, 4))
-        if dproj is not None:
-            d = ab(dproj.astype(np.float64))
-            g[:, ::vs, 0] += cam[:, None, 0] * d[..., 0]
-            g[:, ::vs, 1] += cam[:, None, 1] * d[..., 1]
-            g[:, ::vs, 2] += d[..., 2]
-            dcam = np.stack([(s[..., 0] * d[..., 0]).sum(1), (s[..., 1] * d[..., 1]).sum(1), d[..., 0].sum(1),
-                             d[..., 1].sum(1)], axis=1)
-        out[tag + "verts"], out[tag + "proj"] = verts, proj
-        out[tag + "dv_posed"] = np.einsum("bvrc,bvr->bvc", T[..., :3], g)
-        out[tag + "dA"] = np.einsum("vj,bvr,bvc->bjrc", w64, g, ph).reshape(B, 24, 12)
-        out[tag + "dcam"] = dcam
-    return out
 
 
 def terms(name, V):
