@@ -602,6 +602,38 @@ int smplr_pen_fwd(const float *verts, const int32_t *faces, const int32_t *vf_of
 int smplr_pen_bwd(const float *verts, const int32_t *near, const uint8_t *inside, const int32_t *status, const float *g, int B,
                   int V, float *dverts, void *stream);
 
+/* ---- 2D keypoint term: sparse joints, orthographic projection, robust energy, gradients (beyond the reference);
+ * INTEGRATION.md 4p ---------------------------------------------------------------------------------------------------------
+ * Sources of row b: i < V is verts[b, i] (verts (B, V, 3) fp32); with jtr (B, 24, 3) fp32 not NULL, V <= i < V + 24 is
+ * jtr[b, i - V]; S = V or V + 24.  The joints are a CSR over K rows: off (K + 1), idx (nnz) in [0, S) increasing within a row,
+ * w (nnz) fp32; its transpose is source-major: t_off (S + 1), t_joint (nnz) increasing within a source, t_w (nnz).  The
+ * kernels TRUST these arrays: keypoints.KeypointSpec builds them on the host and checks every offset, index and weight there
+ * once; what they still do is skip an offset range outside [0, nnz], a source outside [0, S) and a joint outside [0, K).
+ * cam (B, 4) = (k_u, k_v, u0, v0), the decoder's four columns; target (B, K, 2) in that camera's pixel frame; conf (B, K).
+ *   J[b, k] = sum over row k of w source[b, idx] (an empty row: 0); p = (u0 + k_u J_x, v0 + k_v J_y); r = p - target;
+ *   d2 = r_u^2 + r_v^2; joint k counts iff conf > 0 (a NaN does not): e = conf rho(d2), else e = 0 whatever target holds;
+ *   rho(s) = sigma^2 s / (sigma^2 + s), or s with sigma = 0.
+ * smplr_kp_fwd writes e, d2 (B, K), proj (B, K, 2), joints (B, K, 3), status (B) and ws (B, K, 4) fp64 = (J_x, J_y, r_u, r_v),
+ *   which smplr_kp_bwd reads.  One launch of B workgroups.
+ * smplr_kp_bwd, g (B, K) the cotangent of e: q = g conf rho'(d2) 2 r for a joint that counts (rho'(s) = sigma^4 / (sigma^2 + s)^2,
+ *   or 1), else 0; dJ = (q_u k_u, q_v k_v, 0); dverts[b, i] = sum_k w_ki dJ_k in increasing k, every row written (exact zeros
+ *   where no joint uses the vertex); djtr (B, 24, 3) or NULL likewise for the joint sources; dcam (B, 4) or NULL =
+ *   (sum q_u J_x, sum q_v J_y, sum q_u, sum q_v).  One launch of ceil(S / 256) x B workgroups.
+ * All products and sums are fp64 on the fp32 operands in an order the launch geometry fixes; each output is rounded to fp32
+ * once; no atomics: a row's results are the same bits on every launch and in any batch.
+ * status: SMPLR_KP_NONFINITE when a coordinate of a source that a counted joint uses, a cam column, or a counted joint's
+ *   target is NaN / Inf - the row's e, d2, proj, joints, dverts, djtr and dcam are NaN; other rows are not affected.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= V <= 2^24, 1 <= K <= 64, 0 <= nnz <= 2^24, sigma finite and >= 0,
+ * B >= 0 (B = 0 is a no-op; smplr_kp_bwd: B <= 65535); no null pointer except jtr, djtr, dcam (and idx, w, t_joint, t_w
+ * with nnz = 0).                                                                                                           */
+#define SMPLR_KP_NONFINITE 1
+int smplr_kp_fwd(const float *verts, const float *jtr, const float *cam, const int32_t *off, const int32_t *idx, const float *w,
+                 const float *target, const float *conf, int B, int V, int K, int nnz, float sigma, float *e, float *d2,
+                 float *proj, float *joints, int32_t *status, double *ws, void *stream);
+int smplr_kp_bwd(const float *cam, const int32_t *t_off, const int32_t *t_joint, const float *t_w, const float *conf,
+                 const int32_t *status, const double *ws, const float *g, int B, int V, int K, int nnz, float sigma,
+                 float *dverts, float *djtr, float *dcam, void *stream);
+
 /* ---- prediction figures: predict.py:28-77 (_seg.png, _projects.png, _verts_overlay.png), train.py:283-290,
  * train_stage2_silhouette.py:318-329, predict_realtime.py:75-96; INTEGRATION.md 4h -------------------------------------
  * One launch each on the caller's stream; no workspace, no allocation, no synchronisation, no global atomics.  Colours

@@ -93,6 +93,8 @@ SIGNATURES = {
     "smplr_scan_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P]),
     "smplr_pen_fwd": (c_int, [P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P, P, P]),
     "smplr_pen_bwd": (c_int, [P, P, P, P, P, I, I, P, P]),
+    "smplr_kp_fwd": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, c_float, P, P, P, P, P, P, P]),
+    "smplr_kp_bwd": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, c_float, P, P, P, P]),
     "smplr_seg_colour": (c_int, [P, P, I, I, I, I, P, I, I, P, I, I, I, P, P]),
     "smplr_scatter_points": (c_int, [P, P, P, I, P, I, I, I, I, c_float, I, I, I, I, P, P, P]),
     "smplr_fit_step": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, c_float, P, P, I, I, I, c_float, c_float, c_float,

@@ -228,3 +228,40 @@ def evaluate_penetration(verts, topo, collide=None):
                        (count > 0).sum().to(torch.float64), ok.sum().to(torch.float64)]).cpu()
     return {"inside": count, "max_depth": depth, "total_inside": int(tot[0]), "max_depth_overall": float(tot[1]),
             "meshes_with_penetration": int(tot[2]), "count": int(tot[3]), "nonfinite": int(verts.shape[0]) - int(tot[3])}
+
+
+@torch.no_grad()
+def evaluate_keypoints(proj_or_details, target, conf, thresholds=(0.05, 0.1, 0.2), scale=None):
+    """2D joint errors in pixels from `keypoints.keypoint_energy`'s details (its d2 and status; stock torch, CPU tensors
+    too) or from a plain proj (B, K, 2) tensor, against target (B, K, 2) and conf (B, K): a joint counts iff conf > 0 and
+    its row is finite.  A row is left out whole when its status is NONFINITE or a counted joint's d2 is NaN / Inf.
+    scale (B,) or None (ones): the per-row length that PCK's thresholds multiply (a torso or head size in pixels).
+    -> dict(mean_error = the mean of sqrt(d2) over counted joints (NaN without one), per_joint (K,) float64 = that mean per
+    joint (NaN where none counts), pck = {t: share of counted joints with sqrt(d2) <= t scale_b}, count = counted joints,
+    per_joint_count (K,) int64, rows = rows counted, nonfinite = rows left out)."""
+    if isinstance(proj_or_details, dict):
+        d2 = proj_or_details["d2"].to(torch.float64)
+        status = proj_or_details.get("status")
+    else:
+        r = proj_or_details.to(torch.float64) - target.to(torch.float64)
+        d2, status = (r * r).sum(-1), None
+    B, K = int(d2.shape[0]), int(d2.shape[1])
+    if tuple(conf.shape) != (B, K):
+        raise ValueError("conf must be (%d, %d), got %s" % (B, K, tuple(conf.shape)))
+    counted = conf > 0
+    bad = (counted & ~torch.isfinite(d2)).any(1)
+    if status is not None:
+        bad = bad | (status != 0)
+    counted = counted & ~bad[:, None]
+    zero = torch.zeros((), dtype=torch.float64, device=d2.device)
+    dist = torch.where(counted, d2, zero).sqrt()
+    s = torch.ones(B, dtype=torch.float64, device=d2.device) if scale is None else torch.as_tensor(scale).to(d2.device, torch.float64)
+    if tuple(s.shape) != (B,):
+        raise ValueError("scale must be (%d,), got %s" % (B, tuple(s.shape)))
+    n_k = counted.sum(0)
+    n = int(n_k.sum())
+    nan = float("nan")
+    pck = {float(t): (float((counted & (dist <= float(t) * s[:, None])).sum()) / n if n else nan) for t in thresholds}
+    return {"mean_error": float(dist.sum()) / n if n else nan,
+            "per_joint": torch.where(n_k > 0, dist.sum(0) / n_k.clamp(min=1), torch.full_like(zero, nan)),
+            "pck": pck, "count": n, "per_joint_count": n_k, "rows": B - int(bad.sum()), "nonfinite": int(bad.sum())}

@@ -85,6 +85,16 @@ the detached loss handed to `fit_step` (so the recorded loss, the best iterate a
 enters `torch.autograd.grad` through a preallocated cotangent pen_weight / V on e.  The weight lives in a device scalar and the
 cotangent in a device tensor, both rewritten at stage boundaries, so a captured graph follows them.  `fit_step` and
 csrc/fit.hip are untouched; without `penetration` a fitter runs exactly the launches it ran before.
+
+2D keypoints (keypoints.py, csrc/keypoints.hip; detected image joints, SMPLify's data term):
+
+    fitter = ParamFitter(smpl_path, keypoints=KeypointSpec.from_model(model), kp_sigma=3.0)
+    r = fitter.fit(labels, keypoints=(target, conf), stages=[(100, cs), (100, cs)], kp_weight=[1.0, 0.1])
+    r = KeypointFitter(smpl_path, sigma=3.0).fit(target, conf, steps=200)      # the keypoint term as the only data term
+
+kp_weight mean_K(e[b, :]), e = `keypoint_energy` of the iteration's vertices (and posed joints) under cam = x[:, :4], joins the
+loss and the one `torch.autograd.grad` call exactly as the self-penetration term does, through a cotangent kp_weight / K;
+targets are in the decoder's pixel frame.  Without `keypoints` a fitter runs exactly the launches it ran before.
 """
 from __future__ import annotations
 
@@ -635,20 +645,20 @@ def _stage_prior_weights(prior, prior_weights, stage_list):
     return [check_prior_weights(w) for w in (pw if per_stage else [pw] * len(stage_list))]
 
 
-def _stage_pen_weights(pen_weight, stage_list):
-    """`fit`'s pen_weight (None: 1, one float, or a list of one float per stage) -> one float per stage."""
+def _stage_pen_weights(pen_weight, stage_list, name="pen_weight"):
+    """`fit`'s pen_weight or kp_weight (None: 1, one float, or a list of one float per stage) -> one float per stage."""
     pw = 1.0 if pen_weight is None else pen_weight
     per_stage = isinstance(pw, (list, tuple))
     if per_stage and len(pw) != len(stage_list):
-        raise ValueError("pen_weight lists %d weights for %d stages" % (len(pw), len(stage_list)))
+        raise ValueError("%s lists %d weights for %d stages" % (name, len(pw), len(stage_list)))
     out = [float(w) for w in (pw if per_stage else [pw] * len(stage_list))]
     if any(not math.isfinite(w) or w < 0 or w > float(np.finfo(np.float32).max) for w in out):
-        raise ValueError("pen_weight must be finite and >= 0, got %r" % (pen_weight,))
+        raise ValueError("%s must be finite and >= 0, got %r" % (name, pen_weight))
     return out
 
 
 class _Fitter:
-    """What `ParamFitter` and `ScanFitter` share; a fitter adds its data term (`_iteration`) and sets num_cam and P."""
+    """What `ParamFitter`, `ScanFitter` and `KeypointFitter` share; a fitter adds its data term (`_iteration`) and sets num_cam and P."""
     pen_topo = None            # a render.MeshTopology when the fitter was built with `penetration`
     pen_collide = None         # its part-pair table (None: `penetration.part_collision_table(topo, 1)`)
 
@@ -691,6 +701,73 @@ class _Fitter:
         e = self_penetration(verts, self.pen_topo, self.pen_collide)
         return e, loss.detach() + (pen["w"] * e.detach().mean(1))[:, None]
 
+    # ---- the 2D keypoint term (keypoints.py), beside the self-penetration helpers and in their mould ----------------------
+    kp_spec = None             # a keypoints.KeypointSpec when the fitter was built with `keypoints`
+    kp_sigma = None            # the robust function's sigma in pixels (None: rho(s) = s)
+
+    def _kp_init(self, keypoints, model, sigma=None):
+        """`keypoints` of a fitter's constructor: None (no term) or a KeypointSpec over the model's vertices."""
+        from .keypoints import KeypointSpec, check_sigma
+        check_sigma(sigma)
+        if keypoints is None:
+            if sigma is not None:
+                raise ValueError("kp_sigma goes with a fitter built with keypoints=...")
+            return
+        if not isinstance(keypoints, KeypointSpec):
+            raise TypeError("keypoints must be a keypoints.KeypointSpec")
+        if keypoints.num_verts != model.num_verts:
+            raise ValueError("the keypoint spec has %d vertices, the model %d" % (keypoints.num_verts, model.num_verts))
+        if self.num_cam != 4:
+            raise ValueError("the keypoint term projects with four camera columns")
+        self.kp_spec, self.kp_sigma = keypoints, sigma
+
+    def _kp_data(self, keypoints, B, dev):
+        """`fit`'s / `losses`' keypoints=(target (B, K, 2), conf (B, K)) -> both as fp32 device tensors; None without."""
+        if keypoints is None:
+            return None
+        if not isinstance(keypoints, (tuple, list)) or len(keypoints) != 2:
+            raise ValueError("keypoints must be (target (B, K, 2), conf (B, K))")
+        K = self.kp_spec.K
+        target, conf = (torch.as_tensor(a) for a in keypoints)
+        if tuple(target.shape) != (B, K, 2) or tuple(conf.shape) != (B, K):
+            raise ValueError("keypoints must be (target (%d, %d, 2), conf (%d, %d)), got %s and %s"
+                             % (B, K, B, K, tuple(target.shape), tuple(conf.shape)))
+        return (target.detach().to(device=dev, dtype=torch.float32).contiguous(),
+                conf.detach().to(device=dev, dtype=torch.float32).contiguous())
+
+    def _kp_check(self, keypoints, kp_weight):
+        """The pairing rules, before anything touches a device: data and weight only with a spec, a spec only with data."""
+        if self.kp_spec is None:
+            if keypoints is not None or kp_weight is not None:
+                raise ValueError("keypoints and kp_weight go with a fitter built with keypoints=...")
+        elif keypoints is None:
+            raise ValueError("this fitter was built with keypoints=...: pass keypoints=(target, conf)")
+
+    def _kp_state(self, kp_weight, stage_list, B, dev, keypoints=None):
+        """None without the term; else dict(w (1,) and cot (B, K) device tensors, stages = one weight per stage, K, target,
+        conf)."""
+        self._kp_check(keypoints, kp_weight)
+        if self.kp_spec is None:
+            return None
+        K = self.kp_spec.K
+        target, conf = self._kp_data(keypoints, B, dev)
+        return dict(w=torch.zeros(1, dtype=torch.float32, device=dev), cot=torch.zeros((B, K), dtype=torch.float32, device=dev),
+                    stages=_stage_pen_weights(kp_weight, stage_list, "kp_weight"), K=K, target=target, conf=conf)
+
+    @staticmethod
+    def _kp_set(kp, w):
+        """The weight of a stage into the device scalar and the cotangent (outside any captured graph)."""
+        kp["w"].fill_(w)
+        kp["cot"].fill_(w / kp["K"])
+
+    def _kp_term(self, verts, cam, jtr, loss, kp):
+        """-> (e (B, K) of `keypoint_energy`, differentiable in verts, cam and jtr; loss.detach() + w mean_K(e) on every
+        column): three stock launches (mean, product, sum) beside the term's own kernels."""
+        from .keypoints import keypoint_energy
+        e = keypoint_energy(verts, cam, self.kp_spec, kp["target"], kp["conf"], self.kp_sigma,
+                            jtr if self.kp_spec.with_joints else None)
+        return e, loss.detach() + (kp["w"] * e.detach().mean(1))[:, None]
+
     def _initial(self, B, init, device, default):
         """`initial`: a (B, P) tensor as it is, anything else from default(); then the move to the device."""
         if isinstance(init, torch.Tensor):
@@ -712,29 +789,35 @@ class _Fitter:
         return dict(prior=prior.to(dev), prior_weights=check_prior_weights((1.0, 1.0, 1.0) if weights is None else weights).to(dev),
                     num_cam=self.num_cam)
 
-    def _losses(self, x, loss, silh_loss, silh_weight, prior, prior_weights, verts=None, pen_weight=None):
+    def _losses(self, x, loss, silh_loss, silh_weight, prior, prior_weights, verts=None, pen_weight=None, kp=None):
         """The tail of `losses`: per-term losses of x -> (B,) by the kernel of the loop, a call with a zero gradient on a
         scratch state that records one row of history.  A fitter with `penetration` passes its vertices: the term joins
-        `loss` as in `fit`, with pen_weight (None: 1)."""
+        `loss` as in `fit`, with pen_weight (None: 1).  kp = (cam, J_transformed, keypoints, kp_weight) of a fitter built
+        with `keypoints`: that term joins likewise."""
         if self.pen_topo is not None:
             pen = self._pen_state(pen_weight, [None], int(x.shape[0]), x.device)
             self._pen_set(pen, pen["stages"][0])
             loss = self._pen_term(verts, loss, pen)[1].contiguous()
         elif pen_weight is not None:
             raise ValueError("pen_weight goes with a fitter built with penetration=...")
+        if kp is not None:
+            st = self._kp_state(kp[3], [None], int(x.shape[0]), x.device, kp[2])
+            self._kp_set(st, st["stages"][0])
+            loss = self._kp_term(verts, kp[0], kp[1], loss, st)[1].contiguous()
         hist = torch.empty((1, int(x.shape[0])), dtype=torch.float32, device=x.device)
         fit_step(FitState.new(x), torch.zeros_like(x), loss, silh_loss, silh_weight, None, hist,
                  **self._prior_kw(prior, prior_weights, x.device))
         return hist[0]
 
     def _fit(self, B, dev, start, data, *, steps, lr, mode, stages, patience, grad_scale, graph, check_every, history, beta1, beta2,
-             eps, graph_steps, prior, prior_weights, group_size, tie, smooth, pen_weight=None):
+             eps, graph_steps, prior, prior_weights, group_size, tie, smooth, pen_weight=None, kp_weight=None, keypoints=None):
         """The rest of `fit` behind a fitter's own look at its inputs (`fit`'s arguments by name; B rows on device dev): the
         checks of groups, stages and prior weights, the start from start() (tied columns set to their group's mean), the
         state, the stages with their column scales and prior weights, graph capture and replay, the stop on `check_every`.
         data() -> make_one, called between the groups' checks and the stages': whatever the fitter checks of its data there;
         make_one(cs, kw, pen) -> one(state, hist): one iteration (forward, backward, `fit_step`) of its data term; pen is
-        `_pen_state`'s dict (None without the term), its tensors rewritten here at each stage boundary."""
+        `_pen_state`'s dict (None without the term), its tensors rewritten here at each stage boundary.  A fitter built with
+        `keypoints` gets make_one(cs, kw, pen, kp) with `_kp_state`'s dict, kept the same way."""
         P = self.P
         grp = check_group(B, group_size)
         grouped = grp != 1 or smooth is not None
@@ -745,6 +828,9 @@ class _Fitter:
         stage_w = _stage_prior_weights(prior, prior_weights, stage_list)
         if self.pen_topo is None and pen_weight is not None:
             raise ValueError("pen_weight goes with a fitter built with penetration=...")
+        self._kp_check(keypoints, kp_weight)
+        if self.kp_spec is not None:
+            _stage_pen_weights(kp_weight, stage_list, "kp_weight")
         kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
                   mode=mode, patience=int(patience))
         total = sum(n for n, _ in stage_list)
@@ -769,7 +855,10 @@ class _Fitter:
             pen = self._pen_state(pen_weight, stage_list, B, dev)
             if pen is not None:
                 self._pen_set(pen, pen["stages"][0])
-            one = make_one(cs, kw, pen)
+            kp = self._kp_state(kp_weight, stage_list, B, dev, keypoints)
+            if kp is not None:
+                self._kp_set(kp, kp["stages"][0])
+            one = make_one(cs, kw, pen) if kp is None else make_one(cs, kw, pen, kp)
             replay = None
             if graph and B > 0 and any(n >= G for n, _ in stage_list):
                 # warm-up on a side stream and on a scratch state, then G iterations of the real state in one graph
@@ -793,6 +882,8 @@ class _Fitter:
                     kw["prior_weights"].copy_(stage_w[si])
                 if pen is not None:
                     self._pen_set(pen, pen["stages"][si])
+                if kp is not None:
+                    self._kp_set(kp, kp["stages"][si])
                 left = n
                 while left > 0 and not stopped:
                     if replay is not None and left >= G:
@@ -819,7 +910,8 @@ class ParamFitter(_Fitter):
     weights; `fit`'s are Keras' Adam (lr 1e-3, eps 1e-7)."""
 
     def __init__(self, smpl_path=None, img_wh=48, gamma=5.0, weight_classes=False, with_silhouette=False, silh_wh=None,
-                 silh_weight=1.0, vertex_sampling=None, deterministic=False, penetration=None, collide=None):
+                 silh_weight=1.0, vertex_sampling=None, deterministic=False, penetration=None, collide=None, keypoints=None,
+                 kp_sigma=None):
         from .decoder import SMPLDecoder
         from .focal_loss import softmax_focal_loss
         self.img_wh = int(img_wh)
@@ -828,16 +920,19 @@ class ParamFitter(_Fitter):
         with_pen = penetration is not None and penetration is not False
         if with_pen and vertex_sampling not in (None, 1):
             raise ValueError("penetration needs every vertex: vertex_sampling must be None or 1, got %r" % (vertex_sampling,))
+        if keypoints is not None and vertex_sampling not in (None, 1):
+            raise ValueError("keypoints need every vertex: vertex_sampling must be None or 1, got %r" % (vertex_sampling,))
         # (streams=1: one chain of launches, so a captured graph has no parallel branches)
         self.decoder = SMPLDecoder(smpl_path, img_wh=self.img_wh, vertex_sampling=vertex_sampling,
                                    with_silhouette=self.with_silhouette, silh_wh=silh_wh, streams=1,
-                                   deterministic=deterministic, outputs=("verts",) if with_pen else (),
+                                   deterministic=deterministic, outputs=("verts",) if with_pen or keypoints is not None else (),
                                    loss=softmax_focal_loss(gamma, weight_classes),
                                    silh_loss=softmax_focal_loss(0.0, False) if self.with_silhouette else None)
         self._pen_init(penetration, self.decoder._model, collide)
         self.num_cam = self.decoder.num_cam
         self.P = self.num_cam + 82
         self.silh_wh = self.decoder.silh_wh
+        self._kp_init(keypoints, self.decoder._model, kp_sigma)
 
     # ---- inputs -------------------------------------------------------------------------------------------------------
     def initial(self, B, init=None, generator=None, device=None):
@@ -863,12 +958,15 @@ class ParamFitter(_Fitter):
         return _lib.require_cuda(labels.to(torch.int32).reshape(B, W, W), name, torch.int32)
 
     # ---- one iteration ------------------------------------------------------------------------------------------------
-    def losses(self, x, labels, silh_labels=None, prior=None, prior_weights=None, pen_weight=None):
+    def losses(self, x, labels, silh_labels=None, prior=None, prior_weights=None, pen_weight=None, keypoints=None,
+               kp_weight=None):
         """Per-row loss (B,) fp32 of parameters x (B, P) against the labels: one gradient-free decoder forward reduced by
         the kernel of the loop (a call with a zero gradient on a scratch state), so the bits are those `fit` would record
         for x in its history.  With a prior its weighted energy E is part of the loss, as in `fit`; so is the
-        self-penetration term of a fitter built with `penetration` (pen_weight None: 1)."""
+        self-penetration term of a fitter built with `penetration` (pen_weight None: 1) and the keypoint term of one built
+        with `keypoints` (keypoints = (target, conf), kp_weight None: 1)."""
         B = int(x.shape[0])
+        self._kp_check(keypoints, kp_weight)
         labels = self._labels(labels, B, self.img_wh, "labels")
         if (silh_labels is not None) != self.with_silhouette:
             raise ValueError("silh_labels go with ParamFitter(with_silhouette=True), and only with it")
@@ -877,10 +975,11 @@ class ParamFitter(_Fitter):
         x = _lib.require_cuda(x.detach(), "x")
         with torch.no_grad(), torch.cuda.device(x.device):
             out = self.decoder(x, labels, silh_labels=silh_labels)
+            kp = None if self.kp_spec is None else (x[:, :4], out["J_transformed"], keypoints, kp_weight)
             return self._losses(x, out["seg_loss"], out["silh_loss"] if silh_labels is not None else None, self.silh_weight, prior,
-                                prior_weights, out.get("verts"), pen_weight)
+                                prior_weights, out.get("verts"), pen_weight, kp)
 
-    def _iteration(self, state, labels, silh_labels, gout, sgout, cs, hist, kw, pen=None):
+    def _iteration(self, state, labels, silh_labels, gout, sgout, cs, hist, kw, pen=None, kp=None):
         x = state.x.detach().requires_grad_(True)                 # (shares x's memory: the kernel updates it in place)
         out = self.decoder(x, labels, silh_labels=silh_labels)
         seg_loss = out["seg_loss"]
@@ -893,6 +992,9 @@ class ParamFitter(_Fitter):
         if pen is not None:
             e, loss = self._pen_term(out["verts"], seg_loss, pen)
             terms, cots = terms + [e], cots + [pen["cot"]]
+        if kp is not None:
+            ek, loss = self._kp_term(out["verts"], x[:, :4], out["J_transformed"], loss, kp)
+            terms, cots = terms + [ek], cots + [kp["cot"]]
         (g,) = torch.autograd.grad(terms, [x], grad_outputs=cots)
         fit_step(state, g.contiguous(), loss, sl, self.silh_weight, cs, hist, **kw)
 
@@ -900,7 +1002,7 @@ class ParamFitter(_Fitter):
     def fit(self, labels, init=None, steps=1601, lr=1e-3, mode="keras", stages=None, silh_labels=None, patience=0,
             grad_scale=1.0, graph=False, check_every=0, history=False, beta1=0.9, beta2=0.999, eps=KERAS_EPS,
             graph_steps=4, generator=None, prior=None, prior_weights=None, group_size=1, tie=("shape",), smooth=None,
-            pen_weight=None):
+            pen_weight=None, keypoints=None, kp_weight=None):
         """labels (B, W, W) integer part maps on the HIP device -> FitResult.
 
         steps: iterations (decoder_loss_debugging.py:123 runs 1601), or stages = [(steps, column_scale), ...] run one after
@@ -921,9 +1023,14 @@ class ParamFitter(_Fitter):
         the group's, repeated per row.  With group_size = 1 and no smooth, tie has no effect.
 
         pen_weight (a fitter built with `penetration` only; None: 1): the weight of the self-penetration term
-        pen_weight mean_V(e), one float or a list of one per stage."""
+        pen_weight mean_V(e), one float or a list of one per stage.
+
+        keypoints = (target (B, K, 2), conf (B, K)) and kp_weight (a fitter built with `keypoints` only; kp_weight None: 1):
+        detected 2D joints in the decoder's pixel frame; the term kp_weight mean_K(e), e = `keypoints.keypoint_energy`, joins
+        every column of the loss and the one `torch.autograd.grad` call, as the self-penetration term does."""
         if mode not in MODES:
             raise ValueError("mode %r is none of %s" % (mode, MODES))
+        self._kp_check(keypoints, kp_weight)
         if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
             raise ValueError("labels must be a (B, W, W) integer tensor")
         B, W, dev = int(labels.shape[0]), self.img_wh, labels.device
@@ -934,16 +1041,17 @@ class ParamFitter(_Fitter):
                 raise ValueError("silh_labels go with ParamFitter(with_silhouette=True), and only with it")
             slab = self._labels(silh_labels, B, self.silh_wh, "silh_labels") if silh_labels is not None else None
 
-            def make_one(cs, kw, pen):
+            def make_one(cs, kw, pen, kp=None):
                 N, Ns = W * W, self.silh_wh * self.silh_wh
                 gout = torch.full((B, N), 1.0 / N, dtype=torch.float32, device=dev)
                 sgout = torch.full((B, Ns), self.silh_weight / Ns, dtype=torch.float32, device=dev) if self.with_silhouette else None
-                return lambda st, h: self._iteration(st, lab, slab, gout, sgout, cs, h, kw, pen)
+                return lambda st, h: self._iteration(st, lab, slab, gout, sgout, cs, h, kw, pen, kp)
             return make_one
         return self._fit(B, dev, lambda: self.initial(B, init, generator, dev), data, steps=steps, lr=lr, mode=mode, stages=stages,
                          patience=patience, grad_scale=grad_scale, graph=graph, check_every=check_every, history=history,
                          beta1=beta1, beta2=beta2, eps=eps, graph_steps=graph_steps, prior=prior, prior_weights=prior_weights,
-                         group_size=group_size, tie=tie, smooth=smooth, pen_weight=pen_weight)
+                         group_size=group_size, tie=tie, smooth=smooth, pen_weight=pen_weight, kp_weight=kp_weight,
+                         keypoints=keypoints)
 
 
 def robust_rho(d2, sigma):
@@ -1097,6 +1205,108 @@ class ScanFitter(_Fitter):
         def make_one(cs, kw, pen):
             gout, sgout = self._cotangents(B, N, dev)
             return lambda st, h: self._iteration(st, points, counts, gout, sgout, cs, h, kw, pen)
+        return self._fit(B, dev, lambda: self.initial(B, init, dev), lambda: make_one, steps=steps, lr=lr, mode=mode, stages=stages,
+                         patience=patience, grad_scale=grad_scale, graph=graph, check_every=check_every, history=history,
+                         beta1=beta1, beta2=beta2, eps=eps, graph_steps=graph_steps, prior=prior, prior_weights=prior_weights,
+                         group_size=group_size, tie=tie, smooth=smooth, pen_weight=pen_weight)
+
+
+class KeypointFitter(_Fitter):
+    """`ScanFitter`'s shape with detected 2D joints as the only data term: `SMPLLayer -> keypoints.keypoint_energy` with
+    cam = x[:, :4], the decoder's camera columns, so targets are in the pixel frame of a decoder at `img_wh`.  Row b's data
+    term is mean_K(e[b, :]), e = conf rho(d2) per joint (rho = `robust_rho` with `sigma` in pixels, the identity when sigma is
+    None), handed to `fit_step` as per-term losses with the constant cotangent 1 / K.  A row whose status is NONFINITE has a
+    NaN loss and gradient and counts as a bad call (nothing changes).  Every launch of an iteration reproduces its bits, so
+    two fits from the same start agree bit for bit.
+
+        fitter = KeypointFitter(smpl_path, sigma=3.0)               # spec: the model's cocoplus joints
+        r = fitter.fit(target, conf, steps=200, lr=0.02, prior=prior, prior_weights=(1, 1, 1))
+    """
+
+    def __init__(self, smpl_path=None, spec=None, sigma=None, img_wh=48, penetration=None, collide=None):
+        from .keras_smpl.batch_smpl import SMPLLayer
+        from .keypoints import KeypointSpec, check_sigma
+        self.layer = smpl_path if isinstance(smpl_path, SMPLLayer) else SMPLLayer(smpl_path)
+        self.num_cam = self.layer.num_cam
+        if self.num_cam != 4:
+            raise ValueError("KeypointFitter projects with four camera columns")
+        self.P = self.num_cam + 82
+        self.img_wh = int(img_wh)
+        if spec is None:
+            spec = KeypointSpec.from_model(self.layer)
+        if not isinstance(spec, KeypointSpec):
+            raise TypeError("spec must be a keypoints.KeypointSpec")
+        if spec.num_verts != self.layer._model.num_verts:
+            raise ValueError("the keypoint spec has %d vertices, the model %d" % (spec.num_verts, self.layer._model.num_verts))
+        check_sigma(sigma)
+        self.spec, self.sigma = spec, sigma
+        self._pen_init(penetration, self.layer._model, collide)
+
+    def initial(self, B, init=None, device=None):
+        """(B, 86) float32 start: None = `smpl_model.mean86(img_wh)` per row; a (B, 86) tensor as it is."""
+        from .smpl_model import mean86
+
+        def default():
+            if init is not None:
+                raise ValueError("init must be None or a (B, %d) tensor, got %r" % (self.P, init))
+            return torch.as_tensor(mean86(self.img_wh), dtype=torch.float32).repeat(B, 1)
+        return self._initial(B, init, device, default)
+
+    def terms(self, x, target, conf):
+        """-> (e (B, K) differentiable in x, the op's details, verts): what `fit_step` gets as `loss`."""
+        from .keypoints import keypoint_energy
+        verts = self.layer(x)
+        jtr = self.layer.J_transformed if self.spec.with_joints else None
+        e, det = keypoint_energy(verts, x[:, :4], self.spec, target, conf, self.sigma, jtr, return_details=True)
+        return e, det, verts
+
+    def _data(self, target, conf):
+        K = self.spec.K
+        if not isinstance(target, torch.Tensor) or target.dim() != 3 or tuple(target.shape[1:]) != (K, 2):
+            raise ValueError("target must be a (B, %d, 2) tensor" % K)
+        B = int(target.shape[0])
+        if not isinstance(conf, torch.Tensor) or tuple(conf.shape) != (B, K):
+            raise ValueError("conf must be a (%d, %d) tensor" % (B, K))
+        target = _lib.require_cuda(target.detach().to(torch.float32), "target")
+        conf = _lib.require_cuda(conf.detach().to(torch.float32), "conf")
+        if conf.device != target.device:
+            raise RuntimeError("conf lives on %s, target on %s" % (conf.device, target.device))
+        return target, conf
+
+    def _iteration(self, state, target, conf, gout, cs, hist, kw, pen=None):
+        x = state.x.detach().requires_grad_(True)                 # (shares x's memory: the kernel updates it in place)
+        e, _, verts = self.terms(x, target, conf)
+        terms, cots, loss = [e], [gout], e.detach()
+        if pen is not None:
+            ep, loss = self._pen_term(verts, e, pen)
+            terms, cots = terms + [ep], cots + [pen["cot"]]
+        (g,) = torch.autograd.grad(terms, [x], grad_outputs=cots)
+        fit_step(state, g.contiguous(), loss.contiguous(), None, 1.0, cs, hist, **kw)
+
+    def losses(self, x, target, conf, prior=None, prior_weights=None, pen_weight=None):
+        """Per-row loss (B,) of parameters x against the detections, reduced by the kernel of the loop (a call with a zero
+        gradient on a scratch state): the bits `fit` would record for x in its history."""
+        target, conf = self._data(target, conf)
+        x = _lib.require_cuda(x.detach(), "x")
+        with torch.no_grad(), torch.cuda.device(x.device):
+            e, _, verts = self.terms(x, target, conf)
+            return self._losses(x, e.contiguous(), None, 1.0, prior, prior_weights, verts, pen_weight)
+
+    def fit(self, target, conf, init=None, steps=200, lr=1e-2, mode="torch", stages=None, patience=0, grad_scale=1.0,
+            graph=False, check_every=0, history=False, beta1=0.9, beta2=0.999, eps=KERAS_EPS, graph_steps=4, prior=None,
+            prior_weights=None, group_size=1, tie=("shape",), smooth=None, pen_weight=None):
+        """target (B, K, 2) and conf (B, K) fp32 on the HIP device -> FitResult.  Everything else as `ParamFitter.fit`: steps or
+        stages = [(steps, column_scale), ...], patience, grad_scale, graph / graph_steps, check_every, history, prior and
+        prior_weights (one triple or one per stage), group_size / tie / smooth for several views or frames of one body,
+        pen_weight with a fitter built with `penetration`."""
+        if mode not in MODES:
+            raise ValueError("mode %r is none of %s" % (mode, MODES))
+        target, conf = self._data(target, conf)
+        B, K, dev = int(target.shape[0]), self.spec.K, target.device
+
+        def make_one(cs, kw, pen):
+            gout = torch.full((B, K), 1.0 / K, dtype=torch.float32, device=dev)
+            return lambda st, h: self._iteration(st, target, conf, gout, cs, h, kw, pen)
         return self._fit(B, dev, lambda: self.initial(B, init, dev), lambda: make_one, steps=steps, lr=lr, mode=mode, stages=stages,
                          patience=patience, grad_scale=grad_scale, graph=graph, check_every=check_every, history=history,
                          beta1=beta1, beta2=beta2, eps=eps, graph_steps=graph_steps, prior=prior, prior_weights=prior_weights,
