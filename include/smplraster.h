@@ -634,6 +634,42 @@ int smplr_kp_bwd(const float *cam, const int32_t *t_off, const int32_t *t_joint,
                  const int32_t *status, const double *ws, const float *g, int B, int V, int K, int nnz, float sigma,
                  float *dverts, float *djtr, float *dcam, void *stream);
 
+/* ---- mesh regularisers of SMPL+D registration: Laplacian and relative edge length, with gradients (beyond the reference);
+ * INTEGRATION.md 4q ---------------------------------------------------------------------------------------------------------
+ * verts (B, V, 3) fp32.  The one-ring of the topology is a CSR: nb_off (V + 1), nb_idx (nnz) and nb_w (nnz, 3) fp32 =
+ * [w_ik, w_ki, 1 / l_ik^2] per entry (i, k): the weight of k in row i, the weight of i in row k, and the inverse squared
+ * length of the edge in the reference mesh (0: the edge is left out of E_edge).  The adjacency is symmetric and holds no
+ * (i, i); meshreg.MeshRegSpec builds and checks it on the host.  lap_ref (V, 3) or NULL (zeros), vweight (V) or NULL (ones).
+ *   L(v)_i = v_i - sum_k w_ik v_k, and 0 for a vertex whose row is empty;
+ *   terms[b, 0] = E_lap  = 1/V sum_i vweight_i |L(v)_i - lap_ref_i|^2
+ *   terms[b, 1] = E_edge = 1/E sum over the entries with i < k and 1 / l^2 != 0 of (|v_i - v_k|^2 / l_ik^2 - 1)^2; 0 with E = 0.
+ * E is the number of such entries, counted by the caller.
+ * smplr_mesh_reg_fwd: ceil(V / 256) x B workgroups write one fp64 partial pair each into the workspace
+ *   (smplr_mesh_reg_workspace(B, V) bytes, 8-byte aligned), then one wave per mesh adds them in a fixed order.
+ * smplr_mesh_reg_bwd, g (B, 2) the cotangent of terms: dverts[b, i] = g_0 2 (r_i - sum_k w_ki r_k) / V
+ *   + g_1 4 / E sum_k (|v_i - v_k|^2 / l_ik^2 - 1) / l_ik^2 (v_i - v_k), r = vweight (L(v) - lap_ref), the r_k recomputed from
+ *   verts; r_i leaves the first bracket for a vertex whose row is empty.  Every row of dverts is stored.
+ * All products and sums are fp64 on the fp32 operands in an order the launch geometry fixes; each output is rounded to fp32
+ * once; no atomics: a mesh's results are the same bits on every launch and in any batch.  A mesh with a coordinate that is
+ * not finite has NaN terms; the other meshes are not affected.  An entry naming a vertex outside [0, V) is skipped.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= V <= 2^24, 0 <= nnz <= 2^28, 0 <= 2 E <= nnz, B >= 0 (B = 0 is a
+ * no-op); no null pointer except lap_ref, vweight (and nb_idx, nb_w with nnz = 0).                                         */
+size_t smplr_mesh_reg_workspace(int B, int V);
+int smplr_mesh_reg_fwd(const float *verts, const int32_t *nb_off, const int32_t *nb_idx, const float *nb_w, int nnz,
+                       const float *lap_ref, const float *vweight, int E, int B, int V, float *terms, void *workspace,
+                       void *stream);
+int smplr_mesh_reg_bwd(const float *verts, const int32_t *nb_off, const int32_t *nb_idx, const float *nb_w, int nnz,
+                       const float *lap_ref, const float *vweight, int E, const float *g, int B, int V, float *dverts,
+                       void *stream);
+/* Adam over free offsets D (B, n), n = 3 V: smplr_fit_step's update 5 with col_scale = gscale = 1 and the row's own step
+ * count t[b], in either mode (SMPLR_FIT_KERAS / SMPLR_FIT_TORCH), operation for operation.  g, m, v (B, n); t, bad (B) int32;
+ * loss (B).  A row whose loss[b] is not finite is a bad call: bad[b] += 1 and D, m, v, t of the row keep their bits.
+ * Otherwise t[b] += 1 and m, v are stored; D[b, j] is not stored to where the new m is 0.  One launch of B workgroups, all
+ * state in device memory: a captured graph replays it.  Limits: 1 <= n <= 3 * 2^24, beta1, beta2 in [0, 1), eps >= 0, lr
+ * finite, B >= 0 (B = 0 is a no-op), no null pointer.                                                                      */
+int smplr_offset_step(float *D, const float *g, float *m, float *v, int32_t *t, int32_t *bad, const float *loss, float lr,
+                      float beta1, float beta2, float eps, int mode, int B, int n, void *stream);
+
 /* ---- prediction figures: predict.py:28-77 (_seg.png, _projects.png, _verts_overlay.png), train.py:283-290,
  * train_stage2_silhouette.py:318-329, predict_realtime.py:75-96; INTEGRATION.md 4h -------------------------------------
  * One launch each on the caller's stream; no workspace, no allocation, no synchronisation, no global atomics.  Colours

@@ -95,6 +95,10 @@ SIGNATURES = {
     "smplr_pen_bwd": (c_int, [P, P, P, P, P, I, I, P, P]),
     "smplr_kp_fwd": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, c_float, P, P, P, P, P, P, P]),
     "smplr_kp_bwd": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, c_float, P, P, P, P]),
+    "smplr_mesh_reg_workspace": (c_size_t, [I, I]),
+    "smplr_mesh_reg_fwd": (c_int, [P, P, P, P, I, P, P, I, I, I, P, P, P]),
+    "smplr_mesh_reg_bwd": (c_int, [P, P, P, P, I, P, P, I, P, I, I, P, P]),
+    "smplr_offset_step": (c_int, [P, P, P, P, P, P, P, c_float, c_float, c_float, c_float, I, I, I, P]),
     "smplr_seg_colour": (c_int, [P, P, I, I, I, I, P, I, I, P, I, I, I, P, P]),
     "smplr_scatter_points": (c_int, [P, P, P, I, P, I, I, I, I, c_float, I, I, I, I, P, P, P]),
     "smplr_fit_step": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, c_float, P, P, I, I, I, c_float, c_float, c_float,

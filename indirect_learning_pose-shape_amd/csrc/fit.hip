@@ -43,6 +43,7 @@
 //                    definition a - h, tests/_fit_group_oracle.py restates it.
 //  prior_kernel      the prior alone (smplr_prior_energy): energy (B, 4) = E_pose, E_angle, E_shape unweighted and the
 //                    weighted E; comp (B) = k*; grad (B, P) or NULL, every column written.
+//  offset_adam_kernel  update 5 alone over a row of n = 3 V free vertex offsets (smplr_offset_step), one workgroup per row.
 #include <tuple>
 #include "common.h"
 #include "prior_device.h"
@@ -355,6 +356,37 @@ __global__ __launch_bounds__(FT_T) void prior_kernel(const float *__restrict__ x
   if (grad && j < P) grad[row + j] = po.grad;
 }
 
+// Adam over free per-vertex offsets (smplr_offset_step): row b's n = 3 V entries with the row's own step count.  One
+// workgroup of OS_T lanes per row walks the row - the row's scalars t[b] and loss[b] are read by every lane before the one
+// barrier and written by lane 0 behind it, so no lane of the row can meet the new count (rows split over several
+// workgroups would need a second launch for that).  ft_bias / ft_adam with col_scale = gscale = 1: the two modes are
+// fit_step_kernel's, operation for operation.
+constexpr int OS_T = 1024;
+
+__global__ __launch_bounds__(OS_T) void offset_adam_kernel(float *__restrict__ D, const float *__restrict__ g, float *__restrict__ m,
+                                                           float *__restrict__ v, int *__restrict__ t, int *__restrict__ bad,
+                                                           const float *__restrict__ loss, float lr, float beta1, float beta2,
+                                                           float eps, int mode, int n) {
+  const int b = blockIdx.x;
+  const int t0 = t[b];
+  const float L = loss[b];
+  __syncthreads();
+  if (!finitef(L)) {
+    if (threadIdx.x == 0) bad[b] += 1;
+    return;
+  }
+  const int t1 = t0 + 1;
+  if (threadIdx.x == 0) t[b] = t1;
+  const FtBias bc = ft_bias(lr, beta1, beta2, mode, t1);
+  const long long row = (long long)b * n;
+  for (int j = threadIdx.x; j < n; j += OS_T) {
+    const FtNew o = ft_adam(g[row + j], m[row + j], v[row + j], D[row + j], 1.0f, bc, beta1, beta2, eps, 1.0f, mode);
+    m[row + j] = o.m;
+    v[row + j] = o.v;
+    if (o.move) D[row + j] = o.x;
+  }
+}
+
 // the checks the two prior launchers share; 0 or SMPLR_EINVAL with the message set
 static int prior_args_check(const char *who, int P, const PriorArgs &pa, bool launches) {
   SMPLR_REQUIRE(pa.num_cam >= 0 && P == pa.num_cam + 82 && P <= FT_T, "%s: P=%d is not num_cam + 82 (num_cam=%d, 0..%d)", who, P,
@@ -386,6 +418,21 @@ int smplr_prior_energy(const float *x, int B, int P, int num_cam, const float *m
   SMPLR_REQUIRE(x && energy && comp, "smplr_prior_energy: null pointer (only grad may be NULL)");
   hipLaunchKernelGGL(prior_kernel, dim3((unsigned)B), dim3(FT_T), 0, as_stream(stream), x, P, pa, energy, comp, grad);
   SMPLR_LAUNCH_CHECK("smplr_prior_energy");
+  return 0;
+}
+
+int smplr_offset_step(float *D, const float *g, float *m, float *v, int32_t *t, int32_t *bad, const float *loss, float lr,
+                      float beta1, float beta2, float eps, int mode, int B, int n, void *stream) {
+  using namespace smplr;
+  SMPLR_REQUIRE(B >= 0 && n >= 1 && n <= 3 * (1 << 24), "smplr_offset_step: bad sizes B=%d n=%d (B >= 0, 1 <= n <= 3 * 2^24)", B, n);
+  SMPLR_REQUIRE(mode == SMPLR_FIT_KERAS || mode == SMPLR_FIT_TORCH, "smplr_offset_step: mode %d is neither keras (0) nor torch (1)", mode);
+  SMPLR_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "smplr_offset_step: beta1, beta2 must lie in [0, 1)");
+  SMPLR_REQUIRE(eps >= 0.f && lr - lr == 0.f, "smplr_offset_step: eps must be >= 0 and lr finite");
+  if (B == 0) return 0;
+  SMPLR_REQUIRE(D && g && m && v && t && bad && loss, "smplr_offset_step: null pointer");
+  hipLaunchKernelGGL(offset_adam_kernel, dim3((unsigned)B), dim3(OS_T), 0, as_stream(stream), D, g, m, v,
+                     reinterpret_cast<int *>(t), reinterpret_cast<int *>(bad), loss, lr, beta1, beta2, eps, mode, n);
+  SMPLR_LAUNCH_CHECK("smplr_offset_step");
   return 0;
 }
 

@@ -1187,6 +1187,83 @@ Tensor mesh_measures_bwd_meta(const Tensor &verts, const Tensor &faces, const Te
   return at::empty({d.B, d.V, 3}, verts.options());
 }
 
+// ---- mesh regularisers (csrc/meshreg.hip): verts (B, V, 3), the one-ring CSR nb_off (V + 1) int32, nb_idx (nnz) int32,
+// nb_w (nnz, 3) = [w_ik, w_ki, 1 / l^2], lap_ref (V, 3) or None, vweight (V) or None, E counted edges -> terms (B, 2) =
+// (E_lap, E_edge); the backward takes g (B, 2) and returns dverts (B, V, 3) -------------------------------------------------
+struct MeshRegDims { int64_t B, V, nnz; };
+MeshRegDims mesh_reg_check(const Tensor &verts, const Tensor &nb_off, const Tensor &nb_idx, const Tensor &nb_w,
+                           const c10::optional<Tensor> &lap_ref, const c10::optional<Tensor> &vweight, int64_t E) {
+  TORCH_CHECK(verts.dim() == 3 && verts.size(2) == 3 && verts.scalar_type() == at::kFloat, "verts must be (B, V, 3) float32");
+  MeshRegDims d{verts.size(0), verts.size(1), nb_idx.numel()};
+  TORCH_CHECK(d.V >= 1 && d.V <= (1 << 24) && d.B <= INT32_MAX, "V must be in 1..2^24");
+  TORCH_CHECK(nb_off.dim() == 1 && nb_off.size(0) == d.V + 1 && nb_off.scalar_type() == at::kInt, "nb_off must be (V + 1,) int32");
+  TORCH_CHECK(nb_idx.dim() == 1 && d.nnz <= (1 << 28) && nb_idx.scalar_type() == at::kInt, "nb_idx must be (nnz,) int32, nnz <= 2^28");
+  TORCH_CHECK(nb_w.dim() == 2 && nb_w.size(0) == d.nnz && nb_w.size(1) == 3 && nb_w.scalar_type() == at::kFloat,
+              "nb_w must be (nnz, 3) float32");
+  TORCH_CHECK(!lap_ref || (lap_ref->dim() == 2 && lap_ref->size(0) == d.V && lap_ref->size(1) == 3 && lap_ref->scalar_type() == at::kFloat),
+              "lap_ref must be (V, 3) float32");
+  TORCH_CHECK(!vweight || (vweight->dim() == 1 && vweight->size(0) == d.V && vweight->scalar_type() == at::kFloat),
+              "vweight must be (V,) float32");
+  TORCH_CHECK(E >= 0 && 2 * E <= d.nnz, "E = ", E, " edges need 0 <= 2 E <= nnz = ", d.nnz);
+  return d;
+}
+void mesh_reg_on_device(const Tensor &verts, const Tensor &nb_off, const Tensor &nb_idx, const Tensor &nb_w,
+                        const c10::optional<Tensor> &lap_ref, const c10::optional<Tensor> &vweight) {
+  dev_f32(verts, "verts");
+  dev_typed(nb_off, at::kInt, "nb_off"); dev_typed(nb_idx, at::kInt, "nb_idx"); dev_f32(nb_w, "nb_w");
+  same_device(verts, {{"nb_off", &nb_off}, {"nb_idx", &nb_idx}, {"nb_w", &nb_w}});
+  if (lap_ref) { dev_f32(*lap_ref, "lap_ref"); same_device(verts, {{"lap_ref", &*lap_ref}}); }
+  if (vweight) { dev_f32(*vweight, "vweight"); same_device(verts, {{"vweight", &*vweight}}); }
+}
+Tensor mesh_reg_fwd(const Tensor &verts, const Tensor &nb_off, const Tensor &nb_idx, const Tensor &nb_w,
+                    const c10::optional<Tensor> &lap_ref, const c10::optional<Tensor> &vweight, int64_t E) {
+  const MeshRegDims d = mesh_reg_check(verts, nb_off, nb_idx, nb_w, lap_ref, vweight, E);
+  mesh_reg_on_device(verts, nb_off, nb_idx, nb_w, lap_ref, vweight);
+  DeviceGuard g(verts.device());
+  Tensor terms = f32({d.B, 2}, verts);
+  if (d.B == 0) return terms;
+  Tensor ws = bytes(smplr_mesh_reg_workspace((int)d.B, (int)d.V), verts);
+  ok(smplr_mesh_reg_fwd(verts.data_ptr<float>(), nb_off.data_ptr<int32_t>(), d.nnz ? nb_idx.data_ptr<int32_t>() : nullptr,
+                        d.nnz ? nb_w.data_ptr<float>() : nullptr, (int)d.nnz, static_cast<const float *>(opt_ptr(lap_ref)),
+                        static_cast<const float *>(opt_ptr(vweight)), (int)E, (int)d.B, (int)d.V, terms.data_ptr<float>(),
+                        ws.data_ptr(), cur_stream()),
+     "smplr_mesh_reg_fwd");
+  return terms;
+}
+Tensor mesh_reg_fwd_meta(const Tensor &verts, const Tensor &nb_off, const Tensor &nb_idx, const Tensor &nb_w,
+                         const c10::optional<Tensor> &lap_ref, const c10::optional<Tensor> &vweight, int64_t E) {
+  const MeshRegDims d = mesh_reg_check(verts, nb_off, nb_idx, nb_w, lap_ref, vweight, E);
+  return at::empty({d.B, 2}, verts.options());
+}
+MeshRegDims mesh_reg_bwd_check(const Tensor &verts, const Tensor &nb_off, const Tensor &nb_idx, const Tensor &nb_w,
+                               const c10::optional<Tensor> &lap_ref, const c10::optional<Tensor> &vweight, int64_t E,
+                               const Tensor &g) {
+  const MeshRegDims d = mesh_reg_check(verts, nb_off, nb_idx, nb_w, lap_ref, vweight, E);
+  TORCH_CHECK(g.dim() == 2 && g.size(0) == d.B && g.size(1) == 2 && g.scalar_type() == at::kFloat, "g must be (B, 2) float32");
+  return d;
+}
+Tensor mesh_reg_bwd(const Tensor &verts, const Tensor &nb_off, const Tensor &nb_idx, const Tensor &nb_w,
+                    const c10::optional<Tensor> &lap_ref, const c10::optional<Tensor> &vweight, int64_t E, const Tensor &g) {
+  const MeshRegDims d = mesh_reg_bwd_check(verts, nb_off, nb_idx, nb_w, lap_ref, vweight, E, g);
+  mesh_reg_on_device(verts, nb_off, nb_idx, nb_w, lap_ref, vweight);
+  dev_f32(g, "g");
+  same_device(verts, {{"g", &g}});
+  DeviceGuard guard(verts.device());
+  Tensor dverts = f32({d.B, d.V, 3}, verts);
+  if (d.B == 0) return dverts;
+  ok(smplr_mesh_reg_bwd(verts.data_ptr<float>(), nb_off.data_ptr<int32_t>(), d.nnz ? nb_idx.data_ptr<int32_t>() : nullptr,
+                        d.nnz ? nb_w.data_ptr<float>() : nullptr, (int)d.nnz, static_cast<const float *>(opt_ptr(lap_ref)),
+                        static_cast<const float *>(opt_ptr(vweight)), (int)E, g.data_ptr<float>(), (int)d.B, (int)d.V,
+                        dverts.data_ptr<float>(), cur_stream()),
+     "smplr_mesh_reg_bwd");
+  return dverts;
+}
+Tensor mesh_reg_bwd_meta(const Tensor &verts, const Tensor &nb_off, const Tensor &nb_idx, const Tensor &nb_w,
+                         const c10::optional<Tensor> &lap_ref, const c10::optional<Tensor> &vweight, int64_t E, const Tensor &g) {
+  const MeshRegDims d = mesh_reg_bwd_check(verts, nb_off, nb_idx, nb_w, lap_ref, vweight, E, g);
+  return at::empty({d.B, d.V, 3}, verts.options());
+}
+
 int64_t abi_version() { return smplr_abi_version(); }
 #ifndef SMPLR_TORCH_OPS_ID
 #define SMPLR_TORCH_OPS_ID "unknown"
@@ -1250,6 +1327,9 @@ TORCH_LIBRARY(smplraster, m) {
   m.def("mesh_measures_bwd(Tensor verts, Tensor faces, Tensor vf_off, Tensor vf_face, Tensor? face_part, Tensor? planes, "
         "Tensor? part_mask, Tensor ext_idx, Tensor status, Tensor? g_volume, Tensor? g_area, Tensor? g_extent, "
         "Tensor? g_girth) -> Tensor");
+  m.def("mesh_reg_fwd(Tensor verts, Tensor nb_off, Tensor nb_idx, Tensor nb_w, Tensor? lap_ref, Tensor? vweight, int E) -> Tensor");
+  m.def("mesh_reg_bwd(Tensor verts, Tensor nb_off, Tensor nb_idx, Tensor nb_w, Tensor? lap_ref, Tensor? vweight, int E, "
+        "Tensor g) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch key is named CUDA in torch)
@@ -1279,6 +1359,8 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("fit_step_group", &fit_step_group);
   m.impl("mesh_measures", &mesh_measures);
   m.impl("mesh_measures_bwd", &mesh_measures_bwd);
+  m.impl("mesh_reg_fwd", &mesh_reg_fwd);
+  m.impl("mesh_reg_bwd", &mesh_reg_bwd);
 }
 
 TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
@@ -1308,4 +1390,6 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("fit_step_group", &fit_step_group_meta);
   m.impl("mesh_measures", &mesh_measures_meta);
   m.impl("mesh_measures_bwd", &mesh_measures_bwd_meta);
+  m.impl("mesh_reg_fwd", &mesh_reg_fwd_meta);
+  m.impl("mesh_reg_bwd", &mesh_reg_bwd_meta);
 }

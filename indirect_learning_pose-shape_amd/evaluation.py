@@ -265,3 +265,28 @@ def evaluate_keypoints(proj_or_details, target, conf, thresholds=(0.05, 0.1, 0.2
     return {"mean_error": float(dist.sum()) / n if n else nan,
             "per_joint": torch.where(n_k > 0, dist.sum(0) / n_k.clamp(min=1), torch.full_like(zero, nan)),
             "pck": pck, "count": n, "per_joint_count": n_k, "rows": B - int(bad.sum()), "nonfinite": int(bad.sum())}
+
+
+@torch.no_grad()
+def evaluate_registration(verts, topo, points, counts, spec, reg_verts=None):
+    """How well registered meshes verts (B, V, 3) fp32 (metres) lie on scans points (B, N, 3) with counts (B,) or None, and
+    what the surface paid for it: one `scan.surface_distance` call and one `meshreg.mesh_regularisers` call.  topo the
+    meshes' `render.MeshTopology`, spec a `meshreg.MeshRegSpec`; reg_verts (B, V, 3) is the mesh the regulariser sees when
+    that is not verts (`OffsetFitter` regularises v_template + D, not the posed surface).
+    -> dict(scan_to_mesh (B,), mesh_to_scan (B,) float64 = the mean of sqrt(d2) over the row's counted points / of sqrt(vd2)
+    over its vertices, in metres (NaN for a row without one or with a status), e_lap (B,), e_edge (B,) fp32, nonfinite =
+    rows with a status).  Everything stays on verts' device but `nonfinite`."""
+    from .meshreg import mesh_regularisers
+    from .scan import surface_distance
+    out = surface_distance(verts, topo, points, counts)
+    ok = out["status"] == 0
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=verts.device)
+
+    def mean_dist(d2, hit):
+        hit = hit & ok[:, None]
+        n = hit.sum(1)
+        s = torch.where(hit, d2.to(torch.float64), torch.zeros((), dtype=torch.float64, device=verts.device)).sqrt().sum(1)
+        return torch.where(n > 0, s / n.clamp(min=1), nan)
+    terms = mesh_regularisers(verts if reg_verts is None else reg_verts, spec, return_terms=True)
+    return {"scan_to_mesh": mean_dist(out["d2"], out["face"] >= 0), "mesh_to_scan": mean_dist(out["vd2"], out["vpoint"] >= 0),
+            "e_lap": terms[:, 0], "e_edge": terms[:, 1], "nonfinite": int((~ok).sum())}

@@ -1118,15 +1118,19 @@ class ScanFitter(_Fitter):
             return torch.as_tensor(row, dtype=torch.float32).repeat(B, 1)
         return self._initial(B, init, device, default)
 
-    def place(self, x):
-        """x (B, 86) -> the body in the scan's frame: x[:, 0] SMPLLayer(x) + x[:, 1:4]; differentiable."""
-        return x[:, 0, None, None] * self.layer(x) + x[:, None, 1:4]
+    def place(self, x, offsets=None):
+        """x (B, 86) -> the body in the scan's frame: x[:, 0] SMPLLayer(x) + x[:, 1:4]; differentiable.  offsets (B, V, 3):
+        SMPL+D offsets, handed to the layer (differentiable in them as well)."""
+        if offsets is None:
+            return x[:, 0, None, None] * self.layer(x) + x[:, None, 1:4]
+        return x[:, 0, None, None] * self.layer(x, offsets) + x[:, None, 1:4]
 
-    def terms(self, x, points, counts=None, verts=None):
+    def terms(self, x, points, counts=None, verts=None, offsets=None):
         """-> (p2m terms (B, N) scaled by N / counts or None, m2p terms (B, V) or None, the op's dict): what `fit_step`
-        gets as `loss` and `silh_loss`; differentiable in x.  verts: `place(x)` when the caller has it already."""
+        gets as `loss` and `silh_loss`; differentiable in x.  verts: `place(x)` when the caller has it already; offsets go
+        to `place` when it has not."""
         from .scan import surface_distance
-        out = surface_distance(self.place(x) if verts is None else verts, self.topo, points, counts, self.directions)
+        out = surface_distance(self.place(x, offsets) if verts is None else verts, self.topo, points, counts, self.directions)
         rho = (lambda d: d) if self.sigma is None else (lambda d: robust_rho(d, self.sigma))
         N = int(points.shape[1])
         p2m = m2p = None
@@ -1311,3 +1315,209 @@ class KeypointFitter(_Fitter):
                          patience=patience, grad_scale=grad_scale, graph=graph, check_every=check_every, history=history,
                          beta1=beta1, beta2=beta2, eps=eps, graph_steps=graph_steps, prior=prior, prior_weights=prior_weights,
                          group_size=group_size, tie=tie, smooth=smooth, pen_weight=pen_weight)
+
+
+# ---- SMPL+D registration: free vertex offsets under mesh regularisers --------------------------------------------------
+def offset_step(D, grad, m, v, t, bad, loss, lr=1e-3, beta1=0.9, beta2=0.999, eps=KERAS_EPS, mode="torch"):
+    """One smplr_offset_step launch (in place): Adam over the rows of D (B, V, 3) with the row's own step count t (B,) int32,
+    in `fit_step`'s keras or torch form.  grad, m, v: D's shape; loss (B,): a row whose loss is not finite is a bad call -
+    bad[b] += 1 and nothing else of the row changes.  HIP tensors only."""
+    if mode not in MODES:
+        raise ValueError("mode %r is none of %s" % (mode, MODES))
+    rc = _lib.require_cuda
+    if not D.is_contiguous():
+        raise RuntimeError("D must be contiguous (it is updated in place)")
+    rc(D, "D")
+    B = int(D.shape[0])
+    n = int(D.numel() // B) if B else int(np.prod(D.shape[1:]))
+    if D.dim() < 2 or n < 1:
+        raise RuntimeError("D must be (B, ...) with at least one entry per row, got %s" % (tuple(D.shape),))
+    for name, a in (("grad", grad), ("m", m), ("v", v)):
+        if tuple(a.shape) != tuple(D.shape) or not a.is_contiguous():
+            raise RuntimeError("%s must be a contiguous %s tensor, got %s" % (name, tuple(D.shape), tuple(a.shape)))
+        rc(a, name)
+    for name, a in (("t", t), ("bad", bad)):
+        if tuple(a.shape) != (B,):
+            raise RuntimeError("%s must be (%d,), got %s" % (name, B, tuple(a.shape)))
+        rc(a, name, torch.int32)
+    if tuple(loss.shape) != (B,) or not loss.is_contiguous():
+        raise RuntimeError("loss must be a contiguous (%d,) tensor, got %s" % (B, tuple(loss.shape)))
+    rc(loss, "loss")
+    for name, a in (("grad", grad), ("m", m), ("v", v), ("t", t), ("bad", bad), ("loss", loss)):
+        if a.device != D.device:
+            raise RuntimeError("%s lives on %s, D on %s" % (name, a.device, D.device))
+    with torch.cuda.device(D.device):
+        check(_lib.load().smplr_offset_step(ptr(D), ptr(grad), ptr(m), ptr(v), ptr(t), ptr(bad), ptr(loss), float(lr), float(beta1),
+                                            float(beta2), float(eps), MODES.index(mode), B, n, stream()), "smplr_offset_step")
+    return D
+
+
+@dataclass
+class OffsetFitResult:
+    """offsets (B, V, 3): D at the end; x (B, 86): the parameters at the end (the start, unless fit_params); history
+    (steps, B) fp32 per-row loss trace or None; bad (B,) int32: iterations that met a non-finite loss (and changed nothing of
+    D); steps: iterations run; t (B,) int32: D's update count; state: the `FitState` of x with fit_params, else None."""
+    offsets: torch.Tensor
+    x: torch.Tensor
+    history: Optional[torch.Tensor]
+    bad: torch.Tensor
+    steps: int
+    t: torch.Tensor
+    state: Optional[FitState] = None
+
+
+class OffsetFitter:
+    """SMPL+D registration behind a `ScanFitter`: free per-vertex offsets D (B, V, 3) move the surface onto the scan, held
+    together by the regularisers of a `meshreg.MeshRegSpec`.  Row b's loss is
+
+        L_b = [ScanFitter's data terms of place(x, D)] + lap_weight E_lap + edge_weight E_edge + offset_weight mean_i |D_i|^2
+
+    with (E_lap, E_edge) = `mesh_regularisers(v_template + D, spec)`: the regulariser sees the UNPOSED mesh in the template's
+    frame - the frame a spec built on v_template was measured in (E_lap with lap_ref = L(ref) is not invariant under a
+    rotation of the mesh, so the posed surface would be penalised for its pose), and there E_lap is mean |L(D)|^2.  An
+    iteration is place, the terms, one `autograd.grad` with respect to D (and x with fit_params), `fit_step` on x (with
+    fit_params) and `offset_step` on D; every launch reproduces its bits, so two fits from the same start agree bit for bit.
+    penetration=True adds the scan fitter's self-penetration term (it must have been built with one).
+
+        reg = OffsetFitter(scan_fitter, MeshRegSpec(scan_fitter.topo, model.v_template, "cotangent"))
+        r = reg.fit(points, counts, x=fit.x, steps=200, lr=1e-3, lap_weight=1e4, edge_weight=1.0, offset_weight=1.0)
+    """
+
+    def __init__(self, scan_fitter, spec, penetration=None):
+        from .meshreg import MeshRegSpec
+        if not isinstance(scan_fitter, ScanFitter):
+            raise TypeError("scan_fitter must be a ScanFitter")
+        if not isinstance(spec, MeshRegSpec):
+            raise TypeError("spec must be a meshreg.MeshRegSpec")
+        if spec.num_verts != scan_fitter.topo.num_verts:
+            raise ValueError("the spec has %d vertices, the fitter's topology %d" % (spec.num_verts, scan_fitter.topo.num_verts))
+        if penetration not in (None, False, True):
+            raise TypeError("penetration must be None, False or True (the scan fitter's own term)")
+        if penetration and scan_fitter.pen_topo is None:
+            raise ValueError("penetration=True needs a ScanFitter built with penetration=...")
+        self.scan, self.spec, self.penetration = scan_fitter, spec, bool(penetration)
+        self.V = spec.num_verts
+        self._template = {}
+
+    def template(self, device):
+        """v_template (1, V, 3) fp32 on `device`: the frame the regulariser works in."""
+        device = torch.device(device)
+        t = self._template.get(device)
+        if t is None:
+            t = torch.as_tensor(np.asarray(self.scan.layer._model.v_template), dtype=torch.float32).reshape(1, self.V, 3).to(device)
+            self._template[device] = t
+        return t
+
+    def row_loss(self, x, D, points, counts, wts, pen_w=None):
+        """-> L (B,), differentiable in x and D: the composition `fit` iterates.  wts (3,) device tensor = (lap_weight,
+        edge_weight, offset_weight); pen_w (1,) device tensor with the penetration term."""
+        from .meshreg import mesh_regularisers
+        sf = self.scan
+        verts = sf.place(x, D)
+        p2m, m2p, _ = sf.terms(x, points, counts, verts)
+        L = None
+        if p2m is not None:
+            L = p2m.sum(1) / float(p2m.shape[1])
+        if m2p is not None:
+            d = m2p.sum(1) / float(m2p.shape[1])
+            L = d if L is None else L + sf.m2p_weight * d
+        reg = mesh_regularisers(self.template(D.device) + D, self.spec, return_terms=True)
+        L = L + wts[0] * reg[:, 0] + wts[1] * reg[:, 1] + wts[2] * ((D * D).sum((1, 2)) / float(self.V))
+        if pen_w is not None:
+            from .penetration import self_penetration
+            L = L + pen_w * self_penetration(verts, sf.pen_topo, sf.pen_collide).mean(1)
+        return L
+
+    def _iteration(self, D, m, v, t, bad, state, points, counts, wts, pen_w, hist, it, kw, xkw, fit_params):
+        x = state.x.detach().requires_grad_(True) if fit_params else state.x
+        Dg = D.detach().requires_grad_(True)                      # (shares D's memory: the kernel updates it in place)
+        L = self.row_loss(x, Dg, points, counts, wts, pen_w)
+        grads = torch.autograd.grad(L.sum(), [Dg, x] if fit_params else [Dg])
+        Ld = L.detach().contiguous()
+        if hist is not None:
+            hist.index_copy_(0, it, Ld[None])
+            it.add_(1)
+        if fit_params:
+            fit_step(state, grads[1].contiguous(), Ld[:, None].contiguous(), None, 1.0, xkw["cs"], None, **xkw["kw"])
+        offset_step(D, grads[0].contiguous(), m, v, t, bad, Ld, **kw)
+
+    def fit(self, points, counts, x, steps=200, lr=1e-3, lap_weight=1.0, edge_weight=1.0, offset_weight=0.0, stages=None,
+            fit_params=False, history=False, graph=False, offsets=None, mode="torch", beta1=0.9, beta2=0.999, eps=KERAS_EPS,
+            x_lr=None, pen_weight=None):
+        """points (B, N, 3) fp32 on the HIP device, counts (B,) or None, x (B, 86) the parameters a `ScanFitter.fit` ended
+        with -> OffsetFitResult.  steps, or stages = [(steps, column_scale), ...] as `ScanFitter.fit` takes them (the column
+        scales act on x, with fit_params); lap_weight, edge_weight, offset_weight (and pen_weight with penetration=True): one
+        float or a list of one per stage.  offsets: the start (None: zeros).  fit_params: x moves too, through `fit_step`
+        with x_lr (None: lr).  graph: one iteration is captured once and replayed."""
+        if mode not in MODES:
+            raise ValueError("mode %r is none of %s" % (mode, MODES))
+        sf = self.scan
+        points, counts = sf._points(points, counts)
+        B, dev = int(points.shape[0]), points.device
+        if not isinstance(x, torch.Tensor) or tuple(x.shape) != (B, sf.P):
+            raise ValueError("x must be a (%d, %d) tensor" % (B, sf.P))
+        stage_list = check_stages(stages, sf.P, steps)
+        names = ("lap_weight", "edge_weight", "offset_weight")
+        per = [_stage_pen_weights(w, stage_list, n) for w, n in zip((lap_weight, edge_weight, offset_weight), names)]
+        if self.penetration:
+            pen_stages = _stage_pen_weights(pen_weight, stage_list)
+        elif pen_weight is not None:
+            raise ValueError("pen_weight goes with OffsetFitter(..., penetration=True)")
+        total = sum(n for n, _ in stage_list)
+        kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), mode=mode)
+        with torch.cuda.device(dev):
+            x0 = _lib.require_cuda(x.detach().to(dev), "x").clone()
+            if offsets is None:
+                D = torch.zeros((B, self.V, 3), dtype=torch.float32, device=dev)
+            else:
+                if tuple(offsets.shape) != (B, self.V, 3):
+                    raise ValueError("offsets must be (%d, %d, 3), got %s" % (B, self.V, tuple(offsets.shape)))
+                D = _lib.require_cuda(offsets.detach().to(dev), "offsets").clone()
+            m, v = torch.zeros_like(D), torch.zeros_like(D)
+            t = torch.zeros(B, dtype=torch.int32, device=dev)
+            bad = torch.zeros(B, dtype=torch.int32, device=dev)
+            state = FitState.new(x0)
+            wts = torch.zeros(3, dtype=torch.float32, device=dev)
+            pen_w = torch.zeros(1, dtype=torch.float32, device=dev) if self.penetration else None
+            hist = torch.full((total, B), float("nan"), dtype=torch.float32, device=dev) if history and total else None
+            it = torch.zeros(1, dtype=torch.long, device=dev)
+            cs = torch.ones(sf.P, dtype=torch.float32, device=dev)
+            xkw = dict(cs=cs, kw=dict(kw, lr=float(lr if x_lr is None else x_lr), grad_scale=1.0, patience=0))
+
+            def set_stage(si):
+                wts.copy_(torch.tensor([p[si] for p in per], dtype=torch.float32))
+                cs.copy_(stage_list[si][1].to(dev))
+                if pen_w is not None:
+                    pen_w.fill_(pen_stages[si])
+
+            def one(D_, m_, v_, t_, bad_, st, h, i):
+                self._iteration(D_, m_, v_, t_, bad_, st, points, counts, wts, pen_w, h, i, kw, xkw, fit_params)
+            replay = None
+            if total:
+                set_stage(0)
+            if graph and B > 0 and total > 0:
+                # warm-up on a side stream and on scratch copies, then one iteration of the real state in a graph
+                scratch = (D.clone(), m.clone(), v.clone(), t.clone(), bad.clone(), state.clone())
+                side = torch.cuda.Stream(device=dev)
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    for _ in range(3):
+                        one(*scratch, None, None)
+                torch.cuda.current_stream().wait_stream(side)
+                torch.cuda.synchronize()
+                g_ = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g_):
+                    one(D, m, v, t, bad, state, hist, it)
+                replay = g_.replay
+                # (the capture ran nothing; the state is still the start's)
+            done = 0
+            for si, (n, _) in enumerate(stage_list):
+                set_stage(si)
+                for _ in range(n):
+                    if replay is not None:
+                        replay()
+                    else:
+                        one(D, m, v, t, bad, state, hist, it)
+                    done += 1
+            torch.cuda.synchronize()
+        return OffsetFitResult(offsets=D, x=state.x, history=hist, bad=bad, steps=done, t=t, state=state if fit_params else None)

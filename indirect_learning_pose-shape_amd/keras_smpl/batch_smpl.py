@@ -58,11 +58,16 @@ class SMPLLayer(nn.Module):
             self._consts_device = device
         return self._consts
 
-    def forward(self, x):
+    def forward(self, x, offsets=None):
+        """offsets: None, or (B, V, 3) fp32 free vertex offsets D (SMPL+D), added to v_posed after the blend shapes and
+        before skinning; `J_transformed` does not depend on them.  Differentiable in x and D."""
         if x.dim() != 2 or x.shape[1] != self.num_cam + self.num_thetas + self.num_betas:
             raise RuntimeError("SMPLLayer expects x of shape (B, %d), got %s"
                                % (self.num_cam + 82, tuple(x.shape)))
-        verts, jt = ops.BatchSMPLFn.apply(x, self.constants(x.device), self.num_cam)
+        if offsets is not None:
+            verts, jt = ops.BatchSMPLOffsetFn.apply(x, offsets, self.constants(x.device), self.num_cam)
+        else:
+            verts, jt = ops.BatchSMPLFn.apply(x, self.constants(x.device), self.num_cam)
         self.J_transformed = jt
         return verts
 

@@ -694,6 +694,81 @@ class BatchSMPLFn(torch.autograd.Function):
         return dx, None, None
 
 
+@on_device
+def _skin_bwd(dverts, v_posed, A, x, c: SMPLConstants):
+    """smplr_skin_bwd for a cotangent on verts alone -> dv_posed (B, V, 3), dA (B, 24, 12)."""
+    lib = _lib.load()
+    B = v_posed.shape[0]
+    dv_posed, dA = _empty((B, c.V, 3), v_posed), _empty((B, 24, 12), v_posed)
+    ws = _workspace(lib.smplr_skin_bwd_workspace(B, c.V), v_posed)
+    check(lib.smplr_skin_bwd(ptr(dverts), None, ptr(v_posed), ptr(c.lbs_weights), ptr(c.lbs_top4), ptr(A), ptr(x), x.shape[1],
+                             B, c.V, 1, ptr(dv_posed), ptr(dA), None, ptr(ws), stream()), "smplr_skin_bwd")
+    return dv_posed, dA
+
+
+@on_device
+def _blend_pose_bwd(x, num_cam, c: SMPLConstants, Rs, J, A, dv_posed, dA, dJt):
+    """smplr_blend3_bwd | smplr_blend_bwd, then smplr_pose_bwd: dv_posed, dA (+ optional dJ_transformed) -> dx (B, x_stride);
+    behind `_skin_bwd` the chain smplr_smpl_bwd fuses, bit for bit."""
+    lib = _lib.load()
+    B = x.shape[0]
+    dcoef = _empty((B, 220), x)
+    if c.blend3_bwd is not None:
+        ws = _workspace(lib.smplr_blend3_bwd_workspace(B, 3 * c.V), x)
+        check(lib.smplr_blend3_bwd(ptr(dv_posed), ptr(c.blend3_bwd), B, 3 * c.V, ptr(dcoef), ptr(ws), stream()), "smplr_blend3_bwd")
+    else:
+        ws = _workspace(lib.smplr_blend_bwd_workspace(B, 3 * c.V), x)
+        check(lib.smplr_blend_bwd(ptr(dv_posed), ptr(c.blend_t), B, 3 * c.V, ptr(dcoef), ptr(ws), stream()), "smplr_blend_bwd")
+    dx = _empty(tuple(x.shape), x)
+    if x.shape[1] > num_cam + 82:
+        dx.zero_()
+    check(lib.smplr_pose_bwd(ptr(x), x.shape[1], num_cam, B, ptr(c.J_dirs), ptr(c.parents), ptr(Rs), ptr(J), ptr(A), ptr(dcoef),
+                             ptr(dA), ptr(dJt), None, ptr(dx), stream()), "smplr_pose_bwd")
+    return dx
+
+
+class BatchSMPLOffsetFn(torch.autograd.Function):
+    """SMPL+D: x (B, num_cam+82), offsets D (B,V,3) -> verts (B,V,3), J_transformed (B,24,3) with D added to v_posed after
+    the blend shapes and before skinning; the joints come from the shaped mesh and do not see D.  The backward is the
+    granular chain: smplr_skin_bwd's dv_posed IS dD; dx follows through the blend and pose backwards only when x needs it."""
+
+    @staticmethod
+    @on_device
+    def forward(ctx, x, offsets, consts: SMPLConstants, num_cam: int):
+        x = require_cuda(x, "x")
+        offsets = require_cuda(offsets, "offsets")
+        if tuple(offsets.shape) != (x.shape[0], consts.V, 3):
+            raise RuntimeError("offsets must be (%d, %d, 3), got %s" % (x.shape[0], consts.V, tuple(offsets.shape)))
+        if offsets.device != x.device:
+            raise RuntimeError("offsets live on %s, x on %s" % (offsets.device, x.device))
+        ctx.set_materialize_grads(False)
+        if consts.blend3_fwd is not None:
+            Rs, J, A, Jt, v_posed = _pose_blend_fwd(x, num_cam, consts)        # one launch
+        else:
+            coef, Rs, J, A, Jt = _pose_fwd(x, num_cam, consts)
+            v_posed = _blend_fwd(coef, consts, x.shape[0])
+        v_posed.add_(offsets)                # (saved with D in it: the skinning backward's dA reads the skinned points)
+        verts, _ = _skin_fwd(v_posed, A, consts)
+        ctx.consts, ctx.num_cam = consts, num_cam
+        ctx.save_for_backward(x, Rs, J, A, v_posed)
+        return verts, Jt
+
+    @staticmethod
+    @on_device
+    def backward(ctx, dverts, dJt):
+        x, Rs, J, A, v_posed = ctx.saved_tensors
+        want_x, want_d = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dverts = require_cuda(dverts, "dverts") if dverts is not None else None
+        dJt = require_cuda(dJt, "dJ_transformed") if dJt is not None else None
+        if dverts is None:
+            if not want_x:
+                return None, torch.zeros_like(v_posed) if want_d else None, None, None
+            dverts = torch.zeros_like(v_posed)
+        dv_posed, dA = _skin_bwd(dverts, v_posed, A, x, ctx.consts)
+        dx = _blend_pose_bwd(x, ctx.num_cam, ctx.consts, Rs, J, A, dv_posed, dA, dJt) if want_x else None
+        return dx, dv_posed if want_d else None, None, None
+
+
 class ProjectFn(torch.autograd.Function):
     """(verts (B,V,3), smpl (B,>=4)) -> (B,V',3)   (keras_smpl/projection.py:54-81)."""
 

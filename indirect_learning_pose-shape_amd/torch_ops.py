@@ -86,6 +86,10 @@ SCHEMAS = {
     "mesh_measures_bwd": ("smplraster::mesh_measures_bwd(Tensor verts, Tensor faces, Tensor vf_off, Tensor vf_face, "
                           "Tensor? face_part, Tensor? planes, Tensor? part_mask, Tensor ext_idx, Tensor status, "
                           "Tensor? g_volume, Tensor? g_area, Tensor? g_extent, Tensor? g_girth) -> Tensor"),
+    "mesh_reg_fwd": ("smplraster::mesh_reg_fwd(Tensor verts, Tensor nb_off, Tensor nb_idx, Tensor nb_w, Tensor? lap_ref, "
+                     "Tensor? vweight, int E) -> Tensor"),
+    "mesh_reg_bwd": ("smplraster::mesh_reg_bwd(Tensor verts, Tensor nb_off, Tensor nb_idx, Tensor nb_w, Tensor? lap_ref, "
+                     "Tensor? vweight, int E, Tensor g) -> Tensor"),
 }
 
 _ns = None
