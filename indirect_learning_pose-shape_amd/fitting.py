@@ -645,28 +645,127 @@ def _stage_prior_weights(prior, prior_weights, stage_list):
     return [check_prior_weights(w) for w in (pw if per_stage else [pw] * len(stage_list))]
 
 
-def _stage_pen_weights(pen_weight, stage_list, name="pen_weight"):
-    """`fit`'s pen_weight or kp_weight (None: 1, one float, or a list of one float per stage) -> one float per stage."""
-    pw = 1.0 if pen_weight is None else pen_weight
+def _stage_weights(weight, stage_list, name):
+    """A scalar weight of `fit` - pen_weight, kp_weight, lap_weight, edge_weight, offset_weight - (None: 1, one float, or a
+    list of one float per stage) -> one float per stage; `name` is the argument's, for the messages."""
+    pw = 1.0 if weight is None else weight
     per_stage = isinstance(pw, (list, tuple))
     if per_stage and len(pw) != len(stage_list):
         raise ValueError("%s lists %d weights for %d stages" % (name, len(pw), len(stage_list)))
     out = [float(w) for w in (pw if per_stage else [pw] * len(stage_list))]
     if any(not math.isfinite(w) or w < 0 or w > float(np.finfo(np.float32).max) for w in out):
-        raise ValueError("%s must be finite and >= 0, got %r" % (name, pen_weight))
+        raise ValueError("%s must be finite and >= 0, got %r" % (name, weight))
     return out
 
 
+# the loop's arguments: what every `fit` of `_Fitter`'s family hands on to `_Fitter._fit` by name
+_LOOP_ARGS = ("steps", "lr", "mode", "stages", "patience", "grad_scale", "graph", "check_every", "history", "beta1", "beta2", "eps",
+             "graph_steps", "prior", "prior_weights", "group_size", "tie", "smooth")
+
+
+def _fit_args(given):
+    """What every `fit` starts with, on its own locals(): the mode check - so it is the first error a bad call raises - and
+    the loop's arguments among them, by name."""
+    if given["mode"] not in MODES:
+        raise ValueError("mode %r is none of %s" % (given["mode"], MODES))
+    return {k: given[k] for k in _LOOP_ARGS if k in given}
+
+
+def _capture(body, scratch, real, k, dev):
+    """body(*scratch) 3 times on a side stream (the warm-up, on scratch state), a synchronise, then body(*real) k times
+    captured into one graph -> its replay.  The capture runs nothing: the real state is still the start's."""
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            body(*scratch)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g_ = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g_):
+        for _ in range(k):
+            body(*real)
+    return g_.replay
+
+
+def _run_stages(stage_list, set_stage, one, replay=None, G=1, check_every=0, any_active=None):
+    """The stages one after the other -> iterations run.  set_stage(i) at every stage boundary, outside any captured graph
+    (it rewrites the device tensors a graph reads: column scales and weights); then the stage's iterations, replay() - G of
+    them - while at least G are left, else one().  check_every = k > 0: any_active() is read whenever the count passes a
+    multiple of k, and the loop ends when it says no."""
+    done, stopped = 0, False
+    for si, (n, _) in enumerate(stage_list):
+        set_stage(si)
+        left = n
+        while left > 0 and not stopped:
+            if replay is not None and left >= G:
+                replay()
+                k = G
+            else:
+                one()
+                k = 1
+            left -= k
+            if check_every > 0 and (done + k) // check_every > done // check_every:
+                stopped = not any_active()
+            done += k
+        if stopped:
+            break
+    return done
+
+
+class _SideTerm:
+    """A weighted side term w mean_n(e[b, :]) of a fitter, built by its constructor: `name` of its weight argument (the word
+    in its messages too), its column count n, energy(x, verts, joints, data) -> e (B, n) differentiable, on what the forward
+    produced, and check(data, B, dev) -> the term's own data on the device (None: the term has none).  `begin` makes the
+    copy one fit works with: w (1,) and cot (B, n) device tensors - the weight in the loss and the cotangent w / n of e, so a
+    captured graph follows both - one weight per stage, and the data."""
+
+    def __init__(self, name, n, energy, check=None):
+        self.name, self.n, self.energy, self.check = name, int(n), energy, check
+
+    def begin(self, stages, B, dev, data=None):
+        """-> the term for one fit over B rows on dev, at its first stage's weight; stages: `_stage_weights`' list."""
+        t = _SideTerm(self.name, self.n, self.energy)
+        t.stages, t.data = stages, self.check(data, B, dev) if self.check is not None else None
+        t.w = torch.zeros(1, dtype=torch.float32, device=dev)
+        t.cot = torch.zeros((B, self.n), dtype=torch.float32, device=dev)
+        t.set(0)
+        return t
+
+    def set(self, stage):
+        """The weight of a stage into the device scalar and the cotangent (outside any captured graph)."""
+        self.w.fill_(self.stages[stage])
+        self.cot.fill_(self.stages[stage] / self.n)
+
+    def join(self, e, loss):
+        """-> loss.detach() + w mean_n(e) on every column: three stock launches (mean, product, sum)."""
+        return loss.detach() + (self.w * e.detach().mean(1))[:, None]
+
+
 class _Fitter:
-    """What `ParamFitter`, `ScanFitter` and `KeypointFitter` share; a fitter adds its data term (`_iteration`) and sets num_cam and P."""
+    """What `ParamFitter`, `ScanFitter` and `KeypointFitter` share: the iteration, `losses`, the loop.  A fitter adds its data
+    term - `_forward(x, data)` and `_cotangents(B, dev, data)` - and sets num_cam and P."""
     pen_topo = None            # a render.MeshTopology when the fitter was built with `penetration`
     pen_collide = None         # its part-pair table (None: `penetration.part_collision_table(topo, 1)`)
+    kp_spec = None             # a keypoints.KeypointSpec when the fitter was built with `keypoints`
+    kp_sigma = None            # the robust function's sigma in pixels (None: rho(s) = s)
+    _pen = _kp = None          # their `_SideTerm`s; a fitter's side terms come in this order: penetration, then keypoints
+
+    def _layer_init(self, smpl_path, four_columns):
+        """A fitter over an `SMPLLayer` (given, or built from a path or a model): layer, num_cam - which must be 4, else a
+        ValueError of `four_columns` - and P."""
+        from .keras_smpl.batch_smpl import SMPLLayer
+        self.layer = smpl_path if isinstance(smpl_path, SMPLLayer) else SMPLLayer(smpl_path)
+        self.num_cam = self.layer.num_cam
+        if self.num_cam != 4:
+            raise ValueError(four_columns)
+        self.P = self.num_cam + 82
 
     def _pen_init(self, penetration, model, collide=None):
         """`penetration` of a fitter's constructor: None / False (no term), True (the faces of `model`) or a MeshTopology."""
         if penetration is None or penetration is False:
             return
-        from .penetration import check_collide
+        from .penetration import check_collide, self_penetration
         from .render import MeshTopology
         if penetration is True:
             if getattr(model, "faces", None) is None:
@@ -677,37 +776,13 @@ class _Fitter:
         if penetration.num_verts != model.num_verts:
             raise ValueError("the topology has %d vertices, the model %d" % (penetration.num_verts, model.num_verts))
         self.pen_topo, self.pen_collide = penetration, check_collide(collide, penetration)
-
-    def _pen_state(self, pen_weight, stage_list, B, dev):
-        """None without the term; else dict(w (1,) and cot (B, V) device tensors, stages = one weight per stage, V)."""
-        if self.pen_topo is None:
-            if pen_weight is not None:
-                raise ValueError("pen_weight goes with a fitter built with penetration=...")
-            return None
-        V = self.pen_topo.num_verts
-        return dict(w=torch.zeros(1, dtype=torch.float32, device=dev), cot=torch.zeros((B, V), dtype=torch.float32, device=dev),
-                    stages=_stage_pen_weights(pen_weight, stage_list), V=V)
-
-    @staticmethod
-    def _pen_set(pen, w):
-        """The weight of a stage into the device scalar and the cotangent (outside any captured graph)."""
-        pen["w"].fill_(w)
-        pen["cot"].fill_(w / pen["V"])
-
-    def _pen_term(self, verts, loss, pen):
-        """-> (e (B, V) of `self_penetration(verts)`, differentiable; loss.detach() + w mean_V(e) on every column): three stock
-        launches (mean, product, sum) beside the term's own kernels."""
-        from .penetration import self_penetration
-        e = self_penetration(verts, self.pen_topo, self.pen_collide)
-        return e, loss.detach() + (pen["w"] * e.detach().mean(1))[:, None]
-
-    # ---- the 2D keypoint term (keypoints.py), beside the self-penetration helpers and in their mould ----------------------
-    kp_spec = None             # a keypoints.KeypointSpec when the fitter was built with `keypoints`
-    kp_sigma = None            # the robust function's sigma in pixels (None: rho(s) = s)
+        self._pen = _SideTerm("pen_weight", penetration.num_verts,
+                              lambda x, verts, joints, data: self_penetration(verts, self.pen_topo, self.pen_collide))
 
     def _kp_init(self, keypoints, model, sigma=None):
-        """`keypoints` of a fitter's constructor: None (no term) or a KeypointSpec over the model's vertices."""
-        from .keypoints import KeypointSpec, check_sigma
+        """`keypoints` of a fitter's constructor: None (no term) or a KeypointSpec over the model's vertices.  The term is
+        `keypoint_energy` of the iteration's vertices (and posed joints) under cam = x[:, :4]."""
+        from .keypoints import KeypointSpec, check_sigma, keypoint_energy
         check_sigma(sigma)
         if keypoints is None:
             if sigma is not None:
@@ -721,10 +796,13 @@ class _Fitter:
             raise ValueError("the keypoint term projects with four camera columns")
         self.kp_spec, self.kp_sigma = keypoints, sigma
 
+        def energy(x, verts, joints, data):
+            return keypoint_energy(verts, x[:, :4], self.kp_spec, data[0], data[1], self.kp_sigma,
+                                   joints if self.kp_spec.with_joints else None)
+        self._kp = _SideTerm("kp_weight", keypoints.K, energy, self._kp_data)
+
     def _kp_data(self, keypoints, B, dev):
-        """`fit`'s / `losses`' keypoints=(target (B, K, 2), conf (B, K)) -> both as fp32 device tensors; None without."""
-        if keypoints is None:
-            return None
+        """`fit`'s / `losses`' keypoints=(target (B, K, 2), conf (B, K)) -> both as fp32 device tensors."""
         if not isinstance(keypoints, (tuple, list)) or len(keypoints) != 2:
             raise ValueError("keypoints must be (target (B, K, 2), conf (B, K))")
         K = self.kp_spec.K
@@ -735,38 +813,17 @@ class _Fitter:
         return (target.detach().to(device=dev, dtype=torch.float32).contiguous(),
                 conf.detach().to(device=dev, dtype=torch.float32).contiguous())
 
-    def _kp_check(self, keypoints, kp_weight):
-        """The pairing rules, before anything touches a device: data and weight only with a spec, a spec only with data."""
-        if self.kp_spec is None:
+    def _check_sides(self, pen_weight=None, keypoints=None, kp_weight=None):
+        """The pairing rules, before anything touches a device: a weight only with its term, keypoint data only with a spec
+        and a spec only with data -> [(term, its weight argument, its data)] of the terms the fitter has, in their order."""
+        if self._pen is None and pen_weight is not None:
+            raise ValueError("pen_weight goes with a fitter built with penetration=...")
+        if self._kp is None:
             if keypoints is not None or kp_weight is not None:
                 raise ValueError("keypoints and kp_weight go with a fitter built with keypoints=...")
         elif keypoints is None:
             raise ValueError("this fitter was built with keypoints=...: pass keypoints=(target, conf)")
-
-    def _kp_state(self, kp_weight, stage_list, B, dev, keypoints=None):
-        """None without the term; else dict(w (1,) and cot (B, K) device tensors, stages = one weight per stage, K, target,
-        conf)."""
-        self._kp_check(keypoints, kp_weight)
-        if self.kp_spec is None:
-            return None
-        K = self.kp_spec.K
-        target, conf = self._kp_data(keypoints, B, dev)
-        return dict(w=torch.zeros(1, dtype=torch.float32, device=dev), cot=torch.zeros((B, K), dtype=torch.float32, device=dev),
-                    stages=_stage_pen_weights(kp_weight, stage_list, "kp_weight"), K=K, target=target, conf=conf)
-
-    @staticmethod
-    def _kp_set(kp, w):
-        """The weight of a stage into the device scalar and the cotangent (outside any captured graph)."""
-        kp["w"].fill_(w)
-        kp["cot"].fill_(w / kp["K"])
-
-    def _kp_term(self, verts, cam, jtr, loss, kp):
-        """-> (e (B, K) of `keypoint_energy`, differentiable in verts, cam and jtr; loss.detach() + w mean_K(e) on every
-        column): three stock launches (mean, product, sum) beside the term's own kernels."""
-        from .keypoints import keypoint_energy
-        e = keypoint_energy(verts, cam, self.kp_spec, kp["target"], kp["conf"], self.kp_sigma,
-                            jtr if self.kp_spec.with_joints else None)
-        return e, loss.detach() + (kp["w"] * e.detach().mean(1))[:, None]
+        return [(t, w, d) for t, w, d in ((self._pen, pen_weight, None), (self._kp, kp_weight, keypoints)) if t is not None]
 
     def _initial(self, B, init, device, default):
         """`initial`: a (B, P) tensor as it is, anything else from default(); then the move to the device."""
@@ -789,53 +846,66 @@ class _Fitter:
         return dict(prior=prior.to(dev), prior_weights=check_prior_weights((1.0, 1.0, 1.0) if weights is None else weights).to(dev),
                     num_cam=self.num_cam)
 
-    def _losses(self, x, loss, silh_loss, silh_weight, prior, prior_weights, verts=None, pen_weight=None, kp=None):
-        """The tail of `losses`: per-term losses of x -> (B,) by the kernel of the loop, a call with a zero gradient on a
-        scratch state that records one row of history.  A fitter with `penetration` passes its vertices: the term joins
-        `loss` as in `fit`, with pen_weight (None: 1).  kp = (cam, J_transformed, keypoints, kp_weight) of a fitter built
-        with `keypoints`: that term joins likewise."""
-        if self.pen_topo is not None:
-            pen = self._pen_state(pen_weight, [None], int(x.shape[0]), x.device)
-            self._pen_set(pen, pen["stages"][0])
-            loss = self._pen_term(verts, loss, pen)[1].contiguous()
-        elif pen_weight is not None:
-            raise ValueError("pen_weight goes with a fitter built with penetration=...")
-        if kp is not None:
-            st = self._kp_state(kp[3], [None], int(x.shape[0]), x.device, kp[2])
-            self._kp_set(st, st["stages"][0])
-            loss = self._kp_term(verts, kp[0], kp[1], loss, st)[1].contiguous()
-        hist = torch.empty((1, int(x.shape[0])), dtype=torch.float32, device=x.device)
-        fit_step(FitState.new(x), torch.zeros_like(x), loss, silh_loss, silh_weight, None, hist,
-                 **self._prior_kw(prior, prior_weights, x.device))
-        return hist[0]
+    def _compose(self, x, data, sides):
+        """The forward of one iteration, and of `losses`: the fitter's `_forward(x, data)` -> (its data terms, the second
+        term's weight, verts, posed joints or None), then the side terms on those.  -> (terms, loss, silh_loss, silh_weight):
+        every term in the order `autograd.grad` takes them, and what `fit_step` gets.  The bits depend on these rules:
+          - terms: the data terms first - [seg_loss, silh_loss?] of `ParamFitter`, [p2m, m2p] or the one direction present of
+            `ScanFitter` (p2m scaled by N / counts inside `terms()`), [e] of `KeypointFitter` - then penetration, then
+            keypoints: autograd accumulates into x in that order.
+          - loss: the first data term detached, then + w_pen mean_V, then + w_kp mean_K, each onto every column; silh_loss:
+            the second data term where there is one (with `ScanFitter` the m2p terms, silh_weight = m2p_weight, only when both
+            directions are on; with one direction the weight is 1.0).  Both contiguous."""
+        terms, silh_weight, verts, joints = self._forward(x, data)
+        loss = terms[0].detach()
+        silh_loss = terms[1].detach().contiguous() if len(terms) == 2 else None
+        for s in sides:
+            e = s.energy(x, verts, joints, s.data)
+            terms, loss = terms + [e], s.join(e, loss)
+        return terms, loss.contiguous(), silh_loss, silh_weight
 
-    def _fit(self, B, dev, start, data, *, steps, lr, mode, stages, patience, grad_scale, graph, check_every, history, beta1, beta2,
-             eps, graph_steps, prior, prior_weights, group_size, tie, smooth, pen_weight=None, kp_weight=None, keypoints=None):
-        """The rest of `fit` behind a fitter's own look at its inputs (`fit`'s arguments by name; B rows on device dev): the
-        checks of groups, stages and prior weights, the start from start() (tied columns set to their group's mean), the
-        state, the stages with their column scales and prior weights, graph capture and replay, the stop on `check_every`.
-        data() -> make_one, called between the groups' checks and the stages': whatever the fitter checks of its data there;
-        make_one(cs, kw, pen) -> one(state, hist): one iteration (forward, backward, `fit_step`) of its data term; pen is
-        `_pen_state`'s dict (None without the term), its tensors rewritten here at each stage boundary.  A fitter built with
-        `keypoints` gets make_one(cs, kw, pen, kp) with `_kp_state`'s dict, kept the same way."""
+    def _iteration(self, state, data, sides, cots, cs, hist, kw):
+        """One iteration on `state`: `_compose` on x, ONE `torch.autograd.grad` over all terms with their constant
+        cotangents cots (the data terms', then each side term's `cot`, in `_compose`'s order), one `fit_step`."""
+        x = state.x.detach().requires_grad_(True)                 # (shares x's memory: the kernel updates it in place)
+        terms, loss, silh_loss, silh_weight = self._compose(x, data, sides)
+        (g,) = torch.autograd.grad(terms, [x], grad_outputs=cots)
+        fit_step(state, g.contiguous(), loss, silh_loss, silh_weight, cs, hist, **kw)
+
+    def _losses(self, x, data, prior, prior_weights, sides):
+        """`losses` behind a fitter's own look at its inputs: `_compose` - the forward `fit` iterates - without a gradient,
+        reduced to (B,) by the kernel of the loop: a call with a zero gradient on a scratch state that records one row of
+        history.  sides: `_check_sides`' list; each term joins at its weight (None: 1)."""
+        x = _lib.require_cuda(x.detach(), "x")
+        with torch.no_grad(), torch.cuda.device(x.device):
+            B = int(x.shape[0])
+            sides = [t.begin(_stage_weights(w, [None], t.name), B, x.device, d) for t, w, d in sides]
+            _, loss, silh_loss, silh_weight = self._compose(x, data, sides)
+            hist = torch.empty((1, B), dtype=torch.float32, device=x.device)
+            fit_step(FitState.new(x), torch.zeros_like(x), loss, silh_loss, silh_weight, None, hist,
+                     **self._prior_kw(prior, prior_weights, x.device))
+            return hist[0]
+
+    def _fit(self, B, dev, start, check_data, sides, *, steps, lr, mode, stages, patience, grad_scale, graph, check_every, history,
+             beta1, beta2, eps, graph_steps, prior, prior_weights, group_size, tie, smooth):
+        """The rest of `fit` behind a fitter's own look at its inputs (the `_LOOP_ARGS` by name; B rows on device dev): the
+        checks of groups, stages and weights, the start from start() (tied columns set to their group's mean), the state,
+        the stages with their column scales, prior weights and side-term weights, graph capture and replay, the stop on
+        `check_every`.  check_data() -> the fitter's checked data, called between the groups' checks and the stages':
+        whatever the fitter checks of its data there; sides: `_check_sides`' list."""
         P = self.P
         grp = check_group(B, group_size)
         grouped = grp != 1 or smooth is not None
         tie_m = check_tie(tie, P, self.num_cam) if grouped else None
         smooth_w = check_smooth(smooth, P) if smooth is not None else None
-        make_one = data()
+        data = check_data()
         stage_list = check_stages(stages, P, steps)
         stage_w = _stage_prior_weights(prior, prior_weights, stage_list)
-        if self.pen_topo is None and pen_weight is not None:
-            raise ValueError("pen_weight goes with a fitter built with penetration=...")
-        self._kp_check(keypoints, kp_weight)
-        if self.kp_spec is not None:
-            _stage_pen_weights(kp_weight, stage_list, "kp_weight")
+        sides = [(t, _stage_weights(w, stage_list, t.name), d) for t, w, d in sides]
         kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
                   mode=mode, patience=int(patience))
         total = sum(n for n, _ in stage_list)
         G = max(1, int(graph_steps))
-        check_every = int(check_every)
         with torch.cuda.device(dev):
             x0 = start()
             if grouped:
@@ -852,52 +922,23 @@ class _Fitter:
             if prior is not None:
                 kw.update(self._prior_kw(prior, stage_w[0], dev))     # (the (3,) tensor is rewritten at each stage boundary)
                 stage_w = [w.to(dev) for w in stage_w]
-            pen = self._pen_state(pen_weight, stage_list, B, dev)
-            if pen is not None:
-                self._pen_set(pen, pen["stages"][0])
-            kp = self._kp_state(kp_weight, stage_list, B, dev, keypoints)
-            if kp is not None:
-                self._kp_set(kp, kp["stages"][0])
-            one = make_one(cs, kw, pen) if kp is None else make_one(cs, kw, pen, kp)
-            replay = None
-            if graph and B > 0 and any(n >= G for n, _ in stage_list):
-                # warm-up on a side stream and on a scratch state, then G iterations of the real state in one graph
-                scratch = state.clone()
-                side = torch.cuda.Stream(device=dev)
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(3):
-                        one(scratch, None)
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                g_ = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_):
-                    for _ in range(G):
-                        one(state, hist)
-                replay = g_.replay
-            done, stopped = 0, False
-            for si, ((n, _), sc) in enumerate(zip(stage_list, scales)):
-                cs.copy_(sc)
+            sides = [t.begin(ws, B, dev, d) for t, ws, d in sides]
+            cots = self._cotangents(B, dev, data) + [s.cot for s in sides]
+
+            def one(st, h):
+                self._iteration(st, data, sides, cots, cs, h, kw)
+
+            def set_stage(si):
+                cs.copy_(scales[si])
                 if prior is not None:
                     kw["prior_weights"].copy_(stage_w[si])
-                if pen is not None:
-                    self._pen_set(pen, pen["stages"][si])
-                if kp is not None:
-                    self._kp_set(kp, kp["stages"][si])
-                left = n
-                while left > 0 and not stopped:
-                    if replay is not None and left >= G:
-                        replay()
-                        k = G
-                    else:
-                        one(state, hist)
-                        k = 1
-                    left -= k
-                    if check_every > 0 and B > 0 and (done + k) // check_every > done // check_every:
-                        stopped = not bool(state.active.any())
-                    done += k
-                if stopped:
-                    break
+                for s in sides:
+                    s.set(si)
+            replay = None
+            if graph and B > 0 and any(n >= G for n, _ in stage_list):
+                replay = _capture(one, (state.clone(), None), (state, hist), G, dev)
+            done = _run_stages(stage_list, set_stage, lambda: one(state, hist), replay, G, int(check_every) if B > 0 else 0,
+                               lambda: bool(state.active.any()))
             torch.cuda.synchronize()
         return FitResult(x=state.best_x, loss=state.best_loss, step=state.best_step, final_x=state.x, nonfinite=state.bad,
                          active=state.active.bool(), history=hist[:done] if hist is not None else None, steps=done,
@@ -957,7 +998,24 @@ class ParamFitter(_Fitter):
             raise ValueError("%s must be an integer map of %d x %d x %d entries" % (name, B, W, W))
         return _lib.require_cuda(labels.to(torch.int32).reshape(B, W, W), name, torch.int32)
 
+    def _data(self, labels, silh_labels, B):
+        """-> (labels (B, W, W), silh_labels (B, Ws, Ws) or None) int32 on the device; silh_labels go with the silhouette."""
+        labels = self._labels(labels, B, self.img_wh, "labels")
+        if (silh_labels is not None) != self.with_silhouette:
+            raise ValueError("silh_labels go with ParamFitter(with_silhouette=True), and only with it")
+        return labels, self._labels(silh_labels, B, self.silh_wh, "silh_labels") if silh_labels is not None else None
+
     # ---- one iteration ------------------------------------------------------------------------------------------------
+    def _forward(self, x, data):
+        out = self.decoder(x, data[0], silh_labels=data[1])
+        terms = [out["seg_loss"]] if data[1] is None else [out["seg_loss"], out["silh_loss"]]
+        return terms, self.silh_weight, out.get("verts"), out.get("J_transformed")
+
+    def _cotangents(self, B, dev, data):
+        N, Ns = self.img_wh * self.img_wh, self.silh_wh * self.silh_wh
+        gout = torch.full((B, N), 1.0 / N, dtype=torch.float32, device=dev)
+        return [gout] if data[1] is None else [gout, torch.full((B, Ns), self.silh_weight / Ns, dtype=torch.float32, device=dev)]
+
     def losses(self, x, labels, silh_labels=None, prior=None, prior_weights=None, pen_weight=None, keypoints=None,
                kp_weight=None):
         """Per-row loss (B,) fp32 of parameters x (B, P) against the labels: one gradient-free decoder forward reduced by
@@ -965,38 +1023,8 @@ class ParamFitter(_Fitter):
         for x in its history.  With a prior its weighted energy E is part of the loss, as in `fit`; so is the
         self-penetration term of a fitter built with `penetration` (pen_weight None: 1) and the keypoint term of one built
         with `keypoints` (keypoints = (target, conf), kp_weight None: 1)."""
-        B = int(x.shape[0])
-        self._kp_check(keypoints, kp_weight)
-        labels = self._labels(labels, B, self.img_wh, "labels")
-        if (silh_labels is not None) != self.with_silhouette:
-            raise ValueError("silh_labels go with ParamFitter(with_silhouette=True), and only with it")
-        if silh_labels is not None:
-            silh_labels = self._labels(silh_labels, B, self.silh_wh, "silh_labels")
-        x = _lib.require_cuda(x.detach(), "x")
-        with torch.no_grad(), torch.cuda.device(x.device):
-            out = self.decoder(x, labels, silh_labels=silh_labels)
-            kp = None if self.kp_spec is None else (x[:, :4], out["J_transformed"], keypoints, kp_weight)
-            return self._losses(x, out["seg_loss"], out["silh_loss"] if silh_labels is not None else None, self.silh_weight, prior,
-                                prior_weights, out.get("verts"), pen_weight, kp)
-
-    def _iteration(self, state, labels, silh_labels, gout, sgout, cs, hist, kw, pen=None, kp=None):
-        x = state.x.detach().requires_grad_(True)                 # (shares x's memory: the kernel updates it in place)
-        out = self.decoder(x, labels, silh_labels=silh_labels)
-        seg_loss = out["seg_loss"]
-        terms, cots, sl = [seg_loss], [gout], None
-        if silh_labels is not None:
-            sl = out["silh_loss"]
-            terms, cots = terms + [sl], cots + [sgout]
-            sl = sl.detach()
-        loss = seg_loss.detach()
-        if pen is not None:
-            e, loss = self._pen_term(out["verts"], seg_loss, pen)
-            terms, cots = terms + [e], cots + [pen["cot"]]
-        if kp is not None:
-            ek, loss = self._kp_term(out["verts"], x[:, :4], out["J_transformed"], loss, kp)
-            terms, cots = terms + [ek], cots + [kp["cot"]]
-        (g,) = torch.autograd.grad(terms, [x], grad_outputs=cots)
-        fit_step(state, g.contiguous(), loss, sl, self.silh_weight, cs, hist, **kw)
+        sides = self._check_sides(pen_weight, keypoints, kp_weight)
+        return self._losses(x, self._data(labels, silh_labels, int(x.shape[0])), prior, prior_weights, sides)
 
     # ---- the loop -----------------------------------------------------------------------------------------------------
     def fit(self, labels, init=None, steps=1601, lr=1e-3, mode="keras", stages=None, silh_labels=None, patience=0,
@@ -1028,30 +1056,13 @@ class ParamFitter(_Fitter):
         keypoints = (target (B, K, 2), conf (B, K)) and kp_weight (a fitter built with `keypoints` only; kp_weight None: 1):
         detected 2D joints in the decoder's pixel frame; the term kp_weight mean_K(e), e = `keypoints.keypoint_energy`, joins
         every column of the loss and the one `torch.autograd.grad` call, as the self-penetration term does."""
-        if mode not in MODES:
-            raise ValueError("mode %r is none of %s" % (mode, MODES))
-        self._kp_check(keypoints, kp_weight)
+        loop = _fit_args(locals())
+        sides = self._check_sides(pen_weight, keypoints, kp_weight)
         if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
             raise ValueError("labels must be a (B, W, W) integer tensor")
-        B, W, dev = int(labels.shape[0]), self.img_wh, labels.device
-
-        def data():
-            lab = self._labels(labels, B, W, "labels")
-            if (silh_labels is not None) != self.with_silhouette:
-                raise ValueError("silh_labels go with ParamFitter(with_silhouette=True), and only with it")
-            slab = self._labels(silh_labels, B, self.silh_wh, "silh_labels") if silh_labels is not None else None
-
-            def make_one(cs, kw, pen, kp=None):
-                N, Ns = W * W, self.silh_wh * self.silh_wh
-                gout = torch.full((B, N), 1.0 / N, dtype=torch.float32, device=dev)
-                sgout = torch.full((B, Ns), self.silh_weight / Ns, dtype=torch.float32, device=dev) if self.with_silhouette else None
-                return lambda st, h: self._iteration(st, lab, slab, gout, sgout, cs, h, kw, pen, kp)
-            return make_one
-        return self._fit(B, dev, lambda: self.initial(B, init, generator, dev), data, steps=steps, lr=lr, mode=mode, stages=stages,
-                         patience=patience, grad_scale=grad_scale, graph=graph, check_every=check_every, history=history,
-                         beta1=beta1, beta2=beta2, eps=eps, graph_steps=graph_steps, prior=prior, prior_weights=prior_weights,
-                         group_size=group_size, tie=tie, smooth=smooth, pen_weight=pen_weight, kp_weight=kp_weight,
-                         keypoints=keypoints)
+        B, dev = int(labels.shape[0]), labels.device
+        return self._fit(B, dev, lambda: self.initial(B, init, generator, dev), lambda: self._data(labels, silh_labels, B), sides,
+                         **loop)
 
 
 def robust_rho(d2, sigma):
@@ -1081,13 +1092,8 @@ class ScanFitter(_Fitter):
 
     def __init__(self, smpl_path=None, topo=None, m2p_weight=1.0, sigma=None, directions=("p2m", "m2p"), penetration=None,
                  collide=None):
-        from .keras_smpl.batch_smpl import SMPLLayer
         from .render import MeshTopology
-        self.layer = smpl_path if isinstance(smpl_path, SMPLLayer) else SMPLLayer(smpl_path)
-        self.num_cam = self.layer.num_cam
-        if self.num_cam != 4:
-            raise ValueError("ScanFitter keeps (s, t_x, t_y, t_z) in four leading columns")
-        self.P = self.num_cam + 82
+        self._layer_init(smpl_path, "ScanFitter keeps (s, t_x, t_y, t_z) in four leading columns")
         if topo is None:
             faces = self.layer._model.faces
             if faces is None:
@@ -1142,28 +1148,19 @@ class ScanFitter(_Fitter):
             m2p = rho(out["vd2"])
         return p2m, m2p, out
 
-    def _cotangents(self, B, N, dev):
-        V = self.topo.num_verts
+    def _forward(self, x, data):
+        verts = self.place(x)
+        p2m, m2p, _ = self.terms(x, data[0], data[1], verts)
+        terms = [t for t in (p2m, m2p) if t is not None]
+        return terms, self.m2p_weight if len(terms) == 2 else 1.0, verts, None
+
+    def _cotangents(self, B, dev, data):
+        N, V = int(data[0].shape[1]), self.topo.num_verts
         gout = torch.full((B, N), 1.0 / N, dtype=torch.float32, device=dev) if "p2m" in self.directions else None
         sgout = torch.full((B, V), 1.0 / V, dtype=torch.float32, device=dev) if "m2p" in self.directions else None
         if gout is not None and sgout is not None:
             sgout = sgout * self.m2p_weight
-        return gout, sgout
-
-    def _iteration(self, state, points, counts, gout, sgout, cs, hist, kw, pen=None):
-        x = state.x.detach().requires_grad_(True)                 # (shares x's memory: the kernel updates it in place)
-        verts = self.place(x)
-        p2m, m2p, _ = self.terms(x, points, counts, verts)
-        both = p2m is not None and m2p is not None
-        first, second = (p2m, m2p) if both else ((p2m, None) if p2m is not None else (m2p, None))
-        terms, cots = ([p2m, m2p], [gout, sgout]) if both else ([first], [gout if p2m is not None else sgout])
-        loss = first.detach()
-        if pen is not None:
-            e, loss = self._pen_term(verts, first, pen)
-            terms, cots = terms + [e], cots + [pen["cot"]]
-        (g,) = torch.autograd.grad(terms, [x], grad_outputs=cots)
-        fit_step(state, g.contiguous(), loss.contiguous(), second.detach().contiguous() if both else None,
-                 self.m2p_weight if both else 1.0, cs, hist, **kw)
+        return [c for c in (gout, sgout) if c is not None]
 
     def _points(self, points, counts):
         if not isinstance(points, torch.Tensor) or points.dim() != 3 or points.shape[2] != 3 or points.shape[1] < 1:
@@ -1183,14 +1180,7 @@ class ScanFitter(_Fitter):
         """Per-row loss (B,) of parameters x against the scans, reduced by the kernel of the loop (a call with a zero
         gradient on a scratch state): the bits `fit` would record for x in its history (the self-penetration term of a
         fitter built with `penetration` included, pen_weight None: 1)."""
-        points, counts = self._points(points, counts)
-        x = _lib.require_cuda(x.detach(), "x")
-        with torch.no_grad(), torch.cuda.device(x.device):
-            verts = self.place(x)
-            p2m, m2p, _ = self.terms(x, points, counts, verts)
-            first, second = (p2m, m2p) if p2m is not None else (m2p, None)
-            return self._losses(x, first.contiguous(), None if second is None else second.contiguous(), self.m2p_weight, prior,
-                                prior_weights, verts, pen_weight)
+        return self._losses(x, self._points(points, counts), prior, prior_weights, self._check_sides(pen_weight))
 
     def fit(self, points, counts=None, init=None, steps=200, lr=1e-2, mode="torch", stages=None, patience=0, grad_scale=1.0,
             graph=False, check_every=0, history=False, beta1=0.9, beta2=0.999, eps=KERAS_EPS, graph_steps=4, prior=None,
@@ -1200,19 +1190,10 @@ class ScanFitter(_Fitter):
         grad_scale, graph / graph_steps, check_every, history, prior and prior_weights (one triple or one per stage),
         group_size / tie / smooth for several scans of one body (tie="cam" would tie the placement as well), pen_weight with
         a fitter built with `penetration`."""
-        if mode not in MODES:
-            raise ValueError("mode %r is none of %s" % (mode, MODES))
-        points, counts = self._points(points, counts)
-        B, N = int(points.shape[0]), int(points.shape[1])
-        dev = points.device
-
-        def make_one(cs, kw, pen):
-            gout, sgout = self._cotangents(B, N, dev)
-            return lambda st, h: self._iteration(st, points, counts, gout, sgout, cs, h, kw, pen)
-        return self._fit(B, dev, lambda: self.initial(B, init, dev), lambda: make_one, steps=steps, lr=lr, mode=mode, stages=stages,
-                         patience=patience, grad_scale=grad_scale, graph=graph, check_every=check_every, history=history,
-                         beta1=beta1, beta2=beta2, eps=eps, graph_steps=graph_steps, prior=prior, prior_weights=prior_weights,
-                         group_size=group_size, tie=tie, smooth=smooth, pen_weight=pen_weight)
+        loop = _fit_args(locals())
+        data = self._points(points, counts)
+        B, dev = int(data[0].shape[0]), data[0].device
+        return self._fit(B, dev, lambda: self.initial(B, init, dev), lambda: data, self._check_sides(pen_weight), **loop)
 
 
 class KeypointFitter(_Fitter):
@@ -1228,13 +1209,8 @@ class KeypointFitter(_Fitter):
     """
 
     def __init__(self, smpl_path=None, spec=None, sigma=None, img_wh=48, penetration=None, collide=None):
-        from .keras_smpl.batch_smpl import SMPLLayer
         from .keypoints import KeypointSpec, check_sigma
-        self.layer = smpl_path if isinstance(smpl_path, SMPLLayer) else SMPLLayer(smpl_path)
-        self.num_cam = self.layer.num_cam
-        if self.num_cam != 4:
-            raise ValueError("KeypointFitter projects with four camera columns")
-        self.P = self.num_cam + 82
+        self._layer_init(smpl_path, "KeypointFitter projects with four camera columns")
         self.img_wh = int(img_wh)
         if spec is None:
             spec = KeypointSpec.from_model(self.layer)
@@ -1264,6 +1240,13 @@ class KeypointFitter(_Fitter):
         e, det = keypoint_energy(verts, x[:, :4], self.spec, target, conf, self.sigma, jtr, return_details=True)
         return e, det, verts
 
+    def _forward(self, x, data):
+        e, _, verts = self.terms(x, *data)
+        return [e], 1.0, verts, None
+
+    def _cotangents(self, B, dev, data):
+        return [torch.full((B, self.spec.K), 1.0 / self.spec.K, dtype=torch.float32, device=dev)]
+
     def _data(self, target, conf):
         K = self.spec.K
         if not isinstance(target, torch.Tensor) or target.dim() != 3 or tuple(target.shape[1:]) != (K, 2):
@@ -1277,24 +1260,10 @@ class KeypointFitter(_Fitter):
             raise RuntimeError("conf lives on %s, target on %s" % (conf.device, target.device))
         return target, conf
 
-    def _iteration(self, state, target, conf, gout, cs, hist, kw, pen=None):
-        x = state.x.detach().requires_grad_(True)                 # (shares x's memory: the kernel updates it in place)
-        e, _, verts = self.terms(x, target, conf)
-        terms, cots, loss = [e], [gout], e.detach()
-        if pen is not None:
-            ep, loss = self._pen_term(verts, e, pen)
-            terms, cots = terms + [ep], cots + [pen["cot"]]
-        (g,) = torch.autograd.grad(terms, [x], grad_outputs=cots)
-        fit_step(state, g.contiguous(), loss.contiguous(), None, 1.0, cs, hist, **kw)
-
     def losses(self, x, target, conf, prior=None, prior_weights=None, pen_weight=None):
         """Per-row loss (B,) of parameters x against the detections, reduced by the kernel of the loop (a call with a zero
         gradient on a scratch state): the bits `fit` would record for x in its history."""
-        target, conf = self._data(target, conf)
-        x = _lib.require_cuda(x.detach(), "x")
-        with torch.no_grad(), torch.cuda.device(x.device):
-            e, _, verts = self.terms(x, target, conf)
-            return self._losses(x, e.contiguous(), None, 1.0, prior, prior_weights, verts, pen_weight)
+        return self._losses(x, self._data(target, conf), prior, prior_weights, self._check_sides(pen_weight))
 
     def fit(self, target, conf, init=None, steps=200, lr=1e-2, mode="torch", stages=None, patience=0, grad_scale=1.0,
             graph=False, check_every=0, history=False, beta1=0.9, beta2=0.999, eps=KERAS_EPS, graph_steps=4, prior=None,
@@ -1303,18 +1272,10 @@ class KeypointFitter(_Fitter):
         stages = [(steps, column_scale), ...], patience, grad_scale, graph / graph_steps, check_every, history, prior and
         prior_weights (one triple or one per stage), group_size / tie / smooth for several views or frames of one body,
         pen_weight with a fitter built with `penetration`."""
-        if mode not in MODES:
-            raise ValueError("mode %r is none of %s" % (mode, MODES))
-        target, conf = self._data(target, conf)
-        B, K, dev = int(target.shape[0]), self.spec.K, target.device
-
-        def make_one(cs, kw, pen):
-            gout = torch.full((B, K), 1.0 / K, dtype=torch.float32, device=dev)
-            return lambda st, h: self._iteration(st, target, conf, gout, cs, h, kw, pen)
-        return self._fit(B, dev, lambda: self.initial(B, init, dev), lambda: make_one, steps=steps, lr=lr, mode=mode, stages=stages,
-                         patience=patience, grad_scale=grad_scale, graph=graph, check_every=check_every, history=history,
-                         beta1=beta1, beta2=beta2, eps=eps, graph_steps=graph_steps, prior=prior, prior_weights=prior_weights,
-                         group_size=group_size, tie=tie, smooth=smooth, pen_weight=pen_weight)
+        loop = _fit_args(locals())
+        data = self._data(target, conf)
+        B, dev = int(data[0].shape[0]), data[0].device
+        return self._fit(B, dev, lambda: self.initial(B, init, dev), lambda: data, self._check_sides(pen_weight), **loop)
 
 
 # ---- SMPL+D registration: free vertex offsets under mesh regularisers --------------------------------------------------
@@ -1428,17 +1389,21 @@ class OffsetFitter:
             L = L + pen_w * self_penetration(verts, sf.pen_topo, sf.pen_collide).mean(1)
         return L
 
-    def _iteration(self, D, m, v, t, bad, state, points, counts, wts, pen_w, hist, it, kw, xkw, fit_params):
-        x = state.x.detach().requires_grad_(True) if fit_params else state.x
+    def _iteration(self, var, data, wts, pen_w, hist, it, kw, xkw=None):
+        """One iteration on var = (D, m, v, t, bad, state) - the real state or a scratch copy - against data = (points,
+        counts).  hist (steps, B) with its row counter `it` (1,) on the device, or None; kw: `offset_step`'s; xkw: `fit_step`'s
+        with the column scales under "col_scale" when x moves too (fit_params), else None."""
+        D, m, v, t, bad, state = var
+        x = state.x.detach().requires_grad_(True) if xkw is not None else state.x
         Dg = D.detach().requires_grad_(True)                      # (shares D's memory: the kernel updates it in place)
-        L = self.row_loss(x, Dg, points, counts, wts, pen_w)
-        grads = torch.autograd.grad(L.sum(), [Dg, x] if fit_params else [Dg])
+        L = self.row_loss(x, Dg, data[0], data[1], wts, pen_w)
+        grads = torch.autograd.grad(L.sum(), [Dg, x] if xkw is not None else [Dg])
         Ld = L.detach().contiguous()
         if hist is not None:
             hist.index_copy_(0, it, Ld[None])
             it.add_(1)
-        if fit_params:
-            fit_step(state, grads[1].contiguous(), Ld[:, None].contiguous(), None, 1.0, xkw["cs"], None, **xkw["kw"])
+        if xkw is not None:
+            fit_step(state, grads[1].contiguous(), Ld[:, None].contiguous(), **xkw)
         offset_step(D, grads[0].contiguous(), m, v, t, bad, Ld, **kw)
 
     def fit(self, points, counts, x, steps=200, lr=1e-3, lap_weight=1.0, edge_weight=1.0, offset_weight=0.0, stages=None,
@@ -1449,18 +1414,17 @@ class OffsetFitter:
         scales act on x, with fit_params); lap_weight, edge_weight, offset_weight (and pen_weight with penetration=True): one
         float or a list of one per stage.  offsets: the start (None: zeros).  fit_params: x moves too, through `fit_step`
         with x_lr (None: lr).  graph: one iteration is captured once and replayed."""
-        if mode not in MODES:
-            raise ValueError("mode %r is none of %s" % (mode, MODES))
+        _fit_args(locals())                                       # (for its mode check: this loop names its own arguments)
         sf = self.scan
-        points, counts = sf._points(points, counts)
-        B, dev = int(points.shape[0]), points.device
+        data = sf._points(points, counts)
+        B, dev = int(data[0].shape[0]), data[0].device
         if not isinstance(x, torch.Tensor) or tuple(x.shape) != (B, sf.P):
             raise ValueError("x must be a (%d, %d) tensor" % (B, sf.P))
         stage_list = check_stages(stages, sf.P, steps)
         names = ("lap_weight", "edge_weight", "offset_weight")
-        per = [_stage_pen_weights(w, stage_list, n) for w, n in zip((lap_weight, edge_weight, offset_weight), names)]
+        per = [_stage_weights(w, stage_list, n) for w, n in zip((lap_weight, edge_weight, offset_weight), names)]
         if self.penetration:
-            pen_stages = _stage_pen_weights(pen_weight, stage_list)
+            pen_stages = _stage_weights(pen_weight, stage_list, "pen_weight")
         elif pen_weight is not None:
             raise ValueError("pen_weight goes with OffsetFitter(..., penetration=True)")
         total = sum(n for n, _ in stage_list)
@@ -1473,16 +1437,14 @@ class OffsetFitter:
                 if tuple(offsets.shape) != (B, self.V, 3):
                     raise ValueError("offsets must be (%d, %d, 3), got %s" % (B, self.V, tuple(offsets.shape)))
                 D = _lib.require_cuda(offsets.detach().to(dev), "offsets").clone()
-            m, v = torch.zeros_like(D), torch.zeros_like(D)
-            t = torch.zeros(B, dtype=torch.int32, device=dev)
-            bad = torch.zeros(B, dtype=torch.int32, device=dev)
-            state = FitState.new(x0)
+            zi = lambda: torch.zeros(B, dtype=torch.int32, device=dev)
+            var = (D, torch.zeros_like(D), torch.zeros_like(D), zi(), zi(), FitState.new(x0))
             wts = torch.zeros(3, dtype=torch.float32, device=dev)
             pen_w = torch.zeros(1, dtype=torch.float32, device=dev) if self.penetration else None
             hist = torch.full((total, B), float("nan"), dtype=torch.float32, device=dev) if history and total else None
             it = torch.zeros(1, dtype=torch.long, device=dev)
             cs = torch.ones(sf.P, dtype=torch.float32, device=dev)
-            xkw = dict(cs=cs, kw=dict(kw, lr=float(lr if x_lr is None else x_lr), grad_scale=1.0, patience=0))
+            xkw = dict(kw, lr=float(lr if x_lr is None else x_lr), grad_scale=1.0, patience=0, col_scale=cs) if fit_params else None
 
             def set_stage(si):
                 wts.copy_(torch.tensor([p[si] for p in per], dtype=torch.float32))
@@ -1490,34 +1452,14 @@ class OffsetFitter:
                 if pen_w is not None:
                     pen_w.fill_(pen_stages[si])
 
-            def one(D_, m_, v_, t_, bad_, st, h, i):
-                self._iteration(D_, m_, v_, t_, bad_, st, points, counts, wts, pen_w, h, i, kw, xkw, fit_params)
+            def one(var_, h, i):
+                self._iteration(var_, data, wts, pen_w, h, i, kw, xkw)
             replay = None
             if total:
                 set_stage(0)
             if graph and B > 0 and total > 0:
-                # warm-up on a side stream and on scratch copies, then one iteration of the real state in a graph
-                scratch = (D.clone(), m.clone(), v.clone(), t.clone(), bad.clone(), state.clone())
-                side = torch.cuda.Stream(device=dev)
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(3):
-                        one(*scratch, None, None)
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                g_ = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_):
-                    one(D, m, v, t, bad, state, hist, it)
-                replay = g_.replay
-                # (the capture ran nothing; the state is still the start's)
-            done = 0
-            for si, (n, _) in enumerate(stage_list):
-                set_stage(si)
-                for _ in range(n):
-                    if replay is not None:
-                        replay()
-                    else:
-                        one(D, m, v, t, bad, state, hist, it)
-                    done += 1
+                replay = _capture(one, (tuple(a.clone() for a in var), None, None), (var, hist, it), 1, dev)
+            done = _run_stages(stage_list, set_stage, lambda: one(var, hist, it), replay)
             torch.cuda.synchronize()
+        D, _, _, t, bad, state = var
         return OffsetFitResult(offsets=D, x=state.x, history=hist, bad=bad, steps=done, t=t, state=state if fit_params else None)

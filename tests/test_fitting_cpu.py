@@ -150,3 +150,63 @@ def test_fit_step_op_schema_and_meta_kernel():
         ns.fit_step(*args("meta"), mode=2)
     with pytest.raises((RuntimeError, NotImplementedError)):
         ns.fit_step(*args("cpu"))                                                # a CPU tensor: no kernel registered for it
+
+
+# ---- the public surface of the fitters: `inspect.signature` of every public callable, as literals ----------------------------
+SIGNATURES = {
+    "ParamFitter.__init__": ("(self, smpl_path=None, img_wh=48, gamma=5.0, weight_classes=False, with_silhouette=False, "
+        "silh_wh=None, silh_weight=1.0, vertex_sampling=None, deterministic=False, penetration=None, "
+        "collide=None, keypoints=None, kp_sigma=None)"),
+    "ParamFitter.initial": "(self, B, init=None, generator=None, device=None)",
+    "ParamFitter.losses": ("(self, x, labels, silh_labels=None, prior=None, prior_weights=None, pen_weight=None, keypoints=None,"
+        " kp_weight=None)"),
+    "ParamFitter.fit": ("(self, labels, init=None, steps=1601, lr=0.001, mode='keras', stages=None, silh_labels=None, "
+        "patience=0, grad_scale=1.0, graph=False, check_every=0, history=False, beta1=0.9, beta2=0.999, "
+        "eps=1e-07, graph_steps=4, generator=None, prior=None, prior_weights=None, group_size=1, "
+        "tie=('shape',), smooth=None, pen_weight=None, keypoints=None, kp_weight=None)"),
+    "ScanFitter.__init__": ("(self, smpl_path=None, topo=None, m2p_weight=1.0, sigma=None, directions=('p2m', 'm2p'), "
+        "penetration=None, collide=None)"),
+    "ScanFitter.initial": "(self, B, init=None, device=None)",
+    "ScanFitter.place": "(self, x, offsets=None)",
+    "ScanFitter.terms": "(self, x, points, counts=None, verts=None, offsets=None)",
+    "ScanFitter.losses": "(self, x, points, counts=None, prior=None, prior_weights=None, pen_weight=None)",
+    "ScanFitter.fit": ("(self, points, counts=None, init=None, steps=200, lr=0.01, mode='torch', stages=None, patience=0, "
+        "grad_scale=1.0, graph=False, check_every=0, history=False, beta1=0.9, beta2=0.999, eps=1e-07, "
+        "graph_steps=4, prior=None, prior_weights=None, group_size=1, tie=('shape',), smooth=None, "
+        "pen_weight=None)"),
+    "KeypointFitter.__init__": "(self, smpl_path=None, spec=None, sigma=None, img_wh=48, penetration=None, collide=None)",
+    "KeypointFitter.initial": "(self, B, init=None, device=None)",
+    "KeypointFitter.terms": "(self, x, target, conf)",
+    "KeypointFitter.losses": "(self, x, target, conf, prior=None, prior_weights=None, pen_weight=None)",
+    "KeypointFitter.fit": ("(self, target, conf, init=None, steps=200, lr=0.01, mode='torch', stages=None, patience=0, "
+        "grad_scale=1.0, graph=False, check_every=0, history=False, beta1=0.9, beta2=0.999, eps=1e-07, "
+        "graph_steps=4, prior=None, prior_weights=None, group_size=1, tie=('shape',), smooth=None, "
+        "pen_weight=None)"),
+    "OffsetFitter.__init__": "(self, scan_fitter, spec, penetration=None)",
+    "OffsetFitter.template": "(self, device)",
+    "OffsetFitter.row_loss": "(self, x, D, points, counts, wts, pen_w=None)",
+    "OffsetFitter.fit": ("(self, points, counts, x, steps=200, lr=0.001, lap_weight=1.0, edge_weight=1.0, offset_weight=0.0, "
+        "stages=None, fit_params=False, history=False, graph=False, offsets=None, mode='torch', beta1=0.9, "
+        "beta2=0.999, eps=1e-07, x_lr=None, pen_weight=None)"),
+    "fit_step": ("(state, grad, loss, silh_loss=None, silh_weight=1.0, col_scale=None, history=None, lr=0.001, "
+        "beta1=0.9, beta2=0.999, eps=1e-07, grad_scale=1.0, mode='keras', patience=0, prior=None, "
+        "prior_weights=None, num_cam=4, group_size=1, tie=None, smooth=None)"),
+    "offset_step": "(D, grad, m, v, t, bad, loss, lr=0.001, beta1=0.9, beta2=0.999, eps=1e-07, mode='torch')",
+}
+RESULT_FIELDS = {
+    "FitResult": ("x", "loss", "step", "final_x", "nonfinite", "active", "history", "steps", "state", "group_size"),
+    "OffsetFitResult": ("offsets", "x", "history", "bad", "steps", "t", "state"),
+}
+
+
+def test_public_signatures_are_the_recorded_ones():
+    """Names, order and defaults of what callers and tools use: a change to the fitters' host side leaves them alone."""
+    import dataclasses
+    import inspect
+    for name, want in SIGNATURES.items():
+        obj = fitting
+        for part in name.split("."):
+            obj = getattr(obj, part)
+        assert str(inspect.signature(obj)) == want, name
+    for name, want in RESULT_FIELDS.items():
+        assert tuple(f.name for f in dataclasses.fields(getattr(fitting, name))) == want, name

@@ -133,7 +133,7 @@ def main():
     state = FitState.new(x.clone())
 
     def iteration():
-        fitter._iteration(Dw, m, vv, tt, bad, state, pts, None, wts, None, None, hist_it, kw, None, False)
+        fitter._iteration((Dw, m, vv, tt, bad, state), (pts, None), wts, None, None, hist_it, kw)
 
     legs = {"reg_fwd": lambda: reg(False), "reg_fwd_bwd": lambda: reg(True), "stock_fwd_bwd": stock, "scan_fwd_bwd": scan,
             "offset_step": lambda: offset_step(Dw, g, m, vv, tt, bad, loss, **kw), "iteration": iteration}
