@@ -634,6 +634,44 @@ int smplr_kp_bwd(const float *cam, const int32_t *t_off, const int32_t *t_joint,
                  const int32_t *status, const double *ws, const float *g, int B, int V, int K, int nnz, float sigma,
                  float *dverts, float *djtr, float *dcam, void *stream);
 
+/* ---- label-map distance term: projected vertices against an integer label map, both directions, by class, with gradients
+ * (beyond the reference); INTEGRATION.md 4r ---------------------------------------------------------------------------------
+ * verts (B, V, 3) fp32, cam (B, 4) = (k_u, k_v, u0, v0), labels (B, W, W) int32: stored pixel q = r W + c sits at the point
+ * (c, W - 1 - r) of the projection frame, or at (c, r) with flip_rows = 0.  C classes, 0 the background; a label outside
+ * 0 .. C - 1 is neither a target nor a query.  vclass (V) int32; vweight (B, V) fp32 or NULL (ones): vertex i of row b is
+ * counted iff vclass[i] in 1 .. C - 1 and vweight[b, i] > 0 (a NaN does not count).
+ *   p_i = (u0 + k_u X, v0 + k_v Y) in fp64; d2 = du du + dv dv, du = p_u - q_u, dv = p_v - q_v, each operation rounded to fp64.
+ *   m2i: counted vertex i -> the pixel labelled vclass[i] of smallest d2, ties to the lower stored index: near_pix, d2_v (B, V).
+ *   i2m: pixel q labelled c in 1 .. C - 1 -> the counted vertex of class c of smallest d2, ties to the lower vertex: near_vert,
+ *        d2_p (B, W, W).  Nothing to search (not counted, background, a class absent from the other side): -1, +Inf, e = 0.
+ *   s = max(d2 - slack, 0); e_v = vweight rho(s), e_p = rho(s); rho(s) = sigma^2 s / (sigma^2 + s), or s with sigma = 0.
+ * smplr_ld_prep: per image a stable counting sort of the stored pixel indices by label -> off (B, C + 1) and pix (B, W W),
+ *   class-major, increasing within a class, -1 beyond off[C].  One launch of B workgroups, once per label batch.
+ * smplr_ld_fwd: vorder (nslots) = the vertices class-major, each class's run padded with -1 to a multiple of 256, then the
+ *   vertices without a class (every vertex once); vrun (nrun) the classed vertices class-major and increasing, voff (C + 1)
+ *   its runs.  A direction is computed when its e is not NULL (e_v, near_pix, d2_v; e_p, near_vert, d2_p); proj (B, V, 2) or
+ *   NULL.  One launch.
+ * smplr_ld_bwd: g_v (B, V), g_p (B, W, W) the cotangents of e_v, e_p (NULL: zero).  On the projection of vertex i
+ *   dP_i = g_v w rho'(s) [d2 > slack] 2 (p_i - q_near) + sum over the pixels q with near_vert = i, in stored order, of
+ *   g_p rho'(s_q) [d2_q > slack] 2 (p_i - q) in fp64; dverts (B, V, 3) = (dP_u k_u, dP_v k_v, 0), every row written; dcam
+ *   (B, 4) or NULL = (sum dP_u X, sum dP_v Y, sum dP_u, sum dP_v) through part (B, ceil(nslots / 256), 4) fp64, in tile
+ *   order.  One launch, and one small one for dcam.  No atomics: the same bits on every launch and in any batch.
+ * status: SMPLR_LD_NONFINITE when a cam column, or X or Y of a counted vertex, is NaN / Inf - the row's float outputs and
+ *   gradients are NaN and its indices -1; other rows are not affected.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 0 <= B <= 65535 (B = 0 is a no-op), 1 <= W <= 160, 2 <= C <= 32,
+ * 1 <= V <= 2^24, 0 <= nrun <= V, sigma and slack finite and >= 0.  Every index read from memory is range-checked.         */
+#define SMPLR_LD_NONFINITE 1
+int smplr_ld_prep(const int32_t *labels, int B, int W, int C, int32_t *off, int32_t *pix, void *stream);
+int smplr_ld_fwd(const float *verts, const float *cam, const int32_t *labels, const int32_t *off, const int32_t *pix,
+                 const int32_t *vclass, const int32_t *vorder, const int32_t *voff, const int32_t *vrun, const float *vweight,
+                 int B, int V, int W, int C, int nslots, int nrun, int flip_rows, float sigma, float slack, float *e_v,
+                 float *e_p, int32_t *near_pix, int32_t *near_vert, float *d2_v, float *d2_p, float *proj, int32_t *status,
+                 void *stream);
+int smplr_ld_bwd(const float *verts, const float *cam, const int32_t *off, const int32_t *pix, const int32_t *vclass,
+                 const int32_t *vorder, const float *vweight, const int32_t *near_pix, const int32_t *near_vert,
+                 const int32_t *status, const float *g_v, const float *g_p, int B, int V, int W, int C, int nslots, int flip_rows,
+                 float sigma, float slack, float *dverts, float *dcam, double *part, void *stream);
+
 /* ---- mesh regularisers of SMPL+D registration: Laplacian and relative edge length, with gradients (beyond the reference);
  * INTEGRATION.md 4q ---------------------------------------------------------------------------------------------------------
  * verts (B, V, 3) fp32.  The one-ring of the topology is a CSR: nb_off (V + 1), nb_idx (nnz) and nb_w (nnz, 3) fp32 =

@@ -10,6 +10,7 @@ csrc/measure.hip), which needs ground-truth parameters but no ground-truth verti
 correspondences at all (scan.py, csrc/scan.hip)."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from .eval3d import Eval3D
@@ -265,6 +266,33 @@ def evaluate_keypoints(proj_or_details, target, conf, thresholds=(0.05, 0.1, 0.2
     return {"mean_error": float(dist.sum()) / n if n else nan,
             "per_joint": torch.where(n_k > 0, dist.sum(0) / n_k.clamp(min=1), torch.full_like(zero, nan)),
             "pck": pck, "count": n, "per_joint_count": n_k, "rows": B - int(bad.sum()), "nonfinite": int(bad.sum())}
+
+
+@torch.no_grad()
+def evaluate_label_distance(details, targets):
+    """How far a mesh lies from its label map, from `labeldist.label_distance`'s details (stock torch, CPU tensors too) and
+    the `LabelTargets` they were computed against (B images).  Per direction that the details hold - "m2i" from d2_v over
+    the vertices that found a pixel of their class, "i2m" from d2_p over the labelled pixels that found a vertex - a dict of
+    mean_px and median_px of sqrt(d2) (NaN without an entry), within_1px = the share with sqrt(d2) <= 1, count = the
+    entries; a row whose status is NONFINITE is left out whole.  -> {"m2i": ..., "i2m": ..., "rows": rows counted,
+    "nonfinite_rows": rows left out}."""
+    status = details["status"]
+    B = int(status.shape[0])
+    if B != targets.B:
+        raise ValueError("the details have %d rows, the targets %d images" % (B, targets.B))
+    bad = status != 0
+    out = {"rows": B - int(bad.sum()), "nonfinite_rows": int(bad.sum())}
+    nan = float("nan")
+    for name, key in (("m2i", "d2_v"), ("i2m", "d2_p")):
+        d2 = details.get(key)
+        if d2 is None:
+            continue
+        d2 = d2.to(torch.float64).reshape(B, -1)
+        dist = d2[torch.isfinite(d2) & ~bad[:, None]].sqrt()
+        n = int(dist.numel())
+        out[name] = {"mean_px": float(dist.mean()) if n else nan, "median_px": float(np.median(dist.cpu().numpy())) if n else nan,
+                     "within_1px": float((dist <= 1.0).sum()) / n if n else nan, "count": n}
+    return out
 
 
 @torch.no_grad()

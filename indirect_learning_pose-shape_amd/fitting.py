@@ -95,6 +95,16 @@ csrc/fit.hip are untouched; without `penetration` a fitter runs exactly the laun
 kp_weight mean_K(e[b, :]), e = `keypoint_energy` of the iteration's vertices (and posed joints) under cam = x[:, :4], joins the
 loss and the one `torch.autograd.grad` call exactly as the self-penetration term does, through a cotangent kp_weight / K;
 targets are in the decoder's pixel frame.  Without `keypoints` a fitter runs exactly the launches it ran before.
+
+Label-map distances (labeldist.py, csrc/labeldist.hip; the one data term that pulls from far away and needs only the labels):
+
+    fitter = LabelDistanceFitter(smpl_path, label_distance=True, ld_sigma=8.0) # or "visible", or a LabelDistanceSpec; a ParamFitter
+    r = fitter.fit(labels, stages=[(100, cs), (100, cs)], ld_weight=[1.0, 0.1])
+
+ld_weight mean(e[b, :]), e = `label_distance` of the iteration's vertices under cam = x[:, :4] against the fit's own labels -
+every vertex to the nearest pixel of its part beside every labelled pixel to the nearest vertex of its part - is the third
+side term, after penetration and keypoints, through a cotangent ld_weight / (V + W W).  The labels are sorted by class once
+per fit, outside any captured graph.  `ParamFitter` itself keeps its signatures and runs exactly the launches it ran before.
 """
 from __future__ import annotations
 
@@ -749,7 +759,9 @@ class _Fitter:
     pen_collide = None         # its part-pair table (None: `penetration.part_collision_table(topo, 1)`)
     kp_spec = None             # a keypoints.KeypointSpec when the fitter was built with `keypoints`
     kp_sigma = None            # the robust function's sigma in pixels (None: rho(s) = s)
-    _pen = _kp = None          # their `_SideTerm`s; a fitter's side terms come in this order: penetration, then keypoints
+    ld_spec = None             # a labeldist.LabelDistanceSpec when the fitter was built with `label_distance`
+    _pen = _kp = _ld = None    # their `_SideTerm`s; a fitter's side terms come in this order: penetration, keypoints, then
+                               # label distance
 
     def _layer_init(self, smpl_path, four_columns):
         """A fitter over an `SMPLLayer` (given, or built from a path or a model): layer, num_cam - which must be 4, else a
@@ -813,9 +825,10 @@ class _Fitter:
         return (target.detach().to(device=dev, dtype=torch.float32).contiguous(),
                 conf.detach().to(device=dev, dtype=torch.float32).contiguous())
 
-    def _check_sides(self, pen_weight=None, keypoints=None, kp_weight=None):
+    def _check_sides(self, pen_weight=None, keypoints=None, kp_weight=None, ld_weight=None, labels=None):
         """The pairing rules, before anything touches a device: a weight only with its term, keypoint data only with a spec
-        and a spec only with data -> [(term, its weight argument, its data)] of the terms the fitter has, in their order."""
+        and a spec only with data -> [(term, its weight argument, its data)] of the terms the fitter has, in their order.
+        The label-distance term's data are the fit's own `labels`."""
         if self._pen is None and pen_weight is not None:
             raise ValueError("pen_weight goes with a fitter built with penetration=...")
         if self._kp is None:
@@ -823,7 +836,10 @@ class _Fitter:
                 raise ValueError("keypoints and kp_weight go with a fitter built with keypoints=...")
         elif keypoints is None:
             raise ValueError("this fitter was built with keypoints=...: pass keypoints=(target, conf)")
-        return [(t, w, d) for t, w, d in ((self._pen, pen_weight, None), (self._kp, kp_weight, keypoints)) if t is not None]
+        if self._ld is None and ld_weight is not None:
+            raise ValueError("ld_weight goes with a LabelDistanceFitter built with label_distance=...")
+        return [(t, w, d) for t, w, d in ((self._pen, pen_weight, None), (self._kp, kp_weight, keypoints),
+                                          (self._ld, ld_weight, labels)) if t is not None]
 
     def _initial(self, B, init, device, default):
         """`initial`: a (B, P) tensor as it is, anything else from default(); then the move to the device."""
@@ -949,6 +965,7 @@ class ParamFitter(_Fitter):
     """Owns an `SMPLDecoder(outputs=(), loss=softmax_focal_loss(gamma, weight_classes)[, silh_loss=...])` and fits its
     input to label maps.  The defaults are those of decoder_loss_debugging.py:117-118: focal loss with gamma = 5, no class
     weights; `fit`'s are Keras' Adam (lr 1e-3, eps 1e-7)."""
+    _ld_options = (None, None, 0.5, ("m2i", "i2m"))    # label_distance, ld_sigma, ld_slack, ld_directions: no third side term
 
     def __init__(self, smpl_path=None, img_wh=48, gamma=5.0, weight_classes=False, with_silhouette=False, silh_wh=None,
                  silh_weight=1.0, vertex_sampling=None, deterministic=False, penetration=None, collide=None, keypoints=None,
@@ -963,10 +980,17 @@ class ParamFitter(_Fitter):
             raise ValueError("penetration needs every vertex: vertex_sampling must be None or 1, got %r" % (vertex_sampling,))
         if keypoints is not None and vertex_sampling not in (None, 1):
             raise ValueError("keypoints need every vertex: vertex_sampling must be None or 1, got %r" % (vertex_sampling,))
+        label_distance, ld_sigma, ld_slack, ld_directions = self._ld_options     # (`LabelDistanceFitter` sets them)
+        with_ld = label_distance is not None and label_distance is not False
+        if with_ld and vertex_sampling not in (None, 1):
+            raise ValueError("label_distance needs every vertex: vertex_sampling must be None or 1, got %r" % (vertex_sampling,))
+        outputs = ("verts",) if with_pen or keypoints is not None or with_ld else ()
+        if with_ld and isinstance(label_distance, str) and label_distance == "visible":
+            outputs += ("mask",)
         # (streams=1: one chain of launches, so a captured graph has no parallel branches)
         self.decoder = SMPLDecoder(smpl_path, img_wh=self.img_wh, vertex_sampling=vertex_sampling,
                                    with_silhouette=self.with_silhouette, silh_wh=silh_wh, streams=1,
-                                   deterministic=deterministic, outputs=("verts",) if with_pen or keypoints is not None else (),
+                                   deterministic=deterministic, outputs=outputs,
                                    loss=softmax_focal_loss(gamma, weight_classes),
                                    silh_loss=softmax_focal_loss(0.0, False) if self.with_silhouette else None)
         self._pen_init(penetration, self.decoder._model, collide)
@@ -974,6 +998,47 @@ class ParamFitter(_Fitter):
         self.P = self.num_cam + 82
         self.silh_wh = self.decoder.silh_wh
         self._kp_init(keypoints, self.decoder._model, kp_sigma)
+        self._ld_init(label_distance, ld_sigma, ld_slack, ld_directions)
+
+    def _ld_init(self, label_distance, sigma, slack, directions):
+        """`label_distance` of `LabelDistanceFitter`'s constructor: None / False (no term), True (`LabelDistanceSpec.from_parts` of the decoder's
+        part table), "visible" (that, with vweight = (the decoder's mask == 1), detached) or a LabelDistanceSpec.  The term
+        is `labeldist.label_distance` of the iteration's vertices under cam = x[:, :4] against the fit's own labels: e =
+        the directions in use side by side, (B, V + W W) for both."""
+        from .labeldist import LabelDistanceSpec, LabelTargets, check_directions, check_slack, label_distance as ld_energy
+        from .keypoints import check_sigma
+        from .smpl_model import load_part_tables
+        check_sigma(sigma)
+        if label_distance is None or label_distance is False:
+            if sigma is not None:
+                raise ValueError("ld_sigma goes with a fitter built with label_distance=...")
+            return
+        V, W = self.decoder._model.num_verts, self.img_wh
+        visible = isinstance(label_distance, str) and label_distance == "visible"
+        if label_distance is True or visible:
+            label_distance = LabelDistanceSpec.from_parts(load_part_tables(1), V)
+        if not isinstance(label_distance, LabelDistanceSpec):
+            raise TypeError("label_distance must be True, \"visible\" or a labeldist.LabelDistanceSpec")
+        if label_distance.num_verts != V:
+            raise ValueError("the label-distance spec has %d vertices, the model %d" % (label_distance.num_verts, V))
+        if self.num_cam != 4:
+            raise ValueError("the label-distance term projects with four camera columns")
+        dirs, slack = check_directions(directions), check_slack(slack)
+        self.ld_spec, self.ld_sigma, self.ld_slack, self.ld_directions, self.ld_visible = label_distance, sigma, slack, dirs, visible
+        n = (V if "m2i" in dirs else 0) + (W * W if "i2m" in dirs else 0)
+
+        def energy(x, verts, joints, data):
+            targets, mask = data
+            e = ld_energy(verts, x[:, :4], self.ld_spec, targets, (mask[0] == 1).to(torch.float32) if visible else None,
+                          self.ld_sigma, self.ld_slack, dirs)
+            e = e if isinstance(e, tuple) else (e,)
+            return torch.cat([t.reshape(t.shape[0], -1) for t in e], 1)
+
+        def check(labels, B, dev):
+            # (the prep launch: once per fit, outside any captured graph; mask: the cell `_forward` fills every iteration)
+            return LabelTargets(self._labels(labels, B, W, "labels"), self.ld_spec.num_classes), self._ld_mask
+        self._ld_mask = [None]
+        self._ld = _SideTerm("ld_weight", n, energy, check)
 
     # ---- inputs -------------------------------------------------------------------------------------------------------
     def initial(self, B, init=None, generator=None, device=None):
@@ -1009,6 +1074,8 @@ class ParamFitter(_Fitter):
     def _forward(self, x, data):
         out = self.decoder(x, data[0], silh_labels=data[1])
         terms = [out["seg_loss"]] if data[1] is None else [out["seg_loss"], out["silh_loss"]]
+        if self._ld is not None and self.ld_visible:
+            self._ld_mask[0] = out["mask"].detach()
         return terms, self.silh_weight, out.get("verts"), out.get("J_transformed")
 
     def _cotangents(self, B, dev, data):
@@ -1023,7 +1090,12 @@ class ParamFitter(_Fitter):
         for x in its history.  With a prior its weighted energy E is part of the loss, as in `fit`; so is the
         self-penetration term of a fitter built with `penetration` (pen_weight None: 1) and the keypoint term of one built
         with `keypoints` (keypoints = (target, conf), kp_weight None: 1)."""
-        sides = self._check_sides(pen_weight, keypoints, kp_weight)
+        return self._losses_maps(x, labels, silh_labels, prior, prior_weights, pen_weight, keypoints, kp_weight)
+
+    def _losses_maps(self, x, labels, silh_labels=None, prior=None, prior_weights=None, pen_weight=None, keypoints=None,
+                     kp_weight=None, ld_weight=None):
+        """`losses`, with the weight of the label-distance term that only `LabelDistanceFitter.losses` takes."""
+        sides = self._check_sides(pen_weight, keypoints, kp_weight, ld_weight, labels)
         return self._losses(x, self._data(labels, silh_labels, int(x.shape[0])), prior, prior_weights, sides)
 
     # ---- the loop -----------------------------------------------------------------------------------------------------
@@ -1056,13 +1128,50 @@ class ParamFitter(_Fitter):
         keypoints = (target (B, K, 2), conf (B, K)) and kp_weight (a fitter built with `keypoints` only; kp_weight None: 1):
         detected 2D joints in the decoder's pixel frame; the term kp_weight mean_K(e), e = `keypoints.keypoint_energy`, joins
         every column of the loss and the one `torch.autograd.grad` call, as the self-penetration term does."""
-        loop = _fit_args(locals())
-        sides = self._check_sides(pen_weight, keypoints, kp_weight)
+        return self._fit_maps(locals())
+
+    def _fit_maps(self, given, ld_weight=None):
+        """`fit` on its own arguments by name (`given`), with the weight of the label-distance term that only
+        `LabelDistanceFitter.fit` takes."""
+        loop = _fit_args(given)
+        labels, init, generator, silh_labels = (given[k] for k in ("labels", "init", "generator", "silh_labels"))
+        sides = self._check_sides(given["pen_weight"], given["keypoints"], given["kp_weight"], ld_weight, labels)
         if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
             raise ValueError("labels must be a (B, W, W) integer tensor")
         B, dev = int(labels.shape[0]), labels.device
         return self._fit(B, dev, lambda: self.initial(B, init, generator, dev), lambda: self._data(labels, silh_labels, B), sides,
                          **loop)
+
+
+class LabelDistanceFitter(ParamFitter):
+    """`ParamFitter` with the label-distance term (labeldist.py) as a third side term, after penetration and keypoints: every
+    vertex to the nearest pixel of its part beside every labelled pixel to the nearest vertex of its part, against the fit's
+    own labels - the term that pulls from far away, where the focal loss of the soft scores says nothing.  A class of its
+    own because `ParamFitter`'s constructor, `fit` and `losses` keep the signatures their callers rely on; every other
+    argument of those three passes through by name.
+
+    label_distance: True (`LabelDistanceSpec.from_parts` of the decoder's part table), "visible" (that, with vweight = (the
+    decoder's mask == 1), detached, the decoder built with "mask" among its outputs), a LabelDistanceSpec, or None / False
+    (no term: a plain `ParamFitter`).  ld_sigma (pixels; None: rho(s) = s), ld_slack (px^2) and ld_directions as
+    `labeldist.label_distance` takes them.  vertex_sampling must be None or 1.
+    fit(labels, ld_weight=None, ...) and losses(x, labels, ld_weight=None, ...): ld_weight (None: 1, one float, or one per
+    stage) times mean(e) joins every column of the loss and the one `torch.autograd.grad` call through a cotangent
+    ld_weight / n, n = V + W W for both directions, cam = x[:, :4].  The labels are sorted by class once per fit, before the
+    loop: the prep launch stays outside any captured graph."""
+
+    def __init__(self, smpl_path=None, label_distance=True, ld_sigma=None, ld_slack=0.5, ld_directions=("m2i", "i2m"),
+                 **param_fitter):
+        self._ld_options = (label_distance, ld_sigma, ld_slack, ld_directions)
+        super().__init__(smpl_path, **param_fitter)
+
+    def losses(self, x, labels, ld_weight=None, **losses_kw):
+        return self._losses_maps(x, labels, ld_weight=ld_weight, **losses_kw)
+
+    def fit(self, labels, ld_weight=None, **fit_kw):
+        import inspect
+        given = inspect.signature(ParamFitter.fit).bind(self, labels, **fit_kw)    # (an unknown name: TypeError, as `fit` gives)
+        given.apply_defaults()
+        return self._fit_maps(dict(given.arguments), ld_weight)
 
 
 def robust_rho(d2, sigma):

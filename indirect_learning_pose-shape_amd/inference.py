@@ -31,7 +31,9 @@ def refine_predictions(smpl_model, fitter, images, labels, **fit_kw):
     -> dict(smpl (N, 86): the network's parameters, refined (N, 86): the best iterate of each row, loss (N,): its loss,
     result: the whole `fitting.FitResult`).  The best iterate includes step 0, so `refined` is never worse than `smpl`
     under the fitter's loss.  Every keyword of `fit` passes through, so `group_size=G, tie=..., smooth=...` refine G
-    consecutive images as views or frames of one body (the predictions' tied columns start at the group's mean)."""
+    consecutive images as views or frames of one body (the predictions' tied columns start at the group's mean), and
+    `ld_weight=` reaches a fitter built with `label_distance=...`: the term that still pulls when the prediction lies many
+    pixels from its labels."""
     was_training = smpl_model.training
     smpl_model.eval()
     try:
