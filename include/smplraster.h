@@ -836,6 +836,60 @@ int smplr_fit_step_group(float *x, const float *g, float *m, float *v, int32_t *
                          const float *angle_scale, const float *shape_mean, int K, int A, const float *weights, int G,
                          const uint8_t *tie, const float *smooth, void *stream);
 
+/* ---- per-row L-BFGS with a backtracking Armijo line search, in smplr_fit_step's place; INTEGRATION.md 4s --------------
+ * A state machine that advances by exactly ONE function evaluation per launch: B workgroups, one per row of x (B, P),
+ * P <= 256; no workspace, no allocation, no synchronisation, no atomics.  Every row has its own memory, direction, step
+ * length and line-search state and accepts, shrinks, resets or stops on its own.  State (in/out), beyond smplr_fit_step's
+ * x, best_x, t, calls, stall, bad, best_step, active, best_loss (the same meaning; no m, v):
+ *   x0, g0, d (B, P) fp32: the accepted iterate, its scaled gradient, the direction; f0, gd, alpha (B) fp32: its loss, g0 . d,
+ *   the step length; ls, pairs (B) int32: rejections in this line search, pairs ever stored (ring slot pairs % M);
+ *   phase (B) uint8: 0 - the next evaluation starts a search from x, 1 - x is a trial point; S, Y (B, M, P) fp32, 1 <= M <= 16.
+ * x is always the point the next forward evaluates.  One call, for row b (c = col_scale):
+ *   1. L as smplr_fit_step's step 1 (the same device functions: the same bits).
+ *   2. history[calls[b], b] = L while calls[b] < H; calls[b] += 1.
+ *   3. g^_j = c_j (gscale g_j): two fp32 products.  The method works in z = x / c: c is a diagonal preconditioner, c_j = 0
+ *      freezes column j.
+ *   4. L or any g_j not finite: bad[b] += 1; in phase 0 nothing else of the row changes; in phase 1 an active row takes the
+ *      call as a rejected trial (8), without 6.
+ *   5. an inactive row: nothing else changes.
+ *   6. L < best_loss (strict): best_loss = L, best_x = x, best_step = t, stall = 0; otherwise stall += 1; patience > 0 and
+ *      stall >= patience: active = 0 and nothing below happens.
+ *   7. accept in phase 0, or when (double)L <= (double)f0 + ((double)c1 (double)alpha) (double)gd.  Then, in this order:
+ *      7.1 (phase 1) s_j = fp32(alpha d_j) (one fp32 product), y_j = g^_j - g0_j, ys = y . s; ys > 1e-10: S, Y[pairs % M] = s, y and
+ *          pairs += 1; t += 1 either way.
+ *      7.2 x0 = x, f0 = L, g0 = g^.
+ *      7.3 |g^_j| <= tol_grad for every j: active = 0, and nothing below happens.
+ *      7.4 k = min(pairs, M): the two-loop recursion in fp64 over the k newest pairs: q = g^; newest first rho_i = 1 / (y_i . s_i),
+ *          a_i = rho_i (s_i . q), q -= a_i y_i; q *= (y . s) / (y . y) of the newest pair; oldest first b = rho_i (y_i . q),
+ *          q += (a_i - b) s_i; d = fp32(-q), gd = fp32(g^ . d) on the stored d.
+ *      7.5 k > 0 and not gd < 0: pairs = 0.
+ *      7.6 k = 0 or pairs = 0: d = -g^, gd = fp32(-(g^ . g^)), alpha = fp32(lr min(1, 1 / |g^|_1)); otherwise alpha = lr.
+ *      7.7 ls = 0, phase = 1.
+ *   8. reject: ls += 1.  ls > max_ls: with pairs > 0 the memory is dropped and the search restarts along steepest descent
+ *      from x0 - pairs = 0, d = -g0, gd = fp32(-(g0 . g0)), alpha = fp32(lr min(1, 1 / |g0|_1)), ls = 0; with pairs = 0 the
+ *      line search has failed at fp32 resolution: active = 0.  Otherwise alpha = fp32(0.5 alpha).
+ *   9. an active row: x_j = x0_j + (alpha c_j) d_j - three fp32 operations; not stored where c_j = 0.
+ * Every dot product is fp64 on the fp32 operands (q stays fp64 inside 7.4), thread j's term combined by the loss's tree: the xor
+ * butterfly of a wave, then the waves (0 + 1) + (2 + 3); a stored value is rounded to fp32 once.  The same bits on every launch
+ * and for any batch around the row.  smplr_lbfgs_step_prior: L = fp32(L_data + E) and g_j + dE_j (one fp32 addition, before
+ * anything else) in place of L and g, exactly as smplr_fit_step_prior.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= P <= 256; 1 <= M <= 16; N >= 1; Ns >= 1 with silh_loss; H >= 0;
+ * patience >= 0; max_ls >= 0; lr > 0 and finite; 0 < c1 < 1; tol_grad >= 0; gscale, silh_weight finite; with a prior
+ * smplr_fit_step_prior's limits; B >= 0 (B = 0 is a no-op); no null pointer but silh_loss and history.                     */
+int smplr_lbfgs_step(float *x, const float *g, float *x0, float *g0, float *d, float *S, float *Y, float *f0, float *gd,
+                     float *alpha, int32_t *ls, int32_t *pairs, uint8_t *phase, int32_t *t, int32_t *calls, int32_t *stall,
+                     int32_t *bad, int32_t *best_step, uint8_t *active, float *best_loss, float *best_x, const float *loss, int N,
+                     const float *silh_loss, int Ns, float silh_weight, const float *col_scale, float *history, int H, int B,
+                     int P, int M, float lr, float c1, int max_ls, float tol_grad, float gscale, int patience, void *stream);
+int smplr_lbfgs_step_prior(float *x, const float *g, float *x0, float *g0, float *d, float *S, float *Y, float *f0, float *gd,
+                           float *alpha, int32_t *ls, int32_t *pairs, uint8_t *phase, int32_t *t, int32_t *calls,
+                           int32_t *stall, int32_t *bad, int32_t *best_step, uint8_t *active, float *best_loss, float *best_x,
+                           const float *loss, int N, const float *silh_loss, int Ns, float silh_weight, const float *col_scale,
+                           float *history, int H, int B, int P, int M, float lr, float c1, int max_ls, float tol_grad,
+                           float gscale, int patience, int num_cam, const float *mean, const float *factor, const float *offset,
+                           const int32_t *angle_idx, const float *angle_scale, const float *shape_mean, int K, int A,
+                           const float *weights, void *stream);
+
 /* ---- projects_to_silhouette: keras_smpl/projects_to_silhouette.py:14-44 ----------------- */
 /* silh (B,W,W,2) = [1-s, s], s = max_v exp(-|proj_v-(c,r)|/1.2) over ALL VP vertices, rows
  * flipped; arg (B,W,W) int32 = maximising vertex.  workspace: smplr_silh_workspace(B,VP,W) B.  */

@@ -111,6 +111,9 @@ SIGNATURES = {
                                      c_float, c_float, c_float, I, I, I, P, P, P, P, P, P, I, I, P, P]),
     "smplr_fit_step_group": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, c_float, P, P, I, I, I, c_float, c_float,
                                      c_float, c_float, c_float, I, I, I, P, P, P, P, P, P, I, I, P, I, P, P, P]),
+    "smplr_lbfgs_step": (c_int, [P] * 22 + [I, P, I, c_float, P, P, I, I, I, I, c_float, c_float, I, c_float, c_float, I, P]),
+    "smplr_lbfgs_step_prior": (c_int, [P] * 22 + [I, P, I, c_float, P, P, I, I, I, I, c_float, c_float, I, c_float, c_float, I,
+                                                  I, P, P, P, P, P, P, I, I, P, P]),
     "smplr_silh_workspace": (c_size_t, [I, I, I]),
     "smplr_silh_fwd": (c_int, [P, I, I, I, P, P, P, P]),
     "smplr_silh_fwd_hint": (c_int, [P, P, I, I, I, P, P, P, P]),

@@ -1060,6 +1060,136 @@ void fit_step_group_meta(Tensor &x, const Tensor &g, Tensor &m, Tensor &v, Tenso
                        num_cam);
 }
 
+// ---- per-row L-BFGS in fit_step's place (csrc/lbfgs.hip): one function evaluation per launch ----------------------------
+// state, all changed in place: x, x0, g0, d, best_x (B, P) fp32; S, Y (B, M, P) fp32, 1 <= M <= 16; f0, gd, alpha, best_loss (B)
+// fp32; ls, pairs, t, calls, stall, bad, best_step (B) int32; phase, active (B) uint8.  g, loss, silh_loss, col_scale, history
+// as fit_step's.  LbTensors: the 25 tensors of a call, by reference, with the checks and the launch spelled once.
+struct LbTensors {
+  const Tensor &x, &g, &x0, &g0, &d, &S, &Y, &f0, &gd, &alpha, &ls, &pairs, &phase, &t, &calls, &stall, &bad, &best_step, &active,
+      &best_loss, &best_x, &loss;
+  const c10::optional<Tensor> &silh_loss;
+  const Tensor &col_scale;
+  const c10::optional<Tensor> &history;
+
+  void check(int64_t max_ls, int64_t patience) const {
+    TORCH_CHECK(x.dim() == 2 && x.size(1) >= 1 && x.size(1) <= 256 && x.scalar_type() == at::kFloat, "x must be (B, P) float32, 1 <= P <= 256");
+    const int64_t B = x.size(0), P = x.size(1);
+    for (const auto &nt : {std::make_pair("g", &g), std::make_pair("x0", &x0), std::make_pair("g0", &g0), std::make_pair("d", &d),
+                           std::make_pair("best_x", &best_x)})
+      TORCH_CHECK(nt.second->sizes() == x.sizes() && nt.second->scalar_type() == at::kFloat, nt.first, " must be (B, P) float32 as x");
+    TORCH_CHECK(S.dim() == 3 && S.size(0) == B && S.size(1) >= 1 && S.size(1) <= 16 && S.size(2) == P && S.scalar_type() == at::kFloat,
+                "S must be (B, M, P) float32, 1 <= M <= 16");
+    TORCH_CHECK(Y.sizes() == S.sizes() && Y.scalar_type() == at::kFloat, "Y must be (B, M, P) float32 as S");
+    for (const auto &nt : {std::make_pair("f0", &f0), std::make_pair("gd", &gd), std::make_pair("alpha", &alpha),
+                           std::make_pair("best_loss", &best_loss)})
+      TORCH_CHECK(nt.second->dim() == 1 && nt.second->size(0) == B && nt.second->scalar_type() == at::kFloat, nt.first, " must be (B,) float32");
+    for (const auto &nt : {std::make_pair("ls", &ls), std::make_pair("pairs", &pairs), std::make_pair("t", &t),
+                           std::make_pair("calls", &calls), std::make_pair("stall", &stall), std::make_pair("bad", &bad),
+                           std::make_pair("best_step", &best_step)})
+      TORCH_CHECK(nt.second->dim() == 1 && nt.second->size(0) == B && nt.second->scalar_type() == at::kInt, nt.first, " must be (B,) int32");
+    for (const auto &nt : {std::make_pair("phase", &phase), std::make_pair("active", &active)})
+      TORCH_CHECK(nt.second->dim() == 1 && nt.second->size(0) == B && nt.second->scalar_type() == at::kByte, nt.first, " must be (B,) uint8");
+    TORCH_CHECK(loss.dim() == 2 && loss.size(0) == B && loss.size(1) >= 1 && loss.size(1) <= INT32_MAX && loss.scalar_type() == at::kFloat,
+                "loss must be (B, N) float32, N >= 1");
+    TORCH_CHECK(!silh_loss || (silh_loss->dim() == 2 && silh_loss->size(0) == B && silh_loss->size(1) >= 1 &&
+                               silh_loss->size(1) <= INT32_MAX && silh_loss->scalar_type() == at::kFloat),
+                "silh_loss must be (B, Ns) float32, Ns >= 1");
+    TORCH_CHECK(col_scale.dim() == 1 && col_scale.size(0) == P && col_scale.scalar_type() == at::kFloat, "col_scale must be (P,) float32");
+    TORCH_CHECK(!history || (history->dim() == 2 && history->size(1) == B && history->size(0) <= INT32_MAX &&
+                             history->scalar_type() == at::kFloat), "history must be (H, B) float32");
+    TORCH_CHECK(max_ls >= 0 && max_ls <= INT32_MAX, "max_ls must be >= 0");
+    TORCH_CHECK(patience >= 0 && patience <= INT32_MAX && B <= INT32_MAX, "patience must be >= 0");
+  }
+  void on_device() const {
+    const Tensor none;
+    for (const auto &nt : {std::make_pair("x", &x), std::make_pair("g", &g), std::make_pair("x0", &x0), std::make_pair("g0", &g0),
+                           std::make_pair("d", &d), std::make_pair("S", &S), std::make_pair("Y", &Y), std::make_pair("f0", &f0),
+                           std::make_pair("gd", &gd), std::make_pair("alpha", &alpha), std::make_pair("best_loss", &best_loss),
+                           std::make_pair("best_x", &best_x), std::make_pair("loss", &loss), std::make_pair("col_scale", &col_scale)})
+      dev_f32(*nt.second, nt.first);
+    for (const auto &nt : {std::make_pair("ls", &ls), std::make_pair("pairs", &pairs), std::make_pair("t", &t),
+                           std::make_pair("calls", &calls), std::make_pair("stall", &stall), std::make_pair("bad", &bad),
+                           std::make_pair("best_step", &best_step)})
+      dev_typed(*nt.second, at::kInt, nt.first);
+    dev_typed(phase, at::kByte, "phase");
+    dev_typed(active, at::kByte, "active");
+    if (silh_loss) dev_f32(*silh_loss, "silh_loss");
+    if (history) dev_f32(*history, "history");
+    same_device(x, {{"g", &g}, {"x0", &x0}, {"g0", &g0}, {"d", &d}, {"S", &S}, {"Y", &Y}, {"f0", &f0}, {"gd", &gd}, {"alpha", &alpha},
+                    {"ls", &ls}, {"pairs", &pairs}, {"phase", &phase}, {"t", &t}, {"calls", &calls}, {"stall", &stall}, {"bad", &bad},
+                    {"best_step", &best_step}, {"active", &active}, {"best_loss", &best_loss}, {"best_x", &best_x}, {"loss", &loss},
+                    {"silh_loss", silh_loss ? &*silh_loss : &none}, {"col_scale", &col_scale}, {"history", history ? &*history : &none}});
+  }
+  // launcher(the operands every launcher starts with, extra..., stream); `extra`: a tuple of what follows patience in this one
+  template <class Launcher, class Extra>
+  void launch(Launcher launcher, const char *name, double lr, double c1, int64_t max_ls, double tol_grad, double gscale,
+              double silh_weight, int64_t patience, const Extra &extra) const {
+    const bool hist = history && history->numel() > 0;
+    std::apply([&](auto... e) {
+      ok(launcher(x.data_ptr<float>(), g.data_ptr<float>(), x0.data_ptr<float>(), g0.data_ptr<float>(), d.data_ptr<float>(),
+                  S.data_ptr<float>(), Y.data_ptr<float>(), f0.data_ptr<float>(), gd.data_ptr<float>(), alpha.data_ptr<float>(),
+                  ls.data_ptr<int32_t>(), pairs.data_ptr<int32_t>(), phase.data_ptr<uint8_t>(), t.data_ptr<int32_t>(),
+                  calls.data_ptr<int32_t>(), stall.data_ptr<int32_t>(), bad.data_ptr<int32_t>(), best_step.data_ptr<int32_t>(),
+                  active.data_ptr<uint8_t>(), best_loss.data_ptr<float>(), best_x.data_ptr<float>(), loss.data_ptr<float>(),
+                  (int)loss.size(1), silh_loss ? silh_loss->data_ptr<float>() : nullptr, silh_loss ? (int)silh_loss->size(1) : 0,
+                  (float)silh_weight, col_scale.data_ptr<float>(), hist ? history->data_ptr<float>() : nullptr,
+                  hist ? (int)history->size(0) : 0, (int)x.size(0), (int)x.size(1), (int)S.size(1), (float)lr, (float)c1, (int)max_ls,
+                  (float)tol_grad, (float)gscale, (int)patience, e..., cur_stream()),
+         name);
+    }, extra);
+  }
+};
+void lbfgs_step(Tensor &x, const Tensor &g, Tensor &x0, Tensor &g0, Tensor &d, Tensor &S, Tensor &Y, Tensor &f0, Tensor &gd,
+                Tensor &alpha, Tensor &ls, Tensor &pairs, Tensor &phase, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
+                Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
+                const c10::optional<Tensor> &silh_loss, const Tensor &col_scale, c10::optional<Tensor> history, double lr, double c1,
+                int64_t max_ls, double tol_grad, double gscale, double silh_weight, int64_t patience) {
+  const LbTensors f{x, g, x0, g0, d, S, Y, f0, gd, alpha, ls, pairs, phase, t, calls, stall, bad, best_step, active, best_loss, best_x,
+                    loss, silh_loss, col_scale, history};
+  f.check(max_ls, patience);
+  f.on_device();
+  DeviceGuard guard(x.device());
+  if (x.size(0) == 0) return;
+  f.launch(smplr_lbfgs_step, "smplr_lbfgs_step", lr, c1, max_ls, tol_grad, gscale, silh_weight, patience, std::make_tuple());
+}
+void lbfgs_step_meta(Tensor &x, const Tensor &g, Tensor &x0, Tensor &g0, Tensor &d, Tensor &S, Tensor &Y, Tensor &f0, Tensor &gd,
+                     Tensor &alpha, Tensor &ls, Tensor &pairs, Tensor &phase, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
+                     Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
+                     const c10::optional<Tensor> &silh_loss, const Tensor &col_scale, c10::optional<Tensor> history, double, double,
+                     int64_t max_ls, double, double, double, int64_t patience) {
+  LbTensors{x, g, x0, g0, d, S, Y, f0, gd, alpha, ls, pairs, phase, t, calls, stall, bad, best_step, active, best_loss, best_x, loss,
+            silh_loss, col_scale, history}.check(max_ls, patience);
+}
+void lbfgs_step_prior(Tensor &x, const Tensor &g, Tensor &x0, Tensor &g0, Tensor &d, Tensor &S, Tensor &Y, Tensor &f0, Tensor &gd,
+                      Tensor &alpha, Tensor &ls, Tensor &pairs, Tensor &phase, Tensor &t, Tensor &calls, Tensor &stall, Tensor &bad,
+                      Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
+                      const c10::optional<Tensor> &silh_loss, const Tensor &col_scale, c10::optional<Tensor> history,
+                      const Tensor &mean, const Tensor &factor, const Tensor &offset, const Tensor &angle_idx,
+                      const Tensor &angle_scale, const Tensor &shape_mean, const Tensor &weights, double lr, double c1, int64_t max_ls,
+                      double tol_grad, double gscale, double silh_weight, int64_t patience, int64_t num_cam) {
+  const LbTensors f{x, g, x0, g0, d, S, Y, f0, gd, alpha, ls, pairs, phase, t, calls, stall, bad, best_step, active, best_loss, best_x,
+                    loss, silh_loss, col_scale, history};
+  const PriorTensors p(mean, factor, offset, angle_idx, angle_scale, shape_mean, weights);
+  f.check(max_ls, patience);
+  p.check(x, num_cam);
+  f.on_device();
+  p.on_device(x);
+  DeviceGuard guard(x.device());
+  if (x.size(0) == 0) return;
+  f.launch(smplr_lbfgs_step_prior, "smplr_lbfgs_step_prior", lr, c1, max_ls, tol_grad, gscale, silh_weight, patience, p.args(num_cam));
+}
+void lbfgs_step_prior_meta(Tensor &x, const Tensor &g, Tensor &x0, Tensor &g0, Tensor &d, Tensor &S, Tensor &Y, Tensor &f0, Tensor &gd,
+                           Tensor &alpha, Tensor &ls, Tensor &pairs, Tensor &phase, Tensor &t, Tensor &calls, Tensor &stall,
+                           Tensor &bad, Tensor &best_step, Tensor &active, Tensor &best_loss, Tensor &best_x, const Tensor &loss,
+                           const c10::optional<Tensor> &silh_loss, const Tensor &col_scale, c10::optional<Tensor> history,
+                           const Tensor &mean, const Tensor &factor, const Tensor &offset, const Tensor &angle_idx,
+                           const Tensor &angle_scale, const Tensor &shape_mean, const Tensor &weights, double, double,
+                           int64_t max_ls, double, double, double, int64_t patience, int64_t num_cam) {
+  LbTensors{x, g, x0, g0, d, S, Y, f0, gd, alpha, ls, pairs, phase, t, calls, stall, bad, best_step, active, best_loss, best_x, loss,
+            silh_loss, col_scale, history}.check(max_ls, patience);
+  PriorTensors(mean, factor, offset, angle_idx, angle_scale, shape_mean, weights).check(x, num_cam);
+}
+
 // ---- body measurements (csrc/measure.hip): verts (B, V, 3), faces (F, 3) int32, face_part (F) uint8, planes (K, 4) or
 // (B, K, 4), part_mask (K) int32 holding the 32 mask bits -> [volume (B), area (B), extent (B, 3), ext_idx (B, 6) int32,
 // girth (B, K), dgirth_dplane (B, K, 4) or (0) without plane_grad, status (B) int32]; K = 0 without planes -----------------
@@ -1322,6 +1452,17 @@ TORCH_LIBRARY(smplraster, m) {
         "Tensor? offset, Tensor? angle_idx, Tensor? angle_scale, Tensor? shape_mean, Tensor? weights, int group_size=1, "
         "float lr=0.001, float beta1=0.9, float beta2=0.999, float eps=1e-07, float gscale=1.0, float silh_weight=1.0, "
         "int mode=0, int patience=0, int num_cam=4) -> ()");
+  m.def("lbfgs_step(Tensor(a!) x, Tensor g, Tensor(b!) x0, Tensor(c!) g0, Tensor(d!) d, Tensor(e!) S, Tensor(f!) Y, Tensor(g!) f0, "
+        "Tensor(h!) gd, Tensor(i!) alpha, Tensor(j!) ls, Tensor(k!) pairs, Tensor(l!) phase, Tensor(m!) t, Tensor(n!) calls, "
+        "Tensor(o!) stall, Tensor(p!) bad, Tensor(q!) best_step, Tensor(r!) active, Tensor(s!) best_loss, Tensor(t!) best_x, "
+        "Tensor loss, Tensor? silh_loss, Tensor col_scale, Tensor(u!)? history, float lr=1.0, float c1=0.0001, int max_ls=10, float tol_grad=0.0, float gscale=1.0, "
+        "float silh_weight=1.0, int patience=0) -> ()");
+  m.def("lbfgs_step_prior(Tensor(a!) x, Tensor g, Tensor(b!) x0, Tensor(c!) g0, Tensor(d!) d, Tensor(e!) S, Tensor(f!) Y, Tensor(g!) f0, "
+        "Tensor(h!) gd, Tensor(i!) alpha, Tensor(j!) ls, Tensor(k!) pairs, Tensor(l!) phase, Tensor(m!) t, Tensor(n!) calls, "
+        "Tensor(o!) stall, Tensor(p!) bad, Tensor(q!) best_step, Tensor(r!) active, Tensor(s!) best_loss, Tensor(t!) best_x, "
+        "Tensor loss, Tensor? silh_loss, Tensor col_scale, Tensor(u!)? history, Tensor mean, Tensor factor, Tensor offset, "
+        "Tensor angle_idx, Tensor angle_scale, Tensor shape_mean, Tensor weights, float lr=1.0, float c1=0.0001, int max_ls=10, float tol_grad=0.0, float gscale=1.0, "
+        "float silh_weight=1.0, int patience=0, int num_cam=4) -> ()");
   m.def("mesh_measures(Tensor verts, Tensor faces, Tensor? face_part=None, Tensor? planes=None, Tensor? part_mask=None, "
         "bool plane_grad=True) -> Tensor[]");
   m.def("mesh_measures_bwd(Tensor verts, Tensor faces, Tensor vf_off, Tensor vf_face, Tensor? face_part, Tensor? planes, "
@@ -1357,6 +1498,8 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("prior_energy", &prior_energy);
   m.impl("fit_step_prior", &fit_step_prior);
   m.impl("fit_step_group", &fit_step_group);
+  m.impl("lbfgs_step", &lbfgs_step);
+  m.impl("lbfgs_step_prior", &lbfgs_step_prior);
   m.impl("mesh_measures", &mesh_measures);
   m.impl("mesh_measures_bwd", &mesh_measures_bwd);
   m.impl("mesh_reg_fwd", &mesh_reg_fwd);
@@ -1388,6 +1531,8 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("prior_energy", &prior_energy_meta);
   m.impl("fit_step_prior", &fit_step_prior_meta);
   m.impl("fit_step_group", &fit_step_group_meta);
+  m.impl("lbfgs_step", &lbfgs_step_meta);
+  m.impl("lbfgs_step_prior", &lbfgs_step_prior_meta);
   m.impl("mesh_measures", &mesh_measures_meta);
   m.impl("mesh_measures_bwd", &mesh_measures_bwd_meta);
   m.impl("mesh_reg_fwd", &mesh_reg_fwd_meta);

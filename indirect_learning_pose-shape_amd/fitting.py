@@ -105,6 +105,45 @@ ld_weight mean(e[b, :]), e = `label_distance` of the iteration's vertices under 
 every vertex to the nearest pixel of its part beside every labelled pixel to the nearest vertex of its part - is the third
 side term, after penetration and keypoints, through a cotangent ld_weight / (V + W W).  The labels are sorted by class once
 per fit, outside any captured graph.  `ParamFitter` itself keeps its signatures and runs exactly the launches it ran before.
+
+Per-row L-BFGS (csrc/lbfgs.hip, smplr_lbfgs_step; tests/_lbfgs_oracle.py restates it in NumPy float64).  The keypoint, scan and
+prior terms are smooth least-squares-like energies that a quasi-Newton method minimises in far fewer evaluations than Adam:
+
+    r = KeypointFitter(smpl_path, sigma=3.0).fit(target, conf, steps=60, mode="lbfgs")
+    r = fitter.fit(labels, stages=[(40, cs0), (40, cs1)], mode=Lbfgs(memory=8, c1=1e-4, max_ls=10, tol_grad=0.0, lr=1.0), graph=True)
+
+`mode` picks the update rule of `ParamFitter`, `LabelDistanceFitter`, `ScanFitter` and `KeypointFitter`: Adam's two forms, or
+"lbfgs" / an `Lbfgs` record - a limited-memory BFGS with a backtracking Armijo line search, written as a state machine that
+advances by exactly ONE function evaluation per launch, in `fit_step`'s place: the iteration (forward, one `autograd.grad`,
+side terms, one launch), stages, graph capture, history, best iterate and patience stay as they are, and every row has its own
+memory, direction, step length and line-search state.  `steps` and stage counts are evaluations; the record's `lr` is the first
+trial step (fit's `lr`, `beta1`, `beta2`, `eps` are Adam's and ignored); a stage boundary also calls `state.restart()` - column
+scales and weights change the objective, so the memory and f0 are void.  group_size > 1, tie with groups, or smooth raise
+ValueError.  `LbfgsState` = `FitState` without m, v, plus x0, g0 (B, P) the accepted iterate and its scaled gradient, f0 (B,) its
+loss, d (B, P) the direction, gd = g0 . d, alpha the step length, ls rejections in this line search, pairs (B,) int32 pairs ever
+stored (ring slot pairs % M), phase (B,) uint8 (0: the next evaluation starts a search from x; 1: x is a trial point), S, Y
+(B, M, P) the memory, 1 <= M <= 16.  state.x is always the point the next forward evaluates.  One call, for row b:
+  1. L exactly as `fit_step`'s step 1 (+ prior): the same device functions, the same bits.
+  2. history[calls[b], b] = L while calls[b] < H; calls[b] += 1.
+  3. g^_j = c_j (grad_scale g_j), c = col_scale: two fp32 products.  The method works in z = x / c, so column scales are a
+     diagonal preconditioner and c_j = 0 freezes column j.
+  4. L or any g_j not finite: bad[b] += 1; in phase 0 nothing else of the row changes; in phase 1 an active row takes the call as
+     a rejected trial (8), without 6.
+  5. An inactive row: nothing else changes.
+  6. `fit_step`'s step 4 on the evaluated point: L < best_loss (strict) -> best_loss, best_x = x, best_step = t, stall = 0,
+     otherwise stall += 1; patience > 0 and stall >= patience: active = 0 and nothing below happens.
+  7. Accept in phase 0, or when L <= f0 + c1 alpha gd (fp64 on the four fp32 values).  Then, in this order: (7.1, phase 1)
+     s_j = fp32(alpha d_j), y_j = g^_j - g0_j; y . s > 1e-10 (the rule of `torch.optim.LBFGS`): the pair goes to slot pairs % M and
+     pairs += 1; t += 1 either way.  (7.2) x0 = x, f0 = L, g0 = g^.  (7.3) max_j |g^_j| <= tol_grad: active = 0, stop here.  (7.4) the
+     two-loop recursion in fp64 over the k = min(pairs, M) newest pairs, rho_i = 1 / (y_i . s_i) from the stored vectors, scaled by
+     (y . s) / (y . y) of the newest pair between the loops; d = fp32(-q), gd = fp32(g^ . d).  (7.5) k > 0 and not gd < 0: pairs = 0.
+     (7.6) k = 0 or pairs = 0: d = -g^, gd = fp32(-g^ . g^), alpha = fp32(lr min(1, 1 / |g^|_1)); otherwise alpha = lr.  (7.7) ls = 0,
+     phase = 1.
+  8. Reject: ls += 1.  ls > max_ls: with pairs > 0 the memory is forgotten and the search restarts along steepest descent from x0
+     (pairs = 0, d = -g0, gd = fp32(-g0 . g0), alpha = fp32(lr min(1, 1 / |g0|_1)), ls = 0); with pairs = 0 already the line search
+     has failed at fp32 resolution: active = 0.  Otherwise alpha = fp32(alpha / 2).
+  9. An active row: x_j = x0_j + (alpha c_j) d_j, three fp32 operations; not stored where c_j = 0.
+Dot products are fp64 on the fp32 operands, combined by the loss's fixed tree; every stored value is rounded to fp32 once.
 """
 from __future__ import annotations
 
@@ -130,6 +169,7 @@ SMPLIFY_ANGLE_IDX = (55, 58, 12, 15)
 SMPLIFY_ANGLE_SCALE = (1.0, -1.0, -1.0, -1.0)
 MAX_GROUP = 16                 # rows of a group (csrc/fit.hip FT_GMAX)
 TIE_NAMES = ("cam", "global_rot", "pose", "shape")
+MAX_MEMORY = 16                # pairs of a row's L-BFGS memory (csrc/lbfgs.hip LB_MMAX)
 
 
 @dataclass
@@ -166,6 +206,110 @@ class FitState:
 
     def clone(self):
         return FitState(**{f.name: getattr(self, f.name).clone() for f in fields(self)})
+
+
+@dataclass(frozen=True)
+class Lbfgs:
+    """`fit(mode=Lbfgs(...))`: per-row L-BFGS in Adam's place ("lbfgs" = the defaults).  memory: pairs kept per row, 1..16;
+    c1: the Armijo constant, in (0, 1); max_ls: halvings of a line search before the memory is dropped (then: before the row
+    stops); tol_grad: a row stops when max_j |g^_j| <= tol_grad; lr: the first trial step of a search, > 0."""
+    memory: int = 8
+    c1: float = 1e-4
+    max_ls: int = 10
+    tol_grad: float = 0.0
+    lr: float = 1.0
+
+    def __post_init__(self):
+        check_memory(self.memory)
+        if isinstance(self.max_ls, bool) or not isinstance(self.max_ls, (int, np.integer)) or self.max_ls < 0:
+            raise ValueError("max_ls must be an integer >= 0, got %r" % (self.max_ls,))
+        if not (0.0 < float(self.c1) < 1.0):
+            raise ValueError("c1 must lie in (0, 1), got %r" % (self.c1,))
+        if not (math.isfinite(float(self.tol_grad)) and float(self.tol_grad) >= 0.0):
+            raise ValueError("tol_grad must be finite and >= 0, got %r" % (self.tol_grad,))
+        if not (math.isfinite(float(self.lr)) and float(self.lr) > 0.0):
+            raise ValueError("lr must be finite and > 0, got %r" % (self.lr,))
+
+
+def check_memory(memory):
+    if isinstance(memory, bool) or not isinstance(memory, (int, np.integer)) or not 1 <= memory <= MAX_MEMORY:
+        raise ValueError("memory must be an integer in 1..%d, got %r" % (MAX_MEMORY, memory))
+    return int(memory)
+
+
+def check_mode(mode, lbfgs=True):
+    """`fit`'s mode -> None for Adam's two forms, an `Lbfgs` record for "lbfgs" or a record; anything else: ValueError."""
+    if isinstance(mode, Lbfgs):
+        opt = mode
+    elif isinstance(mode, str) and mode == "lbfgs":
+        opt = Lbfgs()
+    elif isinstance(mode, str) and mode in MODES:
+        return None
+    else:
+        raise ValueError("mode %r is none of %s%s" % (mode, MODES, ", \"lbfgs\" or an Lbfgs record" if lbfgs else ""))
+    if not lbfgs:
+        raise ValueError("mode %r: this loop runs Adam only, mode is one of %s" % (mode, MODES))
+    return opt
+
+
+@dataclass
+class LbfgsState:
+    """The per-row state smplr_lbfgs_step reads and writes: every field of `FitState` but m and v, with the same meaning, and
+    x0, g0, d (B, P) fp32; f0, gd, alpha (B,) fp32; ls, pairs (B,) int32; phase (B,) uint8; S, Y (B, M, P) fp32 (the module's
+    semantics).  x is always the point the next forward evaluates."""
+    x: torch.Tensor
+    best_x: torch.Tensor
+    t: torch.Tensor
+    calls: torch.Tensor
+    stall: torch.Tensor
+    bad: torch.Tensor
+    best_step: torch.Tensor
+    active: torch.Tensor
+    best_loss: torch.Tensor
+    x0: torch.Tensor
+    g0: torch.Tensor
+    f0: torch.Tensor
+    d: torch.Tensor
+    gd: torch.Tensor
+    alpha: torch.Tensor
+    ls: torch.Tensor
+    pairs: torch.Tensor
+    phase: torch.Tensor
+    S: torch.Tensor
+    Y: torch.Tensor
+
+    @classmethod
+    def new(cls, x0, memory=8):
+        """x0 (B, P) -> a fresh state around a float32 copy of it: phase = 0, an empty memory of `memory` pairs, every counter 0,
+        active = 1, best_loss = +inf, best_x = x0 = x."""
+        M = check_memory(memory)
+        base = FitState.new(x0)
+        x = base.x
+        B, P = int(x.shape[0]), int(x.shape[1])
+        zf = lambda: torch.zeros(B, dtype=torch.float32, device=x.device)
+        zi = lambda: torch.zeros(B, dtype=torch.int32, device=x.device)
+        return cls(x=x, best_x=base.best_x, t=base.t, calls=base.calls, stall=base.stall, bad=base.bad, best_step=base.best_step,
+                   active=base.active, best_loss=base.best_loss, x0=x.clone(), g0=torch.zeros_like(x), f0=zf(), d=torch.zeros_like(x),
+                   gd=zf(), alpha=zf(), ls=zi(), pairs=zi(), phase=torch.zeros(B, dtype=torch.uint8, device=x.device),
+                   S=torch.zeros((B, M, P), dtype=torch.float32, device=x.device),
+                   Y=torch.zeros((B, M, P), dtype=torch.float32, device=x.device))
+
+    @property
+    def memory(self):
+        return int(self.S.shape[1])
+
+    def clone(self):
+        return LbfgsState(**{f.name: getattr(self, f.name).clone() for f in fields(self)})
+
+    def restart(self):
+        """The objective has changed (column scales, weights): rows at a trial point go back to their accepted iterate, and every
+        row forgets its memory and starts a new search with its next evaluation - x <- x0 where phase = 1; pairs = ls = 0,
+        phase = 0.  Counters and the best iterate run on.  In place, on the tensors' device, no host synchronisation."""
+        self.x.copy_(torch.where((self.phase != 0)[:, None], self.x0, self.x))
+        self.pairs.zero_()
+        self.ls.zero_()
+        self.phase.zero_()
+        return self
 
 
 def column_scale(cam=1.0, pose=1.0, shape=1.0, num_cam=4):
@@ -621,6 +765,84 @@ def fit_step(state, grad, loss, silh_loss=None, silh_weight=1.0, col_scale=None,
     return state
 
 
+@_lib.on_device
+def lbfgs_step(state, grad, loss, silh_loss=None, silh_weight=1.0, col_scale=None, history=None, lr=1.0, c1=1e-4, max_ls=10,
+               tol_grad=0.0, grad_scale=1.0, patience=0, prior=None, prior_weights=None, num_cam=4):
+    """One smplr_lbfgs_step launch on `state` (an `LbfgsState`, in place; see the module's semantics): ONE function evaluation
+    of every row's own L-BFGS with a backtracking Armijo line search.  grad, loss, silh_loss, col_scale, history, grad_scale,
+    patience, prior, prior_weights and num_cam as `fit_step` takes them (with a prior the launch is smplr_lbfgs_step_prior);
+    HIP tensors only."""
+    rc = _lib.require_cuda
+    if not isinstance(state, LbfgsState):
+        raise TypeError("state must be an LbfgsState")
+    if not state.x.is_contiguous():
+        raise RuntimeError("x must be contiguous (it is updated in place)")
+    x = rc(state.x, "x")
+    B, P = int(x.shape[0]), int(x.shape[1])
+    same = {"grad": grad, "best_x": state.best_x, "x0": state.x0, "g0": state.g0, "d": state.d}
+    ints = {"t": state.t, "calls": state.calls, "stall": state.stall, "bad": state.bad, "best_step": state.best_step,
+            "ls": state.ls, "pairs": state.pairs}
+    flts = {"best_loss": state.best_loss, "f0": state.f0, "gd": state.gd, "alpha": state.alpha}
+    byts = {"active": state.active, "phase": state.phase}
+    for name, a in same.items():
+        if tuple(a.shape) != (B, P) or not a.is_contiguous():
+            raise RuntimeError("%s must be a contiguous (%d, %d) tensor, got %s" % (name, B, P, tuple(a.shape)))
+        rc(a, name)
+    for group, dt in ((ints, torch.int32), (flts, torch.float32), (byts, torch.uint8)):
+        for name, a in group.items():
+            if tuple(a.shape) != (B,):
+                raise RuntimeError("%s must be (%d,), got %s" % (name, B, tuple(a.shape)))
+            rc(a, name, dt)
+    M = int(state.S.shape[1]) if state.S.dim() == 3 else -1
+    if not 1 <= M <= MAX_MEMORY:
+        raise RuntimeError("S must be (B, M, P) with 1 <= M <= %d, got %s" % (MAX_MEMORY, tuple(state.S.shape)))
+    mem = {"S": state.S, "Y": state.Y}
+    for name, a in mem.items():
+        if tuple(a.shape) != (B, M, P) or not a.is_contiguous():
+            raise RuntimeError("%s must be a contiguous (%d, %d, %d) tensor, got %s" % (name, B, M, P, tuple(a.shape)))
+        rc(a, name)
+    if loss.dim() != 2 or loss.shape[0] != B or loss.shape[1] < 1 or not loss.is_contiguous():
+        raise RuntimeError("loss must be a contiguous (%d, N) tensor, got %s" % (B, tuple(loss.shape)))
+    rc(loss, "loss")
+    Ns = 0
+    if silh_loss is not None:
+        if silh_loss.dim() != 2 or silh_loss.shape[0] != B or silh_loss.shape[1] < 1 or not silh_loss.is_contiguous():
+            raise RuntimeError("silh_loss must be a contiguous (%d, Ns) tensor, got %s" % (B, tuple(silh_loss.shape)))
+        rc(silh_loss, "silh_loss")
+        Ns = int(silh_loss.shape[1])
+    if col_scale is None:
+        col_scale = torch.ones(P, dtype=torch.float32, device=x.device)
+    if tuple(col_scale.shape) != (P,) or not col_scale.is_contiguous():
+        raise RuntimeError("col_scale must be a contiguous (%d,) tensor, got %s" % (P, tuple(col_scale.shape)))
+    rc(col_scale, "col_scale")
+    H = 0
+    if history is not None:
+        if history.dim() != 2 or history.shape[1] != B or not history.is_contiguous():
+            raise RuntimeError("history must be a contiguous (H, %d) tensor, got %s" % (B, tuple(history.shape)))
+        rc(history, "history")
+        H = int(history.shape[0])
+    for name, a in (list(same.items()) + list(ints.items()) + list(flts.items()) + list(byts.items()) + list(mem.items()) +
+                    [("loss", loss), ("silh_loss", silh_loss), ("col_scale", col_scale), ("history", history)]):
+        if a is not None and a.device != x.device:
+            raise RuntimeError("%s lives on %s, x on %s" % (name, a.device, x.device))
+    w = None
+    if prior is not None:
+        prior, w = _prior_operands(prior, prior_weights, x)
+    elif prior_weights is not None:
+        raise ValueError("prior_weights without a prior")
+    common = (ptr(x), ptr(grad), ptr(state.x0), ptr(state.g0), ptr(state.d), ptr(state.S), ptr(state.Y), ptr(state.f0), ptr(state.gd),
+              ptr(state.alpha), ptr(state.ls), ptr(state.pairs), ptr(state.phase), ptr(state.t), ptr(state.calls), ptr(state.stall),
+              ptr(state.bad), ptr(state.best_step), ptr(state.active), ptr(state.best_loss), ptr(state.best_x), ptr(loss),
+              int(loss.shape[1]), ptr(silh_loss), Ns, float(silh_weight), ptr(col_scale), ptr(history) if H else None, H, B, P, M,
+              float(lr), float(c1), int(max_ls), float(tol_grad), float(grad_scale), int(patience))
+    lib = _lib.load()
+    if prior is not None:
+        check(lib.smplr_lbfgs_step_prior(*common, *_prior_args(prior, w, num_cam), stream()), "smplr_lbfgs_step_prior")
+    else:
+        check(lib.smplr_lbfgs_step(*common, stream()), "smplr_lbfgs_step")
+    return state
+
+
 @dataclass
 class FitResult:
     """x (B, P): the best iterate of each row; loss (B,): its loss; step (B,) int32: the update count it was reached at;
@@ -628,7 +850,9 @@ class FitResult:
     changed nothing); active (B,) bool: rows the patience rule had not stopped; history (steps run, B) fp32 loss trace or
     None; steps: iterations run (fewer than asked for when `check_every` found every row stopped); state: the whole
     `FitState` the loop ended with (moments and counters included); group_size: rows per group - with groups, loss, step and
-    active are the group's, repeated on each of its rows (history holds every row's own loss)."""
+    active are the group's, repeated on each of its rows (history holds every row's own loss).  `optimizer` (a property, read
+    off the state): "adam", or "lbfgs" - then state is an `LbfgsState`, steps are evaluations, step counts accepted steps and
+    final_x is the last ACCEPTED iterate state.x0 (state.x may be a trial point)."""
     x: torch.Tensor
     loss: torch.Tensor
     step: torch.Tensor
@@ -639,6 +863,10 @@ class FitResult:
     steps: int
     state: Optional[FitState] = None
     group_size: int = 1
+
+    @property
+    def optimizer(self):
+        return "lbfgs" if isinstance(self.state, LbfgsState) else "adam"
 
 
 def _stage_prior_weights(prior, prior_weights, stage_list):
@@ -673,11 +901,10 @@ _LOOP_ARGS = ("steps", "lr", "mode", "stages", "patience", "grad_scale", "graph"
              "graph_steps", "prior", "prior_weights", "group_size", "tie", "smooth")
 
 
-def _fit_args(given):
+def _fit_args(given, lbfgs=False):
     """What every `fit` starts with, on its own locals(): the mode check - so it is the first error a bad call raises - and
-    the loop's arguments among them, by name."""
-    if given["mode"] not in MODES:
-        raise ValueError("mode %r is none of %s" % (given["mode"], MODES))
+    the loop's arguments among them, by name.  lbfgs: the loop also takes mode = "lbfgs" or an `Lbfgs` record."""
+    check_mode(given["mode"], lbfgs)
     return {k: given[k] for k in _LOOP_ARGS if k in given}
 
 
@@ -882,11 +1109,13 @@ class _Fitter:
 
     def _iteration(self, state, data, sides, cots, cs, hist, kw):
         """One iteration on `state`: `_compose` on x, ONE `torch.autograd.grad` over all terms with their constant
-        cotangents cots (the data terms', then each side term's `cot`, in `_compose`'s order), one `fit_step`."""
+        cotangents cots (the data terms', then each side term's `cot`, in `_compose`'s order), one `fit_step` - or, on an
+        `LbfgsState`, one `lbfgs_step` in its place (kw: that function's)."""
         x = state.x.detach().requires_grad_(True)                 # (shares x's memory: the kernel updates it in place)
         terms, loss, silh_loss, silh_weight = self._compose(x, data, sides)
         (g,) = torch.autograd.grad(terms, [x], grad_outputs=cots)
-        fit_step(state, g.contiguous(), loss, silh_loss, silh_weight, cs, hist, **kw)
+        step = lbfgs_step if isinstance(state, LbfgsState) else fit_step
+        step(state, g.contiguous(), loss, silh_loss, silh_weight, cs, hist, **kw)
 
     def _losses(self, x, data, prior, prior_weights, sides):
         """`losses` behind a fitter's own look at its inputs: `_compose` - the forward `fit` iterates - without a gradient,
@@ -910,16 +1139,23 @@ class _Fitter:
         `check_every`.  check_data() -> the fitter's checked data, called between the groups' checks and the stages':
         whatever the fitter checks of its data there; sides: `_check_sides`' list."""
         P = self.P
+        opt = check_mode(mode)                                    # an `Lbfgs` record, or None: Adam
         grp = check_group(B, group_size)
         grouped = grp != 1 or smooth is not None
+        if opt is not None and grouped:
+            raise ValueError("mode \"lbfgs\" fits every row on its own: group_size > 1, tie and smooth need Adam's modes")
         tie_m = check_tie(tie, P, self.num_cam) if grouped else None
         smooth_w = check_smooth(smooth, P) if smooth is not None else None
         data = check_data()
         stage_list = check_stages(stages, P, steps)
         stage_w = _stage_prior_weights(prior, prior_weights, stage_list)
         sides = [(t, _stage_weights(w, stage_list, t.name), d) for t, w, d in sides]
-        kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
-                  mode=mode, patience=int(patience))
+        if opt is None:
+            kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
+                      mode=mode, patience=int(patience))
+        else:
+            kw = dict(lr=float(opt.lr), c1=float(opt.c1), max_ls=int(opt.max_ls), tol_grad=float(opt.tol_grad),
+                      grad_scale=float(grad_scale), patience=int(patience))
         total = sum(n for n, _ in stage_list)
         G = max(1, int(graph_steps))
         with torch.cuda.device(dev):
@@ -929,7 +1165,7 @@ class _Fitter:
                 if grp > 1:                                           # a group starts with one value in every tied column
                     mean = x0.reshape(B // grp, grp, P).mean(1, keepdim=True).expand(-1, grp, -1).reshape(B, P)
                     x0 = torch.where(tie_m.bool(), mean, x0)
-            state = FitState.new(x0)
+            state = FitState.new(x0) if opt is None else LbfgsState.new(x0, opt.memory)
             hist = torch.full((total, B), float("nan"), dtype=torch.float32, device=dev) if history and total else None
             cs = torch.ones(P, dtype=torch.float32, device=dev)
             scales = [c.to(dev) for _, c in stage_list]
@@ -950,13 +1186,16 @@ class _Fitter:
                     kw["prior_weights"].copy_(stage_w[si])
                 for s in sides:
                     s.set(si)
+                if opt is not None:                                   # (the objective changes: the memory and f0 are void)
+                    state.restart()
             replay = None
             if graph and B > 0 and any(n >= G for n, _ in stage_list):
                 replay = _capture(one, (state.clone(), None), (state, hist), G, dev)
             done = _run_stages(stage_list, set_stage, lambda: one(state, hist), replay, G, int(check_every) if B > 0 else 0,
                                lambda: bool(state.active.any()))
             torch.cuda.synchronize()
-        return FitResult(x=state.best_x, loss=state.best_loss, step=state.best_step, final_x=state.x, nonfinite=state.bad,
+        return FitResult(x=state.best_x, loss=state.best_loss, step=state.best_step, final_x=state.x if opt is None else state.x0,
+                         nonfinite=state.bad,
                          active=state.active.bool(), history=hist[:done] if hist is not None else None, steps=done,
                          state=state, group_size=grp)
 
@@ -1114,6 +1353,12 @@ class ParamFitter(_Fitter):
         loss inside the same launch, with prior_weights = (w_pose, w_angle, w_shape) (None: ones) or a list of one triple
         per stage (SMPLify's annealing).
 
+        mode: "keras" or "torch" - Adam's two forms - or "lbfgs" / an `Lbfgs(memory, c1, max_ls, tol_grad, lr)` record: per-row
+        L-BFGS with a backtracking line search, one `lbfgs_step` launch per evaluation in `fit_step`'s place (the module's
+        semantics).  Then steps and stage counts are evaluations, the record's lr is the first trial step (lr, beta1, beta2 and
+        eps here are Adam's and ignored), every stage boundary restarts the searches, final_x is the last accepted iterate,
+        and groups or smooth raise ValueError.
+
         group_size = G > 1: rows kG .. kG + G - 1 of labels are views or frames of ONE body (B a multiple of G).  tie: the
         column blocks that are one unknown per group - names among "cam", "global_rot", "pose", "shape", or a (P,) mask of
         0 / 1 (`tie_mask`); the start's tied columns are replaced by their mean over the group (also with init=prediction), so
@@ -1133,7 +1378,7 @@ class ParamFitter(_Fitter):
     def _fit_maps(self, given, ld_weight=None):
         """`fit` on its own arguments by name (`given`), with the weight of the label-distance term that only
         `LabelDistanceFitter.fit` takes."""
-        loop = _fit_args(given)
+        loop = _fit_args(given, lbfgs=True)
         labels, init, generator, silh_labels = (given[k] for k in ("labels", "init", "generator", "silh_labels"))
         sides = self._check_sides(given["pen_weight"], given["keypoints"], given["kp_weight"], ld_weight, labels)
         if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
@@ -1299,7 +1544,7 @@ class ScanFitter(_Fitter):
         grad_scale, graph / graph_steps, check_every, history, prior and prior_weights (one triple or one per stage),
         group_size / tie / smooth for several scans of one body (tie="cam" would tie the placement as well), pen_weight with
         a fitter built with `penetration`."""
-        loop = _fit_args(locals())
+        loop = _fit_args(locals(), lbfgs=True)
         data = self._points(points, counts)
         B, dev = int(data[0].shape[0]), data[0].device
         return self._fit(B, dev, lambda: self.initial(B, init, dev), lambda: data, self._check_sides(pen_weight), **loop)
@@ -1381,7 +1626,7 @@ class KeypointFitter(_Fitter):
         stages = [(steps, column_scale), ...], patience, grad_scale, graph / graph_steps, check_every, history, prior and
         prior_weights (one triple or one per stage), group_size / tie / smooth for several views or frames of one body,
         pen_weight with a fitter built with `penetration`."""
-        loop = _fit_args(locals())
+        loop = _fit_args(locals(), lbfgs=True)
         data = self._data(target, conf)
         B, dev = int(data[0].shape[0]), data[0].device
         return self._fit(B, dev, lambda: self.initial(B, init, dev), lambda: data, self._check_sides(pen_weight), **loop)

@@ -81,6 +81,20 @@ SCHEMAS = {
                        "Tensor? angle_idx, Tensor? angle_scale, Tensor? shape_mean, Tensor? weights, int group_size=1, "
                        "float lr=0.001, float beta1=0.90000000000000002, float beta2=0.999, float eps=9.9999999999999995e-08, "
                        "float gscale=1., float silh_weight=1., int mode=0, int patience=0, int num_cam=4) -> ()"),
+    "lbfgs_step": ("smplraster::lbfgs_step(Tensor(a!) x, Tensor g, Tensor(b!) x0, Tensor(c!) g0, Tensor(d!) d, Tensor(e!) S, "
+                   "Tensor(f!) Y, Tensor(g!) f0, Tensor(h!) gd, Tensor(i!) alpha, Tensor(j!) ls, Tensor(k!) pairs, Tensor(l!) phase, "
+                   "Tensor(m!) t, Tensor(n!) calls, Tensor(o!) stall, Tensor(p!) bad, Tensor(q!) best_step, Tensor(r!) active, "
+                   "Tensor(s!) best_loss, Tensor(t!) best_x, Tensor loss, Tensor? silh_loss, Tensor col_scale, "
+                   "Tensor(u!)? history, float lr=1., float c1=0.0001, int max_ls=10, float tol_grad=0., float gscale=1., "
+                   "float silh_weight=1., int patience=0) -> ()"),
+    "lbfgs_step_prior": ("smplraster::lbfgs_step_prior(Tensor(a!) x, Tensor g, Tensor(b!) x0, Tensor(c!) g0, Tensor(d!) d, "
+                         "Tensor(e!) S, Tensor(f!) Y, Tensor(g!) f0, Tensor(h!) gd, Tensor(i!) alpha, Tensor(j!) ls, "
+                         "Tensor(k!) pairs, Tensor(l!) phase, Tensor(m!) t, Tensor(n!) calls, Tensor(o!) stall, Tensor(p!) bad, "
+                         "Tensor(q!) best_step, Tensor(r!) active, Tensor(s!) best_loss, Tensor(t!) best_x, Tensor loss, "
+                         "Tensor? silh_loss, Tensor col_scale, Tensor(u!)? history, Tensor mean, Tensor factor, Tensor offset, "
+                         "Tensor angle_idx, Tensor angle_scale, Tensor shape_mean, Tensor weights, float lr=1., float c1=0.0001, "
+                         "int max_ls=10, float tol_grad=0., float gscale=1., float silh_weight=1., int patience=0, "
+                         "int num_cam=4) -> ()"),
     "mesh_measures": ("smplraster::mesh_measures(Tensor verts, Tensor faces, Tensor? face_part=None, Tensor? planes=None, "
                       "Tensor? part_mask=None, bool plane_grad=True) -> Tensor[]"),
     "mesh_measures_bwd": ("smplraster::mesh_measures_bwd(Tensor verts, Tensor faces, Tensor vf_off, Tensor vf_face, "

@@ -1,5 +1,6 @@
 """Iterations per second of fitting SMPL parameters to label maps, three loops at the same commit, one GPU:
     python tools/fit_time.py [--batch 128] [--iters 1600] [--rounds 3] [--launches] [--prior K [--angles A]] [--group G [--smooth]] [--loops fitter,graph]
+                             [--optimizer lbfgs [--memory M] [--evaluations]]
 At B = 128, W = 48 (the reference's decoder_loss_debugging.py runs the loop at W = 48), targets = the arg-max part maps
 of seeded parameters, start = those parameters with pose noise and a camera shift:
     stock     the loop a user of the decoder writes with stock torch: the same `SMPLDecoder(loss=...)`, `seg_loss.mean(1)`,
@@ -15,7 +16,14 @@ the rows in groups of G consecutive rows with the shape tied within a group, --s
 group's rows (the fitter's two loops; still one launch per iteration, smplr_fit_step_group; the problem's rows stay the seeded,
 unrelated ones: the figure is a time, not a fit).  --loops picks
 the loops to run.  --launches counts the device kernels per iteration of each loop with torch.profiler in a short run of its own (tracing
-slows the host: no timing is taken from it)."""
+slows the host: no timing is taken from it).
+--optimizer lbfgs [--memory M] adds the fitter's two loops with mode=Lbfgs(memory=M) - "fitter_lbfgs" and "graph_lbfgs", one
+smplr_lbfgs_step launch per evaluation in smplr_fit_step's place - beside Adam's on the same build, and the step kernels' own
+device time (the median over a short traced run, and one launch alone between two events on a state in mid-fit) next to the
+whole iteration's.  With --evaluations it reports instead, for `KeypointFitter`, `ScanFitter` and `ParamFitter` on seeded
+synthetic problems, how many evaluations L-BFGS needs to reach the loss Adam has after its first n = 25, 50, ... --iters
+steps: per row the first evaluation whose loss is at or below Adam's best so far; the median over the rows that get there,
+and how many do (--batch rows; 16 is plenty)."""
 import argparse
 import json
 import os
@@ -108,6 +116,136 @@ def seeded_prior(K, A, seed=0):
                      angle_scale=rng.uniform(-2.0, 2.0, A), shape_mean=rng.normal(0.0, 0.5, 10))
 
 
+def keypoint_problem(B, seed=0):
+    """`KeypointFitter` on the cocoplus joints: targets = the joints' projections at seeded parameters, start = `problem`'s."""
+    from _inputs import make_x
+    from ilps_amd.fitting import KeypointFitter
+    from ilps_amd.smpl_model import synthetic_smpl_model
+    dev = torch.device("cuda:0")
+    fitter = KeypointFitter(synthetic_smpl_model(1234), sigma=3.0, img_wh=48)
+    xs = torch.from_numpy(make_x(B, 48, seed=seed)).to(dev)
+    rng = np.random.default_rng(seed + 1)
+    d = np.zeros((B, 86), np.float32)
+    d[:, 2:4] = 1.5 * rng.choice([-1.0, 1.0], (B, 2))
+    d[:, 4:76] = rng.normal(0.0, 0.05, (B, 72))
+    K = fitter.spec.K
+    with torch.no_grad():
+        _, det, _ = fitter.terms(xs, torch.zeros((B, K, 2), device=dev), torch.ones((B, K), device=dev))
+    return fitter, (det["proj"].clone(), torch.ones((B, K), device=dev)), xs + torch.from_numpy(d).to(dev)
+
+
+def scan_problem(B, N=512, seed=0):
+    """`ScanFitter` over an open triangle soup on the synthetic model's vertices (it carries no faces: consecutive vertices of
+    the part table, three at a time): points sampled from the body at seeded parameters, start = those with pose noise and a
+    shifted placement."""
+    from _inputs import make_x
+    from ilps_amd.fitting import ScanFitter
+    from ilps_amd.render import MeshTopology
+    from ilps_amd.scan import sample_surface
+    from ilps_amd.smpl_model import load_part_tables, synthetic_smpl_model
+    dev = torch.device("cuda:0")
+    ids, _ = load_part_tables(1)
+    faces = np.asarray(ids[:(len(ids) // 3) * 3], np.int32).reshape(-1, 3)
+    fitter = ScanFitter(synthetic_smpl_model(1234), MeshTopology(faces, 6890))
+    x = make_x(B, 48, seed=seed)
+    x[:, :4] = (1.0, 0.0, 0.0, 0.0)
+    xs = torch.from_numpy(x).to(dev)
+    with torch.no_grad():
+        pts, _, _ = sample_surface(fitter.place(xs).cpu(), fitter.topo, N, torch.Generator().manual_seed(seed + 2))
+    rng = np.random.default_rng(seed + 1)
+    d = np.zeros((B, 86), np.float32)
+    d[:, 1:4] = (0.05, -0.04, 0.03)
+    d[:, 4:76] = rng.normal(0.0, 0.05, (B, 72))
+    return fitter, (pts.to(dev).contiguous(),), xs + torch.from_numpy(d).to(dev)
+
+
+def evaluations_to_reach(history, goal):
+    """history (n, B) losses of every evaluation, goal (B,) -> per row the 1-based evaluation whose loss is the first at or
+    below the goal, 0 where none is."""
+    hit = torch.nan_to_num(history, nan=float("inf")) <= goal[None]
+    first = torch.where(hit.any(0), hit.float().argmax(0) + 1, torch.zeros_like(goal, dtype=torch.long))
+    return first.cpu().tolist()
+
+
+def evaluations_report(B, iters, memory):
+    from ilps_amd.fitting import Lbfgs, ParamFitter
+    param = ParamFitter(None, img_wh=48)
+    labels, px0, _ = problem(param, B, 48)
+    kfit, kdata, kx0 = keypoint_problem(B)
+    sfit, sdata, sx0 = scan_problem(B)
+    legs = {"KeypointFitter": (lambda **kw: kfit.fit(*kdata, init=kx0, **kw), dict(lr=2e-2)),
+            "ScanFitter": (lambda **kw: sfit.fit(*sdata, init=sx0, **kw), dict(lr=1e-2)),
+            "ParamFitter": (lambda **kw: param.fit(labels, init=px0, **kw), dict(lr=1e-3))}
+    out = {}
+    for name, (fit, adam_kw) in legs.items():
+        adam = fit(steps=iters, history=True, **adam_kw)
+        lb = fit(steps=iters, history=True, mode=Lbfgs(memory=memory))
+        table = {}
+        n = 25
+        while n <= iters:                                           # Adam's best loss after its first n steps, n = 25, 50, ...
+            goal = adam.history[:n].min(0).values
+            got = sorted(k for k in evaluations_to_reach(lb.history, goal) if k > 0)
+            table[n] = {"adam_mean_loss": float("%.4g" % float(goal.mean())), "rows_reaching": len(got),
+                        "evaluations_median": statistics.median(got) if got else None, "evaluations_max": got[-1] if got else None}
+            n = iters if n < iters < 2 * n else 2 * n
+        out[name] = {"adam": dict(adam_kw, steps=iters), "rows": B,
+                     "mean_loss": {"start": float("%.4g" % float(adam.history[0].mean())), "adam": float("%.4g" % float(adam.loss.mean())),
+                                   "lbfgs": float("%.4g" % float(lb.loss.mean()))},
+                     "after_adams_first_n_steps": table, "lbfgs_rows_stopped": int((~lb.active).sum()),
+                     "lbfgs_accepted_steps_median": statistics.median(lb.state.t.cpu().tolist())}
+    return out
+
+
+def step_alone_us(B, memory, reps=40):
+    """One step launch between two events, on a P = 86 state in mid-fit restored before every launch (L-BFGS: a full memory and
+    an accepted trial, so the launch stores a pair and runs the whole recursion): the median over reps, us.  An upper bound
+    on the kernel's own time: the events add the launch's gaps."""
+    from dataclasses import fields
+    from ilps_amd.fitting import FitState, LbfgsState, fit_step, lbfgs_step
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(0)
+    a = torch.logspace(0, 2, 86, device=dev)
+    x = torch.randn((B, 86), device=dev, generator=gen)
+    fg = lambda x: ((0.5 * (a * x * x).sum(1))[:, None].contiguous(), (a * x).contiguous())
+    lb = LbfgsState.new(x, memory)
+    for _ in range(3 * memory):
+        loss, grad = fg(lb.x)
+        lbfgs_step(lb, grad, loss)
+    ad = FitState.new(x)
+    out = {}
+    for name, st, step in (("lbfgs_step", lb, lbfgs_step), ("fit_step", ad, fit_step)):
+        saved = st.clone()
+        loss, grad = fg(st.x)
+        us = []
+        for _ in range(reps):
+            for f in fields(st):
+                getattr(st, f.name).copy_(getattr(saved, f.name))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            step(st, grad, loss)
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        out[name] = round(statistics.median(us), 2)
+    out["lbfgs_pairs_median"] = statistics.median(lb.pairs.cpu().tolist())
+    return out
+
+
+def step_kernel_us(fn, iters):
+    """Median device time (us) of the step kernels in a traced run of fn(iters): {kernel: us}."""
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn(iters)
+        torch.cuda.synchronize()
+    seen = {}
+    for e in prof.events():
+        for key in ("lbfgs_step_kernel", "fit_step_kernel"):
+            if e.device_type == torch.autograd.DeviceType.CUDA and key in e.name:
+                seen.setdefault(key, []).append(e.device_time)
+    return {k: round(statistics.median(v), 2) for k, v in seen.items()}
+
+
 def wall(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -146,6 +284,9 @@ def main():
     ap.add_argument("--loops", default="stock,fitter,graph")
     ap.add_argument("--group", type=int, default=1, help="rows per group for the fitter's loops: shape tied within a group (1: none)")
     ap.add_argument("--smooth", action="store_true", help="with --group: a first-difference penalty on camera, global rotation and pose")
+    ap.add_argument("--optimizer", default="adam", choices=("adam", "lbfgs"), help="lbfgs: the fitter's loops with mode=Lbfgs too")
+    ap.add_argument("--memory", type=int, default=8, help="pairs of L-BFGS memory per row")
+    ap.add_argument("--evaluations", action="store_true", help="with --optimizer lbfgs: evaluations to reach Adam's loss, three fitters")
     a = ap.parse_args()
     from ilps_amd import _lib
     from ilps_amd.fitting import ParamFitter
@@ -161,7 +302,18 @@ def main():
     loops = {"stock": lambda n: stock_fit(fitter.decoder, labels, x0, n),
              "fitter": lambda n: fitter.fit(labels, init=x0, steps=n, **pkw),
              "graph": lambda n: fitter.fit(labels, init=x0, steps=n, graph=True, graph_steps=G, **pkw)}
-    loops = {k: fn for k, fn in loops.items() if k in a.loops.split(",")}
+    if a.optimizer == "lbfgs":
+        from ilps_amd.fitting import Lbfgs
+        if a.group > 1 or a.smooth:
+            ap.error("--optimizer lbfgs fits every row on its own: no --group, no --smooth")
+        if a.evaluations:
+            print(json.dumps({"build_id": _lib.build_id()[:16], "B": B, "iters": a.iters, "memory": a.memory,
+                              "evaluations_to_adams_loss": evaluations_report(B, a.iters, a.memory)}))
+            return
+        lb = Lbfgs(memory=a.memory)
+        loops["fitter_lbfgs"] = lambda n: fitter.fit(labels, init=x0, steps=n, mode=lb, **pkw)
+        loops["graph_lbfgs"] = lambda n: fitter.fit(labels, init=x0, steps=n, graph=True, graph_steps=G, mode=lb, **pkw)
+    loops = {k: fn for k, fn in loops.items() if k.split("_")[0] in a.loops.split(",")}
     res = {"build_id": _lib.build_id()[:16], "B": B, "W": W, "iters": a.iters, "graph_steps": G, "prior_K": a.prior,
            "prior_A": a.angles if a.prior > 0 else 0, "group": a.group, "smooth": bool(a.smooth)}
     if a.launches:
@@ -180,6 +332,10 @@ def main():
     res["us_per_iteration_rounds"] = {k: [round(v, 1) for v in vs] for k, vs in us.items()}
     res["us_per_iteration"] = {k: round(statistics.median(vs), 1) for k, vs in us.items()}
     res["iterations_per_s"] = {k: round(1e6 / statistics.median(vs)) for k, vs in us.items()}
+    if a.optimizer == "lbfgs":
+        res["memory"] = a.memory
+        res["step_kernel_us"] = {k: step_kernel_us(fn, 4 * G) for k, fn in loops.items() if k.startswith("fitter")}
+        res["step_alone_us"] = step_alone_us(B, a.memory)
     # the three loops on the same problem: mean best loss against the start's (not the same optimiser: stock is torch's Adam)
     if "stock" in loops and "fitter" in loops and not pkw:
         s = stock_fit(fitter.decoder, labels, x0, n)
