@@ -473,6 +473,37 @@ int smplr_affine_warp(const uint8_t *pool, int N, int Hs, int Ws, int C, const f
 int smplr_resize_pad(const uint8_t *data, long long data_bytes, const long long *desc, int N, int C, const void *index,
                      int index_i64, int B, int H, int W, int mode, int flags, float rescale, void *out, void *stream);
 
+/* ---- proxy inputs for synthetic training: a rendered part map + 2D joints -> the encoder's input; DESIGN.md 25,
+ * INTEGRATION.md 4t -----------------------------------------------------------------------------------------------------
+ * One launch writes out (B, C, H, W) fp32, contiguous NCHW, C = C_seg + J: the seg channels of the (corrupted) part map,
+ * then one Gaussian heatmap per joint.
+ *   part    (B, H, W) uint8: 0 background, 1..P parts (smplr_mesh_raster's part output at the input size), P <= 31
+ *   joints  (B, J, 2) fp32 (x, y) in pixels, integer coordinates = pixel centres; NULL iff J = 0
+ *   keep    (B, J) uint8, 0: the joint's channel is all zero; NULL: all kept
+ *   remove  (B) int32, bit p (1 <= p <= 31) set: class p becomes background; bit 0 is ignored; NULL: none
+ *   boxes   (B, NB, 4) int32 (x0, y0, x1, y1), half-open: pixels inside become background; x1 <= x0 or y1 <= y0 is an
+ *           empty box, coordinates outside the image clip; NULL iff NB = 0
+ * Per sample b and pixel (x, y), l = part[b, y, x]: l' = 0 if l > P, or bit l of remove[b] is set, or (x, y) lies in a box
+ * of b; else l' = l.
+ *   seg_mode SMPLR_PROXY_SEG_INDEX       one channel, float(l') * rescale (one fp32 multiply)
+ *            SMPLR_PROXY_SEG_ONEHOT      P + 1 channels, channel c = (l' == c) ? 1 : 0
+ *            SMPLR_PROXY_SEG_SILHOUETTE  one channel, l' > 0
+ *            SMPLR_PROXY_SEG_NONE        no seg channel (needs J >= 1)
+ * Heat channel j, fp32 in this order with no FMA contraction: dx = float(x) - jx, dy = float(y) - jy,
+ * d2 = dx * dx + dy * dy; the value is exp(-(d2 * inv2s2)) if keep[b, j] is set, jx and jy are finite and d2 <= cut2,
+ * else 0.  inv2s2 = 1 / (2 sigma^2) and cut2 = (cut sigma)^2 are formed by the caller.  Boxes and remove do not touch the
+ * heat channels.  Every output element is a function of its own sample alone.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= P <= 31; 0 <= J <= 64; 0 <= NB <= 4; 1 <= H, W <= 4096; inv2s2
+ * and cut2 finite and positive when J > 0; B >= 0 (B = 0 is a no-op); part and out non-null; the launch has
+ * B * ceil(H * W / 1024) workgroups (/ 256 when W % 4 != 0 or out is not 16-byte aligned), fewer than 2^31. */
+#define SMPLR_PROXY_SEG_INDEX 0
+#define SMPLR_PROXY_SEG_ONEHOT 1
+#define SMPLR_PROXY_SEG_SILHOUETTE 2
+#define SMPLR_PROXY_SEG_NONE 3
+int smplr_proxy_inputs(const uint8_t *part, const float *joints, const uint8_t *keep, const int32_t *remove,
+                       const int32_t *boxes, int B, int H, int W, int J, int NB, int P, int seg_mode, float rescale,
+                       float inv2s2, float cut2, float *out, void *stream);
+
 /* ---- 3D evaluation: per-vertex error, MPJPE, scale-corrected and Procrustes-aligned error (the figures evaluate3d.py:32-65
  * stops short of: it reports a mean squared error over 69 pose parameters); INTEGRATION.md 4f -------------------------
  * pred, gt (B, N, 3) fp32, contiguous: two point sets per mesh (vertices, or joints), in metres.  One launch computes each

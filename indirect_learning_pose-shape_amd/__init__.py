@@ -27,4 +27,7 @@ def __getattr__(name):
     if name in ("RaggedImages", "EvalBatches", "load_images", "load_labels", "pad_geometry"):
         from . import preprocess
         return getattr(preprocess, name)
+    if name in ("SyntheticBatches", "BodySampler", "proxy_inputs", "corruption_draws", "frame_cameras"):
+        from . import synthetic
+        return getattr(synthetic, name)
     raise AttributeError(name)

@@ -647,6 +647,63 @@ void affine_warp_meta(const Tensor &pool, const Tensor &matrices, const c10::opt
   affine_warp_check(pool, matrices, index, out, mode);
 }
 
+// ---- proxy inputs (synthetic.py): part (B, H, W) uint8 + joints (B, J, 2) -> out (B, C, H, W) fp32, in place ---------------
+// C = seg channels (1, P + 1, 1 or 0 by seg_mode) + J; keep (B, J) uint8, remove (B) int32, boxes (B, NB, 4) int32 optional.
+struct ProxyDims { int64_t B, H, W, J, NB; };
+ProxyDims proxy_inputs_check(const Tensor &part, const c10::optional<Tensor> &joints, const c10::optional<Tensor> &keep,
+                             const c10::optional<Tensor> &remove, const c10::optional<Tensor> &boxes, const Tensor &out,
+                             int64_t P, int64_t seg_mode) {
+  TORCH_CHECK(part.dim() == 3 && part.scalar_type() == at::kByte, "part must be (B, H, W) uint8");
+  const int64_t B = part.size(0), H = part.size(1), W = part.size(2);
+  TORCH_CHECK(B <= INT32_MAX && H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "H and W of part must be in 1..4096");
+  TORCH_CHECK(P >= 1 && P <= 31, "num_parts must be in 1..31");
+  TORCH_CHECK(seg_mode >= 0 && seg_mode <= 3, "seg_mode must be 0 (index), 1 (onehot), 2 (silhouette) or 3 (none)");
+  const int64_t J = joints ? joints->size(joints->dim() > 1 ? 1 : 0) : 0;
+  TORCH_CHECK(!joints || (joints->dim() == 3 && joints->size(0) == B && joints->size(2) == 2 && joints->scalar_type() == at::kFloat),
+              "joints must be (B, J, 2) float32 with B = part.size(0) = ", B);
+  TORCH_CHECK(J <= 64, "at most 64 joints");
+  TORCH_CHECK(seg_mode != 3 || J >= 1, "seg_mode 3 (none) needs joints");
+  TORCH_CHECK(!keep || (keep->dim() == 2 && keep->size(0) == B && keep->size(1) == J && keep->scalar_type() == at::kByte),
+              "keep must be (B, J) uint8");
+  TORCH_CHECK(!remove || (remove->dim() == 1 && remove->size(0) == B && remove->scalar_type() == at::kInt),
+              "remove must be (B,) int32");
+  const int64_t NB = boxes ? boxes->size(boxes->dim() > 1 ? 1 : 0) : 0;
+  TORCH_CHECK(!boxes || (boxes->dim() == 3 && boxes->size(0) == B && boxes->size(2) == 4 && boxes->scalar_type() == at::kInt),
+              "boxes must be (B, NB, 4) int32");
+  TORCH_CHECK(NB <= 4, "at most 4 boxes per sample");
+  const int64_t C = (seg_mode == 1 ? P + 1 : (seg_mode == 3 ? 0 : 1)) + J;
+  TORCH_CHECK(out.dim() == 4 && out.size(0) == B && out.size(1) == C && out.size(2) == H && out.size(3) == W &&
+                  out.scalar_type() == at::kFloat,
+              "out must be (B, C, H, W) float32 with C = ", C);
+  return {B, H, W, J, NB};
+}
+void proxy_inputs(const Tensor &part, const c10::optional<Tensor> &joints, const c10::optional<Tensor> &keep,
+                  const c10::optional<Tensor> &remove, const c10::optional<Tensor> &boxes, Tensor &out, int64_t P,
+                  int64_t seg_mode, double rescale, double inv2s2, double cut2) {
+  const ProxyDims d = proxy_inputs_check(part, joints, keep, remove, boxes, out, P, seg_mode);
+  dev_typed(out, at::kFloat, "out");
+  dev_typed(part, at::kByte, "part");
+  if (joints) dev_f32(*joints, "joints");
+  if (keep) dev_typed(*keep, at::kByte, "keep");
+  if (remove) dev_typed(*remove, at::kInt, "remove");
+  if (boxes) dev_typed(*boxes, at::kInt, "boxes");
+  const Tensor none;
+  same_device(out, {{"part", &part}, {"joints", joints ? &*joints : &none}, {"keep", keep ? &*keep : &none},
+                    {"remove", remove ? &*remove : &none}, {"boxes", boxes ? &*boxes : &none}});
+  DeviceGuard g(out.device());
+  if (d.B == 0) return;
+  ok(smplr_proxy_inputs(part.data_ptr<uint8_t>(), d.J ? joints->data_ptr<float>() : nullptr,
+                        d.J && keep ? keep->data_ptr<uint8_t>() : nullptr, remove ? remove->data_ptr<int32_t>() : nullptr,
+                        d.NB ? boxes->data_ptr<int32_t>() : nullptr, (int)d.B, (int)d.H, (int)d.W, (int)d.J, (int)d.NB, (int)P,
+                        (int)seg_mode, (float)rescale, (float)inv2s2, (float)cut2, out.data_ptr<float>(), cur_stream()),
+     "smplr_proxy_inputs");
+}
+void proxy_inputs_meta(const Tensor &part, const c10::optional<Tensor> &joints, const c10::optional<Tensor> &keep,
+                       const c10::optional<Tensor> &remove, const c10::optional<Tensor> &boxes, Tensor &out, int64_t P,
+                       int64_t seg_mode, double, double, double) {
+  proxy_inputs_check(part, joints, keep, remove, boxes, out, P, seg_mode);
+}
+
 // ---- input preprocessing (predict.py:17-25, evaluate.py:13-19,96-100): data (bytes) uint8 + desc (N, 4) int64 -> out, in place --
 // mode 0 / 1: images, bilinear / nearest, out (B, C, H, W) fp32; mode 2 / 3: labels / labels > 0, out (B, H, W) int32.
 // flags: 1 pad, 2 swap_rb, 4 quantize, 8 pil rule.  desc rows (byte offset, pitch, h, w) and the VALUES of index are
@@ -1430,6 +1487,8 @@ TORCH_LIBRARY(smplraster, m) {
   m.def("affine_warp(Tensor pool, Tensor matrices, Tensor? index, Tensor(a!) out, int mode=0, float rescale=1.0) -> ()");
   m.def("resize_pad(Tensor data, Tensor desc, Tensor? index, Tensor(a!) out, int channels, int mode=0, int flags=4, "
         "float rescale=1.0) -> ()");
+  m.def("proxy_inputs(Tensor part, Tensor? joints, Tensor? keep, Tensor? remove, Tensor? boxes, Tensor(a!) out, "
+        "int num_parts, int seg_mode, float rescale, float inv2s2, float cut2) -> ()");
   m.def("point_errors(Tensor pred, Tensor gt, int root=-1, int per_point_mode=-1, bool transform=False) -> "
         "(Tensor, Tensor, Tensor, Tensor)");
   m.def("seg_colour(Tensor input, Tensor lut, Tensor? background, int H, int W, int alpha_q=256, int bad_colour=0) -> Tensor");
@@ -1491,6 +1550,7 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("mesh_render", &mesh_render);
   m.impl("affine_warp", &affine_warp);
   m.impl("resize_pad", &resize_pad);
+  m.impl("proxy_inputs", &proxy_inputs);
   m.impl("point_errors", &point_errors);
   m.impl("seg_colour", &seg_colour);
   m.impl("scatter_points", &scatter_points);
@@ -1524,6 +1584,7 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("mesh_render", &mesh_render_meta);
   m.impl("affine_warp", &affine_warp_meta);
   m.impl("resize_pad", &resize_pad_meta);
+  m.impl("proxy_inputs", &proxy_inputs_meta);
   m.impl("point_errors", &point_errors_meta);
   m.impl("seg_colour", &seg_colour_meta);
   m.impl("scatter_points", &scatter_points_meta);

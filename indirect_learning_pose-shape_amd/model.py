@@ -82,13 +82,16 @@ class _Bottleneck(nn.Module):
 
 
 class ENetEncoder(nn.Module):
-    """`build_enet` (encoder_enet_simple.py:83-104): (N,3,256,256) -> (N,128,32,32)."""
+    """`build_enet` (encoder_enet_simple.py:83-104): (N,3,256,256) -> (N,128,32,32).  in_channels: the input's
+    channels C; the initial block concatenates its 13 filters with the pooled input, 13 + C channels (16 for images,
+    14 for the autoencoder's part map, as Keras builds it)."""
 
-    def __init__(self, dropout_rate=0.01):
+    def __init__(self, dropout_rate=0.01, in_channels=3):
         super().__init__()
-        self.init_conv = nn.Conv2d(3, 13, 3, stride=2, padding=1)            # initial block (:10-14)
-        self.init_bn, self.init_act = _bn(16, 0.1), PReLU(16)
-        blocks = [_Bottleneck(16, 64, downsample=True, dropout_rate=dropout_rate)]
+        c0 = 13 + int(in_channels)
+        self.init_conv = nn.Conv2d(int(in_channels), 13, 3, stride=2, padding=1)   # initial block (:10-14)
+        self.init_bn, self.init_act = _bn(c0, 0.1), PReLU(c0)
+        blocks = [_Bottleneck(c0, 64, downsample=True, dropout_rate=dropout_rate)]
         blocks += [_Bottleneck(64, 64, dropout_rate=dropout_rate) for _ in range(4)]
         blocks += [_Bottleneck(64, 128, downsample=True)]
         for _ in range(2):
@@ -110,9 +113,9 @@ class ENetEncoder(nn.Module):
 class _ENetBackbone(nn.Module):
     """ENet + the three conv/BN/pool stages of model.py:38-54 -> (N, 2048)."""
 
-    def __init__(self):
+    def __init__(self, in_channels=3):
         super().__init__()
-        self.enet = ENetEncoder()
+        self.enet = ENetEncoder(in_channels=in_channels)
 
         def stage(cin, cout, pool):
             return nn.Sequential(nn.Conv2d(cin, cout, 3, padding=1), nn.ReLU(inplace=True), _bn(cout),
@@ -142,9 +145,9 @@ class _ResNet50Backbone(nn.Module):
     """keras.applications.resnet50.ResNet50(include_top=False, weights=None) of Keras 2.1 (7x7 average
     pool kept) followed by Reshape((2048,)) (model.py:56-60)."""
 
-    def __init__(self):
+    def __init__(self, in_channels=3):
         super().__init__()
-        self.stem = nn.Sequential(nn.Conv2d(3, 64, 7, 2, 3), _bn(64), nn.ReLU(inplace=True), nn.MaxPool2d(3, 2, 1))
+        self.stem = nn.Sequential(nn.Conv2d(int(in_channels), 64, 7, 2, 3), _bn(64), nn.ReLU(inplace=True), nn.MaxPool2d(3, 2, 1))
         layers, cin = [], 64
         for mid, n, stride in ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2)):
             for i in range(n):
@@ -163,14 +166,19 @@ class SMPLRegressor(nn.Module):
     """Backbone + regression module (model.py:36-105): images -> final_param (N, 86).
 
     This is the reference's `smpl_model` (the only part with trainable weights, train.py:302-315).
+    in_channels: 3 for images, 1 for the autoencoders' part map (train_autoencoder.py), any C for the proxy inputs of
+    `synthetic.SyntheticBatches`; with the default, names and shapes of the parameters are unchanged.
     """
 
-    def __init__(self, output_wh, encoder_architecture="resnet50", use_IEF=False, scaledown=0.005):
+    def __init__(self, output_wh, encoder_architecture="resnet50", use_IEF=False, scaledown=0.005, in_channels=3):
         super().__init__()
+        self.in_channels = int(in_channels)
+        if self.in_channels < 1:
+            raise ValueError("in_channels must be positive")
         if encoder_architecture == "enet":
-            self.backbone = _ENetBackbone()
+            self.backbone = _ENetBackbone(self.in_channels)
         elif encoder_architecture == "resnet50":
-            self.backbone = _ResNet50Backbone()
+            self.backbone = _ResNet50Backbone(self.in_channels)
         else:
             raise ValueError("encoder_architecture must be 'enet' or 'resnet50' (model.py:38,56)")
         self.output_wh, self.use_IEF, self.scaledown = output_wh, bool(use_IEF), float(scaledown)
@@ -183,7 +191,7 @@ class SMPLRegressor(nn.Module):
                                      nn.Linear(2048, 1024), nn.ReLU(inplace=True), nn.Linear(1024, 86))
 
     def forward(self, images):
-        if images.dim() == 4 and images.shape[1] != 3 and images.shape[3] == 3:
+        if images.dim() == 4 and images.shape[1] != self.in_channels and images.shape[3] == self.in_channels:
             images = images.permute(0, 3, 1, 2)               # NHWC (Keras) -> NCHW
         feats = self.backbone(images.contiguous())
         if not self.use_IEF:
@@ -228,12 +236,15 @@ class FullModel(nn.Module):
 
 
 def build_model(train_batch_size, input_shape, smpl_path, output_wh, num_classes,
-                encoder_architecture="resnet50", use_IEF=False, vertex_sampling=None, scaledown=0.005):
+                encoder_architecture="resnet50", use_IEF=False, vertex_sampling=None, scaledown=0.005, in_channels=None):
     """`build_model`, model.py:16-129.  Returns (segs_model, smpl_model, verts_model, projects_model);
-    the four share one encoder/regressor and one decoder, as the Keras models share one graph."""
+    the four share one encoder/regressor and one decoder, as the Keras models share one graph.
+    in_channels: the encoder's input channels; default `input_shape[-1]`, the reference's (H, W, C)."""
     if num_classes != 32:
         raise ValueError("the decoder produces 32 classes (31 parts + background)")
-    smpl_model = SMPLRegressor(output_wh, encoder_architecture, use_IEF, scaledown)
+    if in_channels is None:
+        in_channels = int(input_shape[-1])
+    smpl_model = SMPLRegressor(output_wh, encoder_architecture, use_IEF, scaledown, in_channels)
     decoder = SMPLDecoder(smpl_path, img_wh=output_wh, vertex_sampling=vertex_sampling)
     return (FullModel(smpl_model, decoder, "segs"), smpl_model, FullModel(smpl_model, decoder, "verts"),
             FullModel(smpl_model, decoder, "projects"))

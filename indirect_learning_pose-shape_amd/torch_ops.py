@@ -52,6 +52,8 @@ SCHEMAS = {
                     "float rescale=1.) -> ()"),
     "resize_pad": ("smplraster::resize_pad(Tensor data, Tensor desc, Tensor? index, Tensor(a!) out, int channels, "
                    "int mode=0, int flags=4, float rescale=1.) -> ()"),
+    "proxy_inputs": ("smplraster::proxy_inputs(Tensor part, Tensor? joints, Tensor? keep, Tensor? remove, Tensor? boxes, "
+                     "Tensor(a!) out, int num_parts, int seg_mode, float rescale, float inv2s2, float cut2) -> ()"),
     "point_errors": ("smplraster::point_errors(Tensor pred, Tensor gt, int root=-1, int per_point_mode=-1, "
                      "bool transform=False) -> (Tensor, Tensor, Tensor, Tensor)"),
     "seg_colour": ("smplraster::seg_colour(Tensor input, Tensor lut, Tensor? background, int H, int W, int alpha_q=256, "

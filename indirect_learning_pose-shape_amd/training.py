@@ -68,7 +68,7 @@ class SegTrainer:
 
     def __init__(self, smpl_path=None, input_wh=256, output_wh=48, encoder_architecture="enet", use_IEF=True,
                  weight_classes=True, gamma=2.0, lr=1e-4, device=None, ddp=False, bucket_mb=25,
-                 with_silhouette=False, silh_wh=None, fused_loss=True, fused_silh_loss=False, amp=None):
+                 with_silhouette=False, silh_wh=None, fused_loss=True, fused_silh_loss=False, amp=None, in_channels=3):
         amp_dtype(amp)                                                # (ValueError before anything is built)
         if amp is not None and os.environ.get("SMPLR_ENCODER_LAYOUT", "").lower() == "channels_last":
             # that layout runs torch's own BatchNorm2d (the package's kernels read NCHW planes), and torch 2.10 / ROCm 7.0's
@@ -82,7 +82,8 @@ class SegTrainer:
         if self.device.type == "cuda" and os.environ.get("SMPLR_CONV_BACKEND", "default") == "find":
             configure_conv_backend()
         self.output_wh = output_wh
-        self.smpl_model = SMPLRegressor(output_wh, encoder_architecture, use_IEF).to(self.device)
+        self.in_channels = int(in_channels)                           # (3: images; synthetic.SyntheticBatches.in_channels)
+        self.smpl_model = SMPLRegressor(output_wh, encoder_architecture, use_IEF, in_channels=self.in_channels).to(self.device)
         # OPT-IN (`SMPLR_ENCODER_LAYOUT=channels_last`): the encoder's weights and activations in NHWC, the layout
         # MIOpen's implicit-GEMM convolution solvers work in (the default NCHW tensors are transposed around them:
         # `batched_transpose_32x32_dword` in the train step's kernel trace).  The package's fused batch-norm / PReLU
@@ -120,7 +121,7 @@ class SegTrainer:
         self.opt = torch.optim.Adam(self.smpl_model.parameters(), lr=lr)       # train.py:179
 
     def step(self, images, labels, silh_labels=None, metrics=None, _marks=None):
-        """images (N,3,H,W) or (N,H,W,3); labels (N,W,W) integer class map or (N,W*W,32) one-hot, or None for the
+        """images (N,C,H,W) or (N,H,W,C), C = in_channels (3 by default); labels (N,W,W) integer class map or (N,W*W,32) one-hot, or None for the
         silhouette-only step of the alternating schedule (then silh_labels is required).
         metrics: Keras' metrics=['accuracy'] (train.py:207-215, train_stage2_silhouette.py:228-234) - a
         `metrics.SegConfusion(32, device)` for the seg head, or a pair (seg, silhouette) of which either may be None,
@@ -132,7 +133,7 @@ class SegTrainer:
         mark = (lambda k: None) if _marks is None else _marks
         mark("start")
         self.opt.zero_grad(set_to_none=True)
-        if self.channels_last and images.dim() == 4 and images.shape[1] == 3:
+        if self.channels_last and images.dim() == 4 and images.shape[1] == self.in_channels:
             images = images.contiguous(memory_format=torch.channels_last)
         param = regress(self.net, images, self.amp)
         mark("encoder_fwd")
