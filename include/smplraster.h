@@ -665,6 +665,45 @@ int smplr_kp_bwd(const float *cam, const int32_t *t_off, const int32_t *t_joint,
                  const int32_t *status, const double *ws, const float *g, int B, int V, int K, int nnz, float sigma,
                  float *dverts, float *djtr, float *dcam, void *stream);
 
+/* ---- supervised 3D losses: vertices, sparse 3D joints, pose as rotation matrices, shape, camera, with gradients (beyond the
+ * reference); INTEGRATION.md 4u ---------------------------------------------------------------------------------------------
+ * Row b: x, x_t (B rows of x_stride floats) = predicted and true parameters in the decoder's layout, cam (num_cam), theta (72),
+ * beta (10); verts, verts_t (B, V, 3); jtr, jtr_t (B, 24, 3), or both NULL.  The joints are the CSR of smplr_kp_fwd (off (K + 1),
+ * idx (nnz), w (nnz)) over S = V or V + 24 sources, with the same trust and skip rules; smplr_sup_bwd takes its transpose
+ * (t_off (S + 1), t_joint, t_w).  K = 0 turns term 1 off.  root in -1 .. K - 1: with root >= 0 both joint sets are taken
+ * relative to their own joint root.  row_w (B, 5) or NULL (ones): term t of row b counts iff row_w[b, t] > 0 (a NaN does not);
+ * a term that does not count is 0 and gives no gradient whatever its targets hold.  cam_scale (num_cam).
+ *   terms[b, 0] = w_0 / V sum_i |v_i - v*_i|^2
+ *   terms[b, 1] = w_1 / K sum_k |d_k - d_root|^2, d_k = sum over row k of w (source - source*) (d_root = 0 with root < 0)
+ *   terms[b, 2] = w_2 / 24 sum_j |R(theta_j) - R(theta*_j)|_F^2; R(t): a = |t + 1e-8|, r = t / a,
+ *                 R = cos a I + (1 - cos a) r r^T + sin a [r]x, both sides in fp64
+ *   terms[b, 3] = w_3 / 10 sum (beta - beta*)^2
+ *   terms[b, 4] = w_4 / num_cam sum_c (cam_scale_c (x_c - x*_c))^2 (0 with num_cam = 0)
+ * smplr_sup_fwd writes terms (B, 5), status (B) and ws (B, SMPLR_SUP_WS_DOUBLES) fp64 = the joint residuals d_k - d_root
+ *   (64, 3) and the rotation differences (24, 9), which smplr_sup_bwd reads.  One launch of B workgroups of 1024 lanes.
+ * smplr_sup_bwd, g (B, 5) the cotangent of terms: dverts (B, V, 3) = g_0 w_0 2 / V (v - v*) + sum_k w_ki dd_k in increasing k,
+ *   dd_k = g_1 w_1 2 / K (d_k - d_root), the root's dd the negative sum of the others; djtr (B, 24, 3) or NULL likewise for the
+ *   joint sources (not NULL only with a CSR over V + 24 sources); dx (B rows of x_stride floats): the theta columns from term 2
+ *   (the analytic derivative of R), beta from term 3, cam from term 4.  Every element of dverts, djtr and dx is written, exact
+ *   zeros where nothing contributes.  One launch of ceil(V / 1024) x B workgroups.
+ * All products and sums are fp64 on the fp32 operands in an order V, K and the CSR fix; each output is rounded to fp32 once; no
+ * atomics: a row's results are the same bits on every launch and in any batch.
+ * status: SMPLR_SUP_NONFINITE when an operand of a counted term of the row is NaN / Inf (term 1: a coordinate of a source that a
+ *   joint uses; a weight > 0 that is infinite) - the row's terms, dverts, djtr and dx are NaN; other rows are not affected.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= V <= 2^24, 0 <= K <= 64, 0 <= nnz <= 2^24, num_cam in 0 .. 8,
+ * x_stride >= num_cam + 82, -1 <= root < K, B >= 0 (B = 0 is a no-op; smplr_sup_bwd: B <= 65535); no null pointer except jtr,
+ * jtr_t, djtr, row_w (and off, idx, w, t_off, t_joint, t_w with nnz = 0, cam_scale with num_cam = 0).                         */
+#define SMPLR_SUP_NONFINITE 1
+#define SMPLR_SUP_WS_DOUBLES 408
+int smplr_sup_fwd(const float *x, const float *x_t, int x_stride, const float *verts, const float *verts_t, const float *jtr,
+                  const float *jtr_t, const int32_t *off, const int32_t *idx, const float *w, int root, const float *row_w,
+                  const float *cam_scale, int B, int V, int K, int nnz, int num_cam, float *terms, int32_t *status, double *ws,
+                  void *stream);
+int smplr_sup_bwd(const float *x, const float *x_t, int x_stride, const float *verts, const float *verts_t, const int32_t *t_off,
+                  const int32_t *t_joint, const float *t_w, int root, const float *row_w, const float *cam_scale,
+                  const int32_t *status, const double *ws, const float *g, int B, int V, int K, int nnz, int num_cam,
+                  float *dverts, float *djtr, float *dx, void *stream);
+
 /* ---- label-map distance term: projected vertices against an integer label map, both directions, by class, with gradients
  * (beyond the reference); INTEGRATION.md 4r ---------------------------------------------------------------------------------
  * verts (B, V, 3) fp32, cam (B, 4) = (k_u, k_v, u0, v0), labels (B, W, W) int32: stored pixel q = r W + c sits at the point

@@ -1461,6 +1461,127 @@ std::string build_tag() { return SMPLR_TORCH_OPS_ID; }
 
 }  // namespace
 
+// ---- supervised 3D losses (include/smplraster.h): x, x_t (B, C >= num_cam + 82) contiguous (C is the row
+// stride), verts, verts_t (B, V, 3), jtr, jtr_t (B, 24, 3) or None, the joints' CSR (off (K + 1), idx, w) or None (K = 0),
+// row_w (B, 5) or None, cam_scale (num_cam) -> terms (B, 5), status (B) int32, ws (B, 408) fp64; the backward takes the
+// transposed CSR, g (B, 5) and returns dverts (B, V, 3), djtr (B, 24, 3) (empty without with_jtr) and dx (B, C) ------------------
+struct SupDims { int64_t B, C, V, K, nnz; };
+SupDims sup_check(const Tensor &x, const Tensor &x_t, const Tensor &verts, const Tensor &verts_t, const c10::optional<Tensor> &row_w,
+                  const c10::optional<Tensor> &cam_scale, int64_t K, int64_t nnz, int64_t root, int64_t num_cam) {
+  TORCH_CHECK(verts.dim() == 3 && verts.size(2) == 3 && verts.scalar_type() == at::kFloat, "verts must be (B, V, 3) float32");
+  TORCH_CHECK(verts_t.sizes() == verts.sizes() && verts_t.scalar_type() == at::kFloat, "verts_t must match verts");
+  SupDims d{verts.size(0), x.dim() == 2 ? x.size(1) : 0, verts.size(1), K, nnz};
+  TORCH_CHECK(num_cam >= 0 && num_cam <= 8, "num_cam = ", num_cam, " must lie in 0 .. 8");
+  TORCH_CHECK(x.dim() == 2 && x.size(0) == d.B && d.C >= num_cam + 82 && x.scalar_type() == at::kFloat,
+              "x must be (B, >= num_cam + 82) float32");
+  TORCH_CHECK(x_t.sizes() == x.sizes() && x_t.scalar_type() == at::kFloat, "x_t must match x");
+  TORCH_CHECK(d.V >= 1 && d.V <= (1 << 24) && K >= 0 && K <= 64 && nnz >= 0 && nnz <= (1 << 24),
+              "1 <= V <= 2^24, 0 <= K <= 64, 0 <= nnz <= 2^24 (V = ", d.V, ", K = ", K, ", nnz = ", nnz, ")");
+  TORCH_CHECK(root >= -1 && root < K, "root = ", root, " must lie in -1 .. K - 1");
+  if (row_w) TORCH_CHECK(row_w->dim() == 2 && row_w->size(0) == d.B && row_w->size(1) == 5, "row_w must be (B, 5)");
+  TORCH_CHECK(num_cam == 0 || (cam_scale && cam_scale->numel() == num_cam), "cam_scale must hold num_cam numbers");
+  return d;
+}
+void sup_on_device(const Tensor &x, const Tensor &x_t, const Tensor &verts, const Tensor &verts_t,
+                   const c10::optional<Tensor> &row_w, const c10::optional<Tensor> &cam_scale) {
+  dev_f32(verts, "verts"); dev_f32(verts_t, "verts_t"); dev_f32(x, "x"); dev_f32(x_t, "x_t");
+  same_device(verts, {{"verts_t", &verts_t}, {"x", &x}, {"x_t", &x_t}});
+  if (row_w) { dev_f32(*row_w, "row_w"); same_device(verts, {{"row_w", &*row_w}}); }
+  if (cam_scale) { dev_f32(*cam_scale, "cam_scale"); same_device(verts, {{"cam_scale", &*cam_scale}}); }
+}
+void sup_csr(const Tensor &verts, const c10::optional<Tensor> &off, const c10::optional<Tensor> &idx, const c10::optional<Tensor> &w,
+             int64_t rows, int64_t nnz, const char *what) {
+  if (nnz == 0) return;
+  TORCH_CHECK(off && idx && w && off->numel() == rows + 1 && w->numel() == nnz, what, ": offsets (rows + 1), indices and weights (nnz)");
+  dev_typed(*off, at::kInt, what); dev_typed(*idx, at::kInt, what); dev_f32(*w, what);
+  same_device(verts, {{what, &*off}, {what, &*idx}, {what, &*w}});
+}
+void sup_jtr(const Tensor &verts, const c10::optional<Tensor> &jtr, const char *name) {
+  if (!jtr) return;
+  dev_f32(*jtr, name);
+  TORCH_CHECK(jtr->dim() == 3 && jtr->size(0) == verts.size(0) && jtr->size(1) == 24 && jtr->size(2) == 3, name, " must be (B, 24, 3)");
+  same_device(verts, {{name, &*jtr}});
+}
+std::tuple<Tensor, Tensor, Tensor> sup_fwd(const Tensor &x, const Tensor &x_t, const Tensor &verts, const Tensor &verts_t,
+                                           const c10::optional<Tensor> &jtr, const c10::optional<Tensor> &jtr_t,
+                                           const c10::optional<Tensor> &off, const c10::optional<Tensor> &idx,
+                                           const c10::optional<Tensor> &w, int64_t K, int64_t root,
+                                           const c10::optional<Tensor> &row_w, const c10::optional<Tensor> &cam_scale,
+                                           int64_t num_cam) {
+  const int64_t nnz = idx ? idx->numel() : 0;
+  const SupDims d = sup_check(x, x_t, verts, verts_t, row_w, cam_scale, K, nnz, root, num_cam);
+  TORCH_CHECK(jtr.has_value() == jtr_t.has_value(), "jtr and jtr_t go together");
+  sup_on_device(x, x_t, verts, verts_t, row_w, cam_scale);
+  sup_jtr(verts, jtr, "jtr"); sup_jtr(verts, jtr_t, "jtr_t");
+  sup_csr(verts, off, idx, w, K, nnz, "the joints' CSR");
+  DeviceGuard guard(verts.device());
+  Tensor terms = f32({d.B, 5}, verts), status = at::empty({d.B}, verts.options().dtype(at::kInt));
+  Tensor ws = at::empty({d.B, SMPLR_SUP_WS_DOUBLES}, verts.options().dtype(at::kDouble));
+  if (d.B == 0) return {terms, status, ws};
+  ok(smplr_sup_fwd(x.data_ptr<float>(), x_t.data_ptr<float>(), (int)d.C, verts.data_ptr<float>(), verts_t.data_ptr<float>(),
+                   static_cast<const float *>(opt_ptr(jtr)), static_cast<const float *>(opt_ptr(jtr_t)),
+                   nnz ? off->data_ptr<int32_t>() : nullptr, nnz ? idx->data_ptr<int32_t>() : nullptr,
+                   nnz ? w->data_ptr<float>() : nullptr, (int)root, static_cast<const float *>(opt_ptr(row_w)),
+                   static_cast<const float *>(opt_ptr(cam_scale)), (int)d.B, (int)d.V, (int)K, (int)nnz, (int)num_cam,
+                   terms.data_ptr<float>(), status.data_ptr<int32_t>(), ws.data_ptr<double>(), cur_stream()),
+     "smplr_sup_fwd");
+  return {terms, status, ws};
+}
+std::tuple<Tensor, Tensor, Tensor> sup_fwd_meta(const Tensor &x, const Tensor &x_t, const Tensor &verts, const Tensor &verts_t,
+                                                const c10::optional<Tensor> &, const c10::optional<Tensor> &,
+                                                const c10::optional<Tensor> &, const c10::optional<Tensor> &idx,
+                                                const c10::optional<Tensor> &, int64_t K, int64_t root,
+                                                const c10::optional<Tensor> &row_w, const c10::optional<Tensor> &cam_scale,
+                                                int64_t num_cam) {
+  const SupDims d = sup_check(x, x_t, verts, verts_t, row_w, cam_scale, K, idx ? idx->numel() : 0, root, num_cam);
+  return {at::empty({d.B, 5}, verts.options()), at::empty({d.B}, verts.options().dtype(at::kInt)),
+          at::empty({d.B, SMPLR_SUP_WS_DOUBLES}, verts.options().dtype(at::kDouble))};
+}
+SupDims sup_bwd_check(const Tensor &x, const Tensor &x_t, const Tensor &verts, const Tensor &verts_t,
+                      const c10::optional<Tensor> &t_joint, int64_t K, int64_t root, const c10::optional<Tensor> &row_w,
+                      const c10::optional<Tensor> &cam_scale, const Tensor &status, const Tensor &ws, const Tensor &g,
+                      int64_t num_cam) {
+  const SupDims d = sup_check(x, x_t, verts, verts_t, row_w, cam_scale, K, t_joint ? t_joint->numel() : 0, root, num_cam);
+  TORCH_CHECK(g.dim() == 2 && g.size(0) == d.B && g.size(1) == 5 && g.scalar_type() == at::kFloat, "g must be (B, 5) float32");
+  TORCH_CHECK(status.numel() == d.B && status.scalar_type() == at::kInt, "status must be (B) int32");
+  TORCH_CHECK(ws.numel() == d.B * SMPLR_SUP_WS_DOUBLES && ws.scalar_type() == at::kDouble, "ws must be (B, 408) float64");
+  TORCH_CHECK(d.B <= 65535, "at most 65535 rows");
+  return d;
+}
+std::tuple<Tensor, Tensor, Tensor> sup_bwd(const Tensor &x, const Tensor &x_t, const Tensor &verts, const Tensor &verts_t,
+                                           const c10::optional<Tensor> &t_off, const c10::optional<Tensor> &t_joint,
+                                           const c10::optional<Tensor> &t_w, int64_t K, int64_t root,
+                                           const c10::optional<Tensor> &row_w, const c10::optional<Tensor> &cam_scale,
+                                           const Tensor &status, const Tensor &ws, const Tensor &g, bool with_jtr,
+                                           int64_t num_cam) {
+  const SupDims d = sup_bwd_check(x, x_t, verts, verts_t, t_joint, K, root, row_w, cam_scale, status, ws, g, num_cam);
+  sup_on_device(x, x_t, verts, verts_t, row_w, cam_scale);
+  dev_f32(g, "g"); dev_typed(status, at::kInt, "status"); dev_typed(ws, at::kDouble, "ws");
+  same_device(verts, {{"g", &g}, {"status", &status}, {"ws", &ws}});
+  sup_csr(verts, t_off, t_joint, t_w, d.V + (with_jtr ? 24 : 0), d.nnz, "the transposed CSR");
+  DeviceGuard guard(verts.device());
+  Tensor dverts = f32({d.B, d.V, 3}, verts), djtr = f32({with_jtr ? d.B : 0, 24, 3}, verts), dx = f32({d.B, d.C}, verts);
+  if (d.B == 0) return {dverts, djtr, dx};
+  ok(smplr_sup_bwd(x.data_ptr<float>(), x_t.data_ptr<float>(), (int)d.C, verts.data_ptr<float>(), verts_t.data_ptr<float>(),
+                   d.nnz ? t_off->data_ptr<int32_t>() : nullptr, d.nnz ? t_joint->data_ptr<int32_t>() : nullptr,
+                   d.nnz ? t_w->data_ptr<float>() : nullptr, (int)root, static_cast<const float *>(opt_ptr(row_w)),
+                   static_cast<const float *>(opt_ptr(cam_scale)), status.data_ptr<int32_t>(), ws.data_ptr<double>(),
+                   g.data_ptr<float>(), (int)d.B, (int)d.V, (int)K, (int)d.nnz, (int)num_cam, dverts.data_ptr<float>(),
+                   with_jtr ? djtr.data_ptr<float>() : nullptr, dx.data_ptr<float>(), cur_stream()),
+     "smplr_sup_bwd");
+  return {dverts, djtr, dx};
+}
+std::tuple<Tensor, Tensor, Tensor> sup_bwd_meta(const Tensor &x, const Tensor &x_t, const Tensor &verts, const Tensor &verts_t,
+                                                const c10::optional<Tensor> &, const c10::optional<Tensor> &t_joint,
+                                                const c10::optional<Tensor> &, int64_t K, int64_t root,
+                                                const c10::optional<Tensor> &row_w, const c10::optional<Tensor> &cam_scale,
+                                                const Tensor &status, const Tensor &ws, const Tensor &g, bool with_jtr,
+                                                int64_t num_cam) {
+  const SupDims d = sup_bwd_check(x, x_t, verts, verts_t, t_joint, K, root, row_w, cam_scale, status, ws, g, num_cam);
+  return {at::empty({d.B, d.V, 3}, verts.options()), at::empty({with_jtr ? d.B : 0, 24, 3}, verts.options()),
+          at::empty({d.B, d.C}, verts.options())};
+}
+
 TORCH_LIBRARY(smplraster, m) {
   m.def("abi_version() -> int", &abi_version);
   m.def("build_tag() -> str", &build_tag);
@@ -1530,6 +1651,11 @@ TORCH_LIBRARY(smplraster, m) {
   m.def("mesh_reg_fwd(Tensor verts, Tensor nb_off, Tensor nb_idx, Tensor nb_w, Tensor? lap_ref, Tensor? vweight, int E) -> Tensor");
   m.def("mesh_reg_bwd(Tensor verts, Tensor nb_off, Tensor nb_idx, Tensor nb_w, Tensor? lap_ref, Tensor? vweight, int E, "
         "Tensor g) -> Tensor");
+  m.def("sup_fwd(Tensor x, Tensor x_t, Tensor verts, Tensor verts_t, Tensor? jtr, Tensor? jtr_t, Tensor? off, Tensor? idx, "
+        "Tensor? w, int K, int root, Tensor? row_w, Tensor? cam_scale, int num_cam=4) -> (Tensor, Tensor, Tensor)");
+  m.def("sup_bwd(Tensor x, Tensor x_t, Tensor verts, Tensor verts_t, Tensor? t_off, Tensor? t_joint, Tensor? t_w, int K, "
+        "int root, Tensor? row_w, Tensor? cam_scale, Tensor status, Tensor ws, Tensor g, bool with_jtr=False, int num_cam=4) -> "
+        "(Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch key is named CUDA in torch)
@@ -1564,6 +1690,8 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("mesh_measures_bwd", &mesh_measures_bwd);
   m.impl("mesh_reg_fwd", &mesh_reg_fwd);
   m.impl("mesh_reg_bwd", &mesh_reg_bwd);
+  m.impl("sup_fwd", &sup_fwd);
+  m.impl("sup_bwd", &sup_bwd);
 }
 
 TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
@@ -1598,4 +1726,6 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("mesh_measures_bwd", &mesh_measures_bwd_meta);
   m.impl("mesh_reg_fwd", &mesh_reg_fwd_meta);
   m.impl("mesh_reg_bwd", &mesh_reg_bwd_meta);
+  m.impl("sup_fwd", &sup_fwd_meta);
+  m.impl("sup_bwd", &sup_bwd_meta);
 }

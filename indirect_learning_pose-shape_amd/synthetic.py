@@ -372,6 +372,9 @@ class SyntheticBatches:
     """An endless iterator of (images, labels) or, with silh_wh, (images, labels, silh_labels) for `training.fit(trainer,
     batches, ...)` and `SegTrainer.step`: images (B, C, input_wh, input_wh) fp32 proxy inputs, labels (B, output_wh,
     output_wh) int32 the CLEAN part map in the decoder's layout, silh_labels = labels > 0 rendered at silh_wh.
+    truth=True: (images, labels, silh_labels or None, truth) for `training.SupervisedTrainer.step`, truth = dict(x, verts,
+    J_transformed, joints (the clean 2D joints, or None)) - the very tensors the sampler made (`last`'s), not copies; the
+    generator's draws are the same either way.
 
     smpl_path_or_layer: an `SMPLLayer`, or what it is built from (a path, an `SMPLModelData`).  sampler: a `BodySampler`
     (default: `BodySampler(layer)`).  spec: a `keypoints.KeypointSpec` for the heatmaps, None for none.  seg, sigma:
@@ -383,10 +386,10 @@ class SyntheticBatches:
     One `next()`: the sampler (in output_wh units: `last["x"]` is what the regressor should predict); the part map at
     input_wh with scale = input_wh / output_wh, as `render.render_predictions`; the part map at output_wh (and silh_wh);
     the 2D joints from `spec`'s dense form with the same camera and scale; `corruption_draws`; `proxy_inputs`.
-    `last` keeps the batch's x, verts, joints (clean), keep and draws.  No host synchronisation per batch."""
+    `last` keeps the batch's x, verts, J_transformed, joints (clean), keep and draws.  No host synchronisation per batch."""
 
     def __init__(self, smpl_path_or_layer, batch_size, input_wh, output_wh, *, sampler=None, spec=None, seg="index", sigma=4.0,
-                 corruption=None, silh_wh=None, seed=1, generator=None, topology=None, device=None, num_parts=31):
+                 corruption=None, silh_wh=None, seed=1, generator=None, topology=None, device=None, num_parts=31, truth=False):
         from .keras_smpl.batch_smpl import SMPLLayer
         from .render import MeshTopology
         # (an SMPLLayer by what it offers, not by isinstance: the package is importable under two names)
@@ -415,6 +418,7 @@ class SyntheticBatches:
         self.generator = generator
         self.device = generator.device
         self.last = None
+        self.truth = bool(truth)
 
     def __iter__(self):
         return self
@@ -449,7 +453,8 @@ class SyntheticBatches:
             K = self.spec.K
             joints = self._joints(s)
             keep = torch.ones((B, K), dtype=torch.uint8, device=joints.device)
-        last = {"x": s["x"], "verts": s["verts"], "joints": joints, "keep": keep, "draws": None}
+        last = {"x": s["x"], "verts": s["verts"], "J_transformed": s.get("J_transformed"), "joints": joints, "keep": keep,
+                "draws": None}
         remove = boxes = None
         used = joints
         if corrupt and self.corruption is not None:
@@ -465,6 +470,8 @@ class SyntheticBatches:
 
     def __next__(self):
         images, labels, silh = self._batch(True)
+        if self.truth:
+            return images, labels, silh, {k: self.last[k] for k in ("x", "verts", "J_transformed", "joints")}
         return (images, labels) if silh is None else (images, labels, silh)
 
     def truth_batches(self, n):

@@ -106,6 +106,12 @@ SCHEMAS = {
                      "Tensor? vweight, int E) -> Tensor"),
     "mesh_reg_bwd": ("smplraster::mesh_reg_bwd(Tensor verts, Tensor nb_off, Tensor nb_idx, Tensor nb_w, Tensor? lap_ref, "
                      "Tensor? vweight, int E, Tensor g) -> Tensor"),
+    "sup_fwd": ("smplraster::sup_fwd(Tensor x, Tensor x_t, Tensor verts, Tensor verts_t, Tensor? jtr, Tensor? jtr_t, Tensor? off, "
+                "Tensor? idx, Tensor? w, int K, int root, Tensor? row_w, Tensor? cam_scale, int num_cam=4) -> "
+                "(Tensor, Tensor, Tensor)"),
+    "sup_bwd": ("smplraster::sup_bwd(Tensor x, Tensor x_t, Tensor verts, Tensor verts_t, Tensor? t_off, Tensor? t_joint, "
+                "Tensor? t_w, int K, int root, Tensor? row_w, Tensor? cam_scale, Tensor status, Tensor ws, Tensor g, "
+                "bool with_jtr=False, int num_cam=4) -> (Tensor, Tensor, Tensor)"),
 }
 
 _ns = None

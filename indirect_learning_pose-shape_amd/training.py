@@ -128,17 +128,37 @@ class SegTrainer:
         the silhouette one a SegConfusion(2, device); each pixel's (label, arg-max) is added to it (for the seg head
         inside the rasteriser's loss epilogue when the loss is fused), no host sync.
         Returns the mean loss (a 0-d tensor; no host sync).  (`_marks`: see `step_timed`.)"""
-        seg_m, silh_m = metrics if isinstance(metrics, (tuple, list)) else (metrics, None)
-        as_map = lambda t: t if t.dtype in (torch.int64, torch.int32, torch.int16, torch.uint8) else t.argmax(dim=-1)
         mark = (lambda k: None) if _marks is None else _marks
+        param = self._regress(images, mark, _marks is not None)
+        loss = self.param_loss(param, labels, silh_labels, metrics)
+        return self._update(loss, mark)
+
+    def _regress(self, images, mark, hook):
+        """The frame's first half: zero_grad and the regressor's forward -> param (N, 86)."""
         mark("start")
         self.opt.zero_grad(set_to_none=True)
         if self.channels_last and images.dim() == 4 and images.shape[1] == self.in_channels:
             images = images.contiguous(memory_format=torch.channels_last)
         param = regress(self.net, images, self.amp)
         mark("encoder_fwd")
-        if _marks is not None and param.requires_grad:
+        if hook and param.requires_grad:
             param.register_hook(lambda g: (mark("decoder_bwd"), g)[1])     # fires between the decoder's and the encoder's backward
+        return param
+
+    def _update(self, loss, mark):
+        """The frame's second half: backward and Adam -> the detached loss."""
+        mark("decoder_fwd")
+        loss.backward()
+        mark("backward")
+        self.opt.step()
+        mark("optimizer")
+        return loss.detach()
+
+    def param_loss(self, param, labels, silh_labels=None, metrics=None):
+        """The step's loss from the regressed `param` (N, 86): the decoder, the focal loss and, with silhouette labels, the
+        silhouette cross-entropy, as `step` describes them -> the mean loss (0-d, differentiable in param)."""
+        seg_m, silh_m = metrics if isinstance(metrics, (tuple, list)) else (metrics, None)
+        as_map = lambda t: t if t.dtype in (torch.int64, torch.int32, torch.int16, torch.uint8) else t.argmax(dim=-1)
         if labels is None:
             # `silhouettes_model.fit` (train_stage2_silhouette.py:226-234, the 150 silhouette steps of :262-270):
             # the silhouette head alone - no mask, no binning, no 31-part rasteriser
@@ -169,14 +189,9 @@ class SegTrainer:
                 loss = loss + self.silh_loss_fn(silh_labels, out["silhouette"]).mean()
                 if silh_m is not None:
                     silh_m.update(out["silhouette"], as_map(silh_labels))
-        mark("decoder_fwd")
-        loss.backward()
-        mark("backward")
-        self.opt.step()
-        mark("optimizer")
-        return loss.detach()
+        return loss
 
-    def step_timed(self, images, labels, silh_labels=None):
+    def step_timed(self, images, labels, silh_labels=None, **kw):
         """One `step` with HIP events between its sections -> dict(encoder_ms, decoder_ms, optimizer_ms, total_ms):
         encoder = regressor forward + its backward (under DDP that includes the all-reduce buckets it overlaps),
         decoder = decoder + loss forward and backward (up to the gradient of the 86-vector), optimizer = zero_grad +
@@ -187,7 +202,7 @@ class SegTrainer:
             e = torch.cuda.Event(enable_timing=True)
             e.record(torch.cuda.current_stream(self.device))
             ev[k] = e
-        self.step(images, labels, silh_labels, _marks=mark)
+        self.step(images, labels, silh_labels, _marks=mark, **kw)          # (kw: what a subclass's step takes beyond these)
         torch.cuda.synchronize(self.device)
         dt = lambda a, b: ev[a].elapsed_time(ev[b])
         dec_bwd_end = "decoder_bwd" if "decoder_bwd" in ev else "backward"
@@ -231,6 +246,85 @@ class SegTrainer:
                                % (ck["output_wh"], ck["output_wh"], self.output_wh, self.output_wh))
         self.smpl_model.load_state_dict(ck["smpl_model"])
         self.opt.load_state_dict(ck["optimizer"])
+        return int(ck.get("trial", -1)) + 1
+
+
+class SupervisedTrainer(SegTrainer):
+    """`SegTrainer` with the supervised 3D losses of `supervised.py` on the regressed parameters - how "Synthetic Training
+    for Accurate 3D Human Pose and Shape Estimation" trains - for batches that know their truth
+    (`synthetic.SyntheticBatches(..., truth=True)`).
+
+    spec, root, cam_scale: `supervised_terms`' (spec None: no 3D joint term).  weights None: the five terms are weighted by
+    learned homoscedastic uncertainties (`supervised.UncertaintyWeights`), whose log-variances join Adam's parameters and
+    the checkpoints; a 5-tuple: fixed weights.  indirect_weight > 0 adds that many times `SegTrainer`'s loss (part
+    rasteriser and, with silhouette labels, the silhouette head) whenever a step gets labels; with 0 (the default) no
+    binning or rasteriser kernel is launched and labels may be None.  ddp=True needs fixed weights: the log-variances live
+    outside the DDP module."""
+
+    def __init__(self, *args, spec=None, root=-1, weights=None, indirect_weight=0.0, cam_scale=None, **kw):
+        import inspect
+        from .keras_smpl.batch_smpl import SMPLLayer
+        from .supervised import UncertaintyWeights
+        if weights is None and inspect.signature(SegTrainer.__init__).bind(self, *args, **kw).arguments.get("ddp", False):
+            raise ValueError("ddp=True needs fixed weights=(w0, .., w4): the learned log-variances live outside the DDP module")
+        super().__init__(*args, **kw)
+        self.spec, self.root, self.indirect_weight = spec, int(root), float(indirect_weight)
+        self.cam_scale = None if cam_scale is None else torch.tensor([float(c) for c in cam_scale], dtype=torch.float32,
+                                                                     device=self.device)
+        self.weights = UncertaintyWeights(fixed=weights).to(self.device)
+        if self.weights.learned:
+            self.opt.add_param_group({"params": [self.weights.s]})
+        self.smpl_layer = SMPLLayer(self.decoder._model, num_cam=self.decoder.num_cam)      # (the decoder's model and constants)
+        self.last_terms = None
+
+    def step(self, images, labels=None, silh_labels=None, truth=None, metrics=None, _marks=None):
+        """images, labels, silh_labels, metrics: `SegTrainer.step`'s (labels are read only with indirect_weight > 0); truth:
+        dict(x (N, 86), verts (N, V, 3), J_transformed (N, 24, 3)) on the device.  Returns the mean loss (0-d, no host sync);
+        `last_terms` then holds the batch means of the five terms, (5,), detached."""
+        from .supervised import supervised_terms
+        if truth is None:
+            raise ValueError("SupervisedTrainer.step needs truth= (SyntheticBatches(..., truth=True) yields it)")
+        mark = (lambda k: None) if _marks is None else _marks
+        param = self._regress(images, mark, _marks is not None)
+        layer = self.smpl_layer
+        layer._consts, layer._consts_device = self.decoder.constants(param.device), param.device
+        verts = layer(param)
+        terms = supervised_terms(param, verts, layer.J_transformed, truth, self.spec, self.root, None, self.cam_scale,
+                                 self.decoder.num_cam)
+        loss = self.weights(terms).mean()
+        if self.indirect_weight > 0 and labels is not None:
+            loss = loss + self.indirect_weight * self.param_loss(param, labels, silh_labels, metrics)
+        self.last_terms = terms.detach().mean(0)
+        return self._update(loss, mark)
+
+    def save(self, path, trial=0):
+        """`SegTrainer.save` plus the log-variances under "uncertainty" (the Adam state covers them already)."""
+        torch.save({"smpl_model": self.smpl_model.state_dict(), "optimizer": self.opt.state_dict(), "trial": int(trial),
+                    "output_wh": int(self.output_wh), "uncertainty": self.weights.state_dict()}, path)
+
+    def resume(self, path):
+        """-> the trial to continue from.  A `SegTrainer` checkpoint (no "uncertainty") is accepted: its Adam state goes to
+        the regressor's parameters and the log-variances start at 0."""
+        ck = torch.load(path, map_location=self.device)
+        has_s = "s" in ck.get("uncertainty", {})
+        if "smpl_model" not in ck or has_s == self.weights.learned:
+            if has_s:
+                self.weights.load_state_dict(ck["uncertainty"])
+            return super().resume(path)
+        if has_s:
+            raise RuntimeError("the checkpoint carries learned log-variances, this trainer has fixed weights")
+        if int(ck.get("output_wh", self.output_wh)) != int(self.output_wh):
+            raise RuntimeError("checkpoint was trained at %dx%d, this trainer renders %dx%d"
+                               % (ck["output_wh"], ck["output_wh"], self.output_wh, self.output_wh))
+        self.smpl_model.load_state_dict(ck["smpl_model"])
+        own = torch.optim.Adam(self.smpl_model.parameters(), lr=self.opt.defaults["lr"])
+        own.load_state_dict(ck["optimizer"])
+        for p, st in own.state.items():
+            self.opt.state[p] = st
+        self.opt.param_groups[0].update({k: v for k, v in own.param_groups[0].items() if k != "params"})
+        with torch.no_grad():
+            self.weights.s.zero_()
+        self.opt.state.pop(self.weights.s, None)
         return int(ck.get("trial", -1)) + 1
 
 
