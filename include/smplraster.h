@@ -704,6 +704,31 @@ int smplr_sup_bwd(const float *x, const float *x_t, int x_stride, const float *v
                   const int32_t *status, const double *ws, const float *g, int B, int V, int K, int nnz, int num_cam,
                   float *dverts, float *djtr, float *dx, void *stream);
 
+/* ---- 6D rotation pose head: [cam | 24 x 6 | beta] -> the decoder's [cam | theta (72) | beta], with its gradient (beyond the
+ * reference); INTEGRATION.md 4v -------------------------------------------------------------------------------------------
+ * Row b: y (B rows, y_stride floats apart) = cam (num_cam), a (24 x 6), beta (10); x (B, num_cam + 82) contiguous = cam,
+ * theta (72), beta; cam and beta are bit copies.  Joint j reads its six numbers as a 3 x 2 row-major matrix with columns a1, a2:
+ *   b1 = a1 / |a1|, u = a2 - (b1 . a2) b1, b2 = u / |u|, b3 = b1 x b2, R = [b1 b2 b3] as columns;
+ *   (w, v) = the unit quaternion of R by the largest of (trace, R00, R11, R22), ties to the lowest index, flipped so that w >= 0
+ *   (w == 0 stays as the candidate gives it); phi = 2 atan2(|v|, w) in [0, pi], theta_j = phi v / |v|, exactly 0 at |v| == 0.
+ * status (B): the OR over the row's joints of SMPLR_ROT6D_NONFINITE (one of the six is NaN / Inf: that joint's theta and its six
+ *   gradients are NaN) and SMPLR_ROT6D_DEGENERATE (the six finite and not (|a1| >= 1e-6 and |u| >= 1e-6): theta 0, gradients 0);
+ *   other joints and other rows are not affected.
+ * smplr_rot6d_bwd, dx (B rows, dx_stride floats apart) the cotangent of x, status (B) the forward's (required, not read: every
+ *   joint's flags are recomputed from y, so a stale status changes nothing): dy (B, num_cam + 154) contiguous = dcam copy, da,
+ *   dbeta copy; da the exact derivative (one-sided at phi = pi): g_w = (I + [theta]x / 2 +
+ *   c [theta]x^2) g, c = 1 / phi^2 - cot(phi / 2) / (2 phi), dL/dR = [g_w]x R / 2, then the Gram-Schmidt backward.  R is recomputed
+ *   from y: there is no workspace.
+ * One launch each, ceil(B / 8) workgroups of 256 lanes.  All arithmetic is fp64 on the fp32 operands; each output is rounded to
+ * fp32 once; no atomics: a row's results are the same bits on every launch and in any batch.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 0 <= B <= 2^24 (B = 0 is a no-op), num_cam in 0 .. 8, y_stride >= num_cam +
+ * 154, dx_stride >= num_cam + 82; no null pointer.                                                                            */
+#define SMPLR_ROT6D_NONFINITE 1
+#define SMPLR_ROT6D_DEGENERATE 2
+int smplr_rot6d_fwd(const float *y, int y_stride, int B, int num_cam, float *x, int32_t *status, void *stream);
+int smplr_rot6d_bwd(const float *y, int y_stride, const int32_t *status, const float *dx, int dx_stride, int B, int num_cam,
+                    float *dy, void *stream);
+
 /* ---- label-map distance term: projected vertices against an integer label map, both directions, by class, with gradients
  * (beyond the reference); INTEGRATION.md 4r ---------------------------------------------------------------------------------
  * verts (B, V, 3) fp32, cam (B, 4) = (k_u, k_v, u0, v0), labels (B, W, W) int32: stored pixel q = r W + c sits at the point

@@ -1582,6 +1582,67 @@ std::tuple<Tensor, Tensor, Tensor> sup_bwd_meta(const Tensor &x, const Tensor &x
           at::empty({d.B, d.C}, verts.options())};
 }
 
+// ---- 6D rotation pose head (include/smplraster.h): y (B, num_cam + 154) = cam, 24 x 6, beta -> x (B, num_cam +
+// 82) = cam, theta, beta and status (B) int32; the backward takes y, status and dx (B, num_cam + 82) and returns dy (B, num_cam +
+// 154).  y and dx may be column slices of wider tensors: unit column stride, rows at least their width apart ---------------------
+int64_t rot6d_rows(const Tensor &t, int64_t cols, const char *name) {
+  TORCH_CHECK(t.dim() == 2 && t.size(1) == cols && t.scalar_type() == at::kFloat, name, " must be (B, ", cols, ") float32");
+  if (t.size(0) <= 1) {
+    TORCH_CHECK(t.numel() == 0 || t.stride(1) == 1, name, ": the last dimension must be contiguous");
+    return cols;
+  }
+  TORCH_CHECK(t.stride(1) == 1 && t.stride(0) >= cols && t.stride(0) <= INT32_MAX, name,
+              ": the last dimension must be contiguous and rows at least ", cols, " floats apart");
+  return t.stride(0);
+}
+void rot6d_on_device(const Tensor &t, const char *name) {
+  TORCH_CHECK(t.is_cuda(), name, " must live on a HIP device (got ", t.device(), "); this library has no CPU path");
+}
+int64_t rot6d_cam(int64_t num_cam) {
+  TORCH_CHECK(num_cam >= 0 && num_cam <= 8, "num_cam = ", num_cam, " must lie in 0 .. 8");
+  return num_cam;
+}
+std::tuple<Tensor, Tensor> rot6d_fwd(const Tensor &y, int64_t num_cam) {
+  const int64_t stride = rot6d_rows(y, rot6d_cam(num_cam) + 154, "y"), B = y.size(0);
+  rot6d_on_device(y, "y");
+  DeviceGuard guard(y.device());
+  Tensor x = f32({B, num_cam + 82}, y), status = at::empty({B}, y.options().dtype(at::kInt));
+  if (B == 0) return {x, status};
+  ok(smplr_rot6d_fwd(y.data_ptr<float>(), (int)stride, (int)B, (int)num_cam, x.data_ptr<float>(), status.data_ptr<int32_t>(),
+                     cur_stream()),
+     "smplr_rot6d_fwd");
+  return {x, status};
+}
+std::tuple<Tensor, Tensor> rot6d_fwd_meta(const Tensor &y, int64_t num_cam) {
+  rot6d_rows(y, rot6d_cam(num_cam) + 154, "y");
+  return {at::empty({y.size(0), num_cam + 82}, y.options()), at::empty({y.size(0)}, y.options().dtype(at::kInt))};
+}
+void rot6d_bwd_check(const Tensor &y, const Tensor &status, const Tensor &dx, int64_t num_cam, int64_t *ys, int64_t *ds) {
+  *ys = rot6d_rows(y, rot6d_cam(num_cam) + 154, "y");
+  *ds = rot6d_rows(dx, num_cam + 82, "dx");
+  TORCH_CHECK(dx.size(0) == y.size(0), "dx must have y's rows");
+  TORCH_CHECK(status.dim() == 1 && status.size(0) == y.size(0) && status.scalar_type() == at::kInt, "status must be (B) int32");
+}
+Tensor rot6d_bwd(const Tensor &y, const Tensor &status, const Tensor &dx, int64_t num_cam) {
+  int64_t ys, ds;
+  rot6d_bwd_check(y, status, dx, num_cam, &ys, &ds);
+  rot6d_on_device(y, "y"); rot6d_on_device(dx, "dx"); dev_typed(status, at::kInt, "status");
+  same_device(y, {{"dx", &dx}, {"status", &status}});
+  DeviceGuard guard(y.device());
+  const int64_t B = y.size(0);
+  Tensor dy = f32({B, num_cam + 154}, y);
+  if (B == 0) return dy;
+  ok(smplr_rot6d_bwd(y.data_ptr<float>(), (int)ys, status.data_ptr<int32_t>(), dx.data_ptr<float>(), (int)ds, (int)B, (int)num_cam,
+                     dy.data_ptr<float>(), cur_stream()),
+     "smplr_rot6d_bwd");
+  return dy;
+}
+Tensor rot6d_bwd_meta(const Tensor &y, const Tensor &status, const Tensor &dx, int64_t num_cam) {
+  int64_t ys, ds;
+  rot6d_bwd_check(y, status, dx, num_cam, &ys, &ds);
+  return at::empty({y.size(0), num_cam + 154}, y.options());
+}
+
 TORCH_LIBRARY(smplraster, m) {
   m.def("abi_version() -> int", &abi_version);
   m.def("build_tag() -> str", &build_tag);
@@ -1656,6 +1717,8 @@ TORCH_LIBRARY(smplraster, m) {
   m.def("sup_bwd(Tensor x, Tensor x_t, Tensor verts, Tensor verts_t, Tensor? t_off, Tensor? t_joint, Tensor? t_w, int K, "
         "int root, Tensor? row_w, Tensor? cam_scale, Tensor status, Tensor ws, Tensor g, bool with_jtr=False, int num_cam=4) -> "
         "(Tensor, Tensor, Tensor)");
+  m.def("rot6d_fwd(Tensor y, int num_cam=4) -> (Tensor, Tensor)");
+  m.def("rot6d_bwd(Tensor y, Tensor status, Tensor dx, int num_cam=4) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch key is named CUDA in torch)
@@ -1692,6 +1755,8 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("mesh_reg_bwd", &mesh_reg_bwd);
   m.impl("sup_fwd", &sup_fwd);
   m.impl("sup_bwd", &sup_bwd);
+  m.impl("rot6d_fwd", &rot6d_fwd);
+  m.impl("rot6d_bwd", &rot6d_bwd);
 }
 
 TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
@@ -1728,4 +1793,6 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("mesh_reg_bwd", &mesh_reg_bwd_meta);
   m.impl("sup_fwd", &sup_fwd_meta);
   m.impl("sup_bwd", &sup_bwd_meta);
+  m.impl("rot6d_fwd", &rot6d_fwd_meta);
+  m.impl("rot6d_bwd", &rot6d_bwd_meta);
 }

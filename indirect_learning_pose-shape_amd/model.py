@@ -168,10 +168,19 @@ class SMPLRegressor(nn.Module):
     This is the reference's `smpl_model` (the only part with trainable weights, train.py:302-315).
     in_channels: 3 for images, 1 for the autoencoders' part map (train_autoencoder.py), any C for the proxy inputs of
     `synthetic.SyntheticBatches`; with the default, names and shapes of the parameters are unchanged.
+    pose_repr: "axis_angle", the reference's 72 regressed numbers, or "rot6d" (beyond the reference): the last layer puts out
+    158 = [cam | 24 x 6 | beta], the IEF state is those 158 and starts at `rot6d.mean_rot6d_row`, `scaledown` applies to the
+    158-delta, and `rot6d.params_from_rot6d` turns the result into the (N, 86) every consumer takes; its status (N,) int32
+    stays on the device as `self.pose_status` (None before the first forward and with "axis_angle").
     """
 
-    def __init__(self, output_wh, encoder_architecture="resnet50", use_IEF=False, scaledown=0.005, in_channels=3):
+    def __init__(self, output_wh, encoder_architecture="resnet50", use_IEF=False, scaledown=0.005, in_channels=3,
+                 pose_repr="axis_angle"):
         super().__init__()
+        if pose_repr not in ("axis_angle", "rot6d"):
+            raise ValueError("pose_repr must be 'axis_angle' or 'rot6d'")
+        self.pose_repr, self.pose_status = pose_repr, None
+        nout = 158 if pose_repr == "rot6d" else 86
         self.in_channels = int(in_channels)
         if self.in_channels < 1:
             raise ValueError("in_channels must be positive")
@@ -183,17 +192,33 @@ class SMPLRegressor(nn.Module):
             raise ValueError("encoder_architecture must be 'enet' or 'resnet50' (model.py:38,56)")
         self.output_wh, self.use_IEF, self.scaledown = output_wh, bool(use_IEF), float(scaledown)
         if use_IEF:                                            # shared across the 3 iterations (:66-68)
-            self.IEF_layer_1 = nn.Linear(2048 + 86, 1024)
+            self.IEF_layer_1 = nn.Linear(2048 + nout, 1024)
             self.IEF_layer_2 = nn.Linear(1024, 1024)
-            self.IEF_layer_3 = nn.Linear(1024, 86)
+            self.IEF_layer_3 = nn.Linear(1024, nout)
         else:
             self.mlp = nn.Sequential(nn.Linear(2048, 2048), nn.ReLU(inplace=True),
-                                     nn.Linear(2048, 1024), nn.ReLU(inplace=True), nn.Linear(1024, 86))
+                                     nn.Linear(2048, 1024), nn.ReLU(inplace=True), nn.Linear(1024, nout))
+
+    def _forward_rot6d(self, feats):
+        """The regression module in 6D space -> (N, 86): the mean row and the state are (N, 158), the pose head is fp32."""
+        from .rot6d import mean_rot6d_row, params_from_rot6d
+        mean = mean_rot6d_row(self.output_wh, feats.device)
+        if not self.use_IEF:
+            y = self.mlp(feats) * self.scaledown + mean
+        else:
+            y = mean.expand(feats.shape[0], 158)
+            for _ in range(3):
+                state = torch.cat([feats, y], dim=1)
+                y = y + self.IEF_layer_3(F.relu(self.IEF_layer_2(F.relu(self.IEF_layer_1(state))))) * self.scaledown
+        x, self.pose_status = params_from_rot6d(y.float(), return_status=True)
+        return x
 
     def forward(self, images):
         if images.dim() == 4 and images.shape[1] != self.in_channels and images.shape[3] == self.in_channels:
             images = images.permute(0, 3, 1, 2)               # NHWC (Keras) -> NCHW
         feats = self.backbone(images.contiguous())
+        if self.pose_repr == "rot6d":
+            return self._forward_rot6d(feats)
         if not self.use_IEF:
             return load_mean_set_cam_params(self.mlp(feats) * self.scaledown, self.output_wh)   # :100-105
         state = concat_mean_param(feats, self.output_wh)                                         # :70-71
@@ -236,15 +261,17 @@ class FullModel(nn.Module):
 
 
 def build_model(train_batch_size, input_shape, smpl_path, output_wh, num_classes,
-                encoder_architecture="resnet50", use_IEF=False, vertex_sampling=None, scaledown=0.005, in_channels=None):
+                encoder_architecture="resnet50", use_IEF=False, vertex_sampling=None, scaledown=0.005, in_channels=None,
+                pose_repr="axis_angle"):
     """`build_model`, model.py:16-129.  Returns (segs_model, smpl_model, verts_model, projects_model);
     the four share one encoder/regressor and one decoder, as the Keras models share one graph.
-    in_channels: the encoder's input channels; default `input_shape[-1]`, the reference's (H, W, C)."""
+    in_channels: the encoder's input channels; default `input_shape[-1]`, the reference's (H, W, C).
+    pose_repr: `SMPLRegressor`'s ("rot6d": the regressor works in the 6D rotation representation)."""
     if num_classes != 32:
         raise ValueError("the decoder produces 32 classes (31 parts + background)")
     if in_channels is None:
         in_channels = int(input_shape[-1])
-    smpl_model = SMPLRegressor(output_wh, encoder_architecture, use_IEF, scaledown, in_channels)
+    smpl_model = SMPLRegressor(output_wh, encoder_architecture, use_IEF, scaledown, in_channels, pose_repr)
     decoder = SMPLDecoder(smpl_path, img_wh=output_wh, vertex_sampling=vertex_sampling)
     return (FullModel(smpl_model, decoder, "segs"), smpl_model, FullModel(smpl_model, decoder, "verts"),
             FullModel(smpl_model, decoder, "projects"))

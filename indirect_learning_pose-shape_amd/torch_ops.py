@@ -112,6 +112,8 @@ SCHEMAS = {
     "sup_bwd": ("smplraster::sup_bwd(Tensor x, Tensor x_t, Tensor verts, Tensor verts_t, Tensor? t_off, Tensor? t_joint, "
                 "Tensor? t_w, int K, int root, Tensor? row_w, Tensor? cam_scale, Tensor status, Tensor ws, Tensor g, "
                 "bool with_jtr=False, int num_cam=4) -> (Tensor, Tensor, Tensor)"),
+    "rot6d_fwd": "smplraster::rot6d_fwd(Tensor y, int num_cam=4) -> (Tensor, Tensor)",
+    "rot6d_bwd": "smplraster::rot6d_bwd(Tensor y, Tensor status, Tensor dx, int num_cam=4) -> Tensor",
 }
 
 _ns = None

@@ -68,7 +68,8 @@ class SegTrainer:
 
     def __init__(self, smpl_path=None, input_wh=256, output_wh=48, encoder_architecture="enet", use_IEF=True,
                  weight_classes=True, gamma=2.0, lr=1e-4, device=None, ddp=False, bucket_mb=25,
-                 with_silhouette=False, silh_wh=None, fused_loss=True, fused_silh_loss=False, amp=None, in_channels=3):
+                 with_silhouette=False, silh_wh=None, fused_loss=True, fused_silh_loss=False, amp=None, in_channels=3,
+                 pose_repr="axis_angle"):
         amp_dtype(amp)                                                # (ValueError before anything is built)
         if amp is not None and os.environ.get("SMPLR_ENCODER_LAYOUT", "").lower() == "channels_last":
             # that layout runs torch's own BatchNorm2d (the package's kernels read NCHW planes), and torch 2.10 / ROCm 7.0's
@@ -83,7 +84,8 @@ class SegTrainer:
             configure_conv_backend()
         self.output_wh = output_wh
         self.in_channels = int(in_channels)                           # (3: images; synthetic.SyntheticBatches.in_channels)
-        self.smpl_model = SMPLRegressor(output_wh, encoder_architecture, use_IEF, in_channels=self.in_channels).to(self.device)
+        self.smpl_model = SMPLRegressor(output_wh, encoder_architecture, use_IEF, in_channels=self.in_channels,
+                                        pose_repr=pose_repr).to(self.device)      # ("rot6d": rot6d.py; still (N, 86) out)
         # OPT-IN (`SMPLR_ENCODER_LAYOUT=channels_last`): the encoder's weights and activations in NHWC, the layout
         # MIOpen's implicit-GEMM convolution solvers work in (the default NCHW tensors are transposed around them:
         # `batched_transpose_32x32_dword` in the train step's kernel trace).  The package's fused batch-norm / PReLU
