@@ -21,6 +21,16 @@ inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s);
     }                                                  \
   } while (0)
 
+// The launch geometry of a kernel with ceil(n / T) workgroups of T lanes per mesh: nblk per mesh, nwg = B nblk in all, which
+// must stay below 2^31 (`what` names n in the message).  -> 0 or SMPLR_EINVAL.
+struct MeshGrid { int nblk; long long nwg; };
+inline int mesh_grid(const char *who, const char *what, int B, int n, int T, MeshGrid *g) {
+  g->nblk = (n + T - 1) / T;
+  g->nwg = (long long)B * g->nblk;
+  SMPLR_REQUIRE(g->nwg < (1ll << 31), "%s: B * ceil(%s / %d) = %lld workgroups exceed 2^31", who, what, T, g->nwg);
+  return 0;
+}
+
 #define SMPLR_LAUNCH_CHECK(name)                                              \
   do {                                                                        \
     hipError_t e__ = hipGetLastError();                                       \
@@ -213,6 +223,21 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_min_f(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ float wave_max_f(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ unsigned wave_or_u(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v |= (unsigned)__shfl_xor((int)v, o, 64);
   return v;
 }
 

@@ -23,7 +23,7 @@
 //
 // The index arrays are built and checked once on the host (keypoints.KeypointSpec); the kernels still skip an offset range
 // outside [0, nnz], a source outside [0, S) and a joint outside [0, K).
-#include "common.h"
+#include "mesh_device.h"
 
 #pragma clang fp contract(off)
 
@@ -33,12 +33,6 @@ namespace {
 constexpr int KP_T = 256;          // lanes per workgroup
 constexpr int KP_MAXK = 64;        // joints of a spec: one wave scores them
 constexpr int KP_NJ = 24;          // posed joints that may follow the vertices as sources
-
-__device__ __forceinline__ double kp_rho(double s, double s2) { return s2 > 0.0 ? (s2 * s) / (s2 + s) : s; }
-__device__ __forceinline__ double kp_drho(double s, double s2) {
-  const double h = s2 + s;
-  return s2 > 0.0 ? (s2 * s2) / (h * h) : 1.0;
-}
 
 __global__ __launch_bounds__(KP_T) void kp_fwd_kernel(const float *__restrict__ verts, const float *__restrict__ jtr,
                                                       const float *__restrict__ cam, const int *__restrict__ off,
@@ -101,7 +95,7 @@ __global__ __launch_bounds__(KP_T) void kp_fwd_kernel(const float *__restrict__ 
     rv = pv - (double)tv;
     dd = ru * ru + rv * rv;
     const double s2 = (double)sigma * (double)sigma;
-    ee = counted ? (double)cf * kp_rho(dd, s2) : 0.0;
+    ee = counted ? (double)cf * robust_rho(dd, s2) : 0.0;
     my_bad = counted && (s_bad[tid] || !finitef(tu) || !finitef(tv));
   }
   const int row_bad = __syncthreads_or(my_bad) | cam_bad;
@@ -145,7 +139,7 @@ __global__ __launch_bounds__(KP_T) void kp_bwd_kernel(const float *__restrict__ 
         Jy = ws[o * 4 + 1];
         const double ru = ws[o * 4 + 2], rv = ws[o * 4 + 3];
         const double s2 = (double)sigma * (double)sigma;
-        const double c = ((double)g[o] * (double)cf) * kp_drho(ru * ru + rv * rv, s2);
+        const double c = ((double)g[o] * (double)cf) * robust_drho(ru * ru + rv * rv, s2);
         qu = c * (2.0 * ru);
         qv = c * (2.0 * rv);
       }

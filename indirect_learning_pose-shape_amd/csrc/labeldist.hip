@@ -30,7 +30,7 @@
 //   between off[c] and off[c + 1], or the vertices vrun between voff[c] and voff[c + 1], projected by the loading lane -
 //   through LDS in tiles of 256 that every lane of the class walks with broadcast reads; a later entry wins only when
 //   strictly closer, so ties go to the earlier, lower one.  All of it fp64: the winner is the definition's, not a bound's.
-//   Every workgroup finds its row's status itself (one strided pass over vclass, vweight, X, Y: scan.hip's way), so no
+//   Every workgroup finds its row's status itself (one strided pass over vclass, vweight, X, Y, as mesh_device.h's mesh_nonfinite does), so no
 //   second launch has to overwrite a row; with a workgroup per tile that pass was most of the launch's time at W = 48.
 //
 // ld_bwd_kernel: grid (ceil(nslots / 256), B), gather form, a lane per vertex in slot order.  Its own term first,
@@ -42,7 +42,7 @@
 //
 // Every index read from memory is range-checked: a slot, vertex, class, offset range or pixel outside its range is
 // skipped, so a hostile vclass, label or index array cannot make a kernel read or write out of bounds.
-#include "common.h"
+#include "mesh_device.h"
 
 #pragma clang fp contract(off)
 
@@ -54,12 +54,6 @@ constexpr int LD_MAXC = 32;        // classes, background included
 constexpr int LD_MAXW = 160;       // label maps up to 160 x 160
 constexpr int LD_FWD_WG = 4096;    // workgroups the forward launch aims at: a row's tiles are shared out among
                                    // max(8, 4096 / B) workgroups, each walking every n-th tile of its row
-
-__device__ __forceinline__ double ld_rho(double s, double s2) { return s2 > 0.0 ? (s2 * s) / (s2 + s) : s; }
-__device__ __forceinline__ double ld_drho(double s, double s2) {
-  const double h = s2 + s;
-  return s2 > 0.0 ? (s2 * s2) / (h * h) : 1.0;
-}
 
 struct LdCam { double ku, kv, u0, v0; int bad; };
 __device__ __forceinline__ LdCam ld_cam(const float *__restrict__ cam, int b) {
@@ -104,11 +98,10 @@ __device__ __forceinline__ void ld_run(const int *__restrict__ off, int c, int l
 
 struct LdTile { double u[LD_T], v[LD_T]; int id[LD_T]; unsigned cls[LD_T / WAVE]; };
 
-// The bitwise OR of v over the workgroup, the same value in every lane (__syncthreads_or reduces !!v, not v): a butterfly
+// The bitwise OR of v over the workgroup, the same value in every lane (__syncthreads_or reduces !!v, not v): wave_or_u
 // per wave, then the waves' words through LDS.  Every lane of the workgroup calls it.
 __device__ __forceinline__ unsigned ld_block_or(LdTile &t, unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v |= (unsigned)__shfl_xor((int)v, o, 64);
+  v = wave_or_u(v);
   __syncthreads();                                            // (an earlier call's words may still be read)
   if ((threadIdx.x & (WAVE - 1)) == 0) t.cls[threadIdx.x / WAVE] = v;
   __syncthreads();
@@ -272,7 +265,7 @@ __global__ __launch_bounds__(LD_T) void ld_fwd_kernel(const float *__restrict__ 
       const bool has = besti >= 0;
       double s = best - sl;
       s = s > 0.0 ? s : 0.0;
-      e_v[o] = bad ? qnan : (has ? (float)((double)w * ld_rho(s, s2)) : 0.f);
+      e_v[o] = bad ? qnan : (has ? (float)((double)w * robust_rho(s, s2)) : 0.f);
       d2_v[o] = bad ? qnan : (has ? (float)best : inf);
       near_pix[o] = has ? besti : -1;
     }
@@ -305,7 +298,7 @@ __global__ __launch_bounds__(LD_T) void ld_fwd_kernel(const float *__restrict__ 
           const bool has = besti >= 0;
           double s = best - sl;
           s = s > 0.0 ? s : 0.0;
-          e_p[o] = has ? (float)ld_rho(s, s2) : 0.f;
+          e_p[o] = has ? (float)robust_rho(s, s2) : 0.f;
           d2_p[o] = has ? (float)best : inf;
           near_vert[o] = has ? besti : -1;
         }
@@ -351,7 +344,7 @@ __global__ __launch_bounds__(LD_T) void ld_bwd_kernel(const float *__restrict__ 
       const double du = (cm.u0 + cm.ku * X) - qu, dv = (cm.v0 + cm.kv * Y) - qv;
       const double d2 = du * du + dv * dv;
       if (d2 > sl) {
-        const double cf = ((double)g_v[(size_t)b * V + i] * (double)w) * ld_drho(d2 - sl, s2);
+        const double cf = ((double)g_v[(size_t)b * V + i] * (double)w) * robust_drho(d2 - sl, s2);
         au = cf * (2.0 * du);
         av = cf * (2.0 * dv);
       }
@@ -377,7 +370,7 @@ __global__ __launch_bounds__(LD_T) void ld_bwd_kernel(const float *__restrict__ 
           const double dv = (cm.v0 + cm.kv * (double)P[(size_t)nv * 3 + 1]) - qv;
           const double d2 = du * du + dv * dv;
           if (d2 > sl) {
-            const double cf = (double)g_p[(size_t)b * N + q] * ld_drho(d2 - sl, s2);
+            const double cf = (double)g_p[(size_t)b * N + q] * robust_drho(d2 - sl, s2);
             ru = cf * (2.0 * du);
             rv = cf * (2.0 * dv);
             id = nv;

@@ -23,7 +23,7 @@
 // A mesh with a coordinate or a plane entry that is not finite has every output (and every dverts row) NaN, ext_idx -1
 // and SMPLR_MM_NONFINITE in status; the other meshes are untouched.  Every index read from memory is range-checked: a
 // face naming a vertex outside [0, V) contributes nothing, a CSR entry outside [0, F) is skipped.
-#include "common.h"
+#include "mesh_device.h"
 
 #pragma clang fp contract(off)
 
@@ -36,21 +36,13 @@ constexpr int MM_NRED = 2 + 5 * MM_PK;
 constexpr int MM_KMAX = 16;
 constexpr int MM_BT = 256;       // lanes per workgroup in the backward kernel
 
-struct D3 { double x, y, z; };
-__device__ __forceinline__ D3 operator-(const D3 &a, const D3 &b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double ddot(const D3 &a, const D3 &b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ D3 dcross(const D3 &a, const D3 &b) {
-  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
+using D3 = V3<double>;
 __device__ __forceinline__ D3 dsel(bool c, const D3 &a, const D3 &b) { return {c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z}; }
-__device__ __forceinline__ D3 load_vertex(const float *__restrict__ P, int i) {
-  return {(double)P[(size_t)i * 3], (double)P[(size_t)i * 3 + 1], (double)P[(size_t)i * 3 + 2]};
-}
 struct PlaneD { D3 n; double o; };
 __device__ __forceinline__ PlaneD load_plane(const float *__restrict__ p) {
   return {{(double)p[0], (double)p[1], (double)p[2]}, (double)p[3]};
 }
-__device__ __forceinline__ double plane_dist(const PlaneD &p, const D3 &v) { return ((p.n.x * v.x + p.n.y * v.y) + p.n.z * v.z) - p.o; }
+__device__ __forceinline__ double plane_dist(const PlaneD &p, const D3 &v) { return dot3(p.n, v) - p.o; }
 
 // The cut of one face by one plane.  Returns false when the face's vertices lie on one side.  Otherwise L = |q - q'| and,
 // as asked for, gv[c] = dL / d(corner c) and gp = dL / d(n_x, n_y, n_z, o).
@@ -79,11 +71,11 @@ __device__ __forceinline__ bool cut_face(const D3 &v0, const D3 &v1, const D3 &v
   const D3 q1 = {i1.x + t1 * e1.x, i1.y + t1 * e1.y, i1.z + t1 * e1.z};
   const D3 q2 = {i2.x + t2 * e2.x, i2.y + t2 * e2.y, i2.z + t2 * e2.z};
   const D3 dq = q1 - q2;
-  L = sqrt(ddot(dq, dq));
+  L = sqrt(dot3(dq, dq));
   if (!(WANT_V || WANT_P)) return true;
   const double inv = L > 0.0 ? 1.0 / L : 0.0;
   const D3 g = {dq.x * inv, dq.y * inv, dq.z * inv};        // dL/dq1; dL/dq2 = -g
-  const double s1 = ddot(g, e1), s2 = -ddot(g, e2);
+  const double s1 = dot3(g, e1), s2 = -dot3(g, e2);
   const double r1 = 1.0 / (D1 * D1), r2 = 1.0 / (D2 * D2);
   if (WANT_P) {
     const double c1 = s1 * r1, c2 = s2 * r2;
@@ -198,11 +190,11 @@ __global__ __launch_bounds__(MM_T) void measure_fwd_kernel(const float *__restri
     for (int f = tid; f < F; f += MM_T) {
       const int i0 = faces[(size_t)f * 3], i1 = faces[(size_t)f * 3 + 1], i2 = faces[(size_t)f * 3 + 2];
       if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) continue;
-      const D3 v0 = load_vertex(P, i0), v1 = load_vertex(P, i1), v2 = load_vertex(P, i2);
+      const D3 v0 = load_v3<double>(P, i0), v1 = load_v3<double>(P, i1), v2 = load_v3<double>(P, i2);
       if (r == 0) {
-        acc[0] += ddot(v0, dcross(v1, v2));
-        const D3 c = dcross(v1 - v0, v2 - v0);
-        acc[1] += sqrt(ddot(c, c));
+        acc[0] += dot3(v0, cross3(v1, v2));
+        const D3 c = cross3(v1 - v0, v2 - v0);
+        acc[1] += sqrt(dot3(c, c));
       }
       const unsigned pbit = K > 0 ? 1u << (face_part[f] & 31) : 0u;
 #pragma unroll
@@ -284,22 +276,22 @@ __global__ __launch_bounds__(MM_BT) void measure_bwd_kernel(const float *__restr
     else if (i1 == v && left-- == 0) corner = 1;
     else if (i2 == v && left-- == 0) corner = 2;
     if (corner < 0) continue;
-    const D3 v0 = load_vertex(P, i0), v1 = load_vertex(P, i1), v2 = load_vertex(P, i2);
+    const D3 v0 = load_v3<double>(P, i0), v1 = load_v3<double>(P, i1), v2 = load_v3<double>(P, i2);
     // this corner first, the others in cyclic order: det and the area are invariant under the rotation
     const bool c0 = corner == 0, c1 = corner == 1;
     const D3 a = dsel(c0, v0, dsel(c1, v1, v2)), b = dsel(c0, v1, dsel(c1, v2, v0)), c = dsel(c0, v2, dsel(c1, v0, v1));
     if (g_volume) {
-      const D3 n = dcross(b, c);                               // d det[a, b, c] / da
+      const D3 n = cross3(b, c);                               // d det[a, b, c] / da
       ax += gvol * n.x; ay += gvol * n.y; az += gvol * n.z;
     }
     if (g_area) {
-      const D3 eb = b - a, ec = c - a, n = dcross(eb, ec);
-      const double len = sqrt(ddot(n, n));
+      const D3 eb = b - a, ec = c - a, n = cross3(eb, ec);
+      const double len = sqrt(dot3(n, n));
       if (len > 0.0) {
         // n changes by da x (b - c), so d|n|/da = (b - c) x n / |n|
         const double inv = 1.0 / len;
         const D3 u = {n.x * inv, n.y * inv, n.z * inv};
-        const D3 g = dcross(b - c, u);
+        const D3 g = cross3(b - c, u);
         ax += gar * g.x; ay += gar * g.y; az += gar * g.z;
       }
     }
@@ -370,18 +362,17 @@ int smplr_mesh_measures_bwd(const float *verts, const int32_t *faces, const int3
   SMPLR_REQUIRE(K >= 0 && K <= MM_KMAX, "smplr_mesh_measures_bwd: K=%d planes outside 0..%d", K, MM_KMAX);
   SMPLR_REQUIRE(plane_bstride == 0 || plane_bstride >= (long long)K * 4,
                 "smplr_mesh_measures_bwd: plane_bstride=%lld is neither 0 (shared planes) nor at least 4 K", plane_bstride);
-  const int nblk = (V + MM_BT - 1) / MM_BT;
-  SMPLR_REQUIRE((long long)B * nblk < (1ll << 31), "smplr_mesh_measures_bwd: B * ceil(V / %d) = %lld workgroups exceed 2^31",
-                MM_BT, (long long)B * nblk);
+  MeshGrid mg;
+  if (mesh_grid("smplr_mesh_measures_bwd", "V", B, V, MM_BT, &mg)) return SMPLR_EINVAL;
   if (B == 0) return 0;
   SMPLR_REQUIRE(verts && (faces || F == 0) && vf_off && (vf_face || nnz == 0) && status && dverts,
                 "smplr_mesh_measures_bwd: null pointer (verts, faces, vf_off, vf_face, status and dverts are required)");
   SMPLR_REQUIRE(!g_extent || ext_idx, "smplr_mesh_measures_bwd: null pointer (g_extent needs ext_idx)");
   SMPLR_REQUIRE(K == 0 || !g_girth || (face_part && planes && part_mask),
                 "smplr_mesh_measures_bwd: null pointer (g_girth with K > 0 needs face_part, planes and part_mask)");
-  hipLaunchKernelGGL(measure_bwd_kernel, dim3((unsigned)((long long)B * nblk)), dim3(MM_BT), 0, as_stream(stream), verts, faces,
+  hipLaunchKernelGGL(measure_bwd_kernel, dim3((unsigned)mg.nwg), dim3(MM_BT), 0, as_stream(stream), verts, faces,
                      vf_off, vf_face, nnz, face_part, planes, plane_bstride, part_mask, reinterpret_cast<const int *>(ext_idx),
-                     reinterpret_cast<const int *>(status), g_volume, g_area, g_extent, g_girth, B, V, F, K, nblk, dverts);
+                     reinterpret_cast<const int *>(status), g_volume, g_area, g_extent, g_girth, B, V, F, K, mg.nblk, dverts);
   SMPLR_LAUNCH_CHECK("smplr_mesh_measures_bwd");
   return 0;
 }

@@ -24,7 +24,7 @@
 // A mesh with a NaN or infinite coordinate has NaN terms (and NaN gradient rows where the coordinate reaches); the other
 // meshes are untouched.  Every index read from memory is range-checked: an entry naming a vertex outside [0, V) is
 // skipped, offsets are clamped to [0, nnz].
-#include "common.h"
+#include "mesh_device.h"
 
 #pragma clang fp contract(off)
 
@@ -33,10 +33,7 @@ namespace smplr {
 constexpr int MR_T = 256;        // lanes per workgroup, both kernels
 constexpr int MR_NW = MR_T / WAVE;
 
-struct MrV3 { double x, y, z; };
-__device__ __forceinline__ MrV3 mr_load(const float *__restrict__ P, int i) {
-  return {(double)P[(size_t)i * 3], (double)P[(size_t)i * 3 + 1], (double)P[(size_t)i * 3 + 2]};
-}
+using MrV3 = V3<double>;
 
 struct MrSpec {
   const int *nb_off, *nb_idx;
@@ -60,15 +57,15 @@ __device__ __forceinline__ MrV3 mr_residual(const MrSpec &s, const float *__rest
   for (int e = e0; e < e1; ++e) {
     const int k = s.nb_idx[e];
     if ((unsigned)k >= (unsigned)s.V) continue;
-    const MrV3 vk = mr_load(P, k);
+    const MrV3 vk = load_v3<double>(P, k);
     const double w = (double)s.nb_w[(size_t)e * 3];
     sx += w * vk.x; sy += w * vk.y; sz += w * vk.z;
     ++deg;
     if (EDGE && k > i) {
       const double il2 = (double)s.nb_w[(size_t)e * 3 + 2];
       if (il2 != 0.0) {
-        const double dx = vi.x - vk.x, dy = vi.y - vk.y, dz = vi.z - vk.z;
-        const double q = (dx * dx + dy * dy + dz * dz) * il2 - 1.0;
+        const MrV3 d = vi - vk;
+        const double q = dot3(d, d) * il2 - 1.0;
         edge += q * q;
       }
     }
@@ -94,11 +91,11 @@ __global__ __launch_bounds__(MR_T) void meshreg_fwd_kernel(const float *__restri
   double lap = 0.0, edge = 0.0;
   if (i < s.V) {
     const float *P = verts + (size_t)mesh * s.V * 3;
-    const MrV3 vi = mr_load(P, i);
+    const MrV3 vi = load_v3<double>(P, i);
     double vw;
     bool ring;
     const MrV3 d = mr_residual<true>(s, P, i, vi, vw, edge, ring);
-    lap = vw * (d.x * d.x + d.y * d.y + d.z * d.z);
+    lap = vw * dot3(d, d);
   }
   lap = wave_sum_f64(lap);
   edge = wave_sum_f64(edge);
@@ -130,7 +127,7 @@ __global__ __launch_bounds__(MR_T) void meshreg_bwd_kernel(const float *__restri
   const float *P = verts + (size_t)mesh * s.V * 3;
   const double gl = (double)g[(size_t)mesh * 2] * 2.0 / (double)s.V;
   const double ge = E > 0 ? (double)g[(size_t)mesh * 2 + 1] * 4.0 / (double)E : 0.0;
-  const MrV3 vi = mr_load(P, i);
+  const MrV3 vi = load_v3<double>(P, i);
   double vw, unused = 0.0;
   bool ring;
   const MrV3 di = mr_residual<false>(s, P, i, vi, vw, unused, ring);
@@ -142,16 +139,16 @@ __global__ __launch_bounds__(MR_T) void meshreg_bwd_kernel(const float *__restri
   for (int e = e0; e < e1; ++e) {
     const int k = s.nb_idx[e];
     if ((unsigned)k >= (unsigned)s.V) continue;
-    const MrV3 vk = mr_load(P, k);
+    const MrV3 vk = load_v3<double>(P, k);
     const double wki = (double)s.nb_w[(size_t)e * 3 + 1], il2 = (double)s.nb_w[(size_t)e * 3 + 2];
     double vwk;
     const MrV3 dk = mr_residual<false>(s, P, k, vk, vwk, unused, ring);
     const double c = wki * vwk;
     ax -= c * dk.x; ay -= c * dk.y; az -= c * dk.z;
     if (il2 != 0.0) {
-      const double dx = vi.x - vk.x, dy = vi.y - vk.y, dz = vi.z - vk.z;
-      const double q = ((dx * dx + dy * dy + dz * dz) * il2 - 1.0) * il2;
-      bx += q * dx; by += q * dy; bz += q * dz;
+      const MrV3 d = vi - vk;
+      const double q = (dot3(d, d) * il2 - 1.0) * il2;
+      bx += q * d.x; by += q * d.y; bz += q * d.z;
     }
   }
   float *out = dverts + ((size_t)mesh * s.V + i) * 3;
@@ -161,12 +158,10 @@ __global__ __launch_bounds__(MR_T) void meshreg_bwd_kernel(const float *__restri
 }
 
 static int mr_check(const char *who, const float *verts, const int32_t *nb_off, const int32_t *nb_idx, const float *nb_w, int nnz,
-                    int E, int B, int V, long long *nwg) {
+                    int E, int B, int V, MeshGrid *mg) {
   SMPLR_REQUIRE(B >= 0 && V >= 1 && V <= (1 << 24) && nnz >= 0 && nnz <= (1 << 28) && E >= 0 && (long long)E * 2 <= nnz,
                 "%s: bad sizes B=%d V=%d nnz=%d E=%d (B >= 0, 1 <= V <= 2^24, 0 <= nnz <= 2^28, 0 <= 2 E <= nnz)", who, B, V, nnz, E);
-  const int nblk = (V + MR_T - 1) / MR_T;
-  *nwg = (long long)B * nblk;
-  SMPLR_REQUIRE(*nwg < (1ll << 31), "%s: B * ceil(V / %d) = %lld workgroups exceed 2^31", who, MR_T, *nwg);
+  if (mesh_grid(who, "V", B, V, MR_T, mg)) return SMPLR_EINVAL;
   if (B == 0) return 0;
   SMPLR_REQUIRE(verts && nb_off && (nnz == 0 || (nb_idx && nb_w)),
                 "%s: null pointer (verts and nb_off are required, nb_idx and nb_w with nnz > 0)", who);
@@ -184,17 +179,16 @@ int smplr_mesh_reg_fwd(const float *verts, const int32_t *nb_off, const int32_t 
                        const float *lap_ref, const float *vweight, int E, int B, int V, float *terms, void *workspace,
                        void *stream) {
   using namespace smplr;
-  long long nwg;
-  const int rc = mr_check("smplr_mesh_reg_fwd", verts, nb_off, nb_idx, nb_w, nnz, E, B, V, &nwg);
+  MeshGrid mg;
+  const int rc = mr_check("smplr_mesh_reg_fwd", verts, nb_off, nb_idx, nb_w, nnz, E, B, V, &mg);
   if (rc || B == 0) return rc;
   SMPLR_REQUIRE(terms && workspace, "smplr_mesh_reg_fwd: null pointer (terms and workspace are required)");
   SMPLR_REQUIRE(((uintptr_t)workspace & 7) == 0, "smplr_mesh_reg_fwd: the workspace must be 8-byte aligned");
-  const int nblk = (V + MR_T - 1) / MR_T;
   const MrSpec s = {reinterpret_cast<const int *>(nb_off), reinterpret_cast<const int *>(nb_idx), nb_w, lap_ref, vweight, V, nnz};
   double *part = static_cast<double *>(workspace);
-  hipLaunchKernelGGL(meshreg_fwd_kernel, dim3((unsigned)nwg), dim3(MR_T), 0, as_stream(stream), verts, s, B, nblk, part);
+  hipLaunchKernelGGL(meshreg_fwd_kernel, dim3((unsigned)mg.nwg), dim3(MR_T), 0, as_stream(stream), verts, s, B, mg.nblk, part);
   SMPLR_LAUNCH_CHECK("smplr_mesh_reg_fwd");
-  hipLaunchKernelGGL(meshreg_finish_kernel, dim3(B), dim3(WAVE), 0, as_stream(stream), part, B, V, E, nblk, terms);
+  hipLaunchKernelGGL(meshreg_finish_kernel, dim3(B), dim3(WAVE), 0, as_stream(stream), part, B, V, E, mg.nblk, terms);
   SMPLR_LAUNCH_CHECK("smplr_mesh_reg_fwd (finish)");
   return 0;
 }
@@ -203,13 +197,12 @@ int smplr_mesh_reg_bwd(const float *verts, const int32_t *nb_off, const int32_t 
                        const float *lap_ref, const float *vweight, int E, const float *g, int B, int V, float *dverts,
                        void *stream) {
   using namespace smplr;
-  long long nwg;
-  const int rc = mr_check("smplr_mesh_reg_bwd", verts, nb_off, nb_idx, nb_w, nnz, E, B, V, &nwg);
+  MeshGrid mg;
+  const int rc = mr_check("smplr_mesh_reg_bwd", verts, nb_off, nb_idx, nb_w, nnz, E, B, V, &mg);
   if (rc || B == 0) return rc;
   SMPLR_REQUIRE(g && dverts, "smplr_mesh_reg_bwd: null pointer (g and dverts are required)");
-  const int nblk = (V + MR_T - 1) / MR_T;
   const MrSpec s = {reinterpret_cast<const int *>(nb_off), reinterpret_cast<const int *>(nb_idx), nb_w, lap_ref, vweight, V, nnz};
-  hipLaunchKernelGGL(meshreg_bwd_kernel, dim3((unsigned)nwg), dim3(MR_T), 0, as_stream(stream), verts, s, E, g, B, nblk, dverts);
+  hipLaunchKernelGGL(meshreg_bwd_kernel, dim3((unsigned)mg.nwg), dim3(MR_T), 0, as_stream(stream), verts, s, E, g, B, mg.nblk, dverts);
   SMPLR_LAUNCH_CHECK("smplr_mesh_reg_bwd");
   return 0;
 }

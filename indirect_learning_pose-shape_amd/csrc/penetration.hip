@@ -9,21 +9,21 @@
 //   inside[i]  s_i = ((d_x n_x + d_y n_y) + d_z n_z) < 0 with d = v_i - v_near(i)
 //   e[i]       inside[i] ? d2[i] : 0
 //
-// pen_fwd_kernel has scan_m2p_kernel's shape: a workgroup of PN_T = 256 lanes owns 256 queries of one mesh, the mesh's
-// vertices stream through LDS in tiles of 256 as (x, y, z, part) that every lane walks with broadcast reads.
+// pen_fwd_kernel: a workgroup of PN_T = 256 lanes owns 256 queries of one mesh, the mesh's vertices stream through LDS in
+// tiles of 256 as (x, y, z, part) that every lane walks with broadcast reads.
 //   Search, fp32, m2p's arithmetic: e = v_j - v_i, d = (e_x e_x + e_y e_y) + e_z e_z; the pair counts when bit part[j] of the
 //   query's collide row is set (a candidate without a part carries part 31, a bit no row has); the winner is the minimum of
 //   (d, j) in lexicographic order, so it does not depend on the order of the walk.
 //   Finish, fp64, on the winner alone: d2, the normal through the CSR, the sign; each output rounded to fp32 once.
 // Pruning (PRUNE): queries and candidates walk in part-major order (`perm`, built once on the host: every part's vertices
 // padded with -1 to whole tiles, so a tile holds one part).  The loading lanes reduce, per tile, the mask of parts present and
-// a bounding sphere (centre = the middle of the bounding box, radius = the largest distance from it, inflated as in
-// scan.hip).  The tiles stream through twice, as scan_p2m_kernel's faces do: the first pass computes the spheres only and
-// takes, per lane, bound = min over the tiles whose every part the lane's row allows of |centre - v| + radius - no candidate of
-// such a tile is farther, so the nearest candidate is within it; the second pass walks a tile unless, for every lane of the
-// wave, the row misses the mask or `tile_far` proves that no candidate of the tile has an fp32 d <= what the lane's winner
-// will have - so a skipped tile could not have changed (best, near) and every output has the bits of the unpruned walk
-// (natural order, every tile).
+// a bounding sphere (centre = the middle of the bounding box, radius = the largest distance from it, inflated by
+// mesh_device.h's RADIUS_INFLATE).  The tiles stream through twice, as scan_p2m_kernel's faces do: the first pass computes
+// the spheres only and takes, per lane, bound = min over the tiles whose every part the lane's row allows of |centre - v| +
+// radius - no candidate of such a tile is farther, so the nearest candidate is within it; the second pass walks a tile
+// unless, for every lane of the wave, the row misses the mask or mesh_device.h's `sphere_far` proves that no candidate of the
+// tile has an fp32 d <= what the lane's winner will have - so a skipped tile could not have changed (best, near) and every
+// output has the bits of the unpruned walk (natural order, every tile).
 //
 // pen_bwd_kernel: one lane per (mesh, vertex k); acc = 2 g_k inside_k (v_k - v_near(k)), then the mesh's records (near_i,
 // g_i inside_i, v_i) stream through LDS in order and the lane subtracts 2 g_i (v_i - v_k) wherever near_i = k and i is inside,
@@ -33,7 +33,7 @@
 // A mesh with a coordinate that is not finite has SMPLR_PEN_NONFINITE in status, NaN in e, d2 and its dverts rows, near -1 and
 // inside 0; the other meshes are untouched.  Every index read from memory is range-checked: an entry of perm, a CSR offset,
 // face or corner outside its range is skipped, a recorded near outside [0, V) adds nothing.
-#include "common.h"
+#include "mesh_device.h"
 
 #pragma clang fp contract(off)
 
@@ -43,56 +43,7 @@ namespace {
 constexpr int PN_T = 256;          // lanes per workgroup = entries per LDS tile
 constexpr int PN_NOPART = 31;      // the part a candidate without one carries: no collide row has bit 31 (P <= 31)
 
-struct D3 { double x, y, z; };
 __device__ __forceinline__ float dot3f(float x, float y, float z) { return (x * x + y * y) + z * z; }
-__device__ __forceinline__ D3 load_d3(const float *__restrict__ P, int i) {
-  return {(double)P[(size_t)i * 3], (double)P[(size_t)i * 3 + 1], (double)P[(size_t)i * 3 + 2]};
-}
-
-// 1 when a coordinate of the mesh is not finite; the same value in every lane of the workgroup.
-__device__ __forceinline__ int pen_mesh_nonfinite(const float *__restrict__ P, int V) {
-  int bad = 0;
-  for (size_t i = threadIdx.x; i < (size_t)V * 3; i += PN_T) bad |= !finitef(P[i]);
-  return __syncthreads_or(bad);
-}
-
-__device__ __forceinline__ float wave_min_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ unsigned wave_or_u(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v |= (unsigned)__shfl_xor((int)v, o, 64);
-  return v;
-}
-
-// The sphere test of the pruned walk, scan.hip's `sphere_far` with one more factor.  The tile's (centre c, radius r) are
-// fp32 numbers with r >= max_j |v_j - c| in exact arithmetic over the tile's candidates (the fp32 radius is inflated by
-// 1 + 2^-20 = 1 + 16 u, above the 5 u of its sum of squares and the 1.5 u of its root, u = 2^-24), so every candidate is at
-// least sqrt(S) - r from the query v, S = |c - v|^2 exactly.  The tile is skipped when s > fl(fl(h h) m) with
-// s = fl(|fl(c - v)|^2) <= S (1 + 6 u), h = fl(r + fl(sqrt(best))) >= (r + sqrt(best)) (1 - 2 u)(1 - u), m = 1 + 2^-19 =
-// 1 + 32 u.  Then S > (r + sqrt(best))^2 (1 - 8 u)(1 + 32 u) / (1 + 6 u) > (r + sqrt(best))^2 (1 + 17 u), so every candidate's
-// exact squared distance D^2 >= (sqrt(S) - r)^2 > best (1 + 17 u), and the fp32 number the walk would have compared,
-// d = fl(|fl(v_j - v)|^2) >= D^2 (1 - 6 u) > best (1 + 17 u)(1 - 6 u) > best: strictly greater, so the candidate could neither
-// win nor tie.  An infinite best (nothing found yet) makes h and the right side infinite: the comparison is false and the
-// tile is walked; coordinates so large that s overflows give s = +Inf against +Inf, false as well.
-// The first pass's bound enters as best_root too (the smaller of the two): it is fl(fl(sqrt(s)) + r) >= (sqrt(S) + r)(1 - 5 u),
-// inflated by 1 + 16 u, so it is no smaller than the true distance D_far of the farthest candidate of its tile, all of which
-// are candidates of the lane; the lane's final winner has an fp32 d_w <= that of the nearest candidate <= D_far^2 (1 + 6 u),
-// while a tile skipped against the bound has every d > D_far^2 (1 + 17 u)(1 - 6 u) > D_far^2 (1 + 6 u) >= d_w: it could neither
-// win nor tie.  The tile that gave the bound passes its own test (s <= bound^2), so some tile is always walked.
-constexpr float PN_RADIUS_INFLATE = 1.0f + 0x1p-20f;
-constexpr float PN_SPHERE_MARGIN = 1.0f + 0x1p-19f;
-__device__ __forceinline__ bool tile_far(const float4 &sph, float vx, float vy, float vz, float best_root) {
-  const float s = dot3f(sph.x - vx, sph.y - vy, sph.z - vz), h = sph.w + best_root;
-  return s > (h * h) * PN_SPHERE_MARGIN;
-}
 
 // One tile: lane tid loads slot t0 + tid of the walk (vertex perm[slot], or slot itself), with STORE into LDS.  With PRUNE
 // the tile's part mask and its bounding sphere over the candidates that have a part come back in every lane (wave
@@ -146,7 +97,7 @@ __device__ __forceinline__ bool load_tile(const float *__restrict__ Pm, const in
   const float r2 = wave_max_f(valid ? dot3f(c.x - sph.x, c.y - sph.y, c.z - sph.z) : 0.f);
   if ((tid & (WAVE - 1)) == 0) s_red[w][7] = r2;
   __syncthreads();
-  sph.w = sqrtf(fmaxf(fmaxf(s_red[0][7], s_red[1][7]), fmaxf(s_red[2][7], s_red[3][7]))) * PN_RADIUS_INFLATE;
+  sph.w = sqrtf(fmaxf(fmaxf(s_red[0][7], s_red[1][7]), fmaxf(s_red[2][7], s_red[3][7]))) * RADIUS_INFLATE;
   return mask != 0;
 }
 
@@ -173,7 +124,7 @@ __global__ __launch_bounds__(PN_T) void pen_fwd_kernel(const float *__restrict__
     s_rows[tid] = r;
   }
   const float *Pm = verts + (size_t)mesh * V * 3;
-  const int bad = pen_mesh_nonfinite(Pm, V);                  // (a barrier: s_rows is visible after it)
+  const int bad = mesh_nonfinite<PN_T>(Pm, V);                // (a barrier: s_rows is visible after it)
   if (blk == 0 && tid == 0) status[mesh] = bad ? SMPLR_PEN_NONFINITE : 0;
   const int slot = blk * PN_T + tid;
   int i = slot < T ? (PRUNE ? perm[slot] : slot) : -1;
@@ -201,7 +152,7 @@ __global__ __launch_bounds__(PN_T) void pen_fwd_kernel(const float *__restrict__
         unsigned mask;
         if (!load_tile<true, false>(Pm, part, perm, V, P, T, t0, tid, t_c, t_j, s_red, sph, mask)) continue;
         if (search && (mask & ~row) == 0)
-          bound = fminf(bound, (sqrtf(dot3f(sph.x - vx, sph.y - vy, sph.z - vz)) + sph.w) * PN_RADIUS_INFLATE);
+          bound = fminf(bound, (sqrtf(dot3f(sph.x - vx, sph.y - vy, sph.z - vz)) + sph.w) * RADIUS_INFLATE);
       }
     }
     for (int t0 = 0; t0 < T; t0 += PN_T) {
@@ -212,7 +163,7 @@ __global__ __launch_bounds__(PN_T) void pen_fwd_kernel(const float *__restrict__
       bool want = search;
       if (PRUNE) {
         if (!any) continue;                                   // (uniform) no candidate with a part in this tile
-        want = search && (row & mask) != 0 && !tile_far(sph, vx, vy, vz, fminf(bound, sqrtf(best)));
+        want = search && (row & mask) != 0 && !sphere_far(sph, V3<float>{vx, vy, vz}, fminf(bound, sqrtf(best)));
         if (!__any(want)) continue;                           // (wave-uniform; every barrier of the tile is behind us)
       }
       if (want) {
@@ -238,10 +189,9 @@ __global__ __launch_bounds__(PN_T) void pen_fwd_kernel(const float *__restrict__
     bj = -1;
   } else if (bj >= 0) {
     // the finish in fp64 on the fp32 coordinates: d2, the winner's normal through the CSR, the sign
-    const D3 vi = load_d3(Pm, i), vj = load_d3(Pm, bj);
-    const D3 d = {vi.x - vj.x, vi.y - vj.y, vi.z - vj.z};
-    const double dd = (d.x * d.x + d.y * d.y) + d.z * d.z;
-    D3 n = {0.0, 0.0, 0.0};
+    const V3<double> d = load_v3<double>(Pm, i) - load_v3<double>(Pm, bj);
+    const double dd = dot3(d, d);
+    double nx = 0.0, ny = 0.0, nz = 0.0;
     const int k0 = vf_off[bj], k1 = vf_off[bj + 1];
     if (k0 >= 0 && k1 >= k0 && (long long)k1 <= 3ll * F) {
       for (int k = k0; k < k1; ++k) {
@@ -249,14 +199,15 @@ __global__ __launch_bounds__(PN_T) void pen_fwd_kernel(const float *__restrict__
         if ((unsigned)f >= (unsigned)F) continue;
         const int ia = faces[(size_t)f * 3], ib = faces[(size_t)f * 3 + 1], ic = faces[(size_t)f * 3 + 2];
         if ((unsigned)ia >= (unsigned)V || (unsigned)ib >= (unsigned)V || (unsigned)ic >= (unsigned)V) continue;
-        const D3 a = load_d3(Pm, ia), b = load_d3(Pm, ib), c = load_d3(Pm, ic);
-        const D3 u = {b.x - a.x, b.y - a.y, b.z - a.z}, w = {c.x - a.x, c.y - a.y, c.z - a.z};
-        n.x += u.y * w.z - u.z * w.y;
-        n.y += u.z * w.x - u.x * w.z;
-        n.z += u.x * w.y - u.y * w.x;
+        // (cross3(b - a, c - a), written out: through the shared operators this loop takes other registers)
+        const V3<double> a = load_v3<double>(Pm, ia), b = load_v3<double>(Pm, ib), c = load_v3<double>(Pm, ic);
+        const V3<double> u = {b.x - a.x, b.y - a.y, b.z - a.z}, w = {c.x - a.x, c.y - a.y, c.z - a.z};
+        nx += u.y * w.z - u.z * w.y;
+        ny += u.z * w.x - u.x * w.z;
+        nz += u.x * w.y - u.y * w.x;
       }
     }
-    const double s = (d.x * n.x + d.y * n.y) + d.z * n.z;
+    const double s = dot3(d, V3<double>{nx, ny, nz});
     o_in = s < 0.0;
     o_d2 = (float)dd;
     o_e = o_in ? o_d2 : 0.f;
@@ -282,13 +233,13 @@ __global__ __launch_bounds__(PN_T) void pen_bwd_kernel(const float *__restrict__
   const float *Pm = verts + (size_t)mesh * V * 3;
   const size_t base = (size_t)mesh * V;
   double ax = 0.0, ay = 0.0, az = 0.0;
-  D3 vk = {0.0, 0.0, 0.0};
+  V3<double> vk = {0.0, 0.0, 0.0};
   if (!bad) {                                                 // (the same in every lane)
     if (mine) {
-      vk = load_d3(Pm, k);
+      vk = load_v3<double>(Pm, k);
       const int j = near[base + k];
       if (inside[base + k] && (unsigned)j < (unsigned)V) {     // the own term first
-        const D3 vj = load_d3(Pm, j);
+        const V3<double> vj = load_v3<double>(Pm, j);
         const double c = 2.0 * (double)g[base + k];
         ax = c * (vk.x - vj.x);
         ay = c * (vk.y - vj.y);
@@ -353,21 +304,20 @@ int smplr_pen_fwd(const float *verts, const int32_t *faces, const int32_t *vf_of
   const char *env = getenv("SMPLR_PEN_UNPRUNED");
   const bool prune = perm && !(env && env[0] && !(env[0] == '0' && !env[1]));
   const int T = prune ? nperm : V;                            // slots of the walk: the padded part-major order, or the vertices
-  const int nblk = (T + PN_T - 1) / PN_T;
-  SMPLR_REQUIRE((long long)B * nblk < (1ll << 31), "smplr_pen_fwd: B * ceil(slots / %d) = %lld workgroups exceed 2^31", PN_T,
-                (long long)B * nblk);
+  MeshGrid mg;
+  if (mesh_grid("smplr_pen_fwd", "slots", B, T, PN_T, &mg)) return SMPLR_EINVAL;
   if (B == 0) return 0;
   SMPLR_REQUIRE(verts && (faces || F == 0) && vf_off && (vf_face || F == 0) && part && (collide || P == 0) && e && d2 && near &&
                     inside && status,
                 "smplr_pen_fwd: null pointer (verts, faces, vf_off, vf_face, part, collide, e, d2, near, inside and status are "
                 "required)");
-  const dim3 grid((unsigned)((long long)B * nblk)), block(PN_T);
+  const dim3 grid((unsigned)mg.nwg), block(PN_T);
   if (prune)
     hipLaunchKernelGGL(pen_fwd_kernel<true>, grid, block, 0, as_stream(stream), verts, faces, vf_off, vf_face, part, collide, perm,
-                       B, V, F, P, T, nblk, e, d2, reinterpret_cast<int *>(near), inside, reinterpret_cast<int *>(status));
+                       B, V, F, P, T, mg.nblk, e, d2, reinterpret_cast<int *>(near), inside, reinterpret_cast<int *>(status));
   else
     hipLaunchKernelGGL(pen_fwd_kernel<false>, grid, block, 0, as_stream(stream), verts, faces, vf_off, vf_face, part, collide, perm,
-                       B, V, F, P, T, nblk, e, d2, reinterpret_cast<int *>(near), inside, reinterpret_cast<int *>(status));
+                       B, V, F, P, T, mg.nblk, e, d2, reinterpret_cast<int *>(near), inside, reinterpret_cast<int *>(status));
   SMPLR_LAUNCH_CHECK("smplr_pen_fwd");
   return 0;
 }
@@ -376,14 +326,13 @@ int smplr_pen_bwd(const float *verts, const int32_t *near, const uint8_t *inside
                   int V, float *dverts, void *stream) {
   using namespace smplr;
   PEN_SIZES("smplr_pen_bwd");
-  const int nblk = (V + PN_T - 1) / PN_T;
-  SMPLR_REQUIRE((long long)B * nblk < (1ll << 31), "smplr_pen_bwd: B * ceil(V / %d) = %lld workgroups exceed 2^31", PN_T,
-                (long long)B * nblk);
+  MeshGrid mg;
+  if (mesh_grid("smplr_pen_bwd", "V", B, V, PN_T, &mg)) return SMPLR_EINVAL;
   if (B == 0) return 0;
   SMPLR_REQUIRE(verts && near && inside && status && g && dverts,
                 "smplr_pen_bwd: null pointer (verts, near, inside, status, g and dverts are required)");
-  hipLaunchKernelGGL(pen_bwd_kernel, dim3((unsigned)((long long)B * nblk)), dim3(PN_T), 0, as_stream(stream), verts,
-                     reinterpret_cast<const int *>(near), inside, reinterpret_cast<const int *>(status), g, B, V, nblk, dverts);
+  hipLaunchKernelGGL(pen_bwd_kernel, dim3((unsigned)mg.nwg), dim3(PN_T), 0, as_stream(stream), verts,
+                     reinterpret_cast<const int *>(near), inside, reinterpret_cast<const int *>(status), g, B, V, mg.nblk, dverts);
   SMPLR_LAUNCH_CHECK("smplr_pen_bwd");
   return 0;
 }

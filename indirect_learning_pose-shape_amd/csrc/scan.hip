@@ -14,8 +14,8 @@
 //   (centre, radius) that the loading lane computed.  The faces stream through twice: the first walk reads the spheres only
 //   and takes bound = |centre_f - p| + radius_f of the face with the nearest centre, which no point of that face exceeds, so
 //   the nearest face is within it; the second walk runs the closest-point evaluation only when |centre - p|^2 <= (radius + min(bound, sqrt(best)))^2
-//   (1 + 2^-19) in fp32 - see `sphere_far` for why that margin is conservative.  Without the first walk `best` starts at
-//   infinity and a wave whose 64 points lie apart evaluates nearly every face for some lane (2 048 unsorted points against
+//   (1 + 2^-19) in fp32 - mesh_device.h's `sphere_far`, with the proof that the margin is conservative.  Without the first
+//   walk `best` starts at infinity and a wave whose 64 points lie apart evaluates nearly every face for some lane (2 048 unsorted points against
 //   one mesh of 13 776 faces: 11.2 ms without it, 3.0 ms with it).
 //   Finish, fp64, on the winner alone: q, the weights and the distance are recomputed by the same `closest_point` in double
 //   on the fp32 inputs, and each output is rounded to fp32 once - correctly rounded for the chosen index, whatever the
@@ -35,17 +35,13 @@
 // gradient and is no candidate for m2p; points at or beyond counts[b] have zero outputs and face -1.  Every index read from
 // memory is range-checked: a face with a corner outside [0, V) is skipped, a recorded face or point outside its range adds
 // nothing.
-#include "common.h"
+#include "mesh_device.h"
 
 #pragma clang fp contract(off)
 
 namespace smplr {
 
 constexpr int SC_T = 256;          // lanes per workgroup = entries per LDS tile
-
-template <typename T> struct V3 { T x, y, z; };
-template <typename T> __device__ __forceinline__ V3<T> operator-(const V3<T> &a, const V3<T> &b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-template <typename T> __device__ __forceinline__ T dot3(const V3<T> &a, const V3<T> &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
 // The closest point to the ORIGIN of the segment A B, as the weight of B: t = clamp(-(A . E) / (E . E)), 0 for E = 0.
 template <typename T> __device__ __forceinline__ T seg_weight(const V3<T> &A, const V3<T> &Bv) {
@@ -98,34 +94,12 @@ template <typename T, bool FULL> __device__ __forceinline__ Closest<T> closest_p
   return r;
 }
 
-// 1 when a coordinate of the mesh is not finite; the same value in every lane of the workgroup.
-__device__ __forceinline__ int mesh_nonfinite(const float *__restrict__ P, int V) {
-  int bad = 0;
-  for (size_t i = threadIdx.x; i < (size_t)V * 3; i += SC_T) bad |= !finitef(P[i]);
-  return __syncthreads_or(bad);
-}
 __device__ __forceinline__ int used_points(const int *__restrict__ counts, int mesh, int N) {
   return counts ? min(max(counts[mesh], 0), N) : N;
 }
 
-// The sphere test of the p2m search.  The tile's (centre, radius) are fp32 numbers with radius >= max_k |v_k - centre| in
-// exact arithmetic (the loader inflates its fp32 radius by 1 + 2^-20, above the 5 u of its sum of squares and the 1.5 u of
-// its root, u = 2^-24), so every point of the face is at least sqrt(S) - radius away, S = |centre - p|^2 exactly.  The
-// face is skipped when s > fl(fl(h h) m), s = fl(|fl(centre - p)|^2) <= S (1 + 6 u), h = fl(radius + fl(sqrt(best))) >=
-// (radius + sqrt(best)) (1 - 2 u)(1 - u), m = 1 + 2^-19 = 1 + 32 u: then S > (radius + sqrt(best))^2 (1 - 8 u)(1 + 32 u) /
-// (1 + 6 u) > (radius + sqrt(best))^2, so the face's true distance exceeds sqrt(best) and it could not have won.  An
-// infinite best or a NaN makes the comparison false: the face is evaluated.  The first walk's bound enters as best_root:
-// fl(fl(sqrt(s)) + radius) >= (sqrt(S) + radius) (1 - 5 u), inflated by 1 + 2^-20 like the radius, so it is no smaller than
-// the farthest point of its face, the nearest face lies within it and is never skipped; the face that gave the bound
-// passes its own test (s <= bound^2, the same s in both walks), so at least one face is always evaluated.  (The bound is
-// taken from the face with the nearest centre - any face's bound is one - which costs one root per point, not one per pair.)
-constexpr float SC_RADIUS_INFLATE = 1.0f + 0x1p-20f;
-constexpr float SC_SPHERE_MARGIN = 1.0f + 0x1p-19f;
-__device__ __forceinline__ bool sphere_far(const float4 &sph, const V3<float> &p, float best_root) {
-  const V3<float> e = {sph.x - p.x, sph.y - p.y, sph.z - p.z};
-  const float s = dot3(e, e), h = sph.w + best_root;
-  return s > (h * h) * SC_SPHERE_MARGIN;
-}
+// The sphere test of the p2m search is mesh_device.h's `sphere_far`.  The bound of the first walk is taken from the face
+// with the nearest centre - any face's bound is one - which costs one root per point, not one per pair.
 
 // One lane's face of a tile: the corners gathered from the mesh, the sphere around their mean.  A face that names a vertex
 // outside [0, V), and the lanes past the last face, store radius -1 and a centre at 1e30 (farther than any face that counts;
@@ -145,7 +119,7 @@ __device__ __forceinline__ void load_face_tile(const float *__restrict__ P, cons
       const V3<float> e0 = {c0.x - m.x, c0.y - m.y, c0.z - m.z}, e1 = {c1.x - m.x, c1.y - m.y, c1.z - m.z},
                       e2 = {c2.x - m.x, c2.y - m.y, c2.z - m.z};
       const float r2 = fmaxf(dot3(e0, e0), fmaxf(dot3(e1, e1), dot3(e2, e2)));
-      sph = {m.x, m.y, m.z, sqrtf(r2) * SC_RADIUS_INFLATE};
+      sph = {m.x, m.y, m.z, sqrtf(r2) * RADIUS_INFLATE};
     }
   }
   t_sph[tid] = sph;
@@ -168,7 +142,7 @@ __global__ __launch_bounds__(SC_T) void scan_p2m_kernel(const float *__restrict_
   if (mesh >= B) return;
   const int n = blk * SC_T + tid;
   const float *P = verts + (size_t)mesh * V * 3;
-  const int bad = mesh_nonfinite(P, V);
+  const int bad = mesh_nonfinite<SC_T>(P, V);
   if (blk == 0 && tid == 0) status[mesh] = bad ? SMPLR_SCAN_NONFINITE : 0;
   const int cnt = used_points(counts, mesh, N);
   const bool inrange = n < N, used = n < cnt;
@@ -192,14 +166,14 @@ __global__ __launch_bounds__(SC_T) void scan_p2m_kernel(const float *__restrict_
 #pragma unroll 8
         for (int j = 0; j < SC_T; ++j) {
           const float4 s = t_sph[j];
-          const V3<float> e = {s.x - p.x, s.y - p.y, s.z - p.z};
+          const V3<float> e = xyz(s) - p;
           const float ss = dot3(e, e);
           r_min = ss < s_min ? s.w : r_min;
           s_min = fminf(s_min, ss);
         }
       }
     }
-    best_root = r_min >= 0.f ? (sqrtf(s_min) + r_min) * SC_RADIUS_INFLATE : inf;
+    best_root = r_min >= 0.f ? (sqrtf(s_min) + r_min) * RADIUS_INFLATE : inf;
     // second walk: the evaluation where the sphere test cannot rule the face out
     for (int f0 = 0; f0 < F; f0 += SC_T) {
       __syncthreads();
@@ -210,9 +184,7 @@ __global__ __launch_bounds__(SC_T) void scan_p2m_kernel(const float *__restrict_
         for (int j = 0; j < SC_T; ++j) {
           const float4 s = t_sph[j];
           if (s.w < 0.f || sphere_far(s, p, best_root)) continue;
-          const float4 a = t_c[0][j], b = t_c[1][j], c = t_c[2][j];
-          const V3<float> A = {a.x - p.x, a.y - p.y, a.z - p.z}, Bv = {b.x - p.x, b.y - p.y, b.z - p.z},
-                          C = {c.x - p.x, c.y - p.y, c.z - p.z};
+          const V3<float> A = xyz(t_c[0][j]) - p, Bv = xyz(t_c[1][j]) - p, C = xyz(t_c[2][j]) - p;
           const float d = closest_point<float, false>(A, Bv, C).d2;
           if (d < best || bf < 0) {
             best = d;
@@ -235,9 +207,7 @@ __global__ __launch_bounds__(SC_T) void scan_p2m_kernel(const float *__restrict_
     // the finish: the same evaluation in fp64 on the fp32 inputs of the chosen face (its corners passed the range check)
     const int i0 = faces[(size_t)bf * 3], i1 = faces[(size_t)bf * 3 + 1], i2 = faces[(size_t)bf * 3 + 2];
     const V3<double> pd = {(double)p.x, (double)p.y, (double)p.z};
-    const V3<double> A = V3<double>{(double)P[(size_t)i0 * 3], (double)P[(size_t)i0 * 3 + 1], (double)P[(size_t)i0 * 3 + 2]} - pd;
-    const V3<double> Bv = V3<double>{(double)P[(size_t)i1 * 3], (double)P[(size_t)i1 * 3 + 1], (double)P[(size_t)i1 * 3 + 2]} - pd;
-    const V3<double> C = V3<double>{(double)P[(size_t)i2 * 3], (double)P[(size_t)i2 * 3 + 1], (double)P[(size_t)i2 * 3 + 2]} - pd;
+    const V3<double> A = load_v3<double>(P, i0) - pd, Bv = load_v3<double>(P, i1) - pd, C = load_v3<double>(P, i2) - pd;
     const Closest<double> r = closest_point<double, true>(A, Bv, C);
     o_d2 = (float)r.d2;
     o_b[0] = (float)r.w0; o_b[1] = (float)r.w1; o_b[2] = (float)r.w2;
@@ -263,13 +233,13 @@ __global__ __launch_bounds__(SC_T) void scan_m2p_kernel(const float *__restrict_
   const int i = blk * SC_T + tid;
   const float *P = verts + (size_t)mesh * V * 3;
   const float *Q = points + (size_t)mesh * N * 3;
-  const int bad = mesh_nonfinite(P, V);
+  const int bad = mesh_nonfinite<SC_T>(P, V);
   if (blk == 0 && tid == 0) status[mesh] = bad ? SMPLR_SCAN_NONFINITE : 0;
   const int cnt = used_points(counts, mesh, N);
   const bool mine = i < V;
   const float inf = __int_as_float(0x7f800000);
   V3<float> v = {0.f, 0.f, 0.f};
-  if (mine) v = {P[(size_t)i * 3], P[(size_t)i * 3 + 1], P[(size_t)i * 3 + 2]};
+  if (mine) v = load_v3<float>(P, i);
   float best = inf;
   int bi = -1;
   if (!bad) {
@@ -288,7 +258,7 @@ __global__ __launch_bounds__(SC_T) void scan_m2p_kernel(const float *__restrict_
         for (int j = 0; j < m; ++j) {
           const float4 q4 = t_p[j];
           if (q4.w == 0.f) continue;                         // (wave-uniform)
-          const V3<float> e = {q4.x - v.x, q4.y - v.y, q4.z - v.z};
+          const V3<float> e = xyz(q4) - v;
           const float d = dot3(e, e);
           if (d < best || bi < 0) {
             best = d;
@@ -305,8 +275,7 @@ __global__ __launch_bounds__(SC_T) void scan_m2p_kernel(const float *__restrict_
     out = __int_as_float(0x7fc00000);
     bi = -1;
   } else if (bi >= 0) {
-    const V3<double> e = V3<double>{(double)v.x, (double)v.y, (double)v.z} -
-                         V3<double>{(double)Q[(size_t)bi * 3], (double)Q[(size_t)bi * 3 + 1], (double)Q[(size_t)bi * 3 + 2]};
+    const V3<double> e = V3<double>{(double)v.x, (double)v.y, (double)v.z} - load_v3<double>(Q, bi);
     out = (float)dot3(e, e);
   }
   vd2[o] = out;
@@ -397,14 +366,13 @@ int smplr_scan_p2m(const float *verts, const int32_t *faces, const float *points
                    int N, float *d2, int32_t *face, float *bary, float *resid, int32_t *status, void *stream) {
   using namespace smplr;
   SCAN_SIZES("smplr_scan_p2m", true);
-  const int nblk = N > 0 ? (N + SC_T - 1) / SC_T : 1;        // (N = 0: one workgroup per mesh still writes status)
-  SMPLR_REQUIRE((long long)B * nblk < (1ll << 31), "smplr_scan_p2m: B * ceil(N / %d) = %lld workgroups exceed 2^31", SC_T,
-                (long long)B * nblk);
+  MeshGrid mg;                                             // (N = 0: one workgroup per mesh still writes status)
+  if (mesh_grid("smplr_scan_p2m", "N", B, N > 0 ? N : 1, SC_T, &mg)) return SMPLR_EINVAL;
   if (B == 0) return 0;
   SMPLR_REQUIRE(verts && (faces || F == 0) && status && (N == 0 || (points && d2 && face && bary && resid)),
                 "smplr_scan_p2m: null pointer (verts, faces, points, d2, face, bary, resid and status are required)");
-  hipLaunchKernelGGL(scan_p2m_kernel, dim3((unsigned)((long long)B * nblk)), dim3(SC_T), 0, as_stream(stream), verts, faces,
-                     points, counts, B, V, F, N, nblk, d2, reinterpret_cast<int *>(face), bary, resid,
+  hipLaunchKernelGGL(scan_p2m_kernel, dim3((unsigned)mg.nwg), dim3(SC_T), 0, as_stream(stream), verts, faces,
+                     points, counts, B, V, F, N, mg.nblk, d2, reinterpret_cast<int *>(face), bary, resid,
                      reinterpret_cast<int *>(status));
   SMPLR_LAUNCH_CHECK("smplr_scan_p2m");
   return 0;
@@ -415,14 +383,13 @@ int smplr_scan_m2p(const float *verts, const float *points, const int32_t *count
   using namespace smplr;
   const int F = 0;
   SCAN_SIZES("smplr_scan_m2p", false);
-  const int nblk = (V + SC_T - 1) / SC_T;
-  SMPLR_REQUIRE((long long)B * nblk < (1ll << 31), "smplr_scan_m2p: B * ceil(V / %d) = %lld workgroups exceed 2^31", SC_T,
-                (long long)B * nblk);
+  MeshGrid mg;
+  if (mesh_grid("smplr_scan_m2p", "V", B, V, SC_T, &mg)) return SMPLR_EINVAL;
   if (B == 0) return 0;
   SMPLR_REQUIRE(verts && (points || N == 0) && vd2 && vpoint && status,
                 "smplr_scan_m2p: null pointer (verts, points, vd2, vpoint and status are required)");
-  hipLaunchKernelGGL(scan_m2p_kernel, dim3((unsigned)((long long)B * nblk)), dim3(SC_T), 0, as_stream(stream), verts, points,
-                     counts, B, V, N, nblk, vd2, reinterpret_cast<int *>(vpoint), reinterpret_cast<int *>(status));
+  hipLaunchKernelGGL(scan_m2p_kernel, dim3((unsigned)mg.nwg), dim3(SC_T), 0, as_stream(stream), verts, points,
+                     counts, B, V, N, mg.nblk, vd2, reinterpret_cast<int *>(vpoint), reinterpret_cast<int *>(status));
   SMPLR_LAUNCH_CHECK("smplr_scan_m2p");
   return 0;
 }
@@ -432,17 +399,16 @@ int smplr_scan_bwd(const float *verts, const int32_t *faces, const float *points
                    int B, int V, int F, int N, float *dverts, void *stream) {
   using namespace smplr;
   SCAN_SIZES("smplr_scan_bwd", true);
-  const int nblk = (V + SC_T - 1) / SC_T;
-  SMPLR_REQUIRE((long long)B * nblk < (1ll << 31), "smplr_scan_bwd: B * ceil(V / %d) = %lld workgroups exceed 2^31", SC_T,
-                (long long)B * nblk);
+  MeshGrid mg;
+  if (mesh_grid("smplr_scan_bwd", "V", B, V, SC_T, &mg)) return SMPLR_EINVAL;
   if (B == 0) return 0;
   SMPLR_REQUIRE(verts && status && dverts, "smplr_scan_bwd: null pointer (verts, status and dverts are required)");
   SMPLR_REQUIRE(!g_d2 || N == 0 || ((faces || F == 0) && face && bary && resid),
                 "smplr_scan_bwd: null pointer (g_d2 needs faces, face, bary and resid)");
   SMPLR_REQUIRE(!g_vd2 || N == 0 || (points && vpoint), "smplr_scan_bwd: null pointer (g_vd2 needs points and vpoint)");
-  hipLaunchKernelGGL(scan_bwd_kernel, dim3((unsigned)((long long)B * nblk)), dim3(SC_T), 0, as_stream(stream), verts, faces,
+  hipLaunchKernelGGL(scan_bwd_kernel, dim3((unsigned)mg.nwg), dim3(SC_T), 0, as_stream(stream), verts, faces,
                      points, reinterpret_cast<const int *>(face), bary, resid, reinterpret_cast<const int *>(vpoint),
-                     reinterpret_cast<const int *>(status), g_d2, g_vd2, B, V, F, N, nblk, dverts);
+                     reinterpret_cast<const int *>(status), g_d2, g_vd2, B, V, F, N, mg.nblk, dverts);
   SMPLR_LAUNCH_CHECK("smplr_scan_bwd");
   return 0;
 }

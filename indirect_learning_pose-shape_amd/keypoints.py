@@ -41,6 +41,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream
+from ._mesh_common import check_verts, nan_rows
 
 NONFINITE = 1          # SMPLR_KP_NONFINITE
 MAX_JOINTS = 64
@@ -189,7 +190,7 @@ def keypoint_energy_torch(verts, cam, spec, target, conf, sigma=None, joints=Non
     e = torch.where(counted, torch.where(counted, conf.to(f64), zero) * _rho((rc * rc).sum(-1), s2), zero)
     bad = ~torch.isfinite(c).all(1) | (counted & (jbad | ~torch.isfinite(t).all(-1))).any(1)
     b1, b2 = bad[:, None] | jbad, (bad[:, None] | jbad)[..., None]                    # (a joint of non-finite sources: NaN)
-    return {"e": torch.where(bad[:, None], nan, e), "d2": torch.where(b1, nan, d2), "proj": torch.where(b2, nan, p),
+    return {"e": nan_rows(bad, e), "d2": torch.where(b1, nan, d2), "proj": torch.where(b2, nan, p),
             "joints": torch.where(b2, nan, J), "ws": torch.cat([J[..., :2], r], -1).detach(),
             "status": bad.to(torch.int32) * NONFINITE}
 
@@ -199,7 +200,6 @@ def _backward_torch(spec, cam, conf, ws, status, g, s2, num_sources):
     f64 = torch.float64
     d = spec.on(cam.device)
     zero = torch.zeros((), dtype=f64, device=cam.device)
-    nan = torch.full((), float("nan"), dtype=f64, device=cam.device)
     counted = conf > 0
     Jxy, r = ws[..., :2], ws[..., 2:]
     c = g.to(f64) * conf.to(f64) * _drho((r * r).sum(-1), s2)
@@ -209,7 +209,7 @@ def _backward_torch(spec, cam, conf, ws, status, g, s2, num_sources):
     dsrc = torch.einsum("ks,bkc->bsc", d["dense"][:, :num_sources], dJ)
     dcam = torch.cat([(q * Jxy).sum(1), q.sum(1)], -1)
     bad = status != 0
-    return (torch.where(bad[:, None, None], nan, dsrc).to(torch.float32), torch.where(bad[:, None], nan, dcam).to(torch.float32))
+    return nan_rows(bad, dsrc).to(torch.float32), nan_rows(bad, dcam).to(torch.float32)
 
 
 class _KeypointFn(torch.autograd.Function):
@@ -281,11 +281,7 @@ def keypoint_energy(verts, cam, spec, target, conf, sigma=None, joints=None, ret
     autograd."""
     if not isinstance(spec, KeypointSpec):
         raise TypeError("spec must be a KeypointSpec")
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 3 or verts.shape[2] != 3:
-        raise ValueError("verts must be a (B, V, 3) tensor")
-    B, V, K = int(verts.shape[0]), int(verts.shape[1]), spec.K
-    if V != spec.num_verts:
-        raise ValueError("verts have %d vertices, the spec %d" % (V, spec.num_verts))
+    (B, V), K = check_verts(verts, spec=spec), spec.K
     if spec.with_joints != (joints is not None):
         raise ValueError("joints (J_transformed) go with a spec built with_joints=True, and only with it")
     shapes = [("cam", cam, (B, 4)), ("target", target, (B, K, 2)), ("conf", conf, (B, K))]

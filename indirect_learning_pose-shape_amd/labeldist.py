@@ -44,6 +44,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream
+from ._mesh_common import check_verts, nan_rows
 from .keypoints import check_sigma
 
 NONFINITE = 1          # SMPLR_LD_NONFINITE
@@ -224,19 +225,17 @@ def label_distance_torch(verts, cam, spec, targets, vweight=None, sigma=None, sl
     bad = ~torch.isfinite(c).all(1) | (counted & ~(torch.isfinite(X) & torch.isfinite(Y))).any(1)
     live = counted & ~bad[:, None]
     zero = torch.zeros((), dtype=f64, device=dev)
-    nan = torch.full((), float("nan"), dtype=f64, device=dev)
     inf = torch.full((), float("inf"), dtype=f64, device=dev)
     # (what the energies are made of: a vertex that is not live contributes neither a value nor a NaN to any gradient)
     pu = c[:, 2, None] + c[:, 0, None] * torch.where(live, X, zero)
     pv = c[:, 3, None] + c[:, 1, None] * torch.where(live, Y, zero)
-    out = {"proj": torch.where(bad[:, None, None], nan, torch.stack([c[:, 2, None] + c[:, 0, None] * X,
-                                                                     c[:, 3, None] + c[:, 1, None] * Y], -1)).detach(),
+    out = {"proj": nan_rows(bad, torch.stack([c[:, 2, None] + c[:, 0, None] * X, c[:, 3, None] + c[:, 1, None] * Y], -1)).detach(),
            "status": bad.to(torch.int32) * NONFINITE}
 
     def energy(d2, has, weight):
         s = torch.where(d2 > sl, d2 - sl, zero)
         e = _rho(s, s2) if weight is None else weight * _rho(s, s2)
-        return torch.where(bad[:, None], nan, torch.where(has, e, zero))
+        return nan_rows(bad, torch.where(has, e, zero))
 
     with torch.no_grad():
         pud, pvd = pu.detach(), pv.detach()
@@ -263,7 +262,7 @@ def label_distance_torch(verts, cam, spec, targets, vweight=None, sigma=None, sl
         du, dv = pu - qu[qi], pv - qv[qi]
         d2 = du * du + dv * dv
         out["e_m2i"] = energy(d2, has, torch.where(live, w, zero))
-        out["d2_v"] = torch.where(bad[:, None], nan, torch.where(has, d2, inf)).detach()
+        out["d2_v"] = nan_rows(bad, torch.where(has, d2, inf)).detach()
         out["near_pix"] = near.to(torch.int32)
     if "i2m" in dirs:
         has = nearv >= 0
@@ -271,7 +270,7 @@ def label_distance_torch(verts, cam, spec, targets, vweight=None, sigma=None, sl
         du, dv = torch.gather(pu, 1, vi) - qu, torch.gather(pv, 1, vi) - qv
         d2 = du * du + dv * dv
         out["e_i2m"] = energy(d2, has, None).reshape(B, W, W)
-        out["d2_p"] = torch.where(bad[:, None], nan, torch.where(has, d2, inf)).detach().reshape(B, W, W)
+        out["d2_p"] = nan_rows(bad, torch.where(has, d2, inf)).detach().reshape(B, W, W)
         out["near_vert"] = nearv.to(torch.int32).reshape(B, W, W)
     return out
 
@@ -333,11 +332,9 @@ class _LabelDistFn(torch.autograd.Function):
                 pairs = [(o[n], g.to(torch.float64)) for n, g in (("e_m2i", g_v), ("e_i2m", g_p)) if g is not None]
                 dv, dc = torch.autograd.grad([e for e, _ in pairs], [v, c], [g for _, g in pairs], allow_unused=True)
             bad = status != 0
-            nan = torch.full((), float("nan"), dtype=torch.float64)
             dv = torch.zeros_like(v, dtype=torch.float64) if dv is None else dv
             dc = torch.zeros_like(c, dtype=torch.float64) if dc is None else dc
-            dv = torch.where(bad[:, None, None], nan, dv).to(torch.float32)
-            dc = torch.where(bad[:, None], nan, dc).to(torch.float32)
+            dv, dc = nan_rows(bad, dv).to(torch.float32), nan_rows(bad, dc).to(torch.float32)
             return (dv if need_v else None, dc if need_c else None) + (None,) * 6
         dev = verts.device
         d = spec.on(dev)
@@ -368,11 +365,7 @@ def label_distance(verts, cam, spec, targets, vweight=None, sigma=None, slack=0.
     if not isinstance(targets, LabelTargets):
         raise TypeError("targets must be a LabelTargets")
     dirs = check_directions(directions)
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 3 or verts.shape[2] != 3:
-        raise ValueError("verts must be a (B, V, 3) tensor")
-    B, V = int(verts.shape[0]), int(verts.shape[1])
-    if V != spec.num_verts:
-        raise ValueError("verts have %d vertices, the spec %d" % (V, spec.num_verts))
+    B, V = check_verts(verts, spec=spec)
     if spec.num_classes != targets.num_classes:
         raise ValueError("the spec has %d classes, the targets %d" % (spec.num_classes, targets.num_classes))
     if B != targets.B:

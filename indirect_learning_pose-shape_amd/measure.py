@@ -28,6 +28,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream
+from ._mesh_common import check_topo, check_verts, neg_rows, nonfinite_rows
 
 NONFINITE = 1          # SMPLR_MM_NONFINITE
 MAX_PLANES = 16
@@ -40,8 +41,7 @@ class MeasureSpec:
     every part) and optional names.  K <= 16; K = 0 (no planes, no masks) measures volume, area and extents only."""
 
     def __init__(self, topo, planes=None, part_mask=None, names=None):
-        if not all(hasattr(topo, a) for a in ("faces", "vf_off", "vf_face", "face_part", "on")):
-            raise TypeError("topo must be a render.MeshTopology")
+        check_topo(topo, ("faces", "vf_off", "vf_face", "face_part", "on"))
         self.topo = topo
         if planes is not None:
             planes = torch.as_tensor(np.asarray(planes) if not isinstance(planes, torch.Tensor) else planes).detach()
@@ -125,7 +125,7 @@ def measures_torch(verts, faces, face_part, planes, part_mask):
     K = planes.shape[1]
     dev = verts.device
     v_in, p_in = verts.to(torch.float64), planes.to(torch.float64)
-    bad = ~(torch.isfinite(v_in).reshape(B, -1).all(1) & torch.isfinite(p_in).reshape(B, -1).all(1))
+    bad = nonfinite_rows(v_in) | nonfinite_rows(p_in)
     # a bad mesh is computed on zeros (nothing of it reaches its neighbours) and poisoned at the end: NaN outputs, NaN gradient rows
     v = torch.where(bad[:, None, None], torch.zeros_like(v_in), v_in)
     p = torch.where(bad[:, None, None], torch.zeros_like(p_in), p_in)
@@ -145,7 +145,7 @@ def measures_torch(verts, faces, face_part, planes, part_mask):
     imax = torch.where(v.detach() == hi, ar, V).amin(1)
     extent = v.gather(1, imax[:, None])[:, 0] - v.gather(1, imin[:, None])[:, 0]
     ext_idx = torch.cat([imin, imax], 1)
-    ext_idx = torch.where(bad[:, None], torch.full_like(ext_idx, -1), ext_idx).to(torch.int32)
+    ext_idx = neg_rows(bad, ext_idx).to(torch.int32)
     if K > 0:
         n, o = p[:, :, :3], p[:, :, 3]
         d = ((n[:, :, None, 0] * v[:, None, :, 0] + n[:, :, None, 1] * v[:, None, :, 1]) + n[:, :, None, 2] * v[:, None, :, 2]) \
@@ -244,11 +244,9 @@ def mesh_measures(verts, spec, planes=None):
     """verts (B, V, 3) -> dict(volume (B,), area (B,), extent (B, 3), girth (B, K) fp32; status (B,), ext_idx (B, 6) int32).
     planes: (K, 4) or (B, K, 4), overriding the spec's (planes that move with the body: `joint_planes`); K must be the
     spec's.  Differentiable in verts and planes."""
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 3 or verts.shape[2] != 3:
-        raise ValueError("verts must be a (B, V, 3) tensor")
+    B, V = check_verts(verts)
     if not isinstance(spec, MeasureSpec):
         raise TypeError("spec must be a MeasureSpec")
-    B, V = int(verts.shape[0]), int(verts.shape[1])
     if V != spec.topo.num_verts:
         raise ValueError("verts have %d vertices, the topology %d" % (V, spec.topo.num_verts))
     K = spec.num_planes

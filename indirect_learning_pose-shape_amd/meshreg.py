@@ -27,6 +27,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream
+from ._mesh_common import check_topo, check_verts
 
 
 def one_ring(faces, V):
@@ -71,8 +72,7 @@ class MeshRegSpec:
     fp32 or None, vweight (V,) fp32 or None, num_edges = E."""
 
     def __init__(self, topo, ref, weights="uniform", vweight=None, smooth=False):
-        if not all(hasattr(topo, a) for a in ("faces", "num_verts", "on")):
-            raise TypeError("topo must be a render.MeshTopology")
+        check_topo(topo, ("faces", "num_verts", "on"))
         V = int(topo.num_verts)
         r = ref.detach().cpu().numpy() if isinstance(ref, torch.Tensor) else np.asarray(ref)
         if r.shape != (V, 3):
@@ -217,8 +217,7 @@ def _mesh_reg_hip(verts, spec):
 def mesh_regularisers(verts, spec, return_terms=False, lap_weight=1.0, edge_weight=1.0):
     """verts (B, V, 3) -> terms (B, 2) = (E_lap, E_edge) with return_terms, else lap_weight E_lap + edge_weight E_edge (B,).
     Differentiable in verts."""
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 3 or verts.shape[2] != 3:
-        raise ValueError("verts must be a (B, V, 3) tensor")
+    check_verts(verts)
     if not isinstance(spec, MeshRegSpec):
         raise TypeError("spec must be a MeshRegSpec")
     if int(verts.shape[1]) != spec.num_verts:

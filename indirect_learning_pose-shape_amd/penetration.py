@@ -33,6 +33,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream
+from ._mesh_common import check_verts, dot3, nan_rows, neg_rows, nonfinite_rows
 
 NONFINITE = 1          # SMPLR_PEN_NONFINITE
 MAX_PARTS = 31
@@ -115,10 +116,6 @@ def _device_operands(topo, collide, device):
     return (d["faces"], d["vf_off"], d["vf_face"]) + ops
 
 
-def _dot(a, b):
-    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
-
-
 def vertex_normals_torch(v, faces, vf_off, vf_face):
     """v (B, V, 3) float64 -> (B, V, 3): per vertex the sum, in the CSR's order, of cross(v_b - v_a, v_c - v_a) over its
     faces - one addition per vertex and round of the loop, so the order of the sum is the definition's."""
@@ -151,7 +148,7 @@ def self_penetration_torch(verts, topo, collide=None, pairs_per_chunk=1 << 21):
     d = topo.on(dev)
     P = int(collide.shape[0])
     v = verts.detach().to(torch.float64)
-    bad = ~torch.isfinite(v).reshape(B, -1).all(1)
+    bad = nonfinite_rows(v)
     v = torch.where(bad[:, None, None], torch.zeros_like(v), v)
     part = d["vertex_part"].long()
     part = torch.where((part >= 0) & (part < P), part, torch.full_like(part, -1))
@@ -167,7 +164,7 @@ def self_penetration_torch(verts, topo, collide=None, pairs_per_chunk=1 << 21):
             q = slice(s, s + step)
             ok = (part[q, None] >= 0) & (part[None, :] >= 0) & (part[q, None] != part[None, :]) & table[pc[q]][:, pc]   # (C, V)
             e = v[:, None, :, :] - v[:, q, None, :]                                   # (B, C, V, 3)
-            dd = torch.where(ok[None], _dot(e, e), torch.full((), inf, dtype=torch.float64, device=dev))
+            dd = torch.where(ok[None], dot3(e, e), torch.full((), inf, dtype=torch.float64, device=dev))
             mn = dd.amin(2)
             j = torch.where((dd == mn[..., None]) & ok[None], ids[None, None, :], V).amin(2)   # ties: the lowest index
             hit = j < V
@@ -177,14 +174,10 @@ def self_penetration_torch(verts, topo, collide=None, pairs_per_chunk=1 << 21):
     nj = near.clamp(min=0)[..., None].expand(-1, -1, 3)
     n = vertex_normals_torch(v, d["faces"], d["vf_off"], d["vf_face"]).gather(1, nj)
     dv = v - v.gather(1, nj)
-    inside = hit & (_dot(dv, n) < 0)
+    inside = hit & (dot3(dv, n) < 0)
     e = torch.where(inside, d2, torch.zeros_like(d2))
-    nan = float("nan")
-    b1 = bad[:, None]
-    return {"e": torch.where(b1, torch.full_like(e, nan), e).to(torch.float32),
-            "d2": torch.where(b1, torch.full_like(d2, nan), d2).to(torch.float32),
-            "near": torch.where(b1, torch.full_like(near, -1), near).to(torch.int32),
-            "inside": inside & ~b1, "status": bad.to(torch.int32) * NONFINITE}
+    return {"e": nan_rows(bad, e).to(torch.float32), "d2": nan_rows(bad, d2).to(torch.float32),
+            "near": neg_rows(bad, near).to(torch.int32), "inside": inside & ~bad[:, None], "status": bad.to(torch.int32) * NONFINITE}
 
 
 def _backward_torch(verts, near, inside, status, g):
@@ -202,8 +195,7 @@ def _backward_torch(verts, near, inside, status, g):
     sel = live.reshape(-1).nonzero()[:, 0]                                           # (increasing (b, i))
     tgt = (nj + (torch.arange(B, device=dev) * V)[:, None]).reshape(-1)
     dv.index_add_(0, tgt[sel], -term.reshape(B * V, 3)[sel])
-    bad = (status != 0)[:, None, None]
-    return torch.where(bad, torch.full((), float("nan"), dtype=torch.float64, device=dev), dv.reshape(B, V, 3)).to(torch.float32)
+    return nan_rows(status != 0, dv.reshape(B, V, 3)).to(torch.float32)
 
 
 class _SelfPenetrationFn(torch.autograd.Function):
@@ -260,12 +252,7 @@ def self_penetration(verts, topo, collide=None, return_details=False):
     """verts (B, V, 3) fp32, topo a `render.MeshTopology`, collide None (`part_collision_table(topo, 1)`) or a (P, P) table of
     0 / 1 -> e (B, V) fp32, differentiable in verts; with return_details=True also dict(d2 (B, V) fp32, near (B, V) int32,
     inside (B, V) bool, status (B,) int32), constants of the gradient."""
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 3 or verts.shape[2] != 3:
-        raise ValueError("verts must be a (B, V, 3) tensor")
-    if not all(hasattr(topo, a) for a in ("faces", "vf_off", "vf_face", "vertex_part", "num_faces", "num_verts", "on")):
-        raise TypeError("topo must be a render.MeshTopology")
-    if int(verts.shape[1]) != topo.num_verts:
-        raise ValueError("verts have %d vertices, the topology %d" % (int(verts.shape[1]), topo.num_verts))
+    check_verts(verts, topo, ("faces", "vf_off", "vf_face", "vertex_part", "num_faces", "num_verts", "on"))
     if verts.dtype != torch.float32:
         raise RuntimeError("verts must be float32")
     collide = check_collide(collide, topo)

@@ -33,21 +33,18 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream
+from ._mesh_common import check_verts, dot3, nan_rows, neg_rows, nonfinite_rows
 
 NONFINITE = 1          # SMPLR_SCAN_NONFINITE
 DIRECTIONS = ("p2m", "m2p")
 KEYS = ("d2", "face", "bary", "resid", "vd2", "vpoint", "status")
 
 
-def _dot(a, b):
-    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
-
-
 def _seg_weight(A, Bv):
     E = Bv - A
-    ee = _dot(E, E)
+    ee = dot3(E, E)
     pos = ee > 0
-    t = -_dot(A, E) / torch.where(pos, ee, torch.ones_like(ee))
+    t = -dot3(A, E) / torch.where(pos, ee, torch.ones_like(ee))
     return torch.where(pos, t.clamp(0.0, 1.0), torch.zeros_like(t))
 
 
@@ -58,7 +55,7 @@ def closest_point(A, Bv, C):
     t01, t12, t20 = _seg_weight(A, Bv), _seg_weight(Bv, C), _seg_weight(C, A)
     mix = lambda t, X, Y: (1.0 - t)[..., None] * X + t[..., None] * Y
     q01, q12, q20 = mix(t01, A, Bv), mix(t12, Bv, C), mix(t20, C, A)
-    d01, d12, d20 = _dot(q01, q01), _dot(q12, q12), _dot(q20, q20)
+    d01, d12, d20 = dot3(q01, q01), dot3(q12, q12), dot3(q20, q20)
     zero, one = torch.zeros_like(t01), torch.ones_like(t01)
     d2, q = d01, q01
     w = torch.stack([one - t01, t01, zero], -1)
@@ -66,7 +63,7 @@ def closest_point(A, Bv, C):
         m = d < d2
         d2, q, w = torch.where(m, d, d2), torch.where(m[..., None], qq, q), torch.where(m[..., None], ww, w)
     E0, E1 = Bv - A, C - A
-    a00, a01, a11, b0, b1 = _dot(E0, E0), _dot(E0, E1), _dot(E1, E1), -_dot(E0, A), -_dot(E1, A)
+    a00, a01, a11, b0, b1 = dot3(E0, E0), dot3(E0, E1), dot3(E1, E1), -dot3(E0, A), -dot3(E1, A)
     det = a00 * a11 - a01 * a01
     ok = det > 0
     sd = torch.where(ok, det, torch.ones_like(det))
@@ -74,7 +71,7 @@ def closest_point(A, Bv, C):
     ww = (a00 * b1 - a01 * b0) / sd
     u = (1.0 - v) - ww
     qi = (u[..., None] * A + v[..., None] * Bv) + ww[..., None] * C
-    di = _dot(qi, qi)
+    di = dot3(qi, qi)
     m = ok & (v >= 0) & (ww >= 0) & (u >= 0) & (di < d2)
     d2, q, w = torch.where(m, di, d2), torch.where(m[..., None], qi, q), torch.where(m[..., None], torch.stack([u, v, ww], -1), w)
     return d2, w, q
@@ -89,7 +86,7 @@ def surface_distance_torch(verts, faces, points, counts=None, directions=DIRECTI
     N, F = int(points.shape[1]), int(faces.shape[0])
     dev = verts.device
     v, p = verts.detach().to(torch.float64), points.detach().to(torch.float64)
-    bad = ~torch.isfinite(v).reshape(B, -1).all(1)
+    bad = nonfinite_rows(v)
     v = torch.where(bad[:, None, None], torch.zeros_like(v), v)
     cnt = torch.full((B,), N, dtype=torch.long, device=dev) if counts is None else counts.to(dev).long().clamp(0, N)
     used = torch.arange(N, device=dev)[None, :] < cnt[:, None]                        # (B, N)
@@ -125,24 +122,20 @@ def surface_distance_torch(verts, faces, points, counts=None, directions=DIRECTI
         fill3 = torch.where(used[..., None], torch.full_like(bary, nan), torch.zeros_like(bary))
         bary, resid = torch.where(l3, bary, fill3), torch.where(l3, resid, fill3)
         face = torch.where(l1, face, torch.full_like(face, -1))
-        b1, b3 = bad[:, None], bad[:, None, None]
-        out["d2"] = torch.where(b1, torch.full_like(d2, nan), d2).to(torch.float32)
-        out["bary"] = torch.where(b3, torch.full_like(bary, nan), bary).to(torch.float32)
-        out["resid"] = torch.where(b3, torch.full_like(resid, nan), resid).to(torch.float32)
-        out["face"] = torch.where(b1, torch.full_like(face, -1), face).to(torch.int32)
+        out["d2"], out["bary"] = nan_rows(bad, d2).to(torch.float32), nan_rows(bad, bary).to(torch.float32)
+        out["resid"], out["face"] = nan_rows(bad, resid).to(torch.float32), neg_rows(bad, face).to(torch.int32)
     if "m2p" in directions:
         vd2 = torch.full((B, V), inf, dtype=torch.float64, device=dev)
         vpoint = torch.full((B, V), -1, dtype=torch.long, device=dev)
         step = max(1, pairs_per_chunk // max(1, B * V))
         for s in range(0, N, step):
             e = v[:, :, None, :] - p0[:, None, s:s + step, :]                           # (B, V, C, 3)
-            dd = torch.where(live[:, None, s:s + step], _dot(e, e), torch.full((), inf, dtype=torch.float64, device=dev))
+            dd = torch.where(live[:, None, s:s + step], dot3(e, e), torch.full((), inf, dtype=torch.float64, device=dev))
             mn = dd.amin(2)
             j = torch.where(dd == mn[..., None], torch.arange(s, s + dd.shape[2], device=dev)[None, None, :], N).amin(2)
             better = mn < vd2                                                           # (strict: ties stay with the lower point)
             vd2, vpoint = torch.where(better, mn, vd2), torch.where(better, j, vpoint)
-        out["vd2"] = torch.where(bad[:, None], torch.full_like(vd2, nan), vd2).to(torch.float32)
-        out["vpoint"] = torch.where(bad[:, None], torch.full_like(vpoint, -1), vpoint).to(torch.int32)
+        out["vd2"], out["vpoint"] = nan_rows(bad, vd2).to(torch.float32), neg_rows(bad, vpoint).to(torch.int32)
     return out
 
 
@@ -151,8 +144,6 @@ def _backward_torch(verts, faces, points, face, bary, resid, vpoint, status, g_d
     B, V = verts.shape[:2]
     N = points.shape[1]
     dev = verts.device
-    bad = (status != 0)[:, None, None]
-    nan = float("nan")
     dv = torch.zeros((B * V, 3), dtype=torch.float64, device=dev) if want_v else None
     dp = torch.zeros((B * N, 3), dtype=torch.float64, device=dev) if want_p else None
     if g_d2 is not None and face is not None and faces.shape[0]:
@@ -178,8 +169,7 @@ def _backward_torch(verts, faces, points, face, bary, resid, vpoint, status, g_d
             dv += term.reshape(-1, 3)
         if want_p:
             dp.index_add_(0, (j + (torch.arange(B, device=dev) * N)[:, None]).reshape(-1), -term.reshape(-1, 3))
-    fin = lambda t, n: None if t is None else torch.where(bad, torch.full((), nan, dtype=torch.float64, device=dev),
-                                                          t.reshape(B, n, 3)).to(torch.float32)
+    fin = lambda t, n: None if t is None else nan_rows(status != 0, t.reshape(B, n, 3)).to(torch.float32)
     return fin(dv, V), fin(dp, N)
 
 
@@ -249,13 +239,7 @@ def surface_distance(verts, topo, points, counts=None, directions=DIRECTIONS):
     """verts (B, V, 3), points (B, N, 3) fp32, counts (B,) integers or None -> dict(d2 (B, N), face (B, N) int32, bary
     (B, N, 3), resid (B, N, 3) for "p2m"; vd2 (B, V), vpoint (B, V) int32 for "m2p"; status (B,) int32).  Differentiable in
     verts and points through d2 and vd2; bary, resid and the indices are constants of the gradient."""
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 3 or verts.shape[2] != 3:
-        raise ValueError("verts must be a (B, V, 3) tensor")
-    if not all(hasattr(topo, a) for a in ("faces", "num_faces", "num_verts", "on")):
-        raise TypeError("topo must be a render.MeshTopology")
-    B, V = int(verts.shape[0]), int(verts.shape[1])
-    if V != topo.num_verts:
-        raise ValueError("verts have %d vertices, the topology %d" % (V, topo.num_verts))
+    B, V = check_verts(verts, topo, ("faces", "num_faces", "num_verts", "on"))
     if not isinstance(points, torch.Tensor) or points.dim() != 3 or points.shape[0] != B or points.shape[2] != 3:
         raise ValueError("points must be a (%d, N, 3) tensor" % B)
     if points.device != verts.device:

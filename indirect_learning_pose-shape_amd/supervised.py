@@ -39,6 +39,7 @@ from torch import nn
 
 from . import _lib
 from ._lib import check, ptr, stream
+from ._mesh_common import check_verts
 from .keypoints import NUM_POSED, KeypointSpec
 
 NONFINITE = 1            # SMPLR_SUP_NONFINITE
@@ -73,8 +74,7 @@ def _check(x, verts, jtr, truth, spec, root, row_w, cam_scale, num_cam):
     """Shapes and devices of a call -> (x_t, verts_t, jtr, jtr_t, K, cam_scale) with jtr None unless the spec uses it."""
     if spec is not None and not isinstance(spec, KeypointSpec):
         raise TypeError("spec must be a KeypointSpec or None")
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 3 or verts.shape[2] != 3:
-        raise ValueError("verts must be a (B, V, 3) tensor")
+    check_verts(verts)
     num_cam = int(num_cam)
     if not 0 <= num_cam <= MAX_CAM:
         raise ValueError("num_cam must lie in 0 .. %d, got %d" % (MAX_CAM, num_cam))

@@ -18,9 +18,7 @@ import argparse
 import importlib.util
 import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
@@ -29,6 +27,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import ilps_amd  # noqa: E402,F401
+from _timing import calls_per_window, profile_calls, rounds  # noqa: E402
+
+KERNELS = ("kp_fwd_kernel", "kp_bwd_kernel")
 
 
 def problem(B, seed=0):
@@ -51,34 +52,6 @@ def problem(B, seed=0):
     conf = (torch.rand((B, K), generator=gen) * 0.8 + 0.2).cuda()
     conf[:, 3] = 0.0
     return verts, cam, spec, target.contiguous(), conf
-
-
-def wall(fn, iters):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e6 / iters
-
-
-def profile_calls(fn, iters):
-    """-> kernels per call and their summed device time per call (us), ours by name, from a torch.profiler trace."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        for _ in range(iters):
-            fn()
-        torch.cuda.synchronize()
-    ev = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "memcpy" not in e.name.lower()
-          and "memset" not in e.name.lower()]
-    ours = {}
-    for e in ev:
-        for key in ("kp_fwd_kernel", "kp_bwd_kernel"):
-            if key in e.name:
-                ours.setdefault(key, []).append(e.device_time)
-    return {"kernels_per_call": round(len(ev) / iters, 2), "device_us_per_call": round(sum(e.device_time for e in ev) / iters, 1),
-            "kp_kernels_us": {k: round(statistics.median(v), 1) for k, v in ours.items()}}
 
 
 def fit_legs(B, iters, G):
@@ -126,12 +99,7 @@ def main():
         n, legs = fit_legs(B, a.fit_iters, a.graph_steps)
         for fn in legs.values():
             fn()                                                    # untimed: code objects, allocator pools, capture
-        us = {k: [] for k in legs}
-        for _ in range(a.rounds):
-            for k, fn in legs.items():
-                us[k].append(wall(fn, 1) / n)
-        res.update(iters=n, graph_steps=a.graph_steps, us_per_iteration_rounds={k: [round(v, 1) for v in vs] for k, vs in us.items()},
-                   us_per_iteration={k: round(statistics.median(vs), 1) for k, vs in us.items()})
+        res.update(iters=n, graph_steps=a.graph_steps, **rounds(legs, 1, a.rounds, per=n, key="us_per_iteration"))
         print(json.dumps(res))
         return
     verts, cam, spec, target, conf = problem(B)
@@ -151,26 +119,17 @@ def main():
 
     legs = {"hip_fwd": lambda: hip(False), "hip_fwd_bwd": lambda: hip(True), "stock_fwd": lambda: stock(False),
             "stock_fwd_bwd": lambda: stock(True)}
-    iters = {}
-    for k, fn in legs.items():
-        fn()                                                        # untimed: code objects, allocator pools
-        one = wall(fn, 1)
-        iters[k] = int(min(2000, max(2, a.window * 1e6 / max(one, 1.0))))
+    iters = calls_per_window(legs, a.window, cap=2000)
     res["iters"] = iters
     if a.launches:
-        res["profile"] = {k: profile_calls(fn, 3) for k, fn in legs.items()}
+        res["profile"] = {k: profile_calls(fn, 3, KERNELS, "kp_kernels_us") for k, fn in legs.items()}
         print(json.dumps(res))
         return
     with torch.no_grad():
         e = keypoint_energy(verts, cam, spec, target, conf, 3.0)
         s = keypoint_energy_torch(verts, cam, spec, target, conf, 3.0)["e"]
     res["max_abs_diff_hip_stock"] = float((e.double() - s).abs().max())
-    us = {k: [] for k in legs}
-    for _ in range(a.rounds):
-        for k, fn in legs.items():
-            us[k].append(wall(fn, iters[k]))
-    res["us_per_call_rounds"] = {k: [round(v, 1) for v in vs] for k, vs in us.items()}
-    res["us_per_call"] = {k: round(statistics.median(vs), 1) for k, vs in us.items()}
+    res.update(rounds(legs, iters, a.rounds))
     print(json.dumps(res))
 
 

@@ -23,9 +23,7 @@ import argparse
 import importlib.util
 import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
@@ -34,6 +32,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import ilps_amd  # noqa: E402,F401
+from _timing import calls_per_window, profile_calls, rounds  # noqa: E402
 
 KERNELS = ("ld_prep_kernel", "ld_fwd_kernel", "ld_bwd_kernel", "ld_dcam_kernel")
 
@@ -65,34 +64,6 @@ def problem(B, W, seed=0, shift=4.0):
         labels = torch.nn.functional.max_pool2d(flat.reshape(B, 1, W, W).float(), 3, 1, 1).reshape(B, W, W).to(torch.int32)
     cam[:, 2:] += shift
     return verts, cam.contiguous(), spec, labels.contiguous()
-
-
-def wall(fn, iters):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e6 / iters
-
-
-def profile_calls(fn, iters):
-    """-> kernels per call and their summed device time per call (us), ours by name, from a torch.profiler trace."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        for _ in range(iters):
-            fn()
-        torch.cuda.synchronize()
-    ev = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "memcpy" not in e.name.lower()
-          and "memset" not in e.name.lower()]
-    ours = {}
-    for e in ev:
-        for key in KERNELS:
-            if key in e.name:
-                ours.setdefault(key, []).append(e.device_time)
-    return {"kernels_per_call": round(len(ev) / iters, 2), "device_us_per_call": round(sum(e.device_time for e in ev) / iters, 1),
-            "ld_kernels_us": {k: round(statistics.median(v), 1) for k, v in ours.items()}}
 
 
 def fit_legs(B, iters, G):
@@ -132,12 +103,7 @@ def main():
         n, legs = fit_legs(B, a.fit_iters, a.graph_steps)
         for fn in legs.values():
             fn()                                                    # untimed: code objects, allocator pools, capture
-        us = {k: [] for k in legs}
-        for _ in range(a.rounds):
-            for k, fn in legs.items():
-                us[k].append(wall(fn, 1) / n)
-        res.update(iters=n, graph_steps=a.graph_steps, us_per_iteration_rounds={k: [round(v, 1) for v in vs] for k, vs in us.items()},
-                   us_per_iteration={k: round(statistics.median(vs), 1) for k, vs in us.items()})
+        res.update(iters=n, graph_steps=a.graph_steps, **rounds(legs, 1, a.rounds, per=n, key="us_per_iteration"))
         print(json.dumps(res))
         return
     verts, cam, spec, labels = problem(B, W)
@@ -160,14 +126,10 @@ def main():
     legs = {"hip_fwd": lambda: hip(False), "hip_fwd_bwd": lambda: hip(True), "stock_fwd": lambda: stock(False),
             "stock_fwd_bwd": lambda: stock(True), "prep": lambda: LabelTargets(labels, spec.num_classes),
             "hip_fwd_m2i": lambda: hip(False, "m2i"), "hip_fwd_i2m": lambda: hip(False, "i2m")}
-    iters = {}
-    for k, fn in legs.items():
-        fn()                                                        # untimed: code objects, allocator pools
-        one = wall(fn, 1)
-        iters[k] = int(min(2000, max(2, a.window * 1e6 / max(one, 1.0))))
+    iters = calls_per_window(legs, a.window, cap=2000)
     res["iters"] = iters
     if a.launches:
-        res["profile"] = {k: profile_calls(fn, 3) for k, fn in legs.items()}
+        res["profile"] = {k: profile_calls(fn, 3, KERNELS, "ld_kernels_us") for k, fn in legs.items()}
         print(json.dumps(res))
         return
     with torch.no_grad():
@@ -175,12 +137,7 @@ def main():
         s = label_distance_torch(verts, cam, spec, targets, None, 8.0)
     res["max_abs_diff_hip_stock"] = max(float((e_v.double() - s["e_m2i"]).abs().max()), float((e_p.double() - s["e_i2m"]).abs().max()))
     res["winners_equal"] = bool(torch.equal(det["near_pix"], s["near_pix"]) and torch.equal(det["near_vert"], s["near_vert"]))
-    us = {k: [] for k in legs}
-    for _ in range(a.rounds):
-        for k, fn in legs.items():
-            us[k].append(wall(fn, iters[k]))
-    res["us_per_call_rounds"] = {k: [round(v, 1) for v in vs] for k, vs in us.items()}
-    res["us_per_call"] = {k: round(statistics.median(vs), 1) for k, vs in us.items()}
+    res.update(rounds(legs, iters, a.rounds))
     print(json.dumps(res))
 
 

@@ -15,9 +15,7 @@ slows the host: no wall time is taken from it)."""
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
@@ -27,6 +25,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import ilps_amd  # noqa: E402,F401
+from _timing import profile_calls, rounds  # noqa: E402
+
+KERNELS = ("measure_fwd_kernel", "measure_bwd_kernel")
 
 
 def problem(B, K, seed=0):
@@ -41,34 +42,6 @@ def problem(B, K, seed=0):
     planes = np.concatenate([rng.normal(size=(K, 3)), rng.uniform(-0.1, 0.1, (K, 1))], 1).astype(np.float32)
     topo = MeshTopology(f, verts.shape[1])
     return torch.from_numpy(verts).cuda(), MeasureSpec(topo, planes=planes)
-
-
-def wall(fn, iters):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e6 / iters
-
-
-def profile_calls(fn, iters):
-    """-> kernels per call and their summed device time per call (us), by kernel name, from a torch.profiler trace."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        for _ in range(iters):
-            fn()
-        torch.cuda.synchronize()
-    ev = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "memcpy" not in e.name.lower()
-          and "memset" not in e.name.lower()]
-    ours = {}
-    for e in ev:
-        if "measure_" in e.name:
-            key = "measure_fwd_kernel" if "measure_fwd" in e.name else "measure_bwd_kernel"
-            ours.setdefault(key, []).append(e.device_time)
-    return {"kernels_per_call": round(len(ev) / iters, 2), "device_us_per_call": round(sum(e.device_time for e in ev) / iters, 1),
-            "measure_kernels_us": {k: round(statistics.median(v), 1) for k, v in ours.items()}}
 
 
 def main():
@@ -113,19 +86,14 @@ def main():
         fn()
         fn()                                                    # untimed: code objects, allocator pools
     if a.launches:
-        res["profile"] = {k: profile_calls(fn, 5) for k, fn in legs.items()}
+        res["profile"] = {k: profile_calls(fn, 5, KERNELS, "measure_kernels_us") for k, fn in legs.items()}
         print(json.dumps(res))
         return
     with torch.no_grad():
         o = mesh_measures(verts, spec)
         s = measures_torch(verts[:a.stock_chunk], d["faces"], d["face_part"], d["planes"][None].expand(min(B, a.stock_chunk), K, 4), mask64)
     res["max_abs_diff_hip_stock"] = {k: float((o[k][:a.stock_chunk] - s[i]).abs().max()) for i, k in enumerate(("volume", "area", "extent", "girth"))}
-    us = {k: [] for k in legs}
-    for _ in range(a.rounds):
-        for k, fn in legs.items():
-            us[k].append(wall(fn, iters if k.startswith("hip") else max(2, iters // 10)))
-    res["us_per_call_rounds"] = {k: [round(v, 1) for v in vs] for k, vs in us.items()}
-    res["us_per_call"] = {k: round(statistics.median(vs), 1) for k, vs in us.items()}
+    res.update(rounds(legs, {k: iters if k.startswith("hip") else max(2, iters // 10) for k in legs}, a.rounds))
     print(json.dumps(res))
 
 

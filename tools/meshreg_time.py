@@ -24,9 +24,7 @@ once (12 B V) + the CSR (4 (V + 1) + 16 nnz) + lap_ref (12 V); backward the same
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
@@ -36,38 +34,11 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import ilps_amd  # noqa: E402,F401
-
-
-def wall(fn, iters):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e6 / iters
+from _timing import calls_per_window, profile_calls, rounds  # noqa: E402
 
 
 KERNELS = ("meshreg_fwd_kernel", "meshreg_finish_kernel", "meshreg_bwd_kernel", "offset_adam_kernel", "scan_p2m_kernel",
            "scan_m2p_kernel", "scan_bwd_kernel")
-
-
-def profile_calls(fn, iters):
-    """-> kernels per call and their summed device time per call (us), by kernel name, from a torch.profiler trace."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        for _ in range(iters):
-            fn()
-        torch.cuda.synchronize()
-    ev = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "memcpy" not in e.name.lower()
-          and "memset" not in e.name.lower()]
-    ours = {}
-    for e in ev:
-        for key in KERNELS:
-            if key in e.name:
-                ours.setdefault(key, []).append(e.device_time)
-    return {"kernels_per_call": round(len(ev) / iters, 2), "device_us_per_call": round(sum(e.device_time for e in ev) / iters, 1),
-            "own_kernels_us": {k: round(statistics.median(v), 1) for k, v in ours.items()}}
 
 
 def main():
@@ -141,14 +112,9 @@ def main():
     csr = 4 * (V + 1) + 16 * nnz + 12 * V
     res = {"build_id": _lib.build_id()[:16], "B": B, "V": V, "F": topo.num_faces, "N": N, "nnz": nnz, "E": spec.num_edges,
            "bytes": {"reg_fwd": 12 * B * V + csr, "reg_bwd": 24 * B * V + csr, "offset_step": 28 * B * V * 3}}
-    iters = {}
-    for k, fn in legs.items():
-        fn()                                                    # untimed: code objects, allocator pools
-        fn()
-        one = wall(fn, 1)
-        iters[k] = int(min(200, max(2, a.window * 1e6 / max(one, 1.0))))
+    iters = calls_per_window(legs, a.window, warm=2)
     if a.launches:
-        res["profile"] = {k: profile_calls(fn, 3) for k, fn in legs.items() if k != "stock_fwd_bwd"}
+        res["profile"] = {k: profile_calls(fn, 3, KERNELS, "own_kernels_us") for k, fn in legs.items() if k != "stock_fwd_bwd"}
         print(json.dumps(res))
         return
     # one iteration in a graph (warm-up above, on the same state: only the timing matters here)
@@ -165,12 +131,7 @@ def main():
     legs["iteration_graph"] = graph.replay
     iters["iteration_graph"] = iters["iteration"]
     res["iters"] = iters
-    us = {k: [] for k in legs}
-    for _ in range(a.rounds):
-        for k, fn in legs.items():
-            us[k].append(wall(fn, iters[k]))
-    res["us_per_call_rounds"] = {k: [round(v, 1) for v in vs] for k, vs in us.items()}
-    res["us_per_call"] = {k: round(statistics.median(vs), 1) for k, vs in us.items()}
+    res.update(rounds(legs, iters, a.rounds))
     print(json.dumps(res))
 
 

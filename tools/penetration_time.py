@@ -24,9 +24,7 @@ import contextlib
 import importlib.util
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
@@ -36,6 +34,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import ilps_amd  # noqa: E402,F401
+from _timing import calls_per_window, profile_calls, rounds  # noqa: E402
+
+KERNELS = ("pen_fwd_kernel", "pen_bwd_kernel")
 
 
 @contextlib.contextmanager
@@ -72,34 +73,6 @@ def problem(B, seed=0, shrink=1.0):
             c = verts[:, m].mean(1, keepdim=True)
             verts[:, m] = c + shrink * (verts[:, m] - c)
     return verts, topo
-
-
-def wall(fn, iters):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e6 / iters
-
-
-def profile_calls(fn, iters):
-    """-> kernels per call and their summed device time per call (us), ours by name, from a torch.profiler trace."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        for _ in range(iters):
-            fn()
-        torch.cuda.synchronize()
-    ev = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "memcpy" not in e.name.lower()
-          and "memset" not in e.name.lower()]
-    ours = {}
-    for e in ev:
-        for key in ("pen_fwd_kernel", "pen_bwd_kernel"):
-            if key in e.name:
-                ours.setdefault(key, []).append(e.device_time)
-    return {"kernels_per_call": round(len(ev) / iters, 2), "device_us_per_call": round(sum(e.device_time for e in ev) / iters, 1),
-            "pen_kernels_us": {k: round(statistics.median(v), 1) for k, v in ours.items()}}
 
 
 def fit_legs(B, iters, G):
@@ -144,12 +117,7 @@ def main():
         n, legs = fit_legs(B, a.fit_iters, a.graph_steps)
         for fn in legs.values():
             fn()                                                    # untimed: code objects, allocator pools, capture
-        us = {k: [] for k in legs}
-        for _ in range(a.rounds):
-            for k, fn in legs.items():
-                us[k].append(wall(fn, 1) / n)
-        res.update(iters=n, graph_steps=a.graph_steps, us_per_iteration_rounds={k: [round(v, 1) for v in vs] for k, vs in us.items()},
-                   us_per_iteration={k: round(statistics.median(vs), 1) for k, vs in us.items()})
+        res.update(iters=n, graph_steps=a.graph_steps, **rounds(legs, 1, a.rounds, per=n, key="us_per_iteration"))
         print(json.dumps(res))
         return
     verts, topo = problem(B, shrink=a.shrink)
@@ -180,26 +148,17 @@ def main():
         e, det = self_penetration(verts, topo, return_details=True)
     res.update(pairs=B * 6890 * 6890, stock_meshes=sb, stock_pairs=sb * 6890 * 6890,
                with_candidates=float((det["near"] >= 0).float().mean()), inside=float(det["inside"].float().mean()))
-    iters = {}
-    for k, fn in legs.items():
-        fn()                                                        # untimed: code objects, allocator pools
-        one = wall(fn, 1)
-        iters[k] = int(min(200, max(2, a.window * 1e6 / max(one, 1.0))))
+    iters = calls_per_window(legs, a.window)
     res["iters"] = iters
     if a.launches:
-        res["profile"] = {k: profile_calls(fn, 3) for k, fn in legs.items() if k.startswith("hip")}
+        res["profile"] = {k: profile_calls(fn, 3, KERNELS, "pen_kernels_us") for k, fn in legs.items() if k.startswith("hip")}
         print(json.dumps(res))
         return
     if not a.no_stock:
         s = self_penetration_torch(sv, topo)
         res["max_abs_diff_hip_stock"] = float((e[:sb] - s["e"]).abs().max())
         res["index_agreement"] = float((det["near"][:sb] == s["near"]).float().mean())
-    us = {k: [] for k in legs}
-    for _ in range(a.rounds):
-        for k, fn in legs.items():
-            us[k].append(wall(fn, iters[k]))
-    res["us_per_call_rounds"] = {k: [round(v, 1) for v in vs] for k, vs in us.items()}
-    res["us_per_call"] = {k: round(statistics.median(vs), 1) for k, vs in us.items()}
+    res.update(rounds(legs, iters, a.rounds))
     print(json.dumps(res))
 
 

@@ -19,9 +19,7 @@ time limit, chained with && (a leg that fails or hangs ends the chain).
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
@@ -31,6 +29,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import ilps_amd  # noqa: E402,F401
+from _timing import calls_per_window, profile_calls, rounds  # noqa: E402
+
+KERNELS = ("scan_p2m_kernel", "scan_m2p_kernel", "scan_bwd_kernel")
 
 
 def morton_order(points):
@@ -58,34 +59,6 @@ def problem(B, N, morton, seed=0):
     if morton:
         pts = pts.gather(1, morton_order(pts)[..., None].expand(-1, -1, 3))
     return verts, topo, pts.contiguous()
-
-
-def wall(fn, iters):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e6 / iters
-
-
-def profile_calls(fn, iters):
-    """-> kernels per call and their summed device time per call (us), by kernel name, from a torch.profiler trace."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        for _ in range(iters):
-            fn()
-        torch.cuda.synchronize()
-    ev = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "memcpy" not in e.name.lower()
-          and "memset" not in e.name.lower()]
-    ours = {}
-    for e in ev:
-        for key in ("scan_p2m_kernel", "scan_m2p_kernel", "scan_bwd_kernel"):
-            if key in e.name:
-                ours.setdefault(key, []).append(e.device_time)
-    return {"kernels_per_call": round(len(ev) / iters, 2), "device_us_per_call": round(sum(e.device_time for e in ev) / iters, 1),
-            "scan_kernels_us": {k: round(statistics.median(v), 1) for k, v in ours.items()}}
 
 
 def main():
@@ -128,14 +101,10 @@ def main():
     res = {"build_id": _lib.build_id()[:16], "B": B, "V": int(verts.shape[1]), "F": topo.num_faces, "N": N, "morton": a.morton,
            "hip_pairs": B * N * topo.num_faces + B * int(verts.shape[1]) * N,
            "stock_meshes": sb, "stock_points": sn, "stock_pairs": sb * sn * topo.num_faces + sb * int(verts.shape[1]) * sn}
-    iters = {}
-    for k, fn in legs.items():
-        fn()                                                    # untimed: code objects, allocator pools
-        one = wall(fn, 1)
-        iters[k] = int(min(200, max(2, a.window * 1e6 / max(one, 1.0))))
+    iters = calls_per_window(legs, a.window)
     res["iters"] = iters
     if a.launches:
-        res["profile"] = {k: profile_calls(fn, 3) for k, fn in legs.items() if k.startswith("hip")}
+        res["profile"] = {k: profile_calls(fn, 3, KERNELS, "scan_kernels_us") for k, fn in legs.items() if k.startswith("hip")}
         print(json.dumps(res))
         return
     if not a.no_stock:
@@ -143,12 +112,7 @@ def main():
             o, s = surface_distance(sv, topo, sp), surface_distance_torch(sv, faces, sp)
         res["max_abs_diff_hip_stock"] = {k: float((o[k] - s[k]).abs().max()) for k in ("d2", "vd2")}
         res["index_agreement"] = {k: float((o[k] == s[k]).float().mean()) for k in ("face", "vpoint")}
-    us = {k: [] for k in legs}
-    for _ in range(a.rounds):
-        for k, fn in legs.items():
-            us[k].append(wall(fn, iters[k]))
-    res["us_per_call_rounds"] = {k: [round(v, 1) for v in vs] for k, vs in us.items()}
-    res["us_per_call"] = {k: round(statistics.median(vs), 1) for k, vs in us.items()}
+    res.update(rounds(legs, iters, a.rounds))
     print(json.dumps(res))
 
 
