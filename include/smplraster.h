@@ -665,6 +665,41 @@ int smplr_kp_bwd(const float *cam, const int32_t *t_off, const int32_t *t_joint,
                  const int32_t *status, const double *ws, const float *g, int B, int V, int K, int nnz, float sigma,
                  float *dverts, float *djtr, float *dcam, void *stream);
 
+/* ---- dense surface-correspondence term: IUV pixels and markers against named mesh points, robust energy, gradients (beyond
+ * the reference); INTEGRATION.md 4w -----------------------------------------------------------------------------------------
+ * verts (B, V, 3) fp32, faces (F, 3) int32 in [0, V).  Row b holds N correspondences SORTED by face (a stable sort, anything
+ * outside [0, F) last): face (B, N) int32, bary (B, N, 3), target (B, N, D), conf (B, N) fp32, order (B, N) int32 = the
+ * caller's index of each sorted position (a permutation of 0 .. N - 1), c_off (B, F + 1) int32 = the row's CSR over faces
+ * (c_off[b, f] = the entries with face < f).  vc_off (V + 1), vc_fc (3 F) int32: per vertex the (face, corner) pairs it is,
+ * packed 4 face + corner, faces increasing and corners increasing within a face.  The kernels TRUST these arrays
+ * (surface.SurfaceTargets builds and checks them once); what they still do is skip a face outside [0, F), a vertex outside
+ * [0, V), an order entry outside [0, N), a corner above 2 and an offset range outside [0, N] or [0, 3 F].
+ * D = 2: cam (B, 4) = (k_u, k_v, u0, v0), targets in that camera's pixel frame; D = 3: cam is not read (NULL), targets in the
+ * mesh's frame.
+ *   P = (b_0 x_0 + b_1 x_1) + b_2 x_2 per coordinate, x_c = verts[b, faces[face, c]]; r = (u0 + k_u P_x - t_u, v0 + k_v P_y - t_v)
+ *   or P - t; d2 = |r|^2; a correspondence counts iff 0 <= face < F and conf > 0 (a NaN does not): e = conf rho(d2); one that
+ *   does not count has e = d2 = point = 0 whatever it holds; rho(s) = sigma^2 s / (sigma^2 + s), or s with sigma = 0.
+ * smplr_sc_fwd writes e, d2 (B, N) and point (B, N, 3) or NULL in the CALLER's order, status (B) and ws (B, N, 4) fp64 in sorted
+ *   order = (P_x, P_y, r_u, r_v) with D = 2, (r_x, r_y, r_z, 0) with D = 3, at the counted entries - which smplr_sc_bwd reads.
+ *   One launch of B workgroups of 1024 lanes.
+ * smplr_sc_bwd, g (B, N) the cotangent of e in the caller's order: q = g conf rho'(d2) 2 r at a counted entry; dP = (q_u k_u,
+ *   q_v k_v, 0) or q; dverts[b, i] = the sum over vertex i's (face, corner) pairs, and within a face over c_off[b, f] ..
+ *   c_off[b, f + 1] in sorted order, of bary[corner] dP, every row written (exact zeros where nothing lands); dcam (B, 4) or
+ *   NULL (D = 2 only) = (sum q_u P_x, sum q_v P_y, sum q_u, sum q_v).  One launch of ceil(V / 256) x B workgroups.
+ * All products and sums are fp64 on the fp32 operands in an order the launch geometry and the row's own data fix; each output
+ * is rounded to fp32 once; no atomics: a row's results are the same bits on every launch and in any batch.
+ * status: SMPLR_SC_NONFINITE when a counted correspondence uses a vertex coordinate, a weight or a target that is NaN / Inf,
+ *   or (D = 2) a cam column is - the row's e, d2, point, dverts and dcam are NaN; other rows are not affected.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= V <= 2^24, 1 <= F <= 2^24, 1 <= N <= 65536, D 2 or 3, sigma finite
+ * and >= 0, B >= 0 (B = 0 is a no-op; smplr_sc_bwd: B <= 65535); no null pointer except point, dcam (and cam with D = 3).   */
+#define SMPLR_SC_NONFINITE 1
+int smplr_sc_fwd(const float *verts, const float *cam, const int32_t *faces, const int32_t *face, const float *bary,
+                 const float *target, const float *conf, const int32_t *order, int B, int V, int F, int N, int D, float sigma,
+                 float *e, float *d2, float *point, int32_t *status, double *ws, void *stream);
+int smplr_sc_bwd(const float *cam, const int32_t *vc_off, const int32_t *vc_fc, const int32_t *c_off, const int32_t *face,
+                 const float *bary, const float *conf, const int32_t *order, const int32_t *status, const double *ws,
+                 const float *g, int B, int V, int F, int N, int D, float sigma, float *dverts, float *dcam, void *stream);
+
 /* ---- supervised 3D losses: vertices, sparse 3D joints, pose as rotation matrices, shape, camera, with gradients (beyond the
  * reference); INTEGRATION.md 4u ---------------------------------------------------------------------------------------------
  * Row b: x, x_t (B rows of x_stride floats) = predicted and true parameters in the decoder's layout, cam (num_cam), theta (72),

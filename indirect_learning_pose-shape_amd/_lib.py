@@ -96,6 +96,8 @@ SIGNATURES = {
     "smplr_pen_bwd": (c_int, [P, P, P, P, P, I, I, P, P]),
     "smplr_kp_fwd": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, c_float, P, P, P, P, P, P, P]),
     "smplr_kp_bwd": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, c_float, P, P, P, P]),
+    "smplr_sc_fwd": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, I, c_float, P, P, P, P, P, P]),
+    "smplr_sc_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, c_float, P, P, P]),
     "smplr_sup_fwd": (c_int, [P, P, I, P, P, P, P, P, P, P, I, P, P, I, I, I, I, I, P, P, P, P]),
     "smplr_sup_bwd": (c_int, [P, P, I, P, P, P, P, P, I, P, P, P, P, P, I, I, I, I, I, P, P, P, P]),
     "smplr_rot6d_fwd": (c_int, [P, I, I, I, P, P, P]),

@@ -1643,6 +1643,113 @@ Tensor rot6d_bwd_meta(const Tensor &y, const Tensor &status, const Tensor &dx, i
   return at::empty({y.size(0), num_cam + 154}, y.options());
 }
 
+// ---- dense surface-correspondence term (include/smplraster.h): the sorted arrays of a surface.SurfaceTargets;
+// cam given: D = 2, cam None: D = 3 -----------------------------------------------------------------------------------------
+struct ScDims { int64_t B, V, F, N, D; };
+ScDims sc_rows(const Tensor &face, const Tensor &bary, const Tensor &conf, const Tensor &order, const c10::optional<Tensor> &cam,
+               int64_t V, int64_t F, double sigma) {
+  TORCH_CHECK(face.dim() == 2 && face.scalar_type() == at::kInt, "face must be (B, N) int32");
+  ScDims d{face.size(0), V, F, face.size(1), cam ? 2 : 3};
+  TORCH_CHECK(d.N >= 1 && d.N <= 65536, "1 <= N <= 65536 correspondences per row, got ", d.N);
+  TORCH_CHECK(V >= 1 && V <= (1 << 24) && F >= 1 && F <= (1 << 24), "V and F must lie in 1 .. 2^24");
+  TORCH_CHECK(bary.dim() == 3 && bary.size(0) == d.B && bary.size(1) == d.N && bary.size(2) == 3 && bary.scalar_type() == at::kFloat,
+              "bary must be (B, N, 3) float32");
+  TORCH_CHECK(conf.dim() == 2 && conf.size(0) == d.B && conf.size(1) == d.N && conf.scalar_type() == at::kFloat,
+              "conf must be (B, N) float32");
+  TORCH_CHECK(order.dim() == 2 && order.size(0) == d.B && order.size(1) == d.N && order.scalar_type() == at::kInt,
+              "order must be (B, N) int32");
+  if (cam)
+    TORCH_CHECK(cam->dim() == 2 && cam->size(0) == d.B && cam->size(1) == 4 && cam->scalar_type() == at::kFloat,
+                "cam must be (B, 4) float32");
+  TORCH_CHECK(sigma >= 0 && sigma < 3e38, "sigma must be finite and >= 0 (0: no robust function)");
+  return d;
+}
+ScDims sc_fwd_check(const Tensor &verts, const c10::optional<Tensor> &cam, const Tensor &faces, const Tensor &face,
+                    const Tensor &bary, const Tensor &target, const Tensor &conf, const Tensor &order, double sigma) {
+  TORCH_CHECK(verts.dim() == 3 && verts.size(2) == 3 && verts.scalar_type() == at::kFloat, "verts must be (B, V, 3) float32");
+  TORCH_CHECK(faces.dim() == 2 && faces.size(1) == 3 && faces.scalar_type() == at::kInt, "faces must be (F, 3) int32");
+  const ScDims d = sc_rows(face, bary, conf, order, cam, verts.size(1), faces.size(0), sigma);
+  TORCH_CHECK(verts.size(0) == d.B, "verts must have face's rows");
+  TORCH_CHECK(target.dim() == 3 && target.size(0) == d.B && target.size(1) == d.N && target.size(2) == d.D &&
+                  target.scalar_type() == at::kFloat,
+              "target must be (B, N, ", d.D, ") float32 (cam given: 2, cam None: 3)");
+  return d;
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> surface_fwd(const Tensor &verts, const c10::optional<Tensor> &cam,
+                                                               const Tensor &faces, const Tensor &face, const Tensor &bary,
+                                                               const Tensor &target, const Tensor &conf, const Tensor &order,
+                                                               double sigma) {
+  const ScDims d = sc_fwd_check(verts, cam, faces, face, bary, target, conf, order, sigma);
+  dev_f32(verts, "verts"); dev_typed(faces, at::kInt, "faces"); dev_typed(face, at::kInt, "face"); dev_f32(bary, "bary");
+  dev_f32(target, "target"); dev_f32(conf, "conf"); dev_typed(order, at::kInt, "order");
+  if (cam) dev_f32(*cam, "cam");
+  const Tensor none;
+  same_device(verts, {{"cam", cam ? &*cam : &none}, {"faces", &faces}, {"face", &face}, {"bary", &bary}, {"target", &target},
+                      {"conf", &conf}, {"order", &order}});
+  DeviceGuard guard(verts.device());
+  Tensor e = f32({d.B, d.N}, verts), d2 = f32({d.B, d.N}, verts), point = f32({d.B, d.N, 3}, verts);
+  Tensor status = at::empty({d.B}, verts.options().dtype(at::kInt)), ws = at::empty({d.B, d.N, 4}, verts.options().dtype(at::kDouble));
+  if (d.B == 0) return {e, d2, point, status, ws};
+  ok(smplr_sc_fwd(verts.data_ptr<float>(), cam ? cam->data_ptr<float>() : nullptr, faces.data_ptr<int32_t>(),
+                  face.data_ptr<int32_t>(), bary.data_ptr<float>(), target.data_ptr<float>(), conf.data_ptr<float>(),
+                  order.data_ptr<int32_t>(), (int)d.B, (int)d.V, (int)d.F, (int)d.N, (int)d.D, (float)sigma, e.data_ptr<float>(),
+                  d2.data_ptr<float>(), point.data_ptr<float>(), status.data_ptr<int32_t>(), ws.data_ptr<double>(), cur_stream()),
+     "smplr_sc_fwd");
+  return {e, d2, point, status, ws};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> surface_fwd_meta(const Tensor &verts, const c10::optional<Tensor> &cam,
+                                                                    const Tensor &faces, const Tensor &face, const Tensor &bary,
+                                                                    const Tensor &target, const Tensor &conf, const Tensor &order,
+                                                                    double sigma) {
+  const ScDims d = sc_fwd_check(verts, cam, faces, face, bary, target, conf, order, sigma);
+  return {at::empty({d.B, d.N}, verts.options()), at::empty({d.B, d.N}, verts.options()), at::empty({d.B, d.N, 3}, verts.options()),
+          at::empty({d.B}, verts.options().dtype(at::kInt)), at::empty({d.B, d.N, 4}, verts.options().dtype(at::kDouble))};
+}
+ScDims sc_bwd_check(const c10::optional<Tensor> &cam, const Tensor &vc_off, const Tensor &vc_fc, const Tensor &c_off,
+                    const Tensor &face, const Tensor &bary, const Tensor &conf, const Tensor &order, const Tensor &status,
+                    const Tensor &ws, const Tensor &g, double sigma) {
+  TORCH_CHECK(vc_off.dim() == 1 && vc_off.size(0) >= 2 && vc_off.scalar_type() == at::kInt, "vc_off must be (V + 1) int32");
+  TORCH_CHECK(c_off.dim() == 2 && c_off.size(1) >= 2 && c_off.scalar_type() == at::kInt, "c_off must be (B, F + 1) int32");
+  const ScDims d = sc_rows(face, bary, conf, order, cam, vc_off.size(0) - 1, c_off.size(1) - 1, sigma);
+  TORCH_CHECK(d.B <= 65535, "at most 65535 rows, got ", d.B);
+  TORCH_CHECK(c_off.size(0) == d.B, "c_off must have face's rows");
+  TORCH_CHECK(vc_fc.dim() == 1 && vc_fc.size(0) == 3 * d.F && vc_fc.scalar_type() == at::kInt, "vc_fc must be (3 F) int32");
+  TORCH_CHECK(status.dim() == 1 && status.size(0) == d.B && status.scalar_type() == at::kInt, "status must be (B) int32");
+  TORCH_CHECK(ws.dim() == 3 && ws.size(0) == d.B && ws.size(1) == d.N && ws.size(2) == 4 && ws.scalar_type() == at::kDouble,
+              "ws must be (B, N, 4) float64");
+  TORCH_CHECK(g.dim() == 2 && g.size(0) == d.B && g.size(1) == d.N && g.scalar_type() == at::kFloat, "g must be (B, N) float32");
+  return d;
+}
+std::tuple<Tensor, Tensor> surface_bwd(const c10::optional<Tensor> &cam, const Tensor &vc_off, const Tensor &vc_fc,
+                                       const Tensor &c_off, const Tensor &face, const Tensor &bary, const Tensor &conf,
+                                       const Tensor &order, const Tensor &status, const Tensor &ws, const Tensor &g, double sigma) {
+  const ScDims d = sc_bwd_check(cam, vc_off, vc_fc, c_off, face, bary, conf, order, status, ws, g, sigma);
+  dev_typed(vc_off, at::kInt, "vc_off"); dev_typed(vc_fc, at::kInt, "vc_fc"); dev_typed(c_off, at::kInt, "c_off");
+  dev_typed(face, at::kInt, "face"); dev_f32(bary, "bary"); dev_f32(conf, "conf"); dev_typed(order, at::kInt, "order");
+  dev_typed(status, at::kInt, "status"); dev_typed(ws, at::kDouble, "ws"); dev_f32(g, "g");
+  if (cam) dev_f32(*cam, "cam");
+  const Tensor none;
+  same_device(g, {{"cam", cam ? &*cam : &none}, {"vc_off", &vc_off}, {"vc_fc", &vc_fc}, {"c_off", &c_off}, {"face", &face},
+                  {"bary", &bary}, {"conf", &conf}, {"order", &order}, {"status", &status}, {"ws", &ws}});
+  DeviceGuard guard(g.device());
+  Tensor dverts = f32({d.B, d.V, 3}, g), dcam = f32({cam ? d.B : 0, 4}, g);
+  if (d.B == 0) return {dverts, dcam};
+  ok(smplr_sc_bwd(cam ? cam->data_ptr<float>() : nullptr, vc_off.data_ptr<int32_t>(), vc_fc.data_ptr<int32_t>(),
+                  c_off.data_ptr<int32_t>(), face.data_ptr<int32_t>(), bary.data_ptr<float>(), conf.data_ptr<float>(),
+                  order.data_ptr<int32_t>(), status.data_ptr<int32_t>(), ws.data_ptr<double>(), g.data_ptr<float>(), (int)d.B,
+                  (int)d.V, (int)d.F, (int)d.N, (int)d.D, (float)sigma, dverts.data_ptr<float>(),
+                  cam ? dcam.data_ptr<float>() : nullptr, cur_stream()),
+     "smplr_sc_bwd");
+  return {dverts, dcam};
+}
+std::tuple<Tensor, Tensor> surface_bwd_meta(const c10::optional<Tensor> &cam, const Tensor &vc_off, const Tensor &vc_fc,
+                                            const Tensor &c_off, const Tensor &face, const Tensor &bary, const Tensor &conf,
+                                            const Tensor &order, const Tensor &status, const Tensor &ws, const Tensor &g,
+                                            double sigma) {
+  const ScDims d = sc_bwd_check(cam, vc_off, vc_fc, c_off, face, bary, conf, order, status, ws, g, sigma);
+  return {at::empty({d.B, d.V, 3}, g.options()), at::empty({cam ? d.B : 0, 4}, g.options())};
+}
+
 TORCH_LIBRARY(smplraster, m) {
   m.def("abi_version() -> int", &abi_version);
   m.def("build_tag() -> str", &build_tag);
@@ -1719,6 +1826,10 @@ TORCH_LIBRARY(smplraster, m) {
         "(Tensor, Tensor, Tensor)");
   m.def("rot6d_fwd(Tensor y, int num_cam=4) -> (Tensor, Tensor)");
   m.def("rot6d_bwd(Tensor y, Tensor status, Tensor dx, int num_cam=4) -> Tensor");
+  m.def("surface_fwd(Tensor verts, Tensor? cam, Tensor faces, Tensor face, Tensor bary, Tensor target, Tensor conf, Tensor order, "
+        "float sigma) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("surface_bwd(Tensor? cam, Tensor vc_off, Tensor vc_fc, Tensor c_off, Tensor face, Tensor bary, Tensor conf, Tensor order, "
+        "Tensor status, Tensor ws, Tensor g, float sigma) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch key is named CUDA in torch)
@@ -1757,6 +1868,8 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("sup_bwd", &sup_bwd);
   m.impl("rot6d_fwd", &rot6d_fwd);
   m.impl("rot6d_bwd", &rot6d_bwd);
+  m.impl("surface_fwd", &surface_fwd);
+  m.impl("surface_bwd", &surface_bwd);
 }
 
 TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
@@ -1795,4 +1908,6 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("sup_bwd", &sup_bwd_meta);
   m.impl("rot6d_fwd", &rot6d_fwd_meta);
   m.impl("rot6d_bwd", &rot6d_bwd_meta);
+  m.impl("surface_fwd", &surface_fwd_meta);
+  m.impl("surface_bwd", &surface_bwd_meta);
 }

@@ -269,6 +269,30 @@ def evaluate_keypoints(proj_or_details, target, conf, thresholds=(0.05, 0.1, 0.2
 
 
 @torch.no_grad()
+def evaluate_surface(details, targets, thresholds=(1.0, 2.0, 5.0)):
+    """Residuals of dense surface correspondences, in the targets' unit (pixels with image targets, metres with 3D ones), from
+    `surface.surface_energy`'s details (its d2 and status; stock torch, CPU tensors too) and the `SurfaceTargets` they were
+    computed against: a correspondence counts iff it counts in the targets and its row is finite.  A row is left out whole
+    when its status is NONFINITE or a counted d2 is NaN / Inf.  -> dict(mean_error, median_error = the mean and the median of
+    sqrt(d2) over the counted correspondences (NaN without one), within = {t: the share of them with sqrt(d2) <= t}, count =
+    counted correspondences, rows = rows counted, nonfinite = rows left out)."""
+    d2 = details["d2"].to(torch.float64)
+    counted = targets.counted().to(d2.device)
+    if tuple(d2.shape) != tuple(counted.shape):
+        raise ValueError("d2 is %s, the targets (%d, %d)" % (tuple(d2.shape), targets.B, targets.N))
+    bad = (counted & ~torch.isfinite(d2)).any(1)
+    if details.get("status") is not None:
+        bad = bad | (details["status"] != 0)
+    counted = counted & ~bad[:, None]
+    dist = d2[counted].sqrt()
+    n = int(dist.numel())
+    nan = float("nan")
+    return {"mean_error": float(dist.mean()) if n else nan, "median_error": float(dist.median()) if n else nan,
+            "within": {float(t): (float((dist <= float(t)).sum()) / n if n else nan) for t in thresholds}, "count": n,
+            "rows": int(d2.shape[0]) - int(bad.sum()), "nonfinite": int(bad.sum())}
+
+
+@torch.no_grad()
 def evaluate_label_distance(details, targets):
     """How far a mesh lies from its label map, from `labeldist.label_distance`'s details (stock torch, CPU tensors too) and
     the `LabelTargets` they were computed against (B images).  Per direction that the details hold - "m2i" from d2_v over

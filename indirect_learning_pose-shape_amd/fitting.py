@@ -106,6 +106,18 @@ every vertex to the nearest pixel of its part beside every labelled pixel to the
 side term, after penetration and keypoints, through a cotangent ld_weight / (V + W W).  The labels are sorted by class once
 per fit, outside any captured graph.  `ParamFitter` itself keeps its signatures and runs exactly the launches it ran before.
 
+Dense surface correspondences (surface.py, csrc/surface.hip; IUV pixels or markers that each name a face and barycentric weights):
+
+    fitter = with_surface(ParamFitter)(smpl_path, surface=topo, sc_sigma=3.0)  # also LabelDistanceFitter, KeypointFitter, ScanFitter
+    r = fitter.fit(labels, surface=SurfaceTargets(topo, face, bary, target, conf), stages=[(100, cs), (100, cs)], sc_weight=[1.0, 0.1])
+    r = SurfaceFitter(smpl_path, sigma=3.0).fit(targets, steps=200)            # the surface term as the only data term
+
+sc_weight mean_N(e[b, :]), e = `surface_energy` of the iteration's vertices against the fit's `SurfaceTargets` - under cam =
+x[:, :4] with image targets (D = 2), in the vertices' own frame with 3D targets (D = 3; `ScanFitter` takes these only) - is the
+fourth side term, after label distance, through a cotangent sc_weight / N.  The targets are sorted by face once, when they are
+built, outside any captured graph.  `with_surface(cls)` is a class of its own for the reason `LabelDistanceFitter` is one: the
+four fitters' constructors, `fit` and `losses` keep their signatures, and they run exactly the launches they ran before.
+
 Per-row L-BFGS (csrc/lbfgs.hip, smplr_lbfgs_step; tests/_lbfgs_oracle.py restates it in NumPy float64).  The keypoint, scan and
 prior terms are smooth least-squares-like energies that a quasi-Newton method minimises in far fewer evaluations than Adam:
 
@@ -955,17 +967,28 @@ class _SideTerm:
     in its messages too), its column count n, energy(x, verts, joints, data) -> e (B, n) differentiable, on what the forward
     produced, and check(data, B, dev) -> the term's own data on the device (None: the term has none).  `begin` makes the
     copy one fit works with: w (1,) and cot (B, n) device tensors - the weight in the loss and the cotangent w / n of e, so a
-    captured graph follows both - one weight per stage, and the data."""
+    captured graph follows both - one weight per stage, and the data.  width(data) -> n, for a term whose column count is its
+    data's (then n is None until `begin`)."""
 
-    def __init__(self, name, n, energy, check=None):
-        self.name, self.n, self.energy, self.check = name, int(n), energy, check
+    skip_zero = False          # True: a fit (or `losses`) whose weights for the term are 0 in every stage runs without it
+
+    def __init__(self, name, n, energy, check=None, width=None):
+        self.name, self.n, self.energy, self.check, self.width = name, None if n is None else int(n), energy, check, width
+
+    @staticmethod
+    def live(sides):
+        """[(term, its weight per stage, data)] without the `skip_zero` terms whose weights are all 0: those are not
+        evaluated at all, so the fit takes the launches - and gives the bits - of a fitter built without them."""
+        return [(t, ws, d) for t, ws, d in sides if not (t.skip_zero and not any(ws))]
 
     def begin(self, stages, B, dev, data=None):
         """-> the term for one fit over B rows on dev, at its first stage's weight; stages: `_stage_weights`' list."""
         t = _SideTerm(self.name, self.n, self.energy)
         t.stages, t.data = stages, self.check(data, B, dev) if self.check is not None else None
+        if self.width is not None:
+            t.n = int(self.width(t.data))
         t.w = torch.zeros(1, dtype=torch.float32, device=dev)
-        t.cot = torch.zeros((B, self.n), dtype=torch.float32, device=dev)
+        t.cot = torch.zeros((B, t.n), dtype=torch.float32, device=dev)
         t.set(0)
         return t
 
@@ -980,15 +1003,20 @@ class _SideTerm:
 
 
 class _Fitter:
-    """What `ParamFitter`, `ScanFitter` and `KeypointFitter` share: the iteration, `losses`, the loop.  A fitter adds its data
+    """What `ParamFitter`, `ScanFitter`, `KeypointFitter` and `SurfaceFitter` share: the iteration, `losses`, the loop.  A fitter adds its data
     term - `_forward(x, data)` and `_cotangents(B, dev, data)` - and sets num_cam and P."""
     pen_topo = None            # a render.MeshTopology when the fitter was built with `penetration`
     pen_collide = None         # its part-pair table (None: `penetration.part_collision_table(topo, 1)`)
     kp_spec = None             # a keypoints.KeypointSpec when the fitter was built with `keypoints`
     kp_sigma = None            # the robust function's sigma in pixels (None: rho(s) = s)
     ld_spec = None             # a labeldist.LabelDistanceSpec when the fitter was built with `label_distance`
-    _pen = _kp = _ld = None    # their `_SideTerm`s; a fitter's side terms come in this order: penetration, keypoints, then
-                               # label distance
+    sc_topo = None             # a render.MeshTopology when the fitter was built with `surface`
+    sc_sigma = None            # the robust function's sigma, in the targets' unit (None: rho(s) = s)
+    sc_dims = (2, 3)           # the target dimensions the fitter takes (`ScanFitter`: 3 only)
+    _sc_options = (None, None) # surface, sc_sigma of the constructor (`with_surface` sets them; a plain fitter has no term)
+    _sc_call = (None, None)    # surface=, sc_weight= of the `fit` / `losses` call in progress (`with_surface`)
+    _pen = _kp = _ld = _sc = None   # their `_SideTerm`s; a fitter's side terms come in this order: penetration, keypoints,
+                                    # label distance, then surface correspondences
 
     def _layer_init(self, smpl_path, four_columns):
         """A fitter over an `SMPLLayer` (given, or built from a path or a model): layer, num_cam - which must be 4, else a
@@ -1052,10 +1080,54 @@ class _Fitter:
         return (target.detach().to(device=dev, dtype=torch.float32).contiguous(),
                 conf.detach().to(device=dev, dtype=torch.float32).contiguous())
 
+    def _sc_init(self, surface, model, sigma=None):
+        """`surface` of a fitter's constructor: None (no term) or a MeshTopology over the model's vertices.  The term is
+        `surface.surface_energy` of the iteration's vertices against the fit's `SurfaceTargets`: under cam = x[:, :4] with
+        image targets (D = 2), in the vertices' own frame with 3D targets (cam is not used).  Its column count is the data's N:
+        the term is sc_weight mean_N(e), padding included.  With sc_weight = 0 in every stage the term is left out of the fit
+        altogether (`_SideTerm.live`): a cotangent on the vertices, even a zero one, would send the decoder's backward down
+        its per-vertex skinning path, whose sums round in another order than the record-driven one."""
+        from .keypoints import check_sigma
+        from .surface import surface_energy
+        check_sigma(sigma)
+        if surface is None:
+            if sigma is not None:
+                raise ValueError("sc_sigma goes with a fitter built with surface=...")
+            return
+        if not all(hasattr(surface, a) for a in ("faces", "num_verts", "num_faces", "on")):
+            raise TypeError("surface must be a render.MeshTopology")
+        if surface.num_verts != model.num_verts:
+            raise ValueError("the surface topology has %d vertices, the model %d" % (surface.num_verts, model.num_verts))
+        if self.num_cam != 4:
+            raise ValueError("the surface term projects with four camera columns")
+        self.sc_topo, self.sc_sigma = surface, sigma
+
+        def energy(x, verts, joints, data):
+            return surface_energy(verts, x[:, :4] if data.D == 2 else None, data, self.sc_sigma)
+        self._sc = _SideTerm("sc_weight", None, energy, self._sc_data, lambda data: data.N)
+        self._sc.skip_zero = True
+
+    def _sc_data(self, surface, B, dev):
+        """`fit`'s / `losses`' surface=SurfaceTargets: B rows on the fit's device, over the fitter's topology."""
+        from .surface import SurfaceTargets
+        if not isinstance(surface, SurfaceTargets):
+            raise TypeError("surface must be a surface.SurfaceTargets")
+        if surface.B != B:
+            raise ValueError("the surface targets have %d rows, the fit %d" % (surface.B, B))
+        if surface.D not in self.sc_dims:
+            raise ValueError("this fitter takes surface targets with D in %s, got D = %d" % (self.sc_dims, surface.D))
+        if surface.topo is not self.sc_topo and not np.array_equal(surface.topo.faces, self.sc_topo.faces):
+            raise ValueError("the surface targets were built over another topology than the fitter's")
+        if torch.device(surface.device) != torch.device(dev):
+            raise RuntimeError("the surface targets live on %s, the fit on %s" % (surface.device, dev))
+        return surface
+
     def _check_sides(self, pen_weight=None, keypoints=None, kp_weight=None, ld_weight=None, labels=None):
-        """The pairing rules, before anything touches a device: a weight only with its term, keypoint data only with a spec
-        and a spec only with data -> [(term, its weight argument, its data)] of the terms the fitter has, in their order.
-        The label-distance term's data are the fit's own `labels`."""
+        """The pairing rules, before anything touches a device: a weight only with its term, keypoint or surface data only
+        with a spec and a spec only with data -> [(term, its weight argument, its data)] of the terms the fitter has, in their
+        order.  The label-distance term's data are the fit's own `labels`; the surface term's data and weight are the
+        call's `surface=` and `sc_weight=`, which `with_surface`'s `fit` and `losses` hold in `_sc_call` for the call."""
+        surface, sc_weight = self._sc_call
         if self._pen is None and pen_weight is not None:
             raise ValueError("pen_weight goes with a fitter built with penetration=...")
         if self._kp is None:
@@ -1065,8 +1137,13 @@ class _Fitter:
             raise ValueError("this fitter was built with keypoints=...: pass keypoints=(target, conf)")
         if self._ld is None and ld_weight is not None:
             raise ValueError("ld_weight goes with a LabelDistanceFitter built with label_distance=...")
+        if self._sc is None:
+            if surface is not None or sc_weight is not None:
+                raise ValueError("surface and sc_weight go with a fitter built with surface=...")
+        elif surface is None:
+            raise ValueError("this fitter was built with surface=...: pass surface=SurfaceTargets")
         return [(t, w, d) for t, w, d in ((self._pen, pen_weight, None), (self._kp, kp_weight, keypoints),
-                                          (self._ld, ld_weight, labels)) if t is not None]
+                                          (self._ld, ld_weight, labels), (self._sc, sc_weight, surface)) if t is not None]
 
     def _initial(self, B, init, device, default):
         """`initial`: a (B, P) tensor as it is, anything else from default(); then the move to the device."""
@@ -1094,9 +1171,9 @@ class _Fitter:
         term's weight, verts, posed joints or None), then the side terms on those.  -> (terms, loss, silh_loss, silh_weight):
         every term in the order `autograd.grad` takes them, and what `fit_step` gets.  The bits depend on these rules:
           - terms: the data terms first - [seg_loss, silh_loss?] of `ParamFitter`, [p2m, m2p] or the one direction present of
-            `ScanFitter` (p2m scaled by N / counts inside `terms()`), [e] of `KeypointFitter` - then penetration, then
-            keypoints: autograd accumulates into x in that order.
-          - loss: the first data term detached, then + w_pen mean_V, then + w_kp mean_K, each onto every column; silh_loss:
+            `ScanFitter` (p2m scaled by N / counts inside `terms()`), [e] of `KeypointFitter` or `SurfaceFitter` - then penetration,
+            keypoints, label distance and surface correspondences: autograd accumulates into x in that order.
+          - loss: the first data term detached, then + w_pen mean_V, then + w_kp mean_K, + w_ld mean and + w_sc mean_N, each onto every column; silh_loss:
             the second data term where there is one (with `ScanFitter` the m2p terms, silh_weight = m2p_weight, only when both
             directions are on; with one direction the weight is 1.0).  Both contiguous."""
         terms, silh_weight, verts, joints = self._forward(x, data)
@@ -1124,7 +1201,8 @@ class _Fitter:
         x = _lib.require_cuda(x.detach(), "x")
         with torch.no_grad(), torch.cuda.device(x.device):
             B = int(x.shape[0])
-            sides = [t.begin(_stage_weights(w, [None], t.name), B, x.device, d) for t, w, d in sides]
+            sides = [t.begin(ws, B, x.device, d) for t, ws, d in
+                     _SideTerm.live([(t, _stage_weights(w, [None], t.name), d) for t, w, d in sides])]
             _, loss, silh_loss, silh_weight = self._compose(x, data, sides)
             hist = torch.empty((1, B), dtype=torch.float32, device=x.device)
             fit_step(FitState.new(x), torch.zeros_like(x), loss, silh_loss, silh_weight, None, hist,
@@ -1149,7 +1227,7 @@ class _Fitter:
         data = check_data()
         stage_list = check_stages(stages, P, steps)
         stage_w = _stage_prior_weights(prior, prior_weights, stage_list)
-        sides = [(t, _stage_weights(w, stage_list, t.name), d) for t, w, d in sides]
+        sides = _SideTerm.live([(t, _stage_weights(w, stage_list, t.name), d) for t, w, d in sides])
         if opt is None:
             kw = dict(lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), grad_scale=float(grad_scale),
                       mode=mode, patience=int(patience))
@@ -1223,7 +1301,10 @@ class ParamFitter(_Fitter):
         with_ld = label_distance is not None and label_distance is not False
         if with_ld and vertex_sampling not in (None, 1):
             raise ValueError("label_distance needs every vertex: vertex_sampling must be None or 1, got %r" % (vertex_sampling,))
-        outputs = ("verts",) if with_pen or keypoints is not None or with_ld else ()
+        surface, sc_sigma = self._sc_options                                      # (`with_surface` sets them)
+        if surface is not None and vertex_sampling not in (None, 1):
+            raise ValueError("surface needs every vertex: vertex_sampling must be None or 1, got %r" % (vertex_sampling,))
+        outputs = ("verts",) if with_pen or keypoints is not None or with_ld or surface is not None else ()
         if with_ld and isinstance(label_distance, str) and label_distance == "visible":
             outputs += ("mask",)
         # (streams=1: one chain of launches, so a captured graph has no parallel branches)
@@ -1238,6 +1319,7 @@ class ParamFitter(_Fitter):
         self.silh_wh = self.decoder.silh_wh
         self._kp_init(keypoints, self.decoder._model, kp_sigma)
         self._ld_init(label_distance, ld_sigma, ld_slack, ld_directions)
+        self._sc_init(surface, self.decoder._model, sc_sigma)
 
     def _ld_init(self, label_distance, sigma, slack, directions):
         """`label_distance` of `LabelDistanceFitter`'s constructor: None / False (no term), True (`LabelDistanceSpec.from_parts` of the decoder's
@@ -1444,6 +1526,8 @@ class ScanFitter(_Fitter):
         r = fitter.fit(points, counts, init=x0, steps=200, lr=0.02, mode="torch", prior=prior, prior_weights=(1, 1, 1))
     """
 
+    sc_dims = (3,)             # (markers in the scan's frame; the four leading columns are no camera)
+
     def __init__(self, smpl_path=None, topo=None, m2p_weight=1.0, sigma=None, directions=("p2m", "m2p"), penetration=None,
                  collide=None):
         from .render import MeshTopology
@@ -1465,6 +1549,8 @@ class ScanFitter(_Fitter):
         self.sigma = sigma
         # (penetration=True: the fitter's own topology - the verts the term sees are the ones the scan distances see)
         self._pen_init(self.topo if penetration is True else penetration, self.layer._model, collide)
+        # (surface=True: the fitter's own topology; the targets are 3D points in the scan's frame, against `place(x)`)
+        self._sc_init(self.topo if self._sc_options[0] is True else self._sc_options[0], self.layer._model, self._sc_options[1])
 
     def initial(self, B, init=None, device=None):
         """(B, 86) float32 start: None = scale 1, no shift, the mean pose and shape; a (B, 86) tensor as it is."""
@@ -1545,9 +1631,10 @@ class ScanFitter(_Fitter):
         group_size / tie / smooth for several scans of one body (tie="cam" would tie the placement as well), pen_weight with
         a fitter built with `penetration`."""
         loop = _fit_args(locals(), lbfgs=True)
+        sides = self._check_sides(pen_weight)
         data = self._points(points, counts)
         B, dev = int(data[0].shape[0]), data[0].device
-        return self._fit(B, dev, lambda: self.initial(B, init, dev), lambda: data, self._check_sides(pen_weight), **loop)
+        return self._fit(B, dev, lambda: self.initial(B, init, dev), lambda: data, sides, **loop)
 
 
 class KeypointFitter(_Fitter):
@@ -1575,6 +1662,7 @@ class KeypointFitter(_Fitter):
         check_sigma(sigma)
         self.spec, self.sigma = spec, sigma
         self._pen_init(penetration, self.layer._model, collide)
+        self._sc_init(self._sc_options[0], self.layer._model, self._sc_options[1])
 
     def initial(self, B, init=None, device=None):
         """(B, 86) float32 start: None = `smpl_model.mean86(img_wh)` per row; a (B, 86) tensor as it is."""
@@ -1627,9 +1715,137 @@ class KeypointFitter(_Fitter):
         prior_weights (one triple or one per stage), group_size / tie / smooth for several views or frames of one body,
         pen_weight with a fitter built with `penetration`."""
         loop = _fit_args(locals(), lbfgs=True)
+        sides = self._check_sides(pen_weight)
         data = self._data(target, conf)
         B, dev = int(data[0].shape[0]), data[0].device
-        return self._fit(B, dev, lambda: self.initial(B, init, dev), lambda: data, self._check_sides(pen_weight), **loop)
+        return self._fit(B, dev, lambda: self.initial(B, init, dev), lambda: data, sides, **loop)
+
+
+class _WithSurface:
+    """The dense surface-correspondence term on a fitter class: constructor arguments surface= (a render.MeshTopology over
+    the model's vertices; `ScanFitter` also takes True: its own topology) and sc_sigma= (None: rho(s) = s), and on `fit` and
+    `losses` surface= (a `surface.SurfaceTargets` of B rows) and sc_weight= (None: 1, one float, or one per stage).  Every
+    other argument passes through to the fitter's own method; the pairing rules are `_check_sides`'."""
+
+    def __init__(self, *args, surface=None, sc_sigma=None, **kw):
+        self._sc_options = (surface, sc_sigma)
+        super().__init__(*args, **kw)
+
+    def _sc_during(self, call, args, kw, surface, sc_weight):
+        self._sc_call = (surface, sc_weight)
+        try:
+            return call(*args, **kw)
+        finally:
+            self._sc_call = (None, None)
+
+    def fit(self, *args, surface=None, sc_weight=None, **kw):
+        return self._sc_during(super().fit, args, kw, surface, sc_weight)
+
+    def losses(self, *args, surface=None, sc_weight=None, **kw):
+        return self._sc_during(super().losses, args, kw, surface, sc_weight)
+
+
+_with_surface = {}
+
+
+def with_surface(fitter_class):
+    """`ParamFitter`, `LabelDistanceFitter`, `KeypointFitter` or `ScanFitter` -> that fitter with the dense
+    surface-correspondence term as its fourth side term (`_WithSurface`: surface=, sc_sigma= at construction, surface=,
+    sc_weight= on `fit` and `losses`).  A class of its own, as `LabelDistanceFitter` is, because the four fitters' constructors,
+    `fit` and `losses` keep the signatures their callers rely on.  `ScanFitter` takes 3D targets only; the others image targets
+    under cam = x[:, :4] or 3D targets in the vertices' own frame.
+
+        fitter = with_surface(ParamFitter)(smpl_path, surface=topo, sc_sigma=3.0)
+        r = fitter.fit(labels, surface=SurfaceTargets(topo, face, bary, target, conf), sc_weight=[1.0, 0.1], stages=...)
+    """
+    if not (isinstance(fitter_class, type) and issubclass(fitter_class, _Fitter)) or issubclass(fitter_class, (SurfaceFitter, _WithSurface)):
+        raise TypeError("with_surface takes ParamFitter, LabelDistanceFitter, KeypointFitter or ScanFitter")
+    if fitter_class not in _with_surface:
+        _with_surface[fitter_class] = type("Surface" + fitter_class.__name__, (_WithSurface, fitter_class), {"__doc__": _WithSurface.__doc__})
+    return _with_surface[fitter_class]
+
+
+class SurfaceFitter(_Fitter):
+    """`KeypointFitter`'s shape with dense surface correspondences as the only data term: `SMPLLayer ->
+    surface.surface_energy`.  With image targets (D = 2) cam = x[:, :4], the decoder's camera columns, so targets are in the
+    pixel frame of a decoder at `img_wh`; with 3D targets (D = 3) the vertices are compared in the layer's own frame and the
+    four camera columns get no gradient.  Row b's data term is mean_N(e[b, :]) over all N columns (padding counts as 0), e =
+    conf rho(d2) per correspondence (rho = `robust_rho` with `sigma`, the identity when sigma is None), handed to `fit_step`
+    as per-term losses with the constant cotangent 1 / N.  A row whose status is NONFINITE has a NaN loss and gradient and
+    counts as a bad call (nothing changes).  Every launch of an iteration reproduces its bits, so two fits from the same
+    start agree bit for bit.
+
+        fitter = SurfaceFitter(smpl_path, sigma=3.0)                # topo: the model's faces
+        r = fitter.fit(SurfaceTargets(fitter.topo, face, bary, target), steps=200, lr=0.02)
+    """
+
+    def __init__(self, smpl_path=None, topo=None, sigma=None, img_wh=48, penetration=None, collide=None):
+        from .keypoints import check_sigma
+        from .render import MeshTopology
+        self._layer_init(smpl_path, "SurfaceFitter projects with four camera columns")
+        self.img_wh = int(img_wh)
+        if topo is None:
+            faces = self.layer._model.faces
+            if faces is None:
+                raise ValueError("this SMPL model carries no faces: pass topo=MeshTopology(faces, num_verts)")
+            topo = MeshTopology(faces, self.layer._model.num_verts)
+        if not all(hasattr(topo, a) for a in ("faces", "num_verts", "num_faces", "on")):
+            raise TypeError("topo must be a render.MeshTopology")
+        if topo.num_verts != self.layer._model.num_verts:
+            raise ValueError("the topology has %d vertices, the model %d" % (topo.num_verts, self.layer._model.num_verts))
+        check_sigma(sigma)
+        self.topo, self.sigma = topo, sigma
+        self.sc_topo = topo                                       # (what `_sc_data` checks the targets against)
+        self._pen_init(self.topo if penetration is True else penetration, self.layer._model, collide)
+
+    def initial(self, B, init=None, device=None):
+        """(B, 86) float32 start: None = `smpl_model.mean86(img_wh)` per row; a (B, 86) tensor as it is."""
+        from .smpl_model import mean86
+
+        def default():
+            if init is not None:
+                raise ValueError("init must be None or a (B, %d) tensor, got %r" % (self.P, init))
+            return torch.as_tensor(mean86(self.img_wh), dtype=torch.float32).repeat(B, 1)
+        return self._initial(B, init, device, default)
+
+    def terms(self, x, targets):
+        """-> (e (B, N) differentiable in x, the op's details, verts): what `fit_step` gets as `loss`."""
+        from .surface import surface_energy
+        verts = self.layer(x)
+        e, det = surface_energy(verts, x[:, :4] if targets.D == 2 else None, targets, self.sigma, return_details=True)
+        return e, det, verts
+
+    def _forward(self, x, data):
+        e, _, verts = self.terms(x, data)
+        return [e], 1.0, verts, None
+
+    def _cotangents(self, B, dev, data):
+        return [torch.full((B, data.N), 1.0 / data.N, dtype=torch.float32, device=dev)]
+
+    def _data(self, targets):
+        from .surface import SurfaceTargets
+        if not isinstance(targets, SurfaceTargets):
+            raise TypeError("targets must be a surface.SurfaceTargets")
+        if not targets.face.is_cuda:
+            raise RuntimeError("the targets must live on a HIP device (got %s); this framework has no CPU path" % targets.device)
+        return self._sc_data(targets, targets.B, targets.device)
+
+    def losses(self, x, targets, prior=None, prior_weights=None, pen_weight=None):
+        """Per-row loss (B,) of parameters x against the correspondences, reduced by the kernel of the loop (a call with a
+        zero gradient on a scratch state): the bits `fit` would record for x in its history."""
+        return self._losses(x, self._data(targets), prior, prior_weights, self._check_sides(pen_weight))
+
+    def fit(self, targets, init=None, steps=200, lr=1e-2, mode="torch", stages=None, patience=0, grad_scale=1.0, graph=False,
+            check_every=0, history=False, beta1=0.9, beta2=0.999, eps=KERAS_EPS, graph_steps=4, prior=None, prior_weights=None,
+            group_size=1, tie=("shape",), smooth=None, pen_weight=None):
+        """targets: a `surface.SurfaceTargets` on the HIP device -> FitResult.  Everything else as `ParamFitter.fit`: steps or
+        stages = [(steps, column_scale), ...], patience, grad_scale, graph / graph_steps, check_every, history, prior and
+        prior_weights (one triple or one per stage), group_size / tie / smooth for several views or frames of one body,
+        pen_weight with a fitter built with `penetration`."""
+        loop = _fit_args(locals(), lbfgs=True)
+        sides = self._check_sides(pen_weight)
+        data = self._data(targets)
+        return self._fit(data.B, data.device, lambda: self.initial(data.B, init, data.device), lambda: data, sides, **loop)
 
 
 # ---- SMPL+D registration: free vertex offsets under mesh regularisers --------------------------------------------------

@@ -114,6 +114,10 @@ SCHEMAS = {
                 "bool with_jtr=False, int num_cam=4) -> (Tensor, Tensor, Tensor)"),
     "rot6d_fwd": "smplraster::rot6d_fwd(Tensor y, int num_cam=4) -> (Tensor, Tensor)",
     "rot6d_bwd": "smplraster::rot6d_bwd(Tensor y, Tensor status, Tensor dx, int num_cam=4) -> Tensor",
+    "surface_fwd": ("smplraster::surface_fwd(Tensor verts, Tensor? cam, Tensor faces, Tensor face, Tensor bary, Tensor target, "
+                    "Tensor conf, Tensor order, float sigma) -> (Tensor, Tensor, Tensor, Tensor, Tensor)"),
+    "surface_bwd": ("smplraster::surface_bwd(Tensor? cam, Tensor vc_off, Tensor vc_fc, Tensor c_off, Tensor face, Tensor bary, "
+                    "Tensor conf, Tensor order, Tensor status, Tensor ws, Tensor g, float sigma) -> (Tensor, Tensor)"),
 }
 
 _ns = None
