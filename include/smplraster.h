@@ -764,6 +764,52 @@ int smplr_rot6d_fwd(const float *y, int y_stride, int B, int num_cam, float *x, 
 int smplr_rot6d_bwd(const float *y, int y_stride, const int32_t *status, const float *dx, int dx_stride, int B, int num_cam,
                     float *dy, void *stream);
 
+/* ---- probabilistic head: independent Gaussians N(mu_d, exp(s_d)) over the regressor's D-vector - reparameterised samples, the
+ * negative log-likelihood, the product of a group's Gaussians, statistics of sampled meshes (beyond the reference);
+ * INTEGRATION.md 4x ----------------------------------------------------------------------------------------------------------
+ * s is a log-variance, sigma = exp(s / 2).  mu, s, target: B rows of D floats, their strides apart (at least D); every output
+ * is contiguous.  stochastic (D uint8, NULL: all ones) and groups (D int8) are HOST arrays, read during the call.
+ * smplr_prob_sample_fwd: eps (B, S, D) -> x (B, S, D).  Entry (b, i, d) is drawn iff stochastic[d] != 0 and not (mean_first and
+ *   i == 0): x = fl32(mu + sigma eps); every other entry is a bit copy of mu and its eps is not read.  status[b] =
+ *   SMPLR_PROB_NONFINITE when a mu or s of the row or a drawn eps is NaN / Inf, or a sample is not finite after rounding: all of
+ *   the row's samples are NaN.
+ * smplr_prob_sample_bwd: g (B, S, D) the cotangent of x, status the forward's (taken as it is): dmu[b, d] = sum_i g,
+ *   ds[b, d] = sigma / 2 sum_{i drawn} g eps, both in increasing i, ds exactly 0 where stochastic[d] == 0; a flagged row is NaN.
+ * smplr_prob_nll_fwd: groups[d] in -1 .. G - 1 (-1: the column does not count), n_k the columns of group k, w_k = row_w[b, k]
+ *   (row_w (B, G) or NULL: ones); group k counts iff w_k > 0 (a NaN does not), else its term is 0 and nothing of it is read:
+ *   nll[b, k] = w_k / (2 n_k) sum_{d: groups[d] = k} (s_d + (target_d - mu_d)^2 exp(-s_d)) in increasing d (no log 2 pi); an empty
+ *   group gives 0.  status[b]: an operand of a counted group is NaN / Inf or a counted term is not finite in fp32: the row's G
+ *   terms, and in smplr_prob_nll_bwd its 2 D gradients, are NaN.
+ * smplr_prob_nll_bwd: g (B, G): dmu_d = g_k w_k / n_k (mu_d - target_d) exp(-s_d), ds_d = g_k w_k / (2 n_k) (1 - (target_d -
+ *   mu_d)^2 exp(-s_d)), 0 for a column that does not count; both (B, D).
+ * smplr_prob_fuse: rows r G .. r G + G - 1 -> row r of mu_f, s_f (B / G, D), the product of the G Gaussians per column:
+ *   m = min_i s_i, p_i = exp(-(s_i - m)), mu_f = sum mu_i p_i / sum p_i, s_f = m - log sum p_i, in increasing i; G = 1: bit copies.
+ *   A NaN / Inf mu or s: that column's two outputs are NaN and status[r] (B / G) is set.
+ * smplr_prob_spread: points (B S, N, 3), row b's samples consecutive -> mean (B, N, 3), rms (B, N), in one pass over points from
+ *   the sums shifted by sample 0: a = sum_i (p_i - p_0), q = sum_i |p_i - p_0|^2, mean = p_0 + a / S,
+ *   rms = sqrt(max(0, q / S - |a / S|^2)); S = 1: mean a bit copy, rms exactly 0.  A NaN / Inf coordinate: that point's mean and
+ *   rms are NaN and status[b] is set.  points needs 4-byte alignment only.
+ * One kernel launch per call (smplr_prob_spread clears its B status words on the stream first).  All arithmetic is fp64 on the
+ * fp32 operands; each output is rounded to fp32 once; no atomics, no workspace: a row's results are the same bits on every
+ * launch and in any batch.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 0 <= B <= 2^24 (B = 0 is a no-op), 1 <= D <= SMPLR_PROB_MAX_D, strides >= D,
+ * 1 <= S <= 2^16, 1 <= N <= 2^24, likelihood groups 1 <= G <= 8 and every group id in -1 .. G - 1, fused rows 1 <= G <= 16 with
+ * B % G == 0; no null pointer (stochastic and row_w excepted).                                                                  */
+#define SMPLR_PROB_NONFINITE 1
+#define SMPLR_PROB_MAX_D 256
+int smplr_prob_sample_fwd(const float *mu, int mu_stride, const float *s, int s_stride, const float *eps, const uint8_t *stochastic,
+                          int mean_first, int B, int S, int D, float *x, int32_t *status, void *stream);
+int smplr_prob_sample_bwd(const float *s, int s_stride, const float *eps, const uint8_t *stochastic, int mean_first,
+                          const int32_t *status, const float *g, int B, int S, int D, float *dmu, float *ds, void *stream);
+int smplr_prob_nll_fwd(const float *mu, int mu_stride, const float *s, int s_stride, const float *target, int t_stride,
+                       const int8_t *groups, const float *row_w, int B, int D, int G, float *nll, int32_t *status, void *stream);
+int smplr_prob_nll_bwd(const float *mu, int mu_stride, const float *s, int s_stride, const float *target, int t_stride,
+                       const int8_t *groups, const float *row_w, const int32_t *status, const float *g, int B, int D, int G,
+                       float *dmu, float *ds, void *stream);
+int smplr_prob_fuse(const float *mu, int mu_stride, const float *s, int s_stride, int B, int D, int G, float *mu_f, float *s_f,
+                    int32_t *status, void *stream);
+int smplr_prob_spread(const float *points, int B, int S, int N, float *mean, float *rms, int32_t *status, void *stream);
+
 /* ---- label-map distance term: projected vertices against an integer label map, both directions, by class, with gradients
  * (beyond the reference); INTEGRATION.md 4r ---------------------------------------------------------------------------------
  * verts (B, V, 3) fp32, cam (B, 4) = (k_u, k_v, u0, v0), labels (B, W, W) int32: stored pixel q = r W + c sits at the point

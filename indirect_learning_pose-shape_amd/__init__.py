@@ -30,4 +30,7 @@ def __getattr__(name):
     if name in ("SyntheticBatches", "BodySampler", "proxy_inputs", "corruption_draws", "frame_cameras"):
         from . import synthetic
         return getattr(synthetic, name)
+    if name in ("gaussian_samples", "gaussian_nll", "fuse_gaussians", "fuse_shape", "sample_spread"):
+        from . import prob
+        return getattr(prob, name)
     raise AttributeError(name)

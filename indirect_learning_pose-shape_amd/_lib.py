@@ -102,7 +102,13 @@ SIGNATURES = {
     "smplr_sup_bwd": (c_int, [P, P, I, P, P, P, P, P, I, P, P, P, P, P, I, I, I, I, I, P, P, P, P]),
     "smplr_rot6d_fwd": (c_int, [P, I, I, I, P, P, P]),
     "smplr_rot6d_bwd": (c_int, [P, I, P, P, I, I, I, P, P]),
-    "smplr_ld_prep": (c_int, [P, I, I, I, P, P, P]),
+    "smplr_prob_sample_fwd": (c_int, [P, I, P, I, P, P, I, I, I, I, P, P, P]),
+    "smplr_prob_sample_bwd": (c_int, [P, I, P, P, I, P, P, I, I, I, P, P, P]),
+    "smplr_prob_nll_fwd": (c_int, [P, I, P, I, P, I, P, P, I, I, I, P, P, P]),
+    "smplr_prob_nll_bwd": (c_int, [P, I, P, I, P, I, P, P, P, P, I, I, I, P, P, P]),
+    "smplr_prob_fuse": (c_int, [P, I, P, I, I, I, I, P, P, P, P]),
+    "smplr_prob_spread": (c_int, [P, I, I, I, P, P, P, P]),
+    "smplr_ld_prep":(c_int, [P, I, I, I, P, P, P]),
     "smplr_ld_fwd": (c_int, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, c_float, c_float, P, P, P, P, P, P, P, P, P]),
     "smplr_ld_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, c_float, c_float, P, P, P, P]),
     "smplr_mesh_reg_workspace": (c_size_t, [I, I]),

@@ -1643,6 +1643,205 @@ Tensor rot6d_bwd_meta(const Tensor &y, const Tensor &status, const Tensor &dx, i
   return at::empty({y.size(0), num_cam + 154}, y.options());
 }
 
+// ---- probabilistic head (include/smplraster.h): mu, s, target (B, D) fp32, rows at least D apart; eps, g of
+// the samples (B, S, D); the column tables are integer lists (host data: the launchers check them); outputs contiguous ---------
+struct ProbDims { int64_t B, D, ms, ss; };
+ProbDims prob_rows(const Tensor &mu, const Tensor &s) {
+  TORCH_CHECK(mu.dim() == 2 && mu.size(1) >= 1 && mu.size(1) <= SMPLR_PROB_MAX_D, "mu must be (B, D) with 1 <= D <= ", SMPLR_PROB_MAX_D);
+  ProbDims d;
+  d.B = mu.size(0); d.D = mu.size(1);
+  d.ms = rot6d_rows(mu, d.D, "mu");
+  TORCH_CHECK(s.dim() == 2 && s.size(0) == d.B, "s must have mu's shape");
+  d.ss = rot6d_rows(s, d.D, "s");
+  return d;
+}
+void prob_bsd(const Tensor &t, int64_t B, int64_t D, const char *name) {
+  TORCH_CHECK(t.dim() == 3 && t.size(0) == B && t.size(2) == D && t.size(1) >= 1 && t.size(1) <= 65536 && t.scalar_type() == at::kFloat &&
+              t.is_contiguous(), name, " must be a contiguous (B, S, D) float32 tensor with 1 <= S <= 65536");
+}
+std::vector<uint8_t> prob_mask(at::OptionalIntArrayRef stochastic, int64_t D) {
+  std::vector<uint8_t> m((size_t)D, 1);
+  if (stochastic.has_value()) {
+    TORCH_CHECK((int64_t)stochastic->size() == D, "stochastic must hold D = ", D, " flags");
+    for (int64_t d = 0; d < D; ++d) m[(size_t)d] = (*stochastic)[(size_t)d] != 0;
+  }
+  return m;
+}
+std::vector<int8_t> prob_groups(at::IntArrayRef groups, int64_t D, int64_t G) {
+  TORCH_CHECK((int64_t)groups.size() == D, "groups must hold D = ", D, " ids");
+  TORCH_CHECK(G >= 1 && G <= 8, "G = ", G, " must lie in 1 .. 8");
+  std::vector<int8_t> g((size_t)D);
+  for (int64_t d = 0; d < D; ++d) {
+    TORCH_CHECK(groups[(size_t)d] >= -1 && groups[(size_t)d] < G, "group id ", groups[(size_t)d], " at column ", d, " outside -1 .. G - 1");
+    g[(size_t)d] = (int8_t)groups[(size_t)d];
+  }
+  return g;
+}
+void prob_status(const Tensor &status, int64_t B) {
+  TORCH_CHECK(status.dim() == 1 && status.size(0) == B && status.scalar_type() == at::kInt, "status must be (B) int32");
+}
+std::tuple<Tensor, Tensor> prob_sample_fwd(const Tensor &mu, const Tensor &s, const Tensor &eps, at::OptionalIntArrayRef stochastic,
+                                           bool mean_first) {
+  const ProbDims d = prob_rows(mu, s);
+  prob_bsd(eps, d.B, d.D, "eps");
+  const std::vector<uint8_t> mask = prob_mask(stochastic, d.D);
+  rot6d_on_device(mu, "mu"); rot6d_on_device(s, "s"); rot6d_on_device(eps, "eps");
+  same_device(mu, {{"s", &s}, {"eps", &eps}});
+  DeviceGuard guard(mu.device());
+  Tensor x = f32({d.B, eps.size(1), d.D}, mu), status = at::empty({d.B}, mu.options().dtype(at::kInt));
+  if (d.B == 0) return {x, status};
+  ok(smplr_prob_sample_fwd(mu.data_ptr<float>(), (int)d.ms, s.data_ptr<float>(), (int)d.ss, eps.data_ptr<float>(), mask.data(),
+                           mean_first ? 1 : 0, (int)d.B, (int)eps.size(1), (int)d.D, x.data_ptr<float>(), status.data_ptr<int32_t>(),
+                           cur_stream()),
+     "smplr_prob_sample_fwd");
+  return {x, status};
+}
+std::tuple<Tensor, Tensor> prob_sample_fwd_meta(const Tensor &mu, const Tensor &s, const Tensor &eps, at::OptionalIntArrayRef stochastic,
+                                                bool) {
+  const ProbDims d = prob_rows(mu, s);
+  prob_bsd(eps, d.B, d.D, "eps");
+  prob_mask(stochastic, d.D);
+  return {at::empty({d.B, eps.size(1), d.D}, mu.options()), at::empty({d.B}, mu.options().dtype(at::kInt))};
+}
+int64_t prob_sample_bwd_check(const Tensor &s, const Tensor &eps, at::OptionalIntArrayRef stochastic, const Tensor &status,
+                              const Tensor &g) {
+  TORCH_CHECK(s.dim() == 2 && s.size(1) >= 1 && s.size(1) <= SMPLR_PROB_MAX_D, "s must be (B, D) with 1 <= D <= ", SMPLR_PROB_MAX_D);
+  const int64_t ss = rot6d_rows(s, s.size(1), "s");
+  prob_bsd(eps, s.size(0), s.size(1), "eps");
+  prob_bsd(g, s.size(0), s.size(1), "g");
+  TORCH_CHECK(g.size(1) == eps.size(1), "g must have eps' shape");
+  prob_mask(stochastic, s.size(1));
+  prob_status(status, s.size(0));
+  return ss;
+}
+std::tuple<Tensor, Tensor> prob_sample_bwd(const Tensor &s, const Tensor &eps, at::OptionalIntArrayRef stochastic, bool mean_first,
+                                           const Tensor &status, const Tensor &g) {
+  const int64_t ss = prob_sample_bwd_check(s, eps, stochastic, status, g), B = s.size(0), D = s.size(1);
+  const std::vector<uint8_t> mask = prob_mask(stochastic, D);
+  rot6d_on_device(s, "s"); rot6d_on_device(eps, "eps"); rot6d_on_device(g, "g"); dev_typed(status, at::kInt, "status");
+  same_device(s, {{"eps", &eps}, {"g", &g}, {"status", &status}});
+  DeviceGuard guard(s.device());
+  Tensor dmu = f32({B, D}, s), ds = f32({B, D}, s);
+  if (B == 0) return {dmu, ds};
+  ok(smplr_prob_sample_bwd(s.data_ptr<float>(), (int)ss, eps.data_ptr<float>(), mask.data(), mean_first ? 1 : 0,
+                           status.data_ptr<int32_t>(), g.data_ptr<float>(), (int)B, (int)eps.size(1), (int)D, dmu.data_ptr<float>(),
+                           ds.data_ptr<float>(), cur_stream()),
+     "smplr_prob_sample_bwd");
+  return {dmu, ds};
+}
+std::tuple<Tensor, Tensor> prob_sample_bwd_meta(const Tensor &s, const Tensor &eps, at::OptionalIntArrayRef stochastic, bool,
+                                                const Tensor &status, const Tensor &g) {
+  prob_sample_bwd_check(s, eps, stochastic, status, g);
+  return {at::empty({s.size(0), s.size(1)}, s.options()), at::empty({s.size(0), s.size(1)}, s.options())};
+}
+int64_t prob_nll_check(const ProbDims &d, const Tensor &target, int64_t G, const c10::optional<Tensor> &row_w) {
+  TORCH_CHECK(target.dim() == 2 && target.size(0) == d.B, "target must have mu's shape");
+  const int64_t ts = rot6d_rows(target, d.D, "target");
+  if (row_w.has_value())
+    TORCH_CHECK(row_w->dim() == 2 && row_w->size(0) == d.B && row_w->size(1) == G && row_w->scalar_type() == at::kFloat &&
+                row_w->is_contiguous(), "row_w must be a contiguous (B, G) float32 tensor");
+  return ts;
+}
+std::tuple<Tensor, Tensor> prob_nll_fwd(const Tensor &mu, const Tensor &s, const Tensor &target, at::IntArrayRef groups, int64_t G,
+                                        const c10::optional<Tensor> &row_w) {
+  const ProbDims d = prob_rows(mu, s);
+  const std::vector<int8_t> gid = prob_groups(groups, d.D, G);
+  const int64_t ts = prob_nll_check(d, target, G, row_w);
+  rot6d_on_device(mu, "mu"); rot6d_on_device(s, "s"); rot6d_on_device(target, "target");
+  if (row_w.has_value()) rot6d_on_device(*row_w, "row_w");
+  const Tensor none;
+  same_device(mu, {{"s", &s}, {"target", &target}, {"row_w", row_w.has_value() ? &*row_w : &none}});
+  DeviceGuard guard(mu.device());
+  Tensor nll = f32({d.B, G}, mu), status = at::empty({d.B}, mu.options().dtype(at::kInt));
+  if (d.B == 0) return {nll, status};
+  ok(smplr_prob_nll_fwd(mu.data_ptr<float>(), (int)d.ms, s.data_ptr<float>(), (int)d.ss, target.data_ptr<float>(), (int)ts, gid.data(),
+                        row_w.has_value() ? row_w->data_ptr<float>() : nullptr, (int)d.B, (int)d.D, (int)G, nll.data_ptr<float>(),
+                        status.data_ptr<int32_t>(), cur_stream()),
+     "smplr_prob_nll_fwd");
+  return {nll, status};
+}
+std::tuple<Tensor, Tensor> prob_nll_fwd_meta(const Tensor &mu, const Tensor &s, const Tensor &target, at::IntArrayRef groups, int64_t G,
+                                             const c10::optional<Tensor> &row_w) {
+  const ProbDims d = prob_rows(mu, s);
+  prob_groups(groups, d.D, G);
+  prob_nll_check(d, target, G, row_w);
+  return {at::empty({d.B, G}, mu.options()), at::empty({d.B}, mu.options().dtype(at::kInt))};
+}
+std::tuple<Tensor, Tensor> prob_nll_bwd(const Tensor &mu, const Tensor &s, const Tensor &target, at::IntArrayRef groups, int64_t G,
+                                        const c10::optional<Tensor> &row_w, const Tensor &status, const Tensor &g) {
+  const ProbDims d = prob_rows(mu, s);
+  const std::vector<int8_t> gid = prob_groups(groups, d.D, G);
+  const int64_t ts = prob_nll_check(d, target, G, row_w);
+  prob_status(status, d.B);
+  TORCH_CHECK(g.dim() == 2 && g.size(0) == d.B && g.size(1) == G, "g must be (B, G)");
+  dev_f32(g, "g"); dev_typed(status, at::kInt, "status");
+  rot6d_on_device(mu, "mu"); rot6d_on_device(s, "s"); rot6d_on_device(target, "target");
+  if (row_w.has_value()) rot6d_on_device(*row_w, "row_w");
+  const Tensor none;
+  same_device(mu, {{"s", &s}, {"target", &target}, {"row_w", row_w.has_value() ? &*row_w : &none}, {"status", &status}, {"g", &g}});
+  DeviceGuard guard(mu.device());
+  Tensor dmu = f32({d.B, d.D}, mu), ds = f32({d.B, d.D}, mu);
+  if (d.B == 0) return {dmu, ds};
+  ok(smplr_prob_nll_bwd(mu.data_ptr<float>(), (int)d.ms, s.data_ptr<float>(), (int)d.ss, target.data_ptr<float>(), (int)ts, gid.data(),
+                        row_w.has_value() ? row_w->data_ptr<float>() : nullptr, status.data_ptr<int32_t>(), g.data_ptr<float>(),
+                        (int)d.B, (int)d.D, (int)G, dmu.data_ptr<float>(), ds.data_ptr<float>(), cur_stream()),
+     "smplr_prob_nll_bwd");
+  return {dmu, ds};
+}
+std::tuple<Tensor, Tensor> prob_nll_bwd_meta(const Tensor &mu, const Tensor &s, const Tensor &target, at::IntArrayRef groups, int64_t G,
+                                             const c10::optional<Tensor> &row_w, const Tensor &status, const Tensor &g) {
+  const ProbDims d = prob_rows(mu, s);
+  prob_groups(groups, d.D, G);
+  prob_nll_check(d, target, G, row_w);
+  prob_status(status, d.B);
+  TORCH_CHECK(g.dim() == 2 && g.size(0) == d.B && g.size(1) == G && g.scalar_type() == at::kFloat, "g must be (B, G) float32");
+  return {at::empty({d.B, d.D}, mu.options()), at::empty({d.B, d.D}, mu.options())};
+}
+void prob_fuse_check(const ProbDims &d, int64_t G) {
+  TORCH_CHECK(G >= 1 && G <= 16 && d.B % G == 0, "group_size = ", G, " must lie in 1 .. 16 and divide B = ", d.B);
+}
+std::tuple<Tensor, Tensor, Tensor> prob_fuse(const Tensor &mu, const Tensor &s, int64_t G) {
+  const ProbDims d = prob_rows(mu, s);
+  prob_fuse_check(d, G);
+  rot6d_on_device(mu, "mu"); rot6d_on_device(s, "s");
+  same_device(mu, {{"s", &s}});
+  DeviceGuard guard(mu.device());
+  Tensor mu_f = f32({d.B / G, d.D}, mu), s_f = f32({d.B / G, d.D}, mu), status = at::empty({d.B / G}, mu.options().dtype(at::kInt));
+  if (d.B == 0) return {mu_f, s_f, status};
+  ok(smplr_prob_fuse(mu.data_ptr<float>(), (int)d.ms, s.data_ptr<float>(), (int)d.ss, (int)d.B, (int)d.D, (int)G, mu_f.data_ptr<float>(),
+                     s_f.data_ptr<float>(), status.data_ptr<int32_t>(), cur_stream()),
+     "smplr_prob_fuse");
+  return {mu_f, s_f, status};
+}
+std::tuple<Tensor, Tensor, Tensor> prob_fuse_meta(const Tensor &mu, const Tensor &s, int64_t G) {
+  const ProbDims d = prob_rows(mu, s);
+  prob_fuse_check(d, G);
+  return {at::empty({d.B / G, d.D}, mu.options()), at::empty({d.B / G, d.D}, mu.options()),
+          at::empty({d.B / G}, mu.options().dtype(at::kInt))};
+}
+void prob_spread_check(const Tensor &points, int64_t S) {
+  TORCH_CHECK(points.dim() == 3 && points.size(2) == 3 && points.size(1) >= 1 && points.scalar_type() == at::kFloat &&
+              points.is_contiguous(), "points must be a contiguous (B S, N, 3) float32 tensor with N >= 1");
+  TORCH_CHECK(S >= 1 && S <= 65536 && points.size(0) % S == 0, "S = ", S, " must lie in 1 .. 65536 and divide the ", points.size(0), " rows");
+}
+std::tuple<Tensor, Tensor, Tensor> prob_spread(const Tensor &points, int64_t S) {
+  prob_spread_check(points, S);
+  rot6d_on_device(points, "points");
+  DeviceGuard guard(points.device());
+  const int64_t B = points.size(0) / S, N = points.size(1);
+  Tensor mean = f32({B, N, 3}, points), rms = f32({B, N}, points), status = at::empty({B}, points.options().dtype(at::kInt));
+  if (B == 0) return {mean, rms, status};
+  ok(smplr_prob_spread(points.data_ptr<float>(), (int)B, (int)S, (int)N, mean.data_ptr<float>(), rms.data_ptr<float>(),
+                       status.data_ptr<int32_t>(), cur_stream()),
+     "smplr_prob_spread");
+  return {mean, rms, status};
+}
+std::tuple<Tensor, Tensor, Tensor> prob_spread_meta(const Tensor &points, int64_t S) {
+  prob_spread_check(points, S);
+  const int64_t B = points.size(0) / S, N = points.size(1);
+  return {at::empty({B, N, 3}, points.options()), at::empty({B, N}, points.options()), at::empty({B}, points.options().dtype(at::kInt))};
+}
+
 // ---- dense surface-correspondence term (include/smplraster.h): the sorted arrays of a surface.SurfaceTargets;
 // cam given: D = 2, cam None: D = 3 -----------------------------------------------------------------------------------------
 struct ScDims { int64_t B, V, F, N, D; };
@@ -1826,6 +2025,13 @@ TORCH_LIBRARY(smplraster, m) {
         "(Tensor, Tensor, Tensor)");
   m.def("rot6d_fwd(Tensor y, int num_cam=4) -> (Tensor, Tensor)");
   m.def("rot6d_bwd(Tensor y, Tensor status, Tensor dx, int num_cam=4) -> Tensor");
+  m.def("prob_sample_fwd(Tensor mu, Tensor s, Tensor eps, int[]? stochastic=None, bool mean_first=False) -> (Tensor, Tensor)");
+  m.def("prob_sample_bwd(Tensor s, Tensor eps, int[]? stochastic, bool mean_first, Tensor status, Tensor g) -> (Tensor, Tensor)");
+  m.def("prob_nll_fwd(Tensor mu, Tensor s, Tensor target, int[] groups, int G, Tensor? row_w=None) -> (Tensor, Tensor)");
+  m.def("prob_nll_bwd(Tensor mu, Tensor s, Tensor target, int[] groups, int G, Tensor? row_w, Tensor status, Tensor g) -> "
+        "(Tensor, Tensor)");
+  m.def("prob_fuse(Tensor mu, Tensor s, int group_size) -> (Tensor, Tensor, Tensor)");
+  m.def("prob_spread(Tensor points, int S) -> (Tensor, Tensor, Tensor)");
   m.def("surface_fwd(Tensor verts, Tensor? cam, Tensor faces, Tensor face, Tensor bary, Tensor target, Tensor conf, Tensor order, "
         "float sigma) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("surface_bwd(Tensor? cam, Tensor vc_off, Tensor vc_fc, Tensor c_off, Tensor face, Tensor bary, Tensor conf, Tensor order, "
@@ -1868,6 +2074,12 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("sup_bwd", &sup_bwd);
   m.impl("rot6d_fwd", &rot6d_fwd);
   m.impl("rot6d_bwd", &rot6d_bwd);
+  m.impl("prob_sample_fwd", &prob_sample_fwd);
+  m.impl("prob_sample_bwd", &prob_sample_bwd);
+  m.impl("prob_nll_fwd", &prob_nll_fwd);
+  m.impl("prob_nll_bwd", &prob_nll_bwd);
+  m.impl("prob_fuse", &prob_fuse);
+  m.impl("prob_spread", &prob_spread);
   m.impl("surface_fwd", &surface_fwd);
   m.impl("surface_bwd", &surface_bwd);
 }
@@ -1908,6 +2120,12 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("sup_bwd", &sup_bwd_meta);
   m.impl("rot6d_fwd", &rot6d_fwd_meta);
   m.impl("rot6d_bwd", &rot6d_bwd_meta);
+  m.impl("prob_sample_fwd", &prob_sample_fwd_meta);
+  m.impl("prob_sample_bwd", &prob_sample_bwd_meta);
+  m.impl("prob_nll_fwd", &prob_nll_fwd_meta);
+  m.impl("prob_nll_bwd", &prob_nll_bwd_meta);
+  m.impl("prob_fuse", &prob_fuse_meta);
+  m.impl("prob_spread", &prob_spread_meta);
   m.impl("surface_fwd", &surface_fwd_meta);
   m.impl("surface_bwd", &surface_bwd_meta);
 }

@@ -122,6 +122,61 @@ def evaluate_3d(smpl_model, smpl_layer, batches, root_joint=None):
 
 
 @torch.no_grad()
+def evaluate_uncertainty(smpl_model, smpl_layer, batches, samples, generator=None):
+    """Does the predicted spread say where the prediction is wrong?  smpl_model: an `SMPLRegressor(probabilistic=True)`;
+    batches: an iterable of (images, truth) on the model's device, truth a dict with "verts" (N, V, 3) and "x" (N, 86) as
+    `SyntheticBatches(truth=True)` yields it; samples = S >= 2 bodies are drawn per image (sample 0 the mean) from
+    `generator`, decoded by `smpl_layer`, and `prob.sample_spread` gives every vertex its rms distance to the sample mean.
+    -> dict(rms (V,) float64: the mean rms per vertex over all images; error (V,): the mean actual error per vertex of the
+    mean prediction (`eval3d.point_errors(per_point="none")`); correlation: Pearson's r between rms and actual error over
+    all (image, vertex) pairs; nll (2,): the mean pose and shape likelihood (`prob.gaussian_nll`); count: images counted)."""
+    from .eval3d import point_errors
+    from .prob import gaussian_nll, sample_spread
+    S = int(samples)
+    if S < 2:
+        raise ValueError("samples must be at least 2: one body has no spread")
+    if not getattr(smpl_model, "probabilistic", False):
+        raise ValueError("evaluate_uncertainty needs an SMPLRegressor(probabilistic=True)")
+    acc = None
+    was_training = smpl_model.training
+    smpl_model.eval()
+    try:
+        for images, truth in batches:
+            smpl = smpl_model(images)
+            dev, n = smpl.device, int(smpl.shape[0])
+            eps = torch.randn((n, S, smpl_model.nout), generator=generator, device=dev)
+            verts = smpl_layer(smpl_model.sample(eps, mean_first=True))
+            _, rms = sample_spread(verts, S)
+            pred = verts.reshape(n, S, -1, 3)[:, 0].contiguous()
+            err = point_errors(pred, truth["verts"].float(), per_point="none")["per_point"]
+            x_t = truth["x"].float()
+            nc = smpl_layer.num_cam
+            if smpl_model.pose_repr == "rot6d":
+                from .rot6d import axis_angle_to_rot6d
+                x_t = torch.cat([x_t[:, :nc], axis_angle_to_rot6d(x_t[:, nc:nc + 72].reshape(n, 24, 3)).reshape(n, 144),
+                                 x_t[:, nc + 72:]], 1)
+            groups = (-1,) * nc + (0,) * (smpl_model.nout - nc - 10) + (1,) * 10
+            nll = gaussian_nll(smpl_model.mean, smpl_model.log_var, x_t, groups)
+            r, e = rms.double(), err.double()
+            ok = torch.isfinite(r).all(1) & torch.isfinite(e).all(1) & torch.isfinite(nll).all(1)
+            r, e = r[ok], e[ok]
+            part = [r.sum(0), e.sum(0), r.sum(), e.sum(), (r * r).sum(), (e * e).sum(), (r * e).sum(), nll[ok].double().sum(0),
+                    ok.sum().double()]
+            acc = part if acc is None else [a + p for a, p in zip(acc, part)]
+    finally:
+        smpl_model.train(was_training)
+    if acc is None:
+        raise ValueError("evaluate_uncertainty: no batches")
+    count = int(acc[8])
+    m = max(count, 1) * acc[0].numel()
+    sr, se, srr, see, sre = (float(v) for v in acc[2:7])
+    cov, vr, ve = sre / m - sr * se / m ** 2, srr / m - (sr / m) ** 2, see / m - (se / m) ** 2
+    return {"rms": (acc[0] / max(count, 1)).cpu().numpy(), "error": (acc[1] / max(count, 1)).cpu().numpy(),
+            "correlation": cov / np.sqrt(vr * ve) if vr > 0 and ve > 0 else float("nan"),
+            "nll": (acc[7] / max(count, 1)).cpu().numpy(), "count": count}
+
+
+@torch.no_grad()
 def evaluate_measurements(smpl_model, smpl_layer, batches, spec, tpose=True):
     """The loop of `evaluate_3d` with gt = (gt_pose (N, 72), gt_shape (N, 10)), comparing body measurements instead of
     vertices: prediction and ground truth are decoded by the same `smpl_layer` and measured by `mesh_measures(verts, spec)`

@@ -9,20 +9,36 @@ from .training import regress
 
 
 @torch.no_grad()
-def predict_batch(smpl_model, decoder, images, amp=None):
+def predict_batch(smpl_model, decoder, images, amp=None, samples=None, generator=None):
     """images (N,3,H,W) or (N,H,W,3) on the HIP device -> dict(smpl (N,86), verts (N,6890,3),
     projects (N,V',3), segs (N,W,W,32) raw scores, seg_maps (N,W,W) int64 = argmax over channels).
     amp = "bf16": the encoder + regressor run under torch.autocast(bfloat16) (`training.amp_dtype`); the 86-vector and
-    everything the decoder makes of it stay fp32.  amp = None: fp32 throughout."""
+    everything the decoder makes of it stay fp32.  amp = None: fp32 throughout.
+    samples = S >= 1 (an `SMPLRegressor(probabilistic=True)` only; default None: nothing below happens): S bodies per image
+    are drawn from the predicted Gaussian with `generator` (sample 0 the mean) and skinned as N S more rows; the result gains
+    verts_mean (N,6890,3) and verts_rms (N,6890), `prob.sample_spread` of them: the per-vertex uncertainty map."""
     was_training = smpl_model.training
     smpl_model.eval()
     try:
         param = regress(smpl_model, images, amp)               # (amp = None: smpl_model(images) itself)
         out = dict(decoder(param), smpl=param)                 # what FullModel(smpl_model, decoder, "all") returns
+        spread = None
+        if samples is not None:
+            from .keras_smpl.batch_smpl import SMPLLayer
+            from .prob import sample_spread
+            S = int(samples)
+            with torch.no_grad():
+                eps = torch.randn((param.shape[0], S, smpl_model.nout), generator=generator, device=param.device)
+                layer = SMPLLayer(decoder._model, num_cam=decoder.num_cam)
+                layer._consts, layer._consts_device = decoder.constants(param.device), param.device
+                spread = sample_spread(layer(smpl_model.sample(eps, mean_first=True)), S)
     finally:
         smpl_model.train(was_training)
-    return {"smpl": out["smpl"], "verts": out["verts"], "projects": out["projects"], "segs": out["seg"],
-            "seg_maps": out["seg"].argmax(dim=-1)}
+    res = {"smpl": out["smpl"], "verts": out["verts"], "projects": out["projects"], "segs": out["seg"],
+           "seg_maps": out["seg"].argmax(dim=-1)}
+    if spread is not None:
+        res["verts_mean"], res["verts_rms"] = spread
+    return res
 
 
 def refine_predictions(smpl_model, fitter, images, labels, **fit_kw):

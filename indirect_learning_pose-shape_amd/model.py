@@ -172,10 +172,15 @@ class SMPLRegressor(nn.Module):
     158 = [cam | 24 x 6 | beta], the IEF state is those 158 and starts at `rot6d.mean_rot6d_row`, `scaledown` applies to the
     158-delta, and `rot6d.params_from_rot6d` turns the result into the (N, 86) every consumer takes; its status (N,) int32
     stays on the device as `self.pose_status` (None before the first forward and with "axis_angle").
+    probabilistic (beyond the reference, default off: names, shapes and outputs unchanged): the regressor predicts an
+    independent Gaussian per column of the space it works in (86, or 158 with "rot6d").  A layer `spread` = Linear(2048, nout)
+    with zero weight and bias 2 log init_sigma gives the log-variances; forward still returns (N, 86), made from the mean, and
+    leaves `self.mean` and `self.log_var`, both (N, nout) fp32 (also under autocast) and part of the graph, for `prob.py`:
+    `sample(eps)` draws from them.  The camera columns are not stochastic (`self.stochastic`).
     """
 
     def __init__(self, output_wh, encoder_architecture="resnet50", use_IEF=False, scaledown=0.005, in_channels=3,
-                 pose_repr="axis_angle"):
+                 pose_repr="axis_angle", probabilistic=False, init_sigma=0.1):
         super().__init__()
         if pose_repr not in ("axis_angle", "rot6d"):
             raise ValueError("pose_repr must be 'axis_angle' or 'rot6d'")
@@ -198,6 +203,38 @@ class SMPLRegressor(nn.Module):
         else:
             self.mlp = nn.Sequential(nn.Linear(2048, 2048), nn.ReLU(inplace=True),
                                      nn.Linear(2048, 1024), nn.ReLU(inplace=True), nn.Linear(1024, nout))
+        self.probabilistic, self.nout = bool(probabilistic), nout
+        self.mean = self.log_var = None
+        self.stochastic = (0,) * 4 + (1,) * (nout - 4)        # (the camera is regressed, not sampled)
+        if self.probabilistic:
+            import math
+            if not float(init_sigma) > 0:
+                raise ValueError("init_sigma must be positive")
+            self.spread = nn.Linear(2048, nout)
+            nn.init.zeros_(self.spread.weight)
+            nn.init.constant_(self.spread.bias, 2.0 * math.log(float(init_sigma)))
+
+    def _distribution(self, feats, mean):
+        """Keeps the Gaussian of this forward: mean (N, nout) as regressed, log_var = spread(feats), both fp32."""
+        if self.probabilistic:
+            self.mean, self.log_var = mean.float(), self.spread(feats).float()
+
+    def sample(self, eps, mean_first=True):
+        """eps (N, S, nout) standard normal draws (the caller's: torch.randn(..., generator=g)) -> (N S, 86), a row's S samples
+        consecutive: `prob.gaussian_samples` of the last forward's Gaussian and, with "rot6d", `rot6d.params_from_rot6d`.
+        mean_first: sample 0 of every row is the mean itself.  Differentiable in the regressor's parameters."""
+        from .prob import gaussian_samples
+        if not self.probabilistic or self.mean is None:
+            raise RuntimeError("sample() needs probabilistic=True and a forward pass before it")
+        x = gaussian_samples(self.mean, self.log_var, eps, self.stochastic, mean_first)
+        x = x.view(-1, self.nout)
+        if self.pose_repr != "rot6d":
+            return x
+        if x.device.type == "meta":                            # (shapes only: the op's Meta kernel)
+            from . import torch_ops
+            return torch_ops.load().rot6d_fwd(x, 4)[0]
+        from .rot6d import params_from_rot6d
+        return params_from_rot6d(x)
 
     def _forward_rot6d(self, feats):
         """The regression module in 6D space -> (N, 86): the mean row and the state are (N, 158), the pose head is fp32."""
@@ -210,6 +247,7 @@ class SMPLRegressor(nn.Module):
             for _ in range(3):
                 state = torch.cat([feats, y], dim=1)
                 y = y + self.IEF_layer_3(F.relu(self.IEF_layer_2(F.relu(self.IEF_layer_1(state))))) * self.scaledown
+        self._distribution(feats, y)
         x, self.pose_status = params_from_rot6d(y.float(), return_status=True)
         return x
 
@@ -220,13 +258,16 @@ class SMPLRegressor(nn.Module):
         if self.pose_repr == "rot6d":
             return self._forward_rot6d(feats)
         if not self.use_IEF:
-            return load_mean_set_cam_params(self.mlp(feats) * self.scaledown, self.output_wh)   # :100-105
+            param = load_mean_set_cam_params(self.mlp(feats) * self.scaledown, self.output_wh)  # :100-105
+            self._distribution(feats, param)
+            return param
         state = concat_mean_param(feats, self.output_wh)                                         # :70-71
         param = state[:, 2048:]
         for _ in range(3):                                                                       # :77-97
             delta = self.IEF_layer_3(F.relu(self.IEF_layer_2(F.relu(self.IEF_layer_1(state)))))
             param = param + delta * self.scaledown
             state = torch.cat([feats, param], dim=1)
+        self._distribution(feats, param)
         return param
 
 
@@ -262,16 +303,18 @@ class FullModel(nn.Module):
 
 def build_model(train_batch_size, input_shape, smpl_path, output_wh, num_classes,
                 encoder_architecture="resnet50", use_IEF=False, vertex_sampling=None, scaledown=0.005, in_channels=None,
-                pose_repr="axis_angle"):
+                pose_repr="axis_angle", probabilistic=False, init_sigma=0.1):
     """`build_model`, model.py:16-129.  Returns (segs_model, smpl_model, verts_model, projects_model);
     the four share one encoder/regressor and one decoder, as the Keras models share one graph.
     in_channels: the encoder's input channels; default `input_shape[-1]`, the reference's (H, W, C).
-    pose_repr: `SMPLRegressor`'s ("rot6d": the regressor works in the 6D rotation representation)."""
+    pose_repr: `SMPLRegressor`'s ("rot6d": the regressor works in the 6D rotation representation); probabilistic, init_sigma:
+    `SMPLRegressor`'s (a Gaussian per regressed column: prob.py)."""
     if num_classes != 32:
         raise ValueError("the decoder produces 32 classes (31 parts + background)")
     if in_channels is None:
         in_channels = int(input_shape[-1])
-    smpl_model = SMPLRegressor(output_wh, encoder_architecture, use_IEF, scaledown, in_channels, pose_repr)
+    smpl_model = SMPLRegressor(output_wh, encoder_architecture, use_IEF, scaledown, in_channels, pose_repr, probabilistic,
+                               init_sigma)
     decoder = SMPLDecoder(smpl_path, img_wh=output_wh, vertex_sampling=vertex_sampling)
     return (FullModel(smpl_model, decoder, "segs"), smpl_model, FullModel(smpl_model, decoder, "verts"),
             FullModel(smpl_model, decoder, "projects"))

@@ -114,6 +114,16 @@ SCHEMAS = {
                 "bool with_jtr=False, int num_cam=4) -> (Tensor, Tensor, Tensor)"),
     "rot6d_fwd": "smplraster::rot6d_fwd(Tensor y, int num_cam=4) -> (Tensor, Tensor)",
     "rot6d_bwd": "smplraster::rot6d_bwd(Tensor y, Tensor status, Tensor dx, int num_cam=4) -> Tensor",
+    "prob_sample_fwd": ("smplraster::prob_sample_fwd(Tensor mu, Tensor s, Tensor eps, int[]? stochastic=None, bool mean_first=False) -> "
+                        "(Tensor, Tensor)"),
+    "prob_sample_bwd": ("smplraster::prob_sample_bwd(Tensor s, Tensor eps, int[]? stochastic, bool mean_first, Tensor status, "
+                        "Tensor g) -> (Tensor, Tensor)"),
+    "prob_nll_fwd": ("smplraster::prob_nll_fwd(Tensor mu, Tensor s, Tensor target, int[] groups, int G, Tensor? row_w=None) -> "
+                     "(Tensor, Tensor)"),
+    "prob_nll_bwd": ("smplraster::prob_nll_bwd(Tensor mu, Tensor s, Tensor target, int[] groups, int G, Tensor? row_w, Tensor status, "
+                     "Tensor g) -> (Tensor, Tensor)"),
+    "prob_fuse": "smplraster::prob_fuse(Tensor mu, Tensor s, int group_size) -> (Tensor, Tensor, Tensor)",
+    "prob_spread": "smplraster::prob_spread(Tensor points, int S) -> (Tensor, Tensor, Tensor)",
     "surface_fwd": ("smplraster::surface_fwd(Tensor verts, Tensor? cam, Tensor faces, Tensor face, Tensor bary, Tensor target, "
                     "Tensor conf, Tensor order, float sigma) -> (Tensor, Tensor, Tensor, Tensor, Tensor)"),
     "surface_bwd": ("smplraster::surface_bwd(Tensor? cam, Tensor vc_off, Tensor vc_fc, Tensor c_off, Tensor face, Tensor bary, "

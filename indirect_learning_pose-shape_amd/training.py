@@ -69,7 +69,7 @@ class SegTrainer:
     def __init__(self, smpl_path=None, input_wh=256, output_wh=48, encoder_architecture="enet", use_IEF=True,
                  weight_classes=True, gamma=2.0, lr=1e-4, device=None, ddp=False, bucket_mb=25,
                  with_silhouette=False, silh_wh=None, fused_loss=True, fused_silh_loss=False, amp=None, in_channels=3,
-                 pose_repr="axis_angle"):
+                 pose_repr="axis_angle", probabilistic=False, init_sigma=0.1):
         amp_dtype(amp)                                                # (ValueError before anything is built)
         if amp is not None and os.environ.get("SMPLR_ENCODER_LAYOUT", "").lower() == "channels_last":
             # that layout runs torch's own BatchNorm2d (the package's kernels read NCHW planes), and torch 2.10 / ROCm 7.0's
@@ -85,7 +85,8 @@ class SegTrainer:
         self.output_wh = output_wh
         self.in_channels = int(in_channels)                           # (3: images; synthetic.SyntheticBatches.in_channels)
         self.smpl_model = SMPLRegressor(output_wh, encoder_architecture, use_IEF, in_channels=self.in_channels,
-                                        pose_repr=pose_repr).to(self.device)      # ("rot6d": rot6d.py; still (N, 86) out)
+                                        pose_repr=pose_repr, probabilistic=probabilistic,
+                                        init_sigma=init_sigma).to(self.device)    # ("rot6d": rot6d.py; still (N, 86) out)
         # OPT-IN (`SMPLR_ENCODER_LAYOUT=channels_last`): the encoder's weights and activations in NHWC, the layout
         # MIOpen's implicit-GEMM convolution solvers work in (the default NCHW tensors are transposed around them:
         # `batched_transpose_32x32_dword` in the train step's kernel trace).  The package's fused batch-norm / PReLU
@@ -328,6 +329,91 @@ class SupervisedTrainer(SegTrainer):
             self.weights.s.zero_()
         self.opt.state.pop(self.weights.s, None)
         return int(ck.get("trial", -1)) + 1
+
+
+class ProbabilisticTrainer(SupervisedTrainer):
+    """`SupervisedTrainer` on a regressor that predicts a Gaussian per regressed column (`SMPLRegressor(probabilistic=True)`,
+    prob.py) - how "Probabilistic 3D Human Shape and Pose Estimation from Multiple Unconstrained Images in the Wild" trains.
+
+    A step's loss is `SupervisedTrainer`'s on the mean row, plus
+      nll_weight     times the mean over rows and the two groups (pose, shape; the camera does not count) of `gaussian_nll`
+                     against the truth's parameters - with pose_repr="rot6d" against `axis_angle_to_rot6d` of its pose;
+      sample_weight  times the mean over the B S sampled bodies (`samples` = S per row, drawn through the reparameterisation
+                     trick from `generator`, decoded as B S more rows) of `supervised_terms`' vertex and joint terms against
+                     the repeated truth.
+    generator: a torch.Generator on the trainer's device (default: a fresh one seeded with 0); its state goes into the
+    checkpoints, the new layer's weights and Adam state with the regressor's."""
+
+    def __init__(self, *args, samples=4, nll_weight=1.0, sample_weight=1.0, generator=None, init_sigma=0.1, **kw):
+        if kw.pop("probabilistic", True) is not True:
+            raise ValueError("ProbabilisticTrainer trains a probabilistic regressor")
+        super().__init__(*args, probabilistic=True, init_sigma=init_sigma, **kw)
+        self.samples, self.nll_weight, self.sample_weight = int(samples), float(nll_weight), float(sample_weight)
+        if self.samples < 1:
+            raise ValueError("samples must be positive")
+        if generator is None:
+            generator = torch.Generator(device=self.device)
+            generator.manual_seed(0)
+        self.generator = generator
+        nc = self.decoder.num_cam
+        npose = self.smpl_model.nout - nc - 10
+        self.groups = (-1,) * nc + (0,) * npose + (1,) * 10
+        self.last_nll = self.last_sample_terms = None
+
+    def _target(self, x_t):
+        """The truth's (N, 86) in the space the regressor works in."""
+        if self.smpl_model.pose_repr != "rot6d":
+            return x_t
+        from .rot6d import axis_angle_to_rot6d
+        nc, n = self.decoder.num_cam, int(x_t.shape[0])
+        a = axis_angle_to_rot6d(x_t[:, nc:nc + 72].reshape(n, 24, 3)).reshape(n, 144)
+        return torch.cat([x_t[:, :nc], a, x_t[:, nc + 72:]], 1)
+
+    def step(self, images, labels=None, silh_labels=None, truth=None, metrics=None, _marks=None):
+        """`SupervisedTrainer.step`'s arguments and result; afterwards `last_nll` (2,) holds the batch means of the pose and
+        shape likelihoods and `last_sample_terms` (2,) those of the samples' vertex and joint terms, detached."""
+        from .prob import gaussian_nll
+        from .supervised import supervised_terms
+        if truth is None:
+            raise ValueError("ProbabilisticTrainer.step needs truth= (SyntheticBatches(..., truth=True) yields it)")
+        mark = (lambda k: None) if _marks is None else _marks
+        param = self._regress(images, mark, _marks is not None)
+        net, layer, nc = self.smpl_model, self.smpl_layer, self.decoder.num_cam
+        layer._consts, layer._consts_device = self.decoder.constants(param.device), param.device
+        verts = layer(param)
+        terms = supervised_terms(param, verts, layer.J_transformed, truth, self.spec, self.root, None, self.cam_scale, nc)
+        loss = self.weights(terms).mean()
+        if self.indirect_weight > 0 and labels is not None:
+            loss = loss + self.indirect_weight * self.param_loss(param, labels, silh_labels, metrics)
+        self.last_terms = terms.detach().mean(0)
+        nll = gaussian_nll(net.mean, net.log_var, self._target(truth["x"].detach().float()), self.groups)
+        loss = loss + self.nll_weight * nll.mean()
+        self.last_nll = nll.detach().mean(0)
+        if self.sample_weight > 0:
+            B, S = int(param.shape[0]), self.samples
+            eps = torch.randn((B, S, net.nout), generator=self.generator, device=param.device)
+            xs = net.sample(eps, mean_first=False)
+            verts_s = layer(xs)
+            truth_s = {k: v.repeat_interleave(S, 0) for k, v in truth.items() if k in ("x", "verts", "J_transformed")}
+            row_w = torch.tensor([1.0, 1.0, 0.0, 0.0, 0.0], device=param.device).repeat(B * S, 1)
+            terms_s = supervised_terms(xs, verts_s, layer.J_transformed, truth_s, self.spec, self.root, row_w, self.cam_scale, nc)
+            loss = loss + self.sample_weight * terms_s[:, :2].sum(1).mean()
+            self.last_sample_terms = terms_s.detach()[:, :2].mean(0)
+        return self._update(loss, mark)
+
+    def save(self, path, trial=0):
+        """`SupervisedTrainer.save` plus the generator's state under "generator"."""
+        torch.save({"smpl_model": self.smpl_model.state_dict(), "optimizer": self.opt.state_dict(), "trial": int(trial),
+                    "output_wh": int(self.output_wh), "uncertainty": self.weights.state_dict(),
+                    "generator": self.generator.get_state()}, path)
+
+    def resume(self, path):
+        """-> the trial to continue from; a checkpoint that carries a generator state restores it."""
+        trial = super().resume(path)
+        ck = torch.load(path, map_location="cpu")
+        if isinstance(ck, dict) and ck.get("generator") is not None:
+            self.generator.set_state(ck["generator"].cpu())
+        return trial
 
 
 def save_name(dataset, output_wh, use_IEF=True, scaledown=0.005, vertex_sampling=None, weight_classes=True, trial=0,
