@@ -504,6 +504,46 @@ int smplr_proxy_inputs(const uint8_t *part, const float *joints, const uint8_t *
                        const int32_t *boxes, int B, int H, int W, int J, int NB, int P, int seg_mode, float rescale,
                        float inv2s2, float cut2, float *out, void *stream);
 
+/* ---- Canny edge maps: the edge proxy of the synthetic-training papers, on rendered bodies and on photographs; DESIGN.md 31,
+ * INTEGRATION.md 4y -----------------------------------------------------------------------------------------------------
+ * Two launches: edge_classify (source -> class map (B, H, W) uint8: 0 none, 1 weak, 2 strong) and edge_link (class map ->
+ * edges (B, H, W) uint8).  Exact integer arithmetic; the formulation follows cv2.Canny's (aperture 3, fixed-point direction
+ * test, asymmetric ties), the text below is the contract.  Per image, independently of every other image of the batch:
+ * Grey.  g (H, W) in 0..255 from one of four source forms:
+ *   SMPLR_EDGE_GREY_U8      (B, H, W) uint8
+ *   SMPLR_EDGE_RGB_U8       (B, H, W, 3) uint8
+ *   SMPLR_EDGE_RGB_F32_HWC  (B, H, W, 3) fp32 (the mesh renderer's rgb)
+ *   SMPLR_EDGE_RGB_F32_CHW  (B, 3, H, W) fp32 (the resize call's images)
+ *   A float channel c is first quantised: q = clamp(floorf(c * scale + 0.5f), 0, 255), one fp32 multiply then one fp32 add
+ *   (no FMA); NaN gives 0, +inf 255, -inf 0.  Colour to grey: g = (4899 R + 9617 G + 1868 B + 8192) >> 14; bgr != 0: the
+ *   first channel is B and the third R.
+ * Blur (blur = 1; 0: g' = g).  5 x 5 binomial, w = [1 4 6 4 1], indices clamped to the image (replicate border):
+ *   g' = (sum_ij w_i w_j g + 128) >> 8.
+ * Gradient.  3 x 3 Sobel on g', replicate border: gx = (right column weighted 1 2 1) - (left column), gy = (row below) -
+ *   (row above).  l2 = 0: m = |gx| + |gy|, and m counts against a threshold t iff m > t; l2 = 1: m = gx^2 + gy^2, iff m > t^2.
+ *   Everything fits int32.
+ * Thresholds.  Integers 0 <= low <= high <= 2047: the scalars low, high, or with thr (B, 2) int32 row b's (low, high).  A
+ *   row of thr outside that range gives an all-zero class map for that image and status[b] = 1 (status (B) int32, optional;
+ *   0 otherwise); other rows are unaffected.
+ * Non-maximum suppression.  m outside the image is 0 (not replicated).  ax = |gx|, ay = |gy|, T = 13573 ax.
+ *   If (ay << 15) < T: keep iff m > m[y][x-1] and m >= m[y][x+1].
+ *   Else if (ay << 15) > T + (ax << 16): keep iff m > m[y-1][x] and m >= m[y+1][x].
+ *   Else s = ((gx ^ gy) < 0) ? -1 : 1: keep iff m > m[y-1][x-s] and m > m[y+1][x+s].
+ * Class.  2 (strong): kept and over high; 1 (weak): kept and over low; 0: everything else.
+ * Link (hysteresis).  A pixel is an edge iff its class is >= 1 and an 8-connected path of pixels of class >= 1 joins it to
+ *   a pixel of class >= 2 (in a class map handed in from outside any value >= 2 is strong).  edges = value (1..255) on edges,
+ *   0 elsewhere.  The result is the exact transitive closure: the kernel iterates until nothing changes, without a cap.
+ * Limits (SMPLR_EINVAL otherwise, nothing launched): 1 <= H, W <= 512; B >= 0 (B = 0 is a no-op); B * tiles < 2^31; form one
+ * of the four; scale finite; blur, l2, bgr 0 or 1; without thr the scalars in range; 1 <= value <= 255; non-null src / classes /
+ * edges.  No host synchronisation, no global atomics, no workspace beyond the class map. */
+#define SMPLR_EDGE_GREY_U8 0
+#define SMPLR_EDGE_RGB_U8 1
+#define SMPLR_EDGE_RGB_F32_HWC 2
+#define SMPLR_EDGE_RGB_F32_CHW 3
+int smplr_edge_classify(const void *src, int form, int B, int H, int W, float scale, int bgr, int blur, int l2, int low,
+                        int high, const int32_t *thr, uint8_t *classes, int32_t *status, void *stream);
+int smplr_edge_link(const uint8_t *classes, int B, int H, int W, int value, uint8_t *edges, void *stream);
+
 /* ---- 3D evaluation: per-vertex error, MPJPE, scale-corrected and Procrustes-aligned error (the figures evaluate3d.py:32-65
  * stops short of: it reports a mean squared error over 69 pose parameters); INTEGRATION.md 4f -------------------------
  * pred, gt (B, N, 3) fp32, contiguous: two point sets per mesh (vertices, or joints), in metres.  One launch computes each

@@ -86,6 +86,8 @@ SIGNATURES = {
     "smplr_affine_warp": (c_int, [P, I, I, I, I, P, P, I, I, I, I, I, c_float, P, P]),
     "smplr_resize_pad": (c_int, [P, c_longlong, P, I, I, P, I, I, I, I, I, I, c_float, P, P]),
     "smplr_proxy_inputs": (c_int, [P, P, P, P, P, I, I, I, I, I, I, I, c_float, c_float, c_float, P, P]),
+    "smplr_edge_classify": (c_int, [P, I, I, I, I, c_float, I, I, I, I, I, P, P, P, P]),
+    "smplr_edge_link": (c_int, [P, I, I, I, I, P, P]),
     "smplr_point_errors": (c_int, [P, P, I, I, I, I, P, P, P, P, P]),
     "smplr_mesh_measures": (c_int, [P, P, P, P, c_longlong, P, I, I, I, I, P, P, P, P, P, P, P, P]),
     "smplr_mesh_measures_bwd": (c_int, [P, P, P, P, I, P, P, c_longlong, P, P, P, P, P, P, P, I, I, I, I, P, P]),

@@ -704,6 +704,66 @@ void proxy_inputs_meta(const Tensor &part, const c10::optional<Tensor> &joints, 
   proxy_inputs_check(part, joints, keep, remove, boxes, out, P, seg_mode);
 }
 
+// ---- Canny edge maps (edges.py): source images -> class map (B, H, W) uint8 (0 none, 1 weak, 2 strong) + status (B) int32;
+// class map -> edges (B, H, W) uint8.  form 0: (B, H, W) uint8 grey, 1: (B, H, W, 3) uint8, 2: (B, H, W, 3) fp32, 3: (B, 3, H, W)
+// fp32.  thr (B, 2) int32 rows (low, high) replace the scalars; its VALUES are checked by the kernel (status), not read here.
+struct EdgeDims { int64_t B, H, W; };
+EdgeDims edge_classify_check(const Tensor &src, int64_t form, const c10::optional<Tensor> &thr, int64_t low, int64_t high) {
+  TORCH_CHECK(form >= 0 && form <= 3, "form must be 0 (grey u8), 1 (rgb u8), 2 (rgb f32 HWC) or 3 (rgb f32 CHW)");
+  TORCH_CHECK(src.scalar_type() == (form <= 1 ? at::kByte : at::kFloat), "src of form ", form, " must be ", form <= 1 ? "uint8" : "float32");
+  TORCH_CHECK(src.dim() == (form == 0 ? 3 : 4) && (form == 0 || src.size(form == 3 ? 1 : 3) == 3),
+              "src must be (B, H, W), (B, H, W, 3), (B, H, W, 3) or (B, 3, H, W) for forms 0..3");
+  const int64_t B = src.size(0), H = src.size(form == 3 ? 2 : 1), W = src.size(form == 3 ? 3 : 2);
+  TORCH_CHECK(B <= INT32_MAX && H >= 1 && H <= 512 && W >= 1 && W <= 512, "H and W of src must be in 1..512");
+  TORCH_CHECK(!thr || (thr->dim() == 2 && thr->size(0) == B && thr->size(1) == 2 && thr->scalar_type() == at::kInt),
+              "thr must be (B, 2) int32");
+  TORCH_CHECK(thr || (low >= 0 && low <= high && high <= 2047), "thresholds must satisfy 0 <= low <= high <= 2047");
+  return {B, H, W};
+}
+std::tuple<Tensor, Tensor> edge_classify(const Tensor &src, int64_t form, const c10::optional<Tensor> &thr, int64_t low,
+                                         int64_t high, bool blur, bool l2, double scale, bool bgr) {
+  const EdgeDims d = edge_classify_check(src, form, thr, low, high);
+  dev_typed(src, src.scalar_type(), "src");
+  if (thr) dev_typed(*thr, at::kInt, "thr");
+  const Tensor none;
+  same_device(src, {{"thr", thr ? &*thr : &none}});
+  DeviceGuard g(src.device());
+  Tensor classes = at::empty({d.B, d.H, d.W}, src.options().dtype(at::kByte));
+  Tensor status = at::empty({d.B}, src.options().dtype(at::kInt));
+  if (d.B == 0) return {classes, status};
+  ok(smplr_edge_classify(src.data_ptr(), (int)form, (int)d.B, (int)d.H, (int)d.W, (float)scale, bgr ? 1 : 0, blur ? 1 : 0,
+                         l2 ? 1 : 0, thr ? 0 : (int)low, thr ? 0 : (int)high, thr ? thr->data_ptr<int32_t>() : nullptr,
+                         classes.data_ptr<uint8_t>(), status.data_ptr<int32_t>(), cur_stream()),
+     "smplr_edge_classify");
+  return {classes, status};
+}
+std::tuple<Tensor, Tensor> edge_classify_meta(const Tensor &src, int64_t form, const c10::optional<Tensor> &thr, int64_t low,
+                                              int64_t high, bool, bool, double, bool) {
+  const EdgeDims d = edge_classify_check(src, form, thr, low, high);
+  return {at::empty({d.B, d.H, d.W}, src.options().dtype(at::kByte)), at::empty({d.B}, src.options().dtype(at::kInt))};
+}
+void edge_link_check(const Tensor &classes, int64_t value) {
+  TORCH_CHECK(classes.dim() == 3 && classes.scalar_type() == at::kByte, "classes must be (B, H, W) uint8");
+  TORCH_CHECK(classes.size(0) <= INT32_MAX && classes.size(1) >= 1 && classes.size(1) <= 512 && classes.size(2) >= 1 &&
+                  classes.size(2) <= 512, "H and W of classes must be in 1..512");
+  TORCH_CHECK(value >= 1 && value <= 255, "value must be in 1..255");
+}
+Tensor edge_link(const Tensor &classes, int64_t value) {
+  edge_link_check(classes, value);
+  dev_typed(classes, at::kByte, "classes");
+  DeviceGuard g(classes.device());
+  Tensor edges = at::empty_like(classes);
+  if (classes.size(0) == 0) return edges;
+  ok(smplr_edge_link(classes.data_ptr<uint8_t>(), (int)classes.size(0), (int)classes.size(1), (int)classes.size(2), (int)value,
+                     edges.data_ptr<uint8_t>(), cur_stream()),
+     "smplr_edge_link");
+  return edges;
+}
+Tensor edge_link_meta(const Tensor &classes, int64_t value) {
+  edge_link_check(classes, value);
+  return at::empty(classes.sizes(), classes.options());
+}
+
 // ---- input preprocessing (predict.py:17-25, evaluate.py:13-19,96-100): data (bytes) uint8 + desc (N, 4) int64 -> out, in place --
 // mode 0 / 1: images, bilinear / nearest, out (B, C, H, W) fp32; mode 2 / 3: labels / labels > 0, out (B, H, W) int32.
 // flags: 1 pad, 2 swap_rb, 4 quantize, 8 pil rule.  desc rows (byte offset, pitch, h, w) and the VALUES of index are
@@ -1977,6 +2037,9 @@ TORCH_LIBRARY(smplraster, m) {
         "float rescale=1.0) -> ()");
   m.def("proxy_inputs(Tensor part, Tensor? joints, Tensor? keep, Tensor? remove, Tensor? boxes, Tensor(a!) out, "
         "int num_parts, int seg_mode, float rescale, float inv2s2, float cut2) -> ()");
+  m.def("edge_classify(Tensor src, int form, Tensor? thr=None, int low=0, int high=0, bool blur=True, bool l2=True, "
+        "float scale=255.0, bool bgr=False) -> (Tensor, Tensor)");
+  m.def("edge_link(Tensor classes, int value=1) -> Tensor");
   m.def("point_errors(Tensor pred, Tensor gt, int root=-1, int per_point_mode=-1, bool transform=False) -> "
         "(Tensor, Tensor, Tensor, Tensor)");
   m.def("seg_colour(Tensor input, Tensor lut, Tensor? background, int H, int W, int alpha_q=256, int bad_colour=0) -> Tensor");
@@ -2057,6 +2120,8 @@ TORCH_LIBRARY_IMPL(smplraster, CUDA, m) {       // (the HIP backend's dispatch k
   m.impl("affine_warp", &affine_warp);
   m.impl("resize_pad", &resize_pad);
   m.impl("proxy_inputs", &proxy_inputs);
+  m.impl("edge_classify", &edge_classify);
+  m.impl("edge_link", &edge_link);
   m.impl("point_errors", &point_errors);
   m.impl("seg_colour", &seg_colour);
   m.impl("scatter_points", &scatter_points);
@@ -2103,6 +2168,8 @@ TORCH_LIBRARY_IMPL(smplraster, Meta, m) {
   m.impl("affine_warp", &affine_warp_meta);
   m.impl("resize_pad", &resize_pad_meta);
   m.impl("proxy_inputs", &proxy_inputs_meta);
+  m.impl("edge_classify", &edge_classify_meta);
+  m.impl("edge_link", &edge_link_meta);
   m.impl("point_errors", &point_errors_meta);
   m.impl("seg_colour", &seg_colour_meta);
   m.impl("scatter_points", &scatter_points_meta);

@@ -11,6 +11,8 @@ One `next(batches)`: `BodySampler` draws pose, shape, heading and camera and dec
 `keypoints.KeypointSpec`; `corruption_draws` draws part removal, an occluding box, a crop, joint noise, drops and left /
 right swaps; `proxy_inputs` (csrc/proxy.hip, one launch) turns part map and joints into the encoder's (B, C, H, W) input.
 Everything is drawn with torch from one generator on the device: no host traffic, no host synchronisation per batch.
+`SyntheticBatches(seg="edges")` feeds the proxy of the later papers instead: the Canny edge map (`edges.py`) of the same
+render's rgb in the place of the part map, then the same heat channels.
 
 The definition of `proxy_inputs` (include/smplraster.h has the same text; tests/_synthetic_oracle.py is its NumPy form).
 Per sample b and pixel (x, y), l = part[b, y, x]:
@@ -37,6 +39,10 @@ from ._lib import check, ptr, stream
 
 SEG_MODES = {"index": 0, "onehot": 1, "silhouette": 2, "none": 3}      # SMPLR_PROXY_SEG_* of include/smplraster.h
 MAX_JOINTS, MAX_BOXES, MAX_PARTS, MAX_SIDE = 64, 4, 31, 4096
+# `SyntheticBatches(seg="edges")`: the Canny keywords when none are given (the textbook 1 : 2 pair on the blurred L2 gradient: a
+# choice, not a measurement of anything), and the keywords of `edge` that go to `render_mesh` instead
+EDGE_DEFAULTS = {"low": 100, "high": 200}
+EDGE_RENDER_KEYS = ("shading", "albedo", "lights", "background")
 
 
 def seg_channels(seg, num_parts=31):
@@ -378,8 +384,12 @@ class SyntheticBatches:
 
     smpl_path_or_layer: an `SMPLLayer`, or what it is built from (a path, an `SMPLModelData`).  sampler: a `BodySampler`
     (default: `BodySampler(layer)`).  spec: a `keypoints.KeypointSpec` for the heatmaps, None for none.  seg, sigma:
-    `proxy_inputs`' (sigma in input pixels).  corruption: the dict of `corruption_draws`' keywords ({}: its defaults), None
-    for clean inputs.  topology: a `render.MeshTopology`; default: the model's faces with its part tables (a model without
+    `proxy_inputs`' (sigma in input pixels), or seg="edges": one channel, the Canny edge map (`edges.canny_edges`) of the
+    input-size render's rgb - the same render that gives the part map - with the batch's boxes applied, then the heat channels
+    (`proxy_inputs(edges, ..., seg="silhouette", num_parts=1)`); edge: the dict of `canny_edges`' keywords (default
+    `EDGE_DEFAULTS`) plus shading / albedo / lights / background for `render_mesh` (default: Lambert on white); part removal
+    has no meaning on an edge map, so a non-empty remove_parts with seg="edges" is a ValueError.  corruption: the dict of
+    `corruption_draws`' keywords ({}: its defaults), None for clean inputs.  topology: a `render.MeshTopology`; default: the model's faces with its part tables (a model without
     faces, as the synthetic one, needs it: `hull_topology`).  generator: a `torch.Generator` on the device (default: a new
     one on `device` seeded with `seed`).
 
@@ -389,7 +399,8 @@ class SyntheticBatches:
     `last` keeps the batch's x, verts, J_transformed, joints (clean), keep and draws.  No host synchronisation per batch."""
 
     def __init__(self, smpl_path_or_layer, batch_size, input_wh, output_wh, *, sampler=None, spec=None, seg="index", sigma=4.0,
-                 corruption=None, silh_wh=None, seed=1, generator=None, topology=None, device=None, num_parts=31, truth=False):
+                 corruption=None, silh_wh=None, seed=1, generator=None, topology=None, device=None, num_parts=31, truth=False,
+                 edge=None):
         from .keras_smpl.batch_smpl import SMPLLayer
         from .render import MeshTopology
         # (an SMPLLayer by what it offers, not by isinstance: the package is importable under two names)
@@ -408,7 +419,18 @@ class SyntheticBatches:
         self.sampler = sampler if sampler is not None else BodySampler(layer)
         self.spec, self.seg, self.sigma, self.num_parts = spec, seg, float(sigma), int(num_parts)
         self.corruption = None if corruption is None else dict(corruption)
-        self.in_channels = seg_channels(seg, num_parts) + (0 if spec is None else spec.K)
+        self.edge = self.edge_render = None
+        if seg == "edges":
+            if self.corruption is not None and len(tuple(self.corruption.get("remove_parts", ()))) > 0:
+                raise ValueError("remove_parts has no meaning with seg='edges': an edge map has no parts to remove")
+            edge = dict(EDGE_DEFAULTS if edge is None else edge)
+            self.edge_render = {k: edge.pop(k) for k in EDGE_RENDER_KEYS if k in edge}
+            if "value" in edge or "return_status" in edge or "out" in edge:
+                raise ValueError("edge takes canny_edges' keywords except value, return_status and out")
+            self.edge = edge
+        elif edge is not None:
+            raise ValueError("edge= belongs to seg='edges'")
+        self.in_channels = (1 if seg == "edges" else seg_channels(seg, num_parts)) + (0 if spec is None else spec.K)
         if self.in_channels == 0:
             raise ValueError("seg='none' needs a spec")
         if generator is None:
@@ -436,15 +458,18 @@ class SyntheticBatches:
         py = (self.input_wh - 1) - sc * (cam[:, 3, None] + cam[:, 1, None] * Jn[..., 1])
         return torch.stack([px, py], -1).to(torch.float32).contiguous()
 
-    def _render(self, s, wh):
+    def _render(self, s, wh, key="part", **kw):
         from .render import render_mesh
         return render_mesh(s["verts"], self.topo, s["x"][:, :4], mode="ortho", img_wh=wh,
-                           scale=float(wh) / float(self.output_wh))["part"]
+                           scale=float(wh) / float(self.output_wh), **kw)[key]
 
     def _batch(self, corrupt):
         B = self.batch_size
         s = self.sampler.sample(B, self.output_wh, self.generator)
-        part_in = self._render(s, self.input_wh)
+        if self.seg == "edges":                                           # the one input-size render: its rgb, not its part
+            rgb = self._render(s, self.input_wh, "rgb", **self.edge_render)
+        else:
+            part_in = self._render(s, self.input_wh)
         labels = self._render(s, self.output_wh).to(torch.int32)
         silh = None if self.silh_wh is None else (self._render(s, self.silh_wh) > 0).to(torch.int32)
         joints = keep = None
@@ -464,7 +489,12 @@ class SyntheticBatches:
                 used = corrupt_joints(joints, draws, self.corruption.get("swap_pairs", ()))
                 keep = draws["keep"]
             last.update(keep=keep, draws=draws)
-        images = proxy_inputs(part_in, used, keep, remove, boxes, num_parts=self.num_parts, seg=self.seg, sigma=self.sigma)
+        if self.seg == "edges":
+            from .edges import canny_edges
+            images = proxy_inputs(canny_edges(rgb, **self.edge), used, keep, None, boxes, num_parts=1, seg="silhouette",
+                                  sigma=self.sigma)
+        else:
+            images = proxy_inputs(part_in, used, keep, remove, boxes, num_parts=self.num_parts, seg=self.seg, sigma=self.sigma)
         self.last = last
         return images, labels, silh
 

@@ -54,6 +54,9 @@ SCHEMAS = {
                    "int mode=0, int flags=4, float rescale=1.) -> ()"),
     "proxy_inputs": ("smplraster::proxy_inputs(Tensor part, Tensor? joints, Tensor? keep, Tensor? remove, Tensor? boxes, "
                      "Tensor(a!) out, int num_parts, int seg_mode, float rescale, float inv2s2, float cut2) -> ()"),
+    "edge_classify": ("smplraster::edge_classify(Tensor src, int form, Tensor? thr=None, int low=0, int high=0, bool blur=True, "
+                      "bool l2=True, float scale=255., bool bgr=False) -> (Tensor, Tensor)"),
+    "edge_link": "smplraster::edge_link(Tensor classes, int value=1) -> Tensor",
     "point_errors": ("smplraster::point_errors(Tensor pred, Tensor gt, int root=-1, int per_point_mode=-1, "
                      "bool transform=False) -> (Tensor, Tensor, Tensor, Tensor)"),
     "seg_colour": ("smplraster::seg_colour(Tensor input, Tensor lut, Tensor? background, int H, int W, int alpha_q=256, "
